@@ -14,12 +14,15 @@ data, fixed parameters — the data set of tests/golden/syn_codon_m0_full.json, 
 program) every run is checked against.  Default `--scaling strong`: the SAME 10^6 patterns cut into N shards
 (paml_amd_shard_bounds); the reduced lnL is identical, bit for bit, for every N (`lnL_hex`).  `--scaling weak` (and the
 `weak` block of the default line at N > 1): 10^6 patterns per GPU.
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
-Rank 0 prints ONE JSON line; beside the headline it carries `roofline`, `cpu_baseline` (N = 1), the NSsites `sweep`
-(K = 1, 2, 3, 10, 11 classes with the M0 / M1a / M2a / M7 / M8 tables of the goldens) and, at N = 1, every other BASELINE configuration:
-`c1` (configs[0], brown HKY85), `c2` + `c2_batch` (configs[1], 4 states), `c3` (configs[2], stewart LG+G4) with `aa20` (its model class
-at scale), `c5` (configs[4], HIV NSsites 0 1 2 7 8: latency per evaluation and time to the MLEs).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, the lnL and its check against the reference's).  `--dump-outputs DIR` writes what the last
+timed step computed (the total lnL, float64) as DIR/lnL.npy.  `--full` adds everything else: `roofline` (a profiled run of its own),
+`cpu_baseline` (N = 1), the NSsites `sweep` (K = 1, 2, 3, 10, 11 classes with the M0 / M1a / M2a / M7 / M8 tables of the goldens), the
+exchange statistics and weak line at N > 1 and, at N = 1, every other BASELINE configuration: `c1` (configs[0], brown HKY85), `c2` +
+`c2_batch` (configs[1], 4 states), `c3` (configs[2], stewart LG+G4) with `aa20` (its model class at scale), `c5` (configs[4], HIV NSsites
+0 1 2 7 8: latency per evaluation and time to the MLEs).  Inside `--full`, `--no-extras` and `--no-cpu-baseline` leave those blocks out.
 """
 from __future__ import annotations
 
@@ -65,6 +68,13 @@ def golden_lnl(name):
         return None
     with open(path) as f:
         return json.load(f)["lnL"]
+
+
+def dump_outputs(directory, **arrays):
+    """--dump-outputs: each array as <directory>/<name>.npy, float64 (the engine's arithmetic)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def check_lnl(what, lnl, name, n_patt, seed_default):
@@ -134,8 +144,12 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="headline only: no sweep / c2 / weak / read-back blocks")
     ap.add_argument("--cpu-sample", type=int, default=100_000)
     ap.add_argument("--sweep-steps", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="beside the headline: roofline, CPU baseline, NSsites sweep, the other configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--clock-probe", action="store_true", help="(internal) the headline kernel with timeline stamps: shader clock under load")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.clock_probe:
         return clock_probe(args)
     # `python bench.py --gpus N` with no launcher around it (no RANK / WORLD_SIZE in the environment): the bench starts its own N
@@ -241,14 +255,12 @@ def main():
         pb, eng, (lo, hi) = weak_engine(args, world, rank, engine, distributed, synth, force_comm)
     branch = pb.tree.branch.copy()
     dt, lnl, _ = timed(eng, branch, args.steps, args.warmup)                       # the timed region: W warm-up + exactly K steps, no event pairs
-    _, _, prof = timed(eng, branch, max(5, args.steps // 2), 0, profile=True)      # the kernels' own durations (HIP events), outside it
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, lnL=np.array([lnl], dtype=np.float64))      # the last timed step's total
     ref_lnl = check_lnl("M0", lnl, "syn_codon_m0_full", n_full, seed_default and args.scaling == "strong" and args.taxa == 16)
 
     out = None
     if rank == 0:
-        flops_pp = algorithmic_flops_per_pattern(pb.n, args.taxa) * pb.K
-        ms_kernel = prof["ms_prune"] / max(1, prof["n_evals"])
-        achieved = flops_pp * pb.n_patt / (ms_kernel * 1e-3) / 1e12
         out = {
             "metric": "site-patterns/sec per lnL eval (codeml M0, 61 states)",
             "value": n_full * args.steps / dt, "unit": "site-patterns/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -259,6 +271,14 @@ def main():
                        "classes": pb.K, "kernel": eng.kernel_name, "parallelism": "pattern-shard x%d, RCCL all-reduce inside the engine" % world,
                        "patterns_rank0": pb.n_patt},
             "lnL": lnl, "lnL_hex": float(lnl).hex(), "lnL_reference": ref_lnl,
+        }
+    if args.full:
+        _, _, prof = timed(eng, branch, max(5, args.steps // 2), 0, profile=True)      # the kernels' own durations (HIP events), outside the timed region
+    if rank == 0 and args.full:
+        flops_pp = algorithmic_flops_per_pattern(pb.n, args.taxa) * pb.K
+        ms_kernel = prof["ms_prune"] / max(1, prof["n_evals"])
+        achieved = flops_pp * pb.n_patt / (ms_kernel * 1e-3) / 1e12
+        out.update({
             "roofline": {"bound": "mfma", "kernel": "prune_jit", "achieved": achieved, "peak": FP64_PEAK_TFLOPS,
                          "unit": "TFLOP/s", "frac": achieved / FP64_PEAK_TFLOPS, "traffic": None,
                          "flop_per_pattern": flops_pp, "kernel_ms": ms_kernel,
@@ -272,7 +292,7 @@ def main():
                          #  event pair around it then spans its wait for free CUs, which is not kernel time)
                          "pmat_ms": (prof["ms_pmat"] / max(1, prof["n_evals"])) if prof["ms_pmat"] < 0.5 * prof["ms_prune"] else None,
                          "reduce_ms": prof["ms_reduce"] / max(1, prof["n_evals"])},
-        }
+        })
         out["roofline"].update(profiles_evidence(flops_pp * pb.n_patt if (world == 1 and args.patterns == 1_000_000 and args.taxa == 16) else None))
 
     # N > 1: whatever happens in the blocks behind the headline, the headline gets out (HeadlineGuard)
@@ -287,7 +307,7 @@ def main():
                 out["config"]["collective_library"] = engine.comm_library()
             except Exception as ex:      # noqa: BLE001
                 out["config"]["collective_library"] = repr(ex)
-        if world > 1 or force_comm:
+        if args.full and (world > 1 or force_comm):
             try:      # (diagnostics: whatever goes wrong here, the headline above stands)
                 eng.comm_stats(True)
                 dst = torch.zeros(64, dtype=torch.float64, device="cuda")
@@ -308,7 +328,7 @@ def main():
                                    "lane_wait_us": max(b["lane_wait_us"] for b in box), "lane_wait_us_max": max(b["lane_wait_us_max"] for b in box),
                                    "per_rank": box, "pruning_streams": 2 if os.environ.get("PAML_AMD_DUAL", "1") != "0" else 1,
                                    "note": "means over the evaluations, maximum over the ranks; lane_wait_us includes ~12 us of its own event pair"}
-        extras = not args.no_extras
+        extras = args.full and not args.no_extras
         if extras:
             # the same loop with the scalar read back to the host after every evaluation (what a serial optimiser waits for)
             for _ in range(2):
@@ -430,7 +450,7 @@ def main():
                 out[key] = fn(engine, timed, fence)
             except Exception as ex:      # (the C host library or a data file missing: reported, the headline stands)
                 out[key] = {"error": repr(ex)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         pbc = pb if pb.K == 1 else None
         out["cpu_baseline"] = cpu_baseline(pbc, args.cpu_sample)
         out["speedup_vs_cpu_1core"] = out["value"] / out["cpu_baseline"]["value"]

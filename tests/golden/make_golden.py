@@ -777,6 +777,20 @@ CASES = {
     "syn_codon_m7_4000": lambda: case_syn_codon_ns("m7", 4000, None),
 }
 
+
+
+def case_differential():
+    """tests/golden/differential.json: the reference binaries' lnL for every differential case of tests/test_host_c.py (control file,
+    program, parameter vector), so that those tests run where oracle/_ref is absent."""
+    for d in (os.path.join(REPO, "tests"), os.path.join(REPO, "oracle")):
+        if d not in sys.path:
+            sys.path.insert(0, d)
+    import test_host_c
+    test_host_c.record_differential(os.path.join(HERE, "differential.json"))
+
+
+CASES["differential"] = case_differential
+
 if __name__ == "__main__":
     which = sys.argv[1:] or list(CASES)
     for c in which:

@@ -2,6 +2,8 @@
 PHYLIP sequences, Newick tree, dat/lg.dat — and must reproduce the reference's single-evaluation lnL and per-pattern
 lnf (same pattern order as the reference's `lnf` file).  CPU: C host + oracle.  GPU: C host + engine, and the
 pamlh_lnl driver end to end."""
+import contextlib
+import json
 import os
 import re
 import subprocess
@@ -1096,15 +1098,18 @@ def test_host_bivariate_normal_and_autod_gamma_numerics():
             assert np.all(np.diag(M) > 0.75)
 
 
+RANDOM_PARAMETER_CASES = [("hiv_ns2.ctl", "codeml", 1), ("hiv_ns8.ctl", "codeml", 2), ("lyso_bsa.ctl", "codeml", 3),
+                          ("horai_mg4.ctl", "baseml", 4), ("brown_hky85_g4.ctl", "baseml", 5),
+                          # the model options of round 2: free-ratio and fixed-omega branch models, other genetic codes, AAClasses per
+                          # branch label, the mutation-selection model, omega from amino-acid distances, gamma shapes per gene,
+                          # frequency sets per branch, site classes on the 192-taxon tree with scaling nodes
+                          ("lysos_free.ctl", "codeml", 6), ("lysos_branch_fix.ctl", "codeml", 7), ("hiv_ns0_icode5.ctl", "codeml", 8),
+                          ("mtcdna_aaclass_branch.ctl", "codeml", 9), ("hiv_fmutsel.ctl", "codeml", 10), ("mtcdnapri_aadist1.ctl", "codeml", 11),
+                          ("horai_mg4_malpha.ctl", "baseml", 12), ("brown_hky85_nhomo3.ctl", "baseml", 13), ("mhc_ns2.ctl", "codeml", 14)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("ctl,prog,seed", [("hiv_ns2.ctl", "codeml", 1), ("hiv_ns8.ctl", "codeml", 2), ("lyso_bsa.ctl", "codeml", 3),
-                                           ("horai_mg4.ctl", "baseml", 4), ("brown_hky85_g4.ctl", "baseml", 5),
-                                           # the model options of round 2: free-ratio and fixed-omega branch models, other genetic codes, AAClasses per
-                                           # branch label, the mutation-selection model, omega from amino-acid distances, gamma shapes per gene,
-                                           # frequency sets per branch, site classes on the 192-taxon tree with scaling nodes
-                                           ("lysos_free.ctl", "codeml", 6), ("lysos_branch_fix.ctl", "codeml", 7), ("hiv_ns0_icode5.ctl", "codeml", 8),
-                                           ("mtcdna_aaclass_branch.ctl", "codeml", 9), ("hiv_fmutsel.ctl", "codeml", 10), ("mtcdnapri_aadist1.ctl", "codeml", 11),
-                                           ("horai_mg4_malpha.ctl", "baseml", 12), ("brown_hky85_nhomo3.ctl", "baseml", 13), ("mhc_ns2.ctl", "codeml", 14)])
+@pytest.mark.parametrize("ctl,prog,seed", RANDOM_PARAMETER_CASES)
 def test_differential_against_the_reference_binary_at_random_parameters(ctl, prog, seed, tmp_path):
     _differential(ctl, prog, seed, tmp_path)
 
@@ -1169,8 +1174,11 @@ def test_pattern_format_with_genes(ctl, tmp_path):
         assert abs(lb - float(m[-1])) <= 2e-6 * max(1.0, abs(lb) / 1000), (lb, m[-1])
 
 
-@pytest.mark.parametrize("prog,ctl", [("baseml", "brown_hky85_clock.ctl"), ("baseml", "brown_hky85_clock2.ctl"), ("baseml", "hiv2_tipdate.ctl"),
-                                      ("baseml", "hiv2_tipdate_clock2.ctl"), ("codeml", "lysos_m0_clock.ctl")])
+CLOCK_CASES = [("baseml", "brown_hky85_clock.ctl"), ("baseml", "brown_hky85_clock2.ctl"), ("baseml", "hiv2_tipdate.ctl"),
+               ("baseml", "hiv2_tipdate_clock2.ctl"), ("codeml", "lysos_m0_clock.ctl")]
+
+
+@pytest.mark.parametrize("prog,ctl", CLOCK_CASES)
 def test_differential_of_the_clock_models_on_cpu(prog, ctl, tmp_path):
     """The clock models (their parameters are node ages: a random vector would put nodes above their ancestors) at the host's own initial
     values against the reference binary: global and local clocks, dated tips, and the codon model M0 under a global clock."""
@@ -1221,16 +1229,23 @@ def test_differential_of_option_variants_on_cpu(variant, tmp_path):
     UNREST) with gamma rates on brown.nuc, the amino-acid models 0-3, CodonFreq 0 / 1 / 3, fixed kappa / omega (M2a with w2 = 1 and M8a among
     them), a rooted tree analysed without a clock (one branch more than the unrooted tree: the reference warns and goes on), and
     cleandata = 1 on alignments with ambiguity characters (sites removed) — random parameters, live reference."""
+    with _variant_ctl(variant) as (name, prog):
+        _differential(name, prog, 40 + sum(map(ord, variant)), tmp_path, on_gpu=False, key="variant/" + variant)
+
+
+@contextlib.contextmanager
+def _variant_ctl(variant):
+    """The variant's control file, written beside the others (the ../data/ paths stay valid) for the duration: (file name, program)."""
     base, prog = VARIANTS[variant][:2]
     txt = open(os.path.join(CTL, base)).read()
     for a_, b_ in VARIANTS[variant][2:]:
         assert a_ in txt, (base, a_)
         txt = txt.replace(a_, b_)
     name = "variant_%d.ctl" % (abs(hash(variant)) % 10 ** 8)
-    path = os.path.join(CTL, name)      # beside the others: the ../data/ paths stay valid
+    path = os.path.join(CTL, name)
     open(path, "w").write(txt)
     try:
-        _differential(name, prog, 40 + sum(map(ord, variant)), tmp_path, on_gpu=False)
+        yield name, prog
     finally:
         os.remove(path)
 
@@ -1244,36 +1259,100 @@ TOL_LNL_PRINTED_DIGITS = 2e-6
 TOL_LNL_M9_TO_M13_AGAINST_THE_LIVE_BINARY = 5e-3
 
 
-def _differential(ctl, prog, seed, tmp_path, on_gpu=True):
-    """Beyond the committed vectors: the unmodified reference binary (oracle/_ref, when it travelled with the repository) and the
-    engine evaluate the same control file at a RANDOM parameter vector inside the bounds; lnL must agree to the printed digits
-    (TOL_LNL_PRINTED_DIGITS) — to TOL_LNL_M9_TO_M13_AGAINST_THE_LIVE_BINARY = 5e-3 for NSsites 9 .. 13, see above."""
-    import shutil
-    exe = os.path.join(helpers.REPO, "oracle", "_ref", prog)
-    if not os.access(exe, os.X_OK):
-        pytest.skip("oracle/_ref/%s is not here (it is built from /root/reference in the build container)" % prog)
-    a = hostlib.Analysis(os.path.join(CTL, ctl), prog)
+DIFFERENTIAL_GOLDEN = os.path.join(helpers.GOLDEN, "differential.json")
+_STORED = {}
+
+
+def _stored_differential():
+    """tests/golden/differential.json: per differential case the parameter vector and the lnL the unmodified reference binary printed for
+    it (written by record_differential, python tests/golden/make_golden.py differential)."""
+    if not _STORED and os.path.exists(DIFFERENTIAL_GOLDEN):
+        with open(DIFFERENTIAL_GOLDEN) as f:
+            _STORED.update(json.load(f))
+    return _STORED
+
+
+def _differential_x(a, seed):
+    """The parameter vector of a differential case: the host's initial values (seed None) or a random vector inside the bounds."""
     lo, hi = a.bounds()
     if seed is None:
-        x = np.round(a.default_x(), 6)
-    else:
-        rng = np.random.default_rng(seed)
-        x = a.default_x() * np.where(hi <= 1, rng.uniform(0.7, 1.0, a.np), rng.uniform(0.7, 1.4, a.np))     # (proportions only shrink: they stay feasible)
-        x = np.round(np.clip(x, lo * 1.5, np.minimum(hi * 0.9, 50)), 6)           # in.codeml carries six decimals
+        return np.round(a.default_x(), 6)
+    rng = np.random.default_rng(seed)
+    x = a.default_x() * np.where(hi <= 1, rng.uniform(0.7, 1.0, a.np), rng.uniform(0.7, 1.4, a.np))     # (proportions only shrink: they stay feasible)
+    return np.round(np.clip(x, lo * 1.5, np.minimum(hi * 0.9, 50)), 6)           # in.codeml carries six decimals
+
+
+def _reference_lnl(exe, ctl, prog, x, workdir):
+    """The unmodified reference binary's lnL for control file `ctl` at the parameter vector x (single evaluation, in.codeml / in.baseml)."""
+    import shutil
     text = open(os.path.join(CTL, ctl)).read()
     for name in re.findall(r"\.\./data/(\S+)", text):
-        shutil.copy(os.path.join(helpers.GOLDEN, "data", name), tmp_path / name)
+        shutil.copy(os.path.join(helpers.GOLDEN, "data", name), workdir / name)
     for name in ("OmegaAA.dat", "grantham.dat", "miyata.dat"):      # read by fixed names from the working directory (aaDist models)
         for d in (CTL, os.path.join(helpers.GOLDEN, "data")):
             if os.path.exists(os.path.join(d, name)):
-                shutil.copy(os.path.join(d, name), tmp_path / name)
+                shutil.copy(os.path.join(d, name), workdir / name)
     main = "mlc" if prog == "codeml" else "mlb"
-    (tmp_path / (prog + ".ctl")).write_text(text.replace("../data/", "") + "\noutfile = %s\nnoisy = 0\nverbose = 0\nrunmode = 0\ngetSE = 0\nRateAncestor = 0\n" % main)
-    (tmp_path / ("in." + prog)).write_text("-1 " + " ".join("%.6f" % v for v in x) + "\n")
-    r = subprocess.run([exe, prog + ".ctl"], cwd=tmp_path, capture_output=True, text=True, input="\n" * 50, timeout=600)
-    m = re.findall(r"lnL\(ntime:[^\n]*?(-[0-9]+\.[0-9]+)", open(tmp_path / main).read())
+    (workdir / (prog + ".ctl")).write_text(text.replace("../data/", "") + "\noutfile = %s\nnoisy = 0\nverbose = 0\nrunmode = 0\ngetSE = 0\nRateAncestor = 0\n" % main)
+    (workdir / ("in." + prog)).write_text("-1 " + " ".join("%.6f" % v for v in x) + "\n")
+    r = subprocess.run([exe, prog + ".ctl"], cwd=workdir, capture_output=True, text=True, input="\n" * 50, timeout=600)
+    m = re.findall(r"lnL\(ntime:[^\n]*?(-[0-9]+\.[0-9]+)", open(workdir / main).read())
     assert m, r.stdout[-2000:]
-    ref = float(m[-1])
+    return float(m[-1])
+
+
+def _differential(ctl, prog, seed, tmp_path, on_gpu=True, key=None):
+    """Beyond the committed golden cases: the unmodified reference binary and the engine evaluate the same control file at a RANDOM
+    parameter vector inside the bounds; lnL must agree to the printed digits (TOL_LNL_PRINTED_DIGITS) — to
+    TOL_LNL_M9_TO_M13_AGAINST_THE_LIVE_BINARY = 5e-3 for NSsites 9 .. 13, see above.  The reference's lnL is the one stored for the case in
+    tests/golden/differential.json (with the vector it was run at); where the binary is here (oracle/_ref) it is run as well, and its
+    lnL must be the stored one."""
+    key = key or "%s/%s/%s" % (prog, ctl, seed)
+    exe = os.path.join(helpers.REPO, "oracle", "_ref", prog)
+    live = os.access(exe, os.X_OK)
+    stored = _stored_differential().get(key)
+    assert live or stored is not None, "no stored reference lnL for %s: python tests/golden/make_golden.py differential" % key
+    a = hostlib.Analysis(os.path.join(CTL, ctl), prog)
+    x = _differential_x(a, seed)
+    tol = TOL_LNL_M9_TO_M13_AGAINST_THE_LIVE_BINARY if re.search(r"hiv_ns(9|1[0-3])\.ctl", ctl) else None
+    if stored is not None:
+        assert np.array_equal(x, np.asarray(stored["x"], dtype=float)), (key, "the stored lnL is for another parameter vector")
+        ref = stored["lnL"]
+        tol = tol or TOL_LNL_PRINTED_DIGITS * max(1.0, abs(ref) / 1000)
+        if live:
+            live_ref = _reference_lnl(exe, ctl, prog, x, tmp_path)
+            assert abs(live_ref - ref) <= tol, (key, live_ref, ref)
+    else:
+        ref = _reference_lnl(exe, ctl, prog, x, tmp_path)
+        tol = tol or TOL_LNL_PRINTED_DIGITS * max(1.0, abs(ref) / 1000)
     got = a.eval_gpu(x, want_lnf=False)[0] if on_gpu else oracle.evaluate(a.problem(x), want_lnf=False)["lnL"]
-    tol = TOL_LNL_M9_TO_M13_AGAINST_THE_LIVE_BINARY if re.search(r"hiv_ns(9|1[0-3])\.ctl", ctl) else TOL_LNL_PRINTED_DIGITS * max(1.0, abs(ref) / 1000)
     assert abs(got - ref) <= tol, (got, ref)
+
+
+def differential_cases():
+    """Every differential case of this module: (key, control file, program, seed, variant or None)."""
+    out = [("%s/%s/%s" % (prog, ctl, seed), ctl, prog, seed, None) for ctl, prog, seed in RANDOM_PARAMETER_CASES]
+    out += [("%s/%s/%s" % (prog, ctl, 100 + sum(map(ord, ctl))), ctl, prog, 100 + sum(map(ord, ctl)), None) for _, prog, ctl in DIFF_CASES]
+    out += [("%s/%s/%s" % (prog, ctl, 500 + sum(map(ord, ctl))), ctl, prog, 500 + sum(map(ord, ctl)), None)
+            for _, prog, ctl in DIFF_CASES if not ctl.startswith("mhc_ns")]
+    out += [("%s/%s/None" % (prog, ctl), ctl, prog, None, None) for prog, ctl in CLOCK_CASES]
+    out += [("variant/" + v, None, VARIANTS[v][1], 40 + sum(map(ord, v)), v) for v in sorted(VARIANTS)]
+    return out
+
+
+def record_differential(path=DIFFERENTIAL_GOLDEN):
+    """Run the unmodified reference binaries (oracle/_ref) on every differential case and store vector and lnL at `path`."""
+    import pathlib
+    import tempfile
+    rec = {}
+    for key, ctl, prog, seed, variant in differential_cases():
+        exe = os.path.join(helpers.REPO, "oracle", "_ref", prog)
+        with contextlib.ExitStack() as st:
+            if variant is not None:
+                ctl, _ = st.enter_context(_variant_ctl(variant))
+            x = _differential_x(hostlib.Analysis(os.path.join(CTL, ctl), prog), seed)
+            d = pathlib.Path(st.enter_context(tempfile.TemporaryDirectory(prefix="differential_")))
+            rec[key] = {"prog": prog, "x": [float(v) for v in x], "lnL": _reference_lnl(exe, ctl, prog, x, d)}
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=0, sort_keys=True)
+    return rec

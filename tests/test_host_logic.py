@@ -438,35 +438,57 @@ def test_plfun_seam_example_compiles_and_links(tmp_path):
         assert run.returncode == 1 and "no GPU" in run.stderr
 
 
+def _binding_patch_is_confined(patch):
+    """A binding patch only adds lines, and every added line lies inside `#ifdef PAML_AMD`."""
+    added = [ln[1:] for ln in open(patch) if ln.startswith("+") and not ln.startswith("+++")]
+    removed = [ln for ln in open(patch) if ln.startswith("-") and not ln.startswith("---")]
+    assert added and not removed, "the patch only adds lines"
+    depth, outside = 0, []
+    for ln in added:
+        t = ln.strip()
+        if t.startswith("#ifdef PAML_AMD"):
+            depth += 1
+        elif t.startswith("#endif") and depth:
+            depth -= 1
+        elif t.startswith("#else") and depth:
+            pass
+        elif depth == 0 and t:
+            outside.append(ln)
+    assert not outside, outside[:3]
+
+
+def _reference_sources():
+    """Where oracle/Makefile's recipe finds the reference's sources: its REF (from the environment, else the Makefile's default)."""
+    import re
+    ref = os.environ.get("REF")
+    if not ref:
+        m = re.search(r"^REF \?= *(\S+)", open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "Makefile")).read(), re.M)
+        ref = m.group(1) if m else ""
+    return ref
+
+
+def test_reference_binding_patches_touch_nothing_outside_their_ifdef():
+    """integration/{codeml,baseml}_plfun.patch as committed: they only add lines, all inside `#ifdef PAML_AMD` (no reference source needed)."""
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for prog in ("codeml", "baseml"):
+        _binding_patch_is_confined(os.path.join(repo, "integration", prog + "_plfun.patch"))
+
+
 def test_reference_binding_patches_apply_and_link():
-    """integration/{codeml,baseml}_plfun.patch against the reference sources where they lie (build container only): they apply without
-    fuzz or rejects, touch nothing outside `#ifdef PAML_AMD`, and the recipe of oracle/Makefile links the patched programs against
+    """integration/{codeml,baseml}_plfun.patch against the reference sources where they lie (those of oracle/Makefile's recipe): they apply
+    without fuzz or rejects, touch nothing outside `#ifdef PAML_AMD`, and the recipe of oracle/Makefile links the patched programs against
     libpaml_amd.so (running them needs the GPU: tests/test_reference_binding_gpu.py)."""
     import shutil
     import subprocess
-    ref = "/root/reference/src"
-    if not os.path.isdir(ref) or not shutil.which("patch"):
+    ref = _reference_sources()
+    if not ref or not os.path.isdir(ref) or not shutil.which("patch"):
         pytest.skip("the reference sources are not here")
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for prog in ("codeml", "baseml"):
         patch = os.path.join(repo, "integration", prog + "_plfun.patch")
         r = subprocess.run(["patch", "--dry-run", "-o", "/dev/null", os.path.join(ref, prog + ".c"), patch], capture_output=True, text=True)
         assert r.returncode == 0 and "fuzz" not in r.stdout and "FAILED" not in r.stdout, r.stdout + r.stderr
-        added = [ln[1:] for ln in open(patch) if ln.startswith("+") and not ln.startswith("+++")]
-        removed = [ln for ln in open(patch) if ln.startswith("-") and not ln.startswith("---")]
-        assert not removed, "the patch only adds lines"
-        depth, outside = 0, []
-        for ln in added:
-            t = ln.strip()
-            if t.startswith("#ifdef PAML_AMD"):
-                depth += 1
-            elif t.startswith("#endif") and depth:
-                depth -= 1
-            elif t.startswith("#else") and depth:
-                pass
-            elif depth == 0 and t:
-                outside.append(ln)
-        assert not outside, outside[:3]
+        _binding_patch_is_confined(patch)
         exe = os.path.join(repo, "oracle", "_ref", prog + "_gpu")
         assert subprocess.run(["make", "-C", os.path.join(repo, "oracle"), "_ref/" + prog + "_gpu"], capture_output=True).returncode == 0
         assert os.access(exe, os.X_OK)

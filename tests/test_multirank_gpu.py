@@ -114,6 +114,26 @@ def test_two_ranks_with_a_collective_that_needs_a_cu_and_waits_for_its_peers(tmp
             assert r[key] == one[key], (key, r[key], one[key])
 
 
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """bench.py --gpus 1 without --full: the headline only (exactly --steps timed steps, no roofline or CPU baseline); --dump-outputs
+    writes the last timed step's lnL, the line's bits.  With --full (extras left out) the roofline's profiled run is back."""
+    common = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--patterns", "40000"]
+    r = subprocess.run(common + ["--dump-outputs", str(tmp_path / "out")], cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["higher_is_better"] is True and line["dtype"] == "f64" and line["unit"] == "site-patterns/s"
+    assert not {"roofline", "cpu_baseline", "sweep", "c2", "c5"} & set(line)
+    dumped = np.load(tmp_path / "out" / "lnL.npy")
+    assert dumped.dtype == np.float64 and dumped.shape == (1,) and float(dumped[0]).hex() == line["lnL_hex"]
+    r = subprocess.run(common + ["--full", "--no-extras", "--no-cpu-baseline"], cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    full = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    assert full["lnL_hex"] == line["lnL_hex"] and full["roofline"]["kernel_ms"] > 0 and "cpu_baseline" not in full
+
+
 def test_bench_on_two_ranks_of_one_gpu(tmp_path):
     """bench.py --gpus 2 exactly as the driver launches it (torch.distributed.run, one process per rank), but both ranks on
     GPU 0 (PAML_AMD_BENCH_ONE_GPU=1: gloo carries the id and the timing's barrier / max).  Strong scaling of the same patterns:
@@ -125,7 +145,7 @@ def test_bench_on_two_ranks_of_one_gpu(tmp_path):
     assert r1.returncode == 0, r1.stderr.decode()[-3000:]
     one = json.loads(r1.stdout.decode().strip().splitlines()[-1])
     r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                         "--master-port", str(free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2"] + common, env=env, cwd=REPO,
+                         "--master-port", str(free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--full"] + common, env=env, cwd=REPO,
                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert r2.returncode == 0, r2.stderr.decode()[-3000:]
     lines = [ln for ln in r2.stdout.decode().splitlines() if ln.startswith("{")]
@@ -205,7 +225,7 @@ def test_bench_launches_itself_on_real_gpus(world, tmp_path):
                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r1.returncode == 0, r1.stderr.decode()[-3000:]
     one = json.loads(r1.stdout.decode().strip().splitlines()[-1])
-    rn = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(world)] + common, env=env, cwd=REPO,
+    rn = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(world), "--full"] + common, env=env, cwd=REPO,
                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert rn.returncode == 0, rn.stderr.decode()[-3000:]
     lines = [ln for ln in rn.stdout.decode().splitlines() if ln.startswith("{")]

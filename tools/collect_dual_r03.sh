@@ -14,7 +14,7 @@ S=8p,8c,4p,2p,1p,1c,8p
 { for s in 8p 1p; do echo "# hand-over, $s"; PAML_AMD_JIT_CACHE=0 PAML_AMD_PROF_TILES=1 PAML_AMD_PROF_OPS=/tmp/tl.bin python tools/dual_probe.py $s 2>&1 | grep '^[0-9]'; python tools/handover.py /tmp/tl.bin; done; } > $out/handover.txt
 cd /tmp
 for n in 124928 1000000; do
-  rm -rf /tmp/tl; rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -o tl -- python $R/bench.py --no-extras --no-cpu-baseline --steps 30 --patterns $n > /tmp/b.log 2>&1
+  rm -rf /tmp/tl; rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -o tl -- python $R/bench.py --full --no-extras --no-cpu-baseline --steps 30 --patterns $n > /tmp/b.log 2>&1
   { echo "# $n patterns, kernel trace of bench.py's timed loop (rows 60..)"; python $R/tools/raw_timeline.py /tmp/tl 28 60; } > $out/timeline_$n.txt
 done
 cat $out/comm_overhead.txt $out/lanes.txt $out/handover.txt

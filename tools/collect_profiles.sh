@@ -5,7 +5,7 @@ tag=${1:-r01}
 out=$PWD/gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-B="python $PWD/bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+B="python $PWD/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o s -- $B > $out/bench_under_rocprof.json 2>$out/stats.err
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/pmc_fetch -o f -- $B > /dev/null 2>&1
@@ -19,7 +19,7 @@ cd - > /dev/null
   echo "# LDS"; python tools/pmc_summary.py $out/pmc_lds
 } > $out/pmc_summary.txt 2>&1
 find $out/stats -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \;
-python bench.py > $out/bench_1gpu.json 2>$out/bench.err
+python bench.py --full > $out/bench_1gpu.json 2>$out/bench.err
 # keep the merged directory small: raw traces are not needed
 rm -rf $out/stats $out/pmc_fetch $out/pmc_write $out/pmc_mfma $out/pmc_lds
 cat $out/kernel_stats.csv | head -8; cat $out/pmc_summary.txt; cat $out/bench_1gpu.json

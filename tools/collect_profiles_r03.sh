@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 # the evaluation period) and the per-dispatch counters of overlapping dispatches mix.  profiles/r03_dual_stream.txt has the
 # overlapped timeline (tools/collect_dual_r03.sh).
 export PAML_AMD_DUAL=0
-B="python $PWD/bench.py --no-cpu-baseline --no-extras"      # bench.py with its default step counts, headline only
+B="python $PWD/bench.py --full --no-cpu-baseline --no-extras"      # bench.py with its default step counts, headline only
 C2="python $PWD/tools/c2_probe.py"
 M20="python $PWD/tools/m20_probe.py"
 cd /tmp

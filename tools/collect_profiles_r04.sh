@@ -8,7 +8,7 @@ rm -rf $out; mkdir -p $out
 export TMPDIR=/tmp
 export PAML_AMD_DUAL=0      # launches one after the other: per-kernel durations and per-dispatch counters (see collect_profiles_r03.sh)
 R=$PWD
-B="python $R/bench.py --no-cpu-baseline --no-extras"
+B="python $R/bench.py --full --no-cpu-baseline --no-extras"
 BR="python $R/tools/branch_probe.py"
 C2="python $R/tools/c2_probe.py 100000"
 M20="python $R/tools/m20_probe.py 0"

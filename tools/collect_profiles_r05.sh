@@ -8,7 +8,7 @@ rm -rf $out; mkdir -p $out
 export TMPDIR=/tmp
 export PAML_AMD_DUAL=0      # launches one after the other: per-kernel durations and per-dispatch counters (see collect_profiles_r03.sh)
 R=$PWD
-B="python $R/bench.py --no-cpu-baseline --no-extras"
+B="python $R/bench.py --full --no-cpu-baseline --no-extras"
 cd /tmp
 prof() { d=$1; shift; rocprofv3 "$@" > $out/$d.out 2>$out/$d.err; }
 prof stats      --kernel-trace --stats --output-format csv -d $out/stats -o s -- $B

@@ -8,7 +8,7 @@ rm -rf $out; mkdir -p $out
 export TMPDIR=/tmp
 export PAML_AMD_DUAL=0      # launches one after the other: per-kernel durations and per-dispatch counters (see collect_profiles_r03.sh)
 R=$PWD
-B="python $R/bench.py --no-cpu-baseline --no-extras"
+B="python $R/bench.py --full --no-cpu-baseline --no-extras"
 cd /tmp
 prof() { d=$1; shift; rocprofv3 "$@" > $out/$d.out 2>$out/$d.err; }
 stats() { name=$1; shift; prof stats_$name --kernel-trace --stats --output-format csv -d $out/stats_$name -o s -- "$@"; find $out/stats_$name -name "*kernel_stats.csv" -exec cp {} $out/${name}_kernel_stats.csv \; ; grep -v "^W2026\|^E2026" $out/stats_$name.out | tail -3 > $out/${name}_under_rocprof.txt; rm -rf $out/stats_$name $out/stats_$name.out $out/stats_$name.err; }

@@ -3,9 +3,9 @@
 out=$PWD/gpurun_out/r04f
 rm -rf $out; mkdir -p $out; export TMPDIR=/tmp
 R=$PWD
-python bench.py --steps 20 --warmup 5 > $out/bench_driver_command.json 2> $out/bench_driver_command.err
-python bench.py > $out/bench_1gpu.json 2> $out/bench_1gpu.err
-(cd /tmp && PAML_AMD_DUAL=0 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o s -- python $R/bench.py --no-cpu-baseline --no-extras > $out/bench_under_rocprof.json 2> $out/stats.err)
+python bench.py --full --steps 20 --warmup 5 > $out/bench_driver_command.json 2> $out/bench_driver_command.err
+python bench.py --full > $out/bench_1gpu.json 2> $out/bench_1gpu.err
+(cd /tmp && PAML_AMD_DUAL=0 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o s -- python $R/bench.py --full --no-cpu-baseline --no-extras > $out/bench_under_rocprof.json 2> $out/stats.err)
 find $out/stats -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; ; rm -rf $out/stats
 for c in hiv_m0 hiv_m8 stewart brown; do
   (cd /tmp && rm -rf /tmp/tr_$c && rocprofv3 --kernel-trace --output-format csv -d /tmp/tr_$c -o t -- python $R/tools/small_timeline.py $c 200 > /tmp/tr_$c.log 2>&1; tail -1 /tmp/tr_$c.log; python $R/tools/small_timeline_digest.py /tmp/tr_$c | head -5)

@@ -3,7 +3,7 @@
 # performance figure — the lnL bits, the sweep, the weak block, the replicas, the exchange diagnostics, the guard
 out=$PWD/gpurun_out/r04f; mkdir -p $out; export TMPDIR=/tmp
 export PAML_AMD_BENCH_ONE_GPU=1 PAML_AMD_RCCL_LIB=$PWD/tests/shim/librccl_shim.so
-timeout 420 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 8 --steps 5 --warmup 2 > $out/bench_8ranks_one_gpu.json 2> $out/bench_8ranks_one_gpu.err
+timeout 420 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 8 --steps 5 --warmup 2 > $out/bench_8ranks_one_gpu.json 2> $out/bench_8ranks_one_gpu.err
 echo rc=$?
 python - <<'PY'
 import json

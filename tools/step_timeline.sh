@@ -1,7 +1,7 @@
 #!/bin/bash
 # where a step of the headline loop goes: kernel start / end times (rocprofv3 --kernel-trace) of a few consecutive evaluations
 out=$PWD/gpurun_out/steptl; rm -rf $out; mkdir -p $out; export TMPDIR=/tmp
-(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $out -o t -- python $OLDPWD/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > /dev/null 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $out -o t -- python $OLDPWD/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras > /dev/null 2>&1)
 python - "$out" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
