@@ -174,9 +174,6 @@ __device__ __forceinline__ void dma4(__amdgpu_buffer_rsrc_t r, const void *lds, 
 template <int WAVES>
 __device__ __forceinline__ void stage_p(const double *g, double *s, int wave, int lane)
 {
-#ifdef ABL_NO_STAGE
-   return;
-#endif
    const __amdgpu_buffer_rsrc_t r = make_rsrc(g, 32768);
 #pragma unroll
    for (int c = 0; c < 32 / WAVES; c++) {
@@ -191,13 +188,6 @@ __device__ __forceinline__ void mfma_matvec(const double *sPbuf, int lane, const
    const double2 *sp = (const double2 *)sPbuf;
 #pragma unroll
    for (int jb = 0; jb < 4; jb++) acc[jb] = (v4d){0, 0, 0, 0};
-#ifdef ABL_NO_MFMA
-#pragma unroll
-   for (int jb = 0; jb < 4; jb++) {
-      const double2 a2 = sp[jb * 64 + lane];
-      acc[jb] = (v4d){a2.x * cur[4 * jb], a2.y * cur[4 * jb + 1], a2.x * cur[4 * jb + 2], a2.y * cur[4 * jb + 3]};
-   }
-#else
    double2 af[2][4];
 #pragma unroll
    for (int jb = 0; jb < 4; jb++) af[0][jb] = sp[jb * 64 + lane];
@@ -216,21 +206,14 @@ __device__ __forceinline__ void mfma_matvec(const double *sPbuf, int lane, const
          acc[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kb2 & 1][jb].y, cur[2 * kb2 + 1], acc[jb], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
    }
-#endif
 }
 
 
 // XOR swizzle of the eight 16-byte pieces of a tip-table row (row = code * 4 + state quarter): lanes of one
 // ds_read_b128 group read rows of 16 different patterns, i.e. random codes; mixing the code's low and middle bits into
 // the slot spreads them over all 8 slots of their bank half instead of 4.
-// (TIP_SWZ_OFF: build-time experiment — plain rows, the eight pieces at immediate offsets of one address register: eight fewer
-//  vector instructions per gathered row against more bank conflicts.  Measured slower, 1.577 against 1.555 ms per launch at 16 taxa x
-//  10^6 codon patterns (profiles/r04_61state.txt); PAML_AMD_EXTRA_FLAGS=-DTIP_SWZ_OFF=1, see engine.py build())
-#ifdef TIP_SWZ_OFF
-#define TIP_SWZ(row) 0
-#else
+// (plain rows without the swizzle: slower, 1.577 against 1.555 ms per launch, profiles/r04_61state.txt)
 #define TIP_SWZ(row) ((((row) >> 2) ^ ((row) >> 5)) & 7)
-#endif
 struct StreamBlk { int is_tip, node; };
 
 __device__ __forceinline__ void wait_blocks_in_flight(int n)   // allow the n newest blocks (4 loads each) to fly
@@ -252,11 +235,6 @@ __device__ __forceinline__ void tip_gather(const double *Ptip, long tipstride, i
 
 __device__ __forceinline__ void tip_lds(const double *tab, int code, int q, int lane, double2 (&v)[8])
 {
-#ifdef ABL_NO_TIPLOAD
-#pragma unroll
-   for (int p = 0; p < 8; p++) v[p] = make_double2(0.5 + code * 1e-3, 0.25 + q * 1e-3);
-   return;
-#endif
    const int row = code * 4 + q, swz = TIP_SWZ(row);
    const char *base = (const char *)tab + row * 128;
 #pragma unroll
@@ -329,18 +307,12 @@ __device__ __forceinline__ void jit_tip_overflow(const JitAmb &amb, const double
 // the accumulator tuple of row block jb = m >> 2, so MFMA results are partials with no copies, and the
 // B operand of k-block kb is x[kb >> 2][kb & 3].
 // ------------------------------------------------------------------------------------------------
-/* Waves per workgroup of the per-tree kernel = 16-pattern groups per tile.  8 (two per SIMD) or 12 (three per SIMD, <= 168
- * VGPRs): with three, a SIMD's matrix pipe finds a wave with an MFMA ready more often, and the per-step synchronisation is
- * spread over half as much again of arithmetic. */
+/* Waves per workgroup of the per-tree kernel = 16-pattern groups per tile: 8, two per SIMD. */
 #ifndef JIT_WAVES
 #define JIT_WAVES 8
 #endif
 #define JIT_TP (JIT_WAVES * 16)
-#ifdef JIT_ABL_NOBAR
-#define JIT_SYNC() ((void)0)
-#else
 #define JIT_SYNC() __syncthreads()
-#endif
 // `side(kb2)` runs once per k-block pair between the two MFMA groups: the generator puts the ring's refill DMAs there
 // (a few per iteration) so that their issue — which can queue behind the other waves' — never delays the first MFMAs.
 struct JitNoSide { __device__ __forceinline__ void operator()(int) const {} };
@@ -351,11 +323,6 @@ __device__ __forceinline__ double jit_x60(const v4d (&x)[4], int lane) { return 
 
 __device__ __forceinline__ void jit_col_seed(const double *col, int lane, double x60, v4d (&z)[4])
 {
-#ifdef JIT_ABL_NOSEED      // timing experiment (results are garbage): no column reads, no dependent multiplies in front of the first MFMAs
-#pragma unroll
-   for (int i = 0; i < 4; i++) z[i] = (v4d){x60, x60, x60, x60};
-   return;
-#endif
    const double2 *pc = (const double2 *)(col + (lane >> 4) * 16);
 #pragma unroll
    for (int i = 0; i < 8; i++) {
@@ -364,44 +331,6 @@ __device__ __forceinline__ void jit_col_seed(const double *col, int lane, double
       z[i >> 1][(2 * i + 1) & 3] = c.y * x60;
    }
 }
-
-// ---- 61 states without the row padding (JIT_ROWTAIL; pmat_kernel layout 3) ---------------------------------------------------------
-// Rows 0..47 of P are three 16 x 16 x 4 row blocks; rows 48..59 go through v_mfma_f64_4x4x4 (three row quartets m' = 12, 13, 14:
-// an instruction does the quartet's 4 x 4 block of one k-block for all sixteen patterns in a quarter of a 16 x 16 x 4's pipe
-// time, its result lands in the lanes' element m' — the partial's own layout, as in the 20-state kernel), row 60 is a dot product
-// on the vector pipe, rows 61..63 do not exist: 45 + 45 / 4 = 56.25 instead of 60 big-instruction times per product.
-// In the operand block the fourth row block's 1 KB slot of every k-block pair holds instead, for e = 0, 1 and m' = 12, 13, 14,
-// the sixteen words [k][i] = P[4 m' + i][4 (2 kb2 + e) + k] at doubles (e * 3 + m' - 12) * 16 .., and from double 96 on
-// [q][e] = P[60][4 (2 kb2 + e) + q] (column 60 itself arrives through the rank-1 seed).
-#ifdef JIT_ROWTAIL
-#define JIT_RT 1
-#else
-#define JIT_RT 0
-#endif
-struct JitRowTail {
-   double a4[3];      // the k-block's three 4 x 4 x 4 operands (m' = 12, 13, 14); the pair's second k-block re-uses the registers
-   double r60;        // the lane's share of row 60
-};
-__device__ __forceinline__ unsigned jit_lds_addr(const double *p) { return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char *)p; }
-template <int OFF>
-__device__ __forceinline__ double jit_lds64(unsigned addr)
-{
-   double v;
-   asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-   return v;
-}
-// request the three small operands of k-block 2 KB2 + E (base = LDS byte address of the block + the lane's (k, i) word)
-template <int KB2, int E>
-__device__ __forceinline__ void jit_rt_fetch(unsigned base, JitRowTail &rt)
-{
-   constexpr int S = (KB2 * 4 + 3) * 1024 + E * 384;
-   rt.a4[0] = jit_lds64<S + 0 * 128>(base); rt.a4[1] = jit_lds64<S + 1 * 128>(base); rt.a4[2] = jit_lds64<S + 2 * 128>(base);
-}
-__device__ __forceinline__ void jit_rt_wait(JitRowTail &rt)      // the operands have arrived (LDS returns in order); nothing that uses them moves above
-{
-   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rt.a4[0]), "+v"(rt.a4[1]), "+v"(rt.a4[2]));
-}
-#define JIT_MFMA4(A, B, C) __builtin_amdgcn_mfma_f64_4x4x4f64((A), (B), (C), 0, 0, 0)
 
 // RB row blocks of 16 and KB k-blocks of 4 cover the model's states (4, 16 for 61; 2, 5 for 20): blocks beyond them are
 // zero padding in P and are neither fetched nor multiplied; accumulators of skipped row blocks stay 0.
@@ -414,73 +343,33 @@ __device__ __forceinline__ void jit_matvec(const double *sPbuf, int lane, const 
    if constexpr (TAIL61) jit_col_seed(col, lane, x60, z);
    double2 af[2][4];
    constexpr int KB2 = (KB + 1) / 2;
-   constexpr bool RT = JIT_RT && TAIL61 && RB == 4 && KB == 16;      // rows 48..60 without the padding (see JitRowTail)
-   constexpr int RBM = RT ? 3 : RB;
-   JitRowTail rt;
-   const unsigned rtbase = jit_lds_addr(sPbuf) + (((lane >> 4) << 2) + (lane & 3)) * 8;
-   const double2 *sp60 = (const double2 *)(sPbuf + 3 * 128 + 96) + (lane >> 4);      // (+ kb2 * 256 double2: the pair's slot)
 #pragma unroll
    for (int jb = RB; jb < 4; jb++) y[jb] = (v4d){0, 0, 0, 0};
-   if constexpr (RT) { y[3] = z[3]; rt.r60 = 0; }
 #pragma unroll
-   for (int jb = 0; jb < RBM; jb++) af[0][jb] = sp[jb * 64 + lane];
-#define JIT_RT_STEP(KB2V)                                                                                              \
-   if constexpr (RT) {                                                                                                \
-      const double2 p60 = sp60[(KB2V) * 256];                                                                         \
-      jit_rt_fetch<KB2V, 0>(rtbase, rt);                                                                              \
-      rt.r60 = fma(p60.x, x[(2 * (KB2V)) >> 2][(2 * (KB2V)) & 3], rt.r60);                                            \
-      if ((KB2V) != 7) rt.r60 = fma(p60.y, x[(2 * (KB2V) + 1) >> 2][(2 * (KB2V) + 1) & 3], rt.r60);                   \
-   }
-#define JIT_RT_FETCH1(KB2V) if constexpr (RT) { jit_rt_fetch<KB2V, 1>(rtbase, rt); }
-#define JIT_RT_SW(M)                                                                                                   \
-   switch (kb2) {                                                                                                     \
-   case 0: M(0) break; case 1: M(1) break; case 2: M(2) break; case 3: M(3) break;                                    \
-   case 4: M(4) break; case 5: M(5) break; case 6: M(6) break; default: M(7) break;                                   \
-   }
+   for (int jb = 0; jb < RB; jb++) af[0][jb] = sp[jb * 64 + lane];
 #pragma unroll
    for (int kb2 = 0; kb2 < KB2; kb2++) {
       if (kb2 + 1 < KB2) {
 #pragma unroll
-         for (int jb = 0; jb < RBM; jb++) af[(kb2 + 1) & 1][jb] = sp[((kb2 + 1) * 4 + jb) * 64 + lane];
-      }
-      if constexpr (RT) {      // (a literal pair index for the asm offsets)
-         switch (kb2) {
-         case 0: JIT_RT_STEP(0) break; case 1: JIT_RT_STEP(1) break; case 2: JIT_RT_STEP(2) break; case 3: JIT_RT_STEP(3) break;
-         case 4: JIT_RT_STEP(4) break; case 5: JIT_RT_STEP(5) break; case 6: JIT_RT_STEP(6) break; default: JIT_RT_STEP(7) break;
-         }
+         for (int jb = 0; jb < RB; jb++) af[(kb2 + 1) & 1][jb] = sp[((kb2 + 1) * 4 + jb) * 64 + lane];
       }
       __builtin_amdgcn_sched_barrier(0);
       const double b0 = x[(2 * kb2) >> 2][(2 * kb2) & 3], b1 = x[(2 * kb2 + 1) >> 2][(2 * kb2 + 1) & 3];
       if (kb2 == 0) {
 #pragma unroll
-         for (int jb = 0; jb < RBM; jb++)
+         for (int jb = 0; jb < RB; jb++)
             y[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[0][jb].x, b0, z[jb], 0, 0, 0);
       }
       else {
 #pragma unroll
-         for (int jb = 0; jb < RBM; jb++) y[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kb2 & 1][jb].x, b0, y[jb], 0, 0, 0);
-      }
-      if constexpr (RT) {
-         jit_rt_wait(rt);
-         y[3].x = JIT_MFMA4(rt.a4[0], b0, y[3].x); y[3].y = JIT_MFMA4(rt.a4[1], b0, y[3].y); y[3].z = JIT_MFMA4(rt.a4[2], b0, y[3].z);
-         if (kb2 != 7) { JIT_RT_SW(JIT_RT_FETCH1) }      // (sources are read at issue: the registers take the pair's second k-block)
+         for (int jb = 0; jb < RB; jb++) y[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kb2 & 1][jb].x, b0, y[jb], 0, 0, 0);
       }
       side(kb2);
       if (!(TAIL61 && kb2 == 7) && 2 * kb2 + 1 < KB) {
 #pragma unroll
-         for (int jb = 0; jb < RBM; jb++) y[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kb2 & 1][jb].y, b1, y[jb], 0, 0, 0);
-         if constexpr (RT) {
-            jit_rt_wait(rt);
-            y[3].x = JIT_MFMA4(rt.a4[0], b1, y[3].x); y[3].y = JIT_MFMA4(rt.a4[1], b1, y[3].y); y[3].z = JIT_MFMA4(rt.a4[2], b1, y[3].z);
-         }
+         for (int jb = 0; jb < RB; jb++) y[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kb2 & 1][jb].y, b1, y[jb], 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-   }
-   if constexpr (RT) {      // row 60: the four state-quarter lanes' shares, onto the q = 0 lane's element 15 (states 61..63 stay 0)
-      double r = rt.r60;
-      r += __shfl_xor(r, 16);
-      r += __shfl_xor(r, 32);
-      y[3].w = lane < 16 ? y[3].w + r : 0.0;
    }
 }
 
@@ -505,24 +394,15 @@ __device__ __forceinline__ void jit_matvec_tip2(const double *sPbuf, int lane, c
    v4d z[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
    if constexpr (TAIL61) jit_col_seed(col, lane, x60, z);
    double2 af[2][4];
-   constexpr bool RT = JIT_RT && TAIL61 && RB == 4 && KB == 16;      // rows 48..60 without the padding (see JitRowTail)
-   constexpr int RBM = RT ? 3 : RB;
-   JitRowTail rt;
-   const unsigned rtbase = jit_lds_addr(sPbuf) + (((lane >> 4) << 2) + (lane & 3)) * 8;
-   const double2 *sp60 = (const double2 *)(sPbuf + 3 * 128 + 96) + (lane >> 4);
    const int rowa = ca * 4 + q, rowb = cb * 4 + q, swa = TIP_SWZ(rowa), swb = TIP_SWZ(rowb);
    const char *pa = (const char *)ta + rowa * 128, *pb = (const char *)tb + rowb * 128;
-   // (row-tail form: the tip rows fetched in an iteration are multiplied at its end — two more small-MFMA groups per iteration hide
-   //  the LDS latency that the four-row-block form hides by deferring the products to the next iteration — half the staging registers)
-   constexpr int TB = (JIT_RT && TAIL61 && RB == 4 && KB == 16) ? 1 : 2;
-   double2 tv[TB][PPI], tw[TB][PPI];
+   double2 tv[2][PPI], tw[2][PPI];
 #pragma unroll
    for (int jb = RB; jb < 4; jb++) y[jb] = (v4d){0, 0, 0, 0};
 #pragma unroll
    for (int jb = 0; jb < 4; jb++) t[jb] = (v4d){0, 0, 0, 0};
-   if constexpr (RT) { y[3] = z[3]; rt.r60 = 0; }
 #pragma unroll
-   for (int jb = 0; jb < RBM; jb++) af[0][jb] = sp[jb * 64 + lane];
+   for (int jb = 0; jb < RB; jb++) af[0][jb] = sp[jb * 64 + lane];
 #pragma unroll
    for (int kb2 = 0; kb2 < KB2; kb2++) {
       if (kb2 == MID) {
@@ -531,21 +411,15 @@ __device__ __forceinline__ void jit_matvec_tip2(const double *sPbuf, int lane, c
       }
       if (kb2 + 1 < KB2) {
 #pragma unroll
-         for (int jb = 0; jb < RBM; jb++) af[(kb2 + 1) & 1][jb] = sp[((kb2 + 1) * 4 + jb) * 64 + lane];
-      }
-      if constexpr (RT) {
-         switch (kb2) {
-         case 0: JIT_RT_STEP(0) break; case 1: JIT_RT_STEP(1) break; case 2: JIT_RT_STEP(2) break; case 3: JIT_RT_STEP(3) break;
-         case 4: JIT_RT_STEP(4) break; case 5: JIT_RT_STEP(5) break; case 6: JIT_RT_STEP(6) break; default: JIT_RT_STEP(7) break;
-         }
+         for (int jb = 0; jb < RB; jb++) af[(kb2 + 1) & 1][jb] = sp[((kb2 + 1) * 4 + jb) * 64 + lane];
       }
       if (kb2 >= MID) {
 #pragma unroll
          for (int e = 0; e < PPI; e++) {
             const int p = PPI * (kb2 - MID) + e;
             if (p < NP) {
-               tv[kb2 & (TB - 1)][e] = *(const double2 *)(pa + ((p ^ swa) * 16));
-               tw[kb2 & (TB - 1)][e] = *(const double2 *)(pb + ((p ^ swb) * 16));
+               tv[kb2 & 1][e] = *(const double2 *)(pa + ((p ^ swa) * 16));
+               tw[kb2 & 1][e] = *(const double2 *)(pb + ((p ^ swb) * 16));
             }
          }
       }
@@ -553,19 +427,14 @@ __device__ __forceinline__ void jit_matvec_tip2(const double *sPbuf, int lane, c
       const double b0 = x[(2 * kb2) >> 2][(2 * kb2) & 3], b1 = x[(2 * kb2 + 1) >> 2][(2 * kb2 + 1) & 3];
       if (kb2 == 0) {
 #pragma unroll
-         for (int jb = 0; jb < RBM; jb++)
+         for (int jb = 0; jb < RB; jb++)
             y[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[0][jb].x, b0, z[jb], 0, 0, 0);
       }
       else {
 #pragma unroll
-         for (int jb = 0; jb < RBM; jb++) y[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kb2 & 1][jb].x, b0, y[jb], 0, 0, 0);
+         for (int jb = 0; jb < RB; jb++) y[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kb2 & 1][jb].x, b0, y[jb], 0, 0, 0);
       }
-      if constexpr (RT) {
-         jit_rt_wait(rt);
-         y[3].x = JIT_MFMA4(rt.a4[0], b0, y[3].x); y[3].y = JIT_MFMA4(rt.a4[1], b0, y[3].y); y[3].z = JIT_MFMA4(rt.a4[2], b0, y[3].z);
-         if (kb2 != 7) { JIT_RT_SW(JIT_RT_FETCH1) }      // (sources are read at issue: the registers take the pair's second k-block)
-      }
-      if (TB == 2 && kb2 > MID) {      // products of the rows fetched one iteration ago
+      if (kb2 > MID) {      // products of the rows fetched one iteration ago
 #pragma unroll
          for (int e = 0; e < PPI; e++) {
             const int p = PPI * (kb2 - 1 - MID) + e;
@@ -578,32 +447,12 @@ __device__ __forceinline__ void jit_matvec_tip2(const double *sPbuf, int lane, c
       side(kb2);
       if (!(TAIL61 && kb2 == 7) && 2 * kb2 + 1 < KB) {
 #pragma unroll
-         for (int jb = 0; jb < RBM; jb++) y[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kb2 & 1][jb].y, b1, y[jb], 0, 0, 0);
-         if constexpr (RT) {
-            jit_rt_wait(rt);
-            y[3].x = JIT_MFMA4(rt.a4[0], b1, y[3].x); y[3].y = JIT_MFMA4(rt.a4[1], b1, y[3].y); y[3].z = JIT_MFMA4(rt.a4[2], b1, y[3].z);
-         }
-      }
-      if (TB == 1 && kb2 >= MID) {      // products of the rows fetched at the top of this iteration
-#pragma unroll
-         for (int e = 0; e < PPI; e++) {
-            const int p = PPI * (kb2 - MID) + e;
-            if (p < NP) {
-               t[p >> 1][(2 * p) & 3] = tv[0][e].x * tw[0][e].x;
-               t[p >> 1][(2 * p + 1) & 3] = tv[0][e].y * tw[0][e].y;
-            }
-         }
+         for (int jb = 0; jb < RB; jb++) y[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kb2 & 1][jb].y, b1, y[jb], 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
    }
-   if constexpr (RT) {
-      double r = rt.r60;
-      r += __shfl_xor(r, 16);
-      r += __shfl_xor(r, 32);
-      y[3].w = lane < 16 ? y[3].w + r : 0.0;
-   }
 #pragma unroll
-   for (int e = 0; e < PPI && TB == 2; e++) {
+   for (int e = 0; e < PPI; e++) {
       const int p = PPI * (KB2 - 1 - MID) + e;
       if (p < NP) {
          t[p >> 1][(2 * p) & 3] = tv[(KB2 - 1) & 1][e].x * tw[(KB2 - 1) & 1][e].x;
@@ -646,17 +495,7 @@ __device__ __forceinline__ void jit_mul_mem(v4d (&y)[4], const double *sp)   // 
    }
 }
 
-// (JIT_STORE_MODE, experiments through PAML_AMD_JIT_STORE: 0 = nontemporal, 1 = plain, 2 = no store at all — timing only, the resident partials stay unwritten)
-#ifndef JIT_STORE_MODE
-#define JIT_STORE_MODE 0
-#endif
-#if JIT_STORE_MODE == 0
 #define JIT_STORE16(V, P) __builtin_nontemporal_store((V), (P))
-#elif JIT_STORE_MODE == 1
-#define JIT_STORE16(V, P) (*(P) = (V))
-#else
-#define JIT_STORE16(V, P) ((void)0)
-#endif
 // STORE / LOAD of a resident partial (keep-partials mode; layout: part_load / part_store above — element m of the partial is y[m >> 2][m & 3],
 // a lane's elements 2 i, 2 i + 1 one 16-byte access, a wave instruction 1 KB).  Compiler-visible memory operations, like the spills.
 // (streamed past the caches: 7 GB per evaluation at the benchmark's size would otherwise push the P(t) blocks and tip tables, re-read by
@@ -782,11 +621,7 @@ __device__ __forceinline__ void jit_root_lds(const PruneArgs &a, const v4d (&x)[
    if (q == 0 && valid) {
       // fx_r treesub.c:7731-7749 / lfun 7782-7798: the floor here, log + scale factors in the reduction kernel
       if (f <= 0) f = (a.mode == PAML_AMD_MODE_LFUN ? 1e-80 : 1e-300);
-#ifdef JIT_NT_STORE      // experiment: the class likelihoods streamed past L2 (nothing dirty left for the end-of-kernel release)
-      __builtin_nontemporal_store(flag ? f : 0.0, a.fhK + (long)iclass * a.n_patt + h);
-#else
       a.fhK[(long)iclass * a.n_patt + h] = flag ? f : 0.0;
-#endif
       if (a.n_scale) a.fscale[(long)iclass * a.n_patt + h] = lnscale;
    }
 }
@@ -1169,15 +1004,6 @@ __device__ __forceinline__ double m20_lds64(unsigned addr)
    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
    return v;
 }
-template <int K>
-__device__ __forceinline__ void m20_acol_asm(unsigned base, double (&A)[5])
-{
-   A[0] = m20_lds64<(0 * 20 + 4 * K) * 8>(base);
-   A[1] = m20_lds64<(4 * 20 + 4 * K) * 8>(base);
-   A[2] = m20_lds64<(8 * 20 + 4 * K) * 8>(base);
-   A[3] = m20_lds64<(12 * 20 + 4 * K) * 8>(base);
-   A[4] = m20_lds64<(16 * 20 + 4 * K) * 8>(base);
-}
 // wait until at most N LGKM operations are outstanding and tie the five values to the wait, so that nothing using them moves above it
 template <int N>
 __device__ __forceinline__ void m20_wait(double (&A)[5])
@@ -1185,36 +1011,7 @@ __device__ __forceinline__ void m20_wait(double (&A)[5])
    asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(A[0]), "+v"(A[1]), "+v"(A[2]), "+v"(A[3]), "+v"(A[4]) : "n"(N));
 }
 __device__ __forceinline__ unsigned m20_lds_addr(const double *p) { return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char *)p; }
-__device__ __forceinline__ void m20_acol(const double *sPn, int aoff, int K, double (&A)[5])
-{
-#pragma unroll
-   for (int I = 0; I < 5; I++) A[I] = sPn[aoff + (4 * I) * 20 + 4 * K];
-}
-template <int K>
-__device__ __forceinline__ void m20_column(const double (&A)[5], const double (&x0)[5], double (&y0)[5], const double (&x1)[5], double (&y1)[5])
-{
-#pragma unroll
-   for (int I = 0; I < 5; I++) {
-      y0[I] = M20_MFMA(A[I], x0[K], y0[I]);
-      y1[I] = M20_MFMA(A[I], x1[K], y1[I]);
-   }
-}
-__device__ __forceinline__ void m20_matvec2(const double *sPn, const double *sPnext, int aoff, double (&A0)[5], const double (&x0)[5], double (&y0)[5],
-                                            const double (&x1)[5], double (&y1)[5])
-{
-#pragma unroll
-   for (int I = 0; I < 5; I++) { y0[I] = 0; y1[I] = 0; }
-   const unsigned base = m20_lds_addr(sPn) + aoff * 8, nbase = m20_lds_addr(sPnext) + aoff * 8;
-   double A1[5];
-   m20_acol_asm<1>(base, A1);  m20_wait<5>(A0);  m20_column<0>(A0, x0, y0, x1, y1);
-   m20_acol_asm<2>(base, A0);  m20_wait<5>(A1);  m20_column<1>(A1, x0, y0, x1, y1);
-   m20_acol_asm<3>(base, A1);  m20_wait<5>(A0);  m20_column<2>(A0, x0, y0, x1, y1);
-   m20_acol_asm<4>(base, A0);  m20_wait<5>(A1);  m20_column<3>(A1, x0, y0, x1, y1);
-   m20_acol_asm<0>(nbase, A1); m20_wait<5>(A0);  m20_column<4>(A0, x0, y0, x1, y1);
-#pragma unroll
-   for (int I = 0; I < 5; I++) A0[I] = A1[I];      // the next product's first column, possibly still in flight: its wait comes first there
-}
-// ---- hybrid product (jit_generate_m20, default): rows 0-15 of P on v_mfma_f64_16x16x4 (one row block, no padding: its A operand
+// ---- hybrid product (jit_generate_m20): rows 0-15 of P on v_mfma_f64_16x16x4 (one row block, no padding: its A operand
 // is P[lane & 15][4 kb + (lane >> 4)], its accumulator tuple is blocks 0..3 of the partial), rows 16-19 on v_mfma_f64_4x4x4 as
 // above.  Same matrix-pipe time (5 x 64 + 5 x 16 cycles per 16 patterns = 25 x 16), but TEN operand fetches per product instead of
 // twenty-five: the LDS pipe, which the 4x4x4-only product kept 60 % busy (485 reads per 650 MFMAs with the tip rows, every one
@@ -1359,11 +1156,6 @@ __device__ __forceinline__ void m20h_matvec1x(const double *Pc, const double *Pn
 // 4 m + st are 40 contiguous bytes and the four lanes of a pattern read one 160-byte row
 __device__ __forceinline__ void m20_tip(const double *T, int row, int code, int st, double (&v)[5])      // row = doubles per code (20, or 21 in LDS)
 {
-#ifdef M20_ABL_NOTIP
-#pragma unroll
-   for (int m = 0; m < 5; m++) v[m] = 0.05 + 0.001 * code;
-   return;
-#endif
    const double *r = T + code * row + st * 5;
 #pragma unroll
    for (int m = 0; m < 5; m++) v[m] = r[m];

@@ -380,7 +380,7 @@ int paml_amd_eval_branch(paml_amd_engine *e, int node_b, int n_t, const double *
       // keep-partials evaluation — 128-pattern tiles, the operand ring — instead of the 64-pattern interpreter), compiled on the worker
       // thread while the interpreter serves, or at once when the caller asked for per-tree kernels.
       bool refill_done = false;
-      if (run_prog && e->jit_enabled && !e->env.force_gather && e->n_tips <= 207 && (e->n_codes <= 64 || e->amb_ascending)) {
+      if (run_prog && e->jit_enabled && e->n_tips <= 207 && (e->n_codes <= 64 || e->amb_ascending)) {
          int n_store = 0;
          for (const Op &o : prog.ops) n_store += o.code == OP_STORE;
          Program full = prog;
@@ -402,7 +402,7 @@ int paml_amd_eval_branch(paml_amd_engine *e, int node_b, int n_t, const double *
                   job = nullptr;
                }
                if (!have && !job && e->bjit_failed_key != key && (e->jit_forced || e->env.jit_sync || e->jit_count_request(key) >= 2)) {
-                  const std::string src = jit_generate(full, e->n_tips, n, e->n_codes, 8);
+                  const std::string src = jit_generate(full, e->n_tips, n, e->n_codes);
                   std::vector<char> code;
                   if (jit_cached_code(src, &code) || ((e->jit_forced || e->env.jit_sync) && jit_compile_code(src, &code, &e->err) == 0)) {
                      JitKernel nk;
@@ -474,14 +474,7 @@ int paml_amd_eval_branch(paml_amd_engine *e, int node_b, int n_t, const double *
       ea.eigen_of = e->d_eigen_of.p; ea.eigen = e->d_eigen.p; ea.code_mask = e->d_code_mask.p;
       ea.efrag = efrag; ea.ztab = ztab; ea.etab = e->d_bl_etab.p; ea.ecol = n == 61 ? e->d_bl_ecol.p + (size_t)lab_b * K * 128 : nullptr;
       hipLaunchKernelGGL(branch_eigprep_kernel, dim3(K), dim3(256), 0, st, ea);
-      // (timing experiments of profiles/r04_branch.txt — NOFEVAL, and NOSTORE / NOMFMA whose results are garbage — exist only in a library
-      //  built with PAML_AMD_EXTRA_FLAGS=-DPAML_AMD_BEIG_EXPERIMENTS; the production library does not read these variables)
-#ifdef PAML_AMD_BEIG_EXPERIMENTS
-      static const bool exp_nofeval = getenv("PAML_AMD_BEIG_NOFEVAL") != nullptr;
-#else
-      const bool exp_nofeval = false;
-#endif
-      const bool feval = !hit && K == 1 && n_t <= BEIG_NT && !exp_nofeval;
+      const bool feval = !hit && K == 1 && n_t <= BEIG_NT;
       e->bk_timed = false;
       if (e->profiling) {
          for (hipEvent_t &ev : e->ev_bk)
@@ -498,10 +491,6 @@ int paml_amd_eval_branch(paml_amd_engine *e, int node_b, int n_t, const double *
          ba.pint = e->d_pint.p; ba.ptip = e->d_ptip.p; ba.tip_words = (long)tip_words(e);
          ba.efrag = efrag; ba.ztab = ztab; ba.etab = e->d_bl_etab.p;
          ba.ecol = e->d_bl_ecol.p + (size_t)lab_b * K * 128; ba.pcol = e->d_pcol.p;
-#ifdef PAML_AMD_BEIG_EXPERIMENTS
-         static const int exp_abl = (getenv("PAML_AMD_BEIG_NOSTORE") ? 1 : 0) | (getenv("PAML_AMD_BEIG_NOMFMA") ? 2 : 0);
-         ba.no_store = exp_abl;
-#endif
          ba.freqK = e->d_freqK.p; ba.weights = e->d_weights.p; ba.coef = e->d_bl_coef.p; ba.partial = e->d_bpartial.p;
          const bool i0 = n_sons > 0 && !T.is_leaf(son[0]), i1 = n_sons > 1 && !T.is_leaf(son[1]);
          const int variant = n_sons == 0 ? 0 : (n_sons == 1 ? (i0 ? 1 : 2) : (i1 ? 3 : (i0 ? 4 : 5)));      // (two sons: the internal one, if any, comes first)

@@ -35,8 +35,7 @@ int paml_amd_create(paml_amd_engine **out, int n_states, int n_tips, int n_patt,
       e->jit_enabled = (flags & PAML_AMD_JIT) != 0 || (j && j[0] == '1') || (!j && (long)n_patt * max_classes >= 65536);
       e->jit_forced = (flags & PAML_AMD_JIT) != 0 || (j && j[0] == '1');
       if (j && j[0] == '0') e->jit_enabled = false;
-      const char *cj = getenv("PAML_AMD_COOPJIT");
-      e->coopj_enabled = !(j && j[0] == '0') && !(cj && cj[0] == '0');
+      e->coopj_enabled = !(j && j[0] == '0');
    }
    // 20 states: the specialised MFMA kernel trimmed to 2 row blocks x 5 k-blocks beats the scalar-operand kernel 2-3x; the
    // MFMA interpreters (64 MFMAs per product whatever n) do not, so small or keep-partials engines stay on valu20
@@ -47,21 +46,21 @@ int paml_amd_create(paml_amd_engine **out, int n_states, int n_tips, int n_patt,
    //  global memory: up to M20_MAX_TIPS taxa — measured at 60: 0.42 of the FP64 peak against the padded 16x16x4 kernel's 0.39; the
    //  packed tip codes of a unit live in registers, 64 VGPRs at 60 taxa, and beyond 64 taxa the walk would spill more than it gains)
    constexpr int M20_MAX_TIPS = 64;
-   e->want_m20 = n_states == 20 && e->jit_enabled && !(flags & PAML_AMD_KEEP_PARTIALS) && n_tips <= (getenv("PAML_AMD_M20_49") ? 49 : M20_MAX_TIPS) && !e->env.no_m20 && !e->env.valu20;
+   e->want_m20 = n_states == 20 && e->jit_enabled && !(flags & PAML_AMD_KEEP_PARTIALS) && n_tips <= M20_MAX_TIPS && !e->env.no_m20;
    // ... and SMALL 20-state data sets (at most 4096 patterns, round 4): what counts there is the length of one wave's walk, and the
    // cooperative form of the MFMA interpreter (prune_mfma64_coop: four waves per 16-pattern group, 16 MFMAs per wave and branch on
    // the zero-padded matrices) walks a branch in a sixth of the time of the scalar-operand kernel's 400 dependent FMAs per lane
    // (stewart.aa, 6 taxa x 98 patterns x 4 classes: 40 -> 22 us per evaluation, profiles/r04_small_timeline.txt)
    // (its sums are ordered differently from the scalar-operand kernel's: an engine that holds a SHARD of a larger alignment must not
    //  choose by its own size — PAML_AMD_SHARD; paml_amd_comm_init checks)
-   const bool small20 = n_states == 20 && !e->want_m20 && !(flags & (PAML_AMD_KEEP_PARTIALS | PAML_AMD_SHARD)) && n_patt <= 4096 && !e->env.valu20 && !e->env.no_coop;
+   const bool small20 = n_states == 20 && !e->want_m20 && !(flags & (PAML_AMD_KEEP_PARTIALS | PAML_AMD_SHARD)) && n_patt <= 4096 && !e->env.no_coop;
    e->small20 = small20;
-   const bool mfma20 = small20 || (n_states == 20 && !e->want_m20 && e->jit_enabled && !(flags & PAML_AMD_KEEP_PARTIALS) && n_tips <= 95 && !e->env.valu20);
+   const bool mfma20 = small20 || (n_states == 20 && !e->want_m20 && e->jit_enabled && !(flags & PAML_AMD_KEEP_PARTIALS) && n_tips <= 95);
    if (n_states == 4) e->kk = KK_VALU4;
    else if (n_states == 5) e->kk = KK_VALU5;
    else if (n_states == 20 && !mfma20) e->kk = KK_VALU20;
    else e->kk = KK_MFMA64;
-   e->mfma_dma = n_tips <= MFMA_ZT && !e->env.force_gather;
+   e->mfma_dma = n_tips <= MFMA_ZT;
    e->mfma_waves = e->mfma_dma ? DMA_WAVES : GATHER_WAVES;
    e->tile_patt = e->kk == KK_MFMA64 ? e->mfma_waves * 16 : 256;
    *out = e;
@@ -95,7 +94,7 @@ const char *paml_amd_kernel_name(const paml_amd_engine *e)
 {
    if (!e) return "";
    switch (e->kk) {
-   case KK_VALU4: return e->use_jit ? (e->fused ? (e->fused_mfma4 ? "mfma4_jit" : "valu4_fused_jit") : "valu4_jit") : "valu4";
+   case KK_VALU4: return e->use_jit ? (e->fused ? "valu4_fused_jit" : "valu4_jit") : "valu4";
    case KK_VALU5: return e->use_jit ? (e->fused ? "valu5_fused_jit" : "valu5_jit") : "valu5";
    case KK_VALU20: return e->use_jit ? (e->m20 ? "mfma4x20_jit" : "valu20_jit") : "valu20";
    default: return e->use_jit ? (e->jit_stage == 1 ? "mfma64_jit_quick" : "mfma64_jit") : (e->mfma_dma ? "mfma64_stream" : (e->coopj ? "mfma64_coopjit" : (e->coop ? "mfma64_coop" : "mfma64_gather")));
@@ -462,12 +461,11 @@ static int eigen_qrev_batch(paml_amd_engine *e, int n_sets, const int *set_ids, 
    static const int sweep_limit = getenv("PAML_AMD_EIGEN_SWEEP_LIMIT") ? std::max(1, atoi(getenv("PAML_AMD_EIGEN_SWEEP_LIMIT"))) : 40;
    a.max_sweeps = sweep_limit;
    if (e->eigen_warm) { a.R0 = dptr + 3 * (size_t)n_sets; a.Rout = dptr + 4 * (size_t)n_sets; }
-   // (the orders with a register form: R^T in a ninth wave's registers; PAML_AMD_EIGEN_LDS=1: the any-order form for them too)
-   static const bool lds_form = getenv("PAML_AMD_EIGEN_LDS") != nullptr;
+   // (the orders with a register form: R^T in a ninth wave's registers)
    const int N_even = ((int)n + 1) & ~1;
-   if (N_even == 62 && !lds_form) hipLaunchKernelGGL(eigen_qrev_kernel<62>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
-   else if (N_even == 60 && !lds_form) hipLaunchKernelGGL(eigen_qrev_kernel<60>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
-   else if (N_even == 20 && !lds_form) hipLaunchKernelGGL(eigen_qrev_kernel<20>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
+   if (N_even == 62) hipLaunchKernelGGL(eigen_qrev_kernel<62>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
+   else if (N_even == 60) hipLaunchKernelGGL(eigen_qrev_kernel<60>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
+   else if (N_even == 20) hipLaunchKernelGGL(eigen_qrev_kernel<20>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
    else hipLaunchKernelGGL(eigen_qrev_kernel<0>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
    HIPCHK(hipGetLastError());
    // (the host arrays were pageable: the runtime has staged them on return; the evaluations that follow on the engine's stream see the sets)
@@ -660,7 +658,7 @@ int paml_amd_get_pmat(paml_amd_engine *e, int gene, int iclass, int node, double
    // (... which holds for every code table the reference builds — the states come first — but is the caller's choice at this boundary)
    if (e->plain_codes < n)
       return fail(e, PAML_AMD_EUNSUPPORTED, "get_pmat: a tip branch's matrix is rebuilt from the tip's column table, which needs the codes 0 .. n-1 to be the "
-                                            "single states (set_tips); PAML_AMD_PMAT_ROWMAJOR=1 keeps the row-major copies");
+                                            "single states (set_tips)");
    const size_t tw = tip_words(e);
    std::vector<double> tab(tw);
    HIPCHK(hipMemcpyAsync(tab.data(), e->d_ptip.p + slot * tw, tw * sizeof(double), hipMemcpyDeviceToHost, e->stream));

@@ -100,11 +100,10 @@ static void launch_valu(paml_amd_engine *e, int max_stack, int n_blocks, const P
 }
 
 // 21..64 states in the mfma64 layout, every eigen system a (U, V, Root) one: four workgroups per matrix on the matrix cores
-// (pmat_mfma_kernel; PAML_AMD_PMAT_MFMA=0: pmat_kernel_t<64>, one workgroup per matrix on the vector units)
+// (pmat_mfma_kernel)
 bool pmat_on_matrix_cores(const paml_amd_engine *e, const PmatArgs &pa)
 {
-   static const bool off = getenv("PAML_AMD_PMAT_MFMA") && atoi(getenv("PAML_AMD_PMAT_MFMA")) == 0;
-   bool ok = e->kk == KK_MFMA64 && pa.layout == 1 && e->n_codes <= 256 && !off;
+   bool ok = e->kk == KK_MFMA64 && pa.layout == 1 && e->n_codes <= 256;
    for (const EigenHost &h : e->eigen) ok = ok && (h.kind == PAML_AMD_EIGEN_UVROOT || h.kind < 0);      // (< 0: an id never set, referred to by nothing)
    return ok;
 }
@@ -113,12 +112,11 @@ void launch_pmat(const PmatArgs &pa, const InlineVec &iv, int n_nodes, int psets
 {
    const int gx = (n_nodes + std::max(pa.npb, 1) - 1) / std::max(pa.npb, 1);
    if (mfma) {
-      static const int nt_env = getenv("PAML_AMD_PMAT_NT") ? atoi(getenv("PAML_AMD_PMAT_NT")) : -1;      // (experiments: 0 / 1 for every launch)
-      if (nt_env >= 0 ? nt_env != 0 : (long)n_nodes * psets >= 128) hipLaunchKernelGGL(pmat_mfma_kernel<true>, dim3(n_nodes, psets, 4), dim3(256), 0, s, pa, iv);
+      if ((long)n_nodes * psets >= 128) hipLaunchKernelGGL(pmat_mfma_kernel<true>, dim3(n_nodes, psets, 4), dim3(256), 0, s, pa, iv);
       else hipLaunchKernelGGL(pmat_mfma_kernel<false>, dim3(n_nodes, psets, 4), dim3(256), 0, s, pa, iv);
    }
    else if (small) hipLaunchKernelGGL(pmat_small_kernel, dim3((n_nodes * psets + 7) / 8), dim3(256), 0, s, pa, iv);
-   else if (pa.n <= 32 && pa.layout != 1 && pa.layout != 3) hipLaunchKernelGGL(pmat_kernel_t<32>, dim3(gx, psets), dim3(256), 2 * 32 * 32 * sizeof(double), s, pa, iv);
+   else if (pa.n <= 32 && pa.layout != 1) hipLaunchKernelGGL(pmat_kernel_t<32>, dim3(gx, psets), dim3(256), 2 * 32 * 32 * sizeof(double), s, pa, iv);
    else hipLaunchKernelGGL(pmat_kernel_t<64>, dim3(gx, psets), dim3(256), 2 * 4096 * sizeof(double), s, pa, iv);
 }
 
@@ -187,7 +185,7 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
    // (worth its event traffic only where the pruning kernel is long: the 21..64-state kernels and the 20-state matrix-core kernel on
    //  >= 10^5 pattern-classes)
    want_pipe = want_pipe && (e->kk == KK_MFMA64 || (e->kk == KK_VALU20 && e->want_m20)) && (long)e->n_patt * e->K >= 100000;
-   const bool pipe = want_pipe && e->pipe_ok && !bs && !clean && !keep && !new_prog && !e->eigen_dirty && !e->env.no_pipeline;
+   const bool pipe = want_pipe && e->pipe_ok && !bs && !clean && !keep && !new_prog && !e->eigen_dirty;
    // Two pruning streams (paml_amd_engine::sb): from the second evaluation of such a run on, the evaluations alternate between the
    // engine's stream and `sb`, so that the persistent workgroups of evaluation i + 1 take the CUs as those of evaluation i leave
    // them — no kernel boundary, reduction or half-empty last round of tiles between two pruning kernels.  lane = reduction slot.
@@ -307,27 +305,26 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
    //   stream — the interpreter over the same operand stream (lean programs only), 128 patterns per workgroup
    //   gather — the full interpreter (keep-partials STORE/LOAD, deep stacks, > MFMA_ZT tips, > 64 codes), 64 per workgroup
    if (e->kk == KK_MFMA64) {
-      bool lean = e->prog.max_stack <= MFMA_RS && e->n_tips <= MFMA_ZT && e->n_codes <= 64 && !e->env.force_gather;
+      bool lean = e->prog.max_stack <= MFMA_RS && e->n_tips <= MFMA_ZT && e->n_codes <= 64;
       // small data sets (at most a quarter of the CUs get a 128-pattern tile): the 64-pattern workgroups of the gather kernel —
       // one wave per SIMD, twice as many workgroups — finish a tile in 0.63 of the time (13 taxa x 79 codon patterns: 42 against 66 us,
       // a batched gradient of 25 evaluations 0.125 against 0.151 ms; profiles/r02_small_latency.jsonl)
-      if ((e->n_patt + 127) / 128 <= e->n_cu / 4 && !e->env.force_stream) lean = false;
+      if ((e->n_patt + 127) / 128 <= e->n_cu / 4) lean = false;
       for (const Op &o : e->prog.ops)
          if (o.code == OP_PUSH || o.code == OP_SCALE || o.code == OP_STORE || o.code == OP_LOAD) lean = false;
       bool jit_ok = false;
-      // waves per workgroup of the per-tree kernel: 8 (two per SIMD, 128 patterns per tile).  PAML_AMD_JIT_WAVES=12 builds the
-      // three-per-SIMD variant (192-pattern tiles, <= 168 VGPRs): measured SLOWER on MI355X (1.659 against 1.622 ms at C4, 4.73 against
-      // 4.63 ms with three classes — 40 spilled dwords and a third more LDS / DMA traffic per step), kept as a generator parameter
-      int jw = 8;
-      if (e->env.jit_waves == 12 && jit_supported(e->prog, e->n_tips, e->n_codes, e->n_pi, 6, 192) && jit_zbuffers(e->n_tips, 192) == 2) jw = 12;
+      // waves per workgroup of the per-tree kernel: 8 (two per SIMD, 128 patterns per tile).  The three-per-SIMD variant (192-pattern
+      // tiles, <= 168 VGPRs) measured SLOWER on MI355X (1.659 against 1.622 ms at C4, 4.73 against 4.63 ms with three classes — 40
+      // spilled dwords and a third more LDS / DMA traffic per step) and was removed
+      const int jw = 8;
       // (more than 64 codes: the per-tree kernel sums the rows of a code's states in ascending order — e->amb_ascending, set_tips)
       // LOAD programs (paml_amd_eval_dirty: one per set of clean nodes) get a kernel too (round 6) — compiled on the worker thread from the
       // SECOND time a set is asked for (minbranches' walk repeats its sets cycle after cycle; a set seen once is not worth 0.5 s of compiler),
       // the interpreter serving meanwhile; code-block pieces follow one program's order, so trees beyond 207 tips keep the interpreter there
       bool has_load = false;
       for (const Op &o : e->prog.ops) has_load = has_load || o.code == OP_LOAD;
-      if (e->jit_enabled && !e->env.force_gather && !(has_load && e->n_tips > 207) && (e->n_codes <= 64 || e->amb_ascending) && jit_supported(e->prog, e->n_tips, e->n_codes, e->n_pi, 6, jw * 16, true)) {
-         const std::string key = "m" + std::to_string(n) + "c" + std::to_string(e->n_codes) + "w" + std::to_string(jw) + (jit_rowtail(n) ? "r:" : ":") + jit_program_key(e->prog, e->n_tips);
+      if (e->jit_enabled && !(has_load && e->n_tips > 207) && (e->n_codes <= 64 || e->amb_ascending) && jit_supported(e->prog, e->n_tips, e->n_codes, e->n_pi, 6, jw * 16, true)) {
+         const std::string key = "m" + std::to_string(n) + "c" + std::to_string(e->n_codes) + "w" + std::to_string(jw) + ":" + jit_program_key(e->prog, e->n_tips);
          // Large trees (> 120 ops: roughly more than 35 taxa): tens of thousands of instructions, many seconds of compiler time.  Unless the
          // caller asked to wait (PAML_AMD_JIT flag / PAML_AMD_JIT_SYNC), the kernel is built on a worker thread while the interpreter kernels
          // serve, and the engine changes over when the code object is there; one found on disk is loaded at once.  Round 5: the generator
@@ -339,7 +336,7 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
          const bool wanted = !has_load || e->jit_forced || e->env.jit_sync || e->jit_recall(key) || e->jit_count_request(key) >= 2;
          if (!wanted) jit_ok = false;
          else if (!background) {
-            int r = ensure_jit(e, key, [&]() { return jit_strip_big(jit_generate(e->prog, e->n_tips, n, e->n_codes, jw)); }, &jit_ok);
+            int r = ensure_jit(e, key, [&]() { return jit_strip_big(jit_generate(e->prog, e->n_tips, n, e->n_codes)); }, &jit_ok);
             if (r) return r;
             if (jit_ok) { e->jit_stage = 2; e->jit.stage = 2; }
          }
@@ -377,10 +374,10 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
             }
             auto may_build = [&](int stage) { return (stage == 1 ? e->jit_failed_key : e->jit_stage2_failed_key) != key; };
             // two-stage build (generators without block splits only): the quick kernel first, the full one replaces it; else the one build
-            const bool two = jit_split_mode(e->prog.ops.size()) != 2 && !getenv("PAML_AMD_JIT_ONE_STAGE");
+            const bool two = jit_split_mode(e->prog.ops.size()) != 2;
             const int next = (e->jit_stage == 0 && two && may_build(1)) ? 1 : 2;
             if (!job && e->jit_stage < 2 && may_build(next)) {
-               const std::string quick = jit_generate(e->prog, e->n_tips, n, e->n_codes, jw), full = jit_strip_big(quick);
+               const std::string quick = jit_generate(e->prog, e->n_tips, n, e->n_codes), full = jit_strip_big(quick);
                std::vector<char> code;
                if (e->jit_stage == 0) {      // a code object on disk is loaded at once
                   if (may_build(2) && jit_cached_code(full, &code)) { if (!load(code, 2)) e->jit_stage2_failed_key = key; }
@@ -417,16 +414,11 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
          // the profiler (within 4 % of it under rocprofv3, equal instruction counts) was bisected to the table fill living inside the
          // chunk loop and not resolved: profiles/r06_genes_4state.txt.  PAML_AMD_VF_GENES=1 switches it on (tests, measurements).
          const bool vf_genes = getenv("PAML_AMD_VF_GENES") && atoi(getenv("PAML_AMD_VF_GENES")) != 0;      // (read per call: tests switch it)
-         if (pl.ok && (G == 1 ? e->n_pi == 1 : (vf_genes && (e->n_pi == 1 || e->n_pi == G))) && e->d_zpm.p && !e->env.no_fused && !(G > 1 && n == 4 && e->env.mfma4) && G <= 64) {
-            // 4 states: the matrix-core form (v_mfma_f64_4x4x4) is an experiment kept behind PAML_AMD_MFMA4=1 — same issue slots as
-            // the FMA form (an FP64 MFMA of 256 MACs takes 16 cycles, sixteen v_fma_f64 of a wave 64) and four times the
-            // integer work per pattern (a lane is a (state, pattern) pair): 0.32 of peak against 0.64, profiles/r02_valu_fused_shapes.txt
-            const bool m4 = n == 4 && e->env.mfma4;
-            int r = ensure_jit(e, std::string(m4 ? "m4" : "vf") + std::to_string(n) + "c" + std::to_string(e->n_codes) + "k" + std::to_string(Km) + "r" + std::to_string(pl.R) + "w" +
+         if (pl.ok && (G == 1 ? e->n_pi == 1 : (vf_genes && (e->n_pi == 1 || e->n_pi == G))) && e->d_zpm.p && G <= 64) {
+            // (4 states: a matrix-core form (v_mfma_f64_4x4x4) was correct but slower, 0.32 of peak against 0.64: profiles/r02_valu_fused_shapes.txt)
+            int r = ensure_jit(e, std::string("vf") + std::to_string(n) + "c" + std::to_string(e->n_codes) + "k" + std::to_string(Km) + "r" + std::to_string(pl.R) + "w" +
                                      std::to_string(pl.CW) + (pl.cherry ? "y" : "n") + (G > 1 ? "g" + std::to_string(G) + ":" : ":") + jit_program_key(e->prog, e->n_tips),
-                               [&]() { return m4 ? jit_generate_mfma4(e->prog, e->n_tips, e->n_codes, Km, e->chunk)
-                                                 : jit_generate_valu_fused(e->prog, n, e->n_tips, e->n_codes, Km, e->chunk, G); }, &jit_ok);
-            e->fused_mfma4 = jit_ok && m4;
+                               [&]() { return jit_generate_valu_fused(e->prog, n, e->n_tips, e->n_codes, Km, e->chunk, G); }, &jit_ok);
             if (r) return r;
             fused = jit_ok;
             e->fused_threads = 256 * pl.CW;
@@ -439,7 +431,7 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
       }
       e->m20 = false;
       if (e->want_m20 && !clean && jit_m20_supported(e->prog, e->n_tips, G)) {
-         int r = ensure_jit(e, std::string(getenv("PAML_AMD_M20_W12") ? "m20w12c" : getenv("PAML_AMD_M20_HALF") ? "m20hc" : "m20c") + std::to_string(e->n_codes) + (G > 1 ? "g:" : ":") + jit_program_key(e->prog, e->n_tips), [&]() { return jit_generate_m20(e->prog, e->n_tips, e->n_codes, G > 1 ? 2 : 1); }, &jit_ok);
+         int r = ensure_jit(e, std::string("m20c") + std::to_string(e->n_codes) + (G > 1 ? "g:" : ":") + jit_program_key(e->prog, e->n_tips), [&]() { return jit_generate_m20(e->prog, e->n_tips, e->n_codes, G > 1 ? 2 : 1); }, &jit_ok);
          if (r) return r;
          e->m20 = jit_ok;
       }
@@ -520,7 +512,7 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
    // Kernel A: batched P(t)
    PmatArgs pa{};
    pa.n = n; pa.n_nodes = nn; pa.root = e->tree.root; pa.K = Km; pa.n_genes = G; pa.n_labels = e->n_labels;
-   pa.n_codes = e->n_codes; pa.layout = e->kk == KK_MFMA64 ? ((e->use_jit && jit_rowtail(n)) ? 3 : 1) : ((e->kk == KK_VALU20 && e->use_jit && e->m20) ? 2 : 0);
+   pa.n_codes = e->n_codes; pa.layout = e->kk == KK_MFMA64 ? 1 : ((e->kk == KK_VALU20 && e->use_jit && e->m20) ? 2 : 0);
    pa.label = e->d_label.p; pa.is_leaf = e->d_is_leaf.p; pa.branch = pipe ? e->d2_branch.p : e->d_branch.p; pa.rate = e->d_rate.p;
    pa.gene_rate = pipe ? e->d2_gene_rate.p : e->d_gene_rate.p; pa.eigen_of = e->d_eigen_of.p; pa.qfactor = e->d_qfactor.p;
    pa.eigen = e->d_eigen.p; pa.n_chara = e->d_n_chara.p; pa.chara_map = e->d_chara_map.p; pa.plain_codes = e->plain_codes;
@@ -529,17 +521,12 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
    if (bs && bs->eigen_of) { pa.eigen_of = e->d_b_eigen_of.p; pa.eigen_of_bs = (long)G * Km * e->n_labels; }
    if (bs && bs->qfactor) { pa.qfactor = e->d_b_qfactor.p; pa.qfactor_bs = (long)Km * e->n_labels; }
    pa.rate_gs = e->rate_per_gene ? Km : 0;
-   // PAML_AMD_PMAT_NPB=n (experiment): in a run of evaluations, where P(t) is built ahead on the side stream with the few CUs the
-   // pruning kernels leave it, n nodes per workgroup with the eigen vectors kept on chip from node to node.  Measured on MI355X with
-   // n = 8: 20 states 0.1887 against 0.1884 ms per evaluation, 61 states SLOWER (0.211 against 0.203 ms at the 8-GPU shard size,
-   // 1.547 against 1.534 at 10^6 patterns: fewer workgroups, each eight times longer, and the pruning kernel waits for the last)
-   static const int npb_run = getenv("PAML_AMD_PMAT_NPB") ? atoi(getenv("PAML_AMD_PMAT_NPB")) : 1;
-   pa.npb = pipe ? npb_run : 1;
+   // (several nodes per workgroup in a run of evaluations: 20 states no faster, 61 states slower, 0.211 against 0.203 ms at the 8-GPU shard size)
+   pa.npb = 1;
    if (bs && bs->rate) { pa.rate = e->d_b_rate.p; pa.rate_bs = e->rate_per_gene ? (long)G * Km : Km; }
    const bool pmat_mfma = pmat_on_matrix_cores(e, pa);
    // ... on the matrix cores in the mfma64 layout nobody reads the row-major copy (paml_amd_get_pmat rebuilds P from the operand-order ones)
-   static const bool want_rowmajor = getenv("PAML_AMD_PMAT_ROWMAJOR") != nullptr;
-   if (pmat_mfma && pa.layout == 1 && !want_rowmajor) pa.rowmajor = nullptr;
+   if (pmat_mfma && pa.layout == 1) pa.rowmajor = nullptr;
    e->rowmajor_valid = pa.rowmajor != nullptr;
    e->pmat_B = B;
    // ... and single evaluations get label -> eigen_of -> eigen set -> U / V / Root resolved on the host (PmatArgs::res)
@@ -663,8 +650,8 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
       pr.lnf = want_lnf ? e->d_lnf.p : nullptr;
       pr.red_partial = dpart.p; pr.red_out = lnl_out; pr.nb_local = nb;
       if (int rc = wait_slot()) return rc;      // (this kernel writes the partial sums itself)
-      // the total: a one-block stage-2 launch (default), or PAML_AMD_TAIL=1: the workgroup that finishes last forms it (tickets)
-      pr.red_counter = (e->comm || !e->env.tail) ? nullptr : e->d_red_counter.p;
+      // the total: a one-block stage-2 launch
+      pr.red_counter = nullptr;
       if (coopj) pr.red_counter = e->d_red_counter.p;      // (the cooperative per-tree kernel: always the last workgroup, of each batch element)
    }
    const int prof_stride = std::max((int)e->prog.ops.size() + 3, e->env.prof_tiles ? 96 : 0);      // experiments only
@@ -725,7 +712,7 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
          // single evaluations: one workgroup per chunk; batched ones: about two resident workgroups per CU in all, each walking every
          // gx-th chunk of its element (the LDS tables of an element's P(t) are filled once per workgroup, not once per 256 patterns)
          int gx = nb;
-         if (B > 1 && !pr.red_counter && !e->fused_mfma4) gx = std::max(1, std::min(nb, 2 * e->n_cu / B));
+         if (B > 1) gx = std::max(1, std::min(nb, 2 * e->n_cu / B));
          HIPCHK(hipModuleLaunchKernel(e->jit.fn, gx, B, 1, e->fused_threads, 1, 1, 0, ms, params, nullptr));
       }
       else if (e->use_jit && e->m20) {      // persistent: a multiple of the class count, every workgroup keeps its class's P(t) in LDS
@@ -742,9 +729,8 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
             auto rounds = [&](int g) { return ((units + g / K - 1) / (g / K) + 7) / 8; };
             if (g78 >= K && g78 < grid && rounds(g78) == rounds(grid)) grid = g78;
          }
-         static const int m20_threads = getenv("PAML_AMD_M20_W12") ? 768 : 512;      // (experiment: jit_generate_m20)
          // (several genes: a workgroup serves one (gene, class); the kernel deals a class's workgroups to the genes, at least one each)
-         HIPCHK(hipModuleLaunchKernel(e->jit.fn, std::max(grid / K, G > 1 ? G : 1) * K, 1, 1, m20_threads, 1, 1, 0, ms, params, nullptr));
+         HIPCHK(hipModuleLaunchKernel(e->jit.fn, std::max(grid / K, G > 1 ? G : 1) * K, 1, 1, 512, 1, 1, 0, ms, params, nullptr));
       }
       else if (e->use_jit) {
          void *params[] = {&pr};
@@ -778,8 +764,7 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
 
    // Kernel C: mixture + log + weighted sum.  Stage 1 leaves one partial sum per chunk of patterns at the chunk's global
    // position; with a communicator the ranks' (disjoint, zero elsewhere) arrays are summed over RCCL — adding zeros is exact,
-   // so every rank then holds the same array whatever the number of ranks — and stage 2 adds it up in a fixed order.  On one
-   // GPU the workgroup that finishes last forms the total itself (red_block_finish): no second launch.
+   // so every rank then holds the same array whatever the number of ranks — and stage 2 adds it up in a fixed order.
    ReduceArgs ra{};
    ra.fhK = dfhk.p; ra.weights = e->d_weights.p; ra.freqK = e->d_freqK.p; ra.lnf = want_lnf ? e->d_lnf.p : nullptr;
    ra.partial = dpart.p; ra.out = lnl_out;
@@ -788,8 +773,6 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
    ra.first_chunk = e->first_chunk; ra.nb_stride = nbg;
    // (measured on MI355X, 32 taxa x 10^5 nucleotide patterns: 28.2 us per evaluation with the separate one-block launch against
    //  30.2 with tickets — the agent-scope store + two atomics + coherent reads cross the XCDs' L2s and cost more than a launch)
-   const bool tail = !side_total && !offload && e->env.tail;
-   ra.counter = tail ? e->d_red_counter.p : nullptr;
    if (bs && bs->freqK) { ra.freqK = e->d_b_freqK.p; ra.freqK_bs = Km; }
    hipStream_t rs = ms;      // the stream of the reduction
    if (offload) {
@@ -820,7 +803,7 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
       }
       hipLaunchKernelGGL(reduce_stage2, dim3(B), dim3(256), 0, e->sc, (const double *)dtot.p, nbg, ra.out);
    }
-   else if (!tail && nbg > 1 && !coopj) hipLaunchKernelGGL(reduce_stage2, dim3(B), dim3(256), 0, rs, (const double *)dpart.p, nbg, ra.out);      // (one block per element: stage 1 wrote the total)
+   else if (nbg > 1 && !coopj) hipLaunchKernelGGL(reduce_stage2, dim3(B), dim3(256), 0, rs, (const double *)dpart.p, nbg, ra.out);      // (one block per element: stage 1 wrote the total)
    if (side_total || offload) {
       if (e->comm_stats && side_total) { HIPCHK(hipEventRecord(e->st_done[e->st_count % paml_amd_engine::NSTAT], e->sc)); e->st_count++; }
       HIPCHK(hipEventRecord(e->ev_done[slot], e->sc));

@@ -64,18 +64,15 @@ int paml_amd_debug_jit(int n_tips, int n_nodes, int root, const int *sons_ptr, c
    else if (fusedK) {
       const int chunk = (compile_all >> 2) & 0x3f ? ((compile_all >> 2) & 0x3f) * 256 : 256;      // bits 2..7: reduction chunk / 256
       if (!jit_valu_fused_plan(p, n_states, n_tips, fusedNC, fusedK, chunk).ok) return PAML_AMD_EUNSUPPORTED;
-      text = (n_states == 4 && getenv("PAML_AMD_MFMA4")) ? jit_generate_mfma4(p, n_tips, fusedNC, fusedK, chunk)
-                                                              : jit_generate_valu_fused(p, n_states, n_tips, fusedNC, fusedK, chunk, prebuild_genes());
+      text = jit_generate_valu_fused(p, n_states, n_tips, fusedNC, fusedK, chunk, prebuild_genes());
    }
    else if (n_states == 4 || n_states == 5 || n_states == 20) {
       if (!jit_valu_supported(p)) return PAML_AMD_EUNSUPPORTED;
       text = jit_generate_valu(p, n_states);
    }
    else {
-      int jw = 8;
-      if (const char *v = getenv("PAML_AMD_JIT_WAVES")) if (atoi(v) == 12 && jit_zbuffers(n_tips, 192) == 2) jw = 12;
-      if (!jit_supported(p, n_tips, 61, 1, 6, jw * 16)) return PAML_AMD_EUNSUPPORTED;
-      text = jit_generate(p, n_tips, 61, 64, jw);
+      if (!jit_supported(p, n_tips, 61)) return PAML_AMD_EUNSUPPORTED;
+      text = jit_generate(p, n_tips, 61, 64);
    }
    int rc = (int)text.size();
    if (compile) {
@@ -123,14 +120,11 @@ int paml_amd_jit_prebuild(int n_states, int n_tips, int n_codes, int K, long n_p
       if (!jit_valu_supported(p)) return PAML_AMD_EUNSUPPORTED;
       const int chunk = red_chunk(n_patt_global);
       text = !jit_valu_fused_plan(p, n_states, n_tips, n_codes, K, chunk).ok ? jit_generate_valu(p, n_states)
-             : (n_states == 4 && getenv("PAML_AMD_MFMA4"))                     ? jit_generate_mfma4(p, n_tips, n_codes, K, chunk)
                                                                                : jit_generate_valu_fused(p, n_states, n_tips, n_codes, K, chunk, prebuild_genes());
    }
    else {
-      int jw = 8;
-      if (const char *v = getenv("PAML_AMD_JIT_WAVES")) if (atoi(v) == 12 && jit_zbuffers(n_tips, 192) == 2) jw = 12;
-      if (!jit_supported(p, n_tips, n_codes, 1, 6, jw * 16)) return PAML_AMD_EUNSUPPORTED;
-      text = jit_generate(p, n_tips, n_states, n_codes, jw);
+      if (!jit_supported(p, n_tips, n_codes)) return PAML_AMD_EUNSUPPORTED;
+      text = jit_generate(p, n_tips, n_states, n_codes);
       if (!getenv("PAML_AMD_PREBUILD_QUICK")) text = jit_strip_big(text);      // (large trees: the full build, what an engine looks for first)
    }
    if (const char *dump = getenv("PAML_AMD_JIT_DUMP")) {

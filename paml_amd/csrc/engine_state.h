@@ -162,39 +162,30 @@ inline int red_chunk(long n_global) { return (int)std::max<long>(256, ((n_global
 
 // Environment switches, read once when the engine is created.
 struct EnvCfg {
-   bool force_stream = false;
    bool offload = false;
    bool dual = true;
    bool no_coef_cache = false;      // PAML_AMD_NO_COEF_CACHE (measurements): every eval_branch call forms the coefficients again
    bool no_branch_eig = false;      // PAML_AMD_NO_BRANCH_EIG: eval_branch in the P / dP / ddP form (round 2's kernels) also where the eigen-basis form applies
    bool no_coop = false;            // PAML_AMD_COOP=0: small data sets on the gather kernel (one wave per 16-pattern group) instead of prune_mfma64_coop
-   bool no_pipeline = false, force_gather = false, jit_sync = false, jit_strict = false, valu20 = false, no_fused = false, mfma4 = false, tail = false, no_m20 = false;
-   int jit_waves = 0, comm_cus = -1, lanes = 0;
+   bool jit_sync = false, jit_strict = false, no_m20 = false;
+   int comm_cus = -1, lanes = 0;
    std::string jit_dump, prof_ops;
    int prof_tid = 0;
    bool prof_tiles = false;      // the dump is a workgroup timeline (jit.h proft) instead of per-op stamps
    bool comm_stats = false;
    void read()
    {
-      no_pipeline = getenv("PAML_AMD_NO_PIPELINE") != nullptr;
       if (const char *v = getenv("PAML_AMD_COOP")) no_coop = atoi(v) == 0;
       offload = getenv("PAML_AMD_OFFLOAD") != nullptr;      // experiment (measured no faster, profiles/r03_comm_overhead.txt): the reduction of eval_device on the side stream
       if (const char *v = getenv("PAML_AMD_DUAL")) dual = atoi(v) != 0;      // 0: one pruning stream (consecutive evaluations' kernels never overlap)
-      force_gather = getenv("PAML_AMD_FORCE_GATHER") != nullptr;
-      force_stream = getenv("PAML_AMD_FORCE_STREAM") != nullptr;      // experiments: the stream interpreter also on small data sets
       jit_sync = getenv("PAML_AMD_JIT_SYNC") != nullptr;
       jit_strict = getenv("PAML_AMD_JIT_STRICT") != nullptr;
-      valu20 = getenv("PAML_AMD_VALU20") != nullptr;
-      no_fused = getenv("PAML_AMD_NO_FUSED") != nullptr;
-      mfma4 = getenv("PAML_AMD_MFMA4") != nullptr;
       no_m20 = getenv("PAML_AMD_NO_M20") != nullptr;
       no_branch_eig = getenv("PAML_AMD_NO_BRANCH_EIG") != nullptr;
       no_coef_cache = getenv("PAML_AMD_NO_COEF_CACHE") != nullptr;
-      tail = getenv("PAML_AMD_TAIL") != nullptr;
       if (const char *v = getenv("PAML_AMD_COMM_CUS")) comm_cus = atoi(v);
       comm_stats = getenv("PAML_AMD_COMM_STATS") != nullptr;
       if (const char *v = getenv("PAML_AMD_LANES")) lanes = atoi(v);      // evaluations of a run in flight at once (2 .. 4; default 2: three measured 5 % slower, four 25 %)
-      if (const char *v = getenv("PAML_AMD_JIT_WAVES")) jit_waves = atoi(v);        // experiment: the last workgroup forms the total instead of a stage-2 launch
       if (const char *v = getenv("PAML_AMD_JIT_DUMP")) jit_dump = v;
       if (const char *v = getenv("PAML_AMD_PROF_OPS")) prof_ops = v;
       if (const char *v = getenv("PAML_AMD_PROF_TID")) prof_tid = atoi(v);
@@ -292,7 +283,6 @@ struct paml_amd_engine {
    double *h_out = nullptr;           // pinned, device-visible: the synchronous entry points have lnL written straight to the host
    size_t h_out_cap = 0;
    bool fused = false;                // the selected kernel forms the reduction itself
-   bool fused_mfma4 = false;
    bool rate_per_gene = false;      // paml_amd_set_gene_class_rates: class rates [n_genes][K]
    std::vector<double> class_rate;  // the [K] rates of set_classes (what set_gene_class_rates(NULL) goes back to)
    bool want_m20 = false, m20 = false;      // 20 states on v_mfma_f64_4x4x4 (jit_generate_m20)
@@ -404,7 +394,7 @@ struct paml_amd_engine {
    // ... or its per-tree form with the reduction inside (jit.h: jit_generate_coop).  A module of its own: an engine goes back and forth
    // between it (an evaluation, a small batch) and the interpreters (a batched gradient too large for one 16-pattern group per CU).
    // The kernel is compiled on a worker thread unless its code object is already on disk (lib/jit or the user's cache) or the caller
-   // asked to wait (PAML_AMD_JIT flag / PAML_AMD_JIT_SYNC); the interpreter form serves until it is there.  PAML_AMD_COOPJIT=0 / PAML_AMD_JIT=0: never.
+   // asked to wait (PAML_AMD_JIT flag / PAML_AMD_JIT_SYNC); the interpreter form serves until it is there.  PAML_AMD_JIT=0: never.
    JitKernel jit_coop;
    bool coopj = false, coopj_enabled = true;
    // Consecutive paml_amd_eval_device calls (the loop of a benchmark or of an optimiser's independent evaluations) build the
@@ -630,7 +620,7 @@ inline void mark(paml_amd_engine *e) { mark_on(e, e->stream); }
 inline hipError_t create_engine_stream(hipStream_t *s)
 {
    int least = 0, greatest = 0;
-   if (getenv("PAML_AMD_STREAM_PRIO_NORMAL") || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess)      // (experiments)
+   if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess)
       return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
    if (hipStreamCreateWithPriority(s, hipStreamNonBlocking, greatest) == hipSuccess) return hipSuccess;
    (void)hipGetLastError();

@@ -147,24 +147,7 @@ inline bool jit_supported(const Program &p, int n_tips, int n_codes, int n_pi = 
    return true;
 }
 
-// 61 states: rows 48..60 of every product without the padded rows 61..63 (device_common.h, JitRowTail; pmat_kernel layout 3) —
-// built and measured in round 4 (profiles/r04_61state.txt): bit-compatible results, 6 % fewer matrix-pipe cycles per product, and
-// no faster (1.573 against 1.569 ms at 16 taxa x 10^6 patterns): the 45 extra operand fetches, the row-60 dot product and their waits
-// take out of the shared issue port what the dropped rows put in.  Kept behind PAML_AMD_JIT_ROWTAIL=1; the default is the
-// four-row-block form.
-// Timing experiments whose kernels compute garbage (ablations: no barriers, no rank-1 seed, skewed waves, resident partials not stored,
-// tip factors / operands left out): read only by a library built with -DPAML_AMD_JIT_EXPERIMENTS (PAML_AMD_EXTRA_FLAGS + engine.build(),
-// tools/build_variant.sh); a production library ignores the variables.
-inline const char *jit_experiment_env(const char *name)
-{
-#ifdef PAML_AMD_JIT_EXPERIMENTS
-   return getenv(name);
-#else
-   (void)name;
-   return nullptr;
-#endif
-}
-inline bool jit_rowtail(int n_states) { return n_states == 61 && getenv("PAML_AMD_JIT_ROWTAIL") && !getenv("PAML_AMD_JIT_NOTAIL"); }
+// (61 states: rows 48..60 of every product without the padded rows 61..63: no faster, 1.573 against 1.569 ms, profiles/r04_61state.txt)
 
 inline std::string jit_program_key(const Program &p, int n_tips)
 {
@@ -197,9 +180,10 @@ inline int jit_split_mode(size_t nops)
    if (const char *v = getenv("PAML_AMD_JIT_SPLIT")) return !strcmp(v, "asm") ? 1 : !strcmp(v, "br") ? 2 : 0;
    return nops > JIT_SPLIT_OPS ? 2 : 0;
 }
-inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states, int n_codes, int first, int *first_out, int waves = 8)
+inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states, int n_codes, int first, int *first_out)
 {
    std::ostringstream s;
+   const int waves = 8;
    const int nblk = (int)p.stream.size() / 2;
    const int TP = waves * 16;
    const JitZPlan zpl = jit_zplan(p, n_tips, TP);
@@ -207,14 +191,13 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
    const size_t nops = p.ops.size();
    // states beyond n are zero padding: only RB row blocks and KB k-blocks of every P take part (4 and 16 at 61 states)
    const int RB = (n_states + 15) / 16, KB = (n_states + 3) / 4, KB2 = (KB + 1) / 2, NPc = KB2;   // NPc: 16-byte pieces per tip-table row
-   const bool fuse_tips = !getenv("PAML_AMD_JIT_NOFUSE") && KB2 >= 2;   // cherries gathered under the preceding matmul
+   const bool fuse_tips = KB2 >= 2;   // cherries gathered under the preceding matmul
    const int MID = KB2 / 2;                                             // ... from this k-block pair on (jit_matvec_tip2)
-   const bool spread = !getenv("PAML_AMD_JIT_NOSPREAD");    // ring refill issued from inside the MFMA loops
    const bool proft = getenv("PAML_AMD_PROF_TILES") != nullptr;            // kernel experiments: s_memrealtime (100 MHz) at workgroup start and at the end of each of its tiles
    const bool prof = !proft && getenv("PAML_AMD_PROF_OPS") != nullptr;      // kernel experiments: s_memtime stamp at every op
    // 61 states: the last k-block of P is the single column 60 — its rank-1 term goes through the vector pipe (a 512-byte
    // column table travels with every P block as a fifth DMA piece) and the k-block's four MFMAs are dropped
-   const bool tail61 = n_states == 61 && !getenv("PAML_AMD_JIT_NOTAIL");
+   const bool tail61 = n_states == 61;
    int last_mm = -1;
    for (size_t i = 0; i < nops; i++)
       if (p.ops[i].code == OP_MATMUL || p.ops[i].code == OP_MATMUL_POP) last_mm = (int)i;
@@ -227,7 +210,7 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
    // one code block only (large trees): it is replaced between tiles, so nothing of the next tile can start early
    const bool zsingle = zpl.bufs == 1, zhalf = zpl.half;
    int cur_piece = 0;         // (piece mode) the piece of the tile's codes that is in LDS
-   const bool peel = fuse_tips && !getenv("PAML_AMD_JIT_NOPEEL") && nops > 2 && p.ops[0].code == OP_SET_TIP2 && last_mm > 1 &&
+   const bool peel = fuse_tips && nops > 2 && p.ops[0].code == OP_SET_TIP2 && last_mm > 1 &&
                      p.ops[1].code != OP_MUL_TIP && p.ops[1].code != OP_MUL_TIP2 && !tail_blocks && !zsingle;
 
    // chunks of a tip table that hold codes of this data set (two codes per 1 KB chunk)
@@ -235,17 +218,6 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
    // DMA rounds per block: a P has chunks pair * 4 + row block (< KB2 * 4 used), a tip table TCH chunks; `waves` chunks per round
    const int P_ROUNDS = (KB2 * 4 + waves - 1) / waves, T_ROUNDS = (TCH + waves - 1) / waves;
    s << "#define JIT_KB2 " << KB2 << "\n#define JIT_RB " << RB << "\n#define JIT_TCH " << TCH << "\n#define JIT_WAVES " << waves << "\n";
-   if (jit_rowtail(n_states)) s << "#define JIT_ROWTAIL 1\n";
-#ifdef TIP_SWZ_OFF
-   s << "#define TIP_SWZ_OFF 1\n";      // (the library's P(t) kernel writes the tip tables without the swizzle: the per-tree kernel must read them so)
-#endif
-   // how STORE writes (device_common.h): 0 spread under the next product (default), 1 at the op; 2 — not at all, the ceiling measurement — is an experiment
-   if (const char *v = getenv("PAML_AMD_JIT_STORE"))
-      if (atoi(v) != 2 || jit_experiment_env("PAML_AMD_JIT_STORE")) s << "#define JIT_STORE_MODE " << atoi(v) << "\n";
-   if (getenv("PAML_AMD_JIT_NT_STORE")) s << "#define JIT_NT_STORE 1\n";         // experiment: non-temporal stores of the class likelihoods
-   if (jit_experiment_env("PAML_AMD_JIT_ABL_NOSEED")) s << "#define JIT_ABL_NOSEED 1\n";      // timing experiment: the rank-1 seed without its LDS reads and multiplies
-   if (jit_experiment_env("PAML_AMD_JIT_ABL_NOBAR")) s << "#define JIT_ABL_NOBAR 1\n";      // timing experiment: no workgroup barriers (results are garbage)
-   const char *abl_skew = jit_experiment_env("PAML_AMD_JIT_ABL_SKEW");                       // ... and waves 4-7 start this many x 64 cycles late
    if (zsingle) s << "#define JIT_ZB 1\n";
    if (zhalf) s << "#define JIT_ZPIECES " << zpl.pieces << "\n";
    const bool amb_over = n_codes > 64;      // codes beyond the 64 a ring block has rows for: summed from the rows of their states (device_common.h)
@@ -258,7 +230,6 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
       s << "   if (a.n_pi == 1) for (int i = tid; i < a.n_codes - 64; i += JIT_WAVES * 64) ((unsigned long long *)sPi)[64 + i] = a.code_mask[64 + i];\n";
       s << "   const JitAmb amb{a.code_mask, (__attribute__((address_space(3))) const unsigned long long *)(sPi + 64), a.n_pi == 1};\n";
    }
-   if (abl_skew) s << "   if (wave >= 4) { for (int i_ = 0; i_ < " << atoi(abl_skew) << "; i_++) __builtin_amdgcn_s_sleep(1); }\n";
    s << "   roff = " << ((4 - nblk % 4) & 3) << ";\n";
 
    // ---- static bookkeeping of what is in flight (per thread: pieces = vector-memory instructions) -------------------
@@ -312,7 +283,7 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
          z_pending = false;
       }
       const int upto = consumed + 4;
-      if (!defer || !spread) {
+      if (!defer) {
          if (!pend_store.empty()) {
             s << "  ";
             for (const std::string &st : pend_store) s << " " << st;
@@ -357,7 +328,7 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
    };
    const int prof_every = getenv("PAML_AMD_PROF_EVERY") ? std::max(1, atoi(getenv("PAML_AMD_PROF_EVERY"))) : 1;      // (experiments: a stamp at every n-th op only)
    const int split_mode = jit_split_mode(nops);      // (large trees: a branch every `split_every` ops, see jit_split_mode)
-   const int split_every = getenv("PAML_AMD_JIT_SPLIT_EVERY") ? std::max(1, atoi(getenv("PAML_AMD_JIT_SPLIT_EVERY"))) : 8;
+   const int split_every = 8;
    auto stamp = [&](size_t iop) {
       if (prof && iop % prof_every == 0)
          s << "   if (a.prof && tid == a.prof_tid && ptile) a.prof[(long)blockIdx.x * a.prof_stride + 1 + " << iop
@@ -489,13 +460,11 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
          const int out = alloc();
          // a cherry right after a pushed matmul: its two tip gathers ride under this matmul's second half
          // (piece mode: a cherry whose codes lie in the NEXT piece is not folded under this product — the crossing then happens at the cherry's
-         //  own step; there are at most pieces - 1 of them per tile.  The folded form is kept behind PAML_AMD_JIT_FOLD_CROSSING=1: one run of the
-         //  1 000-tip tree of tests/test_engine_gpu.py came out wrong with it during development and could not be reproduced — the identical
-         //  generated source gives the oracle's value on the final build — so the form every full test run has exercised is the default.)
+         //  own step; there are at most pieces - 1 of them per tile.  The folded form gave a wrong lnL once on the 1 000-tip tree of
+         //  tests/test_engine_gpu.py, cause not found, and was removed.)
          const bool crossing_cherry = zhalf && iop + 1 < nops && p.ops[iop + 1].code == OP_SET_TIP2 &&
                                       std::max(zpl.piece[p.ops[iop + 1].a], zpl.piece[p.ops[iop + 1].b]) > cur_piece;
-         const bool fuse = fuse_tips && push >= 0 && iop + 1 < nops && p.ops[iop + 1].code == OP_SET_TIP2 &&
-                           (!crossing_cherry || getenv("PAML_AMD_JIT_FOLD_CROSSING"));
+         const bool fuse = fuse_tips && push >= 0 && iop + 1 < nops && p.ops[iop + 1].code == OP_SET_TIP2 && !crossing_cherry;
          const bool fuse_next = peel && (int)iop == last_mm;     // ... or the next tile's first cherry under the last matmul
          if (fuse) cross_if({p.ops[iop + 1].a, p.ops[iop + 1].b});
          // (tip tables the ring could not hold earlier are requested in the first k-block pairs and awaited at the midpoint)
@@ -555,7 +524,7 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
       // counted waits that follow let them fly (a wait computed without them would make every block step wait for the stores'
       // completion in HBM).  At a tile's start the list lacks the previous tile's last stores: those waits are stricter than needed, never laxer.
       case OP_STORE: {
-         const bool under_product = spread && iop + 1 < nops && (p.ops[iop + 1].code == OP_MATMUL || p.ops[iop + 1].code == OP_MATMUL_POP) && p.ops[iop + 1].a == o.a;
+         const bool under_product = iop + 1 < nops && (p.ops[iop + 1].code == OP_MATMUL || p.ops[iop + 1].code == OP_MATMUL_POP) && p.ops[iop + 1].a == o.a;
          if (under_product)      // (the product that follows reads this very array and leaves it alone: see step)
             for (int i = 0; i < 8; i++)
                pend_store.push_back("JIT_STORE_PIECE(" + name(cur) + ", JIT_PART_DST(" + std::to_string(o.a) + "), " + std::to_string(i) + ");");
@@ -598,13 +567,13 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
    return s.str();
 }
 
-inline std::string jit_generate(const Program &p, int n_tips, int n_states = 61, int n_codes = 64, int waves = 8)
+inline std::string jit_generate(const Program &p, int n_tips, int n_states = 61, int n_codes = 64)
 {
    int first = 3, got = 3;
-   std::string src = jit_generate_impl(p, n_tips, n_states, n_codes, first, &got, waves);
+   std::string src = jit_generate_impl(p, n_tips, n_states, n_codes, first, &got);
    if (got != first) {
       first = got;
-      src = jit_generate_impl(p, n_tips, n_states, n_codes, first, &got, waves);
+      src = jit_generate_impl(p, n_tips, n_states, n_codes, first, &got);
    }
    if (got != first) return std::string("#error \"jit schedule does not close\"\n");
    // (one basic block of > 120 ops: the quick build first.  With the block splits the full passes take no longer than the quick ones.)
@@ -720,16 +689,12 @@ inline ValuFusedPlan jit_valu_fused_plan(const Program &p, int N, int n_tips, in
    (void)chunk;
    pl.CW = K >= 2 ? 2 : 1;
    pl.R = 1;
-   if (const char *v = getenv("PAML_AMD_VF_R")) pl.R = atoi(v) == 2 && chunk >= 512 ? 2 : 1;
-   if (const char *v = getenv("PAML_AMD_VF_CW")) pl.CW = std::max(1, std::min(std::min(4, K), atoi(v)));
-   if (pl.CW == 3) pl.CW = 2;
-   if (pl.CW > 1) pl.R = 1;
    const size_t rows = (size_t)K * n_tips * n_codes * N * 8;
    const size_t ch = (size_t)K * pl.n_cherry * n_codes * n_codes * N * 8;
    const size_t xch = pl.CW > 1 ? (size_t)K * 256 * 8 : 0;
    if (rows + xch > 60 * 1024) return pl;               // (the unfused kernel, gathering from L2, takes such models)
    pl.ok = true;
-   pl.cherry = pl.n_cherry > 0 && n_codes <= 8 && rows + ch + xch <= 56 * 1024 && !getenv("PAML_AMD_VF_NOCHERRY");
+   pl.cherry = pl.n_cherry > 0 && n_codes <= 8 && rows + ch + xch <= 56 * 1024;
    pl.lds_bytes = rows + (pl.cherry ? ch : 0) + xch;
    return pl;
 }
@@ -971,202 +936,6 @@ inline std::string jit_generate_valu_fused(const Program &p, int N, int n_tips, 
    return s.str();
 }
 
-// ---- 4-state models on the matrix cores: v_mfma_f64_4x4x4_4b_f64 (jit_generate_mfma4) -------------------------------------------
-// Measured on MI355X (profiles/r02_mfma4_layout.txt): the instruction runs at the full FP64 rate with a single wave per SIMD, and
-// its result layout equals its B-operand layout — lane = 16 i + 4 b + j holds row i of column (b, j).  So a partial is ONE double
-// per lane: state = lane >> 4, pattern = lane & 15 (four blocks of four patterns, all with the same A = P), and L' = P . L is one
-// instruction per 16 patterns whose result is the next B operand.  P arrives as a per-lane vector operand (lane (k, b, i) holds
-// P[i][k], a 128-byte line of the row-major matrix): no scalar-cache traffic, no lgkmcnt coupling with the LDS tip tables, which
-// is what held the one-pattern-per-lane kernel at 0.51 - 0.63 of the FP64 peak.  Everything else is the fused kernel's frame:
-// tip (and cherry) tables in LDS, classes inside, mixture + log + weighted chunk sum in the epilogue, CW class groups.
-// A wave owns 64 patterns as G = 4 independent groups of 16 (four MFMA chains in flight); elementwise products, tip factors and
-// the root stage use all 64 lanes (4 states x 16 patterns).
-inline std::string jit_generate_mfma4(const Program &p, int n_tips, int n_codes, int K, int chunk)
-{
-   const ValuFusedPlan pl = jit_valu_fused_plan(p, 4, n_tips, n_codes, K, chunk);
-   std::ostringstream s;
-   const int N = 4, G = 4, CW = pl.CW;
-   const int NC = n_codes, ROWW = n_tips * NC * N, CHW = pl.cherry ? pl.n_cherry * NC * NC * N : 0, TABW = ROWW + CHW;   // doubles per class
-   const int ZW = ((n_tips + 3) / 4 + 3) / 4 * 4;
-   const int NTH = 256 * CW;
-   s << "#include \"device_common.h\"\nusing namespace paml_amd;\n";
-   s << "extern \"C\" __global__ __launch_bounds__(" << NTH << ") void prune_jit(PruneArgs a)\n{\n";
-   s << "   constexpr int N = 4, NC = " << NC << ", K = " << K << ", ROWW = " << ROWW << ", TABW = " << TABW << ", ZW = " << ZW << ", CW = " << CW
-     << ", NTH = " << NTH << ";\n";
-   s << "   __shared__ __attribute__((aligned(16))) double sTab[K * TABW];\n   __shared__ double sV[256];\n";
-   if (CW > 1) s << "   __shared__ double sF[K * 256];\n";
-   s << "   const int tid = threadIdx.x & 255, cw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8), bat = blockIdx.y;\n   (void)cw;\n";
-   s << "   const int lane = tid & 63, wv = tid >> 6, st = lane >> 4, col = lane & 15;\n";
-   s << "   const long cls0 = (long)bat * K;\n";
-   s << "   for (int ir = 0; ir < K; ir++) {\n"
-        "      const double *src = a.ptip + (cls0 + ir) * a.n_nodes * a.tip_words;\n"
-        "      for (int i = threadIdx.x; i < ROWW; i += NTH) sTab[ir * TABW + i] = src[i];\n"
-        "   }\n   __syncthreads();\n";
-   if (pl.cherry) {
-      int c = 0;
-      s << "   for (int i = threadIdx.x; i < K * NC * NC * N; i += NTH) {\n"
-           "      const int ir = i / (NC * NC * N), r = i % (NC * NC * N), ca = r / (NC * N), cb = (r / N) % NC, j = r % N;\n"
-           "      const double *rw = sTab + ir * TABW;\n";
-      for (const Op &o : p.ops)
-         if (o.code == OP_SET_TIP2) {
-            s << "      sTab[ir * TABW + ROWW + " << c * NC * NC * N << " + r] = rw[(" << o.a << " * NC + ca) * N + j] * rw[(" << o.b << " * NC + cb) * N + j];\n";
-            c++;
-         }
-      s << "   }\n   __syncthreads();\n";
-   }
-   s << "   const long c_lo = (long)blockIdx.x * a.chunk, c_hi = (c_lo + a.chunk < (long)a.n_patt) ? c_lo + a.chunk : (long)a.n_patt;\n";
-   s << "   const CONST_AS double *fK = as_const(a.freqK + bat * a.freqK_bs);\n";
-   s << "   const double pis = a.pi[st];\n";
-   s << "   const int aidx = (lane & 3) * 4 + (lane >> 4);      /* A operand: lane (k, b, i) <- P[i][k] */\n";
-   s << "   double acc = 0;\n";
-   s << "   for (long h0 = c_lo; h0 < c_hi; h0 += 256) {\n";
-   auto gx = [&](int g) { return "_" + std::to_string(g); };
-   for (int g = 0; g < G; g++) {
-      const std::string x = gx(g);
-      s << "      const long h" << x << " = h0 + wv * 64 + " << 16 * g << " + col;\n      const bool valid" << x << " = h" << x << " < c_hi;\n";
-      s << "      unsigned int zw" << x << "[ZW];\n      { const uint4 *zp = (const uint4 *)(a.zpm + (valid" << x << " ? h" << x << " : c_hi - 1) * ZW);\n";
-      for (int i = 0; i < ZW / 4; i++)
-         s << "        { const uint4 t = zp[" << i << "]; zw" << x << "[" << 4 * i << "] = t.x; zw" << x << "[" << 4 * i + 1 << "] = t.y; zw" << x << "[" << 4 * i + 2
-           << "] = t.z; zw" << x << "[" << 4 * i + 3 << "] = t.w; }\n";
-      s << "      }\n";
-      s << "#define zw zw" << x << "\n";
-      int c = 0;
-      std::vector<char> seen(n_tips, 0);
-      for (const Op &o : p.ops)
-         if (o.code == OP_SET_TIP2 && pl.cherry) {
-            s << "      const int oc" << c << x << " = ROWW + " << c * NC * NC * N << " + (JVF_CODE(" << o.a << ") * NC + JVF_CODE(" << o.b << ")) * N + st;\n";
-            seen[o.a] = seen[o.b] = 1;
-            c++;
-         }
-      for (const Op &o : p.ops) {
-         auto tipoff = [&](int t) {
-            if (!seen[t]) { s << "      const int ot" << t << x << " = (" << t << " * NC + JVF_CODE(" << t << ")) * N + st;\n"; seen[t] = 2; }
-         };
-         switch (o.code) {
-         case OP_SET_TIP: case OP_MUL_TIP: tipoff(o.a); break;
-         case OP_MUL_TIP2: tipoff(o.a); tipoff(o.b); break;
-         case OP_SET_TIP2: if (!pl.cherry) { tipoff(o.a); tipoff(o.b); } break;
-         case OP_INIT_TIP: s << "      const int ci" << o.a << x << " = JVF_CODE(" << o.a << ");\n"; break;
-         default: break;
-         }
-      }
-      s << "#undef zw\n";
-      s << "      double fh" << x << " = 0, v" << x << " = 0;\n";
-   }
-   s << "      _Pragma(\"unroll 1\") for (int ir = " << (CW > 1 ? "cw" : "0") << "; ir < K; ir += CW) {\n";
-   s << "         const double *Pint = a.pint + (cls0 + ir) * a.n_nodes * (N * N) + aidx;\n";
-   s << "         const double *tab = sTab + ir * TABW;\n";
-   const int NA = p.max_stack + 2;
-   for (int g = 0; g < G; g++) {
-      s << "         double lnscale" << gx(g) << " = 0;\n         (void)lnscale" << gx(g) << ";\n";
-      s << "         double";
-      for (int i = 0; i < NA; i++) s << (i ? ", " : " ") << "A" << i << gx(g) << " = 0";
-      s << ";\n";
-   }
-   std::vector<int> freeA;
-   for (int i = NA - 1; i >= 0; i--) freeA.push_back(i);
-   auto alloc = [&]() { int r = freeA.back(); freeA.pop_back(); return r; };
-   auto release = [&](int r) { freeA.push_back(r); };
-   auto name = [&](int a, int g) { return "A" + std::to_string(a) + gx(g); };
-   std::vector<int> slot(256, -1);
-   int cur = -1, ich = 0;
-   for (const Op &o : p.ops) {
-      int out = -1, pop = -1, push = -1, curin = cur;
-      if (o.code == OP_INIT_ONES || o.code == OP_INIT_TIP || o.code == OP_SET_TIP || o.code == OP_SET_TIP2) {
-         if (cur < 0) cur = alloc();
-         curin = cur;
-      }
-      if (o.code == OP_MATMUL || o.code == OP_MATMUL_POP) {
-         pop = mm_pop_slot(o); push = mm_push_slot(o); out = alloc();
-         s << "         { const double pa = Pint[" << (long)o.a * N * N << "];\n";
-      }
-      for (int g = 0; g < G; g++) {
-         const std::string x = gx(g), C = name(curin, g);
-         switch (o.code) {
-         case OP_INIT_ONES: s << "         " << C << " = 1.0;\n"; break;
-         case OP_INIT_TIP: s << "         " << C << " = (a.cleandata && st == ci" << o.a << x << ") ? 1.0 : 0.0;\n"; break;
-         case OP_SET_TIP: s << "         " << C << " = tab[ot" << o.a << x << "];\n"; break;
-         case OP_MUL_TIP: s << "         " << C << " *= tab[ot" << o.a << x << "];\n"; break;
-         case OP_SET_TIP2:
-            if (pl.cherry) s << "         " << C << " = tab[oc" << ich << x << "];\n";
-            else s << "         " << C << " = tab[ot" << o.a << x << "] * tab[ot" << o.b << x << "];\n";
-            break;
-         case OP_MUL_TIP2: s << "         " << C << " = (" << C << " * tab[ot" << o.a << x << "]) * tab[ot" << o.b << x << "];\n"; break;
-         case OP_MATMUL:
-         case OP_MATMUL_POP:
-            s << "           " << name(out, g) << " = __builtin_amdgcn_mfma_f64_4x4x4f64(pa, " << C << ", 0.0, 0, 0, 0);\n";
-            break;
-         case OP_SCALE:      // NodeScale treesub.c:7200-7230: the maximum over the four states sits on lane bits 4-5
-            s << "         { double mx = " << C << " > 0 ? " << C << " : 0; { const double o1 = __shfl_xor(mx, 16); mx = o1 > mx ? o1 : mx; } { const double o2 = __shfl_xor(mx, 32); mx = o2 > mx ? o2 : mx; }\n"
-              << "           if (mx < 1e-300) { " << C << " = 1.0; lnscale" << x << " += -800; } else { " << C << " /= mx; lnscale" << x << " += log(mx); } }\n";
-            break;
-         case OP_ROOT:
-            s << "         { double f = pis * " << C << "; f += __shfl_xor(f, 16); f += __shfl_xor(f, 32);\n"
-              << "            const bool own = st == 0 && valid" << x << ";\n"
-              << "            const double wtz = own ? a.weights[h" << x << "] : 0.0;\n"
-              << "            if (a.mode == PAML_AMD_MODE_LFUN) { if (f <= 0) f = 1e-80; v" << x << " = log(f) + lnscale" << x << "; if (a.want_fhk && own) a.fhK[(cls0 + ir) * a.n_patt + h" << x
-              << "] = wtz > 0 ? v" << x << " : 0.0; }\n"
-              << "            else {\n"
-              << "               if (f <= 0) f = 1e-300;\n"
-              << "               if (a.n_scale) { if (own) a.fhK[(cls0 + ir) * a.n_patt + h" << x << "] = wtz > 0 ? log(f) + lnscale" << x << " : 0.0; }\n"
-              << "               else {\n";
-            if (CW > 1) s << "                  if (st == 0) sF[ir * 256 + wv * 64 + " << 16 * g << " + col] = f;\n";
-            else s << "                  fh" << x << " += fK[ir] * f;\n";
-            s << "                  if (a.want_fhk && own) a.fhK[(cls0 + ir) * a.n_patt + h" << x << "] = wtz > 0 ? f : 0.0; }\n"
-              << "            } }\n";
-            break;
-         default: break;
-         }
-      }
-      if (o.code == OP_MATMUL || o.code == OP_MATMUL_POP) {
-         s << "         }\n";
-         if (pop >= 0)
-            for (int g = 0; g < G; g++) s << "         " << name(out, g) << " = " << name(slot[pop], g) << " * " << name(out, g) << ";\n";
-      }
-      switch (o.code) {
-      case OP_SET_TIP2: if (pl.cherry) ich++; break;
-      case OP_PUSH: slot[o.b] = cur; cur = -1; break;
-      case OP_MATMUL:
-      case OP_MATMUL_POP:
-         release(curin);
-         if (pop >= 0) { release(slot[pop]); slot[pop] = -1; }
-         if (push >= 0) { slot[push] = out; cur = -1; }
-         else cur = out;
-         break;
-      case OP_ROOT: release(cur); cur = -1; break;
-      default: break;
-      }
-   }
-   s << "      }\n";      // classes
-   if (CW > 1) s << "      __syncthreads();\n";
-   for (int g = 0; g < G; g++) {
-      const std::string x = gx(g);
-      s << "      if (a.mode != PAML_AMD_MODE_LFUN" << (CW > 1 ? " && cw == 0" : "") << ") {\n"
-           "         if (a.n_scale) {      /* log-sum-exp around the first maximum (treesub.c:7640-7649) */\n"
-           "            const double *fk = a.fhK + cls0 * a.n_patt + (valid" << x << " ? h" << x << " : c_hi - 1);\n"
-           "            int it = 0;\n"
-           "            for (int ir = 1; ir < K; ir++) if (fk[(long)ir * a.n_patt] > fk[(long)it * a.n_patt]) it = ir;\n"
-           "            const double t = fk[(long)it * a.n_patt];\n"
-           "            double fh = 0;\n"
-           "            for (int ir = 0; ir < K; ir++) fh += fK[ir] * exp(fk[(long)ir * a.n_patt] - t);\n"
-           "            v" << x << " = t + log(fh);\n"
-           "         }\n"
-           "         else {\n";
-      if (CW > 1) s << "            for (int ir = 0; ir < K; ir++) fh" << x << " += fK[ir] * sF[ir * 256 + wv * 64 + " << 16 * g << " + col];\n";
-      s << "            if (fh" << x << " <= 0) fh" << x << " = 1e-300;\n            v" << x << " = log(fh" << x << ");\n         }\n      }\n";
-      s << "      if (st == 0" << (CW > 1 ? " && cw == 0" : "") << ") sV[wv * 64 + " << 16 * g << " + col] = v" << x << ";\n";
-   }
-   s << "      __syncthreads();\n";
-   // the chunk's weighted sum in reduce_stage1's order: thread t adds pattern h0 + t
-   s << "      if (" << (CW > 1 ? "cw == 0 && " : "") << "h0 + tid < c_hi) { const double wt = a.weights[h0 + tid]; const double v = wt > 0 ? sV[tid] : 0.0; acc += v * wt; if (a.lnf) a.lnf[(long)bat * a.n_patt + h0 + tid] = v; }\n";
-   s << "      __syncthreads();\n";
-   s << "   }\n";      // sub-tiles
-   if (CW > 1) s << "   if (cw > 0) acc = 0;\n";
-   s << "   red_block_finish<" << CW << ">(acc, a.red_partial + (long)bat * a.nb_stride, a.first_chunk + blockIdx.x, a.nb_stride, a.red_out + bat, a.red_counter ? a.red_counter + bat * RED_TICKET_WORDS : nullptr);\n";
-   s << "}\n";
-   return s.str();
-}
-
 // ---- 20 states on v_mfma_f64_4x4x4 (m20_* in device_common.h) -----------------------------------------------------------------
 // One class per workgroup (grid = a multiple of the class count, persistent over the 256-pattern tiles of its class): the
 // row-major P(t) of every internal branch of that class sits in LDS (3 200 bytes each) for the whole launch; 8 waves x 2 groups
@@ -1197,25 +966,15 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
    std::vector<int> mm_nodes;
    for (const Op &o : p.ops)
       if (o.code == OP_MATMUL || o.code == OP_MATMUL_POP) { mm_nodes.push_back(o.a); nmm++; }
-   if (const char *abl = jit_experiment_env("PAML_AMD_M20_ABL")) {      // timing experiments (results are garbage)
-      if (strstr(abl, "notip")) s << "#define M20_ABL_NOTIP 1\n";
-      if (strstr(abl, "noa")) s << "#define M20_ABL_NOA 1\n";
-   }
    s << "#include \"device_common.h\"\nusing namespace paml_amd;\n";
-   // experiment (PAML_AMD_M20_W12=1): 12 waves per workgroup, every unit a half unit (one 16-pattern group per wave, three waves per SIMD)
-   const bool w12 = getenv("PAML_AMD_M20_W12") != nullptr;
-   const int NTH = w12 ? 768 : 512;
+   const int NTH = 512;
    s << "extern \"C\" __global__ __launch_bounds__(" << NTH << ") void prune_jit(PruneArgs a)\n{\n";
    // tip tables: as many as fit beside the P(t) blocks go to LDS (in order of use), the others are gathered from L1 / L2
    const int tip_bytes = n_codes * 168;      // rows padded to 21 doubles in LDS: with 20, codes c and c + 8 share all their banks
-   // 16x16x4 + 4x4x4 (m20h_matvec2), else all on 4x4x4 — the latter only for trees whose P(t) all fit in LDS (it reads row-major blocks)
-   const bool hybrid = !getenv("PAML_AMD_M20_NOHYBRID") || nmm > M20_LDS_NODES;
-   // (experiments: PAML_AMD_M20_NL = P(t) blocks kept in LDS — the rest of LDS takes tip tables; PAML_AMD_M20_GA = products ahead of their
-   //  use at which rows gathered from L2 are requested)
-   const int lds_nodes = getenv("PAML_AMD_M20_NL") ? std::max(0, std::min(M20_LDS_NODES, atoi(getenv("PAML_AMD_M20_NL")))) : M20_LDS_NODES;
-   const int NL = hybrid ? std::min(nmm, lds_nodes) : nmm;      // products 0 .. NL - 1: operands in LDS; the others: in global memory, operand order
+   // 16x16x4 + 4x4x4 (m20h_matvec2)
+   const int NL = std::min(nmm, M20_LDS_NODES);      // products 0 .. NL - 1: operands in LDS; the others: in global memory, operand order
    const int room = 158 * 1024 - NL * 3200;
-   const int n_lds_max = getenv("PAML_AMD_M20_NOLDSTIP") ? 0 : std::max(0, room / tip_bytes);
+   const int n_lds_max = std::max(0, room / tip_bytes);
    std::vector<int> lds_slot(n_tips, -1);
    int n_lds = 0;
    for (const Op &o : p.ops) {
@@ -1249,8 +1008,8 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
       s << "   if (as_const(a.gene_off)[gene + 1] <= hbeg) return;      /* (a shard that holds nothing of this gene) */\n";
    }
    // (a.pint: the branches' P(t) in operand order — [kb][lane] <- P[lane & 15][4 kb + (lane >> 4)], then [kb][k][i] <- P[16 + i][4 kb + k],
-   //  written so by pmat_kernel_t<32> in layout 2; a.pcol: the row-major copies, which the all-4x4x4 form reads)
-   s << "   const double *Pall = " << (hybrid ? "a.pint" : "a.pcol") << " + ((long)gene * a.K + iclass) * a.n_nodes * 400;\n";
+   //  written so by pmat_kernel_t<32> in layout 2)
+   s << "   const double *Pall = " << "a.pint" << " + ((long)gene * a.K + iclass) * a.n_nodes * 400;\n";
    s << "   const double *Ptip = a.ptip + ((long)gene * a.K + iclass) * a.n_nodes * a.tip_words;\n";
    for (int k = 0; k < NL; k++)
       s << "   for (int i = tid; i < 400; i += " << NTH << ") sP[" << k * 400 << " + i] = Pall[" << (long)mm_nodes[k] * 400 << " + i];\n";
@@ -1282,9 +1041,7 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
    // (profiles/r03_20state.txt: the tail was 6 % of the span).  Ticket t < nfull: the full unit ubase + t; else the half
    // (t - nfull) & 1 of unit ubase + nfull + (t - nfull) / 2.  A wave's first ticket is its own number; the next one is drawn a
    // unit ahead, so that its tip codes arrive while the current unit is walked.
-   // (PAML_AMD_M20_HALF=1, experiment: every unit a half unit — one 16-pattern group per wave, half the partial arrays: deep trees whose
-   //  two-group walk spills)
-   const int SPLIT = (w12 || getenv("PAML_AMD_M20_HALF")) ? (1 << 20) : (hybrid && !getenv("PAML_AMD_M20_NOSPLIT")) ? 8 : 0;
+   const int SPLIT = 8;
    s << "#define M20_UNIT_OF(T) ((T) < nfull ? ubase + (T) : ubase + nfull + (((T) - nfull) >> 1))\n";
    s << "#define M20_HALF_OF(T) ((T) < nfull ? -1 : (((T) - nfull) & 1))\n";
    s << "#define M20_FETCH_CODES(T) { int tn_ = (T) < nt ? (T) : nt - 1; tn_ = tn_ < 0 ? 0 : tn_; const int un_ = M20_UNIT_OF(tn_), hf_ = M20_HALF_OF(tn_); \\\n"
@@ -1294,10 +1051,9 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
         "      hn = h0n + 16 + col; if (hn >= hend) hn = hend - 1; zp = (const uint4 *)(a.zpm + hn * ZW); \\\n"
         "      { const uint4 t = zp[zq]; zn_1[0] = t.x; zn_1[1] = t.y; zn_1[2] = t.z; zn_1[3] = t.w; } }\n";
    s << "#define M20_TICKET() __builtin_amdgcn_readfirstlane(lane == 0 ? __hip_atomic_fetch_add(&sTicket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0)\n";
-   if (hybrid && NL > 0) s << "   double Acol[5], AsN[5] = {0, 0, 0, 0, 0};\n   (void)AsN;\n   m20h_read_big(m20_lds_addr(sP), lane, Acol);      /* the first product's big operands (a unit's last product fetches them for the next unit) */\n   (void)aoff;\n";
-   else if (hybrid)      // (no P(t) block in LDS: the first product's operands come from global memory like every other's)
+   if (NL > 0) s << "   double Acol[5], AsN[5] = {0, 0, 0, 0, 0};\n   (void)AsN;\n   m20h_read_big(m20_lds_addr(sP), lane, Acol);      /* the first product's big operands (a unit's last product fetches them for the next unit) */\n   (void)aoff;\n";
+   else      // (no P(t) block in LDS: the first product's operands come from global memory like every other's)
       s << "   double Acol[5], AsN[5];\n   { const double *Pn_ = Pall + " << (long)mm_nodes[0] * 400 << "; _Pragma(\"unroll\") for (int i = 0; i < 5; i++) { Acol[i] = Pn_[i * 64 + lane]; AsN[i] = Pn_[320 + i * 16 + ((lane >> 4) << 2) + (lane & 3)]; } }\n   (void)aoff; (void)sP;\n";
-   else s << "   double Acol[5];\n   m20_acol_asm<0>(m20_lds_addr(sP) + aoff * 8, Acol);      /* first column of the first product (a unit's last product fetches it for the next unit) */\n";
    const bool proft = getenv("PAML_AMD_PROF_TILES") != nullptr;      // experiments: workgroup timeline (tools/prof_tiles.py)
    const char *ptid = getenv("PAML_AMD_PROF_TID");                   // ... stamped by this thread (default 0)
    const std::string pt = ptid ? ptid : "0";
@@ -1370,8 +1126,7 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
          if (is_tip(p.ops[j]) && !loaded[j] && (which & (all_lds(p.ops[j]) ? 1 : 2))) emit_loads(j);
    };
    emit_loads_after(-1, 3);
-   const bool ga1 = getenv("PAML_AMD_M20_GA") && atoi(getenv("PAML_AMD_M20_GA")) == 1;
-   if (!ga1) emit_loads_after(0, 2);
+   emit_loads_after(0, 2);
    std::vector<int> slot(256, -1);
    int cur = -1, imm = 0;
    for (size_t iop = 0; iop < nops; iop++) {
@@ -1403,15 +1158,13 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
       case OP_MATMUL_POP:
          pop = mm_pop_slot(o); push = mm_push_slot(o); out = alloc();
          emit_loads_after(imm, 1);
-         emit_loads_after(ga1 ? imm : imm + 1, 2);
+         emit_loads_after(imm + 1, 2);
          s << "      __builtin_amdgcn_sched_barrier(0);\n";
          {
             const int nxt = (imm + 1) % nmm;
             auto opnd = [&](int k) { return k < NL ? "sP + " + std::to_string(k * 400) : "Pall + " + std::to_string((long)mm_nodes[k] * 400); };
             const std::string tpl = std::string("<") + (imm >= NL ? "true" : "false") + ", " + (nxt >= NL ? "true" : "false") + ">";
-            if (!hybrid && G == 2)
-               s << "      m20_matvec2(sP + " << imm * 400 << ", sP + " << nxt * 400 << ", aoff, Acol, " << name(curin, 0) << ", " << name(out, 0) << ", " << name(curin, 1) << ", " << name(out, 1) << ");\n";
-            else if (G == 2)
+            if (G == 2)
                s << "      m20h_matvec2x" << tpl << "(" << opnd(imm) << ", " << opnd(nxt) << ", lane, Acol, AsN, " << name(curin, 0) << ", " << name(out, 0) << ", "
                  << name(curin, 1) << ", " << name(out, 1) << ");\n";
             else
@@ -1443,15 +1196,11 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
       }
    }
    };      // emit_body
-   if (w12 || getenv("PAML_AMD_M20_HALF")) emit_body(1);
-   else if (SPLIT) {
-      s << "      if (half < 0) {\n";
-      emit_body(2);
-      s << "      } else {\n";
-      emit_body(1);
-      s << "      }\n";
-   }
-   else emit_body(2);
+   s << "      if (half < 0) {\n";
+   emit_body(2);
+   s << "      } else {\n";
+   emit_body(1);
+   s << "      }\n";
    if (proft) s << "      if (a.prof && tid == " << pt << " && ptc < a.prof_stride - 4) { a.prof[(long)blockIdx.x * a.prof_stride + 1 + ptc] = __builtin_amdgcn_s_memrealtime(); a.prof[(long)blockIdx.x * a.prof_stride + a.prof_stride - 1] = __builtin_amdgcn_s_memtime(); }\n      ptc++;\n";
    s << "      u = unext; unext = unext2;\n";
    s << "   }\n}\n";
@@ -1629,27 +1378,23 @@ inline std::string jit_source_dir()
 //                              the benchmark's trees), so a fresh machine does not start with a compile;
 //   the user's cache           read-write: $PAML_AMD_JIT_CACHE, else $XDG_CACHE_HOME/paml_amd/jit, else $HOME/.cache/paml_amd/jit;
 //                              PAML_AMD_JIT_CACHE=0 (or empty) switches it off.
-inline const char *jit_opt_level() { return getenv("PAML_AMD_JIT_OPT") ? getenv("PAML_AMD_JIT_OPT") : "-O3"; }      // experiments: -O1 / -O2
+inline const char *jit_opt_level() { return "-O3"; }
 
 // Kernels of large trees (the generator marks their source): one basic block of tens of thousands of instructions, on which three
 // passes of the compiler are quadratic and gain nothing here — measured on the 192-taxon kernel (340 KB of code), this container's CPU:
 // GPU Load and Store Vectorizer 56 s of 82 (every access is already 16 bytes wide), Machine CSE 6 s, Machine Copy Propagation 3 s.
 // Without them 23 s, the same registers and 115 spilled dwords against 106 (tools/README.md, profiles/r05_big_trees.txt).
 static const char *const JIT_BIG_FLAGS[] = {"-mllvm", "-amdgpu-load-store-vectorizer=0", "-mllvm", "-disable-machine-cse", "-mllvm", "-disable-copyprop"};
-inline bool jit_is_big(const std::string &src) { return src.compare(0, 10, "// JIT_BIG") == 0 && !getenv("PAML_AMD_JIT_BIG_DEFAULT_FLAGS"); }
+inline bool jit_is_big(const std::string &src) { return src.compare(0, 10, "// JIT_BIG") == 0; }
 inline std::string jit_strip_big(const std::string &src)      // the same kernel for the compiler's full pipeline (no marker line)
 {
    return src.compare(0, 10, "// JIT_BIG") == 0 ? src.substr(src.find('\n') + 1) : src;
 }
-inline std::vector<std::string> jit_big_flags(const std::string &src)      // (PAML_AMD_JIT_BIG_FLAGS="-mllvm -x ...": experiments)
+inline std::vector<std::string> jit_big_flags(const std::string &src)
 {
    std::vector<std::string> f;
    if (!jit_is_big(src)) return f;
-   if (const char *v = getenv("PAML_AMD_JIT_BIG_FLAGS")) {
-      std::istringstream is(v);
-      for (std::string w; is >> w;) f.push_back(w);
-   }
-   else f.assign(std::begin(JIT_BIG_FLAGS), std::end(JIT_BIG_FLAGS));
+   f.assign(std::begin(JIT_BIG_FLAGS), std::end(JIT_BIG_FLAGS));
    return f;
 }
 

@@ -18,7 +18,7 @@ struct EigenDev {
 
 // Kernel A (kernels_pmat.h): batched P(t)
 struct PmatArgs {
-   int n, n_nodes, root, K, n_genes, n_labels, n_codes, layout;   // layout 0: VALU (row-major), 1: mfma64, 2: as 0 with the tip rows in m20 order, 3: as 1 with rows 48..60 of a 61-state P in the per-tree kernel's row-tail form
+   int n, n_nodes, root, K, n_genes, n_labels, n_codes, layout;   // layout 0: VALU (row-major), 1: mfma64, 2: as 0 with the tip rows in m20 order
    const int *label;             // [n_nodes]
    const unsigned char *is_leaf; // [n_nodes]
    const double *branch;         // [n_nodes]
@@ -74,7 +74,6 @@ struct ReduceArgs {
    double *out;        // scalar
    int n_patt, K, mode, n_scale, chunk;
    int first_chunk, nb_stride;
-   int *counter;       // [batch] tickets of red_block_finish (null: the total is formed by reduce_stage2 after the all-reduce)
 };
 
 // Branch-local evaluation (kernels_branch.h)
@@ -141,7 +140,6 @@ struct BranchEigArgs {
    int n, K, n_patt, n_tips, n_int, n_nodes, n_groups, n_scale, n_t, n_codes;
    int a_node, b_node;                  // the branch's two ends; b may be a tip
    int n_sons, son[2];                  // n_sons > 0: A's partial is formed here from its sons in the tree seen from the branch (then stored)
-   int no_store;                        // timing experiment: the coefficients are not written
    int feval;                           // K == 1: lnL, dlnL, ddlnL of the n_t (<= BEIG_NT) trial lengths are formed in the same pass
    int chunk_groups, nb_local, first_chunk, n_out;      // partial sums [n_out = 3 n_t columns][n_rows]: a row per wave's eighth of a chunk of 16 * chunk_groups patterns, at global positions
    long n_rows;

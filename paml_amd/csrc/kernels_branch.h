@@ -330,23 +330,15 @@ __global__ __launch_bounds__(256) void branch_eigprep_kernel(EigPrepArgs a)
 }
 
 // The partials and coefficients of a call are streamed through once (0.5 GB each at 16 taxa x 10^6 patterns) and nothing of them is
-// read again before the caches have turned over: non-temporal accesses.  BEIG_STREAM (tools/build_variant.sh): bit 0 = the stores,
-// bit 1 = the loads.  Measured on MI355X (gpurun_out/r04b/branch_nt.txt -> profiles/r04_branch.txt): the coefficient-forming kernel
-// is indifferent (0.445 / 0.443 / 0.447 / 0.444 ms per call for 0 / 1 / 2 / 3), the polynomial kernel on the stored coefficients
-// gains 8-15 % from the loads (a further trial length 0.198 -> 0.182 ms, four 0.168 -> 0.150, in the walk 0.215 -> 0.183).
-#ifndef BEIG_STREAM
-#define BEIG_STREAM 3
-#endif
+// read again before the caches have turned over: non-temporal accesses.  Measured on MI355X
+// (profiles/r04_branch.txt): the coefficient-forming kernel is indifferent to them (0.445 against 0.444 ms per call), the polynomial
+// kernel on the stored coefficients gains 8-15 % from the loads (a further trial length 0.198 -> 0.182 ms, four 0.168 -> 0.150).
 __device__ __forceinline__ void beig_load(const double *p, int lane, v4d (&x)[4])      // (part_load's layout, straight into the MFMA tuples)
 {
    const part2_t *p2 = (const part2_t *)p + lane;
 #pragma unroll
    for (int i = 0; i < 8; i++) {
-#if BEIG_STREAM & 2
       const part2_t v = __builtin_nontemporal_load(p2 + i * 64);
-#else
-      const part2_t v = p2[i * 64];
-#endif
       x[i >> 1][(2 * i) & 3] = v.x; x[i >> 1][(2 * i + 1) & 3] = v.y;
    }
 }
@@ -356,11 +348,7 @@ __device__ __forceinline__ void beig_store(double *p, int lane, const v4d (&x)[4
 #pragma unroll
    for (int i = 0; i < 8; i++) {
       const part2_t v = (part2_t){x[i >> 1][(2 * i) & 3], x[i >> 1][(2 * i + 1) & 3]};
-#if BEIG_STREAM & 1
       __builtin_nontemporal_store(v, p2 + i * 64);
-#else
-      p2[i * 64] = v;
-#endif
    }
 }
 // g[d] += sum_m c_m E_d[k = 4m + q]: the lane's share of f, f', f'' for one trial length (et: [3][64] in LDS, element q*16 + m)
@@ -464,8 +452,7 @@ __global__ __launch_bounds__(512, 2) void branch_eig_kernel(BranchEigArgs a)
    __syncthreads();
 #define BEIG_MATVEC(MAT, IDX, X, Y)                                                                                             \
    do {                                                                                                                         \
-      if (a.no_store & 2) { _Pragma("unroll") for (int i_ = 0; i_ < 4; i_++) (Y)[i_] = (X)[i_]; }      /* timing experiment: no products */ \
-      else jit_matvec<T61, 4, 16>((MAT), lane, (X), (Y), JitNoSide(), sCol + (IDX) * 64, T61 ? jit_x60((X), lane) : 0.0);       \
+      jit_matvec<T61, 4, 16>((MAT), lane, (X), (Y), JitNoSide(), sCol + (IDX) * 64, T61 ? jit_x60((X), lane) : 0.0);       \
    } while (0)
 
    const long G = a.n_groups;
@@ -580,7 +567,7 @@ __global__ __launch_bounds__(512, 2) void branch_eig_kernel(BranchEigArgs a)
          v4d c[4];
 #pragma unroll
          for (int i = 0; i < 4; i++) c[i] = (w[i] * zz[i]) * wgt;
-         if (!(a.no_store & 1)) beig_store(cclass + (long)g * 1024, lane, c);
+         beig_store(cclass + (long)g * 1024, lane, c);
          if (a.feval) {
             double g4[BEIG_NT][3];
 #pragma unroll

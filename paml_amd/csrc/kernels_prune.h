@@ -509,11 +509,7 @@ __global__ __launch_bounds__(512, 2) void prune_mfma64_stream(PruneArgs a)
 #define TIP_CODE(tip) ((int)sZ[(tip)*TP + hw])
    // consume the next c blocks of the stream: they have landed for every wave after this returns, and the
    // buffers used by the previous step are refilled with the blocks 3..4 ahead
-#ifdef ABL_NO_BARRIER
-#define STREAM_BARRIER()
-#else
 #define STREAM_BARRIER() __syncthreads()
-#endif
 #define STREAM_STEP(c)                                                                                           \
    do {                                                                                                         \
       wait_blocks_in_flight(issued - (consumed + (c)));                                                         \

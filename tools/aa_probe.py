@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The 20-state model class at scale (codeml seqtype 2 + G4 on synthetic amino-acid patterns): time per evaluation back to back and the
-fraction of the FP64 peak of the algorithmic flops.  usage: python tools/aa_probe.py [taxa] [patterns]   (PAML_AMD_M20_HALF / _W12 / PAML_AMD_NO_M20: variants)"""
+fraction of the FP64 peak of the algorithmic flops.  usage: python tools/aa_probe.py [taxa] [patterns]   (PAML_AMD_NO_M20: the interpreter instead)"""
 import os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO]

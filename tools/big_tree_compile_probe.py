@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Large trees: how long the interpreter serves before the tree's own kernel is compiled (worker thread, JIT_BIG_FLAGS), and the rate
-before and after.  usage: python tools/big_tree_compile_probe.py [taxa ...]   (PAML_AMD_JIT_BIG_DEFAULT_FLAGS=1: the compiler's default passes)"""
+before and after.  usage: python tools/big_tree_compile_probe.py [taxa ...]"""
 import json, os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A variant build of libpaml_amd.so for A/B runs (tools/ab.sh, PAML_AMD_LIB=...): one translation unit recompiled with extra flags,
 # linked with the default build's other objects.   tools/build_variant.sh <name> <unit> <flags...>
-#   e.g. tools/build_variant.sh nt3 engine_branch -DBEIG_STREAM=3   ->  paml_amd/lib/exp/libpaml_amd_nt3.so
+#   e.g. tools/build_variant.sh nolicm engine_branch -mllvm -disable-machine-licm   ->  paml_amd/lib/exp/libpaml_amd_nolicm.so
 set -e
 cd "$(dirname "$0")/.."
 name=$1; unit=$2; shift 2

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """4-state kernel probe: C2 (32 taxa x 1e5 nucleotide patterns, GTR+G4) and the same shape at 4e6 patterns — per-evaluation time
 in the three call styles (eval with host read-back, eval_device back to back) and the kernel's own time (HIP events), checked
-against the oracle on a slice.  PAML_AMD_NO_FUSED=1 selects the round-1 kernel (classes outermost, tips gathered from L2)."""
+against the oracle on a slice."""
 import json
 import os
 import sys

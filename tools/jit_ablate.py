@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Timing-only probe of the 61-state per-tree kernel under generator switches (PAML_AMD_JIT_* environment): ms per evaluation
-of the C4 workload; with --check the lnL is compared with the golden value (ablations that break the results skip it)."""
+"""Timing-only probe of the 61-state per-tree kernel: ms per evaluation of the C4 workload; with --check the lnL is compared with
+the golden value (ablations that break the results skip it)."""
 import json
 import os
 import sys

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The keep-partials evaluation at the benchmark's size (16 taxa x 10^6 codon patterns, every internal node's partial stored: 7.2 GB per
-evaluation) under the store variants of the per-tree kernel.  usage: PAML_AMD_JIT_STORE=<0|1|2> python tools/keep_probe.py [n_evals]
-(2, no stores at all, only with a library built with -DPAML_AMD_JIT_EXPERIMENTS)"""
+evaluation) on the per-tree kernel.  usage: python tools/keep_probe.py [n_evals]
+(the plain and no-store variants measured in profiles/r05_keep_partials.txt were removed)"""
 import os
 import sys
 import time
@@ -24,4 +24,4 @@ for i in range(n):
     eng.eval_device(pb.tree.branch, d.data_ptr() + 8 * (3 + i))
 eng.flush(); torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / n
-print("PAML_AMD_JIT_STORE=%s kernel %s: %.4f ms per evaluation, lnL %.6f" % (os.environ.get("PAML_AMD_JIT_STORE", "0"), eng.kernel_name, dt * 1e3, float(d[-1])))
+print("kernel %s: %.4f ms per evaluation, lnL %.6f" % (eng.kernel_name, dt * 1e3, float(d[-1])))
