@@ -124,7 +124,9 @@ int paml_amd_set_stream(paml_amd_engine *e, void *hip_stream);
 
 /* com.z (treesub.c:1116 EncodeSeqs), nChara/CharaMap (tools.c:20, treesub.c:1218), com.fpatt, com.posG.
  * z is row-major [n_tips][n_patt] one byte per character code; with cleandata != 0 codes are states
- * 0..n-1 and the map may be NULL; otherwise n_chara[code] states listed in chara_map[code*n_states + k].
+ * 0..n-1 and the map may be NULL; otherwise n_chara[code] states listed in chara_map[code*n_states + k], each state at most once
+ * in a code's list (PAML_AMD_EINVAL otherwise).  Any table of up to 256 codes is accepted: codes need not put the single states
+ * first, may repeat a state set, or be empty (and then not occur in z).
  * gene_off has n_genes+1 non-decreasing entries from 0 to n_patt (NULL = one gene covering all patterns; a pattern shard of a
  * multi-GPU run may hold nothing of a gene: equal neighbours).  Uploaded once. */
 int paml_amd_set_tips(paml_amd_engine *e, const unsigned char *z, int cleandata, int n_codes, const int *n_chara,
@@ -332,6 +334,12 @@ int paml_amd_counters(const paml_amd_engine *e, long *n_eval, long *n_pmat);
 int paml_amd_debug_program(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons,
                            const unsigned char *scale_node, int keep_partials, const unsigned char *clean,
                            int *ops_out, int cap, int *max_stack);
+
+/* Host-only: the order in which set_tips keeps the n_codes (> 64) character codes of a table at 21..64 states — order_out[new code] =
+ * the caller's code — given the table and the nz codes of z (the per-tree kernel's rows beyond 64 codes).  Returns n_codes, or a
+ * negative error. */
+int paml_amd_debug_code_order(int n_states, int n_codes, const int *n_chara, const unsigned char *chara_map, const unsigned char *z,
+                              long nz, int *order_out);
 
 /* Host-only: generate (and with compile != 0 also hiprtc-compile for gfx950, no GPU needed) the kernel
  * specialised for a tree (paml_amd/csrc/jit.h).  compile: bit 0 = compile; bits 8..15 = n_states (4, 5 or 20 select the

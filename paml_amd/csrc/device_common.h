@@ -246,7 +246,8 @@ __device__ __forceinline__ void tip_lds(const double *tab, int code, int q, int 
 // A ring block holds a tip's rows of the codes 0 .. 63 (32 KB).  61 sense codons leave three of them to ambiguous triplets; a data set
 // with more (SetMapAmbiguity treesub.c:1218-1286: every distinct ambiguous triplet of a cleandata = 0 alignment is a code of its own) keeps
 // the others out of the block — paml_amd_set_tips numbers the ambiguous codes by frequency x set size, so the ones left out are the rare
-// and the small — and a lane that meets one adds up the rows of the code's states itself: the states are single-state codes < 64, the sum
+// and the small — and a lane that meets one adds up the rows of the code's states itself: state st's row is that of code st (set_tips puts
+// the single-state codes there; the engine takes this path only when every state has one, plain_codes >= n), the sum
 // runs over them in ascending order from 0, the order in which pmat_mfma_kernel forms a table row from CharaMap (codeml.c:3560-3567;
 // the engine takes this path only when every such code lists its states in ascending order, as SetMapAmbiguity does) — the same bits.
 // The state set is a 64-bit mask: from LDS (the unused three quarters of sPi, when there is one frequency vector) or one global load;

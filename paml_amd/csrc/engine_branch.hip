@@ -380,7 +380,7 @@ int paml_amd_eval_branch(paml_amd_engine *e, int node_b, int n_t, const double *
       // keep-partials evaluation — 128-pattern tiles, the operand ring — instead of the 64-pattern interpreter), compiled on the worker
       // thread while the interpreter serves, or at once when the caller asked for per-tree kernels.
       bool refill_done = false;
-      if (run_prog && e->jit_enabled && e->n_tips <= 207 && (e->n_codes <= 64 || e->amb_ascending)) {
+      if (run_prog && e->jit_enabled && e->n_tips <= 207 && (e->n_codes <= 64 || (e->amb_ascending && e->plain_codes >= n))) {      // (as launch_eval's)
          int n_store = 0;
          for (const Op &o : prog.ops) n_store += o.code == OP_STORE;
          Program full = prog;

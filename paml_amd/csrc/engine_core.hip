@@ -131,8 +131,15 @@ int paml_amd_set_tips(paml_amd_engine *e, const unsigned char *z, int cleandata,
       cmap.assign(chara_map, chara_map + (size_t)n_codes * n);
       for (int c = 0; c < n_codes; c++) {
          if (nch[c] < 0 || nch[c] > n) return fail(e, PAML_AMD_EINVAL, "set_tips: n_chara out of range");
-         for (int k = 0; k < nch[c]; k++)
-            if (cmap[(size_t)c * n + k] >= n) return fail(e, PAML_AMD_EINVAL, "set_tips: chara_map state out of range");
+         // (a state listed twice would count twice in the list-summing P(t) tables, as in ConditionalPNode, and once in the bit masks of
+         //  the branch-local and overflow paths: no reference table has one, and the engine refuses it rather than disagree with itself)
+         unsigned long long seen = 0;
+         for (int k = 0; k < nch[c]; k++) {
+            const int s = cmap[(size_t)c * n + k];
+            if (s >= n) return fail(e, PAML_AMD_EINVAL, "set_tips: chara_map state out of range");
+            if ((seen >> s) & 1ull) return fail(e, PAML_AMD_EINVAL, "set_tips: a state listed twice in one code's set");
+            seen |= 1ull << s;
+         }
       }
    }
    const size_t nz = (size_t)e->n_tips * e->n_patt;
@@ -140,18 +147,15 @@ int paml_amd_set_tips(paml_amd_engine *e, const unsigned char *z, int cleandata,
       if (z[i] >= n_codes) return fail(e, PAML_AMD_EINVAL, "set_tips: character code >= n_codes");
    // More than 64 codes at 21 .. 64 states (61 sense codons + more than three ambiguous triplets, SetMapAmbiguity treesub.c:1218-1286): the
    // per-tree kernel's ring block holds a tip's rows of the codes 0 .. 63, and a lane whose code is beyond them adds up the rows of the
-   // code's states itself (jit_tip_overflow) — as many LDS reads as the set has states.  Which ambiguous codes get the fast rows is the
-   // engine's choice: the codes past the single states are renumbered by (cells that hold the code) x (states of its set), descending,
-   // so that "missing" and whatever else is frequent sit below 64.  Invisible to the caller: codes only index the tip tables.
+   // code's states itself (jit_tip_overflow) — as many LDS reads as the set has states, from the rows of the codes 0 .. n-1, which must
+   // therefore be the single states.  The engine numbers the codes itself (code_order, engine_state.h): state s's single-state code
+   // at s, the others by (cells that hold the code) x (states of its set), descending, so that "missing" and whatever else is frequent
+   // sit below 64.  Invisible to the caller: codes only index the tip tables.
    std::vector<unsigned char> zperm;
    if (e->kk == KK_MFMA64 && n_codes > 64) {
-      int plain = 0;
-      while (plain < std::min(n, n_codes) && nch[plain] == 1 && cmap[(size_t)plain * n] == plain) plain++;
       std::vector<long> cnt(n_codes, 0);
       for (size_t i = 0; i < nz; i++) cnt[z[i]]++;
-      std::vector<int> order;      // old code numbers, in their new order
-      for (int c = 0; c < n_codes; c++) order.push_back(c);
-      std::stable_sort(order.begin() + plain, order.end(), [&](int x, int y) { return cnt[x] * nch[x] > cnt[y] * nch[y]; });
+      const std::vector<int> order = code_order(n, n_codes, nch.data(), cmap.data(), cnt.data());      // old code numbers, in their new order
       std::vector<unsigned char> new_of(n_codes);
       std::vector<int> nch2(n_codes);
       std::vector<unsigned char> cmap2((size_t)n_codes * n, 0);

@@ -317,13 +317,14 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
       // tiles, <= 168 VGPRs) measured SLOWER on MI355X (1.659 against 1.622 ms at C4, 4.73 against 4.63 ms with three classes — 40
       // spilled dwords and a third more LDS / DMA traffic per step) and was removed
       const int jw = 8;
-      // (more than 64 codes: the per-tree kernel sums the rows of a code's states in ascending order — e->amb_ascending, set_tips)
+      // (more than 64 codes: the per-tree kernel sums the rows of a code's states in ascending order — e->amb_ascending, set_tips — from
+      //  the rows of the codes 0 .. n-1, which must be the single states — e->plain_codes >= n)
       // LOAD programs (paml_amd_eval_dirty: one per set of clean nodes) get a kernel too (round 6) — compiled on the worker thread from the
       // SECOND time a set is asked for (minbranches' walk repeats its sets cycle after cycle; a set seen once is not worth 0.5 s of compiler),
       // the interpreter serving meanwhile; code-block pieces follow one program's order, so trees beyond 207 tips keep the interpreter there
       bool has_load = false;
       for (const Op &o : e->prog.ops) has_load = has_load || o.code == OP_LOAD;
-      if (e->jit_enabled && !(has_load && e->n_tips > 207) && (e->n_codes <= 64 || e->amb_ascending) && jit_supported(e->prog, e->n_tips, e->n_codes, e->n_pi, 6, jw * 16, true)) {
+      if (e->jit_enabled && !(has_load && e->n_tips > 207) && (e->n_codes <= 64 || (e->amb_ascending && e->plain_codes >= n)) && jit_supported(e->prog, e->n_tips, e->n_codes, e->n_pi, 6, jw * 16, true)) {
          const std::string key = "m" + std::to_string(n) + "c" + std::to_string(e->n_codes) + "w" + std::to_string(jw) + ":" + jit_program_key(e->prog, e->n_tips);
          // Large trees (> 120 ops: roughly more than 35 taxa): tens of thousands of instructions, many seconds of compiler time.  Unless the
          // caller asked to wait (PAML_AMD_JIT flag / PAML_AMD_JIT_SYNC), the kernel is built on a worker thread while the interpreter kernels

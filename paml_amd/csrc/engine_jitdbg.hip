@@ -33,6 +33,26 @@ int paml_amd_debug_program(int n_tips, int n_nodes, int root, const int *sons_pt
    return (int)p.ops.size();
 }
 
+int paml_amd_debug_code_order(int n_states, int n_codes, const int *n_chara, const unsigned char *chara_map, const unsigned char *z,
+                              long nz, int *order_out)
+{
+   if (n_states < 1 || n_states > 64 || n_codes < 1 || n_codes > 256 || !n_chara || !chara_map || (!z && nz > 0) || !order_out)
+      return PAML_AMD_EINVAL;
+   for (int c = 0; c < n_codes; c++) {
+      if (n_chara[c] < 0 || n_chara[c] > n_states) return PAML_AMD_EINVAL;
+      for (int k = 0; k < n_chara[c]; k++)
+         if (chara_map[(size_t)c * n_states + k] >= n_states) return PAML_AMD_EINVAL;
+   }
+   std::vector<long> cnt(n_codes, 0);
+   for (long i = 0; i < nz; i++) {
+      if (z[i] >= n_codes) return PAML_AMD_EINVAL;
+      cnt[z[i]]++;
+   }
+   const std::vector<int> order = code_order(n_states, n_codes, n_chara, chara_map, cnt.data());
+   std::copy(order.begin(), order.end(), order_out);
+   return n_codes;
+}
+
 int paml_amd_debug_jit(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons,
                        const unsigned char *scale_node, char *text_out, int cap, int compile)
 {

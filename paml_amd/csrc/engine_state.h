@@ -590,6 +590,28 @@ inline size_t tip_words(const paml_amd_engine *e)
 }
 inline int pint_words(const paml_amd_engine *e) { return e->kk == KK_MFMA64 ? 4096 : e->n * e->n; }
 
+// The order in which set_tips keeps the character codes of a table with more than 64 codes at 21..64 states (old code numbers, in their
+// new order; cnt = cells that hold each code).  Position s < n gets state s's single-state code — the first one where a table has
+// several — so that the rows of the codes 0 .. n-1 are the rows of the states, which the per-tree kernel's overflow path adds up
+// (jit_tip_overflow).  The other codes follow by cnt x (states of the set), descending, ties in their own order, and also fill the
+// position of a state without a code of its own (plain_codes < n then: the per-tree kernel is not used).  A table whose codes 0 .. n-1
+// are the states in order (SetMapAmbiguity) keeps them there and has the codes from n on sorted by the same key, as before.
+inline std::vector<int> code_order(int n, int n_codes, const int *nch, const unsigned char *cmap, const long *cnt)
+{
+   std::vector<int> order(n_codes, -1), rest;
+   std::vector<char> placed(n_codes, 0);
+   for (int c = 0; c < n_codes; c++) {
+      const int s = cmap[(size_t)c * n];
+      if (nch[c] == 1 && s < n_codes && order[s] < 0) { order[s] = c; placed[c] = 1; }
+   }
+   for (int c = 0; c < n_codes; c++)
+      if (!placed[c]) rest.push_back(c);
+   std::stable_sort(rest.begin(), rest.end(), [&](int x, int y) { return cnt[x] * nch[x] > cnt[y] * nch[y]; });
+   for (int i = 0, k = 0; i < n_codes; i++)
+      if (order[i] < 0) order[i] = rest[k++];
+   return order;
+}
+
 inline hipEvent_t get_event(paml_amd_engine *e)
 {
    hipEvent_t ev;

@@ -29,6 +29,7 @@ EXPORTS = [
     "paml_amd_eval_batch", "paml_amd_eval_adg", "paml_amd_beb_grid", "paml_amd_beb_grid_classes", "paml_amd_compress_patterns", "paml_amd_eval_device", "paml_amd_eval_dirty", "paml_amd_eval_branch", "paml_amd_node_posterior", "paml_amd_get_pmat", "paml_amd_get_partials", "paml_amd_get_scale",
     "paml_amd_device_count", "paml_amd_set_device", "paml_amd_shard_bounds", "paml_amd_max_ranks", "paml_amd_flush", "paml_amd_eigen_status", "paml_amd_comm_unique_id", "paml_amd_comm_init", "paml_amd_comm_destroy", "paml_amd_comm_info", "paml_amd_comm_library", "paml_amd_comm_stats", "paml_amd_get_partial_sums", "paml_amd_branch_counters", "paml_amd_branch_coef_hits", "paml_amd_branch_refill_kernels", "paml_amd_branch_kernel_ms",
     "paml_amd_jit_prebuild", "paml_amd_profile", "paml_amd_profile_read", "paml_amd_counters", "paml_amd_kernel_name", "paml_amd_debug_program", "paml_amd_debug_jit",
+    "paml_amd_debug_code_order",
 ]
 
 
@@ -520,6 +521,21 @@ def debug_program(tree, scale_node=None, keep=False, clean=None):
     if nops < 0:
         raise EngineError("debug_program failed (%d)" % nops)
     return [tuple(int(v) for v in r) for r in ops[:nops]], ms.value
+
+
+def debug_code_order(n_states, n_chara, chara_map, z):
+    """Host-only: the order in which set_tips keeps the codes of a table of more than 64 codes at 21..64 states: order[new code] = the
+    caller's code (paml_amd_debug_code_order)."""
+    L = lib()
+    nch = np.ascontiguousarray(n_chara, dtype=np.int32)
+    cm = np.ascontiguousarray(chara_map, dtype=np.uint8)
+    zz = np.ascontiguousarray(z, dtype=np.uint8).ravel()
+    order = np.zeros(len(nch), dtype=np.int32)
+    L.paml_amd_debug_code_order.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
+    rc = L.paml_amd_debug_code_order(int(n_states), len(nch), _p(nch), _p(cm), _p(zz), zz.size, _p(order))
+    if rc < 0:
+        raise EngineError("debug_code_order failed (%d)" % rc)
+    return order
 
 
 def debug_jit(tree, scale_node=None, compile=True, n_states=0, fused=None):

@@ -2,6 +2,7 @@
 written by tests/golden/make_golden.py, using the numpy host-side model set-up (paml_amd.models)."""
 from __future__ import annotations
 
+import copy
 import json
 import os
 import sys
@@ -293,6 +294,161 @@ def give_genes_their_own_models(pb, seed=0):
     pb.eigen = eig
     pb.eigen_of = np.ascontiguousarray(np.broadcast_to(np.arange(G, dtype=np.int32)[:, None, None], (G, pb.K, pb.n_labels)))
     return pb
+
+
+# ---- character-code tables (paml_amd_set_tips: n_chara[code], chara_map[code][k]) ---------------------------------------------------
+# The reference builds one layout (SetMapAmbiguity treesub.c:1218-1286): codes 0 .. n-1 are the single states in order, the ambiguous
+# codes follow, each listing its states in ascending order.  The ABI takes any table; these build the others.
+
+CODE_TABLE_SHAPES = ("reference", "permuted", "interleaved", "dup_single", "empty_unused", "no_single", "unordered")
+
+
+def _table_sets(sets, n):
+    n_chara = np.zeros(len(sets), dtype=np.int32)
+    cmap = np.zeros((len(sets), n), dtype=np.uint8)
+    for c, s in enumerate(sets):
+        n_chara[c] = len(s)
+        cmap[c, :len(s)] = s
+    return n_chara, cmap
+
+
+def nucleotide_table():
+    """The reference's nucleotide codes TCAGUYRMKSWHBVD-N? (tools.c:15-17): names, n_chara [18], chara_map [18][4]."""
+    names = "TCAGUYRMKSWHBVD-N?"
+    n_chara, cmap = _table_sets([["TCAG".index(b) for b in EQUATE_BASE[c]] for c in names], 4)
+    return names, n_chara, cmap
+
+
+def amino_acid_table():
+    """The reference's amino-acid codes ARNDCQEGHILKMFPSTWYV-*?X (tools.c:19; SetMapAmbiguity treesub.c:1240-1244: the four
+    non-residue characters stand for all 20 residues)."""
+    names = models.AAS + "-*?X"
+    n_chara, cmap = _table_sets([[i] for i in range(20)] + [list(range(20))] * 4, 20)
+    return names, n_chara, cmap
+
+
+def codon_amino_acid_table():
+    """The reference's table for amino acids coded as ambiguous codons (ModelAA2Codon, treesub.c:1274-1282): codes 0 .. 60 the sense
+    codons, 61 .. 63 empty (never in the data), 64 + i amino acid i = its synonymous sense codons in ascending order — 84 codes."""
+    from61 = models.sense_codons()
+    code = models._STD_CODE
+    sets = [[i] for i in range(61)] + [[]] * 3
+    for aa in models.AAS:
+        sets.append([i for i, c in enumerate(from61) if code[c] == aa])
+    names = ["".join(models.BASES[(c >> s) & 3] for s in (4, 2, 0)) for c in from61] + ["", "", ""] + list(models.AAS)
+    n_chara, cmap = _table_sets(sets, 61)
+    return names, n_chara, cmap
+
+
+def code_table(n, n_codes, shape="reference", seed=0):
+    """A character-code table of `n_codes` codes over `n` states in one of CODE_TABLE_SHAPES:
+       reference     codes 0..n-1 the single states in order, then the ambiguous codes ("missing" first), states ascending
+       permuted      the single states shuffled among the codes 0..n-1
+       interleaved   ambiguous codes placed among and before the single states (code 0 is "missing")
+       dup_single    a second single-state code for some states (baseml's U = T)
+       empty_unused  empty codes that never occur in z (codes 61 .. 63 of the ModelAA2Codon table)
+       no_single     one state has no single-state code: it occurs only inside ambiguous sets
+       unordered     ambiguous sets listed in descending or random order (never ascending)
+    Returns (n_chara [n_codes] int32, chara_map [n_codes][n] uint8, code_of): code_of maps a frozenset of states to the codes that
+    stand for it (ascending)."""
+    assert shape in CODE_TABLE_SHAPES, shape
+    rng = np.random.default_rng(seed)
+    miss = int(rng.integers(n)) if shape == "no_single" else -1
+    singles = [[s] for s in range(n) if s != miss]
+    extra = n_codes - len(singles)
+    need = 0 if shape in ("reference", "permuted") else (2 if shape == "no_single" else 1)
+    if extra < need:
+        raise ValueError("code_table: %s needs more than %d codes at %d states" % (shape, n_codes, n))
+    n_dup = min(extra, max(1, n // 4)) if shape == "dup_single" else 0
+    n_empty = min(extra, 3) if shape == "empty_unused" else 0
+    dups = [[int(s)] for s in rng.choice(n, size=n_dup, replace=False)]
+    n_amb = extra - n_dup - n_empty
+    amb = [list(range(n))] if n_amb else []                          # "missing": every state
+    while len(amb) < n_amb:
+        size = int(rng.integers(2, min(n, 16) + 1))
+        s = sorted(int(x) for x in rng.choice(n, size=size, replace=False))
+        if miss >= 0 and len(amb) == 1 and miss not in s:             # the state without a code of its own: in a small set too
+            s = sorted(set(s[1:]) | {miss})
+        amb.append(s)
+    if shape == "unordered":
+        for i, s in enumerate(amb):
+            r = s[::-1] if i % 2 == 0 else [s[j] for j in rng.permutation(len(s))]
+            amb[i] = r if r != s else s[::-1]
+    if shape == "permuted":
+        singles = [singles[i] for i in rng.permutation(len(singles))]
+        if n > 1 and all(s == [i] for i, s in enumerate(singles)):
+            singles = singles[1:] + singles[:1]
+    if shape == "interleaved":
+        others = singles + amb[1:]
+        sets = [amb[0]] + [others[i] for i in rng.permutation(len(others))]
+    else:
+        sets = singles + [[]] * n_empty + dups + amb
+    n_chara, cmap = _table_sets(sets, n)
+    return n_chara, cmap, table_code_of(n_chara, cmap)
+
+
+def table_code_of(n_chara, chara_map):
+    """code_of (frozenset of states -> the codes that stand for it, ascending) of a table."""
+    code_of = {}
+    for c in range(len(n_chara)):
+        if n_chara[c]:
+            code_of.setdefault(frozenset(int(x) for x in chara_map[c, :n_chara[c]]), []).append(c)
+    return code_of
+
+
+def with_table(pb, n_chara, chara_map, seed=0, amb_rate=0.1):
+    """pb's tips re-encoded through the table (n_chara, chara_map): every cell keeps its state set where the table has a code for it
+    (one of them at random where it has several), else it takes the smallest set of the table that contains it (a state without a
+    single-state code).  Then (amb_rate > 0) a fraction `amb_rate` of the cells, and at least one cell per non-empty code, take a random
+    non-empty code, so that every code that may occur does."""
+    rng = np.random.default_rng(seed)
+    code_of = table_code_of(n_chara, chara_map)
+    new_of = []
+    for c in range(pb.n_codes):
+        s = frozenset(int(x) for x in pb.chara_map[c, :pb.n_chara[c]])
+        if s in code_of:
+            new_of.append(code_of[s])
+            continue
+        sup = [k for k in code_of if s <= k]
+        assert sup, "with_table: no code of the table holds %s" % sorted(s)
+        best = min(len(k) for k in sup)
+        new_of.append(sorted(c2 for k in sup if len(k) == best for c2 in code_of[k]))
+    z = np.zeros_like(pb.z)
+    pick = rng.random(pb.z.shape)
+    for old in np.unique(pb.z):
+        cand = np.asarray(new_of[old], dtype=np.uint8)
+        m = pb.z == old
+        z[m] = cand[np.minimum((pick[m] * len(cand)).astype(int), len(cand) - 1)]
+    usable = np.array([c for c in range(len(n_chara)) if n_chara[c] > 0], dtype=np.uint8)
+    z = np.where(rng.random(z.shape) < amb_rate, rng.choice(usable, size=z.shape), z).astype(np.uint8)
+    if 0 < amb_rate and len(usable) <= z.size:
+        z.flat[rng.permutation(z.size)[:len(usable)]] = rng.permutation(usable)
+    q = copy.copy(pb)
+    q.z = np.ascontiguousarray(z)
+    q.cleandata = 0
+    q.n_chara = np.ascontiguousarray(n_chara, dtype=np.int32)
+    q.chara_map = np.ascontiguousarray(chara_map, dtype=np.uint8)
+    return q
+
+
+def with_code_table(pb, n_codes, shape="reference", seed=0, amb_rate=0.1):
+    """pb re-encoded through code_table(pb.n, n_codes, shape, seed) (see with_table)."""
+    n_chara, cmap, _ = code_table(pb.n, n_codes, shape, seed)
+    return with_table(pb, n_chara, cmap, seed=seed + 1, amb_rate=amb_rate)
+
+
+def relabel_codes(pb, perm):
+    """pb with code c renamed perm[c]: the rows of n_chara / chara_map move, z is remapped; the order within every set is untouched."""
+    perm = np.asarray(perm, dtype=np.int64)
+    assert sorted(perm.tolist()) == list(range(pb.n_codes))
+    q = copy.copy(pb)
+    q.n_chara = np.zeros_like(pb.n_chara)
+    q.chara_map = np.zeros_like(pb.chara_map)
+    q.n_chara[perm] = pb.n_chara
+    q.chara_map[perm] = pb.chara_map
+    q.z = np.ascontiguousarray(perm.astype(np.uint8)[pb.z])
+    q.cleandata = 0
+    return q
 
 
 def ymd_names(text):

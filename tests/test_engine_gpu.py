@@ -742,6 +742,12 @@ def test_abi_error_behaviour():
         bad = pb.z.copy()
         bad[0, 0] = 200
         eng.set_tips(bad, pb.weights, cleandata=True)
+    with pytest.raises(EngineError, match="listed twice"):      # a code whose set names state 3 twice ({3, 3})
+        nch = np.array([1, 1, 1, 1, 2], dtype=np.int32)
+        cm = np.zeros((5, 4), dtype=np.uint8)
+        cm[:4, 0] = np.arange(4)
+        cm[4, :2] = 3
+        eng.set_tips(pb.z, pb.weights, cleandata=0, n_chara=nch, chara_map=cm)
     eng.load(pb)
     assert np.isfinite(eng.eval(pb.tree.branch)["lnL"])
     with pytest.raises(EngineError, match="KEEP_PARTIALS"):
