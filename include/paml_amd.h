@@ -369,6 +369,41 @@ const char *paml_amd_kernel_name(const paml_amd_engine *e);
 int paml_amd_compress_patterns(int n_seq, int n_sites, int width, const unsigned char *chars, const int *gene, int *n_patt,
                                int *first_site, double *weights, int *pose);
 
+/* ---- Pairwise maximum-likelihood comparisons (codeml runmode = -2; PairwiseCodon codeml.c:4344-4604, Goldman & Yang 1994).
+ * The reference takes the ns (ns - 1) / 2 pairs one after the other, each a search over (t, kappa, omega) whose every function call
+ * (lfun2dSdN codeml.c:4219-4264) decomposes a rate matrix on one core.  Here a PAIR SET lives on an engine whose tips are clean data
+ * (set_tips with cleandata != 0; no tree is needed), and the unit of work is a batch of ELEMENTS (pair, t, kappa, omega): all pairs'
+ * gradient and line-search points of a round of the host's searches in one call.
+ *
+ * pairset_create: pairs p = (seq_a[p], seq_b[p]), 0-based tips.  Counts the pairs' tables fp[max(za, zb)][min(za, zb)] += w_h
+ *   (codeml.c:4407-4413) on the device and keeps them resident; sizes the arena of eigen systems once (a quarter of the free device
+ *   memory, at most 1 GiB; the environment variable PAML_AMD_PAIR_ARENA_MB gives another size in MiB).  PAML_AMD_EINVAL for unclean
+ *   tips, a pair of a sequence with itself, indices out of range.  Destroy the pair set before its engine.
+ * pairset_get_counts: fp[n_pairs][n * n] (row = the larger state) and ls_pair[n_pairs] = the pairs' numbers of sites (either may be
+ *   NULL) — what the host needs once for the pairs' codon frequencies (codeml.c:4448-4453), and the parity accessor.
+ * pairset_set_pi: pi[n_pairs][n], the codon frequencies of every pair (GetCodonFreqs2 codeml.c:4169-4216 is the host's).
+ * pairset_set_pattern: the elements a rate matrix can have — nnz positions (row[k] >= col[k], each once, the n diagonal positions among
+ *   them: the layout of paml_amd_set_eigen_qrev_batch_sparse) and for each flags[k]: bit 0 = a transition (the rate carries kappa),
+ *   bit 1 = nonsynonymous (omega).  Q_ij = flags' factors x pi_j, scaled to one substitution per codon (eigenQcodon codeml.c:3229-3316).
+ * pairset_eval: lnL[i] = +sum_{j >= k} fp[j][k] log(pi_j P_jk(t_i)) of element i (lfun2dSdN returns -lnL), f <= 0 floored at 1e-70 as
+ *   there (codeml.c:4256-4260).  Only (pair, t, kappa, omega) crosses PCIe; the rate matrices are built, decomposed (the Jacobi of
+ *   paml_amd_set_eigen_qrev_batch, on the pair set's own arena — not the engine's table of eigen sets) and used on the device.  Elements
+ *   of one call with identical (pair, kappa, omega) share one decomposition.  A call of any size is walked in chunks of what the arena
+ *   holds: never PAML_AMD_ENOMEM for n_elem.  An element's lnL has the same bits in whatever call, chunk or company it is evaluated.
+ *   Synchronous.  PAML_AMD_ENOCONV when a decomposition reached its sweep limit: every other element's lnL is valid, and
+ *   pairset_failed lists the indices (into the last call's elements; returns their number, writes at most cap) for the host to redo.
+ * pairset_counters: elements evaluated, decompositions done, chunks walked so far; the arena's capacity in eigen systems. */
+typedef struct paml_amd_pairset paml_amd_pairset;
+int paml_amd_pairset_create(paml_amd_engine *e, paml_amd_pairset **out, int n_pairs, const int *seq_a, const int *seq_b);
+void paml_amd_pairset_destroy(paml_amd_pairset *ps);
+int paml_amd_pairset_get_counts(paml_amd_pairset *ps, double *fp, double *ls_pair);
+int paml_amd_pairset_set_pi(paml_amd_pairset *ps, const double *pi);
+int paml_amd_pairset_set_pattern(paml_amd_pairset *ps, int nnz, const int *row, const int *col, const unsigned char *flags);
+int paml_amd_pairset_eval(paml_amd_pairset *ps, long n_elem, const int *pair, const double *t, const double *kappa, const double *omega,
+                          double *lnL);
+int paml_amd_pairset_failed(const paml_amd_pairset *ps, long *idx, long cap);
+int paml_amd_pairset_counters(const paml_amd_pairset *ps, long *n_elem, long *n_decomp, long *n_chunks, long *arena_slots);
+
 #ifdef __cplusplus
 }
 #endif

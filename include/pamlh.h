@@ -160,6 +160,25 @@ const int *pamlh_pose(const pamlh *p, int *n_sites);
 const double *pamlh_class_omega(const pamlh *p);
 int pamlh_positive_classes(const pamlh *p);             /* trailing classes that allow omega > 1 (2 for branch-site: 2a + 2b) */
 
+/* ---- runmode = -2 (codeml, seqtype = 1): maximum-likelihood t, kappa, omega and dN, dS for every pair of sequences (PairwiseCodon
+ * codeml.c:4344-4604, lfun2dSdN 4219-4264).  pamlh_load* accepts such a control file without a tree file and, like the reference
+ * (codeml.c:1849-1852), deletes every site with a gap or an ambiguity; NSsites, alpha, aaDist, hkyREV, CodonFreq > 3, several genes,
+ * runmode = -3 and seqtype 2 / 3 are refused by name.  The pairs are numbered in the reference's order: (2,1), (3,1), (3,2), (4,1) ...
+ * pamlh_pairwise: the searches of all pairs in lock step on the GPU — every round's gradient and line-search points of all unfinished
+ *   pairs are one paml_amd_pairset_eval call; bounds t [1e-5, 50], kappa [0.4, 999], omega [0.001, 99]; fix_kappa / fix_omega honoured;
+ *   deterministic starting values (pamlh_pairwise.c states the rule).  out[n_pairs][9] = t, kappa, omega, lnL, S, N, dN, dS (as
+ *   eigenQcodon(2, ...) at codeml.c:4522: the code behind pamlh_dnds), likelihood evaluations used.  counters (NULL or 4 entries): elements
+ *   evaluated, decompositions done, evaluate calls, elements done again on the host after PAML_AMD_ENOCONV.
+ * pamlh_pairwise_freqs (host only): the codon frequencies of a pair from its count table fp[n][n] (row = the larger state) and its number
+ *   of sites, by GetCodonFreqs2 (codeml.c:4169-4216).
+ * pamlh_pairwise_write (host only): 2ML.t, 2ML.dN, 2ML.dS and the pair table of rst, in the reference's layout, into `dir`. */
+int pamlh_is_pairwise(const pamlh *p);
+int pamlh_pairwise_n(const pamlh *p);      /* ns (ns - 1) / 2 */
+int pamlh_pairwise(pamlh *p, double *out, long *counters, int verbose);
+int pamlh_pairwise_freqs(const pamlh *p, const double *fp, double ls, double *pi);
+int pamlh_pairwise_write(pamlh *p, const double *out, const char *dir);
+const char *pamlh_seq_name(const pamlh *p, int i);
+
 /* Write the reference's `lnf` file layout (print_lnf_site treesub.c:7598) for the last pamlh_eval_gpu. */
 int pamlh_write_lnf(const pamlh *p, const char *path, const double *lnf);
 

@@ -4,6 +4,29 @@
 #include "engine_state.h"
 #include "eigen_kernels.h"
 
+namespace paml_amd {
+// The batched Jacobi launch (the kernel has its home here): a.max_sweeps is filled in; one workgroup per matrix on the engine's stream.  Also
+// called by the pair sets (engine_pairwise.hip), whose eigen systems live in an arena of their own.
+int launch_eigen_qrev(paml_amd_engine *e, EigenQrevArgs a, int n_sets)
+{
+   if (!e->eigen_attr_set) {
+      for (const void *fn : {(const void *)eigen_qrev_kernel<0>, (const void *)eigen_qrev_kernel<20>, (const void *)eigen_qrev_kernel<60>, (const void *)eigen_qrev_kernel<62>})
+         HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EIG_LDS_BYTES));
+      e->eigen_attr_set = true;
+   }
+   static const int sweep_limit = getenv("PAML_AMD_EIGEN_SWEEP_LIMIT") ? std::max(1, atoi(getenv("PAML_AMD_EIGEN_SWEEP_LIMIT"))) : 40;
+   a.max_sweeps = sweep_limit;
+   // (the orders with a register form: R^T in a ninth wave's registers)
+   const int N_even = (a.n + 1) & ~1;
+   if (N_even == 62) hipLaunchKernelGGL(eigen_qrev_kernel<62>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
+   else if (N_even == 60) hipLaunchKernelGGL(eigen_qrev_kernel<60>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
+   else if (N_even == 20) hipLaunchKernelGGL(eigen_qrev_kernel<20>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
+   else hipLaunchKernelGGL(eigen_qrev_kernel<0>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
+   HIPCHK(hipGetLastError());
+   return 0;
+}
+}  // namespace paml_amd
+
 extern "C" {
 
 int paml_amd_create(paml_amd_engine **out, int n_states, int n_tips, int n_patt, int max_classes, int n_genes,
@@ -452,26 +475,13 @@ static int eigen_qrev_batch(paml_amd_engine *e, int n_sets, const int *set_ids, 
       HIPCHK(hipHostMalloc((void **)&e->h_eig_fail, 64, hipHostMallocDefault));
       *e->h_eig_fail = 0;
    }
-   if (!e->eigen_attr_set) {
-      for (const void *fn : {(const void *)eigen_qrev_kernel<0>, (const void *)eigen_qrev_kernel<20>, (const void *)eigen_qrev_kernel<60>, (const void *)eigen_qrev_kernel<62>})
-         HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EIG_LDS_BYTES));
-      e->eigen_attr_set = true;
-   }
    EigenQrevArgs a{};
    double *const *dptr = (double *const *)(e->d_eq_pi.p + npi + nsc);
    a.n = (int)n; a.Q = e->d_eq_q.p; a.pi = e->d_eq_pi.p; a.scale = e->d_eq_pi.p + npi;
    a.nnz = nnz; a.rc = nnz > 0 ? e->d_eq_rc.p : nullptr;
    a.U = dptr; a.V = dptr + n_sets; a.Root = dptr + 2 * (size_t)n_sets; a.sweeps = e->d_eq_sweeps.p; a.fail = e->h_eig_fail;
-   static const int sweep_limit = getenv("PAML_AMD_EIGEN_SWEEP_LIMIT") ? std::max(1, atoi(getenv("PAML_AMD_EIGEN_SWEEP_LIMIT"))) : 40;
-   a.max_sweeps = sweep_limit;
    if (e->eigen_warm) { a.R0 = dptr + 3 * (size_t)n_sets; a.Rout = dptr + 4 * (size_t)n_sets; }
-   // (the orders with a register form: R^T in a ninth wave's registers)
-   const int N_even = ((int)n + 1) & ~1;
-   if (N_even == 62) hipLaunchKernelGGL(eigen_qrev_kernel<62>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
-   else if (N_even == 60) hipLaunchKernelGGL(eigen_qrev_kernel<60>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
-   else if (N_even == 20) hipLaunchKernelGGL(eigen_qrev_kernel<20>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
-   else hipLaunchKernelGGL(eigen_qrev_kernel<0>, dim3(n_sets), dim3(EIG_NT), EIG_LDS_BYTES, e->stream, a);
-   HIPCHK(hipGetLastError());
+   if (int rc = launch_eigen_qrev(e, a, n_sets)) return rc;
    // (the host arrays were pageable: the runtime has staged them on return; the evaluations that follow on the engine's stream see the sets)
    e->n_eigen_device += n_sets;
    e->eq_last_batch = n_sets;

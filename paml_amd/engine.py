@@ -30,6 +30,8 @@ EXPORTS = [
     "paml_amd_device_count", "paml_amd_set_device", "paml_amd_shard_bounds", "paml_amd_max_ranks", "paml_amd_flush", "paml_amd_eigen_status", "paml_amd_comm_unique_id", "paml_amd_comm_init", "paml_amd_comm_destroy", "paml_amd_comm_info", "paml_amd_comm_library", "paml_amd_comm_stats", "paml_amd_get_partial_sums", "paml_amd_branch_counters", "paml_amd_branch_coef_hits", "paml_amd_branch_refill_kernels", "paml_amd_branch_kernel_ms",
     "paml_amd_jit_prebuild", "paml_amd_profile", "paml_amd_profile_read", "paml_amd_counters", "paml_amd_kernel_name", "paml_amd_debug_program", "paml_amd_debug_jit",
     "paml_amd_debug_code_order",
+    "paml_amd_pairset_create", "paml_amd_pairset_destroy", "paml_amd_pairset_get_counts", "paml_amd_pairset_set_pi", "paml_amd_pairset_set_pattern",
+    "paml_amd_pairset_eval", "paml_amd_pairset_failed", "paml_amd_pairset_counters",
 ]
 
 
@@ -44,7 +46,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -460,6 +462,76 @@ class Engine:
         a, b = C.c_long(), C.c_long()
         self._L.paml_amd_counters(self._h, C.byref(a), C.byref(b))
         return dict(n_eval=a.value, n_pmat=b.value)
+
+
+class PairSet:
+    """Pairwise ML comparisons on an engine's clean tips (paml_amd_pairset_*): pairs[k] = (a, b), 0-based sequences."""
+
+    def __init__(self, eng: Engine, pairs):
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        a, b = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        L = eng._L
+        L.paml_amd_pairset_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
+        L.paml_amd_pairset_destroy.argtypes = [C.c_void_p]
+        L.paml_amd_pairset_destroy.restype = None
+        L.paml_amd_pairset_get_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.paml_amd_pairset_set_pi.argtypes = [C.c_void_p, C.c_void_p]
+        L.paml_amd_pairset_set_pattern.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.paml_amd_pairset_eval.argtypes = [C.c_void_p, C.c_long] + [C.c_void_p] * 5
+        L.paml_amd_pairset_failed.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
+        L.paml_amd_pairset_counters.argtypes = [C.c_void_p] + [C.POINTER(C.c_long)] * 4
+        self._eng, self._L, self.n, self.n_pairs = eng, L, eng.n, len(pr)
+        h = C.c_void_p()
+        eng._chk(L.paml_amd_pairset_create(eng._h, C.byref(h), len(pr), _p(a), _p(b)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.paml_amd_pairset_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def counts(self):
+        """(fp[n_pairs][n][n] with row = the larger state, ls_pair[n_pairs])."""
+        fp, ls = np.zeros((self.n_pairs, self.n, self.n)), np.zeros(self.n_pairs)
+        self._eng._chk(self._L.paml_amd_pairset_get_counts(self._h, _p(fp), _p(ls)))
+        return fp, ls
+
+    def set_pi(self, pi):
+        pi = np.ascontiguousarray(pi, dtype=np.float64)
+        assert pi.shape == (self.n_pairs, self.n)
+        self._eng._chk(self._L.paml_amd_pairset_set_pi(self._h, _p(pi)))
+
+    def set_pattern(self, row, col, flags):
+        row, col = np.ascontiguousarray(row, dtype=np.int32), np.ascontiguousarray(col, dtype=np.int32)
+        fl = np.ascontiguousarray(flags, dtype=np.uint8)
+        assert len(row) == len(col) == len(fl)
+        self._eng._chk(self._L.paml_amd_pairset_set_pattern(self._h, len(row), _p(row), _p(col), _p(fl)))
+
+    def eval(self, pair, t, kappa, omega):
+        """lnL of the elements (pair[i], t[i], kappa[i], omega[i]); raises EngineError (code -5) if a decomposition did not converge —
+        failed() then lists those elements."""
+        pr = np.ascontiguousarray(pair, dtype=np.int32)
+        t, k, w = (np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), pr.shape)) for x in (t, kappa, omega))
+        out = np.zeros(len(pr))
+        self._eng._chk(self._L.paml_amd_pairset_eval(self._h, len(pr), _p(pr), _p(t), _p(k), _p(w), _p(out)))
+        return out
+
+    def failed(self):
+        n = self._L.paml_amd_pairset_failed(self._h, None, 0)
+        idx = np.zeros(max(n, 1), dtype=np.int64)
+        self._L.paml_amd_pairset_failed(self._h, _p(idx), n)
+        return idx[:n]
+
+    def counters(self):
+        v = [C.c_long() for _ in range(4)]
+        self._L.paml_amd_pairset_counters(self._h, *[C.byref(x) for x in v])
+        return dict(n_elem=v[0].value, n_decomp=v[1].value, n_chunks=v[2].value, arena_slots=v[3].value)
 
 
 COMM_ID_BYTES = 128

@@ -102,6 +102,7 @@ struct pamlh {
    int *nh_label, nh_nbtype;   /* nhomo = 5 / fix_kappa = 2: the tree file's '#' labels name the frequency / rate sets; number of branch types */
    int *rate_label, n_brate;   /* clock = 2: rate class of the branch above every node, number of classes */
    int malpha;               /* Malpha: a gamma shape per gene; rate[] then holds [gene][class] */
+   int pairwise;             /* runmode = -2: pairwise comparisons (pamlh_pairwise.c); no tree, no model state */
    int opt_transformed;      /* pamlh_optimize is iterating on transformed proportions (pamlh_opt.c) */
    int aadist, n_omega_type;
    signed char omega_class[26][26];
@@ -153,6 +154,9 @@ int pamlh_engine_ready(pamlh *p);
 int pamlh_engine_model(pamlh *p);      /* pi, eigen systems and class tables of the current model state -> engine */
 int pamlh_model_feasible(const pamlh *p);
 int pamlh_x_to_branches(const pamlh *p, const double *x, double *branch);
+void pamlh_dnds_one(const pamlh *p, const double *pi, double kappa, double omega, double t, double ls, double *N, double *S, double *dN, double *dS);
+double pamlh_codon_q(const pamlh *p, const double *pi, double kappa, double omega, double *Q);
+int pamlh_codon_pattern_flags(const pamlh *p, const int **row, const int **col, unsigned char *flags);      /* flags: room for 704 */
 pamlh *pamlh_state_clone(const pamlh *p);
 void pamlh_state_free(pamlh *q);
 #endif

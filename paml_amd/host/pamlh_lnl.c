@@ -7,7 +7,9 @@
  * else from in.codeml / in.baseml beside the ctl (the reference's "-1 x..." single-evaluation recipe, treesub.c:4057),
  * else the ctl's initial values; evaluates lnL through libpaml_amd.so; prints `lnL = ...` like the reference and
  * writes the per-pattern `lnf` file in the reference's layout.  With --optimize the vector is the starting point of a
- * maximum-likelihood search (pamlh_optimize: BFGS with batched finite differences) and the estimates are printed. */
+ * maximum-likelihood search (pamlh_optimize: BFGS with batched finite differences) and the estimates are printed.
+ * A control file with runmode = -2 (codeml) is the pairwise comparison instead: the estimates of every pair are printed and 2ML.t,
+ * 2ML.dN, 2ML.dS and rst are written into the working directory in the reference's layout (pamlh_pairwise). */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -169,6 +171,24 @@ int main(int argc, char **argv)
    if (gpus > 0 && spawn_ranks(gpus, device, &rank, comm_id)) { fprintf(stderr, "error: could not start %d ranks (GPUs visible: %d; librccl.so.1 present?)\n", gpus, paml_amd_device_count()); return 1; }
    if (pamlh_load_with(&p, argv[2], argv[1], itree, over, err, sizeof(err))) { fprintf(stderr, "error: %s\n", err); return 1; }
    if (gpus > 0 && pamlh_set_shard(p, rank, gpus, comm_id)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+   if (pamlh_is_pairwise(p)) {      /* runmode = -2: all pairs' searches in lock step; 2ML.t, 2ML.dN, 2ML.dS and rst as the reference writes them */
+      const int npair = pamlh_pairwise_n(p);
+      double *res = (double *)malloc((size_t)npair * 9 * sizeof(double));
+      long cnt[4] = {0, 0, 0, 0};
+      int q, is, js;
+      if (gpus > 0) { fprintf(stderr, "error: --gpus does not apply to runmode = -2 (pairs are not sharded yet)\n"); return 1; }
+      if (pamlh_pairwise(p, res, cnt, 0) || pamlh_pairwise_write(p, res, ".")) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      printf("pairwise comparison (Goldman & Yang 1994): %d pairs, %ld likelihood elements in %ld calls, %ld decompositions\n", npair, cnt[0], cnt[2], cnt[1]);
+      for (is = 1, q = 0; q < npair; is++)
+         for (js = 0; js < is; js++, q++) {
+            const double *o = res + (size_t)q * 9;
+            printf("\n%d (%s) ... %d (%s)\nlnL =%12.6f\n %8.5f %8.5f %8.5f\nt= %6.4f  S= %7.1f  N= %7.1f  dN/dS= %7.4f  dN =%7.4f  dS =%7.4f\n",
+                   is + 1, pamlh_seq_name(p, is), js + 1, pamlh_seq_name(p, js), o[3], o[0], o[1], o[2], o[0], o[4], o[5], o[2], o[6], o[7]);
+         }
+      free(res);
+      pamlh_free(p);
+      return 0;
+   }
    pamlh_dims(p, NULL, NULL, &npatt, NULL, NULL, NULL, NULL, NULL, &np, &ntime);
    if (gpus > 0 && (ancestral || pamlh_mgene(p) == 1)) { fprintf(stderr, "error: --gpus gives lnL and estimates; per-site outputs and Mgene = 1 need the whole alignment on one GPU\n"); return 1; }
    if (pamlh_mgene(p) == 1) {      /* separate analyses: every gene on its own (start values: the control file's), lnL summed */

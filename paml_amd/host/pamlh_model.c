@@ -309,8 +309,8 @@ int pamlh_load_with(pamlh **out, const char *ctl_path, const char *program, int 
    if (overrides && (rc = pamlh_ctl_override(p, overrides))) goto bad;
    if (!(v = pamlh_opt(p, "seqfile"))) { rc = pamlh_fail(p, "no seqfile in the control file"); goto bad; }
    resolve(p, v, p->seqfile, sizeof(p->seqfile));
-   if (!(v = pamlh_opt(p, "treefile"))) { rc = pamlh_fail(p, "no treefile in the control file"); goto bad; }
-   resolve(p, v, p->treefile, sizeof(p->treefile));
+   if ((v = pamlh_opt(p, "treefile"))) resolve(p, v, p->treefile, sizeof(p->treefile));
+   else if ((int)pamlh_optd(p, "runmode", 0) >= 0) { rc = pamlh_fail(p, "no treefile in the control file"); goto bad; }      /* (pairwise comparisons need no tree) */
    p->seqtype = p->is_codeml ? (int)pamlh_optd(p, "seqtype", 1) : 0;
    if (p->seqtype == 3) { p->translate = 1; p->seqtype = 2; p->icode = (int)pamlh_optd(p, "icode", 0); }      /* codons translated on reading, then an amino-acid analysis (ReadSeq treesub.c:886-892) */
    p->codonfreq = (int)pamlh_optd(p, "CodonFreq", 0);
@@ -330,7 +330,12 @@ int pamlh_load_with(pamlh **out, const char *ctl_path, const char *program, int 
    /* options that would change the analysis and are not covered: refused, never ignored */
    {
       const int runmode = (int)pamlh_optd(p, "runmode", 0), ndata = (int)pamlh_optd(p, "ndata", 1);
-      if (runmode != 0) { rc = pamlh_fail(p, "runmode = %d is not supported (0: the trees of the tree file; tree search and pairwise comparisons are outside this library)", runmode); goto bad; }
+      /* runmode = -2: pairwise maximum-likelihood dN / dS (PairwiseCodon codeml.c:4344) — codeml with codon sequences only; no tree is read */
+      if (runmode == -2 && p->is_codeml) {
+         if (p->seqtype != 1) { rc = pamlh_fail(p, "runmode = -2 is supported for codon sequences only (seqtype = 1; PairwiseAA, seqtype = 2 / 3, is not)"); goto bad; }
+         p->pairwise = 1;
+      }
+      else if (runmode != 0) { rc = pamlh_fail(p, "runmode = %d is not supported (0: the trees of the tree file, -2: pairwise comparisons of codon sequences with codeml; tree search and runmode = -3 are outside this library)", runmode); goto bad; }
       if (ndata > 1) { rc = pamlh_fail(p, "ndata = %d is not supported (one data set per sequence file)", ndata); goto bad; }
       if ((int)pamlh_optd(p, "hkyREV", 0)) { rc = pamlh_fail(p, "hkyREV = 1 is not supported"); goto bad; }
       if ((int)pamlh_optd(p, "nparK", 0)) { rc = pamlh_fail(p, "nparK = %d is not supported", (int)pamlh_optd(p, "nparK", 0)); goto bad; }
@@ -396,6 +401,7 @@ int pamlh_load_with(pamlh **out, const char *ctl_path, const char *program, int 
       if (p->npi == 2) p->npi = 3 + p->n - 1;      /* FMutSel with estFreq: the codon fitnesses */
       else if (p->npi == -1) p->npi = p->n - 1;    /* Fcodon with estFreq */
       p->aadist = (int)pamlh_optd(p, "aaDist", 0);
+      if (p->pairwise && p->aadist) { rc = pamlh_fail(p, "runmode = -2: aaDist = %d is not supported for pairwise comparisons (codeml.c:1612)", p->aadist); goto bad; }
       if (p->aadist < -6 || p->aadist > 7) { rc = pamlh_fail(p, "aaDist = %d is not supported (1..6 / -1..-6: distance files, 7: AAClasses)", p->aadist); goto bad; }
       if (p->aadist == 7) {
          if (p->nssites || (p->model != 0 && p->model != 2) || p->mg) { rc = pamlh_fail(p, "aaDist = 7 goes with NSsites = 0, model 0 or 2 and CodonFreq <= 3"); goto bad; }
@@ -456,6 +462,24 @@ int pamlh_load_with(pamlh **out, const char *ctl_path, const char *program, int 
       if (p->model > UNREST) { rc = pamlh_fail(p, "baseml model %d is not supported", p->model); goto bad; }
    }
    else { rc = pamlh_fail(p, "seqtype %d is not supported", p->seqtype); goto bad; }
+   if (p->pairwise) {
+      /* what PairwiseCodon covers here: one kappa, one omega, codon frequencies from the pair's counts (CodonFreq 0-3) */
+      if (p->nssites || p->m2a_rel) { rc = pamlh_fail(p, "runmode = -2: NSsites = %d does not apply to pairwise comparisons (use NSsites = 0)", p->m2a_rel ? 22 : p->nssites); goto bad; }
+      if (p->model) { rc = pamlh_fail(p, "runmode = -2: model = %d does not apply to pairwise comparisons (use model = 0)", p->free_ratio ? 1 : p->model); goto bad; }
+      if (p->alpha0 > 0 || !p->fix_alpha) { rc = pamlh_fail(p, "runmode = -2: alpha (gamma rates among sites) does not apply to pairwise comparisons: fix alpha at 0"); goto bad; }
+      if (p->aadist) { rc = pamlh_fail(p, "runmode = -2: aaDist = %d is not supported for pairwise comparisons (codeml.c:1612)", p->aadist); goto bad; }
+      if (p->codonf_model > 3) { rc = pamlh_fail(p, "runmode = -2: CodonFreq = %d (the MG and FMutSel families) is not supported for pairwise comparisons (CodonFreq 0 ... 3)", p->codonf_model); goto bad; }
+      if (p->est_freq) { rc = pamlh_fail(p, "runmode = -2: estFreq = 1 is not supported for pairwise comparisons"); goto bad; }
+      if (p->clock) { rc = pamlh_fail(p, "runmode = -2: clock = %d does not apply to pairwise comparisons", p->clock); goto bad; }
+      if (!p->fix_rho || p->rho0 != 0) { rc = pamlh_fail(p, "runmode = -2: rho does not apply to pairwise comparisons"); goto bad; }
+      p->cleandata_opt = 1;      /* complete deletion of the sites with gaps or ambiguities, as the reference forces (codeml.c:1849-1852) */
+      if ((rc = pamlh_read_seqs(p))) goto bad;
+      if (p->ngene > 1) { rc = pamlh_fail(p, "runmode = -2: Mgene / option G (%d genes) is not supported for pairwise comparisons", p->ngene); goto bad; }
+      if (p->ns < 2) { rc = pamlh_fail(p, "runmode = -2 needs at least two sequences"); goto bad; }
+      p->ntime = 1;
+      p->np = 1 + !p->fix_kappa + !p->fix_omega;
+      goto allocate;
+   }
    if ((rc = pamlh_read_seqs(p))) goto bad;
    if ((rc = pamlh_read_tree(p))) goto bad;
    if (p->nhomo == 1 && (p->ngene > 1 || p->model < F81 || p->model > REV)) { rc = pamlh_fail(p, "nhomo = 1 needs one gene and a model with base frequencies (F81 ... REV)"); goto bad; }
@@ -624,7 +648,8 @@ genes_ok:
       nr += !p->fix_rho;
       p->np = p->ntime + nr;
    }
-   p->branch = (double *)calloc(p->nnode, sizeof(double));
+allocate:
+   p->branch = (double *)calloc(p->nnode + 1, sizeof(double));
    p->pi = (double *)calloc(64 * PAMLH_MAXGENE, sizeof(double));
    p->freqK = (double *)calloc(64, sizeof(double));
    p->rate = (double *)calloc(64 * PAMLH_MAXGENE, sizeof(double));
@@ -764,6 +789,7 @@ static void codon_freqs_from_x(pamlh *p, const double *ppi)
 
 int pamlh_default_x(const pamlh *p, double *x, int cap)
 {
+   if (p->pairwise) return 0;      /* (runmode = -2: every pair has its own three parameters, pamlh_pairwise) */
    int k = 0, i;
    if (cap < p->np) return -1;
    if (p->fix_blength == 3) x[k++] = 1;
@@ -1484,6 +1510,7 @@ int pamlh_x_to_branches(const pamlh *p, const double *x, double *branch)
 
 int pamlh_set_x(pamlh *p, const double *x, int np)
 {
+   if (p->pairwise) return pamlh_fail(p, "runmode = -2 has no tree model to set parameters of: use pamlh_pairwise");
    const int n = p->n;
    if (p->ngene > 1 && p->mgene == 1) return pamlh_fail(p, "Mgene = 1: the genes are analysed separately (pamlh_gene_subset)");
    int k = 0, i, j;
@@ -2377,38 +2404,66 @@ int pamlh_beb_acd(pamlh *p, const double *x, double *post)
  * the synonymous / nonsynonymous shares of the mean rate under the branch's omega and rs0 / ra0 the shares at omega = 1,
  *    S = 3 ls rs0,  N = 3 ls - S,  dS = t rs / (3 rs0),  dN = t ra / (3 ra0).
  * out: [n_branches][6] = t, N, S, omega, dN, dS in the order of the branch lengths in x. */
-int pamlh_dnds(pamlh *p, const double *x, double *out)
+/* ... for one (pi, kappa, omega, t): what eigenQcodon(2, ...) returns (codeml.c:3318-3365); also behind the pairwise comparisons (codeml.c:4522) */
+void pamlh_dnds_one(const pamlh *p, const double *pi, double kappa, double omega, double t, double ls, double *N, double *S, double *dN, double *dS)
 {
    const int n = p->n;
-   double *Q, *Q1;
-   int from61[64], b, i, j, m = 0, rc;
-   if (p->seqtype != 1 || p->nssites || p->aadist || p->ngene > 1 || !(p->model == 0 || p->model == 2))
+   double *Q = (double *)malloc((size_t)2 * n * n * sizeof(double)), *Q1 = Q + (size_t)n * n;
+   double rs = 0, ra = 0, ra0 = 0, mr, rs0;
+   int from61[64], i, j, m = 0;
+   for (i = 0; i < 64; i++) if (p->code[i] != '*') from61[m++] = i;
+   codon_q_pi(p, pi, kappa, 1, Q1);
+   codon_q_pi(p, pi, kappa, omega, Q);
+   for (i = 0; i < n; i++)
+      for (j = 0; j < n; j++) {
+         if (i == j) continue;
+         if (p->code[from61[i]] == p->code[from61[j]]) rs += pi[i] * Q[i * n + j];
+         else { ra += pi[i] * Q[i * n + j]; ra0 += pi[i] * Q1[i * n + j]; }
+      }
+   mr = rs + ra;
+   rs0 = rs / (rs + ra0); ra0 = ra0 / (rs + ra0);
+   *S = 3 * ls * rs0;
+   *N = 3 * ls - *S;
+   *dN = t * (ra / mr) / (3 * ra0);
+   *dS = t * (rs / mr) / (3 * rs0);
+   free(Q);
+}
+
+/* the codon rate matrix (unscaled; returns the mean rate) and the elements it can have with their kinds, for the pairwise comparisons
+ * (pamlh_pairwise.c): row / col as paml_amd_set_eigen_qrev_batch_sparse takes them, flags bit 0 = transition, bit 1 = nonsynonymous */
+double pamlh_codon_q(const pamlh *p, const double *pi, double kappa, double omega, double *Q) { return codon_q_pi(p, pi, kappa, omega, Q); }
+int pamlh_codon_pattern_flags(const pamlh *p, const int **row, const int **col, unsigned char *flags)
+{
+   const codon_pairs_t *cp = codon_pairs(p);
+   int from61[64], k, m = 0, x;
+   for (k = 0; k < 64; k++) if (p->code[k] != '*') from61[m++] = k;
+   for (x = 0; x < cp->nnz; x++) {
+      const int c1 = from61[cp->row[x]], c2 = from61[cp->col[x]];
+      const int f[3] = {c1 / 16, (c1 / 4) % 4, c1 % 4}, t[3] = {c2 / 16, (c2 / 4) % 4, c2 % 4};
+      int pos = 0;
+      flags[x] = 0;
+      if (c1 == c2) continue;
+      for (k = 0; k < 3; k++) if (f[k] != t[k]) pos = k;
+      if (f[pos] + t[pos] == 1 || f[pos] + t[pos] == 5) flags[x] |= 1;
+      if (p->code[c1] != p->code[c2]) flags[x] |= 2;
+   }
+   *row = cp->row; *col = cp->col;
+   return cp->nnz;
+}
+
+int pamlh_dnds(pamlh *p, const double *x, double *out)
+{
+   int b, rc;
+   if (p->seqtype != 1 || p->nssites || p->aadist || p->ngene > 1 || !(p->model == 0 || p->model == 2) || p->pairwise)
       return pamlh_fail(p, "dN and dS per branch are defined for the codon models without site classes (one gene)");
    if ((rc = pamlh_set_x(p, x, p->np))) return rc;
-   for (i = 0; i < 64; i++) if (p->code[i] != '*') from61[m++] = i;
-   Q = (double *)malloc((size_t)2 * n * n * sizeof(double)); Q1 = Q + (size_t)n * n;
-   codon_q(p, p->kappa, 1, Q1);
    for (b = 0; b < p->nbranch; b++) {
       const int node = p->branch_node[b];
       const double w = p->model == 2 ? p->class_w[p->label[node]] : p->omega, t = p->branch[node];
-      double rs = 0, ra = 0, ra0 = 0, mr, rs0;
-      codon_q(p, p->kappa, w, Q);
-      for (i = 0; i < n; i++)
-         for (j = 0; j < n; j++) {
-            if (i == j) continue;
-            if (p->code[from61[i]] == p->code[from61[j]]) rs += p->pi[i] * Q[i * n + j];
-            else { ra += p->pi[i] * Q[i * n + j]; ra0 += p->pi[i] * Q1[i * n + j]; }
-         }
-      mr = rs + ra;
-      rs0 = rs / (rs + ra0); ra0 = ra0 / (rs + ra0);
       out[b * 6 + 0] = t;
-      out[b * 6 + 2] = 3 * p->ls * rs0;
-      out[b * 6 + 1] = 3 * p->ls - out[b * 6 + 2];
       out[b * 6 + 3] = w;
-      out[b * 6 + 4] = t * (ra / mr) / (3 * ra0);
-      out[b * 6 + 5] = t * (rs / mr) / (3 * rs0);
+      pamlh_dnds_one(p, p->pi, p->kappa, w, t, p->ls, &out[b * 6 + 1], &out[b * 6 + 2], &out[b * 6 + 4], &out[b * 6 + 5]);
    }
-   free(Q);
    return 0;
 }
 

@@ -20,7 +20,7 @@ DRIVER_PATH = os.path.join(_HERE, "lib", "pamlh_lnl")
 def build(force=False):
     from . import engine
     engine.build()
-    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
+    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "pamlh.h"))
     if force or not (os.path.exists(LIB_PATH) and os.path.exists(DRIVER_PATH)) or \
             any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
@@ -52,6 +52,8 @@ def lib():
         L.pamlh_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.pamlh_dnds.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.pamlh_free.argtypes = [C.c_void_p]
+        L.pamlh_is_pairwise.argtypes = [C.c_void_p]
+        L.pamlh_pairwise_n.argtypes = [C.c_void_p]
         L.pamlh_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 10
         L.pamlh_default_x.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.pamlh_read_inx.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -101,6 +103,48 @@ class Analysis:
         L.pamlh_dims(h, *[C.byref(v) for v in d])
         (self.n, self.n_tips, self.n_patt, self.n_nodes, self.root, self.n_codes, self.cleandata, self.ls, self.np,
          self.ntime) = [v.value for v in d]
+
+    def is_pairwise(self):
+        return bool(self._L.pamlh_is_pairwise(self._h))
+
+    def n_pairs(self):
+        return int(self._L.pamlh_pairwise_n(self._h))
+
+    def seq_names(self):
+        self._L.pamlh_seq_name.restype = C.c_char_p
+        self._L.pamlh_seq_name.argtypes = [C.c_void_p, C.c_int]
+        return [self._L.pamlh_seq_name(self._h, i).decode() for i in range(self.n_tips)]
+
+    def pairwise(self):
+        """runmode = -2 on the GPU (pamlh_pairwise): dict of arrays over the pairs in the reference's order (2,1), (3,1), (3,2), ... —
+        pairs[k] = (i, j) 0-based with j < i, t, kappa, omega, lnL, S, N, dN, dS, n_eval — plus the counters of the run."""
+        npair = self.n_pairs()
+        out, cnt = np.zeros((npair, 9)), (C.c_long * 4)()
+        self._L.pamlh_pairwise.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        if self._L.pamlh_pairwise(self._h, out.ctypes.data_as(C.c_void_p), cnt, 0) != 0:
+            raise RuntimeError("pamlh_pairwise: " + self._L.pamlh_error(self._h).decode())
+        res = {k: out[:, i].copy() for i, k in enumerate(("t", "kappa", "omega", "lnL", "S", "N", "dN", "dS", "n_eval"))}
+        res["pairs"] = np.array([(i, j) for i in range(1, self.n_tips) for j in range(i)], dtype=np.int32)
+        res["counters"] = dict(n_elem=cnt[0], n_decomp=cnt[1], n_calls=cnt[2], n_host_redone=cnt[3])
+        res["table"] = out
+        return res
+
+    def pairwise_freqs(self, fp, ls):
+        """Codon frequencies of a pair from its count table fp[n][n] (row = the larger state) by GetCodonFreqs2 (host only)."""
+        fp = np.ascontiguousarray(fp, dtype=np.float64)
+        pi = np.zeros(self.n)
+        self._L.pamlh_pairwise_freqs.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+        if self._L.pamlh_pairwise_freqs(self._h, fp.ctypes.data_as(C.c_void_p), float(ls), pi.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_pairwise_freqs failed")
+        return pi
+
+    def pairwise_write(self, table, directory):
+        """2ML.t, 2ML.dN, 2ML.dS and rst in the reference's layout from table[n_pairs][9] (host only)."""
+        tb = np.ascontiguousarray(table, dtype=np.float64)
+        assert tb.shape == (self.n_pairs(), 9)
+        self._L.pamlh_pairwise_write.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
+        if self._L.pamlh_pairwise_write(self._h, tb.ctypes.data_as(C.c_void_p), os.fsencode(directory)) != 0:
+            raise RuntimeError("pamlh_pairwise_write: " + self._L.pamlh_error(self._h).decode())
 
     def dnds(self, x):
         """[n_branches][6] = t, N, S, omega, dN, dS (the reference's "dN & dS for each branch" table)."""
