@@ -387,38 +387,10 @@ int paml_amd_eval_branch(paml_amd_engine *e, int node_b, int n_t, const double *
          finish_program(full);
          if (2 * n_store >= n_int && jit_supported(full, e->n_tips, e->n_codes, e->n_pi, 6, 128, true)) {
             const std::string key = "b" + std::to_string(n) + "c" + std::to_string(e->n_codes) + ":" + jit_program_key(full, e->n_tips);
-            bool have = e->jit_recall(key);
-            if (!have && e->bjit_failed_key != key) {
-               paml_amd_engine::JitJob *job = e->bjit_job.get();
-               if (job && job->state.load() >= 2) {
-                  if (job->th.joinable()) job->th.join();
-                  if (job->state.load() == 2 && job->key == key) {
-                     JitKernel nk;
-                     if (jit_load_code(job->code, &nk) == 0) { nk.key = key; e->jit_retire(); e->jit = nk; have = true; }
-                     else { if (nk.mod) (void)hipModuleUnload(nk.mod); e->bjit_failed_key = key; }
-                  }
-                  else if (job->key == key) { e->bjit_failed_key = key; e->err = "jit (refill): " + job->log; }
-                  e->bjit_job.reset();
-                  job = nullptr;
-               }
-               if (!have && !job && e->bjit_failed_key != key && (e->jit_forced || e->env.jit_sync || e->jit_count_request(key) >= 2)) {
-                  const std::string src = jit_generate(full, e->n_tips, n, e->n_codes);
-                  std::vector<char> code;
-                  if (jit_cached_code(src, &code) || ((e->jit_forced || e->env.jit_sync) && jit_compile_code(src, &code, &e->err) == 0)) {
-                     JitKernel nk;
-                     if (jit_load_code(code, &nk) == 0) { nk.key = key; e->jit_retire(); e->jit = nk; have = true; }
-                     else { if (nk.mod) (void)hipModuleUnload(nk.mod); e->bjit_failed_key = key; }
-                  }
-                  else if (e->jit_forced || e->env.jit_sync) e->bjit_failed_key = key;
-                  else {
-                     e->bjit_job.reset(new paml_amd_engine::JitJob());
-                     job = e->bjit_job.get();
-                     job->key = key; job->src = src;
-                     job->state.store(1);
-                     job->th = std::thread([job]() { job->state.store(jit_compile_code(job->src, &job->code, &job->log) == 0 ? 2 : 3); });
-                  }
-               }
-            }
+            bool have = false;
+            if (e->jit_forced || e->env.jit_sync || e->jit_recall(key) || e->jit_count_request(key) >= 2)
+               if (int rc = obtain_kernel(e, e->bjit_slot, &e->jit, true, key, [&]() { return jit_generate(full, e->n_tips, n, e->n_codes); },
+                                          (e->jit_forced || e->env.jit_sync) ? JIT_WAIT_CALLER : JIT_WAIT_WORKER, "refill", &have)) return rc;
             if (have) {
                e->use_jit = true;      // (kernel_name: the last pruning kernel was a per-tree one)
                if (int rc = select_tiles(e, true, 8, true)) return rc;

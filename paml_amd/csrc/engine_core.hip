@@ -94,9 +94,6 @@ void paml_amd_destroy(paml_amd_engine *e)
 {
    if (!e) return;
    (void)hipStreamSynchronize(e->stream);
-   if (e->jit_job && e->jit_job->th.joinable()) e->jit_job->th.join();
-   if (e->coop_job && e->coop_job->th.joinable()) e->coop_job->th.join();
-   if (e->bjit_job && e->bjit_job->th.joinable()) e->bjit_job->th.join();
    for (hipStream_t s : e->sb)
       if (s) {
          (void)hipStreamSynchronize(s);
@@ -120,7 +117,7 @@ const char *paml_amd_kernel_name(const paml_amd_engine *e)
    case KK_VALU4: return e->use_jit ? (e->fused ? "valu4_fused_jit" : "valu4_jit") : "valu4";
    case KK_VALU5: return e->use_jit ? (e->fused ? "valu5_fused_jit" : "valu5_jit") : "valu5";
    case KK_VALU20: return e->use_jit ? (e->m20 ? "mfma4x20_jit" : "valu20_jit") : "valu20";
-   default: return e->use_jit ? (e->jit_stage == 1 ? "mfma64_jit_quick" : "mfma64_jit") : (e->mfma_dma ? "mfma64_stream" : (e->coopj ? "mfma64_coopjit" : (e->coop ? "mfma64_coop" : "mfma64_gather")));
+   default: return e->use_jit ? "mfma64_jit" : (e->mfma_dma ? "mfma64_stream" : (e->coopj ? "mfma64_coopjit" : (e->coop ? "mfma64_coop" : "mfma64_gather")));
    }
 }
 

@@ -131,28 +131,52 @@ void launch_zpm(const unsigned char *z, long z_stride, int n_tips, int n_patt, i
    hipLaunchKernelGGL(zpm_kernel, dim3((n_patt + 255) / 256), dim3(256), 0, s, z, z_stride, n_tips, n_patt, zw, out);
 }
 
-// The specialised kernel for `key`: reuse the loaded module or generate + compile + load it.  A compile failure is
-// not fatal (the interpreter kernels take over) unless PAML_AMD_JIT_STRICT is set.
-template <class GEN>
-static int ensure_jit(paml_amd_engine *e, const std::string &key, GEN gen, bool *ok)
+// The one way to a per-tree kernel (declared in engine_state.h, which says what it promises).
+int obtain_kernel(paml_amd_engine *e, paml_amd_engine::JitSlot &slot, JitKernel *dst, bool pooled, const std::string &key,
+                  const std::function<std::string()> &gen, JitWait wait, const char *what, bool *have)
 {
-   *ok = false;
-   if (e->jit_recall(key)) { *ok = true; return 0; }      // (the kernel in use, or one of this engine's other programs kept loaded)
-   e->jit_retire();
-   std::string log;
+   *have = pooled ? e->jit_recall(key) : (dst->fn && dst->key == key);      // (the kernel in use, or one of this engine's other programs kept loaded)
+   if (*have || slot.failed.count(key)) return 0;
+   auto failed = [&](const std::string &why) {
+      slot.failed.insert(key);
+      e->err = std::string("jit (") + what + "): " + why;
+      return e->env.jit_strict ? fail(e, PAML_AMD_EHIP, e->err) : 0;
+   };
+   auto load = [&](const std::vector<char> &code) {      // beside the kernel in use, which goes only when this one is there
+      JitKernel nk;
+      if (jit_load_code(code, &nk) != 0) {
+         if (nk.mod) (void)hipModuleUnload(nk.mod);
+         return failed("hipModuleLoadData failed");
+      }
+      if (pooled) e->jit_retire();
+      else if (dst->mod) (void)hipModuleUnload(dst->mod);
+      *dst = nk;
+      dst->key = key;
+      *have = true;
+      return 0;
+   };
+   if (slot.job && slot.job->state.load() >= 2) {      // a finished worker: this key's, or an earlier tree's (dropped silently)
+      const std::unique_ptr<paml_amd_engine::JitJob> job = std::move(slot.job);
+      if (job->th.joinable()) job->th.join();
+      if (job->key == key) return job->state.load() == 2 ? load(job->code) : failed(job->log);
+   }
+   // (a worker still compiling: a caller that does not wait goes on with the interpreter kernels; one that waits is not held up by
+   //  another program's build and compiles its own)
+   if (slot.job && wait == JIT_WAIT_WORKER) return 0;
    const std::string src = gen();
-   if (!e->env.jit_dump.empty()) {
-      FILE *f = fopen(e->env.jit_dump.c_str(), "w");
-      if (f) { fputs(src.c_str(), f); fclose(f); }
+   if (!e->env.jit_dump.empty())
+      if (FILE *f = fopen(e->env.jit_dump.c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
+   std::vector<char> code;
+   if (jit_cached_code(src, &code)) return load(code);      // a code object on disk is loaded at once
+   if (wait == JIT_WAIT_CALLER) {
+      std::string log;
+      return jit_compile_code(src, &code, &log) == 0 ? load(code) : failed(log);
    }
-   if (jit_compile(src, &e->jit, &log) == 0) {
-      e->jit.key = key;
-      *ok = true;
-   }
-   else {
-      e->err = "jit: " + log;
-      if (e->env.jit_strict) return fail(e, PAML_AMD_EHIP, e->err);
-   }
+   paml_amd_engine::JitJob *job = new paml_amd_engine::JitJob();
+   slot.job.reset(job);
+   job->key = key; job->src = src;
+   job->state.store(1);
+   job->th = std::thread([job]() { job->state.store(jit_compile_code(job->src, &job->code, &job->log) == 0 ? 2 : 3); });
    return 0;
 }
 
@@ -330,71 +354,14 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
          // caller asked to wait (PAML_AMD_JIT flag / PAML_AMD_JIT_SYNC), the kernel is built on a worker thread while the interpreter kernels
          // serve, and the engine changes over when the code object is there; one found on disk is loaded at once.  Round 5: the generator
          // cuts such a walk into basic blocks (jit_split_mode), which is what the hardware wants and makes the full build as quick as the
-         // build without the three passes that are quadratic on one giant block (JIT_BIG_FLAGS) — that two-stage build (quick kernel at 0.63
-         // of the FP64 peak first, the full one after) remains for PAML_AMD_JIT_SPLIT=0 / asm.
+         // build without the three passes that are quadratic on one giant block — the two-stage build of rounds before (a quick kernel at
+         // 0.63 of the FP64 peak first, the full one after) went with that.
          const bool big = e->prog.ops.size() > 120;
          const bool background = (big || has_load) && !e->jit_forced && !e->env.jit_sync;
          const bool wanted = !has_load || e->jit_forced || e->env.jit_sync || e->jit_recall(key) || e->jit_count_request(key) >= 2;
-         if (!wanted) jit_ok = false;
-         else if (!background) {
-            int r = ensure_jit(e, key, [&]() { return jit_strip_big(jit_generate(e->prog, e->n_tips, n, e->n_codes)); }, &jit_ok);
-            if (r) return r;
-            if (jit_ok) { e->jit_stage = 2; e->jit.stage = 2; }
-         }
-         else {
-            // (a code object is loaded beside the kernel in use and replaces it only when the load succeeded: a full build that does not
-            //  load leaves the quick one serving, and its key is remembered so that it is not built again and again)
-            auto load = [&](const std::vector<char> &code, int stage) {
-               JitKernel nk;
-               if (jit_load_code(code, &nk) != 0) {
-                  if (nk.mod) (void)hipModuleUnload(nk.mod);
-                  return false;
-               }
-               e->jit_retire();
-               e->jit = nk;
-               e->jit.key = key; e->jit.stage = stage; e->jit_stage = stage;
-               return true;
-            };
-            (void)e->jit_recall(key);      // (one of this engine's other programs, kept loaded)
-            e->jit_stage = (e->jit.fn && e->jit.key == key) ? e->jit.stage : 0;      // (another tree's kernel, or none: stage 0)
-            paml_amd_engine::JitJob *job = e->jit_job.get();
-            if (job && job->state.load() >= 2 && job->th.joinable()) job->th.join();
-            if (job && job->state.load() >= 2) {
-               if (job->key == key && job->state.load() == 2) {          // a code object is there: load it and change over
-                  if (!load(job->code, job->stage)) {
-                     (job->stage == 1 ? e->jit_failed_key : e->jit_stage2_failed_key) = key;
-                     e->err = "jit: hipModuleLoadData failed";
-                  }
-               }
-               else if (job->key == key) {                               // failed
-                  (job->stage == 1 ? e->jit_failed_key : e->jit_stage2_failed_key) = key;
-                  e->err = "jit: " + job->log;
-               }
-               e->jit_job.reset();
-               job = nullptr;
-            }
-            auto may_build = [&](int stage) { return (stage == 1 ? e->jit_failed_key : e->jit_stage2_failed_key) != key; };
-            // two-stage build (generators without block splits only): the quick kernel first, the full one replaces it; else the one build
-            const bool two = jit_split_mode(e->prog.ops.size()) != 2;
-            const int next = (e->jit_stage == 0 && two && may_build(1)) ? 1 : 2;
-            if (!job && e->jit_stage < 2 && may_build(next)) {
-               const std::string quick = jit_generate(e->prog, e->n_tips, n, e->n_codes), full = jit_strip_big(quick);
-               std::vector<char> code;
-               if (e->jit_stage == 0) {      // a code object on disk is loaded at once
-                  if (may_build(2) && jit_cached_code(full, &code)) { if (!load(code, 2)) e->jit_stage2_failed_key = key; }
-                  else if (next == 1 && quick != full && jit_cached_code(quick, &code)) { if (!load(code, 1)) e->jit_failed_key = key; }
-               }
-               const int st = (e->jit_stage == 0 && next == 1 && quick != full) ? 1 : 2;
-               if (e->jit_stage < st && may_build(st)) {
-                  e->jit_job.reset(new paml_amd_engine::JitJob());
-                  job = e->jit_job.get();
-                  job->key = key; job->stage = st; job->src = st == 1 ? quick : full;
-                  job->state.store(1);
-                  job->th = std::thread([job]() { job->state.store(jit_compile_code(job->src, &job->code, &job->log) == 0 ? 2 : 3); });
-               }
-            }
-            jit_ok = e->jit.fn && e->jit.key == key;
-         }
+         if (wanted)
+            if (int r = obtain_kernel(e, e->jit_slot, &e->jit, true, key, [&]() { return jit_generate(e->prog, e->n_tips, n, e->n_codes); },
+                                      background ? JIT_WAIT_WORKER : JIT_WAIT_CALLER, "tree", &jit_ok)) return r;
       }
       e->use_jit = jit_ok;
       const bool big_tiles = jit_ok || lean;
@@ -417,22 +384,23 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
          const bool vf_genes = getenv("PAML_AMD_VF_GENES") && atoi(getenv("PAML_AMD_VF_GENES")) != 0;      // (read per call: tests switch it)
          if (pl.ok && (G == 1 ? e->n_pi == 1 : (vf_genes && (e->n_pi == 1 || e->n_pi == G))) && e->d_zpm.p && G <= 64) {
             // (4 states: a matrix-core form (v_mfma_f64_4x4x4) was correct but slower, 0.32 of peak against 0.64: profiles/r02_valu_fused_shapes.txt)
-            int r = ensure_jit(e, std::string("vf") + std::to_string(n) + "c" + std::to_string(e->n_codes) + "k" + std::to_string(Km) + "r" + std::to_string(pl.R) + "w" +
-                                     std::to_string(pl.CW) + (pl.cherry ? "y" : "n") + (G > 1 ? "g" + std::to_string(G) + ":" : ":") + jit_program_key(e->prog, e->n_tips),
-                               [&]() { return jit_generate_valu_fused(e->prog, n, e->n_tips, e->n_codes, Km, e->chunk, G); }, &jit_ok);
+            int r = obtain_kernel(e, e->jit_slot, &e->jit, true, std::string("vf") + std::to_string(n) + "c" + std::to_string(e->n_codes) + "k" + std::to_string(Km) + "r" + std::to_string(pl.R) + "w" +
+                                        std::to_string(pl.CW) + (pl.cherry ? "y" : "n") + (G > 1 ? "g" + std::to_string(G) + ":" : ":") + jit_program_key(e->prog, e->n_tips),
+                                  [&]() { return jit_generate_valu_fused(e->prog, n, e->n_tips, e->n_codes, Km, e->chunk, G); }, JIT_WAIT_CALLER, "valu fused", &jit_ok);
             if (r) return r;
             fused = jit_ok;
             e->fused_threads = 256 * pl.CW;
          }
          if (!jit_ok) {
-            int r = ensure_jit(e, "v" + std::to_string(n) + ":" + jit_program_key(e->prog, e->n_tips),
-                               [&]() { return jit_generate_valu(e->prog, n); }, &jit_ok);
+            int r = obtain_kernel(e, e->jit_slot, &e->jit, true, "v" + std::to_string(n) + ":" + jit_program_key(e->prog, e->n_tips),
+                                  [&]() { return jit_generate_valu(e->prog, n); }, JIT_WAIT_CALLER, "valu", &jit_ok);
             if (r) return r;
          }
       }
       e->m20 = false;
       if (e->want_m20 && !clean && jit_m20_supported(e->prog, e->n_tips, G)) {
-         int r = ensure_jit(e, std::string("m20c") + std::to_string(e->n_codes) + (G > 1 ? "g:" : ":") + jit_program_key(e->prog, e->n_tips), [&]() { return jit_generate_m20(e->prog, e->n_tips, e->n_codes, G > 1 ? 2 : 1); }, &jit_ok);
+         int r = obtain_kernel(e, e->jit_slot, &e->jit, true, std::string("m20c") + std::to_string(e->n_codes) + (G > 1 ? "g:" : ":") + jit_program_key(e->prog, e->n_tips),
+                               [&]() { return jit_generate_m20(e->prog, e->n_tips, e->n_codes, G > 1 ? 2 : 1); }, JIT_WAIT_CALLER, "m20", &jit_ok);
          if (r) return r;
          e->m20 = jit_ok;
       }
@@ -466,46 +434,8 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
       if (coop && e->coopj_enabled && !e->comm && e->nb_global == (e->n_patt + e->chunk - 1) / e->chunk && e->first_chunk == 0 &&
           jit_coop_supported(e->prog, e->n_tips, e->n_codes)) {
          const std::string key = "cj" + std::to_string(n <= 32 ? n : 64) + ":" + jit_program_key(e->prog, e->n_tips);
-         if (e->jit_coop.fn && e->jit_coop.key == key) coopj = true;
-         else if (e->coop_failed_key != key) {
-            paml_amd_engine::JitJob *job = e->coop_job.get();
-            if (job && job->state.load() >= 2 && job->th.joinable()) job->th.join();
-            std::vector<char> code;
-            bool have = false;
-            if (job && job->state.load() >= 2) {      // a finished compilation: this tree's, or an earlier tree's
-               if (job->state.load() == 2 && job->key == key) { code.swap(job->code); have = true; }
-               else if (job->state.load() == 3 && job->key == key) { e->coop_failed_key = key; e->err = "jit (coop): " + job->log; }
-               e->coop_job.reset();
-               job = nullptr;
-            }
-            if (!have && !job && e->coop_failed_key != key) {
-               const std::string src = jit_generate_coop(e->prog, e->n_tips, n);
-               if (!e->env.jit_dump.empty())
-                  if (FILE *f = fopen(e->env.jit_dump.c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
-               if (jit_cached_code(src, &code)) have = true;
-               else if (e->jit_forced || e->env.jit_sync) {
-                  std::string log;
-                  if (jit_compile_code(src, &code, &log) == 0) have = true;
-                  else {
-                     e->coop_failed_key = key; e->err = "jit (coop): " + log;
-                     if (e->env.jit_strict) return fail(e, PAML_AMD_EHIP, e->err);
-                  }
-               }
-               else {
-                  e->coop_job.reset(new paml_amd_engine::JitJob());
-                  job = e->coop_job.get();
-                  job->key = key; job->src = src;
-                  job->state.store(1);
-                  job->th = std::thread([job]() { job->state.store(jit_compile_code(job->src, &job->code, &job->log) == 0 ? 2 : 3); });
-               }
-            }
-            if (have) {
-               if (e->jit_coop.mod) (void)hipModuleUnload(e->jit_coop.mod);
-               e->jit_coop = JitKernel();
-               if (jit_load_code(code, &e->jit_coop) == 0) { e->jit_coop.key = key; coopj = true; }
-               else { e->coop_failed_key = key; e->err = "jit (coop): hipModuleLoadData failed"; }
-            }
-         }
+         if (int r = obtain_kernel(e, e->coop_slot, &e->jit_coop, false, key, [&]() { return jit_generate_coop(e->prog, e->n_tips, n); },
+                                   (e->jit_forced || e->env.jit_sync) ? JIT_WAIT_CALLER : JIT_WAIT_WORKER, "coop", &coopj)) return r;
       }
    }
    e->coop = coop; e->coopj = coopj;

@@ -145,7 +145,6 @@ int paml_amd_jit_prebuild(int n_states, int n_tips, int n_codes, int K, long n_p
    else {
       if (!jit_supported(p, n_tips, n_codes)) return PAML_AMD_EUNSUPPORTED;
       text = jit_generate(p, n_tips, n_states, n_codes);
-      if (!getenv("PAML_AMD_PREBUILD_QUICK")) text = jit_strip_big(text);      // (large trees: the full build, what an engine looks for first)
    }
    if (const char *dump = getenv("PAML_AMD_JIT_DUMP")) {
       FILE *f = fopen(dump, "w");

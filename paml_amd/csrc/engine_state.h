@@ -17,8 +17,10 @@
 #include <cstring>
 #include <string>
 #include <atomic>
+#include <functional>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <thread>
 #include <vector>
 
@@ -432,17 +434,17 @@ struct paml_amd_engine {
    struct JitJob {
       std::thread th;
       std::atomic<int> state{0};      // 0 idle, 1 compiling, 2 code ready, 3 failed
-      int stage = 2;                  // large trees: 1 = the quick build (JIT_BIG_FLAGS), 2 = the full one that replaces it
       std::string key, src, log;
       std::vector<char> code;
       JitJob() { worker_threads_list(&th, true); }
       ~JitJob() { if (th.joinable()) th.join(); worker_threads_list(&th, false); }
    };
-   std::unique_ptr<JitJob> jit_job, coop_job, bjit_job;      // (bjit: the branch-local evaluation's refill program, engine_branch.hip)
-   std::string bjit_failed_key;
-   std::string jit_failed_key, coop_failed_key;
-   int jit_stage = 0;                 // which build of the large tree's kernel `jit` holds (0: none / a kernel compiled while the caller waited)
-   std::string jit_stage2_failed_key;
+   // One worker at a time per slot (obtain_kernel, below), and the keys of the slot whose kernel did not compile or load: not tried again.
+   struct JitSlot {
+      std::unique_ptr<JitJob> job;
+      std::set<std::string> failed;
+   };
+   JitSlot jit_slot, coop_slot, bjit_slot;      // `jit` in launch_eval, `jit_coop`, and `jit` for eval_branch's refill program (engine_branch.hip)
 
    std::vector<EigenHost> eigen;
    std::vector<int> h_eigen_of;      // the class table's eigen set ids as last set (set_classes): checked against the sets that exist
@@ -725,6 +727,14 @@ struct BatchSpec {
 
 int build_tiles(paml_amd_engine *e);
 int select_tiles(paml_amd_engine *e, bool big_tiles, int want_waves, bool jit_ok);
+// The per-tree kernel of `key` in `*dst` (`pooled`: dst is e->jit, kernels being left go to e->jit_pool and come back from it): the one
+// loaded, else a finished worker's, else one from the code-object cache, else compiled from gen() — while the caller waits, or on the
+// slot's worker thread while the interpreter kernels serve (*have = false until a later call finds the code object).  The kernel in use
+// is replaced only by one that loaded; a key that failed is remembered in the slot and e->err says "jit (<what>): ...".  Returns
+// nonzero only under PAML_AMD_JIT_STRICT.
+enum JitWait { JIT_WAIT_CALLER, JIT_WAIT_WORKER };
+int obtain_kernel(paml_amd_engine *e, paml_amd_engine::JitSlot &slot, JitKernel *dst, bool pooled, const std::string &key,
+                  const std::function<std::string()> &gen, JitWait wait, const char *what, bool *have);
 int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rate, const unsigned char *clean, double *d_lnL_out, bool want_lnf,
                 const BatchSpec *bs = nullptr, bool want_pipe = false, bool want_fhk = true);
 // launches for the other translation units (a __global__ function has one home)

@@ -37,7 +37,6 @@ struct JitKernel {
    hipFunction_t fn = nullptr;
    std::string key;
    size_t n_ops = 0;
-   int stage = 0;            // large trees, two-stage build: which build this is (1 quick, 2 full; 0: compiled while the caller waited)
 };
 
 // Stack slots of the 61-state kernel that live in register arrays (each 32 VGPRs); deeper slots are spilled to global scratch.
@@ -171,15 +170,11 @@ inline std::string jit_program_key(const Program &p, int n_tips)
 // slower than the same instructions with a branch every few ops (230 tips, 256 tiles per launch: 5.8 ms against 1.03 ms; an `s_branch` to
 // the next instruction does as well as a compiler-visible one: profiles/r05_big_tree_split.txt).  Programs of more than JIT_SPLIT_OPS ops
 // get a never-taken uniform branch (JIT_SPLIT) every eighth op; the compiler then also works on blocks of a few thousand instructions
-// instead of one of 10^5 (192 taxa: 28 s instead of 130 on this container's core).   0: none, 1: s_branch, 2: JIT_SPLIT
+// instead of one of 10^5 (192 taxa: 28 s instead of 130 on this container's core), so one full build serves: no quick build in front of it.
 // Small programs get the compiler-visible form too: no front-end effect there (a bare s_branch changes nothing at 16 taxa), but the
 // compiler's schedule of the shorter blocks measures 0.6 % faster (kernel 1.554 -> 1.544 ms at 16 taxa x 10^6 patterns, two runs each).
 static const size_t JIT_SPLIT_OPS = 8;
-inline int jit_split_mode(size_t nops)
-{
-   if (const char *v = getenv("PAML_AMD_JIT_SPLIT")) return !strcmp(v, "asm") ? 1 : !strcmp(v, "br") ? 2 : 0;
-   return nops > JIT_SPLIT_OPS ? 2 : 0;
-}
+inline bool jit_split_mode(size_t nops) { return nops > JIT_SPLIT_OPS; }
 inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states, int n_codes, int first, int *first_out)
 {
    std::ostringstream s;
@@ -327,14 +322,14 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
       return f + " }";
    };
    const int prof_every = getenv("PAML_AMD_PROF_EVERY") ? std::max(1, atoi(getenv("PAML_AMD_PROF_EVERY"))) : 1;      // (experiments: a stamp at every n-th op only)
-   const int split_mode = jit_split_mode(nops);      // (large trees: a branch every `split_every` ops, see jit_split_mode)
+   const bool split_mode = jit_split_mode(nops);      // (large trees: a branch every `split_every` ops, see jit_split_mode)
    const int split_every = 8;
    auto stamp = [&](size_t iop) {
       if (prof && iop % prof_every == 0)
          s << "   if (a.prof && tid == a.prof_tid && ptile) a.prof[(long)blockIdx.x * a.prof_stride + 1 + " << iop
            << "] = __builtin_amdgcn_s_memtime();\n";
       else if (!prof && split_mode && iop && iop % split_every == 0)
-         s << (split_mode == 1 ? "   asm volatile(\"s_branch 0\");\n" : "   JIT_SPLIT()\n");
+         s << "   JIT_SPLIT()\n";
    };
    auto code = [&](int tip) { return "JIT2_CODE(" + std::to_string(ZP) + ", " + std::to_string(zpl.row[tip]) + ")"; };
    auto ncode = [&](int tip) { return "JIT2_NCODE(" + std::to_string(ZP) + ", " + std::to_string(zpl.row[tip]) + ")"; };
@@ -576,8 +571,6 @@ inline std::string jit_generate(const Program &p, int n_tips, int n_states = 61,
       src = jit_generate_impl(p, n_tips, n_states, n_codes, first, &got);
    }
    if (got != first) return std::string("#error \"jit schedule does not close\"\n");
-   // (one basic block of > 120 ops: the quick build first.  With the block splits the full passes take no longer than the quick ones.)
-   if (p.ops.size() > 120 && jit_split_mode(p.ops.size()) != 2) src = "// JIT_BIG: compiled with JIT_BIG_FLAGS (jit_compile_code)\n" + src;
    return src;
 }
 
@@ -1380,24 +1373,6 @@ inline std::string jit_source_dir()
 //                              PAML_AMD_JIT_CACHE=0 (or empty) switches it off.
 inline const char *jit_opt_level() { return "-O3"; }
 
-// Kernels of large trees (the generator marks their source): one basic block of tens of thousands of instructions, on which three
-// passes of the compiler are quadratic and gain nothing here — measured on the 192-taxon kernel (340 KB of code), this container's CPU:
-// GPU Load and Store Vectorizer 56 s of 82 (every access is already 16 bytes wide), Machine CSE 6 s, Machine Copy Propagation 3 s.
-// Without them 23 s, the same registers and 115 spilled dwords against 106 (tools/README.md, profiles/r05_big_trees.txt).
-static const char *const JIT_BIG_FLAGS[] = {"-mllvm", "-amdgpu-load-store-vectorizer=0", "-mllvm", "-disable-machine-cse", "-mllvm", "-disable-copyprop"};
-inline bool jit_is_big(const std::string &src) { return src.compare(0, 10, "// JIT_BIG") == 0; }
-inline std::string jit_strip_big(const std::string &src)      // the same kernel for the compiler's full pipeline (no marker line)
-{
-   return src.compare(0, 10, "// JIT_BIG") == 0 ? src.substr(src.find('\n') + 1) : src;
-}
-inline std::vector<std::string> jit_big_flags(const std::string &src)
-{
-   std::vector<std::string> f;
-   if (!jit_is_big(src)) return f;
-   f.assign(std::begin(JIT_BIG_FLAGS), std::end(JIT_BIG_FLAGS));
-   return f;
-}
-
 inline std::string jit_cache_name(const std::string &src)
 {
    unsigned long long h = 1469598103934665603ull;
@@ -1408,7 +1383,6 @@ inline std::string jit_cache_name(const std::string &src)
       if (f) { char buf[4096]; size_t n; while ((n = fread(buf, 1, sizeof(buf), f)) > 0) mix(std::string(buf, n)); fclose(f); }
    }
    mix(jit_opt_level());
-   for (const std::string &o : jit_big_flags(src)) mix(o);
    int major = 0, minor = 0;
    (void)hiprtcVersion(&major, &minor);
    mix("hiprtc" + std::to_string(major) + "." + std::to_string(minor));
@@ -1481,8 +1455,6 @@ inline int jit_compile_code(const std::string &src, std::vector<char> *code, std
    }
    const std::string inc = "-I" + jit_source_dir();
    std::vector<const char *> opts = {"--offload-arch=gfx950", jit_opt_level(), "-std=c++17", inc.c_str()};
-   std::vector<std::string> big = jit_big_flags(src);
-   for (const std::string &o : big) opts.push_back(o.c_str());
    const hiprtcResult r = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
    size_t ls = 0;
    hiprtcGetProgramLogSize(prog, &ls);
@@ -1515,22 +1487,6 @@ inline int jit_load_code(const std::vector<char> &code, JitKernel *out)
 {
    if (hipModuleLoadData(&out->mod, code.data()) != hipSuccess) return -1;
    if (hipModuleGetFunction(&out->fn, out->mod, "prune_jit") != hipSuccess) return -1;
-   return 0;
-}
-
-// Compile and load.
-inline int jit_compile(const std::string &src, JitKernel *out, std::string *log)
-{
-   std::vector<char> code;
-   if (jit_compile_code(src, &code, log) != 0) return -1;
-   if (hipModuleLoadData(&out->mod, code.data()) != hipSuccess) {
-      *log = "hipModuleLoadData failed";
-      return -1;
-   }
-   if (hipModuleGetFunction(&out->fn, out->mod, "prune_jit") != hipSuccess) {
-      *log = "hipModuleGetFunction failed";
-      return -1;
-   }
    return 0;
 }
 

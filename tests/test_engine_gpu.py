@@ -503,8 +503,8 @@ def test_large_tree_kernel_is_compiled_in_the_background(monkeypatch, tmp_path):
     first = eng.eval(pb.tree.branch, pb.gene_rate)["lnL"]
     assert eng.kernel_name in ("mfma64_gather", "mfma64_coop", "mfma64_coopjit"), eng.kernel_name      # (the interpreter kernels: 69 groups of 16 patterns get a CU each)
     assert abs(first - ref) <= 1e-10 * abs(ref)
-    # two builds on the worker thread: the quick one (the compiler without the passes that are quadratic on a basic block this large:
-    # "mfma64_jit_quick"), then the full one that replaces it ("mfma64_jit"); with a warm code-object cache the engine may skip stages
+    # one build on the worker thread (the walk is cut into basic blocks, so the full build is quick enough to be the only one): the
+    # interpreter kernels serve until its code object is there, then "mfma64_jit"
     t0 = time.time()
     seen = []
     while eng.kernel_name != "mfma64_jit" and time.time() - t0 < 180:
@@ -514,7 +514,7 @@ def test_large_tree_kernel_is_compiled_in_the_background(monkeypatch, tmp_path):
         if eng.kernel_name not in seen:
             seen.append(eng.kernel_name)
     assert eng.kernel_name == "mfma64_jit", "the background compile never finished (%r)" % (seen,)
-    assert all(k in ("mfma64_gather", "mfma64_coop", "mfma64_coopjit", "mfma64_jit_quick", "mfma64_jit") for k in seen), seen
+    assert all(k in ("mfma64_gather", "mfma64_coop", "mfma64_coopjit", "mfma64_jit") for k in seen), seen
     assert abs(eng.eval(pb.tree.branch, pb.gene_rate)["lnL"] - ref) <= 1e-10 * abs(ref)
     eng.close()
     # an engine destroyed while its compile is still running waits for the worker
@@ -537,6 +537,41 @@ def test_compiled_kernels_are_cached_on_disk(monkeypatch, tmp_path):
     t0 = time.time(); eng2, out2, _ = check(pb); t_warm = time.time() - t0
     assert eng2.kernel_name == "mfma64_jit" and out2["lnL"] == out["lnL"]
     assert len(list(tmp_path.glob("*.hsaco"))) == 1 and t_warm < t_cold
+
+
+def test_a_kernel_that_does_not_compile_is_not_compiled_again(monkeypatch, tmp_path):
+    """A per-tree kernel whose compilation fails (here: the compiler cannot find device_common.h — PAML_AMD_CSRC names an empty
+    directory; nothing reaches the GPU) leaves the interpreter kernel serving with "jit (...)" in last_error, and its key is remembered:
+    the next evaluation does not go to the compiler again (PAML_AMD_JIT_SRC_DIR receives every source that does).  With
+    PAML_AMD_JIT_STRICT the evaluation is an error."""
+    from paml_amd.engine import EngineError
+    empty, cache, srcs = tmp_path / "csrc", tmp_path / "cache", tmp_path / "srcs"
+    for d in (empty, cache, srcs):
+        d.mkdir()
+    monkeypatch.setenv("PAML_AMD_JIT", "1")
+    monkeypatch.setenv("PAML_AMD_JIT_CACHE", str(cache))
+    monkeypatch.setenv("PAML_AMD_CSRC", str(empty))
+    monkeypatch.setenv("PAML_AMD_JIT_SRC_DIR", str(srcs))
+    monkeypatch.delenv("PAML_AMD_JIT_STRICT", raising=False)
+    pb = helpers.random_problem(61, 12, 300, K=1, seed=95)
+    ref = oracle.evaluate(pb)["lnL"]
+    eng = engine_for(pb)
+    for second in (False, True):
+        lnl = eng.eval(pb.tree.branch, pb.gene_rate)["lnL"]
+        assert eng.kernel_name in ("mfma64_gather", "mfma64_coop"), eng.kernel_name
+        assert abs(lnl - ref) <= 1e-10 * abs(ref)
+        assert eng._L.paml_amd_last_error(eng._h).decode().startswith("jit ("), eng._L.paml_amd_last_error(eng._h)
+        tried = list(srcs.glob("*.hip"))
+        assert (len(tried) == 0) if second else (len(tried) >= 1), tried      # (the tree's kernel, and the cooperative one of this small data set)
+        for f in tried:
+            f.unlink()
+    eng.close()
+    assert not list(cache.glob("*.hsaco"))
+    monkeypatch.setenv("PAML_AMD_JIT_STRICT", "1")
+    eng = engine_for(pb)
+    with pytest.raises(EngineError, match=r"jit \("):
+        eng.eval(pb.tree.branch, pb.gene_rate)
+    eng.close()
 
 
 def test_per_tree_kernel_spills_deep_stacks(monkeypatch):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Large trees: how long the interpreter serves before the tree's own kernel is compiled (worker thread, JIT_BIG_FLAGS), and the rate
+"""Large trees: how long the interpreter serves before the tree's own kernel is compiled (worker thread), and the rate
 before and after.  usage: python tools/big_tree_compile_probe.py [taxa ...]"""
 import json, os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,14 +29,13 @@ for taxa in [int(a) for a in sys.argv[1:]] or [96, 192]:
     v0 = eng.eval(pb.tree.branch)["lnL"]
     k0, (ms0, f0) = eng.kernel_name, rate()
     out = dict(taxa=taxa, first_kernel=k0, ms_per_eval_first=ms0, frac_first=f0)
-    for want in ("mfma64_jit_quick", "mfma64_jit"):
-        while eng.kernel_name not in (want, "mfma64_jit") and time.perf_counter() - t0 < 180:
-            time.sleep(0.25)
-            eng.eval(pb.tree.branch)
-        if eng.kernel_name == want:
-            secs = time.perf_counter() - t0
-            ms1, f1 = rate()
-            v1 = eng.eval(pb.tree.branch)["lnL"]
-            out[want] = dict(seconds=secs, ms_per_eval=ms1, frac=f1, same_lnL_to_1e12=bool(abs(v1 - v0) <= 1e-12 * abs(v0)))
+    while eng.kernel_name != "mfma64_jit" and time.perf_counter() - t0 < 180:
+        time.sleep(0.25)
+        eng.eval(pb.tree.branch)
+    if eng.kernel_name == "mfma64_jit":
+        secs = time.perf_counter() - t0
+        ms1, f1 = rate()
+        v1 = eng.eval(pb.tree.branch)["lnL"]
+        out["mfma64_jit"] = dict(seconds=secs, ms_per_eval=ms1, frac=f1, same_lnL_to_1e12=bool(abs(v1 - v0) <= 1e-12 * abs(v0)))
     print(json.dumps(out), flush=True)
     eng.close()
