@@ -21,34 +21,33 @@ beig_fn const beig_kernels[6][2][2] = {      // [how A is obtained][B is a tip][
 };
 #undef BEIG_ROW
 
-// Run `prog` with the full-featured kernels (gather / valu) over all patterns and classes, reading the P(t) buffers
-// of the last pmat launch; OP_EXPORT writes to export_buf.  Used by the branch-local evaluation.
-int run_prune_full(paml_amd_engine *e, const Program &prog, double *export_buf, double *export_scale)
+// Run `prog` (its ops in d_ops_tmp) with the full-featured kernels (gather / valu) over all patterns and classes, reading the P(t)
+// buffers of the last pmat launch.  `resident`: STOREs / LOADs address the branch cache's partials; OP_EXPORT writes to export_buf.
+int run_prune_full(paml_amd_engine *e, const Program &prog, bool resident, double *export_buf, double *export_scale)
 {
-   const int nn = e->tree.n_nodes, K = e->K;
-   HIPCHK(upload(e->d_ops_tmp, prog.ops.data(), prog.ops.size(), e->stream));
-   HIPCHK(hipStreamSynchronize(e->stream));
-   const int waves = GATHER_WAVES;
-   const int n_blocks = e->n_tiles_full * K;
+   const int n_blocks = e->n_tiles_full * e->K;
    int overflow = 0;
-   if (e->kk == KK_MFMA64 && prog.max_stack > MFMA_RS) {
-      overflow = prog.max_stack - MFMA_RS;
-      HIPCHK(e->d_stack.ensure((size_t)n_blocks * overflow * waves * 1024));
-   }
-   const int maxd = e->kk == KK_VALU20 ? VALU_MAXD_20 : VALU_MAXD_SMALL;
-   if (e->kk != KK_MFMA64 && prog.max_stack > maxd)
-      return fail(e, PAML_AMD_EUNSUPPORTED, "tree needs a deeper partial stack than this kernel provides");
-   PruneArgs pr{};
-   pr.ops = e->d_ops_tmp.p; pr.z = e->d_z.p; pr.z_stride = e->n_patt; pr.tiles = e->d_tiles_full.p; pr.n_tiles = e->n_tiles_full;
-   pr.gene_off = e->d_gene_off.p; pr.weights = e->d_weights.p;
-   pr.n = e->n; pr.n_tips = e->n_tips; pr.n_nodes = nn; pr.K = K; pr.n_genes = e->n_genes; pr.n_codes = e->n_codes;
-   pr.cleandata = e->cleandata; pr.n_pi = e->n_pi; pr.mode = e->mode; pr.n_scale = 0; pr.keep = 0; pr.n_patt = e->n_patt;
-   pr.pi = e->d_pi.p; pr.pint = e->kk == KK_MFMA64 ? e->d_pint.p : e->d_rowmajor.p; pr.ptip = e->d_ptip.p;
-   pr.fhK = e->d_fhK.p; pr.partials = nullptr; pr.scalef = nullptr; pr.stack_scratch = e->d_stack.p;
-   pr.stack_overflow_slots = overflow; pr.first_matmul = prog.first_matmul; pr.n_int = nn - e->n_tips;
-   pr.first_tip = prog.first_tip; pr.tip_words = (long)tip_words(e); pr.export_buf = export_buf; pr.export_scale = export_scale;
+   if (int rc = check_stack_depth(e, prog)) return rc;
+   if (int rc = stack_overflow(e, prog, n_blocks, GATHER_WAVES, &overflow)) return rc;
+   PruneArgs pr = prune_args(e, prog, e->K, e->d_ops_tmp.p, true, resident ? e->tree.n_scale : 0, resident, resident ? e->d_bl_partials.p : nullptr,
+                             resident ? e->d_bl_scalef.p : nullptr, overflow);
+   pr.export_buf = export_buf; pr.export_scale = export_scale;
    launch_prune_full(e, prog.max_stack, n_blocks, pr, e->stream);
    HIPCHK(hipGetLastError());
+   return 0;
+}
+
+// P(t) of every edge of the tree as re-oriented in d_label_eff / d_branch and rooted at `root`, in one batched launch
+int reoriented_pmat(paml_amd_engine *e, int root, bool pcol)
+{
+   const int psets = e->n_genes * e->K;
+   if (int rc = ensure_pmat_buffers(e, psets, false, pcol)) return rc;
+   const PmatArgs pa = pmat_args(e, root, e->d_label_eff.p, e->kk == KK_MFMA64 ? 1 : 0, pcol ? e->d_pcol.p : nullptr);
+   InlineVec iv;
+   iv.n_branch = iv.n_rate = 0;
+   launch_pmat(pa, iv, e->tree.n_nodes, psets, false, e->stream, pmat_on_matrix_cores(e, pa));
+   e->prog_valid = false;      // d_branch / P buffers now hold the re-oriented edge data: the next eval rebuilds
+   e->pmat_valid = false;
    return 0;
 }
 
@@ -60,7 +59,7 @@ int run_prune_full(paml_amd_engine *e, const Program &prog, double *export_buf, 
 int rerooted_pmat(paml_amd_engine *e, int new_root, int cut_son, const double *branch, const double *gene_rate, TreeDesc *out)
 {
    const TreeDesc &T = e->tree;
-   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, psets = G * K;
+   const int nn = T.n_nodes, K = e->K, G = e->n_genes, psets = G * K;
    std::vector<int> father(nn, -1);
    for (int i = 0; i < nn; i++)
       for (int j = T.sons_ptr[i]; j < T.sons_ptr[i + 1]; j++) father[T.sons[j]] = i;
@@ -99,36 +98,16 @@ int rerooted_pmat(paml_amd_engine *e, int new_root, int cut_son, const double *b
    e->bl_gr_sent = false;
    HIPCHK(upload(e->d_label_eff, lab.data(), lab.size(), e->stream));
    if (e->eigen_dirty) {
-      std::vector<EigenDev> tab(e->eigen.size());
-      for (size_t i = 0; i < e->eigen.size(); i++) {
-         const EigenHost &h = e->eigen[i];
-         tab[i] = EigenDev{h.kind, h.nR, h.kappa, h.U.p, h.V.p, h.Root.p, h.Cijk.p};
-      }
+      std::vector<EigenDev> tab;
+      if (int rc = eigen_table(e, tab)) return rc;
       HIPCHK(upload(e->d_eigen, tab.data(), tab.size(), e->stream));
       e->eigen_dirty = false;
    }
    HIPCHK(hipStreamSynchronize(e->stream));
-   HIPCHK(e->d_rowmajor.ensure((size_t)psets * nn * n * n));
-   if (e->kk == KK_MFMA64) HIPCHK(e->d_pint.ensure((size_t)psets * nn * 4096));
-   HIPCHK(e->d_ptip.ensure((size_t)psets * nn * tip_words(e)));
    HIPCHK(e->d_fhK.ensure((size_t)K * e->n_patt));
-   PmatArgs pa{};
-   pa.n = n; pa.n_nodes = nn; pa.root = new_root; pa.K = K; pa.n_genes = G; pa.n_labels = e->n_labels;
-   pa.n_codes = e->n_codes; pa.layout = e->kk == KK_MFMA64 ? 1 : 0;
-   pa.label = e->d_label_eff.p; pa.is_leaf = e->d_is_leaf.p; pa.branch = e->d_branch.p; pa.rate = e->d_rate.p;
-   pa.gene_rate = e->d_gene_rate.p; pa.eigen_of = e->d_eigen_of.p; pa.qfactor = e->d_qfactor.p;
-   pa.eigen = e->d_eigen.p; pa.n_chara = e->d_n_chara.p; pa.chara_map = e->d_chara_map.p; pa.plain_codes = e->plain_codes;
-   pa.rowmajor = e->d_rowmajor.p; pa.pint = e->d_pint.p; pa.ptip = e->d_ptip.p; pa.tip_words = (long)tip_words(e);
-   pa.B = 1; pa.rate_gs = e->rate_per_gene ? K : 0;
-   {
-      InlineVec iv;
-      iv.n_branch = iv.n_rate = 0;
-      launch_pmat(pa, iv, nn, psets, false, e->stream, pmat_on_matrix_cores(e, pa));
-   }
+   if (int rc = reoriented_pmat(e, new_root, false)) return rc;
    e->n_pmat += (long)psets * (nn - 1);
-   e->prog_valid = false;      // d_branch / P buffers now hold the re-rooted edge data: the next eval rebuilds
    e->partials_valid = false;
-   e->pmat_valid = false;
    return 0;
 }
 
@@ -335,44 +314,16 @@ int paml_amd_eval_branch(paml_amd_engine *e, int node_b, int n_t, const double *
       }
       // the call's small inputs: one pinned arena, asynchronous copies
       HIPCHK(e->stage.begin((size_t)n_t * 8 + (run_pmat ? (size_t)nn * 12 : 0) + (run_prog ? prog.ops.size() * sizeof(Op) : 0) + 256));
-      {
-         const double *ht = e->stage.put(t, (size_t)n_t);
-         HIPCHK(hipMemcpyAsync(e->d_tt.p, ht, (size_t)n_t * 8, hipMemcpyHostToDevice, st));
-      }
+      HIPCHK(e->stage.send(e->d_tt, t, (size_t)n_t, st));
       if (run_pmat) {
-         HIPCHK(e->d_label_eff.ensure(nn));
-         HIPCHK(e->d_branch.ensure(nn));
-         const int *hl = e->stage.put(lab_eff.data(), (size_t)nn);
-         HIPCHK(hipMemcpyAsync(e->d_label_eff.p, hl, (size_t)nn * 4, hipMemcpyHostToDevice, st));
-         const double *hb = e->stage.put(br_eff.data(), (size_t)nn);
-         HIPCHK(hipMemcpyAsync(e->d_branch.p, hb, (size_t)nn * 8, hipMemcpyHostToDevice, st));
+         HIPCHK(e->stage.send(e->d_label_eff, lab_eff.data(), (size_t)nn, st));
+         HIPCHK(e->stage.send(e->d_branch, br_eff.data(), (size_t)nn, st));
       }
-      if (run_prog) {
-         HIPCHK(e->d_ops_tmp.ensure(prog.ops.size()));
-         const Op *ho = e->stage.put(prog.ops.data(), prog.ops.size());
-         HIPCHK(hipMemcpyAsync(e->d_ops_tmp.p, ho, prog.ops.size() * sizeof(Op), hipMemcpyHostToDevice, st));
-      }
+      if (run_prog) HIPCHK(e->stage.send(e->d_ops_tmp, prog.ops.data(), prog.ops.size(), st));
       HIPCHK(e->stage.end(st));
       if (run_pmat) {
-         HIPCHK(e->d_rowmajor.ensure((size_t)psets * nn * n * n));
-         HIPCHK(e->d_pint.ensure((size_t)psets * nn * 4096));
-         HIPCHK(e->d_ptip.ensure((size_t)psets * nn * tip_words(e)));
-         PmatArgs pa{};
-         pa.n = n; pa.n_nodes = nn; pa.root = A; pa.K = K; pa.n_genes = G; pa.n_labels = e->n_labels;
-         pa.n_codes = e->n_codes; pa.layout = 1;
-         pa.label = e->d_label_eff.p; pa.is_leaf = e->d_is_leaf.p; pa.branch = e->d_branch.p; pa.rate = e->d_rate.p;
-         pa.gene_rate = e->d_gene_rate.p; pa.eigen_of = e->d_eigen_of.p; pa.qfactor = e->d_qfactor.p;
-         pa.eigen = e->d_eigen.p; pa.n_chara = e->d_n_chara.p; pa.chara_map = e->d_chara_map.p; pa.plain_codes = e->plain_codes;
-         pa.rowmajor = e->d_rowmajor.p; pa.pint = e->d_pint.p; pa.ptip = e->d_ptip.p; pa.tip_words = (long)tip_words(e);
-         HIPCHK(e->d_pcol.ensure((size_t)psets * nn * 64));
-         pa.pcol = e->d_pcol.p;
-         pa.B = 1; pa.rate_gs = e->rate_per_gene ? K : 0;
-         InlineVec iv;
-         iv.n_branch = iv.n_rate = 0;
-         launch_pmat(pa, iv, nn, psets, false, st, pmat_on_matrix_cores(e, pa));
+         if (int rc = reoriented_pmat(e, A, true)) return rc;
          e->n_pmat += (long)psets * (nn - 2);
-         e->prog_valid = false;      // d_branch / P buffers now hold re-oriented edge data: the next eval rebuilds
-         e->pmat_valid = false;
       }
       // A refill — every branch length moved since the partials were formed (minB's round after ming2 has moved kappa / omega, the first
       // call of a search): the forest of dirty subtrees is most of the tree, and the program is the same every time it happens at this
@@ -392,26 +343,14 @@ int paml_amd_eval_branch(paml_amd_engine *e, int node_b, int n_t, const double *
                if (int rc = obtain_kernel(e, e->bjit_slot, &e->jit, true, key, [&]() { return jit_generate(full, e->n_tips, n, e->n_codes); },
                                           (e->jit_forced || e->env.jit_sync) ? JIT_WAIT_CALLER : JIT_WAIT_WORKER, "refill", &have)) return rc;
             if (have) {
-               e->use_jit = true;      // (kernel_name: the last pruning kernel was a per-tree one)
+               e->kernel = PK_MFMA64_JIT;      // (kernel_name: the last pruning kernel was a per-tree one)
                if (int rc = select_tiles(e, true, 8, true)) return rc;
                const int n_blocks = e->n_tiles * K;
                int overflow = 0;
-               if (full.max_stack > MFMA_RS) {
-                  overflow = full.max_stack - MFMA_RS;
-                  HIPCHK(e->d_stack.ensure((size_t)n_blocks * overflow * 8 * 1024));
-               }
+               if (int rc = stack_overflow(e, full, n_blocks, 8, &overflow)) return rc;
                if (T.n_scale) HIPCHK(e->d_fscale.ensure((size_t)K * e->n_patt));
-               PruneArgs pr{};
-               pr.ops = nullptr; pr.z = e->d_z.p; pr.z_stride = e->n_patt; pr.tiles = e->d_tiles.p; pr.n_tiles = e->n_tiles;
-               pr.gene_off = e->d_gene_off.p; pr.weights = e->d_weights.p; pr.ztiles = e->d_ztiles.p; pr.zt_bytes = e->zt_bytes;
-               pr.n = n; pr.n_tips = e->n_tips; pr.n_nodes = nn; pr.K = K; pr.n_genes = G; pr.n_codes = e->n_codes;
-               pr.cleandata = e->cleandata; pr.n_pi = e->n_pi; pr.mode = e->mode; pr.n_scale = T.n_scale; pr.keep = 1; pr.n_patt = e->n_patt;
-               pr.pi = e->d_pi.p; pr.pint = e->d_pint.p; pr.ptip = e->d_ptip.p; pr.pcol = e->d_pcol.p; pr.fscale = e->d_fscale.p;
                HIPCHK(e->d_fhK.ensure((size_t)K * e->n_patt));
-               pr.fhK = e->d_fhK.p; pr.partials = e->d_bl_partials.p; pr.scalef = e->d_bl_scalef.p; pr.stack_scratch = e->d_stack.p;
-               pr.stack_overflow_slots = overflow; pr.first_matmul = full.first_matmul; pr.n_int = n_int; pr.first_tip = full.first_tip;
-               pr.tip_words = (long)tip_words(e); pr.tile_group0 = e->d_tile_group0.p; pr.part_groups = e->part_groups();
-               pr.part_dump = e->d_bl_partials.p + words; pr.code_mask = e->d_code_mask.p;
+               PruneArgs pr = prune_args(e, full, K, nullptr, false, T.n_scale, true, e->d_bl_partials.p, e->d_bl_scalef.p, overflow);
                void *params[] = {&pr};
                HIPCHK(hipModuleLaunchKernel(e->jit.fn, std::min(n_blocks, e->n_cu), 1, 1, 8 * 64, 1, 1, 0, st, params, nullptr));
                refill_done = true;
@@ -420,23 +359,8 @@ int paml_amd_eval_branch(paml_amd_engine *e, int node_b, int n_t, const double *
          }
       }
       if (run_prog && !refill_done) {
-         const int n_blocks = e->n_tiles_full * K;
-         int overflow = 0;
-         if (prog.max_stack > MFMA_RS) {
-            overflow = prog.max_stack - MFMA_RS;
-            HIPCHK(e->d_stack.ensure((size_t)n_blocks * overflow * GATHER_WAVES * 1024));
-         }
-         PruneArgs pr{};
-         pr.ops = e->d_ops_tmp.p; pr.z = e->d_z.p; pr.z_stride = e->n_patt; pr.tiles = e->d_tiles_full.p; pr.n_tiles = e->n_tiles_full;
-         pr.gene_off = e->d_gene_off.p; pr.weights = e->d_weights.p;
-         pr.n = n; pr.n_tips = e->n_tips; pr.n_nodes = nn; pr.K = K; pr.n_genes = G; pr.n_codes = e->n_codes;
-         pr.cleandata = e->cleandata; pr.n_pi = e->n_pi; pr.mode = e->mode; pr.n_scale = T.n_scale; pr.keep = 1; pr.n_patt = e->n_patt;
-         pr.pi = e->d_pi.p; pr.pint = e->d_pint.p; pr.ptip = e->d_ptip.p;
          HIPCHK(e->d_fhK.ensure((size_t)K * e->n_patt));
-         pr.fhK = e->d_fhK.p; pr.partials = e->d_bl_partials.p; pr.scalef = e->d_bl_scalef.p; pr.stack_scratch = e->d_stack.p;
-         pr.stack_overflow_slots = overflow; pr.first_matmul = prog.first_matmul; pr.n_int = n_int;
-         pr.first_tip = -1; pr.tip_words = (long)tip_words(e); pr.part_groups = e->part_groups();
-         launch_prune_full(e, prog.max_stack, n_blocks, pr, st);
+         if (int rc = run_prune_full(e, prog, true, nullptr, nullptr)) return rc;
       }
       EigPrepArgs ea{};
       ea.n = n; ea.K = K; ea.n_labels = e->n_labels; ea.n_t = n_t; ea.label = T.label[node_b]; ea.n_codes = e->n_codes;
@@ -528,48 +452,14 @@ int paml_amd_eval_branch(paml_amd_engine *e, int node_b, int n_t, const double *
             if (prog.ops[i].code == OP_MATMUL || prog.ops[i].code == OP_MATMUL_POP) { prog.ops[i].c = next; next = prog.ops[i].a; }
          prog.first_matmul = next;
       }
-      const int maxd = e->kk == KK_VALU20 ? VALU_MAXD_20 : VALU_MAXD_SMALL;
-      if (!mfma && prog.max_stack > maxd) return fail(e, PAML_AMD_EUNSUPPORTED, "tree needs a deeper partial stack than this kernel provides");
+      if (int rc = check_stack_depth(e, prog)) return rc;
       // P(t) of every edge in its new orientation
       HIPCHK(upload(e->d_label_eff, lab_eff.data(), lab_eff.size(), st));
       HIPCHK(upload(e->d_branch, br_eff.data(), br_eff.size(), st));
-      HIPCHK(e->d_rowmajor.ensure((size_t)psets * nn * n * n));
-      if (mfma) HIPCHK(e->d_pint.ensure((size_t)psets * nn * 4096));
-      HIPCHK(e->d_ptip.ensure((size_t)psets * nn * tip_words(e)));
-      PmatArgs pa{};
-      pa.n = n; pa.n_nodes = nn; pa.root = A; pa.K = K; pa.n_genes = G; pa.n_labels = e->n_labels;
-      pa.n_codes = e->n_codes; pa.layout = mfma ? 1 : 0;
-      pa.label = e->d_label_eff.p; pa.is_leaf = e->d_is_leaf.p; pa.branch = e->d_branch.p; pa.rate = e->d_rate.p;
-      pa.gene_rate = e->d_gene_rate.p; pa.eigen_of = e->d_eigen_of.p; pa.qfactor = e->d_qfactor.p;
-      pa.eigen = e->d_eigen.p; pa.n_chara = e->d_n_chara.p; pa.chara_map = e->d_chara_map.p; pa.plain_codes = e->plain_codes;
-      pa.rowmajor = e->d_rowmajor.p; pa.pint = e->d_pint.p; pa.ptip = e->d_ptip.p; pa.tip_words = (long)tip_words(e);
-      pa.B = 1; pa.rate_gs = e->rate_per_gene ? K : 0;
-      {
-         InlineVec iv;
-         iv.n_branch = iv.n_rate = 0;
-         launch_pmat(pa, iv, nn, psets, false, st, pmat_on_matrix_cores(e, pa));
-      }
+      if (int rc = reoriented_pmat(e, A, false)) return rc;
       e->n_pmat += (long)psets * (nn - 2);
-      e->prog_valid = false;      // d_branch / P buffers now hold re-oriented edge data: the next eval rebuilds
-      e->pmat_valid = false;
       HIPCHK(upload(e->d_ops_tmp, prog.ops.data(), prog.ops.size(), st));
-      const int n_blocks = e->n_tiles_full * K;
-      int overflow = 0;
-      if (mfma && prog.max_stack > MFMA_RS) {
-         overflow = prog.max_stack - MFMA_RS;
-         HIPCHK(e->d_stack.ensure((size_t)n_blocks * overflow * GATHER_WAVES * 1024));
-      }
-      PruneArgs pr{};
-      pr.ops = e->d_ops_tmp.p; pr.z = e->d_z.p; pr.z_stride = e->n_patt; pr.tiles = e->d_tiles_full.p; pr.n_tiles = e->n_tiles_full;
-      pr.gene_off = e->d_gene_off.p; pr.weights = e->d_weights.p;
-      pr.n = n; pr.n_tips = e->n_tips; pr.n_nodes = nn; pr.K = K; pr.n_genes = G; pr.n_codes = e->n_codes;
-      pr.cleandata = e->cleandata; pr.n_pi = e->n_pi; pr.mode = e->mode; pr.n_scale = T.n_scale; pr.keep = 1; pr.n_patt = e->n_patt;
-      pr.pi = e->d_pi.p; pr.pint = mfma ? e->d_pint.p : e->d_rowmajor.p; pr.ptip = e->d_ptip.p;
-      pr.fhK = e->d_fhK.p; pr.partials = e->d_bl_partials.p; pr.scalef = e->d_bl_scalef.p; pr.stack_scratch = e->d_stack.p;
-      pr.stack_overflow_slots = overflow; pr.first_matmul = prog.first_matmul; pr.n_int = n_int;
-      pr.first_tip = -1; pr.tip_words = (long)tip_words(e); pr.part_groups = e->part_groups();
-      launch_prune_full(e, prog.max_stack, n_blocks, pr, st);
-      HIPCHK(hipGetLastError());
+      if (int rc = run_prune_full(e, prog, true, nullptr, nullptr)) return rc;
       for (int v = e->n_tips; v < nn; v++) { bc.up[v] = up[v]; bc.ok[v] = 1; }
       e->n_branch_nodes += (long)std::count(clean.begin() + e->n_tips, clean.end(), 0);
    }
@@ -705,7 +595,9 @@ int paml_amd_node_posterior(paml_amd_engine *e, int node, const double *branch, 
    const bool scaled = T.n_scale > 0;
    HIPCHK(e->d_expA.ensure((size_t)K * e->n_patt * n));
    if (scaled) HIPCHK(e->d_expSA.ensure((size_t)K * e->n_patt));
-   r = run_prune_full(e, prog, e->d_expA.p, scaled ? e->d_expSA.p : nullptr);
+   HIPCHK(upload(e->d_ops_tmp, prog.ops.data(), prog.ops.size(), e->stream));
+   HIPCHK(hipStreamSynchronize(e->stream));
+   r = run_prune_full(e, prog, false, e->d_expA.p, scaled ? e->d_expSA.p : nullptr);
    if (r) return r;
    HIPCHK(e->d_expB.ensure((size_t)e->n_patt * n));
    PostArgs pa{};

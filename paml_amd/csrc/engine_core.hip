@@ -86,6 +86,7 @@ int paml_amd_create(paml_amd_engine **out, int n_states, int n_tips, int n_patt,
    e->mfma_dma = n_tips <= MFMA_ZT;
    e->mfma_waves = e->mfma_dma ? DMA_WAVES : GATHER_WAVES;
    e->tile_patt = e->kk == KK_MFMA64 ? e->mfma_waves * 16 : 256;
+   e->kernel = e->kk == KK_MFMA64 ? (e->mfma_dma ? PK_MFMA64_STREAM : PK_MFMA64_GATHER) : PruneKernel(3 * e->kk);      // (until the first evaluation chooses)
    *out = e;
    return 0;
 }
@@ -112,13 +113,9 @@ const char *paml_amd_last_error(const paml_amd_engine *e) { return e ? e->err.c_
 
 const char *paml_amd_kernel_name(const paml_amd_engine *e)
 {
-   if (!e) return "";
-   switch (e->kk) {
-   case KK_VALU4: return e->use_jit ? (e->fused ? "valu4_fused_jit" : "valu4_jit") : "valu4";
-   case KK_VALU5: return e->use_jit ? (e->fused ? "valu5_fused_jit" : "valu5_jit") : "valu5";
-   case KK_VALU20: return e->use_jit ? (e->m20 ? "mfma4x20_jit" : "valu20_jit") : "valu20";
-   default: return e->use_jit ? "mfma64_jit" : (e->mfma_dma ? "mfma64_stream" : (e->coopj ? "mfma64_coopjit" : (e->coop ? "mfma64_coop" : "mfma64_gather")));
-   }
+   static const char *const names[] = {"valu4", "valu4_jit", "valu4_fused_jit", "valu5", "valu5_jit", "valu5_fused_jit", "valu20", "valu20_jit", "mfma4x20_jit",
+                                       "mfma64_jit", "mfma64_stream", "mfma64_coop", "mfma64_coopjit", "mfma64_gather"};      // PruneKernel's order
+   return e ? names[e->kernel] : "";
 }
 
 int paml_amd_set_stream(paml_amd_engine *e, void *hip_stream)

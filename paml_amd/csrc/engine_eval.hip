@@ -59,32 +59,28 @@ int build_tiles(paml_amd_engine *e)
 // TileStash) — the resident partials have ONE layout whatever the tile size (PruneArgs::part_groups), they stay valid.
 int select_tiles(paml_amd_engine *e, bool big_tiles, int want_waves, bool jit_ok)
 {
-   if (big_tiles != e->mfma_dma || want_waves != e->mfma_waves) {
+   const bool change = big_tiles != e->mfma_dma || want_waves != e->mfma_waves;
+   if (change) {
       e->swap_tile_stash();
       e->mfma_dma = big_tiles;
       e->mfma_waves = want_waves;
       e->tile_patt = e->mfma_waves * 16;
-      bool have = e->tiles_built_for == e->tile_patt && e->d_tiles.p;
-      if (have && jit_ok && e->tile_patt >= 128 && (e->n_tips > 200 || !e->zt_key.empty())) {      // piece mode: rows in the program's order
-         const JitZPlan zp = jit_zplan(e->prog, e->n_tips, e->tile_patt);
-         have = (zp.half ? jit_program_key(e->prog, e->n_tips) : std::string()) == e->zt_key;
-      }
-      if (!have)
-         if (int r = build_tiles(e)) return r;
    }
-   else if (jit_ok && e->tile_patt >= 128 && (e->n_tips > 200 || !e->zt_key.empty())) {      // piece mode: the code blocks' rows follow the tree's program
+   bool have = !change || (e->tiles_built_for == e->tile_patt && e->d_tiles.p);
+   if (have && jit_ok && e->tile_patt >= 128 && (e->n_tips > 200 || !e->zt_key.empty())) {      // piece mode: the code blocks' rows follow the tree's program
       const JitZPlan zp = jit_zplan(e->prog, e->n_tips, e->tile_patt);
-      if ((zp.half ? jit_program_key(e->prog, e->n_tips) : std::string()) != e->zt_key)
-         if (int r = build_tiles(e)) return r;
+      have = (zp.half ? jit_program_key(e->prog, e->n_tips) : std::string()) == e->zt_key;
    }
-   return 0;
+   return have ? 0 : build_tiles(e);
 }
 
-// The one-pattern-per-lane interpreter: the register-stack instantiation that fits the program, else the scratch one.
-static void launch_valu(paml_amd_engine *e, int max_stack, int n_blocks, const PruneArgs &pr, hipStream_t s)
+// The full interpreters: gather (21..64 states), else one pattern per lane — the register-stack instantiation that fits the program, else
+// the scratch one.
+void launch_prune_full(paml_amd_engine *e, int max_stack, int n_blocks, const PruneArgs &pr, hipStream_t s)
 {
    const dim3 g(n_blocks), b(256);
    switch (e->kk) {
+   case KK_MFMA64: hipLaunchKernelGGL(prune_mfma64_gather<GATHER_WAVES>, g, dim3(GATHER_WAVES * 64), 0, s, pr); break;
    case KK_VALU4:
       if (max_stack <= 4) hipLaunchKernelGGL((prune_valu<4, 4, true>), g, b, 0, s, pr);
       else hipLaunchKernelGGL((prune_valu<4, VALU_MAXD_SMALL>), g, b, 0, s, pr);
@@ -93,7 +89,7 @@ static void launch_valu(paml_amd_engine *e, int max_stack, int n_blocks, const P
       if (max_stack <= 4) hipLaunchKernelGGL((prune_valu<5, 4, true>), g, b, 0, s, pr);
       else hipLaunchKernelGGL((prune_valu<5, VALU_MAXD_SMALL>), g, b, 0, s, pr);
       break;
-   default:      // 20 states: a register stack costs > 256 VGPRs (one wave per SIMD) and measures 2x slower than scratch
+   case KK_VALU20:      // a register stack costs > 256 VGPRs (one wave per SIMD) and measures 2x slower than scratch
       hipLaunchKernelGGL((prune_valu<20, VALU_MAXD_20>), g, b, 0, s, pr);
       break;
    }
@@ -118,12 +114,6 @@ void launch_pmat(const PmatArgs &pa, const InlineVec &iv, int n_nodes, int psets
    else if (small) hipLaunchKernelGGL(pmat_small_kernel, dim3((n_nodes * psets + 7) / 8), dim3(256), 0, s, pa, iv);
    else if (pa.n <= 32 && pa.layout != 1) hipLaunchKernelGGL(pmat_kernel_t<32>, dim3(gx, psets), dim3(256), 2 * 32 * 32 * sizeof(double), s, pa, iv);
    else hipLaunchKernelGGL(pmat_kernel_t<64>, dim3(gx, psets), dim3(256), 2 * 4096 * sizeof(double), s, pa, iv);
-}
-
-void launch_prune_full(paml_amd_engine *e, int max_stack, int n_blocks, const PruneArgs &pr, hipStream_t s)
-{
-   if (e->kk == KK_MFMA64) hipLaunchKernelGGL(prune_mfma64_gather<GATHER_WAVES>, dim3(n_blocks), dim3(GATHER_WAVES * 64), 0, s, pr);
-   else launch_valu(e, max_stack, n_blocks, pr, s);
 }
 
 void launch_zpm(const unsigned char *z, long z_stride, int n_tips, int n_patt, int zw, unsigned int *out, hipStream_t s)
@@ -180,46 +170,98 @@ int obtain_kernel(paml_amd_engine *e, paml_amd_engine::JitSlot &slot, JitKernel 
    return 0;
 }
 
-int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rate, const unsigned char *clean,
-                double *d_lnL_out, bool want_lnf, const BatchSpec *bs, bool want_pipe, bool want_fhk)
+// ---- the argument structures of P(t) and of the pruning kernels, filled in one place each (engine_state.h says what the sites add);
+// to be called once the buffers have their size ----
+PmatArgs pmat_args(const paml_amd_engine *e, int root, const int *label, int layout, double *pcol)
+{
+   PmatArgs pa{};
+   pa.n = e->n; pa.n_nodes = e->tree.n_nodes; pa.root = root; pa.K = e->K; pa.n_genes = e->n_genes; pa.n_labels = e->n_labels;
+   pa.n_codes = e->n_codes; pa.layout = layout; pa.pcol = pcol; pa.B = 1; pa.rate_gs = e->rate_per_gene ? e->K : 0;
+   pa.label = label; pa.is_leaf = e->d_is_leaf.p; pa.branch = e->d_branch.p; pa.rate = e->d_rate.p;
+   pa.gene_rate = e->d_gene_rate.p; pa.eigen_of = e->d_eigen_of.p; pa.qfactor = e->d_qfactor.p;
+   pa.eigen = e->d_eigen.p; pa.n_chara = e->d_n_chara.p; pa.chara_map = e->d_chara_map.p; pa.plain_codes = e->plain_codes;
+   pa.rowmajor = e->d_rowmajor.p; pa.pint = e->d_pint.p; pa.ptip = e->d_ptip.p; pa.tip_words = (long)tip_words(e);
+   return pa;
+}
+
+// `prog` runs from `ops` over the tiles of the selected kernel or the 64-pattern / 256-pattern ones of the full interpreters, for K classes;
+// keep-partials STOREs / LOADs and the scale factors go to `partials` / `scalef`.
+PruneArgs prune_args(const paml_amd_engine *e, const Program &prog, int K, const Op *ops, bool full_tiles, int n_scale, bool keep, double *partials,
+                     double *scalef, int overflow)
+{
+   const bool mfma = e->kk == KK_MFMA64;
+   PruneArgs pr{};
+   pr.ops = ops; pr.z = e->d_z.p; pr.z_stride = e->n_patt;
+   pr.tiles = full_tiles ? e->d_tiles_full.p : e->d_tiles.p; pr.n_tiles = full_tiles ? e->n_tiles_full : e->n_tiles;
+   pr.gene_off = e->d_gene_off.p; pr.weights = e->d_weights.p; pr.ztiles = e->d_ztiles.p; pr.zt_bytes = e->zt_bytes;
+   pr.n = e->n; pr.n_tips = e->n_tips; pr.n_nodes = e->tree.n_nodes; pr.K = K; pr.n_genes = e->n_genes; pr.n_codes = e->n_codes;
+   pr.cleandata = e->cleandata; pr.n_pi = e->n_pi; pr.mode = e->mode; pr.n_scale = n_scale; pr.keep = keep ? 1 : 0; pr.n_patt = e->n_patt;
+   pr.pi = e->d_pi.p; pr.pint = mfma ? e->d_pint.p : e->d_rowmajor.p; pr.ptip = e->d_ptip.p;
+   pr.fscale = e->d_fscale.p; pr.pcol = e->d_pcol.p;
+   pr.fhK = e->d_fhK.p; pr.partials = partials; pr.scalef = scalef; pr.stack_scratch = e->d_stack.p;
+   pr.stack_overflow_slots = overflow; pr.first_matmul = prog.first_matmul; pr.first_tip = prog.first_tip; pr.n_int = pr.n_nodes - e->n_tips;
+   pr.tile_group0 = e->d_tile_group0.p; pr.part_groups = e->part_groups(); pr.code_mask = e->d_code_mask.p;
+   pr.part_dump = (keep && mfma) ? partials + (size_t)K * pr.n_int * e->part_groups() * 1024 : nullptr;
+   pr.stream = e->d_stream.p; pr.n_stream = (int)(e->prog.stream.size() / 2); pr.tip_words = (long)tip_words(e);
+   pr.zpm = e->d_zpm.p; pr.zpm_words = e->zpm_words;
+   return pr;
+}
+
+// ---- one evaluation, phase by phase (launch_eval, below, is the list) -----------------------------------------------------------------
+namespace {
+
+// The arguments of launch_eval and the locals its phases share; lives on launch_eval's stack.
+struct Eval {
+   const double *branch, *gene_rate;
+   const unsigned char *clean; double *d_lnL_out; const BatchSpec *bs;
+   bool want_lnf, want_pipe, want_fhk, slot_waited;
+   int B, K, Km, G, psets;          // Km: classes of the model; K: classes the kernels see
+   bool keep, new_prog, use_inline;
+   bool pipe, dual, skip_entry;     // the fast path of consecutive eval_device calls; two pruning streams; nothing waits for this evaluation's entry event
+   hipStream_t ms, ps;              // the stream of the pruning kernel and the partial sums; of the uploads and the P(t) kernel
+   bool offload, side_total;        // the whole reduction / the (all-reduce and the) fixed-order total on the side stream `sc`
+   int lane, slot;                  // two pruning streams: this evaluation's; its reduction slot
+   int n_blocks, overflow;          // workgroups of the interpreters (tiles x classes); stack slots in global scratch
+};
+
+int begin_eval(paml_amd_engine *e, Eval &c)
 {
    if (!(e->have_tips && e->have_tree && e->have_pi && e->have_classes))
       return fail(e, PAML_AMD_EINVAL, "eval before set_tips/set_tree/set_pi/set_classes");
    if (e->eigen.empty()) return fail(e, PAML_AMD_EINVAL, "eval before any set_eigen_*");
-   const bool keep = (e->flags & PAML_AMD_KEEP_PARTIALS) != 0;
-   if (clean && (!keep || !e->partials_valid))
+   c.keep = (e->flags & PAML_AMD_KEEP_PARTIALS) != 0;
+   if (c.clean && (!c.keep || !e->partials_valid))
       return fail(e, PAML_AMD_EINVAL, "eval_dirty needs PAML_AMD_KEEP_PARTIALS and a previous full evaluation");
-   const int B = bs ? bs->B : 1, Km = e->K;          // Km: classes of the model; K: classes the kernels see
-   const int n = e->n, nn = e->tree.n_nodes, K = Km * B, G = e->n_genes;
-   const int psets = G * K;
-   if (B > 1 && (keep || clean)) return fail(e, PAML_AMD_EUNSUPPORTED, "eval_batch: not with PAML_AMD_KEEP_PARTIALS");
-
+   c.B = c.bs ? c.bs->B : 1; c.Km = e->K; c.K = c.Km * c.B; c.G = e->n_genes; c.psets = c.G * c.K;
+   if (c.B > 1 && (c.keep || c.clean)) return fail(e, PAML_AMD_EUNSUPPORTED, "eval_batch: not with PAML_AMD_KEEP_PARTIALS");
    // program (tree walk) — rebuilt when the tree or the clean set changes
-   const bool new_prog = !e->prog_valid || clean;
-   if (new_prog) {
-      e->prog = build_program(e->tree, keep, clean);
-      e->prog_valid = (clean == nullptr);
-      const int maxd = e->kk == KK_VALU20 ? VALU_MAXD_20 : VALU_MAXD_SMALL;
-      if (e->kk != KK_MFMA64 && e->prog.max_stack > maxd) {
-         e->prog_valid = false;
-         return fail(e, PAML_AMD_EUNSUPPORTED, "tree needs a deeper partial stack than this kernel provides");
-      }
+   c.new_prog = !e->prog_valid || c.clean;
+   if (c.new_prog) {
+      e->prog = build_program(e->tree, c.keep, c.clean);
+      e->prog_valid = (c.clean == nullptr);
+      if (int rc = check_stack_depth(e, e->prog)) { e->prog_valid = false; return rc; }
    }
+   return 0;
+}
+
+// The streams and events of a pipelined evaluation, and what its side stream has to wait for.
+int setup_streams(paml_amd_engine *e, Eval &c)
+{
    // the fast path of consecutive eval_device calls (see pipe_ok): nothing but branch lengths / gene rates may have changed
    // (worth its event traffic only where the pruning kernel is long: the 21..64-state kernels and the 20-state matrix-core kernel on
    //  >= 10^5 pattern-classes)
-   want_pipe = want_pipe && (e->kk == KK_MFMA64 || (e->kk == KK_VALU20 && e->want_m20)) && (long)e->n_patt * e->K >= 100000;
-   const bool pipe = want_pipe && e->pipe_ok && !bs && !clean && !keep && !new_prog && !e->eigen_dirty;
+   c.want_pipe = c.want_pipe && (e->kk == KK_MFMA64 || (e->kk == KK_VALU20 && e->want_m20)) && (long)e->n_patt * e->K >= 100000;
+   c.pipe = c.want_pipe && e->pipe_ok && !c.bs && !c.clean && !c.keep && !c.new_prog && !e->eigen_dirty;
    // Two pruning streams (paml_amd_engine::sb): from the second evaluation of such a run on, the evaluations alternate between the
    // engine's stream and `sb`, so that the persistent workgroups of evaluation i + 1 take the CUs as those of evaluation i leave
    // them — no kernel boundary, reduction or half-empty last round of tiles between two pruning kernels.  lane = reduction slot.
-   const bool dual = pipe && e->dual_ok && !e->profiling;
-   const int lane = dual ? e->red_slot : 0;
-   if (dual && lane && !e->sb[lane - 1]) HIPCHK(create_engine_stream(&e->sb[lane - 1]));
-   if (dual)
+   c.dual = c.pipe && e->dual_ok && !e->profiling;
+   c.lane = c.dual ? e->red_slot : 0;
+   if (c.dual && c.lane && !e->sb[c.lane - 1]) HIPCHK(create_engine_stream(&e->sb[c.lane - 1]));
+   if (c.dual)
       if (int rc = ensure_side_stream(e)) return rc;
-   hipStream_t const ms = lane ? e->sb[lane - 1] : e->stream;      // the stream of this evaluation's pruning kernel and partial sums
-   if (want_pipe && !e->s2) {
+   c.ms = c.lane ? e->sb[c.lane - 1] : e->stream;
+   if (c.want_pipe && !e->s2) {
       for (hipEvent_t &ev : e->ev_setread) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
       for (int i = 0; i < paml_amd_engine::NPSET - 1; i++) e->spare[i].id = i + 1;
       HIPCHK(create_engine_stream(&e->s2));
@@ -227,19 +269,27 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
       HIPCHK(hipEventCreateWithFlags(&e->ev_entry[1], hipEventDisableTiming));
       HIPCHK(hipEventCreateWithFlags(&e->ev_pmat, hipEventDisableTiming));
    }
-   hipStream_t ps = e->stream;                    // stream of the uploads and of the P(t) kernel
-   if (pipe) {
+   c.ps = e->stream;
+   if (c.pipe) {
       // the side stream may overwrite the other P set once everything the main stream held in front of the PREVIOUS pruning
       // kernel is done: that set's last reader (the kernel before it), and the previous evaluation's own uploads and P(t)
-      ps = e->s2;
+      c.ps = e->s2;
       // (two pruning streams: only the run's first such evaluation — the uploads in front of the run; after that the side stream
       //  waits for nothing but the last reader of the set it is about to overwrite, four evaluations back)
-      if (e->have_prev_entry && !(dual && e->dual_run)) HIPCHK(hipStreamWaitEvent(e->s2, e->ev_entry[e->entry_sel ^ 1], 0));
+      if (e->have_prev_entry && !(c.dual && e->dual_run)) HIPCHK(hipStreamWaitEvent(e->s2, e->ev_entry[e->entry_sel ^ 1], 0));
       const int nid = e->spare[e->spare_head].id;
-      if (dual && e->setread_rec[nid]) HIPCHK(hipStreamWaitEvent(e->s2, e->ev_setread[nid], 0));
+      if (c.dual && e->setread_rec[nid]) HIPCHK(hipStreamWaitEvent(e->s2, e->ev_setread[nid], 0));
    }
-   const bool skip_entry = dual && e->dual_run;      // (nothing waits for this evaluation's entry event)
-   e->dual_run = dual;
+   c.skip_entry = c.dual && e->dual_run;
+   e->dual_run = c.dual;
+   return 0;
+}
+
+// The small inputs: branch lengths and gene rates, the batch's class tables, the eigen table, the program.
+int stage_inputs(paml_amd_engine *e, Eval &c, InlineVec &iv)
+{
+   const int B = c.B, Km = c.Km, G = c.G, nn = e->tree.n_nodes;
+   const BatchSpec *const bs = c.bs;
    std::vector<EigenDev> tab;
    if (e->eigen_dirty)
       if (int rc = eigen_table(e, tab)) return rc;
@@ -247,87 +297,69 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
       if (int rc = eigen_refs_ok(e, e->h_eigen_of.data(), e->h_eigen_of.size(), "eval")) return rc;
 
    // branch lengths and gene rates of a single evaluation ride in the kernel arguments of P(t) (InlineVec): no copy at all
-   InlineVec iv;
    iv.n_branch = iv.n_rate = 0;
-   const bool use_inline = B == 1 && nn + G <= PMAT_INLINE_MAX;
-   if (use_inline) {
+   c.use_inline = B == 1 && nn + G <= PMAT_INLINE_MAX;
+   if (c.use_inline) {
       iv.n_branch = nn; iv.n_rate = G;
-      memcpy(iv.v, branch, (size_t)nn * sizeof(double));
-      for (int g = 0; g < G; g++) iv.v[nn + g] = gene_rate ? gene_rate[g] : 1.0;
+      memcpy(iv.v, c.branch, (size_t)nn * sizeof(double));
+      for (int g = 0; g < G; g++) iv.v[nn + g] = c.gene_rate ? c.gene_rate[g] : 1.0;
    }
    // the other small inputs (and the batched ones) go through the pinned arena: async H2D, no host stall
-   if (!use_inline || bs || !tab.empty() || new_prog) {
-      const size_t L = (size_t)e->n_labels;
-      const size_t need = (size_t)B * nn * 8 + (size_t)B * G * 8 + tab.size() * sizeof(EigenDev) +
-                          (bs ? (size_t)B * (G * Km * L * 4 + Km * L * 8 + 2 * Km * 8) + 64 : 0) +
-                          (new_prog ? e->prog.ops.size() * sizeof(Op) + e->prog.stream.size() * sizeof(int) : 0) + 256;
-      HIPCHK(e->stage.begin(need));
-      DevBuf<double> &dbr = pipe ? e->d2_branch : e->d_branch, &dgr = pipe ? e->d2_gene_rate : e->d_gene_rate;   // (the side stream has its own)
-      e->bl_gr_sent = false;
-      HIPCHK(dbr.ensure((size_t)B * nn));
-      HIPCHK(dgr.ensure((size_t)B * G));
-      if (!use_inline) {
-         const double *hb = e->stage.put(branch, (size_t)B * nn);
-         HIPCHK(hipMemcpyAsync(dbr.p, hb, (size_t)B * nn * 8, hipMemcpyHostToDevice, ps));
-         std::vector<double> gr((size_t)B * G, 1.0);
-         if (gene_rate) gr.assign(gene_rate, gene_rate + (size_t)B * G);
-         const double *hg = e->stage.put(gr.data(), gr.size());
-         HIPCHK(hipMemcpyAsync(dgr.p, hg, gr.size() * 8, hipMemcpyHostToDevice, ps));
-      }
-      if (bs) {      // per-element class tables
-         if (bs->eigen_of) {
-            const size_t cnt = (size_t)B * G * Km * L;
-            if (int rc = eigen_refs_ok(e, bs->eigen_of, cnt, "eval_batch")) return rc;
-            HIPCHK(e->d_b_eigen_of.ensure(cnt));
-            const int *h = e->stage.put(bs->eigen_of, cnt);
-            HIPCHK(hipMemcpyAsync(e->d_b_eigen_of.p, h, cnt * 4, hipMemcpyHostToDevice, e->stream));
-         }
-         const double *src[3] = {bs->qfactor, bs->freqK, bs->rate};
-         DevBuf<double> *dst[3] = {&e->d_b_qfactor, &e->d_b_freqK, &e->d_b_rate};
-         const size_t cnt[3] = {(size_t)B * Km * L, (size_t)B * Km, (size_t)B * Km * (e->rate_per_gene ? G : 1)};
-         for (int i = 0; i < 3; i++)
-            if (src[i]) {
-               HIPCHK(dst[i]->ensure(cnt[i]));
-               const double *h = e->stage.put(src[i], cnt[i]);
-               HIPCHK(hipMemcpyAsync(dst[i]->p, h, cnt[i] * 8, hipMemcpyHostToDevice, e->stream));
-            }
-      }
-      if (!tab.empty()) {
-         HIPCHK(e->d_eigen.ensure(tab.size()));
-         const EigenDev *ht = e->stage.put(tab.data(), tab.size());
-         HIPCHK(hipMemcpyAsync(e->d_eigen.p, ht, tab.size() * sizeof(EigenDev), hipMemcpyHostToDevice, e->stream));
-         e->eigen_dirty = false;
-      }
-      if (new_prog) {
-         HIPCHK(e->d_ops.ensure(e->prog.ops.size()));
-         const Op *ho = e->stage.put(e->prog.ops.data(), e->prog.ops.size());
-         HIPCHK(hipMemcpyAsync(e->d_ops.p, ho, e->prog.ops.size() * sizeof(Op), hipMemcpyHostToDevice, e->stream));
-         HIPCHK(e->d_stream.ensure(e->prog.stream.size() + 2));
-         if (!e->prog.stream.empty()) {
-            const int *hs = e->stage.put(e->prog.stream.data(), e->prog.stream.size());
-            HIPCHK(hipMemcpyAsync(e->d_stream.p, hs, e->prog.stream.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-         }
-      }
-      HIPCHK(e->stage.end(ps));
+   if (c.use_inline && !bs && tab.empty() && !c.new_prog) return 0;
+   const size_t L = (size_t)e->n_labels;
+   const size_t need = (size_t)B * nn * 8 + (size_t)B * G * 8 + tab.size() * sizeof(EigenDev) +
+                       (bs ? (size_t)B * (G * Km * L * 4 + Km * L * 8 + 2 * Km * 8) + 64 : 0) +
+                       (c.new_prog ? e->prog.ops.size() * sizeof(Op) + e->prog.stream.size() * sizeof(int) : 0) + 256;
+   HIPCHK(e->stage.begin(need));
+   DevBuf<double> &dbr = c.pipe ? e->d2_branch : e->d_branch, &dgr = c.pipe ? e->d2_gene_rate : e->d_gene_rate;   // (the side stream has its own)
+   e->bl_gr_sent = false;
+   HIPCHK(dbr.ensure((size_t)B * nn));
+   HIPCHK(dgr.ensure((size_t)B * G));
+   if (!c.use_inline) {
+      const double *hb = e->stage.put(c.branch, (size_t)B * nn);
+      HIPCHK(hipMemcpyAsync(dbr.p, hb, (size_t)B * nn * 8, hipMemcpyHostToDevice, c.ps));
+      std::vector<double> gr((size_t)B * G, 1.0);
+      if (c.gene_rate) gr.assign(c.gene_rate, c.gene_rate + (size_t)B * G);
+      const double *hg = e->stage.put(gr.data(), gr.size());
+      HIPCHK(hipMemcpyAsync(dgr.p, hg, gr.size() * 8, hipMemcpyHostToDevice, c.ps));
    }
+   if (bs) {      // per-element class tables
+      if (bs->eigen_of) {
+         const size_t cnt = (size_t)B * G * Km * L;
+         if (int rc = eigen_refs_ok(e, bs->eigen_of, cnt, "eval_batch")) return rc;
+         HIPCHK(e->stage.send(e->d_b_eigen_of, bs->eigen_of, cnt, e->stream));
+      }
+      const double *src[3] = {bs->qfactor, bs->freqK, bs->rate};
+      DevBuf<double> *dst[3] = {&e->d_b_qfactor, &e->d_b_freqK, &e->d_b_rate};
+      const size_t cnt[3] = {(size_t)B * Km * L, (size_t)B * Km, (size_t)B * Km * (e->rate_per_gene ? G : 1)};
+      for (int i = 0; i < 3; i++)
+         if (src[i]) HIPCHK(e->stage.send(*dst[i], src[i], cnt[i], e->stream));
+   }
+   if (!tab.empty()) {
+      HIPCHK(e->stage.send(e->d_eigen, tab.data(), tab.size(), e->stream));
+      e->eigen_dirty = false;
+   }
+   if (c.new_prog) {
+      HIPCHK(e->stage.send(e->d_ops, e->prog.ops.data(), e->prog.ops.size(), e->stream));
+      HIPCHK(e->d_stream.ensure(e->prog.stream.size() + 2));
+      if (!e->prog.stream.empty()) {
+         const int *hs = e->stage.put(e->prog.stream.data(), e->prog.stream.size());
+         HIPCHK(hipMemcpyAsync(e->d_stream.p, hs, e->prog.stream.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+      }
+   }
+   HIPCHK(e->stage.end(c.ps));
+   return 0;
+}
 
-   // P(t) storage (pipelined: the set the previous evaluation did not use)
-   if (pipe) {
-      paml_amd_engine::PSet &sp = e->spare[e->spare_head];      // the set used longest ago
-      std::swap(e->d_rowmajor, sp.rowmajor); std::swap(e->d_pint, sp.pint); std::swap(e->d_ptip, sp.ptip); std::swap(e->d_pcol, sp.pcol);
-      std::swap(e->pset, sp.id);
-      e->spare_head = (e->spare_head + 1) % (paml_amd_engine::NPSET - 1);
-   }
-   HIPCHK(e->d_rowmajor.ensure((size_t)psets * nn * n * n));
-   if (e->kk == KK_MFMA64) HIPCHK(e->d_pint.ensure((size_t)psets * nn * 4096));
-   if (e->kk == KK_VALU20 && e->want_m20) HIPCHK(e->d_pint.ensure((size_t)psets * nn * 400));      // (20 states on the matrix cores: the operand-order copies, pmat layout 2)
-   if (e->kk == KK_MFMA64) HIPCHK(e->d_pcol.ensure((size_t)psets * nn * 64));
-   HIPCHK(e->d_ptip.ensure((size_t)psets * nn * tip_words(e)));
-   HIPCHK(e->d_fhK.ensure((size_t)K * e->n_patt));
-   // kernel choice for the 21..64-state path:
-   //   jit    — straight-line kernel specialised for this tree (jit.h), 128 patterns per workgroup
-   //   stream — the interpreter over the same operand stream (lean programs only), 128 patterns per workgroup
-   //   gather — the full interpreter (keep-partials STORE/LOAD, deep stacks, > MFMA_ZT tips, > 64 codes), 64 per workgroup
+// The pruning kernel of this evaluation: every obtain_kernel call of an evaluation and the tile tables.  Nonzero (*out untouched) only
+// under PAML_AMD_JIT_STRICT or when the tile tables cannot be built.  21..64 states:
+//   jit    — straight-line kernel specialised for this tree (jit.h), 128 patterns per workgroup
+//   stream — the interpreter over the same operand stream (lean programs only), 128 patterns per workgroup
+//   gather — the full interpreter (keep-partials STORE/LOAD, deep stacks, > MFMA_ZT tips, > 64 codes), 64 per workgroup
+//   coop, coopjit — small data sets, below
+int choose_kernel(paml_amd_engine *e, const Eval &c, PruneKernel *out)
+{
+   const int n = e->n, Km = c.Km, G = c.G;
    if (e->kk == KK_MFMA64) {
       bool lean = e->prog.max_stack <= MFMA_RS && e->n_tips <= MFMA_ZT && e->n_codes <= 64;
       // small data sets (at most a quarter of the CUs get a 128-pattern tile): the 64-pattern workgroups of the gather kernel —
@@ -363,73 +395,20 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
             if (int r = obtain_kernel(e, e->jit_slot, &e->jit, true, key, [&]() { return jit_generate(e->prog, e->n_tips, n, e->n_codes); },
                                       background ? JIT_WAIT_WORKER : JIT_WAIT_CALLER, "tree", &jit_ok)) return r;
       }
-      e->use_jit = jit_ok;
       const bool big_tiles = jit_ok || lean;
       const int want_waves = jit_ok ? jw : (lean ? DMA_WAVES : GATHER_WAVES);
       if (int r = select_tiles(e, big_tiles, want_waves, jit_ok)) return r;
-   }
-   if (e->kk != KK_MFMA64) {      // 4 / 5 / 20 states: the interpreter unrolled for this tree
-      bool jit_ok = false, fused = false;
-      // (20 states: the unrolled walk needs > 256 VGPRs and runs at one wave per SIMD, slower than the interpreter)
-      if (e->jit_enabled && !keep && n <= 5 && jit_valu_supported(e->prog)) {
-         // the fused form (classes inside, LDS tip tables, reduction in the epilogue) when the model fits it
-         const ValuFusedPlan pl = jit_valu_fused_plan(e->prog, n, e->n_tips, e->n_codes, Km, e->chunk);
-         // Several genes (round 6): the fused form exists (jit_generate_valu_fused with G > 1: one gene's tables at a time, refilled where a
-         // workgroup's chunks cross into the next gene; same bits) and is NOT the default: on MI355X it measures no faster than the unfused
-         // kernel + reduce_stage1, which serve genes for free — a workgroup is one (tile, class) there — 32 taxa x 10^5 patterns x Gamma-4 in 4
-         // genes: one evaluation 0.050 ms fused against 0.030 unfused, a gradient's 122 evaluations in one launch 1.77 against 1.77 ms (one
-         // gene, fused: 0.029 / 1.33).  Why the several-genes form of the same inner loop runs 1.6 x slower than the one-gene form OUTSIDE
-         // the profiler (within 4 % of it under rocprofv3, equal instruction counts) was bisected to the table fill living inside the
-         // chunk loop and not resolved: profiles/r06_genes_4state.txt.  PAML_AMD_VF_GENES=1 switches it on (tests, measurements).
-         const bool vf_genes = getenv("PAML_AMD_VF_GENES") && atoi(getenv("PAML_AMD_VF_GENES")) != 0;      // (read per call: tests switch it)
-         if (pl.ok && (G == 1 ? e->n_pi == 1 : (vf_genes && (e->n_pi == 1 || e->n_pi == G))) && e->d_zpm.p && G <= 64) {
-            // (4 states: a matrix-core form (v_mfma_f64_4x4x4) was correct but slower, 0.32 of peak against 0.64: profiles/r02_valu_fused_shapes.txt)
-            int r = obtain_kernel(e, e->jit_slot, &e->jit, true, std::string("vf") + std::to_string(n) + "c" + std::to_string(e->n_codes) + "k" + std::to_string(Km) + "r" + std::to_string(pl.R) + "w" +
-                                        std::to_string(pl.CW) + (pl.cherry ? "y" : "n") + (G > 1 ? "g" + std::to_string(G) + ":" : ":") + jit_program_key(e->prog, e->n_tips),
-                                  [&]() { return jit_generate_valu_fused(e->prog, n, e->n_tips, e->n_codes, Km, e->chunk, G); }, JIT_WAIT_CALLER, "valu fused", &jit_ok);
-            if (r) return r;
-            fused = jit_ok;
-            e->fused_threads = 256 * pl.CW;
-         }
-         if (!jit_ok) {
-            int r = obtain_kernel(e, e->jit_slot, &e->jit, true, "v" + std::to_string(n) + ":" + jit_program_key(e->prog, e->n_tips),
-                                  [&]() { return jit_generate_valu(e->prog, n); }, JIT_WAIT_CALLER, "valu", &jit_ok);
-            if (r) return r;
-         }
+      if (jit_ok || e->mfma_dma) {
+         *out = jit_ok ? PK_MFMA64_JIT : PK_MFMA64_STREAM;
+         return 0;
       }
-      e->m20 = false;
-      if (e->want_m20 && !clean && jit_m20_supported(e->prog, e->n_tips, G)) {
-         int r = obtain_kernel(e, e->jit_slot, &e->jit, true, std::string("m20c") + std::to_string(e->n_codes) + (G > 1 ? "g:" : ":") + jit_program_key(e->prog, e->n_tips),
-                               [&]() { return jit_generate_m20(e->prog, e->n_tips, e->n_codes, G > 1 ? 2 : 1); }, JIT_WAIT_CALLER, "m20", &jit_ok);
-         if (r) return r;
-         e->m20 = jit_ok;
-      }
-      e->use_jit = jit_ok;
-      e->fused = fused;
-   }
-   const bool use_dma = e->mfma_dma;
-   const int n_blocks = e->n_tiles * K;
-   const int n_int = nn - e->n_tips;
-   if (keep) {
-      size_t words = e->kk == KK_MFMA64 ? (size_t)K * n_int * e->part_groups() * 1024 + (size_t)std::max(e->mfma_waves, 8) * 1024      // (+ PruneArgs::part_dump: a row per wave)
-                                        : (size_t)K * n_int * e->n_patt * n;
-      HIPCHK(e->d_partials.ensure(words));
-      HIPCHK(e->d_scalef.ensure((size_t)K * std::max(1, e->tree.n_scale) * e->n_patt));
-   }
-   int overflow = 0;
-   if (e->kk == KK_MFMA64 && e->prog.max_stack > MFMA_RS) {
-      overflow = e->prog.max_stack - MFMA_RS;
-      HIPCHK(e->d_stack.ensure((size_t)n_blocks * overflow * e->mfma_waves * 1024));
-   }
-
-   // Small data sets on the 21..64-state interpreters: every 16-pattern group can have a CU (ONE round: the kernels' LDS leaves room for
-   // one workgroup per CU, and two rounds of a 25 us walk lose to one round of the gather kernel's 39) — four waves per group
-   // (prune_mfma64_coop), and once the tree's own kernel is there, that one with the reduction inside (jit_generate_coop: one launch
-   // after P(t) per evaluation).  Single engines only: with pattern shards the chunk sums go through the exchange step.
-   bool coop = false, coopj = false;
-   if (e->kk == KK_MFMA64 && !e->use_jit && !use_dma) {
-      coop = !keep && !clean && !e->env.no_coop && e->tile_patt == 64 && e->prog.max_stack <= COOP_SLOTS &&
-             (long)e->n_tiles * 4 * K <= (long)e->n_cu && !e->env.prof_ops.size();
+      // Small data sets on the 21..64-state interpreters: every 16-pattern group can have a CU (ONE round: the kernels' LDS leaves room for
+      // one workgroup per CU, and two rounds of a 25 us walk lose to one round of the gather kernel's 39) — four waves per group
+      // (prune_mfma64_coop), and once the tree's own kernel is there, that one with the reduction inside (jit_generate_coop: one launch
+      // after P(t) per evaluation).  Single engines only: with pattern shards the chunk sums go through the exchange step.
+      bool coop = !c.keep && !c.clean && !e->env.no_coop && e->tile_patt == 64 && e->prog.max_stack <= COOP_SLOTS &&
+                  (long)e->n_tiles * 4 * c.K <= (long)e->n_cu && !e->env.prof_ops.size();
+      bool coopj = false;
       for (const Op &o : e->prog.ops) coop = coop && o.code != OP_STORE && o.code != OP_LOAD && o.code != OP_EXPORT;
       if (coop && e->coopj_enabled && !e->comm && e->nb_global == (e->n_patt + e->chunk - 1) / e->chunk && e->first_chunk == 0 &&
           jit_coop_supported(e->prog, e->n_tips, e->n_codes)) {
@@ -437,21 +416,83 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
          if (int r = obtain_kernel(e, e->coop_slot, &e->jit_coop, false, key, [&]() { return jit_generate_coop(e->prog, e->n_tips, n); },
                                    (e->jit_forced || e->env.jit_sync) ? JIT_WAIT_CALLER : JIT_WAIT_WORKER, "coop", &coopj)) return r;
       }
+      *out = coopj ? PK_MFMA64_COOPJIT : (coop ? PK_MFMA64_COOP : PK_MFMA64_GATHER);
+      return 0;
    }
-   e->coop = coop; e->coopj = coopj;
+   // 4 / 5 / 20 states: the interpreter unrolled for this tree
+   bool jit_ok = false, second = false;      // second: the fused form (4 / 5 states), the matrix-core form (20)
+   // (20 states: the unrolled walk needs > 256 VGPRs and runs at one wave per SIMD, slower than the interpreter)
+   if (e->jit_enabled && !c.keep && n <= 5 && jit_valu_supported(e->prog)) {
+      // the fused form (classes inside, LDS tip tables, reduction in the epilogue) when the model fits it
+      const ValuFusedPlan pl = jit_valu_fused_plan(e->prog, n, e->n_tips, e->n_codes, Km, e->chunk);
+      // Several genes (round 6): the fused form exists (jit_generate_valu_fused with G > 1: one gene's tables at a time, refilled where a
+      // workgroup's chunks cross into the next gene; same bits) and is NOT the default: on MI355X it measures no faster than the unfused
+      // kernel + reduce_stage1, which serve genes for free — a workgroup is one (tile, class) there — 32 taxa x 10^5 patterns x Gamma-4 in 4
+      // genes: one evaluation 0.050 ms fused against 0.030 unfused, a gradient's 122 evaluations in one launch 1.77 against 1.77 ms (one
+      // gene, fused: 0.029 / 1.33).  Why the several-genes form of the same inner loop runs 1.6 x slower than the one-gene form OUTSIDE
+      // the profiler (within 4 % of it under rocprofv3, equal instruction counts) was bisected to the table fill living inside the
+      // chunk loop and not resolved: profiles/r06_genes_4state.txt.  PAML_AMD_VF_GENES=1 switches it on (tests, measurements).
+      const bool vf_genes = getenv("PAML_AMD_VF_GENES") && atoi(getenv("PAML_AMD_VF_GENES")) != 0;      // (read per call: tests switch it)
+      if (pl.ok && (G == 1 ? e->n_pi == 1 : (vf_genes && (e->n_pi == 1 || e->n_pi == G))) && e->d_zpm.p && G <= 64) {
+         // (4 states: a matrix-core form (v_mfma_f64_4x4x4) was correct but slower, 0.32 of peak against 0.64: profiles/r02_valu_fused_shapes.txt)
+         int r = obtain_kernel(e, e->jit_slot, &e->jit, true, std::string("vf") + std::to_string(n) + "c" + std::to_string(e->n_codes) + "k" + std::to_string(Km) + "r" + std::to_string(pl.R) + "w" +
+                                     std::to_string(pl.CW) + (pl.cherry ? "y" : "n") + (G > 1 ? "g" + std::to_string(G) + ":" : ":") + jit_program_key(e->prog, e->n_tips),
+                               [&]() { return jit_generate_valu_fused(e->prog, n, e->n_tips, e->n_codes, Km, e->chunk, G); }, JIT_WAIT_CALLER, "valu fused", &jit_ok);
+         if (r) return r;
+         second = jit_ok;
+         e->fused_threads = 256 * pl.CW;
+      }
+      if (!jit_ok) {
+         int r = obtain_kernel(e, e->jit_slot, &e->jit, true, "v" + std::to_string(n) + ":" + jit_program_key(e->prog, e->n_tips),
+                               [&]() { return jit_generate_valu(e->prog, n); }, JIT_WAIT_CALLER, "valu", &jit_ok);
+         if (r) return r;
+      }
+   }
+   if (e->want_m20 && !c.clean && jit_m20_supported(e->prog, e->n_tips, G)) {
+      int r = obtain_kernel(e, e->jit_slot, &e->jit, true, std::string("m20c") + std::to_string(e->n_codes) + (G > 1 ? "g:" : ":") + jit_program_key(e->prog, e->n_tips),
+                            [&]() { return jit_generate_m20(e->prog, e->n_tips, e->n_codes, G > 1 ? 2 : 1); }, JIT_WAIT_CALLER, "m20", &jit_ok);
+      if (r) return r;
+      second = jit_ok;
+   }
+   *out = PruneKernel(3 * e->kk + (second ? 2 : (jit_ok ? 1 : 0)));
+   return 0;
+}
 
-   // Kernel A: batched P(t)
-   PmatArgs pa{};
-   pa.n = n; pa.n_nodes = nn; pa.root = e->tree.root; pa.K = Km; pa.n_genes = G; pa.n_labels = e->n_labels;
-   pa.n_codes = e->n_codes; pa.layout = e->kk == KK_MFMA64 ? 1 : ((e->kk == KK_VALU20 && e->use_jit && e->m20) ? 2 : 0);
-   pa.label = e->d_label.p; pa.is_leaf = e->d_is_leaf.p; pa.branch = pipe ? e->d2_branch.p : e->d_branch.p; pa.rate = e->d_rate.p;
-   pa.gene_rate = pipe ? e->d2_gene_rate.p : e->d_gene_rate.p; pa.eigen_of = e->d_eigen_of.p; pa.qfactor = e->d_qfactor.p;
-   pa.eigen = e->d_eigen.p; pa.n_chara = e->d_n_chara.p; pa.chara_map = e->d_chara_map.p; pa.plain_codes = e->plain_codes;
-   pa.rowmajor = e->d_rowmajor.p; pa.pint = e->d_pint.p; pa.ptip = e->d_ptip.p; pa.tip_words = (long)tip_words(e);
-   pa.B = B; pa.branch_bs = nn; pa.gene_rate_bs = G; pa.pcol = e->kk == KK_MFMA64 ? e->d_pcol.p : nullptr;
+// The buffers whose size follows from the choice: P(t) (pipelined: the set the previous evaluation did not use), class likelihoods,
+// the resident partials of a keep-partials engine, the overflow stack of deep trees.
+int ensure_buffers(paml_amd_engine *e, Eval &c)
+{
+   if (c.pipe) {
+      paml_amd_engine::PSet &sp = e->spare[e->spare_head];      // the set used longest ago
+      std::swap(e->d_rowmajor, sp.rowmajor); std::swap(e->d_pint, sp.pint); std::swap(e->d_ptip, sp.ptip); std::swap(e->d_pcol, sp.pcol);
+      std::swap(e->pset, sp.id);
+      e->spare_head = (e->spare_head + 1) % (paml_amd_engine::NPSET - 1);
+   }
+   if (int rc = ensure_pmat_buffers(e, c.psets, e->kk == KK_VALU20 && e->want_m20, e->kk == KK_MFMA64)) return rc;
+   HIPCHK(e->d_fhK.ensure((size_t)c.K * e->n_patt));
+   c.n_blocks = e->n_tiles * c.K;
+   if (c.keep) {
+      const int n_int = e->tree.n_nodes - e->n_tips;
+      size_t words = e->kk == KK_MFMA64 ? (size_t)c.K * n_int * e->part_groups() * 1024 + (size_t)std::max(e->mfma_waves, 8) * 1024      // (+ PruneArgs::part_dump: a row per wave)
+                                        : (size_t)c.K * n_int * e->n_patt * e->n;
+      HIPCHK(e->d_partials.ensure(words));
+      HIPCHK(e->d_scalef.ensure((size_t)c.K * std::max(1, e->tree.n_scale) * e->n_patt));
+   }
+   return stack_overflow(e, e->prog, c.n_blocks, e->mfma_waves, &c.overflow);
+}
+
+// Kernel A: batched P(t), and the events that order the pruning kernel behind it.
+int run_pmat(paml_amd_engine *e, Eval &c, const InlineVec &iv)
+{
+   const int B = c.B, Km = c.Km, G = c.G, nn = e->tree.n_nodes;
+   const BatchSpec *const bs = c.bs;
+   // (layout 2 — 20 states on the matrix cores: operand-order copies beside the row-major matrices)
+   PmatArgs pa = pmat_args(e, e->tree.root, e->d_label.p, e->kk == KK_MFMA64 ? 1 : (e->kernel == PK_MFMA4X20_JIT ? 2 : 0),
+                           e->kk == KK_MFMA64 ? e->d_pcol.p : nullptr);
+   if (c.pipe) { pa.branch = e->d2_branch.p; pa.gene_rate = e->d2_gene_rate.p; }
+   pa.B = B; pa.branch_bs = nn; pa.gene_rate_bs = G;
    if (bs && bs->eigen_of) { pa.eigen_of = e->d_b_eigen_of.p; pa.eigen_of_bs = (long)G * Km * e->n_labels; }
    if (bs && bs->qfactor) { pa.qfactor = e->d_b_qfactor.p; pa.qfactor_bs = (long)Km * e->n_labels; }
-   pa.rate_gs = e->rate_per_gene ? Km : 0;
    // (several nodes per workgroup in a run of evaluations: 20 states no faster, 61 states slower, 0.211 against 0.203 ms at the 8-GPU shard size)
    pa.npb = 1;
    if (bs && bs->rate) { pa.rate = e->d_b_rate.p; pa.rate_bs = e->rate_per_gene ? (long)G * Km : Km; }
@@ -461,9 +502,9 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
    e->rowmajor_valid = pa.rowmajor != nullptr;
    e->pmat_B = B;
    // ... and single evaluations get label -> eigen_of -> eigen set -> U / V / Root resolved on the host (PmatArgs::res)
-   if (pmat_mfma && !bs && use_inline && !e->rate_per_gene && !e->eigen.empty()) {
+   if (pmat_mfma && !bs && c.use_inline && !e->rate_per_gene && !e->eigen.empty()) {
       if (!e->pres_valid) {
-         std::vector<PmatRes> res((size_t)psets * nn);
+         std::vector<PmatRes> res((size_t)c.psets * nn);
          for (int g = 0; g < G; g++)
             for (int ir = 0; ir < Km; ir++)
                for (int v = 0; v < nn; v++) {
@@ -474,130 +515,126 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
                }
          HIPCHK(e->d_pres.ensure(res.size()));
          // (pageable source: staged by the runtime before the call returns; in stream order in front of the P(t) kernel)
-         HIPCHK(hipMemcpyAsync(e->d_pres.p, res.data(), res.size() * sizeof(PmatRes), hipMemcpyHostToDevice, ps));
+         HIPCHK(hipMemcpyAsync(e->d_pres.p, res.data(), res.size() * sizeof(PmatRes), hipMemcpyHostToDevice, c.ps));
          e->pres_valid = true;
       }
       pa.res = e->d_pres.p;
    }
-   mark_on(e, ps);
-   bool small_pmat = e->kk != KK_MFMA64 && n <= 5;
+   mark_on(e, c.ps);
+   bool small_pmat = e->kk != KK_MFMA64 && e->n <= 5;
    for (const EigenHost &h : e->eigen) small_pmat = small_pmat && h.kind != PAML_AMD_EIGEN_QMAT;      // (ids never set: kind < 0, fine)
-   launch_pmat(pa, iv, nn, psets, small_pmat, ps, pmat_mfma);
-   mark_on(e, ps);
-   if (pipe) {      // the pruning kernel (main stream) starts when this P(t) is there
+   launch_pmat(pa, iv, nn, c.psets, small_pmat, c.ps, pmat_mfma);
+   mark_on(e, c.ps);
+   if (c.pipe) {      // the pruning kernel (main stream) starts when this P(t) is there
       HIPCHK(hipEventRecord(e->ev_pmat, e->s2));
-      HIPCHK(hipStreamWaitEvent(ms, e->ev_pmat, 0));
+      HIPCHK(hipStreamWaitEvent(c.ms, e->ev_pmat, 0));
    }
-   if (want_pipe && !skip_entry) {      // "everything on the main stream in front of this pruning kernel": what the next pipelined evaluation waits for
-      HIPCHK(hipEventRecord(e->ev_entry[e->entry_sel], ms));
+   if (c.want_pipe && !c.skip_entry) {      // "everything on the main stream in front of this pruning kernel": what the next pipelined evaluation waits for
+      HIPCHK(hipEventRecord(e->ev_entry[e->entry_sel], c.ms));
       e->entry_sel ^= 1;
       e->have_prev_entry = true;
    }
-   e->n_pmat += (long)psets * (nn - 1);
+   e->n_pmat += (long)c.psets * (nn - 1);
+   return 0;
+}
 
-   // Kernel B: fused pruning
-   PruneArgs pr{};
-   pr.ops = e->d_ops.p; pr.z = e->d_z.p; pr.z_stride = e->n_patt; pr.tiles = e->d_tiles.p; pr.n_tiles = e->n_tiles;
-   pr.gene_off = e->d_gene_off.p; pr.weights = e->d_weights.p; pr.ztiles = e->d_ztiles.p; pr.zt_bytes = e->zt_bytes;
-   pr.n = n; pr.n_tips = e->n_tips; pr.n_nodes = nn; pr.K = K; pr.n_genes = G; pr.n_codes = e->n_codes;
-   pr.cleandata = e->cleandata; pr.n_pi = e->n_pi; pr.mode = e->mode; pr.n_scale = e->tree.n_scale;
-   pr.keep = keep ? 1 : 0; pr.n_patt = e->n_patt;
-   pr.pi = e->d_pi.p; pr.pint = e->kk == KK_MFMA64 ? e->d_pint.p : e->d_rowmajor.p; pr.ptip = e->d_ptip.p;
-   if (e->use_jit && e->tree.n_scale) HIPCHK(e->d_fscale.ensure((size_t)K * e->n_patt));
-   pr.fscale = e->d_fscale.p; pr.pcol = e->d_pcol.p;
-   if (e->kk == KK_VALU20 && e->use_jit && e->m20) { pr.pint = e->d_pint.p; pr.pcol = e->d_rowmajor.p; }      // (operand-order P(t); the row-major copies for the all-4x4x4 experiment)
-   pr.fhK = e->d_fhK.p; pr.partials = e->d_partials.p; pr.scalef = e->d_scalef.p; pr.stack_scratch = e->d_stack.p;
-   pr.stack_overflow_slots = overflow; pr.first_matmul = e->prog.first_matmul; pr.n_int = n_int;
-   pr.first_tip = e->prog.first_tip;
-   pr.tile_group0 = e->d_tile_group0.p; pr.part_groups = e->part_groups();
-   pr.part_dump = (keep && e->kk == KK_MFMA64) ? e->d_partials.p + (size_t)K * n_int * e->part_groups() * 1024 : nullptr;
-   pr.code_mask = e->d_code_mask.p;
-   pr.stream = e->d_stream.p; pr.n_stream = (int)(e->prog.stream.size() / 2); pr.tip_words = (long)tip_words(e);
-   // the reduction's geometry (the fused kernels form the partial sums themselves; the others leave them to reduce_stage1)
-   const int chunk = e->chunk, nbg = e->nb_global;
-   const int nb = (e->n_patt + chunk - 1) / chunk;
+// This evaluation's stream: the reduction that last read its slot (two evaluations ago) is done.  Once per evaluation, whoever
+// asks first: a kernel that writes the slot's class likelihoods or partial sums itself, else the reduction.
+int wait_slot(paml_amd_engine *e, Eval &c)
+{
+   if (c.slot_waited) return 0;
+   c.slot_waited = true;
+   if (e->done_pending[c.slot]) {
+      e->done_pending[c.slot] = false;
+      // (the caller's stream, once joined to that total by flush / enter, is already behind it; any other stream waits here)
+      if (c.ms != e->stream || e->join_pending[c.slot]) {
+         const int si = (int)(e->st_count % paml_amd_engine::NSTAT);
+         if (e->comm_stats) HIPCHK(hipEventRecord(e->st_w0[si], c.ms));
+         HIPCHK(hipStreamWaitEvent(c.ms, e->ev_done[c.slot], 0));
+         if (e->comm_stats) { HIPCHK(hipEventRecord(e->st_w1[si], c.ms)); e->st_waited[si] = true; }
+         if (c.ms == e->stream) e->join_pending[c.slot] = false;
+      }
+   }
+   return 0;
+}
+
+// Where the reduction runs and the slot (class likelihoods, partial sums) it uses; the buffers of the reduction.
+int prepare_slot(paml_amd_engine *e, Eval &c)
+{
+   const int B = c.B, nbg = e->nb_global;
    // PAML_AMD_OFFLOAD=1 (experiment): in a run of paml_amd_eval_device calls the whole reduction of evaluation i (mixture + log +
    // chunk sums, the exchange step, the fixed-order total) runs on the engine's side stream while the main stream goes straight on
    // to the pruning kernel of evaluation i + 1, two slots of class likelihoods alternating.  Measured on MI355X at the 8-GPU shard
    // size (profiles/r03_comm_overhead.txt): 0.2351 ms per evaluation against 0.2281 with the two small kernels left on the main
    // stream — the event record / wait pairs that order the streams cost what the kernel boundaries they remove did.  Not the default;
    // with a communicator only the all-reduce and the total go to the side stream.
-   const bool fusedk = (e->kk != KK_MFMA64 && e->use_jit && e->fused) || coopj;      // the kernel forms the partial sums itself
-   const bool offload = want_pipe && !fusedk && !keep && !clean && !bs && !want_lnf && !e->tree.n_scale && e->env.offload;
-   const bool side_total = e->comm || dual;      // the (all-reduce and the) fixed-order total on the side stream `sc`
-   if (!offload && !side_total)
+   c.offload = c.want_pipe && !pk_forms_reduction(e->kernel) && !c.keep && !c.clean && !c.bs && !c.want_lnf && !e->tree.n_scale && e->env.offload;
+   c.side_total = e->comm || c.dual;
+   if (!c.offload && !c.side_total)
       if (int rc = join_comm(e)) return rc;
-   const int slot = (side_total || offload) ? e->red_slot : 0;
+   c.slot = (c.side_total || c.offload) ? e->red_slot : 0;
    if (e->comm_stats && !e->st_part[0])
       for (int i = 0; i < paml_amd_engine::NSTAT; i++) {
          HIPCHK(hipEventCreate(&e->st_part[i])); HIPCHK(hipEventCreate(&e->st_done[i]));
          HIPCHK(hipEventCreate(&e->st_w0[i])); HIPCHK(hipEventCreate(&e->st_w1[i]));
       }
    if (e->comm_stats) e->st_waited[e->st_count % paml_amd_engine::NSTAT] = false;
-   DevBuf<double> &dpart = e->part_slot(slot);
+   DevBuf<double> &dpart = e->part_slot(c.slot);
    if ((size_t)nbg * B > dpart.cap) {
       if (e->sc) HIPCHK(hipStreamSynchronize(e->sc));      // (reallocation: nothing may still be reading the old buffer)
       HIPCHK(dpart.ensure((size_t)nbg * B));
-      HIPCHK(hipMemsetAsync(dpart.p, 0, dpart.cap * sizeof(double), ms));
+      HIPCHK(hipMemsetAsync(dpart.p, 0, dpart.cap * sizeof(double), c.ms));
    }
-   DevBuf<double> &dfhk = e->fhk_slot((offload || dual) ? slot : 0);
-   if ((offload || dual) && slot) HIPCHK(dfhk.ensure((size_t)K * e->n_patt));
-   pr.fhK = dfhk.p;
-   e->last_fhk = (offload || dual) ? slot : 0;
-   bool slot_waited = false;
-   auto wait_slot = [&]() -> int {      // main stream: the reduction that last read this slot (two evaluations ago) is done
-      if (slot_waited) return 0;
-      slot_waited = true;
-      if (e->done_pending[slot]) {
-         e->done_pending[slot] = false;
-         // (the caller's stream, once joined to that total by flush / enter, is already behind it; any other stream waits here)
-         if (ms != e->stream || e->join_pending[slot]) {
-            const int si = (int)(e->st_count % paml_amd_engine::NSTAT);
-            if (e->comm_stats) HIPCHK(hipEventRecord(e->st_w0[si], ms));
-            HIPCHK(hipStreamWaitEvent(ms, e->ev_done[slot], 0));
-            if (e->comm_stats) { HIPCHK(hipEventRecord(e->st_w1[si], ms)); e->st_waited[si] = true; }
-            if (ms == e->stream) e->join_pending[slot] = false;
-         }
-      }
-      return 0;
-   };
-   if (offload) {
+   e->last_fhk = (c.offload || c.dual) ? c.slot : 0;      // the slot's class likelihoods
+   if (e->last_fhk) HIPCHK(e->fhk_slot(e->last_fhk).ensure((size_t)c.K * e->n_patt));
+   c.slot_waited = false;
+   if (c.offload) {
       if (int rc = ensure_side_stream(e)) return rc;
-      if (int rc = wait_slot()) return rc;      // (the pruning kernel writes this slot's class likelihoods)
+      if (int rc = wait_slot(e, c)) return rc;      // (the pruning kernel writes this slot's class likelihoods)
    }
    if ((size_t)B * RED_TICKET_WORDS > e->d_red_counter.cap) {
       HIPCHK(e->d_red_counter.ensure((size_t)std::max(B, 64) * RED_TICKET_WORDS));
-      HIPCHK(hipMemsetAsync(e->d_red_counter.p, 0, e->d_red_counter.cap * sizeof(int), ms));
+      HIPCHK(hipMemsetAsync(e->d_red_counter.p, 0, e->d_red_counter.cap * sizeof(int), c.ms));
    }
    HIPCHK(e->d_out.ensure(B));
-   if (want_lnf) HIPCHK(e->d_lnf.ensure((size_t)B * e->n_patt));
-   double *const lnl_out = d_lnL_out ? d_lnL_out : e->d_out.p;
-   const bool fused = fusedk;
-   pr.zpm = e->d_zpm.p; pr.zpm_words = e->zpm_words;
-   if (fused) {
-      pr.zpm = e->d_zpm.p; pr.zpm_words = e->zpm_words; pr.Km = Km; pr.chunk = chunk; pr.first_chunk = e->first_chunk; pr.nb_stride = nbg;
-      pr.want_fhk = (want_fhk || e->tree.n_scale) ? 1 : 0;
-      pr.freqK = (bs && bs->freqK) ? e->d_b_freqK.p : e->d_freqK.p; pr.freqK_bs = (bs && bs->freqK) ? Km : 0;
-      pr.lnf = want_lnf ? e->d_lnf.p : nullptr;
-      pr.red_partial = dpart.p; pr.red_out = lnl_out; pr.nb_local = nb;
-      if (int rc = wait_slot()) return rc;      // (this kernel writes the partial sums itself)
-      // the total: a one-block stage-2 launch
-      pr.red_counter = nullptr;
-      if (coopj) pr.red_counter = e->d_red_counter.p;      // (the cooperative per-tree kernel: always the last workgroup, of each batch element)
+   if (c.want_lnf) HIPCHK(e->d_lnf.ensure((size_t)B * e->n_patt));
+   return 0;
+}
+
+// Kernel B: fused pruning — the kernel choose_kernel named.
+int run_prune(paml_amd_engine *e, Eval &c)
+{
+   const PruneKernel k = e->kernel;
+   const int B = c.B, K = c.K, G = c.G, n_blocks = c.n_blocks;
+   const BatchSpec *const bs = c.bs;
+   if (pk_module(k) && e->tree.n_scale) HIPCHK(e->d_fscale.ensure((size_t)K * e->n_patt));
+   PruneArgs pr = prune_args(e, e->prog, K, e->d_ops.p, false, e->tree.n_scale, c.keep, e->d_partials.p, e->d_scalef.p, c.overflow);
+   if (k == PK_MFMA4X20_JIT) { pr.pint = e->d_pint.p; pr.pcol = e->d_rowmajor.p; }      // (operand-order P(t); the row-major copies for the all-4x4x4 experiment)
+   pr.fhK = e->fhk_slot(e->last_fhk).p;
+   const int nb = (e->n_patt + e->chunk - 1) / e->chunk;      // the reduction's geometry: chunks of this engine
+   if (pk_forms_reduction(k)) {      // (the others leave the partial sums to reduce_stage1)
+      pr.Km = c.Km; pr.chunk = e->chunk; pr.first_chunk = e->first_chunk; pr.nb_stride = e->nb_global;
+      pr.want_fhk = (c.want_fhk || e->tree.n_scale) ? 1 : 0;
+      pr.freqK = (bs && bs->freqK) ? e->d_b_freqK.p : e->d_freqK.p; pr.freqK_bs = (bs && bs->freqK) ? c.Km : 0;
+      pr.lnf = c.want_lnf ? e->d_lnf.p : nullptr;
+      pr.red_partial = e->part_slot(c.slot).p; pr.red_out = c.d_lnL_out ? c.d_lnL_out : e->d_out.p; pr.nb_local = nb;
+      if (int rc = wait_slot(e, c)) return rc;      // (this kernel writes the partial sums itself)
+      // the total: a one-block stage-2 launch — but the cooperative per-tree kernel: always the last workgroup, of each batch element
+      pr.red_counter = k == PK_MFMA64_COOPJIT ? e->d_red_counter.p : nullptr;
    }
-   const int prof_stride = std::max((int)e->prog.ops.size() + 3, e->env.prof_tiles ? 96 : 0);      // experiments only
-   if (!e->env.prof_ops.empty()) {
+   if (!e->env.prof_ops.empty()) {      // experiments only
       // per-op stamps: a fresh buffer and a dump after every launch; the workgroup timeline: one buffer, overwritten by every
       // launch and written out when the engine goes (nothing between the launches, so that the clock is the production clock)
+      const int prof_stride = std::max((int)e->prog.ops.size() + 3, e->env.prof_tiles ? 96 : 0);
       const size_t words = (size_t)3 * n_blocks * prof_stride;
       if (!e->env.prof_tiles || words != e->prof_words) {
          if (e->d_prof) (void)hipFree(e->d_prof);
          e->d_prof = nullptr;
          HIPCHK(hipMalloc((void **)&e->d_prof, paml_amd_engine::MAXL * words * 8));      // (pruning streams: one timeline per lane)
-         HIPCHK(hipMemsetAsync(e->d_prof, 0, paml_amd_engine::MAXL * words * 8, ms));
+         HIPCHK(hipMemsetAsync(e->d_prof, 0, paml_amd_engine::MAXL * words * 8, c.ms));
          e->prof_words = words; e->prof_blocks = n_blocks; e->prof_stride = prof_stride;
       }
-      pr.prof = e->d_prof + (size_t)lane * words;
+      pr.prof = e->d_prof + (size_t)c.lane * words;
       pr.prof_stride = prof_stride;
       pr.prof_tid = e->env.prof_tid;
    }
@@ -607,114 +644,116 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
    // first workgroups of the next, so a reservation reserves nothing there and only costs tiles per CU (measured, 16 taxa x 10^6
    // codon patterns: 1.524-1.526 ms per evaluation on 256 CUs against 1.534-1.542 on 254; the same at the 8-GPU shard size, with
    // and without a communicator); the small kernels run when workgroups retire.
-   const bool two_streams = want_pipe && e->env.dual && !e->profiling;
+   const bool two_streams = c.want_pipe && e->env.dual && !e->profiling;
    const int cus = (e->comm && !two_streams) ? std::max(1, e->n_cu - e->comm_cus) : e->n_cu;
-   switch (e->kk) {
-   case KK_MFMA64:
-      if (e->use_jit) {
-         void *params[] = {&pr};
-         const int grid = std::min(n_blocks, cus);     // persistent: one 130 KB-LDS workgroup per CU walks the tiles
-         HIPCHK(hipModuleLaunchKernel(e->jit.fn, grid, 1, 1, e->mfma_waves * 64, 1, 1, 0, ms, params, nullptr));
-      }
-      else if (use_dma) {
-         const size_t lds = (size_t)4 * 4096 * sizeof(double) + (size_t)e->n_tips * 128;
-         if (!e->stream_attr_set) {
-            HIPCHK(hipFuncSetAttribute((const void *)prune_mfma64_stream, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            e->stream_attr_set = true;
-         }
-         hipLaunchKernelGGL(prune_mfma64_stream, dim3(n_blocks), dim3(512), lds, ms, pr);
-      }
-      else {
-         // small data sets — every 16-pattern group can have a CU (ONE round: the kernel's 90 KB of LDS leave room for one workgroup
-         // per CU, and two rounds of its 25 us walks lose to one round of the gather kernel's 39): four waves per group (prune_mfma64_coop)
-         if (coopj) {
-            void *params[] = {&pr};
-            HIPCHK(hipModuleLaunchKernel(e->jit_coop.fn, e->n_tiles * 4 * K, 1, 1, 256, 1, 1, 0, ms, params, nullptr));
-         }
-         else if (coop) hipLaunchKernelGGL(prune_mfma64_coop, dim3(e->n_tiles * 4 * K), dim3(256), 0, ms, pr);
-         else hipLaunchKernelGGL(prune_mfma64_gather<GATHER_WAVES>, dim3(n_blocks), dim3(GATHER_WAVES * 64), 0, ms, pr);
-      }
+   void *params[] = {&pr};
+   hipStream_t const ms = c.ms;
+   switch (k) {
+   case PK_MFMA64_JIT:      // persistent: one 130 KB-LDS workgroup per CU walks the tiles
+      HIPCHK(hipModuleLaunchKernel(e->jit.fn, std::min(n_blocks, cus), 1, 1, e->mfma_waves * 64, 1, 1, 0, ms, params, nullptr));
       break;
-   case KK_VALU4:
-   case KK_VALU5:
-   case KK_VALU20:
-      if (fused) {
-         void *params[] = {&pr};
-         // single evaluations: one workgroup per chunk; batched ones: about two resident workgroups per CU in all, each walking every
-         // gx-th chunk of its element (the LDS tables of an element's P(t) are filled once per workgroup, not once per 256 patterns)
-         int gx = nb;
-         if (B > 1) gx = std::max(1, std::min(nb, 2 * e->n_cu / B));
-         HIPCHK(hipModuleLaunchKernel(e->jit.fn, gx, B, 1, e->fused_threads, 1, 1, 0, ms, params, nullptr));
+   case PK_MFMA64_STREAM:
+      if (!e->stream_attr_set) {
+         HIPCHK(hipFuncSetAttribute((const void *)prune_mfma64_stream, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+         e->stream_attr_set = true;
       }
-      else if (e->use_jit && e->m20) {      // persistent: a multiple of the class count, every workgroup keeps its class's P(t) in LDS
-         void *params[] = {&pr};
-         int grid = std::min(std::max(K, cus / K * K), e->n_tiles * K);
-         // Runs of evaluations on two pruning streams: the small kernels beside this one (partial sums, the next P(t)) are
-         // dispatched to shader engines in turn, and a workgroup sent to an engine whose CUs all hold a persistent workgroup
-         // waits for the end of this kernel even if the engine next door has room (measured: both then end WITH this kernel and
-         // the next pruning kernel, which needs them, cannot be queued ahead).  7/8 of the CUs leave every shader engine one
-         // free; taken when it costs this kernel nothing, i.e. when a wave still walks the same number of 32-pattern units
-         // (10^5 patterns x 4 classes: 7 at 56 workgroups per class as at 63).  0.1885 -> 0.182 ms per evaluation (32 taxa).
-         if (two_streams && G == 1) {
-            const int units = std::min(e->n_tiles * 8, (e->n_patt + 31) / 32), g78 = e->n_cu * 7 / 8 / K * K;
-            auto rounds = [&](int g) { return ((units + g / K - 1) / (g / K) + 7) / 8; };
-            if (g78 >= K && g78 < grid && rounds(g78) == rounds(grid)) grid = g78;
-         }
-         // (several genes: a workgroup serves one (gene, class); the kernel deals a class's workgroups to the genes, at least one each)
-         HIPCHK(hipModuleLaunchKernel(e->jit.fn, std::max(grid / K, G > 1 ? G : 1) * K, 1, 1, 512, 1, 1, 0, ms, params, nullptr));
+      hipLaunchKernelGGL(prune_mfma64_stream, dim3(n_blocks), dim3(512), (size_t)4 * 4096 * sizeof(double) + (size_t)e->n_tips * 128, ms, pr);
+      break;
+   // small data sets — every 16-pattern group can have a CU (ONE round: the kernel's 90 KB of LDS leave room for one workgroup
+   // per CU, and two rounds of its 25 us walks lose to one round of the gather kernel's 39): four waves per group (prune_mfma64_coop)
+   case PK_MFMA64_COOPJIT:
+      HIPCHK(hipModuleLaunchKernel(e->jit_coop.fn, e->n_tiles * 4 * K, 1, 1, 256, 1, 1, 0, ms, params, nullptr));
+      break;
+   case PK_MFMA64_COOP:
+      hipLaunchKernelGGL(prune_mfma64_coop, dim3(e->n_tiles * 4 * K), dim3(256), 0, ms, pr);
+      break;
+   case PK_VALU4_FUSED_JIT: case PK_VALU5_FUSED_JIT: {
+      // single evaluations: one workgroup per chunk; batched ones: about two resident workgroups per CU in all, each walking every
+      // gx-th chunk of its element (the LDS tables of an element's P(t) are filled once per workgroup, not once per 256 patterns)
+      const int gx = B > 1 ? std::max(1, std::min(nb, 2 * e->n_cu / B)) : nb;
+      HIPCHK(hipModuleLaunchKernel(e->jit.fn, gx, B, 1, e->fused_threads, 1, 1, 0, ms, params, nullptr));
+      break;
+   }
+   case PK_MFMA4X20_JIT: {      // persistent: a multiple of the class count, every workgroup keeps its class's P(t) in LDS
+      int grid = std::min(std::max(K, cus / K * K), e->n_tiles * K);
+      // Runs of evaluations on two pruning streams: the small kernels beside this one (partial sums, the next P(t)) are
+      // dispatched to shader engines in turn, and a workgroup sent to an engine whose CUs all hold a persistent workgroup
+      // waits for the end of this kernel even if the engine next door has room (measured: both then end WITH this kernel and
+      // the next pruning kernel, which needs them, cannot be queued ahead).  7/8 of the CUs leave every shader engine one
+      // free; taken when it costs this kernel nothing, i.e. when a wave still walks the same number of 32-pattern units
+      // (10^5 patterns x 4 classes: 7 at 56 workgroups per class as at 63).  0.1885 -> 0.182 ms per evaluation (32 taxa).
+      if (two_streams && G == 1) {
+         const int units = std::min(e->n_tiles * 8, (e->n_patt + 31) / 32), g78 = e->n_cu * 7 / 8 / K * K;
+         auto rounds = [&](int g) { return ((units + g / K - 1) / (g / K) + 7) / 8; };
+         if (g78 >= K && g78 < grid && rounds(g78) == rounds(grid)) grid = g78;
       }
-      else if (e->use_jit) {
-         void *params[] = {&pr};
-         HIPCHK(hipModuleLaunchKernel(e->jit.fn, n_blocks, 1, 1, 256, 1, 1, 0, ms, params, nullptr));
-      }
-      else
-         launch_valu(e, e->prog.max_stack, n_blocks, pr, ms);
+      // (several genes: a workgroup serves one (gene, class); the kernel deals a class's workgroups to the genes, at least one each)
+      HIPCHK(hipModuleLaunchKernel(e->jit.fn, std::max(grid / K, G > 1 ? G : 1) * K, 1, 1, 512, 1, 1, 0, ms, params, nullptr));
+      break;
+   }
+   case PK_VALU4_JIT: case PK_VALU5_JIT: case PK_VALU20_JIT:
+      HIPCHK(hipModuleLaunchKernel(e->jit.fn, n_blocks, 1, 1, 256, 1, 1, 0, ms, params, nullptr));
+      break;
+   case PK_MFMA64_GATHER: case PK_VALU4: case PK_VALU5: case PK_VALU20:      // the full interpreters
+      launch_prune_full(e, e->prog.max_stack, n_blocks, pr, ms);
       break;
    }
    mark(e);
-   if (want_pipe && e->env.dual) {      // this P set's last reader so far
+   if (c.want_pipe && e->env.dual) {      // this P set's last reader so far
       HIPCHK(hipEventRecord(e->ev_setread[e->pset], ms));
       e->setread_rec[e->pset] = true;
    }
-   if (pr.prof && !e->env.prof_tiles) {
-      std::vector<unsigned long long> hp((size_t)3 * n_blocks * prof_stride);
-      HIPCHK(hipMemcpyAsync(hp.data(), e->d_prof, hp.size() * 8, hipMemcpyDeviceToHost, ms));
-      HIPCHK(hipStreamSynchronize(ms));
-      FILE *f = fopen(e->env.prof_ops.c_str(), "wb");
-      if (f) {
-         int hdr[2] = {n_blocks, prof_stride};
-         fwrite(hdr, sizeof(int), 2, f);
-         std::vector<int> codes;
-         for (auto &o : e->prog.ops) codes.push_back(o.code);
-         codes.resize(prof_stride - 3, 0);
-         fwrite(codes.data(), sizeof(int), codes.size(), f);
-         fwrite(hp.data(), 8, hp.size(), f);
-         fclose(f);
-      }
-   }
+   return 0;
+}
 
-   // Kernel C: mixture + log + weighted sum.  Stage 1 leaves one partial sum per chunk of patterns at the chunk's global
-   // position; with a communicator the ranks' (disjoint, zero elsewhere) arrays are summed over RCCL — adding zeros is exact,
-   // so every rank then holds the same array whatever the number of ranks — and stage 2 adds it up in a fixed order.
+// PAML_AMD_PROF_OPS without PAML_AMD_PROF_TILES: the per-op stamps of the launch just queued, written out (a host synchronisation).
+int dump_op_stamps(paml_amd_engine *e, const Eval &c)
+{
+   if (e->env.prof_ops.empty() || e->env.prof_tiles) return 0;
+   std::vector<unsigned long long> hp((size_t)3 * e->prof_blocks * e->prof_stride);
+   HIPCHK(hipMemcpyAsync(hp.data(), e->d_prof, hp.size() * 8, hipMemcpyDeviceToHost, c.ms));
+   HIPCHK(hipStreamSynchronize(c.ms));
+   if (FILE *f = fopen(e->env.prof_ops.c_str(), "wb")) {
+      int hdr[2] = {e->prof_blocks, e->prof_stride};
+      fwrite(hdr, sizeof(int), 2, f);
+      std::vector<int> codes;
+      for (auto &o : e->prog.ops) codes.push_back(o.code);
+      codes.resize(e->prof_stride - 3, 0);
+      fwrite(codes.data(), sizeof(int), codes.size(), f);
+      fwrite(hp.data(), 8, hp.size(), f);
+      fclose(f);
+   }
+   return 0;
+}
+
+// Kernel C: mixture + log + weighted sum.  Stage 1 leaves one partial sum per chunk of patterns at the chunk's global
+// position; with a communicator the ranks' (disjoint, zero elsewhere) arrays are summed over RCCL — adding zeros is exact,
+// so every rank then holds the same array whatever the number of ranks — and stage 2 adds it up in a fixed order.
+int reduce(paml_amd_engine *e, Eval &c)
+{
+   const PruneKernel k = e->kernel;
+   const int B = c.B, Km = c.Km, slot = c.slot, nbg = e->nb_global, nb = (e->n_patt + e->chunk - 1) / e->chunk;
+   const BatchSpec *const bs = c.bs;
+   DevBuf<double> &dpart = e->part_slot(slot);
    ReduceArgs ra{};
-   ra.fhK = dfhk.p; ra.weights = e->d_weights.p; ra.freqK = e->d_freqK.p; ra.lnf = want_lnf ? e->d_lnf.p : nullptr;
-   ra.partial = dpart.p; ra.out = lnl_out;
-   ra.raw = ((e->kk == KK_MFMA64 && e->use_jit) || (e->kk == KK_VALU20 && e->use_jit && e->m20)) ? 1 : 0; ra.fscale = e->d_fscale.p;
-   ra.n_patt = e->n_patt; ra.K = Km; ra.mode = e->mode; ra.n_scale = e->tree.n_scale; ra.chunk = chunk;
+   ra.fhK = e->fhk_slot(e->last_fhk).p; ra.weights = e->d_weights.p; ra.freqK = e->d_freqK.p; ra.lnf = c.want_lnf ? e->d_lnf.p : nullptr;
+   ra.partial = dpart.p; ra.out = c.d_lnL_out ? c.d_lnL_out : e->d_out.p;
+   ra.raw = pk_leaves_log(k) ? 1 : 0; ra.fscale = e->d_fscale.p;
+   ra.n_patt = e->n_patt; ra.K = Km; ra.mode = e->mode; ra.n_scale = e->tree.n_scale; ra.chunk = e->chunk;
    ra.first_chunk = e->first_chunk; ra.nb_stride = nbg;
    // (measured on MI355X, 32 taxa x 10^5 nucleotide patterns: 28.2 us per evaluation with the separate one-block launch against
    //  30.2 with tickets — the agent-scope store + two atomics + coherent reads cross the XCDs' L2s and cost more than a launch)
    if (bs && bs->freqK) { ra.freqK = e->d_b_freqK.p; ra.freqK_bs = Km; }
-   hipStream_t rs = ms;      // the stream of the reduction
-   if (offload) {
-      HIPCHK(hipEventRecord(e->ev_part[slot], ms));
+   hipStream_t rs = c.ms;      // the stream of the reduction
+   if (c.offload) {
+      HIPCHK(hipEventRecord(e->ev_part[slot], c.ms));
       HIPCHK(hipStreamWaitEvent(e->sc, e->ev_part[slot], 0));
       rs = e->sc;
    }
    mark_on(e, rs);
-   if (int rc = wait_slot()) return rc;
-   if (!fused) hipLaunchKernelGGL(reduce_stage1, dim3(nb, B), dim3(256), 0, rs, ra);
-   if (side_total) {
+   if (int rc = wait_slot(e, c)) return rc;
+   if (!pk_forms_reduction(k)) hipLaunchKernelGGL(reduce_stage1, dim3(nb, B), dim3(256), 0, rs, ra);
+   if (c.side_total) {
       // the exchange step, off the pruning stream: the side stream takes over when this evaluation's partial sums are there
       // (ev_part), all-reduces them into the slot's second buffer and forms the fixed-order total; the next evaluation's P(t) and
       // pruning kernel follow on the main stream without waiting for any of it
@@ -723,8 +762,8 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
          HIPCHK(hipStreamSynchronize(e->sc));
          HIPCHK(dtot.ensure((size_t)nbg * B));
       }
-      if (!offload) {
-         HIPCHK(hipEventRecord(e->ev_part[slot], ms));
+      if (!c.offload) {
+         HIPCHK(hipEventRecord(e->ev_part[slot], c.ms));
          HIPCHK(hipStreamWaitEvent(e->sc, e->ev_part[slot], 0));
       }
       if (e->comm_stats) HIPCHK(hipEventRecord(e->st_part[e->st_count % paml_amd_engine::NSTAT], e->sc));      // (on `sc`, behind the wait: "partial sums ready")
@@ -734,9 +773,9 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
       }
       hipLaunchKernelGGL(reduce_stage2, dim3(B), dim3(256), 0, e->sc, (const double *)dtot.p, nbg, ra.out);
    }
-   else if (nbg > 1 && !coopj) hipLaunchKernelGGL(reduce_stage2, dim3(B), dim3(256), 0, rs, (const double *)dpart.p, nbg, ra.out);      // (one block per element: stage 1 wrote the total)
-   if (side_total || offload) {
-      if (e->comm_stats && side_total) { HIPCHK(hipEventRecord(e->st_done[e->st_count % paml_amd_engine::NSTAT], e->sc)); e->st_count++; }
+   else if (nbg > 1 && k != PK_MFMA64_COOPJIT) hipLaunchKernelGGL(reduce_stage2, dim3(B), dim3(256), 0, rs, (const double *)dpart.p, nbg, ra.out);      // (one block per element: stage 1 wrote the total)
+   if (c.side_total || c.offload) {
+      if (e->comm_stats && c.side_total) { HIPCHK(hipEventRecord(e->st_done[e->st_count % paml_amd_engine::NSTAT], e->sc)); e->st_count++; }
       HIPCHK(hipEventRecord(e->ev_done[slot], e->sc));
       e->done_pending[slot] = true;
       e->join_pending[slot] = true;
@@ -747,14 +786,33 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
    HIPCHK(hipGetLastError());
    if (e->profiling) e->prof_evals++;
    e->n_eval++;
-   if (keep && !clean) e->partials_valid = true;
+   if (c.keep && !c.clean) e->partials_valid = true;
    e->pmat_valid = true;
-   e->pipe_ok = want_pipe;      // (every other entry point clears it)
+   e->pipe_ok = c.want_pipe;      // (every other entry point clears it)
    // two pruning streams from the next call on: persistent kernels only (they are what holds every CU to its end), nothing shared
    // between consecutive evaluations but the two slots (class likelihoods, partial sums, P sets)
-   e->dual_ok = want_pipe && e->env.dual && !e->env.offload && e->use_jit && (e->kk == KK_MFMA64 || (e->kk == KK_VALU20 && e->m20)) && !overflow &&
-                !e->tree.n_scale && !keep && !clean && !bs && !want_lnf && nbg > 1 && (e->env.prof_ops.empty() || e->env.prof_tiles);
+   e->dual_ok = c.want_pipe && e->env.dual && !e->env.offload && pk_persistent(k) && !c.overflow &&
+                !e->tree.n_scale && !c.keep && !c.clean && !bs && !c.want_lnf && nbg > 1 && (e->env.prof_ops.empty() || e->env.prof_tiles);
    return 0;
+}
+
+}  // namespace
+
+int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rate, const unsigned char *clean,
+                double *d_lnL_out, bool want_lnf, const BatchSpec *bs, bool want_pipe, bool want_fhk)
+{
+   Eval c{branch, gene_rate, clean, d_lnL_out, bs, want_lnf, want_pipe, want_fhk};
+   InlineVec iv;      // (branch lengths and gene rates inside the arguments of P(t))
+   if (int rc = begin_eval(e, c)) return rc;              // the call is valid; the tree's program
+   if (int rc = setup_streams(e, c)) return rc;           // pipelined and two-stream runs
+   if (int rc = stage_inputs(e, c, iv)) return rc;        // small inputs, uploaded
+   if (int rc = choose_kernel(e, c, &e->kernel)) return rc;
+   if (int rc = ensure_buffers(e, c)) return rc;
+   if (int rc = run_pmat(e, c, iv)) return rc;            // Kernel A
+   if (int rc = prepare_slot(e, c)) return rc;
+   if (int rc = run_prune(e, c)) return rc;               // Kernel B
+   if (int rc = dump_op_stamps(e, c)) return rc;
+   return reduce(e, c);                                   // Kernel C, the exchange step, the total
 }
 
 }  // namespace paml_amd

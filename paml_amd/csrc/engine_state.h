@@ -1,7 +1,10 @@
 // engine_state.h — the engine object behind the C ABI (include/paml_amd.h) and the helpers its translation units share:
 //   engine_core.hip     create / destroy, the set_* entry points, read-back of P(t) / partials / scale factors, profiling
 //   engine_comm.hip     pattern shards over several GPUs: shard bounds, the RCCL communicator, the collective stream
-//   engine_eval.hip     one evaluation (batched P(t), fused pruning, reduction) and the entry points built on it
+//   engine_eval.hip     one evaluation and the entry points built on it.  launch_eval is a list of phases over one struct of shared locals:
+//                       begin_eval, setup_streams, stage_inputs, choose_kernel (-> PruneKernel, below), ensure_buffers, run_pmat,
+//                       prepare_slot, run_prune (a switch on PruneKernel), dump_op_stamps, reduce.  pmat_args / prune_args fill the
+//                       kernels' argument structures for every site, here and in engine_branch.hip
 //   engine_branch.hip   branch-local lnL(t), dlnL, ddlnL on resident partials; node posteriors
 //   engine_beb.hip      the BEB grid integral
 //   engine_jitdbg.hip   per-tree kernel generation without an engine (tests, build-time prebuild)
@@ -37,6 +40,16 @@ namespace paml_amd {
 static_assert(JIT_SCRATCH_BASE == MFMA_RS, "the per-tree kernel addresses the interpreter's overflow-stack scratch");
 
 enum KernelKind { KK_VALU4, KK_VALU5, KK_VALU20, KK_MFMA64 };
+// The pruning kernel in use: one enumerator per name paml_amd_kernel_name reports.  The 4 / 5 / 20-state engines have three each
+// (interpreter, per-tree kernel, its second form) in KernelKind's order: 3 * kk + form (choose_kernel, paml_amd_create).
+enum PruneKernel {
+   PK_VALU4, PK_VALU4_JIT, PK_VALU4_FUSED_JIT, PK_VALU5, PK_VALU5_JIT, PK_VALU5_FUSED_JIT, PK_VALU20, PK_VALU20_JIT, PK_MFMA4X20_JIT,
+   PK_MFMA64_JIT, PK_MFMA64_STREAM, PK_MFMA64_COOP, PK_MFMA64_COOPJIT, PK_MFMA64_GATHER
+};
+inline bool pk_module(PruneKernel k) { return k == PK_MFMA64_JIT || (k < PK_MFMA64_JIT && k % 3 != 0); }      // a hiprtc module, paml_amd_engine::jit
+inline bool pk_forms_reduction(PruneKernel k) { return k == PK_VALU4_FUSED_JIT || k == PK_VALU5_FUSED_JIT || k == PK_MFMA64_COOPJIT; }      // partial sums (and the total) in its epilogue
+inline bool pk_leaves_log(PruneKernel k) { return k == PK_MFMA64_JIT || k == PK_MFMA4X20_JIT; }      // writes floored root sums: reduce_stage1 takes the logarithm (ReduceArgs::raw)
+inline bool pk_persistent(PruneKernel k) { return k == PK_MFMA64_JIT || k == PK_MFMA4X20_JIT; }      // one workgroup per CU walks the tiles and holds the CU to its end
 constexpr int DMA_WAVES = 8;           // mfma64 "stream" kernel: 128 patterns per workgroup, 1 workgroup per CU
 constexpr int GATHER_WAVES = 4;        // mfma64 "gather" kernel: 64 patterns per workgroup, 2 per CU
 constexpr int VALU_MAXD_SMALL = 16, VALU_MAXD_20 = 8;
@@ -92,6 +105,12 @@ struct Staging {
       memcpy(dst, src, n * sizeof(T));
       used += n * sizeof(T);
       return dst;
+   }
+   template <typename T>
+   hipError_t send(DevBuf<T> &b, const T *src, size_t n, hipStream_t s)      // put + the copy into a buffer of at least n elements
+   {
+      const hipError_t r = b.ensure(n);
+      return r != hipSuccess ? r : hipMemcpyAsync(b.p, put(src, n), n * sizeof(T), hipMemcpyHostToDevice, s);
    }
    hipError_t end(hipStream_t s) { pending = true; return hipEventRecord(ev, s); }
    void release()
@@ -226,6 +245,7 @@ struct paml_amd_engine {
    int n = 0, n_tips = 0, n_patt = 0, max_classes = 0, n_genes = 1;
    unsigned flags = 0;
    KernelKind kk = KK_MFMA64;
+   PruneKernel kernel = PK_MFMA64_STREAM;      // the pruning kernel of the last evaluation (launch_eval: choose_kernel; eval_branch's refill)
    bool mfma_dma = true;     // which mfma64 variant (dma needs n_tips <= MFMA_ZT)
    int mfma_waves = DMA_WAVES;
    int tile_patt = 64;
@@ -284,10 +304,9 @@ struct paml_amd_engine {
    bool bpart_colmajor = false;                  // ... stored [column][row] (the eigen-basis kernels), handed out [row][column] either way
    double *h_out = nullptr;           // pinned, device-visible: the synchronous entry points have lnL written straight to the host
    size_t h_out_cap = 0;
-   bool fused = false;                // the selected kernel forms the reduction itself
    bool rate_per_gene = false;      // paml_amd_set_gene_class_rates: class rates [n_genes][K]
    std::vector<double> class_rate;  // the [K] rates of set_classes (what set_gene_class_rates(NULL) goes back to)
-   bool want_m20 = false, m20 = false;      // 20 states on v_mfma_f64_4x4x4 (jit_generate_m20)
+   bool want_m20 = false;             // 20 states on v_mfma_f64_4x4x4 (jit_generate_m20) where the tree allows it
    int fused_threads = 256;
    bool pmat_valid = false;           // d_rowmajor holds the P(t) of an evaluation in the tree's own orientation
    // branch-local evaluation: resident partials on both sides of every edge, re-used from call to call (eval_branch)
@@ -390,15 +409,14 @@ struct paml_amd_engine {
       jit_seen.emplace_back(key, 1);
       return 1;
    }
-   bool jit_enabled = false, use_jit = false;
+   bool jit_enabled = false;
    bool small20 = false;     // 20 states on the MFMA interpreters because the data set is small (engine_core.hip): not as a shard of a larger one
-   bool coop = false;        // the last evaluation ran prune_mfma64_coop (small data sets: four waves per 16-pattern group)
-   // ... or its per-tree form with the reduction inside (jit.h: jit_generate_coop).  A module of its own: an engine goes back and forth
-   // between it (an evaluation, a small batch) and the interpreters (a batched gradient too large for one 16-pattern group per CU).
+   // The per-tree form of prune_mfma64_coop (small data sets: four waves per 16-pattern group) with the reduction inside (jit.h:
+   // jit_generate_coop).  A module of its own: an engine goes back and forth between it (an evaluation, a small batch) and the interpreters (a batched gradient too large for one 16-pattern group per CU).
    // The kernel is compiled on a worker thread unless its code object is already on disk (lib/jit or the user's cache) or the caller
    // asked to wait (PAML_AMD_JIT flag / PAML_AMD_JIT_SYNC); the interpreter form serves until it is there.  PAML_AMD_JIT=0: never.
    JitKernel jit_coop;
-   bool coopj = false, coopj_enabled = true;
+   bool coopj_enabled = true;
    // Consecutive paml_amd_eval_device calls (the loop of a benchmark or of an optimiser's independent evaluations) build the
    // NEXT evaluation's P(t) on a side stream while the previous pruning kernel is still running: its few workgroups fit the CUs
    // that go idle in that kernel's last round.  Two sets of P buffers alternate; the side stream waits for everything the main
@@ -740,6 +758,34 @@ int launch_eval(paml_amd_engine *e, const double *branch, const double *gene_rat
 // launches for the other translation units (a __global__ function has one home)
 void launch_pmat(const PmatArgs &pa, const InlineVec &iv, int n_nodes, int psets, bool small, hipStream_t s, bool mfma = false);
 bool pmat_on_matrix_cores(const paml_amd_engine *e, const PmatArgs &pa);
+// The two argument structures are filled in one place each: every field that follows from the engine's state, and as parameters what the
+// call sites differ in; a site adds what is its own (batch strides, PmatRes, export buffers, the reduction fields of the fused kernels).
+PmatArgs pmat_args(const paml_amd_engine *e, int root, const int *label, int layout, double *pcol);
+PruneArgs prune_args(const paml_amd_engine *e, const Program &prog, int K, const Op *ops, bool full_tiles, int n_scale, bool keep, double *partials,
+                     double *scalef, int overflow);
+// The P(t) buffers of `psets` parameter sets (`m20_pint`: the operand-order copies of 20 states on the matrix cores, pmat layout 2)
+inline int ensure_pmat_buffers(paml_amd_engine *e, int psets, bool m20_pint, bool pcol)
+{
+   const size_t pn = (size_t)psets * e->tree.n_nodes;
+   HIPCHK(e->d_rowmajor.ensure(pn * e->n * e->n));
+   if (e->kk == KK_MFMA64) HIPCHK(e->d_pint.ensure(pn * 4096));
+   if (m20_pint) HIPCHK(e->d_pint.ensure(pn * 400));
+   if (pcol) HIPCHK(e->d_pcol.ensure(pn * 64));
+   HIPCHK(e->d_ptip.ensure(pn * tip_words(e)));
+   return 0;
+}
+inline int check_stack_depth(paml_amd_engine *e, const Program &prog)      // 4 / 5 / 20 states: the interpreter's stack holds the program
+{
+   if (e->kk == KK_MFMA64 || prog.max_stack <= (e->kk == KK_VALU20 ? VALU_MAXD_20 : VALU_MAXD_SMALL)) return 0;
+   return fail(e, PAML_AMD_EUNSUPPORTED, "tree needs a deeper partial stack than this kernel provides");
+}
+// 21..64 states: the stack slots beyond the kernels' registers live in global scratch (d_stack), per workgroup and wave
+inline int stack_overflow(paml_amd_engine *e, const Program &prog, int n_blocks, int waves, int *slots)
+{
+   *slots = (e->kk == KK_MFMA64 && prog.max_stack > MFMA_RS) ? prog.max_stack - MFMA_RS : 0;
+   if (*slots) HIPCHK(e->d_stack.ensure((size_t)n_blocks * *slots * waves * 1024));
+   return 0;
+}
 void launch_prune_full(paml_amd_engine *e, int max_stack, int n_blocks, const PruneArgs &pr, hipStream_t s);      // gather (21..64 states) or valu interpreter
 void launch_zpm(const unsigned char *z, long z_stride, int n_tips, int n_patt, int zw, unsigned int *out, hipStream_t s);
 
