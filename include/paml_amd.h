@@ -328,6 +328,15 @@ int paml_amd_profile_read(paml_amd_engine *e, double *ms_pmat, double *ms_prune,
 /* Counters mirroring NFunCall / NPMatUVRoot (tools.c:88, printed codeml.c:770). */
 int paml_amd_counters(const paml_amd_engine *e, long *n_eval, long *n_pmat);
 
+/* Cherry tables of the last evaluation.  On large codon data sets (61..64 states, at most 64 character codes, one gene and one
+ * frequency vector, no PAML_AMD_KEEP_PARTIALS, single evaluations, at most 95 tips — trees whose tip codes fit two LDS blocks of the
+ * per-tree kernel —; from PAML_AMD_CHERRY_MIN_PATT = 32768 patterns of this engine on, where per-tree kernels are on)
+ * the per-tree kernel replaces the product P(t) . (tipA o tipB) of a cherry — an internal node with two tip sons — by a lookup in a
+ * table of all n_codes^2 such products, built once per evaluation right behind P(t).  Same bits as without.  *n_tabulated: cherries
+ * looked up (in program order, as many as PAML_AMD_CHERRY_CAP_MB = 192 MB of tables hold over all classes); *bytes: the tables' size.
+ * Both 0 when the evaluation ran without.  PAML_AMD_CHERRY_TABLES=0 / 1 switches the tables off / on whatever the number of patterns. */
+int paml_amd_cherry_tables(const paml_amd_engine *e, long *n_tabulated, long *bytes);
+
 /* Host-only introspection (no GPU needed): the flattened post-order program the engine would run for
  * a tree — 4 ints per op (code, a, b, c; paml_amd/csrc/program.h).  Returns the number of ops (or a
  * negative error); at most cap ops are written.  Used by the CPU test-suite to check the traversal. */
@@ -348,6 +357,14 @@ int paml_amd_debug_code_order(int n_states, int n_codes, const int *n_chara, con
  * with the compiler log in text_out. */
 int paml_amd_debug_jit(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons,
                        const unsigned char *scale_node, char *text_out, int cap, int compile);
+
+/* Host-only: the cherry-table form of the 61-state kernel for a tree (61 character codes, one class), at most max_tabs cherries
+ * tabulated in program order: its source in text_out, the operand stream it is left with in stream_out ((is_tip, node) pairs,
+ * *n_stream of them) and the tabulated cherries in tabs_out ((tip a, tip b, node) triples).  Returns the number of cherries
+ * tabulated (0, with empty outputs, where the table form does not apply), or a negative error. */
+int paml_amd_debug_jit_tables(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node,
+                              int max_tabs, char *text_out, int cap, int *stream_out, int stream_cap, int *n_stream, int *tabs_out,
+                              int tabs_cap);
 
 /* Host-only (hiprtc cross-compiles without a GPU): compile the per-tree kernel an engine of these sizes would select for this tree
  * and keep the code object in `dir` (the library's read-only lib/jit directory, or a user cache), so that the first evaluation on

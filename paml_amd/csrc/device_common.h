@@ -86,6 +86,8 @@ struct PruneArgs {
                                 // put their STOREs (every wave must issue the same vector-memory operations: the operand ring's waits count them)
    const unsigned long long *code_mask;      // [n_codes] state sets of the character codes as bit masks (tools.c:20 nChara / CharaMap): the per-tree
                                              // kernel's codes beyond the 64 a ring block has rows for (JIT_AMB_OVERFLOW)
+   const double *ctab;          // per-tree kernel with cherry tables (jit.h: OP_LOOKUP): [class][n_ctab][n_codes * n_codes][64], else null
+   int n_ctab;
 };
 
 __device__ __forceinline__ double root_value(const PruneArgs &a, double f, double lnscale)
@@ -522,6 +524,31 @@ __device__ __forceinline__ void jit_mul(v4d (&y)[4], const v4d (&s)[4])   // y =
 #pragma unroll
    for (int jb = 0; jb < 4; jb++) y[jb] = s[jb] * y[jb];
 }
+
+__device__ __forceinline__ void jit_copy(v4d (&y)[4], const v4d (&s)[4])
+{
+#pragma unroll
+   for (int jb = 0; jb < 4; jb++) y[jb] = s[jb];
+}
+
+// Cherry tables (jit.h: OP_LOOKUP; built by cherry_table_kernel): the finished P(t_c) . (tipA[:,ca] o tipB[:,cb]) of table `tab`, a row of
+// 512 bytes per (ca, cb) laid out [piece i][q][16 bytes] — piece i holds the elements 2 i, 2 i + 1 (states 4 m + q) of lane q, as
+// jit_load reads a resident partial, and the four q-lanes of a pattern read 64 contiguous bytes per instruction.  Eight
+// compiler-visible 16-byte loads per lane (the generator enters them in its in-flight list like jit_load's).  Codes are clamped: a
+// prefetch for a tile that does not exist may read any row, but only rows of the table.
+#define CHERRY_ROW_WORDS 64
+__device__ __forceinline__ void jit_lookup_nc(v4d (&y)[4], const double *tab, int ca, int cb, int q, int nc)
+{
+   ca = ca < nc ? ca : nc - 1;
+   cb = cb < nc ? cb : nc - 1;
+   const part2_t *r = (const part2_t *)(tab + (ca * nc + cb) * CHERRY_ROW_WORDS) + q;
+#pragma unroll
+   for (int i = 0; i < 8; i++) { const part2_t v = r[i * 4]; y[i >> 1][(2 * i) & 3] = v.x; y[i >> 1][(2 * i + 1) & 3] = v.y; }
+}
+#ifdef JIT_NC
+#define JIT_CTAB(CLS, C) (a.ctab + ((long)(CLS) * a.n_ctab + (C)) * (long)(JIT_NC * JIT_NC * CHERRY_ROW_WORDS))
+__device__ __forceinline__ void jit_lookup(v4d (&y)[4], const double *tab, int ca, int cb, int q) { jit_lookup_nc(y, tab, ca, cb, q, JIT_NC); }
+#endif
 
 __device__ __forceinline__ void jit_init_ones(v4d (&y)[4], int q, int n)
 {

@@ -344,6 +344,7 @@ int paml_amd_eval_branch(paml_amd_engine *e, int node_b, int n_t, const double *
                                           (e->jit_forced || e->env.jit_sync) ? JIT_WAIT_CALLER : JIT_WAIT_WORKER, "refill", &have)) return rc;
             if (have) {
                e->kernel = PK_MFMA64_JIT;      // (kernel_name: the last pruning kernel was a per-tree one)
+               e->last_ctab_n = e->last_ctab_bytes = 0;      // (... without cherry tables)
                if (int rc = select_tiles(e, true, 8, true)) return rc;
                const int n_blocks = e->n_tiles * K;
                int overflow = 0;

@@ -760,6 +760,14 @@ int paml_amd_profile_read(paml_amd_engine *e, double *ms_pmat, double *ms_prune,
    return 0;
 }
 
+int paml_amd_cherry_tables(const paml_amd_engine *e, long *n_tabulated, long *bytes)
+{
+   if (!e) return PAML_AMD_EINVAL;
+   if (n_tabulated) *n_tabulated = e->last_ctab_n;
+   if (bytes) *bytes = e->last_ctab_bytes;
+   return 0;
+}
+
 int paml_amd_counters(const paml_amd_engine *e, long *n_eval, long *n_pmat)
 {
    if (!e) return PAML_AMD_EINVAL;

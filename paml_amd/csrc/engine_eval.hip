@@ -380,8 +380,30 @@ int choose_kernel(paml_amd_engine *e, const Eval &c, PruneKernel *out)
       // the interpreter serving meanwhile; code-block pieces follow one program's order, so trees beyond 207 tips keep the interpreter there
       bool has_load = false;
       for (const Op &o : e->prog.ops) has_load = has_load || o.code == OP_LOAD;
+      e->n_ctab = 0;
       if (e->jit_enabled && !(has_load && e->n_tips > 207) && (e->n_codes <= 64 || (e->amb_ascending && e->plain_codes >= n)) && jit_supported(e->prog, e->n_tips, e->n_codes, e->n_pi, 6, jw * 16, true)) {
-         const std::string key = "m" + std::to_string(n) + "c" + std::to_string(e->n_codes) + "w" + std::to_string(jw) + ":" + jit_program_key(e->prog, e->n_tips);
+         const std::string pkey = jit_program_key(e->prog, e->n_tips);
+         std::string key = "m" + std::to_string(n) + "c" + std::to_string(e->n_codes) + "w" + std::to_string(jw) + ":" + pkey;
+         // Cherry tables (jit.h: OP_LOOKUP): one gene and frequency vector, single evaluations of the whole tree, enough patterns for the
+         // builder's launch to pay (EnvCfg), as many cherries, in program order, as the cap on table bytes leaves room for
+         int n_tab = 0;
+         if (e->env.cherry_tables != 0 && G == 1 && e->n_pi == 1 && c.B == 1 && !c.keep && !c.clean && !has_load &&
+             (e->env.cherry_tables == 1 || e->n_patt >= e->env.cherry_min_patt)) {
+            const std::string ckey = std::to_string(c.K) + "k" + std::to_string(n) + "m" + std::to_string(e->n_codes) + "c" + std::to_string(e->env.cherry_cap_mb) + ":" + pkey;
+            if (e->cherry_key != ckey) {      // (a new tree, class count or code table: the count and the table form once)
+               e->cherry_n = jit_cherry_count(e->prog, e->n_tips, n, e->n_codes, c.K, (size_t)e->env.cherry_cap_mb << 20, jw * 16);
+               e->cherry = e->cherry_n ? jit_cherry_program(e->prog, e->cherry_n) : CherryProgram();
+               e->cherry_key = ckey;
+            }
+            n_tab = e->cherry_n;
+         }
+         if (n_tab) {
+            const std::string tkey = "t" + std::to_string(n_tab) + key;
+            bool ok = false;
+            if (int r = obtain_kernel(e, e->jit_slot, &e->jit, true, tkey, [&]() { return jit_generate(e->cherry.prog, e->n_tips, n, e->n_codes, &e->cherry.tabs); },
+                                      (e->prog.ops.size() > 120 && !e->jit_forced && !e->env.jit_sync) ? JIT_WAIT_WORKER : JIT_WAIT_CALLER, "tree, cherry tables", &ok)) return r;
+            if (ok) { jit_ok = true; e->n_ctab = n_tab; }
+         }
          // Large trees (> 120 ops: roughly more than 35 taxa): tens of thousands of instructions, many seconds of compiler time.  Unless the
          // caller asked to wait (PAML_AMD_JIT flag / PAML_AMD_JIT_SYNC), the kernel is built on a worker thread while the interpreter kernels
          // serve, and the engine changes over when the code object is there; one found on disk is loaded at once.  Round 5: the generator
@@ -391,7 +413,7 @@ int choose_kernel(paml_amd_engine *e, const Eval &c, PruneKernel *out)
          const bool big = e->prog.ops.size() > 120;
          const bool background = (big || has_load) && !e->jit_forced && !e->env.jit_sync;
          const bool wanted = !has_load || e->jit_forced || e->env.jit_sync || e->jit_recall(key) || e->jit_count_request(key) >= 2;
-         if (wanted)
+         if (wanted && !jit_ok)      // (also while the table form is still being compiled, or when it could not be)
             if (int r = obtain_kernel(e, e->jit_slot, &e->jit, true, key, [&]() { return jit_generate(e->prog, e->n_tips, n, e->n_codes); },
                                       background ? JIT_WAIT_WORKER : JIT_WAIT_CALLER, "tree", &jit_ok)) return r;
       }
@@ -465,10 +487,15 @@ int ensure_buffers(paml_amd_engine *e, Eval &c)
    if (c.pipe) {
       paml_amd_engine::PSet &sp = e->spare[e->spare_head];      // the set used longest ago
       std::swap(e->d_rowmajor, sp.rowmajor); std::swap(e->d_pint, sp.pint); std::swap(e->d_ptip, sp.ptip); std::swap(e->d_pcol, sp.pcol);
+      std::swap(e->d_ctab, sp.ctab);
       std::swap(e->pset, sp.id);
       e->spare_head = (e->spare_head + 1) % (paml_amd_engine::NPSET - 1);
    }
    if (int rc = ensure_pmat_buffers(e, c.psets, e->kk == KK_VALU20 && e->want_m20, e->kk == KK_MFMA64)) return rc;
+   if (e->kernel != PK_MFMA64_JIT) e->n_ctab = 0;
+   e->last_ctab_n = e->n_ctab;
+   e->last_ctab_bytes = (long)((size_t)c.K * e->n_ctab * cherry_table_bytes(e->n_codes));
+   if (e->n_ctab) HIPCHK(e->d_ctab.ensure((size_t)e->last_ctab_bytes / sizeof(double)));
    HIPCHK(e->d_fhK.ensure((size_t)c.K * e->n_patt));
    c.n_blocks = e->n_tiles * c.K;
    if (c.keep) {
@@ -524,6 +551,21 @@ int run_pmat(paml_amd_engine *e, Eval &c, const InlineVec &iv)
    bool small_pmat = e->kk != KK_MFMA64 && e->n <= 5;
    for (const EigenHost &h : e->eigen) small_pmat = small_pmat && h.kind != PAML_AMD_EIGEN_QMAT;      // (ids never set: kind < 0, fine)
    launch_pmat(pa, iv, nn, c.psets, small_pmat, c.ps, pmat_mfma);
+   if (e->n_ctab) {      // the cherry tables of this P(t): behind it, on its stream
+      CherryTabArgs ca{};
+      ca.n_codes = e->n_codes; ca.n_nodes = nn; ca.n_tabs = e->n_ctab; ca.tip_words = (long)tip_words(e);
+      ca.pint = e->d_pint.p; ca.ptip = e->d_ptip.p; ca.pcol = e->d_pcol.p; ca.ctab = e->d_ctab.p;
+      for (int i = 0; i < e->n_ctab; i++) { ca.tabs[3 * i] = e->cherry.tabs[i].tip_a; ca.tabs[3 * i + 1] = e->cherry.tabs[i].tip_b; ca.tabs[3 * i + 2] = e->cherry.tabs[i].node; }
+      const size_t lds = (size_t)(3 * 4096 + 64) * sizeof(double);
+      if (!e->ctab_attr_set) {
+         HIPCHK(hipFuncSetAttribute((const void *)cherry_table_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+         HIPCHK(hipFuncSetAttribute((const void *)cherry_table_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+         e->ctab_attr_set = true;
+      }
+      const dim3 g((e->n_codes * e->n_codes + 127) / 128, e->n_ctab, c.K);
+      if (e->n == 61) hipLaunchKernelGGL(cherry_table_kernel<true>, g, dim3(512), lds, c.ps, ca);
+      else hipLaunchKernelGGL(cherry_table_kernel<false>, g, dim3(512), lds, c.ps, ca);
+   }
    mark_on(e, c.ps);
    if (c.pipe) {      // the pruning kernel (main stream) starts when this P(t) is there
       HIPCHK(hipEventRecord(e->ev_pmat, e->s2));
@@ -611,6 +653,7 @@ int run_prune(paml_amd_engine *e, Eval &c)
    PruneArgs pr = prune_args(e, e->prog, K, e->d_ops.p, false, e->tree.n_scale, c.keep, e->d_partials.p, e->d_scalef.p, c.overflow);
    if (k == PK_MFMA4X20_JIT) { pr.pint = e->d_pint.p; pr.pcol = e->d_rowmajor.p; }      // (operand-order P(t); the row-major copies for the all-4x4x4 experiment)
    pr.fhK = e->fhk_slot(e->last_fhk).p;
+   if (k == PK_MFMA64_JIT && e->n_ctab) { pr.ctab = e->d_ctab.p; pr.n_ctab = e->n_ctab; }      // (this P set's cherry tables)
    const int nb = (e->n_patt + e->chunk - 1) / e->chunk;      // the reduction's geometry: chunks of this engine
    if (pk_forms_reduction(k)) {      // (the others leave the partial sums to reduce_stage1)
       pr.Km = c.Km; pr.chunk = e->chunk; pr.first_chunk = e->first_chunk; pr.nb_stride = e->nb_global;

@@ -112,6 +112,44 @@ int paml_amd_debug_jit(int n_tips, int n_nodes, int root, const int *sons_ptr, c
    return rc;
 }
 
+// The table form (jit.h: OP_LOOKUP) of the 61-state kernel for a tree, at most max_tabs cherries tabulated: its source, the operand
+// stream it is left with ((is_tip, node) pairs) and the tabulated cherries ((tip a, tip b, node) triples).  Returns the number of
+// cherries tabulated (0: the table form does not apply); *n_stream the number of pairs.
+int paml_amd_debug_jit_tables(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node,
+                              int max_tabs, char *text_out, int cap, int *stream_out, int stream_cap, int *n_stream, int *tabs_out, int tabs_cap)
+{
+   if (!sons_ptr || !sons || n_nodes <= 0 || root < 0 || root >= n_nodes) return PAML_AMD_EINVAL;
+   TreeDesc t;
+   t.n_tips = n_tips; t.n_nodes = n_nodes; t.root = root;
+   t.sons_ptr.assign(sons_ptr, sons_ptr + n_nodes + 1);
+   t.sons.assign(sons, sons + sons_ptr[n_nodes]);
+   t.label.assign(n_nodes, 0);
+   t.scale_node.assign(n_nodes, 0);
+   t.scale_slot.assign(n_nodes, -1);
+   if (scale_node)
+      for (int i = 0; i < n_nodes; i++)
+         if (scale_node[i]) { t.scale_node[i] = 1; t.scale_slot[i] = t.n_scale++; }
+   const Program p = build_program(t, false, nullptr);
+   if (!jit_supported(p, n_tips, 61)) return PAML_AMD_EUNSUPPORTED;
+   const int n_tab = jit_cherry_count(p, n_tips, 61, 61, 1, (size_t)std::max(max_tabs, 0) * cherry_table_bytes(61));
+   if (n_stream) *n_stream = 0;
+   if (text_out && cap > 0) text_out[0] = 0;
+   if (!n_tab) return 0;
+   const CherryProgram cp = jit_cherry_program(p, n_tab);
+   const std::string text = jit_generate(cp.prog, n_tips, 61, 61, &cp.tabs);
+   if (text_out && cap > 0) {
+      const size_t ncp = std::min((size_t)cap - 1, text.size());
+      memcpy(text_out, text.data(), ncp);
+      text_out[ncp] = 0;
+   }
+   if (n_stream) *n_stream = (int)cp.prog.stream.size() / 2;
+   if (stream_out)
+      for (int i = 0; i < (int)cp.prog.stream.size() && i < stream_cap; i++) stream_out[i] = cp.prog.stream[i];
+   if (tabs_out)
+      for (int i = 0; i < n_tab && 3 * i + 2 < tabs_cap; i++) { tabs_out[3 * i] = cp.tabs[i].tip_a; tabs_out[3 * i + 1] = cp.tabs[i].tip_b; tabs_out[3 * i + 2] = cp.tabs[i].node; }
+   return n_tab;
+}
+
 int paml_amd_jit_prebuild(int n_states, int n_tips, int n_codes, int K, long n_patt_global, int n_nodes, int root, const int *sons_ptr,
                           const int *sons, const unsigned char *scale_node, const char *dir, char *log_out, int log_cap)
 {
@@ -145,6 +183,21 @@ int paml_amd_jit_prebuild(int n_states, int n_tips, int n_codes, int K, long n_p
    else {
       if (!jit_supported(p, n_tips, n_codes)) return PAML_AMD_EUNSUPPORTED;
       text = jit_generate(p, n_tips, n_states, n_codes);
+      // ... and the table form an engine of these sizes (one gene, one frequency vector) runs by default: choose_kernel's conditions
+      EnvCfg env;
+      env.read();
+      const bool keep = getenv("PAML_AMD_PREBUILD_KEEP") != nullptr;
+      const int n_tab = (env.cherry_tables != 0 && !keep && (env.cherry_tables == 1 || n_patt_global >= env.cherry_min_patt))
+                           ? jit_cherry_count(p, n_tips, n_states, n_codes, K, (size_t)env.cherry_cap_mb << 20) : 0;
+      if (n_tab) {
+         const CherryProgram cp = jit_cherry_program(p, n_tab);
+         std::vector<char> code;
+         std::string log;
+         if (jit_compile_code(jit_generate(cp.prog, n_tips, n_states, n_codes, &cp.tabs), &code, &log, dir) != 0) {
+            if (log_out && log_cap > 0) { strncpy(log_out, log.c_str(), log_cap - 1); log_out[log_cap - 1] = 0; }
+            return PAML_AMD_EHIP;
+         }
+      }
    }
    if (const char *dump = getenv("PAML_AMD_JIT_DUMP")) {
       FILE *f = fopen(dump, "w");

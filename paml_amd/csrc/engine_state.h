@@ -190,6 +190,11 @@ struct EnvCfg {
    bool no_coop = false;            // PAML_AMD_COOP=0: small data sets on the gather kernel (one wave per 16-pattern group) instead of prune_mfma64_coop
    bool jit_sync = false, jit_strict = false, no_m20 = false;
    int comm_cus = -1, lanes = 0;
+   // cherry tables of the per-tree 61..64-state kernel (jit.h: OP_LOOKUP).  PAML_AMD_CHERRY_TABLES=0 / 1: never / whatever the number of
+   // patterns (the other conditions are correctness gates and stay); PAML_AMD_CHERRY_MIN_PATT, PAML_AMD_CHERRY_CAP_MB: the two measured
+   // choices — patterns of this engine from which the tables pay, and the most table bytes of one evaluation
+   int cherry_tables = -1;
+   long cherry_min_patt = 32768, cherry_cap_mb = 192;
    std::string jit_dump, prof_ops;
    int prof_tid = 0;
    bool prof_tiles = false;      // the dump is a workgroup timeline (jit.h proft) instead of per-op stamps
@@ -207,6 +212,9 @@ struct EnvCfg {
       if (const char *v = getenv("PAML_AMD_COMM_CUS")) comm_cus = atoi(v);
       comm_stats = getenv("PAML_AMD_COMM_STATS") != nullptr;
       if (const char *v = getenv("PAML_AMD_LANES")) lanes = atoi(v);      // evaluations of a run in flight at once (2 .. 4; default 2: three measured 5 % slower, four 25 %)
+      if (const char *v = getenv("PAML_AMD_CHERRY_TABLES")) cherry_tables = atoi(v) != 0 ? 1 : 0;
+      if (const char *v = getenv("PAML_AMD_CHERRY_MIN_PATT")) cherry_min_patt = atol(v);
+      if (const char *v = getenv("PAML_AMD_CHERRY_CAP_MB")) cherry_cap_mb = std::max(0L, atol(v));
       if (const char *v = getenv("PAML_AMD_JIT_DUMP")) jit_dump = v;
       if (const char *v = getenv("PAML_AMD_PROF_OPS")) prof_ops = v;
       if (const char *v = getenv("PAML_AMD_PROF_TID")) prof_tid = atoi(v);
@@ -374,6 +382,17 @@ struct paml_amd_engine {
    DevBuf<int> d_stream;
    Staging stage;
    JitKernel jit;            // per-tree specialised kernel (jit.h), valid when jit.fn != nullptr
+   // Cherry tables (jit.h: OP_LOOKUP; kernels_pmat.h: cherry_table_kernel): the table form of `prog` and its tables (cherry, for
+   // cherry_key = program, classes, codes and cap: formed when one of them changes, not per evaluation; cherry_n = cherries tabulated),
+   // the tables of the current P set (d_ctab: built behind its P(t) on the same stream, rotated with it — so a table is never rewritten
+   // while a pruning kernel of another lane reads it), and what the last evaluation used (paml_amd_cherry_tables).
+   CherryProgram cherry;
+   std::string cherry_key;
+   int cherry_n = 0;
+   DevBuf<double> d_ctab;
+   int n_ctab = 0;
+   bool ctab_attr_set = false;
+   long last_ctab_n = 0, last_ctab_bytes = 0;
    // Kernels of this engine's OTHER programs, kept loaded (round 6): a keep-partials engine alternates between its full program and the LOAD
    // programs of paml_amd_eval_dirty (com.oldconP: one per set of clean nodes, treespace.c:250), eval_branch between the tree seen from a
    // branch and the ordinary one — the kernel being left is retired here instead of unloaded, and recalled by its key.
@@ -431,7 +450,7 @@ struct paml_amd_engine {
    // the others in `spare`, oldest first from spare_head), so that the side stream can build the P(t) of the evaluations to come
    // while several pruning kernels are in flight (pruning streams, below) — it only has the CUs those leave it.
    static constexpr int NPSET = 6;
-   struct PSet { DevBuf<double> rowmajor, pint, ptip, pcol; int id = 0; } spare[NPSET - 1];
+   struct PSet { DevBuf<double> rowmajor, pint, ptip, pcol, ctab; int id = 0; } spare[NPSET - 1];      // (ctab: the set's cherry tables, below)
    int spare_head = 0;
    DevBuf<double> d2_branch, d2_gene_rate;
    // The persistent pruning kernels (per-tree MFMA kernel, 20-state matrix-core kernel) hold every CU until their last round of
@@ -564,13 +583,14 @@ struct paml_amd_engine {
       d_stream.release();
       d_eigen.release();
       d_pres.release();
+      d_ctab.release();
       d_eq_q.release(); d_eq_pi.release(); d_eq_scale.release(); d_eq_ptr.release(); d_eq_rc.release(); d_eq_sweeps.release();
       d_pi_plain.release();
       DevBuf<double> *b3[] = {&d_weights, &d_pi, &d_freqK, &d_rate, &d_qfactor, &d_branch, &d_gene_rate, &d_rowmajor,
                               &d_pint, &d_ptip, &d_pcol, &d_fhK, &d_fscale, &d_lnf, &d_b_qfactor, &d_b_freqK, &d_b_rate, &d_beb_f, &d_beb_part, &d_beb_g, &d_beb_out, &d_beb_pcl, &d_adg_all, &d_partial, &d_out, &d_partials, &d_scalef, &d_stack, &d2_branch, &d2_gene_rate, &d_partial_tot, &d_btot,
                               &d_expA, &d_expB, &d_expSA, &d_expSB, &d_deriv, &d_tt, &d_bpartial, &d_bout};
       for (auto b : b3) b->release();
-      for (auto &sp : spare) { sp.rowmajor.release(); sp.pint.release(); sp.ptip.release(); sp.pcol.release(); }
+      for (auto &sp : spare) { sp.rowmajor.release(); sp.pint.release(); sp.ptip.release(); sp.pcol.release(); sp.ctab.release(); }
       for (int b = 0; b < MAXL - 1; b++) { d_partial_s[b].release(); d_partial_tot_s[b].release(); d_fhK_s[b].release(); }
    }
 };

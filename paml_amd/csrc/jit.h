@@ -156,6 +156,61 @@ inline std::string jit_program_key(const Program &p, int n_tips)
    return k.str();
 }
 
+// ---- cherry tables (61..64 states) ------------------------------------------------------------------------------------
+// A cherry's partial tipA[:,ca] o tipB[:,cb] takes at most n_codes^2 values over the whole alignment, and so does its product with
+// P(t_cherry).  cherry_table_kernel (kernels_pmat.h) forms T_c[ca][cb] = P(t_c) . (tipA[:,ca] o tipB[:,cb]) once per evaluation, right
+// behind P(t), with the walk's own building blocks (same bits), and the walk gathers the finished 64-vector: `SET_TIP2 a b` directly
+// followed by the MATMUL / MATMUL_POP of the cherry's node becomes one OP_LOOKUP, and its three operand blocks leave the stream.
+// Only the per-tree kernel sees this form: it is derived from the tree's program, which the interpreters keep.
+constexpr int OP_LOOKUP = 100;           // a: the cherry's node, b: as MATMUL (pop / push slots), c: its table's number
+constexpr int JIT_LOOKAHEAD = 2;         // lookups whose rows are requested before the one being consumed is awaited
+struct CherryTab { int tip_a, tip_b, node; };
+struct CherryProgram {
+   Program prog;
+   std::vector<CherryTab> tabs;
+};
+constexpr int CHERRY_MAX_TABS = 48;           // cherries of a tree whose tip codes fit two LDS blocks (<= 95 tips): what CherryTabArgs carries
+constexpr size_t CHERRY_ROW_BYTES = 512;      // one (ca, cb) pair: [piece i of 8][q of 4][16 bytes] — the four q-lanes of a pattern read 64 contiguous bytes
+inline size_t cherry_table_bytes(int n_codes) { return (size_t)n_codes * n_codes * CHERRY_ROW_BYTES; }
+
+inline CherryProgram jit_cherry_program(const Program &p, int max_tabs)
+{
+   CherryProgram cp;
+   cp.prog.max_stack = p.max_stack;
+   const std::vector<Op> &o = p.ops;
+   for (size_t i = 0; i < o.size(); i++) {
+      const bool mm = i + 1 < o.size() && (o[i + 1].code == OP_MATMUL || o[i + 1].code == OP_MATMUL_POP);
+      if (o[i].code == OP_SET_TIP2 && mm && (int)cp.tabs.size() < max_tabs) {
+         cp.prog.ops.push_back({OP_LOOKUP, o[i + 1].a, o[i + 1].b, (int)cp.tabs.size()});
+         cp.tabs.push_back({o[i].a, o[i].b, o[i + 1].a});
+         i++;
+         continue;
+      }
+      cp.prog.ops.push_back(o[i]);
+      if (o[i].code == OP_MATMUL || o[i].code == OP_MATMUL_POP) cp.prog.n_matmul++;
+   }
+   finish_program(cp.prog);      // (the stream without the tabulated cherries' blocks; OP_LOOKUP is none of its cases)
+   return cp;
+}
+
+// Cherries to tabulate: in program order while the tables of all K classes stay within `cap_bytes`, and none where the table form does
+// not apply (more than 64 codes, LOAD / STORE programs, trees whose tip codes do not fit two LDS blocks) or would leave the ring fewer
+// than four operand blocks per tile.
+inline int jit_cherry_count(const Program &p, int n_tips, int n_states, int n_codes, int K, size_t cap_bytes, int tp = 128)
+{
+   if (n_states < 61 || n_states > 64 || n_codes > 64 || n_codes < 1 || K < 1) return 0;
+   if (jit_zplan(p, n_tips, tp).bufs != 2) return 0;
+   for (const Op &o : p.ops)
+      if (o.code == OP_LOAD || o.code == OP_STORE) return 0;
+   int want = (int)std::min<size_t>(cap_bytes / ((size_t)K * cherry_table_bytes(n_codes)), (size_t)CHERRY_MAX_TABS);
+   for (; want > 0; want--) {
+      const CherryProgram cp = jit_cherry_program(p, want);
+      if ((int)cp.tabs.size() < want) { want = (int)cp.tabs.size() + 1; continue; }      // (fewer cherries than the cap allows)
+      if (cp.prog.stream.size() / 2 >= 4) return want;
+   }
+   return 0;
+}
+
 // Emit the straight-line kernel for one program.
 //
 // Schedule (all static): the program's operand blocks are consumed in stream order through a ring of four LDS buffers
@@ -175,7 +230,8 @@ inline std::string jit_program_key(const Program &p, int n_tips)
 // compiler's schedule of the shorter blocks measures 0.6 % faster (kernel 1.554 -> 1.544 ms at 16 taxa x 10^6 patterns, two runs each).
 static const size_t JIT_SPLIT_OPS = 8;
 inline bool jit_split_mode(size_t nops) { return nops > JIT_SPLIT_OPS; }
-inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states, int n_codes, int first, int *first_out)
+inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states, int n_codes, int first, int *first_out,
+                                     const std::vector<CherryTab> *tabs = nullptr)
 {
    std::ostringstream s;
    const int waves = 8;
@@ -207,6 +263,19 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
    int cur_piece = 0;         // (piece mode) the piece of the tile's codes that is in LDS
    const bool peel = fuse_tips && nops > 2 && p.ops[0].code == OP_SET_TIP2 && last_mm > 1 &&
                      p.ops[1].code != OP_MUL_TIP && p.ops[1].code != OP_MUL_TIP2 && !tail_blocks && !zsingle;
+   // cherry tables (OP_LOOKUP): the rows of a lookup are requested JIT_LOOKAHEAD lookups ahead of their use, so that a product lies
+   // between request and use; those of a tile's first lookups under the previous tile's last product (or, in front of the loop, for the
+   // first tile), into arrays of their own
+   std::vector<int> lk_op;      // the program's lookups, in order: op index
+   for (size_t i = 0; i < nops; i++)
+      if (p.ops[i].code == OP_LOOKUP) lk_op.push_back((int)i);
+   const int nlk = (int)lk_op.size();
+   const bool lk_cross = nlk > 0 && !peel && !zsingle;      // the first lookups of a tile are requested by its predecessor
+   // (trees that keep three or more partials stacked in registers: one lookup ahead — with two the 23-taxon random tree of the tests
+   //  spills 18 VGPRs)
+   const int LA = std::min(p.max_stack, JIT_REG_SLOTS) >= 3 ? 1 : JIT_LOOKAHEAD;
+   const int lk_ncross = lk_cross ? std::min(nlk, LA) : 0;
+   const int LK_ID = -10;       // in-flight list: lookup j is item LK_ID - j
 
    // chunks of a tip table that hold codes of this data set (two codes per 1 KB chunk)
    const int TCH = (n_codes + 1) / 2 >= 31 ? 32 : (n_codes + 1) / 2;
@@ -217,6 +286,7 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
    if (zhalf) s << "#define JIT_ZPIECES " << zpl.pieces << "\n";
    const bool amb_over = n_codes > 64;      // codes beyond the 64 a ring block has rows for: summed from the rows of their states (device_common.h)
    if (amb_over) s << "#define JIT_AMB_OVERFLOW 1\n";
+   if (nlk) s << "#define JIT_NC " << n_codes << "\n";
    const std::string ambarg = amb_over ? ", amb" : "";
    s << "#include \"device_common.h\"\nusing namespace paml_amd;\n";
    s << "extern \"C\" __global__ __launch_bounds__(" << waves * 64 << ", " << waves / 4 << ") void prune_jit(PruneArgs a)\n{\n";
@@ -259,6 +329,7 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
    };
    bool z_pending = false;                   // the next tile's code block still has to be requested in this tile
    std::vector<std::string> pend_store;      // the pieces of a STORE that ride under the product that follows it (see step)
+   std::vector<std::pair<int, std::string>> pend_lookup;      // (in-flight id, text) of the lookups requested in the last iteration of the product that follows
    // make the next c blocks visible, then top the ring up — at once, or (defer) as a `side` functor that spreads the
    // refill's pieces over the first `iters` k-block pairs of the matmul that follows; the first `now` blocks from
    // `consumed` are needed within this very step and are never delayed
@@ -302,11 +373,15 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
          for (int c4 = 0; c4 < n_pieces(issued); c4++) pieces.push_back({issued, piece(issued, c4)});
          issued++;
       }
-      if (pieces.empty() && stores.empty()) return "JitNoSide()";
+      if (pieces.empty() && stores.empty() && pend_lookup.empty()) return "JitNoSide()";
       const int per = pieces.empty() ? 1 : ((int)pieces.size() + iters - 1) / iters;
       std::vector<std::vector<Piece>> at(iters);
       for (size_t i = 0; i < pieces.size(); i++) at[i / per].push_back(pieces[i]);
       for (size_t i = 0; i < stores.size(); i++) at[i * iters / stores.size()].push_back({-2, stores[i]});
+      // (behind every DMA piece of this step: the order the code in front of the loop issues them in)
+      for (const std::pair<int, std::string> &lk : pend_lookup)
+         for (int i = 0; i < 8; i++) at[iters - 1].push_back({lk.first, i ? std::string() : lk.second});
+      pend_lookup.clear();
       // the in-flight list in the order of issue (a block whose pieces span iterations has several entries: wait_count takes the last)
       std::string f = "[&](int kb2) {";
       for (int i = 0; i < iters; i++) {
@@ -350,11 +425,22 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
 
    // ---- in front of the loop: the first tile is the "next" tile of an empty predecessor ---------------------------
    const int reg_slots = std::min(p.max_stack, JIT_REG_SLOTS);
-   const int NA = reg_slots + 2 + (fuse_tips ? 1 : 0);
+   const int NA = reg_slots + 2 + (fuse_tips ? 1 : 0) + (nlk ? LA : 0);
    const int SPILLED = -2;
    auto spill_ptr = [&](int slot_no) { return "JIT_SPILL_PTR(" + std::to_string(slot_no - JIT_SCRATCH_BASE) + ")"; };
    for (int i = 0; i < NA; i++) s << "   v4d A" << i << "[4];\n";
    if (peel) s << "   v4d AS[4];\n";       // the first cherry of a tile, produced under the predecessor's last matmul
+   for (int k = 0; k < lk_ncross; k++) s << "   v4d AL" << k << "[4];\n";      // the first lookups of a tile, requested by the predecessor
+   const int AL = 2000;
+   std::vector<int> lk_arr(nlk, -1);      // lookup -> its array
+   // the rows of lookup k into array `arr`: of this tile, or (next) of the tile after it
+   auto lookup_text = [&](int k, const std::string &arr, bool next) {
+      const Op &o = p.ops[lk_op[k]];
+      const CherryTab &t = (*tabs)[o.c];
+      return "jit_lookup(" + arr + ", JIT_CTAB(" + (next ? "n_iclass" : "iclass") + ", " + std::to_string(o.c) + "), " +
+             (next ? "JIT2_NCODE(" : "JIT2_CODE(") + std::to_string(ZP) + ", " + std::to_string(zpl.row[t.tip_a]) + "), " +
+             (next ? "JIT2_NCODE(" : "JIT2_CODE(") + std::to_string(ZP) + ", " + std::to_string(zpl.row[t.tip_b]) + "), q);";
+   };
    s << "   JIT2_NEXT_SET()\n   " << issue_z << "\n";
    fl.push_back({-1, ZR});
    issued = nblk;                           // numbered as the blocks after the (empty) predecessor's
@@ -363,6 +449,13 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
       const int nw = wait_count(nblk + 1);
       s << "   JIT_WAIT(" << nw << "); __syncthreads();\n";
       s << "   jit_tip2_set<" << NPc << ">(AS, " << buf(nblk) << ", " << ncode(p.ops[0].a) << ", " << buf(nblk + 1) << ", " << ncode(p.ops[0].b) << ", q, lane" << ambarg << ");\n";
+   }
+   if (lk_ncross) {      // (the first tile's codes have to be there; the list keeps its items: the waits of later trips need them)
+      s << "   JIT_WAIT(0); __syncthreads();\n";
+      for (int k = 0; k < lk_ncross; k++) {
+         s << "   " << lookup_text(k, "AL" + std::to_string(k), true) << "\n";
+         fl.push_back({LK_ID - k, 8});
+      }
    }
    if (zsingle) {      // everything requested so far has to be there when the loop starts: the same state the loop's end leaves
       s << "   JIT_WAIT(0); __syncthreads();\n";
@@ -389,9 +482,13 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
    std::vector<int> freeA;
    for (int i = NA - 1; i >= 0; i--) freeA.push_back(i);
    const int AS = 1000;
-   auto alloc = [&]() { int r = freeA.back(); freeA.pop_back(); return r; };
-   auto release = [&](int r) { if (r != AS) freeA.push_back(r); };
-   auto name = [&](int r) { return r == AS ? std::string("AS") : "A" + std::to_string(r); };
+   bool exhausted = false;      // more arrays wanted than NA declares: the source is an #error, not undefined behaviour here
+   auto alloc = [&]() {
+      if (freeA.empty()) { exhausted = true; return 0; }
+      int r = freeA.back(); freeA.pop_back(); return r;
+   };
+   auto release = [&](int r) { if (r < AS) freeA.push_back(r); };
+   auto name = [&](int r) { return r == AS ? std::string("AS") : r >= AL ? "AL" + std::to_string(r - AL) : "A" + std::to_string(r); };
    std::vector<int> slot(256, -1);   // stack slot -> array
    int cur = peel ? AS : -1;
 
@@ -403,6 +500,23 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
       if (cur >= 0) release(cur);
       cur = alloc();
    };
+   int lk_issued = lk_ncross, lk_seen = 0;      // lookups of this tile requested / consumed so far
+   bool lk_next_done = !lk_cross;               // the next tile's first lookups are requested
+   for (int k = 0; k < lk_ncross; k++) lk_arr[k] = AL + k;
+   auto issue_lookup = [&](int k) {
+      lk_arr[k] = alloc();
+      s << "   " << lookup_text(k, name(lk_arr[k]), false) << "\n";
+      fl.push_back({LK_ID - k, 8});
+   };
+   auto issue_next_lookups = [&]() {            // (behind every operand block the tile requests: the order the code in front of the loop has)
+      for (int k = 0; k < lk_ncross; k++) {
+         s << "   " << lookup_text(k, "AL" + std::to_string(k), true) << "\n";
+         fl.push_back({LK_ID - k, 8});
+      }
+      lk_next_done = true;
+   };
+   if (nlk && !lk_cross)
+      while (lk_issued < std::min(nlk, LA)) issue_lookup(lk_issued++);
    for (size_t iop = 0; iop < nops; iop++) {
       const Op &o = p.ops[iop];
       stamp(iop);
@@ -439,6 +553,41 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
            << ", " << buf(consumed + 1) << ", " << code(o.b) << ", q, lane" << ambarg << ");\n";
          consumed += 2;
          break;
+      case OP_LOOKUP: {
+         const int j = lk_seen++, pop = mm_pop_slot(o), push = mm_push_slot(o);
+         while (lk_issued < nlk && lk_issued <= j + LA) issue_lookup(lk_issued++);
+         if (cur >= 0) release(cur);
+         const int out = lk_arr[j];
+         const int nw = wait_count(LK_ID - j);
+         if (nw >= 0) s << "   JIT_WAIT(" << nw << ");\n";
+         if (out >= AL) {      // (the predecessor's array is wanted again under this tile's last product)
+            const int own = alloc();
+            s << "   jit_copy(" << name(own) << ", " << name(out) << ");\n";
+            lk_arr[j] = own;
+         }
+         const int res = lk_arr[j];
+         if (pop >= 0) {
+            if (slot[pop] == SPILLED)
+               s << "   jit_mul_mem(" << name(res) << ", " << spill_ptr(pop) << ");\n";
+            else {
+               s << "   jit_mul(" << name(res) << ", " << name(slot[pop]) << ");\n";
+               release(slot[pop]);
+            }
+            slot[pop] = -1;
+         }
+         if (push >= JIT_REG_SLOTS) {
+            s << "   jit_spill(" << name(res) << ", " << spill_ptr(push) << ");\n";
+            release(res);
+            slot[push] = SPILLED;
+            cur = -1;
+         }
+         else if (push >= 0) {
+            slot[push] = res;
+            cur = -1;
+         }
+         else
+            cur = res;
+      } break;
       case OP_PUSH:
          if (o.b >= JIT_REG_SLOTS) {
             s << "   jit_spill(" << name(cur) << ", " << spill_ptr(o.b) << ");\n";
@@ -465,6 +614,12 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
          // (tip tables the ring could not hold earlier are requested in the first k-block pairs and awaited at the midpoint)
          // (the cross-lane read of x[60] is issued before the step's wait + barrier so that its latency hides there)
          if (tail61) s << "   { const double x60 = jit_x60(" << name(cur) << ", lane);\n";
+         // the next tile's first lookups: under this, the tile's last, product — once this tile has consumed its own (a cherry that is a
+         // son of the root comes AFTER the last product and still lives in its AL array: then they are requested in front of ROOT)
+         if (lk_cross && (int)iop == last_mm && !tail_blocks && !fuse && !fuse_next && lk_seen >= lk_ncross) {
+            for (int k = 0; k < lk_ncross; k++) pend_lookup.push_back({LK_ID - k, lookup_text(k, "AL" + std::to_string(k), true)});
+            lk_next_done = true;
+         }
          const std::string side = step(1, true, (fuse || fuse_next) ? MID : KB2, 1);
          int tgt = -1;
          if (fuse || fuse_next) {
@@ -537,6 +692,7 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
          // keep-partials mode with scaling nodes: the factors of clean subtrees were stored by earlier evaluations — all of them are
          // summed from memory in slot order, as the interpreter kernels do (MFMA_ROOT_CASE; treesub.c:7746-7747)
          cross_if({n_tips});      // (the weight flags: the last row)
+         if (!lk_next_done) issue_next_lookups();
          if (resident)
             s << "   if (a.keep && a.n_scale) { lnscale = 0; if (valid) for (int k_ = 0; k_ < a.n_scale; k_++) lnscale += a.scalef[((long)iclass * a.n_scale + k_) * a.n_patt + h]; }\n";
          s << "   jit_root_lds(a, " << name(cur) << ", lnscale, sPi + (a.n_pi > 1 ? gene : 0) * 64, " << code(n_tips)
@@ -547,6 +703,7 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
       default: break;
       }
    }
+   if (!lk_next_done) issue_next_lookups();
    // programs whose steps never came by a barrier after the tile switch (no operand blocks): request the codes here
    if (z_pending) {
       s << "   __syncthreads();\n   JIT2_ISSUE_Z(" << ZP << ")\n";
@@ -559,16 +716,18 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
    if (proft) s << "   if (a.prof && tid == 0 && ptc < a.prof_stride - 4) { a.prof[(long)blockIdx.x * a.prof_stride + 1 + ptc] = __builtin_amdgcn_s_memrealtime(); a.prof[(long)blockIdx.x * a.prof_stride + a.prof_stride - 1] = __builtin_amdgcn_s_memtime(); }\n   ptc++;\n";
    s << "   if (!has_next) break;\n   }\n   JIT_WAIT(0);\n}\n";
    *first_out = issued - nblk;
+   if (exhausted) return std::string("#error \"jit register arrays exhausted\"\n");
    return s.str();
 }
 
-inline std::string jit_generate(const Program &p, int n_tips, int n_states = 61, int n_codes = 64)
+// (`tabs`: p is the table form of the tree's program — jit_cherry_program — and these are its tables)
+inline std::string jit_generate(const Program &p, int n_tips, int n_states = 61, int n_codes = 64, const std::vector<CherryTab> *tabs = nullptr)
 {
    int first = 3, got = 3;
-   std::string src = jit_generate_impl(p, n_tips, n_states, n_codes, first, &got);
+   std::string src = jit_generate_impl(p, n_tips, n_states, n_codes, first, &got, tabs);
    if (got != first) {
       first = got;
-      src = jit_generate_impl(p, n_tips, n_states, n_codes, first, &got);
+      src = jit_generate_impl(p, n_tips, n_states, n_codes, first, &got, tabs);
    }
    if (got != first) return std::string("#error \"jit schedule does not close\"\n");
    return src;

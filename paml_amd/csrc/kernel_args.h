@@ -52,6 +52,15 @@ struct PmatRes {
    int leaf, pad;
 };
 
+// Cherry tables (kernels_pmat.h: cherry_table_kernel) of one evaluation's P(t): one gene, K classes
+struct CherryTabArgs {
+   int n_codes, n_nodes, n_tabs;
+   long tip_words;
+   const double *pint, *ptip, *pcol;   // this evaluation's P set
+   int tabs[3 * 48];                   // [n_tabs][3]: tip a, tip b, the cherry's node (inside the arguments: nothing to upload or keep alive; 48 = CHERRY_MAX_TABS, jit.h)
+   double *ctab;                       // [K][n_tabs][n_codes * n_codes][64]
+};
+
 // Branch lengths and gene rates handed over INSIDE the kernel arguments (single evaluations of trees with up to ~440 nodes):
 // the launch itself carries them, so an evaluation needs no host-to-device copy and no staging buffer to keep alive.
 #define PMAT_INLINE_MAX 440

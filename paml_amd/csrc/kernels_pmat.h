@@ -489,4 +489,40 @@ __global__ __launch_bounds__(256) void pmat_mfma_kernel(PmatArgs a, InlineVec iv
    }
 }
 
+// Cherry tables of the per-tree 61..64-state kernel (jit.h: OP_LOOKUP).  For cherry c = (tip a, tip b, node) of class `cls`,
+//   T[ca][cb] = P(t_node) . (tipA[:, ca] o tipB[:, cb])      for every pair of character codes,
+// formed exactly as the walk forms it for a pattern with those codes: the cherry's P block, its column-60 table and the two tip
+// tables come into LDS in the layouts the walk's operand ring holds them in (global memory already has them so, as the ring's DMA
+// sources), a wave takes 16 pairs where the walk takes 16 patterns, and jit_tip2_set, jit_x60 and jit_matvec do the rest: same
+// functions, same operand order, same rank-1 seed, so a table entry has the bits the walk would compute.  Grid: (128-pair tiles,
+// cherries, classes), 8 waves; runs behind P(t) on its stream.  Row layout: jit_lookup_nc (device_common.h).
+template <bool TAIL61>
+__global__ __launch_bounds__(512) void cherry_table_kernel(CherryTabArgs a)
+{
+   extern __shared__ __attribute__((aligned(16))) double ct_lds[];
+   double *sP = ct_lds, *sA = ct_lds + 4096, *sB = ct_lds + 8192, *sC = ct_lds + 12288;
+   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, hl = lane & 15;
+   const int c = blockIdx.y, cls = blockIdx.z, nc = a.n_codes, np = nc * nc;
+   const int tip_a = a.tabs[3 * c], tip_b = a.tabs[3 * c + 1], node = a.tabs[3 * c + 2];
+   const long ps = (long)cls * a.n_nodes;
+   const double2 *gP = (const double2 *)(a.pint + (ps + node) * 4096);
+   const double2 *gA = (const double2 *)(a.ptip + (ps + tip_a) * a.tip_words), *gB = (const double2 *)(a.ptip + (ps + tip_b) * a.tip_words);
+   for (int i = tid; i < 2048; i += 512) ((double2 *)sP)[i] = gP[i];
+   for (int i = tid; i < nc * 32; i += 512) { ((double2 *)sA)[i] = gA[i]; ((double2 *)sB)[i] = gB[i]; }      // (a table holds the rows of the data set's codes)
+   if (tid < 64) sC[tid] = TAIL61 ? a.pcol[(ps + node) * 64 + tid] : 0.0;
+   __syncthreads();
+   const int pair = blockIdx.x * 128 + wave * 16 + hl;
+   const bool valid = pair < np;
+   const int pc = valid ? pair : np - 1;      // (every lane computes: the products are wave-wide)
+   v4d x[4], y[4];
+   jit_tip2_set<8>(x, sA, pc / nc, sB, pc % nc, q, lane);
+   const double x60 = TAIL61 ? jit_x60(x, lane) : 0.0;
+   jit_matvec<TAIL61, 4, 16>(sP, lane, x, y, JitNoSide(), sC, x60);
+   if (valid) {
+      part2_t *r = (part2_t *)(a.ctab + (((long)cls * a.n_tabs + c) * np + pair) * CHERRY_ROW_WORDS) + q;
+#pragma unroll
+      for (int i = 0; i < 8; i++) r[i * 4] = (part2_t){y[i >> 1][(2 * i) & 3], y[i >> 1][(2 * i + 1) & 3]};
+   }
+}
+
 }  // namespace paml_amd

@@ -29,6 +29,7 @@ EXPORTS = [
     "paml_amd_eval_batch", "paml_amd_eval_adg", "paml_amd_beb_grid", "paml_amd_beb_grid_classes", "paml_amd_compress_patterns", "paml_amd_eval_device", "paml_amd_eval_dirty", "paml_amd_eval_branch", "paml_amd_node_posterior", "paml_amd_get_pmat", "paml_amd_get_partials", "paml_amd_get_scale",
     "paml_amd_device_count", "paml_amd_set_device", "paml_amd_shard_bounds", "paml_amd_max_ranks", "paml_amd_flush", "paml_amd_eigen_status", "paml_amd_comm_unique_id", "paml_amd_comm_init", "paml_amd_comm_destroy", "paml_amd_comm_info", "paml_amd_comm_library", "paml_amd_comm_stats", "paml_amd_get_partial_sums", "paml_amd_branch_counters", "paml_amd_branch_coef_hits", "paml_amd_branch_refill_kernels", "paml_amd_branch_kernel_ms",
     "paml_amd_jit_prebuild", "paml_amd_profile", "paml_amd_profile_read", "paml_amd_counters", "paml_amd_kernel_name", "paml_amd_debug_program", "paml_amd_debug_jit",
+    "paml_amd_cherry_tables", "paml_amd_debug_jit_tables",
     "paml_amd_debug_code_order",
     "paml_amd_pairset_create", "paml_amd_pairset_destroy", "paml_amd_pairset_get_counts", "paml_amd_pairset_set_pi", "paml_amd_pairset_set_pattern",
     "paml_amd_pairset_eval", "paml_amd_pairset_failed", "paml_amd_pairset_counters",
@@ -458,6 +459,13 @@ class Engine:
         self._chk(self._L.paml_amd_profile_read(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
         return dict(ms_pmat=a.value, ms_prune=b.value, ms_reduce=c.value, n_evals=n.value)
 
+    def cherry_tables(self):
+        """(cherries tabulated, table bytes) of the last evaluation; (0, 0) when it ran without cherry tables."""
+        a, b = C.c_long(), C.c_long()
+        self._L.paml_amd_cherry_tables.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+        self._chk(self._L.paml_amd_cherry_tables(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def counters(self):
         a, b = C.c_long(), C.c_long()
         self._L.paml_amd_counters(self._h, C.byref(a), C.byref(b))
@@ -626,6 +634,26 @@ def debug_jit(tree, scale_node=None, compile=True, n_states=0, fused=None):
     if rc < 0:
         raise EngineError("debug_jit failed (%d): %s" % (rc, buf.value.decode(errors="replace")[-3000:]))
     return buf.value.decode()
+
+
+def debug_jit_tables(tree, scale_node=None, max_tabs=1 << 20):
+    """Host-only: the cherry-table form of the 61-state kernel specialised for `tree`: (source, operand stream as (is_tip, node) pairs,
+    tabulated cherries as (tip a, tip b, node) triples); at most max_tabs cherries are tabulated."""
+    L = lib()
+    ptr, flat = tree.csr()
+    sc = None if scale_node is None else np.ascontiguousarray(scale_node, dtype=np.uint8)
+    cap = 1 << 21
+    buf = C.create_string_buffer(cap)
+    stream = np.zeros(4 * tree.n_nodes + 8, dtype=np.int32)
+    tabs = np.zeros(3 * tree.n_tips + 3, dtype=np.int32)
+    ns = C.c_int()
+    L.paml_amd_debug_jit_tables.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_int,
+                                            C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_int]
+    rc = L.paml_amd_debug_jit_tables(tree.n_tips, tree.n_nodes, tree.root, _p(ptr), _p(flat), _p(sc), int(max_tabs), buf, cap,
+                                     _p(stream), len(stream), C.byref(ns), _p(tabs), len(tabs))
+    if rc < 0:
+        raise EngineError("debug_jit_tables failed (%d)" % rc)
+    return buf.value.decode(), [tuple(x) for x in stream[:2 * ns.value].reshape(-1, 2)], [tuple(x) for x in tabs[:3 * rc].reshape(-1, 3)]
 
 
 JIT_SHIPPED_DIR = os.path.join(_HERE, "lib", "jit")
