@@ -65,7 +65,7 @@ enum { PAML_AMD_MODE_LFUN = 0 /* treesub.c:7764 */, PAML_AMD_MODE_LFUNDG = 1 /* 
 int paml_amd_create(paml_amd_engine **out, int n_states, int n_tips, int n_patt, int max_classes, int n_genes,
                     unsigned flags);
 void paml_amd_destroy(paml_amd_engine *e);
-const char *paml_amd_last_error(const paml_amd_engine *e);
+const char *paml_amd_last_error(const paml_amd_engine *e);      /* e = NULL: the calling thread's last failed stand-alone entry */
 
 /* ---- Pattern shards over several GPUs (site patterns are independent given the tree, P(t), pi and the class
  * table; the reference has no counterpart — its lfun loops over all of com.npatt on one core, treesub.c:7764-7800).
@@ -385,6 +385,27 @@ const char *paml_amd_kernel_name(const paml_amd_engine *e);
  * key bytes, then run detection and a scan — HBM / latency-bound byte work.  PAML_AMD_EHIP when no device is visible. */
 int paml_amd_compress_patterns(int n_seq, int n_sites, int width, const unsigned char *chars, const int *gene, int *n_patt,
                                int *first_site, double *weights, int *pose);
+
+/* The bootstrap replicates of the tree comparison (the resampling loop of rell(), treesub.c:5844-6009: RELL and Shimodaira-Hasegawa
+ * columns of the table) on the device, stand-alone (no engine).  lnf[n_trees][n_patt] = per-pattern log likelihoods of the trees,
+ * w[n_patt] = pattern counts (non-negative integers below 2^31, at most 2^31 - 1 sites in all), gene_off = n_genes + 1 pattern
+ * offsets (NULL: one gene; a gene without sites is skipped).  Out: rep[n_rep][n_trees],
+ *     rep[r][t] = sum over the ls draws of replicate r of lnf[t][pattern(draw)],
+ * sites drawn with replacement inside each gene.  The likelihoods are re-weighted, not re-estimated, so 10 000 replicates of 10^6
+ * sites are 10^10 gathers of an n_trees-vector: the reference drops to 50 replicates at 10^5 sites, this entry does not.
+ * The draws are counter-based (a SplitMix64 finaliser of (seed, replicate, gene, draw); written out in csrc/kernels_rell.h) and
+ * the summation order is fixed (chunks of 4096 draws; no floating-point atomics): replicate r has the same bits for every n_rep,
+ * batch and call.  n_rep is walked in batches of what the workspace holds (256 MiB of chunk sums; the environment variable
+ * PAML_AMD_RELL_ARENA_MB gives another size in MiB): never PAML_AMD_ENOMEM for n_rep, only for the inputs themselves.
+ * PAML_AMD_EINVAL (message: paml_amd_last_error(NULL), per thread) for n_trees, n_patt or n_rep < 1, a weight that is negative, not
+ * an integer or >= 2^31, no sites at all, a gene_off that does not run non-decreasing from 0 to n_patt; PAML_AMD_EHIP when no device
+ * is visible. */
+int paml_amd_rell_replicates(int n_trees, int n_patt, const double *w, const double *lnf, int n_genes, const int *gene_off, int n_rep,
+                             unsigned long long seed, double *rep);
+/* Constants of the replicate kernels (draws per chunk, trees per pass), the number of batches the calling thread's last
+ * paml_amd_rell_replicates walked and the time of its replicate kernels by HIP events (ms, summed over the batches); any pointer may
+ * be NULL. */
+void paml_amd_rell_info(int *chunk, int *tree_block, int *last_batches, double *last_kernel_ms);
 
 /* ---- Pairwise maximum-likelihood comparisons (codeml runmode = -2; PairwiseCodon codeml.c:4344-4604, Goldman & Yang 1994).
  * The reference takes the ns (ns - 1) / 2 pairs one after the other, each a search over (t, kappa, omega) whose every function call

@@ -42,6 +42,15 @@ int pamlh_dnds(pamlh *p, const double *x, double *out);
  * tree, whose index goes to *best).  li, Dli, SE, pKH are deterministic; pSH and pRELL come from seeded resampling. */
 int pamlh_tree_comparison(int n_trees, int n_patt, const double *w, const double *lnf, int n_genes, const int *gene_off, int n_rep,
                           unsigned long long seed, double *li, double *dli, double *se, double *pkh, double *psh, double *prell, int *best);
+/* The table arithmetic alone, from a given replicate matrix rep[n_rep][n_trees] (rep[r][t] = log likelihood of tree t on resampled
+ * alignment r): same tie rule (within 1e-5: the replicate is shared), same per-tree centring for S-H, pKH = pSH = -1 for the best tree. */
+int pamlh_tree_comparison_from_replicates(int n_trees, int n_patt, const double *w, const double *lnf, int n_rep, const double *rep,
+                                          double *li, double *dli, double *se, double *pkh, double *psh, double *prell, int *best);
+/* pamlh_tree_comparison with the replicates drawn on the GPU (paml_amd_rell_replicates; a generator of its own, so pSH and pRELL differ
+ * from the host path's within Monte-Carlo accuracy).  n_rep = 0: 10 000 replicates at EVERY alignment length — the reference and the host
+ * path drop to 50 at 10^5 sites.  Returns 0 or the engine library's negative code (message: paml_amd_last_error(NULL)). */
+int pamlh_tree_comparison_gpu(int n_trees, int n_patt, const double *w, const double *lnf, int n_genes, const int *gene_off, int n_rep,
+                              unsigned long long seed, double *li, double *dli, double *se, double *pkh, double *psh, double *prell, int *best);
 void pamlh_free(pamlh *p);
 const char *pamlh_error(const pamlh *p);
 

@@ -109,7 +109,9 @@ void paml_amd_destroy(paml_amd_engine *e)
    delete e;
 }
 
-const char *paml_amd_last_error(const paml_amd_engine *e) { return e ? e->err.c_str() : "null engine"; }
+// e == NULL: the message of the calling thread's last failed stand-alone entry (paml_amd_rell_replicates)
+const char *paml_amd_standalone_error(void);      // engine_rell.hip; "" when there is none
+const char *paml_amd_last_error(const paml_amd_engine *e) { return e ? e->err.c_str() : *paml_amd_standalone_error() ? paml_amd_standalone_error() : "null engine"; }
 
 const char *paml_amd_kernel_name(const paml_amd_engine *e)
 {

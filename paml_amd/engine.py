@@ -33,6 +33,7 @@ EXPORTS = [
     "paml_amd_debug_code_order",
     "paml_amd_pairset_create", "paml_amd_pairset_destroy", "paml_amd_pairset_get_counts", "paml_amd_pairset_set_pi", "paml_amd_pairset_set_pattern",
     "paml_amd_pairset_eval", "paml_amd_pairset_failed", "paml_amd_pairset_counters",
+    "paml_amd_rell_replicates", "paml_amd_rell_info",
 ]
 
 
@@ -47,7 +48,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -690,6 +691,47 @@ def compress_patterns(chars, gene=None):
     if rc != 0:
         raise EngineError("paml_amd_compress_patterns failed (%d)" % rc)
     return dict(first_site=first[:npatt.value].copy(), weights=w[:npatt.value].copy(), pose=pose)
+
+
+def rell_info():
+    """Constants of the replicate kernels and the batches of this thread's last rell_replicates (paml_amd_rell_info):
+    dict(chunk, tree_block, last_batches, last_kernel_ms).  Host only."""
+    v, ms = [C.c_int() for _ in range(3)], C.c_double()
+    L = lib()
+    L.paml_amd_rell_info.argtypes = [C.POINTER(C.c_int)] * 3 + [C.POINTER(C.c_double)]
+    L.paml_amd_rell_info.restype = None
+    L.paml_amd_rell_info(*[C.byref(x) for x in v], C.byref(ms))
+    return dict(chunk=v[0].value, tree_block=v[1].value, last_batches=v[2].value, last_kernel_ms=ms.value)
+
+
+def rell_replicates(lnf, w, gene_off=None, n_rep=10000, seed=1, arena_mb=None):
+    """Bootstrap replicates of the tree comparison on the device (paml_amd_rell_replicates): lnf [n_trees][n_patt], w pattern counts,
+    gene_off n_genes + 1 pattern offsets -> rep[n_rep][n_trees].  arena_mb: size of the chunk-sum workspace for this call (the
+    library's PAML_AMD_RELL_ARENA_MB): a small one walks n_rep in several batches — same bits."""
+    lnf = np.ascontiguousarray(np.atleast_2d(lnf), dtype=np.float64)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    assert lnf.ndim == 2 and w.ndim == 1
+    n_trees, n_patt = lnf.shape
+    if w.shape[0] != n_patt:
+        raise ValueError("rell_replicates: %d weights for %d patterns" % (w.shape[0], n_patt))
+    go = None if gene_off is None else np.ascontiguousarray(gene_off, dtype=np.int32)
+    rep = np.zeros((max(int(n_rep), 0), n_trees))
+    L = lib()
+    L.paml_amd_rell_replicates.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_ulonglong, C.c_void_p]
+    old = os.environ.get("PAML_AMD_RELL_ARENA_MB")
+    if arena_mb is not None:
+        os.environ["PAML_AMD_RELL_ARENA_MB"] = repr(float(arena_mb))
+    try:
+        rc = L.paml_amd_rell_replicates(n_trees, n_patt, _p(w), _p(lnf), 1 if go is None else len(go) - 1, _p(go), int(n_rep), int(seed) & (2**64 - 1), _p(rep))
+    finally:
+        if arena_mb is not None:
+            if old is None:
+                del os.environ["PAML_AMD_RELL_ARENA_MB"]
+            else:
+                os.environ["PAML_AMD_RELL_ARENA_MB"] = old
+    if rc != 0:
+        raise EngineError("%s (code %d)" % (L.paml_amd_last_error(None).decode(), rc))
+    return rep
 
 
 def engine_for(pb: Problem, flags=0) -> Engine:

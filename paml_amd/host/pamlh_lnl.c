@@ -2,7 +2,9 @@
  *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize] [--ancestral] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
  *   (--set "key = value": replaces an option of the control file, e.g. one of the site models of an "NSsites = 0 1 2 7 8" list;
  *    --tree K: the K-th tree of the tree file, 1-based; --all-trees: every tree in turn — the reference's loop, Forestry codeml.c:635 —
- *    each optimised from the control file's initial values, then the comparison table of rell(), treesub.c:5844)
+ *    each optimised from the control file's initial values, then the comparison table of rell(), treesub.c:5844;
+ *    --all-trees --rell-gpu [--replicates N]: the table's bootstrap replicates drawn on the device, 10 000 (or N) at every alignment
+ *    length, their number printed under the table)
  * Reads the control file, the sequence and tree files it names, and the parameter vector from the command line,
  * else from in.codeml / in.baseml beside the ctl (the reference's "-1 x..." single-evaluation recipe, treesub.c:4057),
  * else the ctl's initial values; evaluates lnL through libpaml_amd.so; prints `lnL = ...` like the reference and
@@ -110,12 +112,12 @@ int main(int argc, char **argv)
    pamlh *p;
    char err[512];
    double x[4096], lnL, *lnf;
-   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0;
+   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0;
    char over[2048] = "";
    unsigned char comm_id[PAML_AMD_COMM_ID_BYTES];
    int device[MAX_RANKS];
    for (i = 0; i < MAX_RANKS; i++) device[i] = i;
-   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize] [--ancestral] [--gpus N] [--tree K | --all-trees] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
+   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize] [--ancestral] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
    for (i = 3; i < argc && nx < 4096; i++) {
       if (!strcmp(argv[i], "--optimize")) optimize = 1;
       else if (!strcmp(argv[i], "--ancestral")) ancestral = 1;
@@ -127,6 +129,8 @@ int main(int argc, char **argv)
       }
       else if (!strcmp(argv[i], "--tree") && i + 1 < argc) itree = atoi(argv[++i]) - 1;
       else if (!strcmp(argv[i], "--all-trees")) all_trees = 1;
+      else if (!strcmp(argv[i], "--rell-gpu")) rell_gpu = 1;      /* with --all-trees: the bootstrap replicates of the table on the device */
+      else if (!strcmp(argv[i], "--replicates") && i + 1 < argc) replicates = atoi(argv[++i]);
       else if (!strcmp(argv[i], "--set") && i + 1 < argc) {      /* --set "NSsites = 2": replaces the control file's option */
          if (strlen(over) + strlen(argv[i + 1]) + 2 >= sizeof(over)) { fprintf(stderr, "error: too many --set options\n"); return 2; }
          strcat(over, argv[++i]); strcat(over, "\n");
@@ -159,10 +163,17 @@ int main(int argc, char **argv)
       if (nt > 1) {
          int best = 0;
          res = (double *)malloc((size_t)6 * nt * sizeof(double));
-         if (pamlh_tree_comparison(nt, npt, w, all, ng, goff, 0, 20260927ULL, res, res + nt, res + 2 * nt, res + 3 * nt, res + 4 * nt, res + 5 * nt, &best)) return 1;
+         if (rell_gpu) {
+            if (pamlh_tree_comparison_gpu(nt, npt, w, all, ng, goff, replicates, 20260927ULL, res, res + nt, res + 2 * nt, res + 3 * nt, res + 4 * nt, res + 5 * nt, &best)) {
+               fprintf(stderr, "error: %s\n", paml_amd_last_error(NULL));
+               return 1;
+            }
+         }
+         else if (pamlh_tree_comparison(nt, npt, w, all, ng, goff, 0, 20260927ULL, res, res + nt, res + 2 * nt, res + 3 * nt, res + 4 * nt, res + 5 * nt, &best)) return 1;
          printf("\nTree comparisons (Kishino & Hasegawa 1989; Shimodaira & Hasegawa 1999)\n\n%6s %12s %9s %9s%8s%10s%9s\n\n", "tree", "li", "Dli", " +- SE", "pKH", "pSH", "pRELL");
          for (t = 0; t < nt; t++)
             printf("%6d%c%12.3f %9.3f %9.3f%8.3f%10.3f%9.3f\n", t + 1, t == best ? '*' : ' ', res[t], res[nt + t], res[2 * nt + t], res[3 * nt + t], res[4 * nt + t], res[5 * nt + t]);
+         if (rell_gpu) printf("\npSH and pRELL from %d bootstrap replicates drawn on the GPU\n", replicates > 0 ? replicates : 10000);
          free(res);
       }
       free(all); free(w);

@@ -877,18 +877,18 @@ static unsigned long long tc_next(void)
    tc_s[3] = tc_s[3] << 45 | tc_s[3] >> 19;
    return r;
 }
-int pamlh_tree_comparison(int n_trees, int n_patt, const double *w, const double *lnf, int n_genes, const int *gene_off, int n_rep,
-                          unsigned long long seed, double *li, double *dli, double *se, double *pkh, double *psh, double *prell, int *best)
+/* every column of the table from a given replicate matrix rep[n_rep][n_trees] (rep[r][t] = the log likelihood of tree t on the
+ * resampled alignment r): the tie rule (trees within 1e-5 of the best share a replicate), the per-tree centring of S-H and
+ * pKH = pSH = -1 for the best tree are those of rell() */
+int pamlh_tree_comparison_from_replicates(int n_trees, int n_patt, const double *w, const double *lnf, int n_rep, const double *rep,
+                                          double *li, double *dli, double *se, double *pkh, double *psh, double *prell, int *best)
 {
-   int t, h, r, g, k, ml = 0, nbest, one_gene[2];
+   int t, h, r, ml = 0, nbest;
    long ls = 0;
-   double *rep, *mx, y;
-   int *sitelist, *cnt, *btrees;
-   if (n_trees < 2 || n_patt < 1 || !w || !lnf || n_genes < 1) return -1;
-   one_gene[0] = 0; one_gene[1] = n_patt;
-   if (!gene_off) { gene_off = one_gene; n_genes = 1; }
+   double *cen, *mx, y;
+   int *btrees;
+   if (n_trees < 2 || n_patt < 1 || n_rep < 1 || !w || !lnf || !rep) return -1;
    for (h = 0; h < n_patt; h++) ls += (long)w[h];
-   if (n_rep <= 0) n_rep = ls < 100000 ? 10000 : 50;
    for (t = 0; t < n_trees; t++) {
       for (h = 0, li[t] = 0; h < n_patt; h++) li[t] += w[h] * lnf[(size_t)t * n_patt + h];
       if (t && li[t] > li[ml]) ml = t;
@@ -904,14 +904,49 @@ int pamlh_tree_comparison(int n_trees, int n_patt, const double *w, const double
       pkh[t] = (t == ml || fabs(se[t]) < 1e-6) ? -1 : 1 - pamlh_cdf_normal(-dli[t] / se[t]);
       prell[t] = psh[t] = 0;
    }
+   cen = (double *)malloc((size_t)n_trees * n_rep * sizeof(double));
+   mx = (double *)malloc(n_rep * sizeof(double));
+   btrees = (int *)malloc(n_trees * sizeof(int));
+   for (r = 0; r < n_rep; r++) {
+      const double *row = rep + (size_t)r * n_trees;
+      for (t = 1, nbest = 1, btrees[0] = 0, y = row[0]; t < n_trees; t++) {
+         if (fabs(row[t] - y) < 1e-5) btrees[nbest++] = t;
+         else if (row[t] > y) { nbest = 1; btrees[0] = t; y = row[t]; }
+      }
+      for (t = 0; t < nbest; t++) prell[btrees[t]] += 1.0 / ((double)n_rep * nbest);
+   }
+   for (t = 0; t < n_trees; t++) {      /* S-H: centre each tree's replicates */
+      for (r = 0, y = 0; r < n_rep; r++) y += rep[(size_t)r * n_trees + t];
+      for (r = 0, y /= n_rep; r < n_rep; r++) cen[(size_t)r * n_trees + t] = rep[(size_t)r * n_trees + t] - y;
+   }
+   for (r = 0; r < n_rep; r++) for (t = 1, mx[r] = cen[(size_t)r * n_trees]; t < n_trees; t++) if (cen[(size_t)r * n_trees + t] > mx[r]) mx[r] = cen[(size_t)r * n_trees + t];
+   for (t = 0; t < n_trees; t++) {
+      for (r = 0; r < n_rep; r++) if (mx[r] - cen[(size_t)r * n_trees + t] > li[ml] - li[t]) psh[t] += 1.0 / n_rep;
+      if (t == ml || fabs(se[t]) < 1e-6) psh[t] = -1;
+   }
+   if (best) *best = ml;
+   free(cen); free(mx); free(btrees);
+   return 0;
+}
+
+int pamlh_tree_comparison(int n_trees, int n_patt, const double *w, const double *lnf, int n_genes, const int *gene_off, int n_rep,
+                          unsigned long long seed, double *li, double *dli, double *se, double *pkh, double *psh, double *prell, int *best)
+{
+   int t, h, r, g, k, rc, one_gene[2];
+   long ls = 0;
+   double *rep;
+   int *sitelist, *cnt;
+   if (n_trees < 2 || n_patt < 1 || !w || !lnf || n_genes < 1) return -1;
+   one_gene[0] = 0; one_gene[1] = n_patt;
+   if (!gene_off) { gene_off = one_gene; n_genes = 1; }
+   for (h = 0; h < n_patt; h++) ls += (long)w[h];
+   if (n_rep <= 0) n_rep = ls < 100000 ? 10000 : 50;
    /* bootstrap: sites drawn with replacement inside every gene */
    {  unsigned long long z = seed + 0x9E3779B97F4A7C15ULL;
       for (k = 0; k < 4; k++) { unsigned long long v = (z += 0x9E3779B97F4A7C15ULL); v = (v ^ v >> 30) * 0xBF58476D1CE4E5B9ULL; v = (v ^ v >> 27) * 0x94D049BB133111EBULL; tc_s[k] = v ^ v >> 31; } }
    rep = (double *)calloc((size_t)n_trees * n_rep, sizeof(double));
-   mx = (double *)malloc(n_rep * sizeof(double));
    sitelist = (int *)malloc((size_t)ls * sizeof(int));
    cnt = (int *)malloc(n_patt * sizeof(int));
-   btrees = (int *)malloc(n_trees * sizeof(int));
    for (h = 0, k = 0; h < n_patt; h++) for (r = 0; r < (int)w[h]; r++) sitelist[k++] = h;
    for (r = 0; r < n_rep; r++) {
       long s0 = 0;
@@ -923,23 +958,26 @@ int pamlh_tree_comparison(int n_trees, int n_patt, const double *w, const double
          s0 += lg;
       }
       for (h = 0; h < n_patt; h++)
-         if (cnt[h]) for (t = 0; t < n_trees; t++) rep[(size_t)t * n_rep + r] += cnt[h] * lnf[(size_t)t * n_patt + h];
-      for (t = 1, nbest = 1, btrees[0] = 0, y = rep[r]; t < n_trees; t++) {
-         if (fabs(rep[(size_t)t * n_rep + r] - y) < 1e-5) btrees[nbest++] = t;
-         else if (rep[(size_t)t * n_rep + r] > y) { nbest = 1; btrees[0] = t; y = rep[(size_t)t * n_rep + r]; }
-      }
-      for (t = 0; t < nbest; t++) prell[btrees[t]] += 1.0 / ((double)n_rep * nbest);
+         if (cnt[h]) for (t = 0; t < n_trees; t++) rep[(size_t)r * n_trees + t] += cnt[h] * lnf[(size_t)t * n_patt + h];
    }
-   for (t = 0; t < n_trees; t++) {      /* S-H: centre each tree's replicates */
-      for (r = 0, y = 0; r < n_rep; r++) y += rep[(size_t)t * n_rep + r];
-      for (r = 0, y /= n_rep; r < n_rep; r++) rep[(size_t)t * n_rep + r] -= y;
-   }
-   for (r = 0; r < n_rep; r++) for (t = 1, mx[r] = rep[r]; t < n_trees; t++) if (rep[(size_t)t * n_rep + r] > mx[r]) mx[r] = rep[(size_t)t * n_rep + r];
-   for (t = 0; t < n_trees; t++) {
-      for (r = 0; r < n_rep; r++) if (mx[r] - rep[(size_t)t * n_rep + r] > li[ml] - li[t]) psh[t] += 1.0 / n_rep;
-      if (t == ml || fabs(se[t]) < 1e-6) psh[t] = -1;
-   }
-   if (best) *best = ml;
-   free(rep); free(mx); free(sitelist); free(cnt); free(btrees);
-   return 0;
+   rc = pamlh_tree_comparison_from_replicates(n_trees, n_patt, w, lnf, n_rep, rep, li, dli, se, pkh, psh, prell, best);
+   free(rep); free(sitelist); free(cnt);
+   return rc;
+}
+
+/* the same table with the replicates drawn on the device (paml_amd_rell_replicates: its own counter-based generator); n_rep = 0:
+ * 10 000 replicates at every alignment length.  Returns the engine library's code (message: paml_amd_last_error(NULL)). */
+int pamlh_tree_comparison_gpu(int n_trees, int n_patt, const double *w, const double *lnf, int n_genes, const int *gene_off, int n_rep,
+                              unsigned long long seed, double *li, double *dli, double *se, double *pkh, double *psh, double *prell, int *best)
+{
+   double *rep;
+   int rc;
+   if (n_trees < 2 || n_patt < 1 || !w || !lnf || n_genes < 1) return -1;
+   if (n_rep <= 0) n_rep = 10000;
+   rep = (double *)malloc((size_t)n_trees * n_rep * sizeof(double));
+   if (!rep) return -2;
+   rc = paml_amd_rell_replicates(n_trees, n_patt, w, lnf, n_genes, gene_off, n_rep, seed, rep);
+   if (!rc) rc = pamlh_tree_comparison_from_replicates(n_trees, n_patt, w, lnf, n_rep, rep, li, dli, se, pkh, psh, prell, best);
+   free(rep);
+   return rc;
 }

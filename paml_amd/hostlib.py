@@ -73,8 +73,9 @@ def _arr(ptr, dtype, n):
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=(n,)).copy()
 
 
-def tree_comparison(lnf, w, gene_off=None, n_rep=0, seed=1):
-    """pamlh_tree_comparison: lnf [n_trees][n_patt], w pattern counts -> dict of li, dli, se, pKH, pSH, pRELL (arrays) and best."""
+def tree_comparison(lnf, w, gene_off=None, n_rep=0, seed=1, device=False):
+    """pamlh_tree_comparison: lnf [n_trees][n_patt], w pattern counts -> dict of li, dli, se, pKH, pSH, pRELL (arrays) and best.
+    device=True: pamlh_tree_comparison_gpu — the replicates are drawn on the GPU, n_rep = 0 means 10 000 at every alignment length."""
     L = lib()
     lnf = np.ascontiguousarray(lnf, dtype=np.float64)
     w = np.ascontiguousarray(w, dtype=np.float64)
@@ -83,11 +84,33 @@ def tree_comparison(lnf, w, gene_off=None, n_rep=0, seed=1):
     out = [np.zeros(nt) for _ in range(6)]
     best = C.c_int()
     dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))      # noqa: E731
-    L.pamlh_tree_comparison.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_int, C.c_ulonglong] + [C.POINTER(C.c_double)] * 6 + [C.POINTER(C.c_int)]
-    rc = L.pamlh_tree_comparison(nt, npatt, dp(w), dp(lnf), (len(go) - 1) if go is not None else 1, go.ctypes.data if go is not None else None, n_rep, seed,
-                                 *[dp(a) for a in out], C.byref(best))
+    fn = L.pamlh_tree_comparison_gpu if device else L.pamlh_tree_comparison
+    fn.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_int, C.c_ulonglong] + [C.POINTER(C.c_double)] * 6 + [C.POINTER(C.c_int)]
+    rc = fn(nt, npatt, dp(w), dp(lnf), (len(go) - 1) if go is not None else 1, go.ctypes.data if go is not None else None, n_rep, seed,
+            *[dp(a) for a in out], C.byref(best))
+    if rc != 0 and device:
+        from . import engine
+        E = engine.lib()
+        raise RuntimeError("pamlh_tree_comparison_gpu: %s (code %d)" % (E.paml_amd_last_error(None).decode(), rc))
     if rc != 0:
         raise RuntimeError("pamlh_tree_comparison: bad arguments")
+    return dict(zip(("li", "dli", "se", "pKH", "pSH", "pRELL"), out), best=best.value)
+
+
+def tree_comparison_from_replicates(lnf, w, rep):
+    """pamlh_tree_comparison_from_replicates: the table's columns from a given replicate matrix rep[n_rep][n_trees]."""
+    L = lib()
+    lnf = np.ascontiguousarray(lnf, dtype=np.float64)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    rep = np.ascontiguousarray(rep, dtype=np.float64)
+    nt, npatt = lnf.shape
+    assert rep.ndim == 2 and rep.shape[1] == nt
+    out = [np.zeros(nt) for _ in range(6)]
+    best = C.c_int()
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))      # noqa: E731
+    L.pamlh_tree_comparison_from_replicates.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)] + [C.POINTER(C.c_double)] * 6 + [C.POINTER(C.c_int)]
+    if L.pamlh_tree_comparison_from_replicates(nt, npatt, dp(w), dp(lnf), rep.shape[0], dp(rep), *[dp(a) for a in out], C.byref(best)) != 0:
+        raise RuntimeError("pamlh_tree_comparison_from_replicates: bad arguments")
     return dict(zip(("li", "dli", "se", "pKH", "pSH", "pRELL"), out), best=best.value)
 
 

@@ -9,7 +9,7 @@ mkdir -p paml_amd/lib/exp
 python -c "from paml_amd import engine; engine.build()"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -c paml_amd/csrc/$unit.hip -o paml_amd/lib/exp/${unit}_$name.o
 objs=""
-for u in engine_core engine_comm engine_eval engine_branch engine_beb engine_jitdbg engine_compress; do
+for u in engine_core engine_comm engine_eval engine_branch engine_beb engine_jitdbg engine_compress engine_pairwise engine_rell; do
   if [ $u = $unit ]; then objs="$objs paml_amd/lib/exp/${unit}_$name.o"; else objs="$objs paml_amd/lib/obj/$u.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o paml_amd/lib/exp/libpaml_amd_$name.so $objs -lhiprtc -ldl
