@@ -407,6 +407,29 @@ int paml_amd_rell_replicates(int n_trees, int n_patt, const double *w, const dou
  * be NULL. */
 void paml_amd_rell_info(int *chunk, int *tree_block, int *last_batches, double *last_kernel_ms);
 
+/* Alignments drawn under the engine's model on the device: the role of Evolve / Simulate (evolver.c:737-805, 818).  Needs set_tree,
+ * set_pi, set_classes and the eigen sets they refer to; needs no tips and leaves tips alone.  For each of n_sites sites a class is
+ * drawn from freqK, a root state from pi, and along every branch, in pre-order, the state at its lower end from the row of P(t) of the
+ * site's class — the matrices an evaluation at (branch[n_nodes], gene_rate[1] or NULL = 1) would build, by the same kernels; afterwards
+ * paml_amd_get_pmat returns them (branch-local state of eval_branch starts over).  Out: z[n_tips][n_sites] states 0 .. n-1; cls[n_sites]
+ * the sites' classes and anc[n_nodes - n_tips][n_sites] the states at the internal nodes (either may be NULL).  A root that is a tip
+ * gets its drawn state as its sequence.
+ * The draws are counter-based (a SplitMix64 finaliser of (seed, replicate, global site index first_site + j, draw); the whole definition,
+ * inverse CDFs included, is written out in csrc/kernels_simulate.h): site first_site + j has the same bytes in whatever call, batch or
+ * company it is drawn, so callers shard a long alignment by first_site — an engine with a communicator simulates locally.  n_sites is
+ * walked in batches of what the workspace of state bytes holds (256 MiB; the environment variable PAML_AMD_SIM_ARENA_MB gives another
+ * size in MiB): never PAML_AMD_ENOMEM for n_sites.  Synchronous.
+ * PAML_AMD_EINVAL for n_sites < 1, first_site < 0, a null z or branch, a model that is not set yet; PAML_AMD_EUNSUPPORTED for an engine
+ * of several genes (a stated limit: one gene) or class rates per gene; PAML_AMD_ENOCONV when a device eigen-decomposition queued in
+ * front of it reached its sweep limit. */
+int paml_amd_simulate(paml_amd_engine *e, const double *branch, const double *gene_rate, long n_sites, long first_site,
+                      unsigned long long seed, unsigned replicate,
+                      unsigned char *z /* [n_tips][n_sites] states 0..n-1 */,
+                      unsigned char *cls /* [n_sites] or NULL */, unsigned char *anc /* [n_nodes - n_tips][n_sites] or NULL */);
+/* The number of batches the calling thread's last paml_amd_simulate walked and the time of its kernels (P(t), the cumulative tables,
+ * the walk) by HIP events (ms, summed over the batches); either pointer may be NULL. */
+void paml_amd_simulate_info(int *last_batches, double *last_kernel_ms);
+
 /* ---- Pairwise maximum-likelihood comparisons (codeml runmode = -2; PairwiseCodon codeml.c:4344-4604, Goldman & Yang 1994).
  * The reference takes the ns (ns - 1) / 2 pairs one after the other, each a search over (t, kappa, omega) whose every function call
  * (lfun2dSdN codeml.c:4219-4264) decomposes a rate matrix on one core.  Here a PAIR SET lives on an engine whose tips are clean data

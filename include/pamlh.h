@@ -188,6 +188,17 @@ int pamlh_pairwise_freqs(const pamlh *p, const double *fp, double ls, double *pi
 int pamlh_pairwise_write(pamlh *p, const double *out, const char *dir);
 const char *pamlh_seq_name(const pamlh *p, int i);
 
+/* Simulation under the analysis's model on the GPU (the job of evolver: Simulate evolver.c:818, Evolve 753; paml_amd_simulate).
+ * pamlh_simulate: SetParameters(x) (x = NULL: the model state as it stands), the model to the engine as pamlh_eval_gpu sends it, then
+ *   n_sites sites (0: the alignment's own length) drawn with the branch vector an evaluation would get: z[n_tips][n_sites] states
+ *   0 .. n_states - 1, cls[n_sites] the sites' classes (may be NULL).  (seed, replicate) name the data set: the same bytes every time.
+ *   Refused with a message: several genes, rho (rates correlated along the sequence are not independent per site), runmode = -2.
+ * pamlh_write_alignment (host only): z as a sequential PHYLIP file that this library and the reference read — names from
+ *   pamlh_seq_name, nucleotides in T, C, A, G order, amino acids in the reference's order, codons as the triplets of the analysis's
+ *   genetic code (state k = the k-th sense codon). */
+int pamlh_simulate(pamlh *p, const double *x, long n_sites, unsigned long long seed, unsigned replicate, unsigned char *z, unsigned char *cls);
+int pamlh_write_alignment(const pamlh *p, const unsigned char *z, long n_sites, const char *path);
+
 /* Write the reference's `lnf` file layout (print_lnf_site treesub.c:7598) for the last pamlh_eval_gpu. */
 int pamlh_write_lnf(const pamlh *p, const char *path, const double *lnf);
 

@@ -28,25 +28,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "kernels_rng.h"      // rell_mix, rell_stream, RELL_GAMMA: shared with kernels_simulate.h
+
 namespace paml_amd {
 
 #define RELL_CHUNK 4096           // draws per (replicate, chunk) = per wave
 #define RELL_TREE_BLOCK 8         // trees per pass over the draws
 #define RELL_THREADS 256
 #define RELL_SCAN_TILE 2048
-#define RELL_GAMMA 0x9E3779B97F4A7C15ULL
-
-__host__ __device__ __forceinline__ unsigned long long rell_mix(unsigned long long z)
-{
-   z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9ULL;
-   z = (z ^ z >> 27) * 0x94D049BB133111EBULL;
-   return z ^ z >> 31;
-}
-
-__host__ __device__ __forceinline__ unsigned long long rell_stream(unsigned long long seed, unsigned r, unsigned g)
-{
-   return rell_mix(seed + RELL_GAMMA * ((((unsigned long long)r << 32) | g) + 1ULL));
-}
 
 // ---- site list: inclusive scan of the integer weights, then one thread per site ----
 __global__ __launch_bounds__(RELL_THREADS) void rell_tile_sums(const int *w, int n, int *sums)

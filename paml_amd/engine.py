@@ -34,6 +34,7 @@ EXPORTS = [
     "paml_amd_pairset_create", "paml_amd_pairset_destroy", "paml_amd_pairset_get_counts", "paml_amd_pairset_set_pi", "paml_amd_pairset_set_pattern",
     "paml_amd_pairset_eval", "paml_amd_pairset_failed", "paml_amd_pairset_counters",
     "paml_amd_rell_replicates", "paml_amd_rell_info",
+    "paml_amd_simulate", "paml_amd_simulate_info",
 ]
 
 
@@ -48,7 +49,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -437,6 +438,20 @@ class Engine:
         self._chk(self._L.paml_amd_node_posterior(self._h, int(node), _p(b), _p(g), _p(post)))
         return post
 
+    def simulate(self, branch, n_sites, seed=1, replicate=0, first_site=0, gene_rate=None, want_classes=False, want_ancestors=False):
+        """Draw n_sites sites under the loaded model (paml_amd_simulate): dict(z=[n_tips][n_sites] uint8 states, cls=[n_sites] or
+        None, anc=[n_nodes - n_tips][n_sites] or None).  Site first_site + j is a pure function of (seed, replicate, first_site + j)."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        n_sites = int(n_sites)
+        m = max(n_sites, 0)
+        z = np.zeros((self.n_tips, m), dtype=np.uint8)
+        cls = np.zeros(m, dtype=np.uint8) if want_classes else None
+        anc = np.zeros((max(self.n_nodes - self.n_tips, 0), m), dtype=np.uint8) if want_ancestors else None
+        self._L.paml_amd_simulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_ulonglong, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self._L.paml_amd_simulate(self._h, _p(b), _p(g), n_sites, int(first_site), int(seed) & (2**64 - 1), int(replicate), _p(z), _p(cls), _p(anc)))
+        return dict(z=z, cls=cls, anc=anc)
+
     def get_pmat(self, gene, iclass, node):
         P = np.zeros((self.n, self.n))
         self._chk(self._L.paml_amd_get_pmat(self._h, gene, iclass, node, _p(P)))
@@ -702,6 +717,17 @@ def rell_info():
     L.paml_amd_rell_info.restype = None
     L.paml_amd_rell_info(*[C.byref(x) for x in v], C.byref(ms))
     return dict(chunk=v[0].value, tree_block=v[1].value, last_batches=v[2].value, last_kernel_ms=ms.value)
+
+
+def simulate_info():
+    """Batches walked by this thread's last Engine.simulate and the time of its kernels by HIP events (paml_amd_simulate_info):
+    dict(last_batches, last_kernel_ms)."""
+    L = lib()
+    nb, ms = C.c_int(), C.c_double()
+    L.paml_amd_simulate_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.paml_amd_simulate_info.restype = None
+    L.paml_amd_simulate_info(C.byref(nb), C.byref(ms))
+    return dict(last_batches=nb.value, last_kernel_ms=ms.value)
 
 
 def rell_replicates(lnf, w, gene_off=None, n_rep=10000, seed=1, arena_mb=None):

@@ -4,7 +4,11 @@
  *    --tree K: the K-th tree of the tree file, 1-based; --all-trees: every tree in turn — the reference's loop, Forestry codeml.c:635 —
  *    each optimised from the control file's initial values, then the comparison table of rell(), treesub.c:5844;
  *    --all-trees --rell-gpu [--replicates N]: the table's bootstrap replicates drawn on the device, 10 000 (or N) at every alignment
- *    length, their number printed under the table)
+ *    length, their number printed under the table;
+ *    --simulate OUT [--sites N] [--seed S] [--replicates R]: instead of the evaluation, R (default 1) alignments of N sites (default: the
+ *    alignment's own length) drawn on the GPU under the model at the parameter vector the driver would otherwise evaluate — the control
+ *    file's initial values, in.codeml / in.baseml, the command line's, or the estimates after --optimize — written as sequential PHYLIP
+ *    to OUT, or OUT.0000, OUT.0001 ... for R > 1: the parametric bootstrap's data sets, the job of evolver (evolver.c:818))
  * Reads the control file, the sequence and tree files it names, and the parameter vector from the command line,
  * else from in.codeml / in.baseml beside the ctl (the reference's "-1 x..." single-evaluation recipe, treesub.c:4057),
  * else the ctl's initial values; evaluates lnL through libpaml_amd.so; prints `lnL = ...` like the reference and
@@ -114,10 +118,13 @@ int main(int argc, char **argv)
    double x[4096], lnL, *lnf;
    int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0;
    char over[2048] = "";
+   const char *sim_out = NULL;
+   long sim_sites = 0;
+   unsigned long long sim_seed = 1;
    unsigned char comm_id[PAML_AMD_COMM_ID_BYTES];
    int device[MAX_RANKS];
    for (i = 0; i < MAX_RANKS; i++) device[i] = i;
-   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize] [--ancestral] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
+   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize] [--ancestral] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
    for (i = 3; i < argc && nx < 4096; i++) {
       if (!strcmp(argv[i], "--optimize")) optimize = 1;
       else if (!strcmp(argv[i], "--ancestral")) ancestral = 1;
@@ -131,6 +138,9 @@ int main(int argc, char **argv)
       else if (!strcmp(argv[i], "--all-trees")) all_trees = 1;
       else if (!strcmp(argv[i], "--rell-gpu")) rell_gpu = 1;      /* with --all-trees: the bootstrap replicates of the table on the device */
       else if (!strcmp(argv[i], "--replicates") && i + 1 < argc) replicates = atoi(argv[++i]);
+      else if (!strcmp(argv[i], "--simulate") && i + 1 < argc) sim_out = argv[++i];
+      else if (!strcmp(argv[i], "--sites") && i + 1 < argc) sim_sites = atol(argv[++i]);
+      else if (!strcmp(argv[i], "--seed") && i + 1 < argc) sim_seed = strtoull(argv[++i], NULL, 10);
       else if (!strcmp(argv[i], "--set") && i + 1 < argc) {      /* --set "NSsites = 2": replaces the control file's option */
          if (strlen(over) + strlen(argv[i + 1]) + 2 >= sizeof(over)) { fprintf(stderr, "error: too many --set options\n"); return 2; }
          strcat(over, argv[++i]); strcat(over, "\n");
@@ -254,6 +264,27 @@ int main(int argc, char **argv)
          }
          free(se);
       }
+   }
+   if (sim_out) {      /* the data sets of a parametric bootstrap instead of the evaluation */
+      int ns = 0, n_pose = 0, r;
+      const int nrep = replicates > 0 ? replicates : 1;
+      unsigned char *zs;
+      if (gpus > 0) { fprintf(stderr, "error: --simulate runs on one GPU\n"); return 1; }
+      pamlh_dims(p, NULL, &ns, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL);
+      pamlh_pose(p, &n_pose);
+      if (sim_sites < 1) sim_sites = n_pose;
+      zs = (unsigned char *)malloc((size_t)ns * sim_sites);
+      for (r = 0; r < nrep; r++) {
+         char path[4096];
+         if (nrep == 1) snprintf(path, sizeof(path), "%s", sim_out); else snprintf(path, sizeof(path), "%s.%04d", sim_out, r);
+         if (pamlh_simulate(p, x, sim_sites, sim_seed, (unsigned)r, zs, NULL) || pamlh_write_alignment(p, zs, sim_sites, path)) {
+            fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1;
+         }
+         printf("simulated %d sequences x %ld sites (seed %llu, replicate %d) -> %s\n", ns, sim_sites, sim_seed, r, path);
+      }
+      free(zs);
+      pamlh_free(p);
+      return 0;
    }
    if (pamlh_set_x(p, x, np)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
    lnf = (double *)malloc(npatt * sizeof(double));

@@ -20,7 +20,7 @@ DRIVER_PATH = os.path.join(_HERE, "lib", "pamlh_lnl")
 def build(force=False):
     from . import engine
     engine.build()
-    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
+    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "pamlh.h"))
     if force or not (os.path.exists(LIB_PATH) and os.path.exists(DRIVER_PATH)) or \
             any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
@@ -221,6 +221,31 @@ class Analysis:
             self.close()
         except Exception:
             pass
+
+    def simulate(self, x=None, n_sites=None, seed=1, replicate=0):
+        """Draw an alignment under the model at x (None: the model state as it stands) on the GPU (pamlh_simulate): dict(z=[n_tips]
+        [n_sites] uint8 states, cls=[n_sites] site classes).  n_sites None: the alignment's own length."""
+        if n_sites is None:
+            n_sites = len(self.pose())
+        n_sites = int(n_sites)
+        xa = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
+        if xa is not None and len(xa) != self.np:
+            raise ValueError("simulate: %d values for %d parameters" % (len(xa), self.np))
+        z = np.zeros((self.n_tips, max(n_sites, 0)), dtype=np.uint8)
+        cls = np.zeros(max(n_sites, 0), dtype=np.uint8)
+        self._L.pamlh_simulate.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_ulonglong, C.c_uint, C.c_void_p, C.c_void_p]
+        if self._L.pamlh_simulate(self._h, None if xa is None else xa.ctypes.data_as(C.c_void_p), n_sites, int(seed) & (2**64 - 1), int(replicate),
+                                  z.ctypes.data_as(C.c_void_p), cls.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_simulate: " + self._L.pamlh_error(self._h).decode())
+        return dict(z=z, cls=cls)
+
+    def write_alignment(self, z, path):
+        """States z[n_tips][n_sites] as a sequential PHYLIP file (pamlh_write_alignment; host only)."""
+        z = np.ascontiguousarray(z, dtype=np.uint8)
+        assert z.ndim == 2 and z.shape[0] == self.n_tips
+        self._L.pamlh_write_alignment.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_char_p]
+        if self._L.pamlh_write_alignment(self._h, z.ctypes.data_as(C.c_void_p), z.shape[1], os.fsencode(path)) != 0:
+            raise RuntimeError("pamlh_write_alignment: " + self._L.pamlh_error(self._h).decode())
 
     def default_x(self):
         x = np.zeros(max(1, self.np))
