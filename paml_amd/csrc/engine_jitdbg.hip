@@ -6,14 +6,11 @@
 // PAML_AMD_PREBUILD_GENES=G (G > 1): the several-genes form of the 4- / 5-state fused kernel and of the 20-state matrix-core kernel
 static int prebuild_genes() { const char *v = getenv("PAML_AMD_PREBUILD_GENES"); return v && atoi(v) > 1 ? atoi(v) : 1; }
 
-extern "C" {
-
-int paml_amd_debug_program(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons,
-                           const unsigned char *scale_node, int keep_partials, const unsigned char *clean,
-                           int *ops_out, int cap, int *max_stack)
+// The tree of the entry points below, from its sons in CSR form; false: the arguments do not describe one
+static bool tree_from_csr(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node, TreeDesc *out)
 {
-   if (!sons_ptr || !sons || n_nodes <= 0 || root < 0 || root >= n_nodes) return PAML_AMD_EINVAL;
-   TreeDesc t;
+   if (!sons_ptr || !sons || n_nodes <= 0 || root < 0 || root >= n_nodes) return false;
+   TreeDesc &t = *out;
    t.n_tips = n_tips; t.n_nodes = n_nodes; t.root = root;
    t.sons_ptr.assign(sons_ptr, sons_ptr + n_nodes + 1);
    t.sons.assign(sons, sons + sons_ptr[n_nodes]);
@@ -23,6 +20,17 @@ int paml_amd_debug_program(int n_tips, int n_nodes, int root, const int *sons_pt
    if (scale_node)
       for (int i = 0; i < n_nodes; i++)
          if (scale_node[i]) { t.scale_node[i] = 1; t.scale_slot[i] = t.n_scale++; }
+   return true;
+}
+
+extern "C" {
+
+int paml_amd_debug_program(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons,
+                           const unsigned char *scale_node, int keep_partials, const unsigned char *clean,
+                           int *ops_out, int cap, int *max_stack)
+{
+   TreeDesc t;
+   if (!tree_from_csr(n_tips, n_nodes, root, sons_ptr, sons, scale_node, &t)) return PAML_AMD_EINVAL;
    Program p = build_program(t, keep_partials != 0, clean);
    if (max_stack) *max_stack = p.max_stack;
    if (ops_out)
@@ -56,17 +64,8 @@ int paml_amd_debug_code_order(int n_states, int n_codes, const int *n_chara, con
 int paml_amd_debug_jit(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons,
                        const unsigned char *scale_node, char *text_out, int cap, int compile)
 {
-   if (!sons_ptr || !sons || n_nodes <= 0 || root < 0 || root >= n_nodes) return PAML_AMD_EINVAL;
    TreeDesc t;
-   t.n_tips = n_tips; t.n_nodes = n_nodes; t.root = root;
-   t.sons_ptr.assign(sons_ptr, sons_ptr + n_nodes + 1);
-   t.sons.assign(sons, sons + sons_ptr[n_nodes]);
-   t.label.assign(n_nodes, 0);
-   t.scale_node.assign(n_nodes, 0);
-   t.scale_slot.assign(n_nodes, -1);
-   if (scale_node)
-      for (int i = 0; i < n_nodes; i++)
-         if (scale_node[i]) { t.scale_node[i] = 1; t.scale_slot[i] = t.n_scale++; }
+   if (!tree_from_csr(n_tips, n_nodes, root, sons_ptr, sons, scale_node, &t)) return PAML_AMD_EINVAL;
    Program p = build_program(t, false, nullptr);
    const int fusedK = (compile & 2) ? (compile >> 16) & 0xff : 0, fusedNC = (compile >> 24) & 0xff;      // bit 1: the fused 4 / 5-state kernel
    int n_states = (compile >> 8) & 0xff;    // 0: the 61-state kernel; 4 / 5 / 20: the one-pattern-per-lane kernels;
@@ -118,17 +117,8 @@ int paml_amd_debug_jit(int n_tips, int n_nodes, int root, const int *sons_ptr, c
 int paml_amd_debug_jit_tables(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node,
                               int max_tabs, char *text_out, int cap, int *stream_out, int stream_cap, int *n_stream, int *tabs_out, int tabs_cap)
 {
-   if (!sons_ptr || !sons || n_nodes <= 0 || root < 0 || root >= n_nodes) return PAML_AMD_EINVAL;
    TreeDesc t;
-   t.n_tips = n_tips; t.n_nodes = n_nodes; t.root = root;
-   t.sons_ptr.assign(sons_ptr, sons_ptr + n_nodes + 1);
-   t.sons.assign(sons, sons + sons_ptr[n_nodes]);
-   t.label.assign(n_nodes, 0);
-   t.scale_node.assign(n_nodes, 0);
-   t.scale_slot.assign(n_nodes, -1);
-   if (scale_node)
-      for (int i = 0; i < n_nodes; i++)
-         if (scale_node[i]) { t.scale_node[i] = 1; t.scale_slot[i] = t.n_scale++; }
+   if (!tree_from_csr(n_tips, n_nodes, root, sons_ptr, sons, scale_node, &t)) return PAML_AMD_EINVAL;
    const Program p = build_program(t, false, nullptr);
    if (!jit_supported(p, n_tips, 61)) return PAML_AMD_EUNSUPPORTED;
    const int n_tab = jit_cherry_count(p, n_tips, 61, 61, 1, (size_t)std::max(max_tabs, 0) * cherry_table_bytes(61));
@@ -153,17 +143,8 @@ int paml_amd_debug_jit_tables(int n_tips, int n_nodes, int root, const int *sons
 int paml_amd_jit_prebuild(int n_states, int n_tips, int n_codes, int K, long n_patt_global, int n_nodes, int root, const int *sons_ptr,
                           const int *sons, const unsigned char *scale_node, const char *dir, char *log_out, int log_cap)
 {
-   if (!sons_ptr || !sons || !dir || n_nodes <= 0 || root < 0 || root >= n_nodes || n_states < 2 || n_states > 64) return PAML_AMD_EINVAL;
    TreeDesc t;
-   t.n_tips = n_tips; t.n_nodes = n_nodes; t.root = root;
-   t.sons_ptr.assign(sons_ptr, sons_ptr + n_nodes + 1);
-   t.sons.assign(sons, sons + sons_ptr[n_nodes]);
-   t.label.assign(n_nodes, 0);
-   t.scale_node.assign(n_nodes, 0);
-   t.scale_slot.assign(n_nodes, -1);
-   if (scale_node)
-      for (int i = 0; i < n_nodes; i++)
-         if (scale_node[i]) { t.scale_node[i] = 1; t.scale_slot[i] = t.n_scale++; }
+   if (!dir || n_states < 2 || n_states > 64 || !tree_from_csr(n_tips, n_nodes, root, sons_ptr, sons, scale_node, &t)) return PAML_AMD_EINVAL;
    // (PAML_AMD_PREBUILD_KEEP=1: the kernel of a PAML_AMD_KEEP_PARTIALS engine, every internal node's partial stored)
    const Program p = build_program(t, n_states > 20 && getenv("PAML_AMD_PREBUILD_KEEP") != nullptr, nullptr);
    std::string text;

@@ -34,6 +34,7 @@
 
 #include "../../include/paml_amd.h"
 #include "jit.h"
+#include "jit_cache.h"
 #include "kernel_args.h"
 #include "program.h"
 

@@ -1,28 +1,16 @@
-// jit.h — per-tree specialised pruning kernel.
+// jit.h — per-tree specialised pruning kernels: the generators (host C++: a program in, a source text out; jit_cache.h compiles it).
 //
 // The interpreter kernels (kernels_prune.h) pay for their generality on every op: a switch dispatch, scalar
 // loads of the op and stream tables, and — worst on CDNA4, where FP64 MFMA and VALU share the SIMD's
 // issue — dozens of v_mov per op that the compiler needs to merge the loop-carried partials.  For a fixed
 // tree the op sequence is known when paml_amd_set_tree returns, so this header unrolls it: it emits one
 // straight-line HIP kernel (a few dozen calls into the hand-written building blocks of device_common.h,
-// every block index, ring slot, wait count and register array a literal), compiles it for gfx950 with
-// hiprtc and caches the module.  Partials are renamed instead of copied: each MFMA result is a fresh
+// every block index, ring slot, wait count and register array a literal), compiled for gfx950 with
+// hiprtc and cached as a module.  Partials are renamed instead of copied: each MFMA result is a fresh
 // v4d[4] that *is* the next partial.  Same arithmetic, same operand stream, same LDS ring as
 // prune_mfma64_stream; the interpreter remains the fallback (deep stacks, > 64 codes, > 128 tips, no hiprtc).
 #pragma once
-#include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <hip/hiprtc.h>
-
-#include <sys/stat.h>
-#include <sys/types.h>
-#include <unistd.h>
-
-#include <cerrno>
-
 #include <algorithm>
-#include <cstdio>
-#include <cstring>
 #include <cstdlib>
 #include <sstream>
 #include <string>
@@ -31,13 +19,6 @@
 #include "program.h"
 
 namespace paml_amd {
-
-struct JitKernel {
-   hipModule_t mod = nullptr;
-   hipFunction_t fn = nullptr;
-   std::string key;
-   size_t n_ops = 0;
-};
 
 // Stack slots of the 61-state kernel that live in register arrays (each 32 VGPRs); deeper slots are spilled to global scratch.
 // MFMA_RS (the interpreter's register slots) sizes the scratch: the engine allocates max_stack - MFMA_RS slots per workgroup.
@@ -211,7 +192,110 @@ inline int jit_cherry_count(const Program &p, int n_tips, int n_states, int n_co
    return 0;
 }
 
-// Emit the straight-line kernel for one program.
+// ---- what the generators share -------------------------------------------------------------------------------------------
+// The profiling switches of the kernel experiments, read once per generation (build() and the tests change them between calls).
+struct JitProf {
+   const bool tiles = getenv("PAML_AMD_PROF_TILES") != nullptr;            // s_memrealtime (100 MHz) at workgroup start and at the end of each of its tiles (tools/prof_tiles.py)
+   const bool ops = !tiles && getenv("PAML_AMD_PROF_OPS") != nullptr;      // s_memtime stamp at every op
+   const int every = getenv("PAML_AMD_PROF_EVERY") ? std::max(1, atoi(getenv("PAML_AMD_PROF_EVERY"))) : 1;      // ... at every n-th op only
+   const std::string tid = getenv("PAML_AMD_PROF_TID") ? getenv("PAML_AMD_PROF_TID") : "0";                      // the thread that stamps the tiles (20 states)
+};
+
+// A partial's place: an array of the pool (A<i>), one of the 61-state kernel's arrays outside it — AS, the next tile's first cherry, and
+// AL<i>, the rows of its first lookups, both filled under the predecessor's last product — or stack slot i spilled to global scratch.
+struct JitArr {
+   enum Kind { NONE, POOL, NEXT_CHERRY, NEXT_LOOKUP, SPILLED } kind = NONE;
+   int i = -1;
+   std::string name() const { return kind == NEXT_CHERRY ? "AS" : (kind == NEXT_LOOKUP ? "AL" : "A") + std::to_string(i); }
+};
+
+// Register arrays and stack slots of a walk.  Partials are renamed, not copied: a product's result is a fresh array of the pool — a free
+// list, last released first out, on which the arrays' names in the generated text depend — and `cur` names the partial under construction.
+struct JitRegs {
+   enum Step { MUL, MUL_MEM, SPILL };      // what finish_product asks `emit` to write: out *= in;  out *= scratch slot in.i;  scratch slot in.i = out
+   std::vector<int> free_list;
+   std::vector<JitArr> slot = std::vector<JitArr>(256);      // stack slot -> its partial
+   JitArr cur;
+   const int reg_slots;         // stack slots from this one on are spilled (the 61-state kernel)
+   bool exhausted = false;      // more arrays wanted than declared: the generator returns jit_exhausted_source(), not undefined behaviour here
+   explicit JitRegs(int n_arrays, int reg_slots_ = 256) : reg_slots(reg_slots_)
+   {
+      for (int i = n_arrays - 1; i >= 0; i--) free_list.push_back(i);
+   }
+   JitArr alloc()
+   {
+      if (free_list.empty()) { exhausted = true; return {JitArr::POOL, 0}; }
+      const int r = free_list.back();
+      free_list.pop_back();
+      return {JitArr::POOL, r};
+   }
+   void release(const JitArr &r) { if (r.kind == JitArr::POOL) free_list.push_back(r.i); }
+   // An op that starts a partial.  One of the pool that is still held is written over: a forest of subtrees (the branch-local refill,
+   // engine_branch.hip) — the previous subtree's root was stored and is done.  (Not AS: the tile's last product fills it for the NEXT tile
+   // while this tile's later partials would still live in it.)
+   void start_partial() { if (cur.kind != JitArr::POOL) cur = alloc(); }
+   void end_partial() { release(cur); cur = JitArr(); }      // ROOT: the partial is used up
+   template <class Emit> void push(int s, Emit emit) { finish_product(cur, -1, s, emit); }
+   // The tail of a product (or lookup) whose result is in `out`: multiply the popped slot in, then push — to the slot, or spilled — or keep as cur
+   template <class Emit> void finish_product(const JitArr &out, int pop, int push, Emit emit)
+   {
+      if (pop >= 0) {
+         emit(slot[pop].kind == JitArr::SPILLED ? MUL_MEM : MUL, out, slot[pop]);
+         release(slot[pop]);
+         slot[pop] = JitArr();
+      }
+      if (push >= reg_slots) {
+         slot[push] = {JitArr::SPILLED, push};
+         emit(SPILL, out, slot[push]);
+         release(out);
+      }
+      else if (push >= 0) slot[push] = out;
+      cur = push >= 0 ? JitArr() : out;
+   }
+};
+inline std::string jit_exhausted_source() { return "#error \"jit register arrays exhausted\"\n"; }
+
+// The static model of a thread's vector-memory queue (vmcnt): what was issued and is not yet known to have landed, oldest first, in
+// pieces = vector-memory instructions.  Every JIT_WAIT(N) of the 61-state walk is computed here.  The ring's DMA pieces, the tip-code
+// blocks, the eight 1 KB wave stores / loads of a STORE / LOAD and the eight gathers of a lookup are entries of the ONE list because the
+// hardware counts them in one counter, in order of issue: a wait computed without the stores would make every block step wait for their
+// completion in HBM.  (At a tile's start the list lacks the previous tile's last stores: those waits are stricter than needed, never laxer.)
+struct JitItem {
+   enum Kind { RING, CODES, MEM, LOOKUP } kind;      // operand block i of the tile (>= nblk: the next tile's), a code block, a store / load, lookup i
+   int i;
+   bool operator==(const JitItem &o) const { return kind == o.kind && i == o.i; }
+};
+struct JitInFlight {
+   struct Entry { JitItem item; int pieces; };
+   std::vector<Entry> fl;
+   void issue(JitItem it, int pieces) { fl.push_back({it, pieces}); }
+   // a piece issued on its own (the deferred refill): an item whose pieces are interleaved with others' has several entries
+   void add_piece(JitItem it)
+   {
+      if (!fl.empty() && fl.back().item == it) fl.back().pieces++;
+      else fl.push_back({it, 1});
+   }
+   // pieces that may stay in flight once `it` has to be complete (-1: already covered by an earlier wait); everything up to its LAST entry is dropped
+   int wait_for(JitItem it)
+   {
+      int pos = -1, nfl = 0;
+      for (size_t i = 0; i < fl.size(); i++)
+         if (fl[i].item == it) pos = (int)i;
+      if (pos < 0) return -1;
+      for (size_t i = pos + 1; i < fl.size(); i++) nfl += fl[i].pieces;
+      fl.erase(fl.begin(), fl.begin() + pos + 1);
+      return nfl;
+   }
+   void clear() { fl.clear(); }
+   // between the code in front of the loop and the loop body: the blocks requested there are blocks 0.. of the tile the loop starts with
+   void renumber_blocks(int by)
+   {
+      for (Entry &e : fl)
+         if (e.item.kind == JitItem::RING) e.item.i += by;
+   }
+};
+
+// ---- the 61-state walk: one straight-line kernel for one program ------------------------------------------------------------
 //
 // Schedule (all static): the program's operand blocks are consumed in stream order through a ring of four LDS buffers
 // that runs on across tiles (JIT2_* in device_common.h).  Every block step is  s_waitcnt vmcnt(N) + barrier  with N =
@@ -219,8 +303,6 @@ inline int jit_cherry_count(const Program &p, int n_tips, int n_states, int n_co
 // the step's matmul where there is one.  A cherry (SET_TIP2) that follows a pushed matmul is gathered under that
 // matmul's second half; the first cherry of the NEXT tile is gathered under the current tile's last matmul (the tile's
 // own first cherry was done that way by its predecessor; the first tile's is peeled in front of the loop).
-// `first` = operand blocks of a tile already requested when the loop body starts (the body's last step leaves the
-// same number of the next tile's in flight; *first_out reports it so that jit_generate can make the two agree).
 // A tile's walk is one straight line of code — several hundred KB for a large tree — and the hardware runs such a line several times
 // slower than the same instructions with a branch every few ops (230 tips, 256 tiles per launch: 5.8 ms against 1.03 ms; an `s_branch` to
 // the next instruction does as well as a compiler-visible one: profiles/r05_big_tree_split.txt).  Programs of more than JIT_SPLIT_OPS ops
@@ -230,187 +312,198 @@ inline int jit_cherry_count(const Program &p, int n_tips, int n_states, int n_co
 // compiler's schedule of the shorter blocks measures 0.6 % faster (kernel 1.554 -> 1.544 ms at 16 taxa x 10^6 patterns, two runs each).
 static const size_t JIT_SPLIT_OPS = 8;
 inline bool jit_split_mode(size_t nops) { return nops > JIT_SPLIT_OPS; }
-inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states, int n_codes, int first, int *first_out,
-                                     const std::vector<CherryTab> *tabs = nullptr)
-{
-   std::ostringstream s;
-   const int waves = 8;
+// One generation of the 61-state walk: `first` = operand blocks of a tile already requested when the loop body starts (the body's last
+// step leaves the same number of the next tile's in flight; first_out reports it so that jit_generate can make the two agree).
+struct JitWalk {
+   const Program &p;
+   const int n_tips, n_states, n_codes, first;
+   const std::vector<CherryTab> *const tabs;
+   const JitProf &prof;
+   static constexpr int waves = 8, TP = waves * 16;
    const int nblk = (int)p.stream.size() / 2;
-   const int TP = waves * 16;
-   const JitZPlan zpl = jit_zplan(p, n_tips, TP);
-   const int ZP = zpl.ZP, ZR = (ZP * 8 + waves - 1) / waves;      // code block (or half): 2 KB units; DMA rounds per wave
    const size_t nops = p.ops.size();
+   const JitZPlan zpl = jit_zplan(p, n_tips, TP);
+   const int ZP = zpl.ZP, ZR = (ZP * 8 + waves - 1) / waves;      // code block (or piece): 2 KB units; DMA rounds per wave
    // states beyond n are zero padding: only RB row blocks and KB k-blocks of every P take part (4 and 16 at 61 states)
    const int RB = (n_states + 15) / 16, KB = (n_states + 3) / 4, KB2 = (KB + 1) / 2, NPc = KB2;   // NPc: 16-byte pieces per tip-table row
    const bool fuse_tips = KB2 >= 2;   // cherries gathered under the preceding matmul
-   const int MID = KB2 / 2;                                             // ... from this k-block pair on (jit_matvec_tip2)
-   const bool proft = getenv("PAML_AMD_PROF_TILES") != nullptr;            // kernel experiments: s_memrealtime (100 MHz) at workgroup start and at the end of each of its tiles
-   const bool prof = !proft && getenv("PAML_AMD_PROF_OPS") != nullptr;      // kernel experiments: s_memtime stamp at every op
+   const int MID = KB2 / 2;           // ... from this k-block pair on (jit_matvec_tip2)
+   // chunks of a tip table that hold codes of this data set (two codes per 1 KB chunk)
+   const int TCH = (n_codes + 1) / 2 >= 31 ? 32 : (n_codes + 1) / 2;
+   // DMA rounds per block: a P has chunks pair * 4 + row block (< KB2 * 4 used), a tip table TCH chunks; `waves` chunks per round
+   const int P_ROUNDS = (KB2 * 4 + waves - 1) / waves, T_ROUNDS = (TCH + waves - 1) / waves;
    // 61 states: the last k-block of P is the single column 60 — its rank-1 term goes through the vector pipe (a 512-byte
    // column table travels with every P block as a fifth DMA piece) and the k-block's four MFMAs are dropped
    const bool tail61 = n_states == 61;
-   int last_mm = -1;
-   for (size_t i = 0; i < nops; i++)
-      if (p.ops[i].code == OP_MATMUL || p.ops[i].code == OP_MATMUL_POP) last_mm = (int)i;
+   const bool amb_over = n_codes > 64;      // codes beyond the 64 a ring block has rows for: summed from the rows of their states (device_common.h)
+   const std::string ambarg = amb_over ? ", amb" : "";
+   const int last_mm = [&] {
+      int at = -1;
+      for (size_t i = 0; i < nops; i++)
+         if (p.ops[i].code == OP_MATMUL || p.ops[i].code == OP_MATMUL_POP) at = (int)i;
+      return at;
+   }();
    // the next tile's first cherry rides under this tile's last matmul
    // (only when that matmul is the tile's last consumer of operand blocks: the ring has no room for more)
-   bool tail_blocks = false;
-   for (size_t i = last_mm + 1; i < nops; i++)
-      if (p.ops[i].code == OP_SET_TIP || p.ops[i].code == OP_MUL_TIP || p.ops[i].code == OP_SET_TIP2 || p.ops[i].code == OP_MUL_TIP2)
-         tail_blocks = true;
+   const bool tail_blocks = [&] {
+      for (size_t i = last_mm + 1; i < nops; i++)
+         if (p.ops[i].code == OP_SET_TIP || p.ops[i].code == OP_MUL_TIP || p.ops[i].code == OP_SET_TIP2 || p.ops[i].code == OP_MUL_TIP2) return true;
+      return false;
+   }();
    // one code block only (large trees): it is replaced between tiles, so nothing of the next tile can start early
    const bool zsingle = zpl.bufs == 1, zhalf = zpl.half;
-   int cur_piece = 0;         // (piece mode) the piece of the tile's codes that is in LDS
-   const bool peel = fuse_tips && nops > 2 && p.ops[0].code == OP_SET_TIP2 && last_mm > 1 &&
-                     p.ops[1].code != OP_MUL_TIP && p.ops[1].code != OP_MUL_TIP2 && !tail_blocks && !zsingle;
-   // cherry tables (OP_LOOKUP): the rows of a lookup are requested JIT_LOOKAHEAD lookups ahead of their use, so that a product lies
-   // between request and use; those of a tile's first lookups under the previous tile's last product (or, in front of the loop, for the
-   // first tile), into arrays of their own
-   std::vector<int> lk_op;      // the program's lookups, in order: op index
-   for (size_t i = 0; i < nops; i++)
-      if (p.ops[i].code == OP_LOOKUP) lk_op.push_back((int)i);
+   const bool peel = fuse_tips && nops > 2 && p.ops[0].code == OP_SET_TIP2 && last_mm > 1 && p.ops[1].code != OP_MUL_TIP &&
+                     p.ops[1].code != OP_MUL_TIP2 && !tail_blocks && !zsingle;      // the tile's first cherry is produced by its predecessor, into AS
+   // cherry tables (OP_LOOKUP): the rows of a lookup are requested LA lookups ahead of their use, so that a product lies between request
+   // and use; those of a tile's first lookups under the previous tile's last product (or, in front of the loop, for the first tile),
+   // into arrays of their own
+   const std::vector<int> lk_op = [&] {      // the program's lookups, in order: op index
+      std::vector<int> at;
+      for (size_t i = 0; i < nops; i++)
+         if (p.ops[i].code == OP_LOOKUP) at.push_back((int)i);
+      return at;
+   }();
    const int nlk = (int)lk_op.size();
    const bool lk_cross = nlk > 0 && !peel && !zsingle;      // the first lookups of a tile are requested by its predecessor
    // (trees that keep three or more partials stacked in registers: one lookup ahead — with two the 23-taxon random tree of the tests
    //  spills 18 VGPRs)
    const int LA = std::min(p.max_stack, JIT_REG_SLOTS) >= 3 ? 1 : JIT_LOOKAHEAD;
    const int lk_ncross = lk_cross ? std::min(nlk, LA) : 0;
-   const int LK_ID = -10;       // in-flight list: lookup j is item LK_ID - j
+   const int NA = std::min(p.max_stack, JIT_REG_SLOTS) + 2 + (fuse_tips ? 1 : 0) + (nlk ? LA : 0);      // arrays of the pool
+   const bool resident = [&] {      // the program stores or loads resident partials (keep-partials mode)
+      for (const Op &o : p.ops)
+         if (o.code == OP_STORE || o.code == OP_LOAD) return true;
+      return false;
+   }();
+   const bool split_mode = jit_split_mode(nops);      // a branch every `split_every` ops, see jit_split_mode
+   static constexpr int split_every = 8;
 
-   // chunks of a tip table that hold codes of this data set (two codes per 1 KB chunk)
-   const int TCH = (n_codes + 1) / 2 >= 31 ? 32 : (n_codes + 1) / 2;
-   // DMA rounds per block: a P has chunks pair * 4 + row block (< KB2 * 4 used), a tip table TCH chunks; `waves` chunks per round
-   const int P_ROUNDS = (KB2 * 4 + waves - 1) / waves, T_ROUNDS = (TCH + waves - 1) / waves;
-   s << "#define JIT_KB2 " << KB2 << "\n#define JIT_RB " << RB << "\n#define JIT_TCH " << TCH << "\n#define JIT_WAVES " << waves << "\n";
-   if (zsingle) s << "#define JIT_ZB 1\n";
-   if (zhalf) s << "#define JIT_ZPIECES " << zpl.pieces << "\n";
-   const bool amb_over = n_codes > 64;      // codes beyond the 64 a ring block has rows for: summed from the rows of their states (device_common.h)
-   if (amb_over) s << "#define JIT_AMB_OVERFLOW 1\n";
-   if (nlk) s << "#define JIT_NC " << n_codes << "\n";
-   const std::string ambarg = amb_over ? ", amb" : "";
-   s << "#include \"device_common.h\"\nusing namespace paml_amd;\n";
-   s << "extern \"C\" __global__ __launch_bounds__(" << waves * 64 << ", " << waves / 4 << ") void prune_jit(PruneArgs a)\n{\n";
-   s << "   JIT2_PROLOGUE(" << ZP << ")\n";
-   if (amb_over) {      // the state sets of the codes 64 .. : into the three quarters of sPi a single frequency vector leaves unused (192 x 8 bytes)
-      s << "   if (a.n_pi == 1) for (int i = tid; i < a.n_codes - 64; i += JIT_WAVES * 64) ((unsigned long long *)sPi)[64 + i] = a.code_mask[64 + i];\n";
-      s << "   const JitAmb amb{a.code_mask, (__attribute__((address_space(3))) const unsigned long long *)(sPi + 64), a.n_pi == 1};\n";
-   }
-   s << "   roff = " << ((4 - nblk % 4) & 3) << ";\n";
+   std::ostringstream s;
+   JitRegs regs{NA, JIT_REG_SLOTS};
+   JitInFlight fl;
+   int issued = 0, consumed = 0;             // operand blocks requested / used so far
+   int cur_piece = 0;                        // (piece mode) the piece of the tile's codes that is in LDS
+   bool z_pending = false;                   // the next tile's code block still has to be requested in this tile
+   std::vector<std::string> pend_store;      // the pieces of a STORE that ride under the product that follows it (see step_side)
+   std::vector<std::pair<int, std::string>> pend_lookup;      // (lookup, text): the next tile's, requested in the last iteration of the product that follows
+   std::vector<JitArr> lk_arr = std::vector<JitArr>(nlk);     // lookup -> its array
+   int lk_issued = 0, lk_seen = 0;           // lookups of this tile requested / consumed so far
+   bool lk_next_done = false;                // the next tile's first lookups are requested
 
-   // ---- static bookkeeping of what is in flight (per thread: pieces = vector-memory instructions) -------------------
-   struct Item { int id, pieces; };          // id: block number within the tile (>= nblk: next tile's), -1: a code block
-   std::vector<Item> fl;                     // issued, not yet known landed; oldest first
-   int issued = 0, consumed = 0;
-   auto n_rounds = [&](int blk) { return p.stream[2 * (blk % nblk)] ? T_ROUNDS : P_ROUNDS; };
-   auto n_pieces = [&](int blk) { return n_rounds(blk) + ((tail61 && !p.stream[2 * (blk % nblk)]) ? 1 : 0); };
-   auto piece = [&](int blk, int c4) {       // source text of one DMA piece of block blk (the last one of a P: the column table)
+   JitWalk(const Program &p_, int n_tips_, int n_states_, int n_codes_, int first_, const std::vector<CherryTab> *tabs_, const JitProf &prof_)
+      : p(p_), n_tips(n_tips_), n_states(n_states_), n_codes(n_codes_), first(first_), tabs(tabs_), prof(prof_) {}
+
+   // ---- text of the operands ----
+   int n_rounds(int blk) const { return p.stream[2 * (blk % nblk)] ? T_ROUNDS : P_ROUNDS; }
+   int n_pieces(int blk) const { return n_rounds(blk) + ((tail61 && !p.stream[2 * (blk % nblk)]) ? 1 : 0); }
+   std::string piece(int blk, int c4) const      // one DMA piece of block blk (the last one of a P: the column table)
+   {
       const bool nx = blk >= nblk;
       const int loc = blk % nblk, is_tip = p.stream[2 * loc], node = p.stream[2 * loc + 1];
       if (c4 == n_rounds(blk)) return std::string("JIT2_PIECE_") + (nx ? "NPC(" : "PC(") + std::to_string(blk) + ", " + std::to_string(node) + ");";
       return std::string("JIT2_PIECE_") + (nx ? "N" : "") + (is_tip ? "T(" : "P(") + std::to_string(blk) + ", " + std::to_string(node) + ", " +
              std::to_string(c4) + ");";
-   };
-   auto issue_now = [&]() {
+   }
+   std::string code(int tip, bool next = false) const { return (next ? "JIT2_NCODE(" : "JIT2_CODE(") + std::to_string(ZP) + ", " + std::to_string(zpl.row[tip]) + ")"; }
+   std::string buf(int blk) const { return "JIT2_BUF(" + std::to_string(blk) + ")"; }
+   std::string colarg(int blk) const { return tail61 ? ", JIT2_COL(" + std::to_string(blk) + "), x60" : std::string(); }
+   std::string issue_z() const { return zhalf ? "JIT2_ISSUE_ZH(" + std::to_string(ZP) + ", n_tile, 0)" : "JIT2_ISSUE_Z(" + std::to_string(ZP) + ")"; }
+   static std::string spill_ptr(int slot_no) { return "JIT_SPILL_PTR(" + std::to_string(slot_no - JIT_SCRATCH_BASE) + ")"; }
+   // the rows of lookup k into array `arr`: of this tile, or (next) of the tile after it, into its AL array
+   std::string lookup_text(int k, bool next) const
+   {
+      const Op &o = p.ops[lk_op[k]];
+      const CherryTab &t = (*tabs)[o.c];
+      return "jit_lookup(" + (next ? JitArr{JitArr::NEXT_LOOKUP, k} : lk_arr[k]).name() + ", JIT_CTAB(" + (next ? "n_iclass" : "iclass") + ", " + std::to_string(o.c) +
+             "), " + code(t.tip_a, next) + ", " + code(t.tip_b, next) + ", q);";
+   }
+
+   // ---- the schedule ----
+   void issue_now()
+   {
       s << "  ";
       for (int c4 = 0; c4 < n_pieces(issued); c4++) s << " " << piece(issued, c4);
       s << "\n";
-      fl.push_back({issued, n_pieces(issued)});
+      fl.issue({JitItem::RING, issued}, n_pieces(issued));
       issued++;
-   };
-   auto wait_count = [&](int blk) {          // pieces that may stay in flight once block blk has to be complete
-      int pos = -1;
-      for (size_t i = 0; i < fl.size(); i++)
-         if (fl[i].id == blk) pos = (int)i;
-      if (pos < 0) return -1;                // already covered by an earlier wait
-      int nfl = 0;
-      for (size_t i = pos + 1; i < fl.size(); i++) nfl += fl[i].pieces;
-      fl.erase(fl.begin(), fl.begin() + pos + 1);
-      return nfl;
-   };
-   bool z_pending = false;                   // the next tile's code block still has to be requested in this tile
-   std::vector<std::string> pend_store;      // the pieces of a STORE that ride under the product that follows it (see step)
-   std::vector<std::pair<int, std::string>> pend_lookup;      // (in-flight id, text) of the lookups requested in the last iteration of the product that follows
-   // make the next c blocks visible, then top the ring up — at once, or (defer) as a `side` functor that spreads the
-   // refill's pieces over the first `iters` k-block pairs of the matmul that follows; the first `now` blocks from
-   // `consumed` are needed within this very step and are never delayed
-   auto step = [&](int c, bool defer = false, int iters = 8, int now = 1) -> std::string {
+   }
+   // make the next c blocks visible: wait for them, barrier, and (once per tile, behind its first barrier) request the next tile's codes
+   void arrive(int c)
+   {
       // (a step whose blocks the ring has not been asked for yet — a cherry right after the tile's first one, as the forests of the branch-local
       //  refill have them: the top-up of the step before stopped short of it.  Every wave is done with the slots they go to after a barrier.)
       if (issued < consumed + c) {
          s << "   JIT_SYNC();\n";
          while (issued < consumed + c) issue_now();
       }
-      const int nw = wait_count(consumed + c - 1);
+      const int nw = fl.wait_for({JitItem::RING, consumed + c - 1});
       if (nw >= 0) s << "   JIT_WAIT(" << nw << ");";
       s << "   JIT_SYNC();\n";
       if (z_pending) {
          s << "   JIT2_ISSUE_Z(" << ZP << ")\n";
-         fl.push_back({-1, ZR});
+         fl.issue({JitItem::CODES, 0}, ZR);
          z_pending = false;
       }
-      const int upto = consumed + 4;
-      if (!defer) {
-         if (!pend_store.empty()) {
-            s << "  ";
-            for (const std::string &st : pend_store) s << " " << st;
-            s << "\n";
-            fl.push_back({-2, (int)pend_store.size()});
-            pend_store.clear();
-         }
-         while (issued < upto) issue_now();
-         return "JitNoSide()";
+   }
+   // a block step of an op without a product: arrive, then top the ring up at once, to three blocks ahead
+   void step(int c)
+   {
+      arrive(c);
+      if (!pend_store.empty()) {
+         s << "  ";
+         for (const std::string &st : pend_store) s << " " << st;
+         s << "\n";
+         fl.issue({JitItem::MEM, 0}, (int)pend_store.size());
+         pend_store.clear();
       }
-      while (issued < consumed + now && issued < upto) issue_now();
-      // a STORE waiting for this product (keep-partials mode: the partial it multiplies): its eight 1 KB wave stores go out one per
-      // k-block pair, under the MFMAs — issued together they hold the CU's store path for ~5 000 cycles during which no wave of the
-      // workgroup gets to its MFMAs (measured: 2.2 ms per evaluation at 16 taxa x 10^6 codon patterns against 1.56 without the stores).
-      // The in-flight list below records them where they are issued, between the deferred DMA pieces of the same iterations.
-      std::vector<std::string> stores;
-      stores.swap(pend_store);
-      struct Piece { int blk; std::string text; };      // blk = -2: a store
+      while (issued < consumed + 4) issue_now();
+   }
+   // a product's block step: arrive, and the refill as a `side` functor that spreads its pieces over the first `iters` k-block pairs
+   // of the matmul that follows
+   std::string step_side(int iters)
+   {
+      arrive(1);
+      struct Piece { JitItem item; std::string text; };
       std::vector<Piece> pieces;
-      while (issued < upto) {
-         for (int c4 = 0; c4 < n_pieces(issued); c4++) pieces.push_back({issued, piece(issued, c4)});
-         issued++;
-      }
-      if (pieces.empty() && stores.empty() && pend_lookup.empty()) return "JitNoSide()";
+      for (; issued < consumed + 4; issued++)
+         for (int c4 = 0; c4 < n_pieces(issued); c4++) pieces.push_back({{JitItem::RING, issued}, piece(issued, c4)});
+      if (pieces.empty() && pend_store.empty() && pend_lookup.empty()) return "JitNoSide()";
       const int per = pieces.empty() ? 1 : ((int)pieces.size() + iters - 1) / iters;
       std::vector<std::vector<Piece>> at(iters);
       for (size_t i = 0; i < pieces.size(); i++) at[i / per].push_back(pieces[i]);
-      for (size_t i = 0; i < stores.size(); i++) at[i * iters / stores.size()].push_back({-2, stores[i]});
-      // (behind every DMA piece of this step: the order the code in front of the loop issues them in)
+      // a STORE waiting for this product (keep-partials mode: the partial it multiplies): its eight 1 KB wave stores go out one per
+      // k-block pair, under the MFMAs — issued together they hold the CU's store path for ~5 000 cycles during which no wave of the
+      // workgroup gets to its MFMAs (measured: 2.2 ms per evaluation at 16 taxa x 10^6 codon patterns against 1.56 without the stores).
+      for (size_t i = 0; i < pend_store.size(); i++) at[i * iters / pend_store.size()].push_back({{JitItem::MEM, 0}, pend_store[i]});
+      pend_store.clear();
+      // the next tile's lookups: behind every DMA piece of this step — the order the code in front of the loop issues them in
       for (const std::pair<int, std::string> &lk : pend_lookup)
-         for (int i = 0; i < 8; i++) at[iters - 1].push_back({lk.first, i ? std::string() : lk.second});
+         for (int i = 0; i < 8; i++) at[iters - 1].push_back({{JitItem::LOOKUP, lk.first}, i ? std::string() : lk.second});
       pend_lookup.clear();
-      // the in-flight list in the order of issue (a block whose pieces span iterations has several entries: wait_count takes the last)
+      // the in-flight list records every piece where it is issued
       std::string f = "[&](int kb2) {";
       for (int i = 0; i < iters; i++) {
          if (at[i].empty()) continue;
          f += " if (kb2 == " + std::to_string(i) + ") {";
          for (const Piece &pc : at[i]) {
             f += " " + pc.text;
-            if (!fl.empty() && fl.back().id == pc.blk) fl.back().pieces++;
-            else fl.push_back({pc.blk, 1});
+            fl.add_piece(pc.item);
          }
          f += " }";
       }
       return f + " }";
-   };
-   const int prof_every = getenv("PAML_AMD_PROF_EVERY") ? std::max(1, atoi(getenv("PAML_AMD_PROF_EVERY"))) : 1;      // (experiments: a stamp at every n-th op only)
-   const bool split_mode = jit_split_mode(nops);      // (large trees: a branch every `split_every` ops, see jit_split_mode)
-   const int split_every = 8;
-   auto stamp = [&](size_t iop) {
-      if (prof && iop % prof_every == 0)
+   }
+   void stamp(size_t iop)
+   {
+      if (prof.ops && iop % prof.every == 0)
          s << "   if (a.prof && tid == a.prof_tid && ptile) a.prof[(long)blockIdx.x * a.prof_stride + 1 + " << iop
            << "] = __builtin_amdgcn_s_memtime();\n";
-      else if (!prof && split_mode && iop && iop % split_every == 0)
+      else if (!prof.ops && split_mode && iop && iop % split_every == 0)
          s << "   JIT_SPLIT()\n";
-   };
-   auto code = [&](int tip) { return "JIT2_CODE(" + std::to_string(ZP) + ", " + std::to_string(zpl.row[tip]) + ")"; };
-   auto ncode = [&](int tip) { return "JIT2_NCODE(" + std::to_string(ZP) + ", " + std::to_string(zpl.row[tip]) + ")"; };
-   const std::string issue_z = zhalf ? "JIT2_ISSUE_ZH(" + std::to_string(ZP) + ", n_tile, 0)" : "JIT2_ISSUE_Z(" + std::to_string(ZP) + ")";
+   }
    // (piece mode) rows of a later piece are needed from here on: every wave is done with the piece in LDS, the next comes over it
-   auto cross_if = [&](std::initializer_list<int> tips) {
+   void cross_if(std::initializer_list<int> tips)
+   {
       if (!zhalf) return;
       int need = cur_piece;
       for (int t : tips) need = std::max(need, zpl.piece[t]);
@@ -419,315 +512,270 @@ inline std::string jit_generate_impl(const Program &p, int n_tips, int n_states,
          s << "   __syncthreads();\n   JIT2_ISSUE_ZH(" << ZP << ", cur_tile, " << cur_piece << ")\n   JIT_WAIT(0); __syncthreads();\n";
          fl.clear();
       }
-   };
-   auto buf = [&](int blk) { return "JIT2_BUF(" + std::to_string(blk) + ")"; };
-   auto colarg = [&](int blk) { return tail61 ? ", JIT2_COL(" + std::to_string(blk) + "), x60" : std::string(); };
-
-   // ---- in front of the loop: the first tile is the "next" tile of an empty predecessor ---------------------------
-   const int reg_slots = std::min(p.max_stack, JIT_REG_SLOTS);
-   const int NA = reg_slots + 2 + (fuse_tips ? 1 : 0) + (nlk ? LA : 0);
-   const int SPILLED = -2;
-   auto spill_ptr = [&](int slot_no) { return "JIT_SPILL_PTR(" + std::to_string(slot_no - JIT_SCRATCH_BASE) + ")"; };
-   for (int i = 0; i < NA; i++) s << "   v4d A" << i << "[4];\n";
-   if (peel) s << "   v4d AS[4];\n";       // the first cherry of a tile, produced under the predecessor's last matmul
-   for (int k = 0; k < lk_ncross; k++) s << "   v4d AL" << k << "[4];\n";      // the first lookups of a tile, requested by the predecessor
-   const int AL = 2000;
-   std::vector<int> lk_arr(nlk, -1);      // lookup -> its array
-   // the rows of lookup k into array `arr`: of this tile, or (next) of the tile after it
-   auto lookup_text = [&](int k, const std::string &arr, bool next) {
-      const Op &o = p.ops[lk_op[k]];
-      const CherryTab &t = (*tabs)[o.c];
-      return "jit_lookup(" + arr + ", JIT_CTAB(" + (next ? "n_iclass" : "iclass") + ", " + std::to_string(o.c) + "), " +
-             (next ? "JIT2_NCODE(" : "JIT2_CODE(") + std::to_string(ZP) + ", " + std::to_string(zpl.row[t.tip_a]) + "), " +
-             (next ? "JIT2_NCODE(" : "JIT2_CODE(") + std::to_string(ZP) + ", " + std::to_string(zpl.row[t.tip_b]) + "), q);";
-   };
-   s << "   JIT2_NEXT_SET()\n   " << issue_z << "\n";
-   fl.push_back({-1, ZR});
-   issued = nblk;                           // numbered as the blocks after the (empty) predecessor's
-   for (int i = 0; i < first; i++) issue_now();
-   if (peel) {
-      const int nw = wait_count(nblk + 1);
-      s << "   JIT_WAIT(" << nw << "); __syncthreads();\n";
-      s << "   jit_tip2_set<" << NPc << ">(AS, " << buf(nblk) << ", " << ncode(p.ops[0].a) << ", " << buf(nblk + 1) << ", " << ncode(p.ops[0].b) << ", q, lane" << ambarg << ");\n";
    }
-   if (lk_ncross) {      // (the first tile's codes have to be there; the list keeps its items: the waits of later trips need them)
-      s << "   JIT_WAIT(0); __syncthreads();\n";
+   void issue_lookup(int k)
+   {
+      lk_arr[k] = regs.alloc();
+      s << "   " << lookup_text(k, false) << "\n";
+      fl.issue({JitItem::LOOKUP, k}, 8);
+   }
+   void issue_next_lookups()      // (behind every operand block the tile requests: the order the code in front of the loop has)
+   {
       for (int k = 0; k < lk_ncross; k++) {
-         s << "   " << lookup_text(k, "AL" + std::to_string(k), true) << "\n";
-         fl.push_back({LK_ID - k, 8});
-      }
-   }
-   if (zsingle) {      // everything requested so far has to be there when the loop starts: the same state the loop's end leaves
-      s << "   JIT_WAIT(0); __syncthreads();\n";
-      fl.clear();
-   }
-   // renumber for the loop body: those three blocks are blocks 0..2 of the tile the loop starts with
-   for (Item &it : fl)
-      if (it.id >= 0) it.id -= nblk;
-   issued = first;
-   consumed = peel ? 2 : 0;
-
-   if (proft) s << "   int ptc = 0; if (a.prof && tid == 0) { a.prof[(long)blockIdx.x * a.prof_stride] = __builtin_amdgcn_s_memrealtime(); a.prof[(long)blockIdx.x * a.prof_stride + a.prof_stride - 2] = __builtin_amdgcn_s_memtime(); }\n";
-   bool resident = false;      // the program stores or loads resident partials (keep-partials mode)
-   for (const Op &o : p.ops) resident = resident || o.code == OP_STORE || o.code == OP_LOAD;
-   s << "   int ptile = 1;\n   for (;; ptile = 0) {\n";
-   s << "   JIT2_ADVANCE(" << nblk << ")\n";
-   // (n_tile is still this tile's number here; the groups of a tile's waves that start past its gene's end belong to nobody: not stored)
-   if (resident) s << "   const int tg0 = as_const(a.tile_group0)[n_tile];\n   const bool wave_in = h0 + wave * 16 < hend;\n";
-   if (zhalf) s << "   const int cur_tile = n_tile;\n";
-   s << "   work += gridDim.x;\n   JIT2_NEXT_SET()\n";
-   z_pending = !zsingle;
-
-   // register arrays: a free list; `cur` names the array holding the partial under construction
-   std::vector<int> freeA;
-   for (int i = NA - 1; i >= 0; i--) freeA.push_back(i);
-   const int AS = 1000;
-   bool exhausted = false;      // more arrays wanted than NA declares: the source is an #error, not undefined behaviour here
-   auto alloc = [&]() {
-      if (freeA.empty()) { exhausted = true; return 0; }
-      int r = freeA.back(); freeA.pop_back(); return r;
-   };
-   auto release = [&](int r) { if (r < AS) freeA.push_back(r); };
-   auto name = [&](int r) { return r == AS ? std::string("AS") : r >= AL ? "AL" + std::to_string(r - AL) : "A" + std::to_string(r); };
-   std::vector<int> slot(256, -1);   // stack slot -> array
-   int cur = peel ? AS : -1;
-
-   if (prof) s << "   if (a.prof && tid == a.prof_tid && ptile) a.prof[(long)blockIdx.x * a.prof_stride] = __builtin_amdgcn_s_memtime();\n";
-   // An op that starts a partial while one is still held: a forest of subtrees (the branch-local refill, engine_branch.hip) — the previous
-   // subtree's root was stored and is done.  (Not written over in place: after a first subtree that is a lone cherry the array is AS, which the
-   // tile's last product fills for the NEXT tile while this tile's later partials would still live in it.)
-   auto start_partial = [&]() {
-      if (cur >= 0) release(cur);
-      cur = alloc();
-   };
-   int lk_issued = lk_ncross, lk_seen = 0;      // lookups of this tile requested / consumed so far
-   bool lk_next_done = !lk_cross;               // the next tile's first lookups are requested
-   for (int k = 0; k < lk_ncross; k++) lk_arr[k] = AL + k;
-   auto issue_lookup = [&](int k) {
-      lk_arr[k] = alloc();
-      s << "   " << lookup_text(k, name(lk_arr[k]), false) << "\n";
-      fl.push_back({LK_ID - k, 8});
-   };
-   auto issue_next_lookups = [&]() {            // (behind every operand block the tile requests: the order the code in front of the loop has)
-      for (int k = 0; k < lk_ncross; k++) {
-         s << "   " << lookup_text(k, "AL" + std::to_string(k), true) << "\n";
-         fl.push_back({LK_ID - k, 8});
+         s << "   " << lookup_text(k, true) << "\n";
+         fl.issue({JitItem::LOOKUP, k}, 8);
       }
       lk_next_done = true;
-   };
-   if (nlk && !lk_cross)
-      while (lk_issued < std::min(nlk, LA)) issue_lookup(lk_issued++);
-   for (size_t iop = 0; iop < nops; iop++) {
+   }
+   void finish_product(const JitArr &out, int pop, int push)
+   {
+      regs.finish_product(out, pop, push, [&](JitRegs::Step st, const JitArr &o, const JitArr &in) {
+         if (st == JitRegs::MUL) s << "   jit_mul(" << o.name() << ", " << in.name() << ");\n";
+         else s << (st == JitRegs::SPILL ? "   jit_spill(" : "   jit_mul_mem(") << o.name() << ", " << spill_ptr(in.i) << ");\n";
+      });
+   }
+
+   // ---- the stages ----
+   void defines_and_prologue()
+   {
+      s << "#define JIT_KB2 " << KB2 << "\n#define JIT_RB " << RB << "\n#define JIT_TCH " << TCH << "\n#define JIT_WAVES " << waves << "\n";
+      if (zsingle) s << "#define JIT_ZB 1\n";
+      if (zhalf) s << "#define JIT_ZPIECES " << zpl.pieces << "\n";
+      if (amb_over) s << "#define JIT_AMB_OVERFLOW 1\n";
+      if (nlk) s << "#define JIT_NC " << n_codes << "\n";
+      s << "#include \"device_common.h\"\nusing namespace paml_amd;\n";
+      s << "extern \"C\" __global__ __launch_bounds__(" << waves * 64 << ", " << waves / 4 << ") void prune_jit(PruneArgs a)\n{\n";
+      s << "   JIT2_PROLOGUE(" << ZP << ")\n";
+      if (amb_over) {      // the state sets of the codes 64 .. : into the three quarters of sPi a single frequency vector leaves unused (192 x 8 bytes)
+         s << "   if (a.n_pi == 1) for (int i = tid; i < a.n_codes - 64; i += JIT_WAVES * 64) ((unsigned long long *)sPi)[64 + i] = a.code_mask[64 + i];\n";
+         s << "   const JitAmb amb{a.code_mask, (__attribute__((address_space(3))) const unsigned long long *)(sPi + 64), a.n_pi == 1};\n";
+      }
+      s << "   roff = " << ((4 - nblk % 4) & 3) << ";\n";
+      for (int i = 0; i < NA; i++) s << "   v4d A" << i << "[4];\n";
+      if (peel) s << "   v4d AS[4];\n";
+      for (int k = 0; k < lk_ncross; k++) s << "   v4d AL" << k << "[4];\n";
+   }
+   // in front of the loop: the first tile is the "next" tile of an empty predecessor
+   void front_of_loop()
+   {
+      s << "   JIT2_NEXT_SET()\n   " << issue_z() << "\n";
+      fl.issue({JitItem::CODES, 0}, ZR);
+      issued = nblk;                           // numbered as the blocks after the (empty) predecessor's
+      for (int i = 0; i < first; i++) issue_now();
+      if (peel) {
+         const int nw = fl.wait_for({JitItem::RING, nblk + 1});
+         s << "   JIT_WAIT(" << nw << "); __syncthreads();\n";
+         s << "   jit_tip2_set<" << NPc << ">(AS, " << buf(nblk) << ", " << code(p.ops[0].a, true) << ", " << buf(nblk + 1) << ", " << code(p.ops[0].b, true) << ", q, lane" << ambarg << ");\n";
+      }
+      if (lk_ncross) {      // (the first tile's codes have to be there; the list keeps its items: the waits of later trips need them)
+         s << "   JIT_WAIT(0); __syncthreads();\n";
+         issue_next_lookups();
+      }
+      if (zsingle) {      // everything requested so far has to be there when the loop starts: the same state the loop's end leaves
+         s << "   JIT_WAIT(0); __syncthreads();\n";
+         fl.clear();
+      }
+      fl.renumber_blocks(-nblk);
+      issued = first;
+      consumed = peel ? 2 : 0;
+   }
+   void tile_head()
+   {
+      if (prof.tiles) s << "   int ptc = 0; if (a.prof && tid == 0) { a.prof[(long)blockIdx.x * a.prof_stride] = __builtin_amdgcn_s_memrealtime(); a.prof[(long)blockIdx.x * a.prof_stride + a.prof_stride - 2] = __builtin_amdgcn_s_memtime(); }\n";
+      s << "   int ptile = 1;\n   for (;; ptile = 0) {\n";
+      s << "   JIT2_ADVANCE(" << nblk << ")\n";
+      // (n_tile is still this tile's number here; the groups of a tile's waves that start past its gene's end belong to nobody: not stored)
+      if (resident) s << "   const int tg0 = as_const(a.tile_group0)[n_tile];\n   const bool wave_in = h0 + wave * 16 < hend;\n";
+      if (zhalf) s << "   const int cur_tile = n_tile;\n";
+      s << "   work += gridDim.x;\n   JIT2_NEXT_SET()\n";
+      z_pending = !zsingle;
+      if (peel) regs.cur = {JitArr::NEXT_CHERRY, 0};
+      if (prof.ops) s << "   if (a.prof && tid == a.prof_tid && ptile) a.prof[(long)blockIdx.x * a.prof_stride] = __builtin_amdgcn_s_memtime();\n";
+      lk_issued = lk_ncross;
+      lk_next_done = !lk_cross;
+      for (int k = 0; k < lk_ncross; k++) lk_arr[k] = {JitArr::NEXT_LOOKUP, k};
+      if (nlk && !lk_cross)
+         while (lk_issued < std::min(nlk, LA)) issue_lookup(lk_issued++);
+   }
+   void tile_tail()
+   {
+      if (!lk_next_done) issue_next_lookups();
+      // programs whose steps never came by a barrier after the tile switch (no operand blocks): request the codes here
+      if (z_pending) {
+         s << "   __syncthreads();\n   JIT2_ISSUE_Z(" << ZP << ")\n";
+         fl.issue({JitItem::CODES, 0}, ZR);
+      }
+      if (zsingle) {      // all waves are done with this tile's codes: fetch the next tile's (first piece) over them, and wait (once per tile)
+         s << "   __syncthreads();\n   " << issue_z() << "\n   JIT_WAIT(0); __syncthreads();\n";
+         fl.clear();
+      }
+      if (prof.tiles) s << "   if (a.prof && tid == 0 && ptc < a.prof_stride - 4) { a.prof[(long)blockIdx.x * a.prof_stride + 1 + ptc] = __builtin_amdgcn_s_memrealtime(); a.prof[(long)blockIdx.x * a.prof_stride + a.prof_stride - 1] = __builtin_amdgcn_s_memtime(); }\n   ptc++;\n";
+      s << "   if (!has_next) break;\n   }\n   JIT_WAIT(0);\n}\n";
+   }
+
+   // ---- the ops ----
+   void op_init(const Op &o)
+   {
+      regs.start_partial();
+      if (o.code == OP_INIT_TIP) cross_if({o.a});
+      if (o.code == OP_INIT_TIP) s << "   jit_init_tip(" << regs.cur.name() << ", " << code(o.a) << ", q, a.cleandata);\n";
+      else s << "   jit_init_ones(" << regs.cur.name() << ", q, n);\n";
+   }
+   void op_tip(const Op &o)      // SET_TIP, MUL_TIP
+   {
+      if (o.code == OP_SET_TIP) regs.start_partial();
+      cross_if({o.a});
+      step(1);
+      s << "   " << (o.code == OP_SET_TIP ? "jit_tip_set<" : "jit_tip_mul<") << NPc << ">(" << regs.cur.name() << ", " << buf(consumed) << ", " << code(o.a) << ", q, lane" << ambarg << ");\n";
+      consumed += 1;
+   }
+   void op_tip2(const Op &o)      // SET_TIP2, MUL_TIP2
+   {
+      if (o.code == OP_SET_TIP2 || regs.cur.kind == JitArr::NONE) regs.start_partial();
+      cross_if({o.a, o.b});
+      step(2);
+      s << "   " << (o.code == OP_SET_TIP2 ? "jit_tip2_set<" : "jit_tip2_mul<") << NPc << ">(" << regs.cur.name() << ", " << buf(consumed) << ", " << code(o.a)
+        << ", " << buf(consumed + 1) << ", " << code(o.b) << ", q, lane" << ambarg << ");\n";
+      consumed += 2;
+   }
+   void op_lookup(const Op &o)
+   {
+      const int j = lk_seen++;
+      while (lk_issued < nlk && lk_issued <= j + LA) issue_lookup(lk_issued++);
+      regs.release(regs.cur);
+      const int nw = fl.wait_for({JitItem::LOOKUP, j});
+      if (nw >= 0) s << "   JIT_WAIT(" << nw << ");\n";
+      if (lk_arr[j].kind == JitArr::NEXT_LOOKUP) {      // (the predecessor's array is wanted again under this tile's last product)
+         const JitArr own = regs.alloc();
+         s << "   jit_copy(" << own.name() << ", " << lk_arr[j].name() << ");\n";
+         lk_arr[j] = own;
+      }
+      finish_product(lk_arr[j], mm_pop_slot(o), mm_push_slot(o));
+   }
+   // wait, barrier, refill (as the product's side functor), product, pop / push
+   void op_product(size_t &iop)
+   {
       const Op &o = p.ops[iop];
-      stamp(iop);
-      if (iop == 0 && peel) continue;      // done by the predecessor
-      switch (o.code) {
-      case OP_INIT_ONES:
-         start_partial();
-         s << "   jit_init_ones(" << name(cur) << ", q, n);\n";
-         break;
-      case OP_INIT_TIP:
-         start_partial();
-         cross_if({o.a});
-         s << "   jit_init_tip(" << name(cur) << ", " << code(o.a) << ", q, a.cleandata);\n";
-         break;
-      case OP_SET_TIP:
-         start_partial();
-         cross_if({o.a});
-         step(1);
-         s << "   jit_tip_set<" << NPc << ">(" << name(cur) << ", " << buf(consumed) << ", " << code(o.a) << ", q, lane" << ambarg << ");\n";
+      const int pop = mm_pop_slot(o), push = mm_push_slot(o);
+      const JitArr in = regs.cur, out = regs.alloc();
+      const Op *const after = iop + 1 < nops && p.ops[iop + 1].code == OP_SET_TIP2 ? &p.ops[iop + 1] : nullptr;
+      // a cherry right after a pushed matmul: its two tip gathers ride under this matmul's second half
+      // (piece mode: a cherry whose codes lie in the NEXT piece is not folded under this product — the crossing then happens at the cherry's
+      //  own step; there are at most pieces - 1 of them per tile.  The folded form gave a wrong lnL once on the 1 000-tip tree of
+      //  tests/test_engine_gpu.py, cause not found, and was removed.)
+      const bool crossing_cherry = zhalf && after && std::max(zpl.piece[after->a], zpl.piece[after->b]) > cur_piece;
+      const bool fuse = fuse_tips && push >= 0 && after && !crossing_cherry;
+      const bool fuse_next = peel && (int)iop == last_mm;     // ... or the next tile's first cherry under the last matmul
+      if (fuse) cross_if({after->a, after->b});
+      // (tip tables the ring could not hold earlier are requested in the first k-block pairs and awaited at the midpoint)
+      // (the cross-lane read of x[60] is issued before the step's wait + barrier so that its latency hides there)
+      if (tail61) s << "   { const double x60 = jit_x60(" << in.name() << ", lane);\n";
+      // the next tile's first lookups: under this, the tile's last, product — once this tile has consumed its own (a cherry that is a
+      // son of the root comes AFTER the last product and still lives in its AL array: then they are requested in front of ROOT)
+      if (lk_cross && (int)iop == last_mm && !tail_blocks && !fuse && !fuse_next && lk_seen >= lk_ncross) {
+         for (int k = 0; k < lk_ncross; k++) pend_lookup.push_back({k, lookup_text(k, true)});
+         lk_next_done = true;
+      }
+      const std::string side = step_side((fuse || fuse_next) ? MID : KB2);
+      JitArr tgt;
+      if (fuse || fuse_next) {
+         const Op &nx = fuse ? *after : p.ops[0];
+         tgt = fuse ? regs.alloc() : JitArr{JitArr::NEXT_CHERRY, 0};
+         const int mid = fl.wait_for({JitItem::RING, consumed + 2});
+         s << "   jit_matvec_tip2<" << (mid < 0 ? 63 : mid) << (tail61 ? ", true, " : ", false, ") << RB << ", " << KB << ">(" << buf(consumed) << ", lane, " << in.name()
+           << ", " << out.name() << ", " << buf(consumed + 1) << ", " << code(nx.a, !fuse) << ", " << buf(consumed + 2) << ", "
+           << code(nx.b, !fuse) << ", q, " << tgt.name() << ", " << side << colarg(consumed) << (amb_over ? (tail61 ? ", amb" : ", nullptr, 0.0, amb") : "") << ");"
+           << (tail61 ? " }" : "") << "\n";
+         consumed += 3;
+      }
+      else {
+         s << "   jit_matvec<" << (tail61 ? "true" : "false") << ", " << RB << ", " << KB << ">(" << buf(consumed) << ", lane, " << in.name() << ", "
+           << out.name() << ", "
+           << side << colarg(consumed) << ");" << (tail61 ? " }" : "") << "\n";
          consumed += 1;
-         break;
-      case OP_MUL_TIP:
-         cross_if({o.a});
-         step(1);
-         s << "   jit_tip_mul<" << NPc << ">(" << name(cur) << ", " << buf(consumed) << ", " << code(o.a) << ", q, lane" << ambarg << ");\n";
-         consumed += 1;
-         break;
-      case OP_SET_TIP2:
-      case OP_MUL_TIP2:
-         if (o.code == OP_SET_TIP2 || cur < 0) start_partial();
-         cross_if({o.a, o.b});
-         step(2);
-         s << "   " << (o.code == OP_SET_TIP2 ? "jit_tip2_set<" : "jit_tip2_mul<") << NPc << ">(" << name(cur) << ", " << buf(consumed) << ", " << code(o.a)
-           << ", " << buf(consumed + 1) << ", " << code(o.b) << ", q, lane" << ambarg << ");\n";
-         consumed += 2;
-         break;
-      case OP_LOOKUP: {
-         const int j = lk_seen++, pop = mm_pop_slot(o), push = mm_push_slot(o);
-         while (lk_issued < nlk && lk_issued <= j + LA) issue_lookup(lk_issued++);
-         if (cur >= 0) release(cur);
-         const int out = lk_arr[j];
-         const int nw = wait_count(LK_ID - j);
-         if (nw >= 0) s << "   JIT_WAIT(" << nw << ");\n";
-         if (out >= AL) {      // (the predecessor's array is wanted again under this tile's last product)
-            const int own = alloc();
-            s << "   jit_copy(" << name(own) << ", " << name(out) << ");\n";
-            lk_arr[j] = own;
-         }
-         const int res = lk_arr[j];
-         if (pop >= 0) {
-            if (slot[pop] == SPILLED)
-               s << "   jit_mul_mem(" << name(res) << ", " << spill_ptr(pop) << ");\n";
-            else {
-               s << "   jit_mul(" << name(res) << ", " << name(slot[pop]) << ");\n";
-               release(slot[pop]);
-            }
-            slot[pop] = -1;
-         }
-         if (push >= JIT_REG_SLOTS) {
-            s << "   jit_spill(" << name(res) << ", " << spill_ptr(push) << ");\n";
-            release(res);
-            slot[push] = SPILLED;
-            cur = -1;
-         }
-         else if (push >= 0) {
-            slot[push] = res;
-            cur = -1;
-         }
-         else
-            cur = res;
-      } break;
-      case OP_PUSH:
-         if (o.b >= JIT_REG_SLOTS) {
-            s << "   jit_spill(" << name(cur) << ", " << spill_ptr(o.b) << ");\n";
-            release(cur);
-            slot[o.b] = SPILLED;
-         }
-         else
-            slot[o.b] = cur;
-         cur = -1;
-         break;
-      case OP_MATMUL:
-      case OP_MATMUL_POP: {
-         const int pop = mm_pop_slot(o), push = mm_push_slot(o);
-         const int out = alloc();
-         // a cherry right after a pushed matmul: its two tip gathers ride under this matmul's second half
-         // (piece mode: a cherry whose codes lie in the NEXT piece is not folded under this product — the crossing then happens at the cherry's
-         //  own step; there are at most pieces - 1 of them per tile.  The folded form gave a wrong lnL once on the 1 000-tip tree of
-         //  tests/test_engine_gpu.py, cause not found, and was removed.)
-         const bool crossing_cherry = zhalf && iop + 1 < nops && p.ops[iop + 1].code == OP_SET_TIP2 &&
-                                      std::max(zpl.piece[p.ops[iop + 1].a], zpl.piece[p.ops[iop + 1].b]) > cur_piece;
-         const bool fuse = fuse_tips && push >= 0 && iop + 1 < nops && p.ops[iop + 1].code == OP_SET_TIP2 && !crossing_cherry;
-         const bool fuse_next = peel && (int)iop == last_mm;     // ... or the next tile's first cherry under the last matmul
-         if (fuse) cross_if({p.ops[iop + 1].a, p.ops[iop + 1].b});
-         // (tip tables the ring could not hold earlier are requested in the first k-block pairs and awaited at the midpoint)
-         // (the cross-lane read of x[60] is issued before the step's wait + barrier so that its latency hides there)
-         if (tail61) s << "   { const double x60 = jit_x60(" << name(cur) << ", lane);\n";
-         // the next tile's first lookups: under this, the tile's last, product — once this tile has consumed its own (a cherry that is a
-         // son of the root comes AFTER the last product and still lives in its AL array: then they are requested in front of ROOT)
-         if (lk_cross && (int)iop == last_mm && !tail_blocks && !fuse && !fuse_next && lk_seen >= lk_ncross) {
-            for (int k = 0; k < lk_ncross; k++) pend_lookup.push_back({LK_ID - k, lookup_text(k, "AL" + std::to_string(k), true)});
-            lk_next_done = true;
-         }
-         const std::string side = step(1, true, (fuse || fuse_next) ? MID : KB2, 1);
-         int tgt = -1;
-         if (fuse || fuse_next) {
-            const Op &nx = fuse ? p.ops[iop + 1] : p.ops[0];
-            tgt = fuse ? alloc() : AS;
-            const int mid = wait_count(consumed + 2);
-            s << "   jit_matvec_tip2<" << (mid < 0 ? 63 : mid) << (tail61 ? ", true, " : ", false, ") << RB << ", " << KB << ">(" << buf(consumed) << ", lane, " << name(cur)
-              << ", " << name(out) << ", " << buf(consumed + 1) << ", " << (fuse ? code(nx.a) : ncode(nx.a)) << ", " << buf(consumed + 2) << ", "
-              << (fuse ? code(nx.b) : ncode(nx.b)) << ", q, " << name(tgt) << ", " << side << colarg(consumed) << (amb_over ? (tail61 ? ", amb" : ", nullptr, 0.0, amb") : "") << ");"
-              << (tail61 ? " }" : "") << "\n";
-            consumed += 3;
-         }
-         else {
-            s << "   jit_matvec<" << (tail61 ? "true" : "false") << ", " << RB << ", " << KB << ">(" << buf(consumed) << ", lane, " << name(cur) << ", "
-              << name(out) << ", "
-              << side << colarg(consumed) << ");" << (tail61 ? " }" : "") << "\n";
-            consumed += 1;
-         }
-         release(cur);
-         if (pop >= 0) {
-            if (slot[pop] == SPILLED)
-               s << "   jit_mul_mem(" << name(out) << ", " << spill_ptr(pop) << ");\n";
-            else {
-               s << "   jit_mul(" << name(out) << ", " << name(slot[pop]) << ");\n";
-               release(slot[pop]);
-            }
-            slot[pop] = -1;
-         }
-         if (push >= JIT_REG_SLOTS) {
-            s << "   jit_spill(" << name(out) << ", " << spill_ptr(push) << ");\n";
-            release(out);
-            slot[push] = SPILLED;
-            cur = -1;
-         }
-         else if (push >= 0) {
-            slot[push] = out;
-            cur = -1;
-         }
-         else
-            cur = out;
-         if (fuse) {      // the SET_TIP2 is done
-            cur = tgt;
-            iop++;
-            stamp(iop);
-         }
-      } break;
-      case OP_SCALE:
-         s << "   { const double fac = jit_scale(" << name(cur) << ", q, n); lnscale += fac;\n"
-           << "     if (a.keep && q == 0 && valid) a.scalef[((long)iclass * a.n_scale + " << o.b << ") * a.n_patt + h] = fac; }\n";
-         break;
-      // STORE / LOAD: eight vector-memory operations per wave, entered in the in-flight list like the ring's DMA pieces, so that the
-      // counted waits that follow let them fly (a wait computed without them would make every block step wait for the stores'
-      // completion in HBM).  At a tile's start the list lacks the previous tile's last stores: those waits are stricter than needed, never laxer.
-      case OP_STORE: {
-         const bool under_product = iop + 1 < nops && (p.ops[iop + 1].code == OP_MATMUL || p.ops[iop + 1].code == OP_MATMUL_POP) && p.ops[iop + 1].a == o.a;
-         if (under_product)      // (the product that follows reads this very array and leaves it alone: see step)
-            for (int i = 0; i < 8; i++)
-               pend_store.push_back("JIT_STORE_PIECE(" + name(cur) + ", JIT_PART_DST(" + std::to_string(o.a) + "), " + std::to_string(i) + ");");
-         else {
-            s << "   jit_store(" << name(cur) << ", JIT_PART_DST(" << o.a << "), lane);\n";
-            fl.push_back({-2, 8});
-         }
-      } break;
-      case OP_LOAD:
-         start_partial();
-         s << "   jit_load(" << name(cur) << ", JIT_PART_PTR(" << o.a << "), lane);\n";
-         fl.push_back({-2, 8});
-         break;
-      case OP_ROOT:
-         // keep-partials mode with scaling nodes: the factors of clean subtrees were stored by earlier evaluations — all of them are
-         // summed from memory in slot order, as the interpreter kernels do (MFMA_ROOT_CASE; treesub.c:7746-7747)
-         cross_if({n_tips});      // (the weight flags: the last row)
-         if (!lk_next_done) issue_next_lookups();
-         if (resident)
-            s << "   if (a.keep && a.n_scale) { lnscale = 0; if (valid) for (int k_ = 0; k_ < a.n_scale; k_++) lnscale += a.scalef[((long)iclass * a.n_scale + k_) * a.n_patt + h]; }\n";
-         s << "   jit_root_lds(a, " << name(cur) << ", lnscale, sPi + (a.n_pi > 1 ? gene : 0) * 64, " << code(n_tips)
-           << ", iclass, q, h, valid);\n";
-         release(cur);
-         cur = -1;
-         break;
-      default: break;
+      }
+      regs.release(in);
+      finish_product(out, pop, push);
+      if (fuse) {      // the SET_TIP2 is done
+         regs.cur = tgt;
+         stamp(++iop);
       }
    }
-   if (!lk_next_done) issue_next_lookups();
-   // programs whose steps never came by a barrier after the tile switch (no operand blocks): request the codes here
-   if (z_pending) {
-      s << "   __syncthreads();\n   JIT2_ISSUE_Z(" << ZP << ")\n";
-      fl.push_back({-1, ZR});
+   void op_scale(const Op &o)
+   {
+      s << "   { const double fac = jit_scale(" << regs.cur.name() << ", q, n); lnscale += fac;\n"
+        << "     if (a.keep && q == 0 && valid) a.scalef[((long)iclass * a.n_scale + " << o.b << ") * a.n_patt + h] = fac; }\n";
    }
-   if (zsingle) {      // all waves are done with this tile's codes: fetch the next tile's (first half) over them, and wait (once per tile)
-      s << "   __syncthreads();\n   " << issue_z << "\n   JIT_WAIT(0); __syncthreads();\n";
-      fl.clear();
+   // STORE / LOAD: eight vector-memory operations per wave, entered in the in-flight list like the ring's DMA pieces (see JitInFlight)
+   void op_store(size_t iop)
+   {
+      const Op &o = p.ops[iop];
+      const bool under_product = iop + 1 < nops && (p.ops[iop + 1].code == OP_MATMUL || p.ops[iop + 1].code == OP_MATMUL_POP) && p.ops[iop + 1].a == o.a;
+      if (under_product)      // (the product that follows reads this very array and leaves it alone: see step_side)
+         for (int i = 0; i < 8; i++)
+            pend_store.push_back("JIT_STORE_PIECE(" + regs.cur.name() + ", JIT_PART_DST(" + std::to_string(o.a) + "), " + std::to_string(i) + ");");
+      else {
+         s << "   jit_store(" << regs.cur.name() << ", JIT_PART_DST(" << o.a << "), lane);\n";
+         fl.issue({JitItem::MEM, 0}, 8);
+      }
    }
-   if (proft) s << "   if (a.prof && tid == 0 && ptc < a.prof_stride - 4) { a.prof[(long)blockIdx.x * a.prof_stride + 1 + ptc] = __builtin_amdgcn_s_memrealtime(); a.prof[(long)blockIdx.x * a.prof_stride + a.prof_stride - 1] = __builtin_amdgcn_s_memtime(); }\n   ptc++;\n";
-   s << "   if (!has_next) break;\n   }\n   JIT_WAIT(0);\n}\n";
-   *first_out = issued - nblk;
-   if (exhausted) return std::string("#error \"jit register arrays exhausted\"\n");
-   return s.str();
-}
+   void op_load(const Op &o)
+   {
+      regs.start_partial();
+      s << "   jit_load(" << regs.cur.name() << ", JIT_PART_PTR(" << o.a << "), lane);\n";
+      fl.issue({JitItem::MEM, 0}, 8);
+   }
+   void op_root()
+   {
+      cross_if({n_tips});      // (the weight flags: the last row)
+      if (!lk_next_done) issue_next_lookups();
+      // keep-partials mode with scaling nodes: the factors of clean subtrees were stored by earlier evaluations — all of them are
+      // summed from memory in slot order, as the interpreter kernels do (MFMA_ROOT_CASE; treesub.c:7746-7747)
+      if (resident)
+         s << "   if (a.keep && a.n_scale) { lnscale = 0; if (valid) for (int k_ = 0; k_ < a.n_scale; k_++) lnscale += a.scalef[((long)iclass * a.n_scale + k_) * a.n_patt + h]; }\n";
+      s << "   jit_root_lds(a, " << regs.cur.name() << ", lnscale, sPi + (a.n_pi > 1 ? gene : 0) * 64, " << code(n_tips)
+        << ", iclass, q, h, valid);\n";
+      regs.end_partial();
+   }
+
+   std::string generate(int *first_out)
+   {
+      defines_and_prologue();
+      front_of_loop();
+      tile_head();
+      for (size_t iop = 0; iop < nops; iop++) {
+         const Op &o = p.ops[iop];
+         stamp(iop);
+         if (iop == 0 && peel) continue;      // done by the predecessor
+         switch (o.code) {
+         case OP_INIT_ONES: case OP_INIT_TIP: op_init(o); break;
+         case OP_SET_TIP: case OP_MUL_TIP: op_tip(o); break;
+         case OP_SET_TIP2: case OP_MUL_TIP2: op_tip2(o); break;
+         case OP_LOOKUP: op_lookup(o); break;
+         case OP_PUSH: regs.push(o.b, [&](JitRegs::Step, const JitArr &c, const JitArr &to) { s << "   jit_spill(" << c.name() << ", " << spill_ptr(to.i) << ");\n"; }); break;
+         case OP_MATMUL: case OP_MATMUL_POP: op_product(iop); break;
+         case OP_SCALE: op_scale(o); break;
+         case OP_STORE: op_store(iop); break;
+         case OP_LOAD: op_load(o); break;
+         case OP_ROOT: op_root(); break;
+         default: break;
+         }
+      }
+      tile_tail();
+      *first_out = issued - nblk;
+      return regs.exhausted ? jit_exhausted_source() : s.str();
+   }
+};
 
 // (`tabs`: p is the table form of the tree's program — jit_cherry_program — and these are its tables)
 inline std::string jit_generate(const Program &p, int n_tips, int n_states = 61, int n_codes = 64, const std::vector<CherryTab> *tabs = nullptr)
 {
+   const JitProf prof;
    int first = 3, got = 3;
-   std::string src = jit_generate_impl(p, n_tips, n_states, n_codes, first, &got, tabs);
+   std::string src = JitWalk(p, n_tips, n_states, n_codes, first, tabs, prof).generate(&got);
    if (got != first) {
       first = got;
-      src = jit_generate_impl(p, n_tips, n_states, n_codes, first, &got, tabs);
+      src = JitWalk(p, n_tips, n_states, n_codes, first, tabs, prof).generate(&got);
    }
    if (got != first) return std::string("#error \"jit schedule does not close\"\n");
    return src;
@@ -750,67 +798,50 @@ inline std::string jit_generate_valu(const Program &p, int N)
    s << "extern \"C\" __global__ __launch_bounds__(256) void prune_jit(PruneArgs a)\n{\n   JV_PROLOGUE(" << N << ")\n";
    const int NA = p.max_stack + 2;
    for (int i = 0; i < NA; i++) s << "   double A" << i << "[N];\n";
-   std::vector<int> freeA;
-   for (int i = NA - 1; i >= 0; i--) freeA.push_back(i);
-   auto alloc = [&]() { int r = freeA.back(); freeA.pop_back(); return r; };
-   auto release = [&](int r) { freeA.push_back(r); };
-   auto name = [&](int r) { return "A" + std::to_string(r); };
-   std::vector<int> slot(256, -1);
-   int cur = -1;
+   JitRegs regs(NA);
+   const JitArr &cur = regs.cur;
    const char *LOOP = "_Pragma(\"unroll\") for (int j = 0; j < N; j++) ";
+   auto mul_popped = [&](JitRegs::Step, const JitArr &out, const JitArr &in) { s << "   " << LOOP << out.name() << "[j] = " << in.name() << "[j] * " << out.name() << "[j];\n"; };
    for (const Op &o : p.ops) {
       switch (o.code) {
       case OP_INIT_ONES:
-         if (cur < 0) cur = alloc();
-         s << "   " << LOOP << name(cur) << "[j] = 1.0;\n";
+         regs.start_partial();
+         s << "   " << LOOP << cur.name() << "[j] = 1.0;\n";
          break;
       case OP_INIT_TIP:
-         if (cur < 0) cur = alloc();
-         s << "   { const int c = JV_CODE(" << o.a << "); " << LOOP << name(cur) << "[j] = (a.cleandata && j == c) ? 1.0 : 0.0; }\n";
+         regs.start_partial();
+         s << "   { const int c = JV_CODE(" << o.a << "); " << LOOP << cur.name() << "[j] = (a.cleandata && j == c) ? 1.0 : 0.0; }\n";
          break;
-      case OP_SET_TIP:
-      case OP_MUL_TIP:
-         if (cur < 0) cur = alloc();
-         s << "   { const double *r = JV_ROW(" << o.a << ", JV_CODE(" << o.a << ")); " << LOOP << name(cur)
+      case OP_SET_TIP: case OP_MUL_TIP:
+         regs.start_partial();
+         s << "   { const double *r = JV_ROW(" << o.a << ", JV_CODE(" << o.a << ")); " << LOOP << cur.name()
            << (o.code == OP_SET_TIP ? "[j] = r[j]; }\n" : "[j] *= r[j]; }\n");
          break;
-      case OP_SET_TIP2:
-      case OP_MUL_TIP2:
-         if (cur < 0) cur = alloc();
+      case OP_SET_TIP2: case OP_MUL_TIP2:
+         regs.start_partial();
          s << "   { const double *r1 = JV_ROW(" << o.a << ", JV_CODE(" << o.a << ")), *r2 = JV_ROW(" << o.b << ", JV_CODE(" << o.b << ")); "
-           << LOOP << name(cur) << (o.code == OP_SET_TIP2 ? "[j] = r1[j] * r2[j]; }\n" : "[j] = (" + name(cur) + "[j] * r1[j]) * r2[j]; }\n");
+           << LOOP << cur.name() << (o.code == OP_SET_TIP2 ? "[j] = r1[j] * r2[j]; }\n" : "[j] = (" + cur.name() + "[j] * r1[j]) * r2[j]; }\n");
          break;
-      case OP_PUSH:
-         slot[o.b] = cur;
-         cur = -1;
-         break;
-      case OP_MATMUL:
-      case OP_MATMUL_POP: {
-         const int pop = mm_pop_slot(o), push = mm_push_slot(o), out = alloc();
-         s << "   jv_matvec<N>(Pint + " << (long)o.a * N * N << ", " << name(cur) << ", " << name(out) << ");\n";
-         release(cur);
-         if (pop >= 0) {
-            s << "   " << LOOP << name(out) << "[j] = " << name(slot[pop]) << "[j] * " << name(out) << "[j];\n";
-            release(slot[pop]);
-            slot[pop] = -1;
-         }
-         if (push >= 0) { slot[push] = out; cur = -1; }
-         else cur = out;
+      case OP_PUSH: regs.push(o.b, mul_popped); break;
+      case OP_MATMUL: case OP_MATMUL_POP: {
+         const JitArr in = cur, out = regs.alloc();
+         s << "   jv_matvec<N>(Pint + " << (long)o.a * N * N << ", " << in.name() << ", " << out.name() << ");\n";
+         regs.release(in);
+         regs.finish_product(out, mm_pop_slot(o), mm_push_slot(o), mul_popped);
       } break;
       case OP_SCALE:
-         s << "   { const double fac = jv_scale<N>(" << name(cur) << "); lnscale += fac;\n"
+         s << "   { const double fac = jv_scale<N>(" << cur.name() << "); lnscale += fac;\n"
            << "     if (a.keep && valid) a.scalef[((long)iclass * a.n_scale + " << o.b << ") * a.n_patt + h] = fac; }\n";
          break;
       case OP_ROOT:
-         s << "   jv_root<N>(a, " << name(cur) << ", lnscale, gene, iclass, h, valid);\n";
-         release(cur);
-         cur = -1;
+         s << "   jv_root<N>(a, " << cur.name() << ", lnscale, gene, iclass, h, valid);\n";
+         regs.end_partial();
          break;
       default: break;
       }
    }
    s << "}\n";
-   return s.str();
+   return regs.exhausted ? jit_exhausted_source() : s.str();
 }
 
 // ---- fused variant (4 / 5 states): classes as the inner loop, tip factors from LDS tables, reduction in the epilogue --------
@@ -988,21 +1019,17 @@ inline std::string jit_generate_valu_fused(const Program &p, int N, int n_tips, 
       s << "         double lnscale" << sfx(r) << " = 0;\n         (void)lnscale" << sfx(r) << ";\n";
       for (int i = 0; i < NA; i++) s << "         double A" << i << sfx(r) << "[N];\n";
    }
-   std::vector<int> freeA;
-   for (int i = NA - 1; i >= 0; i--) freeA.push_back(i);
-   auto alloc = [&]() { int r = freeA.back(); freeA.pop_back(); return r; };
-   auto release = [&](int r) { freeA.push_back(r); };
-   auto name = [&](int a, int r) { return "A" + std::to_string(a) + sfx(r); };
-   std::vector<int> slot(256, -1);
-   int cur = -1, ich = 0;
+   JitRegs regs(NA);
+   auto name = [&](const JitArr &a, int r) { return a.name() + sfx(r); };
+   int ich = 0;
    const char *LOOP = "_Pragma(\"unroll\") for (int j = 0; j < N; j++) ";
+   auto mul_popped = [&](JitRegs::Step, const JitArr &out, const JitArr &in) {
+      for (int r = 0; r < R; r++) s << "         " << LOOP << name(out, r) << "[j] = " << name(in, r) << "[j] * " << name(out, r) << "[j];\n";
+   };
    for (const Op &o : p.ops) {
-      int out = -1, pop = -1, push = -1, curin = cur;
-      if (o.code == OP_INIT_ONES || o.code == OP_INIT_TIP || o.code == OP_SET_TIP || o.code == OP_SET_TIP2) {
-         if (cur < 0) cur = alloc();
-         curin = cur;
-      }
-      if (o.code == OP_MATMUL || o.code == OP_MATMUL_POP) { pop = mm_pop_slot(o); push = mm_push_slot(o); out = alloc(); }
+      if (o.code == OP_INIT_ONES || o.code == OP_INIT_TIP || o.code == OP_SET_TIP || o.code == OP_SET_TIP2) regs.start_partial();
+      const bool mm = o.code == OP_MATMUL || o.code == OP_MATMUL_POP;
+      const JitArr curin = regs.cur, out = mm ? regs.alloc() : JitArr();
       for (int r = 0; r < R; r++) {
          const std::string x = sfx(r), C = name(curin, r);
          switch (o.code) {
@@ -1021,7 +1048,6 @@ inline std::string jit_generate_valu_fused(const Program &p, int N, int n_tips, 
          case OP_MATMUL:
          case OP_MATMUL_POP:
             s << "         jv_matvec<N>(Pint + " << (long)o.a * N * N << ", " << C << ", " << name(out, r) << ");\n";
-            if (pop >= 0) s << "         " << LOOP << name(out, r) << "[j] = " << name(slot[pop], r) << "[j] * " << name(out, r) << "[j];\n";
             break;
          case OP_SCALE: s << "         lnscale" << x << " += jv_scale<N>(" << C << ");\n"; break;
          case OP_ROOT:
@@ -1043,15 +1069,12 @@ inline std::string jit_generate_valu_fused(const Program &p, int N, int n_tips, 
       }
       switch (o.code) {
       case OP_SET_TIP2: if (pl.cherry) ich++; break;
-      case OP_PUSH: slot[o.b] = cur; cur = -1; break;
-      case OP_MATMUL:
-      case OP_MATMUL_POP:
-         release(curin);
-         if (pop >= 0) { release(slot[pop]); slot[pop] = -1; }
-         if (push >= 0) { slot[push] = out; cur = -1; }
-         else cur = out;
+      case OP_PUSH: regs.push(o.b, mul_popped); break;
+      case OP_MATMUL: case OP_MATMUL_POP:
+         regs.release(curin);
+         regs.finish_product(out, mm_pop_slot(o), mm_push_slot(o), mul_popped);
          break;
-      case OP_ROOT: release(cur); cur = -1; break;
+      case OP_ROOT: regs.end_partial(); break;
       default: break;
       }
    }
@@ -1085,7 +1108,7 @@ inline std::string jit_generate_valu_fused(const Program &p, int N, int n_tips, 
    if (CW > 1) s << "   if (cw > 0) acc = 0;\n";
    s << "   red_block_finish<" << CW << ">(acc, a.red_partial + (long)bat * a.nb_stride, a.first_chunk + cb, a.nb_stride, a.red_out + bat, a.red_counter ? a.red_counter + bat * RED_TICKET_WORDS : nullptr);\n";
    s << "   }\n}\n";
-   return s.str();
+   return regs.exhausted ? jit_exhausted_source() : s.str();
 }
 
 // ---- 20 states on v_mfma_f64_4x4x4 (m20_* in device_common.h) -----------------------------------------------------------------
@@ -1110,7 +1133,7 @@ constexpr int M20_LDS_NODES = 46;      // P(t) blocks (3 200 bytes each) kept in
 
 // Several genes (G > 1): a gene has its own P(t), so a persistent workgroup serves one (gene, class): the workgroups of a class are dealt
 // to the genes in proportion to their 32-pattern units (at least one each), and a gene's workgroups cut ITS units into contiguous ranges.
-inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, int G = 1)
+inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, int G = 1, const JitProf &prof = JitProf())
 {
    std::ostringstream s;
    const bool MG = G > 1;
@@ -1139,7 +1162,7 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
    s << "   __shared__ __attribute__((aligned(16))) double sT[NLT * NC * 21];\n";
    s << "   __shared__ int sTicket;\n";
    s << "   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, st = lane >> 4, col = lane & 15;\n";
-   if (getenv("PAML_AMD_PROF_TILES")) s << "   if (a.prof && tid == 0) a.prof[(long)blockIdx.x * a.prof_stride + a.prof_stride - 3] = __builtin_amdgcn_s_memrealtime();      /* kernel entry, before the LDS fill */\n";
+   if (prof.tiles) s << "   if (a.prof && tid == 0) a.prof[(long)blockIdx.x * a.prof_stride + a.prof_stride - 3] = __builtin_amdgcn_s_memrealtime();      /* kernel entry, before the LDS fill */\n";
    if (!MG) s << "   const int iclass = blockIdx.x % a.K, first = blockIdx.x / a.K, stride = gridDim.x / a.K;\n   constexpr int gene = 0, tile0 = 0;\n   const int hbeg = 0;\n   (void)hbeg;\n";
    else {
       // gene g's workgroups (of this class): [g + rest * cum(g) / tot, g + 1 + rest * cum(g + 1) / tot), cum = units of the genes before,
@@ -1181,10 +1204,6 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
    s << "   const int hend = as_const(a.gene_off)[gene + 1];\n";
    s << "   const int zq = st < ZW / 4 ? st : ZW / 4 - 1, bp0 = col * 4;\n";
    s << "   unsigned int zn_0[4], zn_1[4];\n";
-   // Work inside a workgroup is handed out per wave in units of 32 patterns
-   // from an LDS ticket: the two waves of a SIMD do not advance at the same pace (the older wave wins the MFMA arbitration), and
-   // with fixed slots the kernel ended 20 % after its fastest waves had finished.  The first unit of a wave is its own slot; the
-   // next one is drawn a unit ahead, so that its tip codes arrive while the current unit is walked.
    // Work inside a workgroup is handed out per wave by an LDS ticket, in units of 32 patterns (two 16-pattern groups share every
    // operand fetch): the two waves of a SIMD do not advance at the same pace (the older wave wins the MFMA arbitration, 7 units
    // against 5-6), and with fixed slots the kernel ended 20 % after its fastest waves had finished.  The LAST units of a
@@ -1206,10 +1225,8 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
    if (NL > 0) s << "   double Acol[5], AsN[5] = {0, 0, 0, 0, 0};\n   (void)AsN;\n   m20h_read_big(m20_lds_addr(sP), lane, Acol);      /* the first product's big operands (a unit's last product fetches them for the next unit) */\n   (void)aoff;\n";
    else      // (no P(t) block in LDS: the first product's operands come from global memory like every other's)
       s << "   double Acol[5], AsN[5];\n   { const double *Pn_ = Pall + " << (long)mm_nodes[0] * 400 << "; _Pragma(\"unroll\") for (int i = 0; i < 5; i++) { Acol[i] = Pn_[i * 64 + lane]; AsN[i] = Pn_[320 + i * 16 + ((lane >> 4) << 2) + (lane & 3)]; } }\n   (void)aoff; (void)sP;\n";
-   const bool proft = getenv("PAML_AMD_PROF_TILES") != nullptr;      // experiments: workgroup timeline (tools/prof_tiles.py)
-   const char *ptid = getenv("PAML_AMD_PROF_TID");                   // ... stamped by this thread (default 0)
-   const std::string pt = ptid ? ptid : "0";
-   if (proft) s << "   int ptc = 0; if (a.prof && tid == " << pt << ") { a.prof[(long)blockIdx.x * a.prof_stride] = __builtin_amdgcn_s_memrealtime(); a.prof[(long)blockIdx.x * a.prof_stride + a.prof_stride - 2] = __builtin_amdgcn_s_memtime(); }\n";
+   const std::string &pt = prof.tid;
+   if (prof.tiles) s << "   int ptc = 0; if (a.prof && tid == " << pt << ") { a.prof[(long)blockIdx.x * a.prof_stride] = __builtin_amdgcn_s_memrealtime(); a.prof[(long)blockIdx.x * a.prof_stride + a.prof_stride - 2] = __builtin_amdgcn_s_memtime(); }\n";
    // the class's units (32 patterns each, numbered through its 256-pattern tiles) are cut into one contiguous range per workgroup:
    // 10^5 patterns over 64 workgroups are 48 or 49 units each, where whole tiles were 48 or 56
    s << "   const int total_units = " << (MG ? "(hend - hbeg + 31) / 32" : "min(a.n_tiles * 8, (hend + 31) / 32)") << ";\n";
@@ -1225,6 +1242,7 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
    s << "      _Pragma(\"unroll\") for (int i = 0; i < 4; i++) { zw_0[i] = zn_0[i]; zw_1[i] = zn_1[i]; }\n";
    s << "      M20_FETCH_CODES(unext)\n";
    s << "      const int unext2 = M20_TICKET();\n";
+   bool exhausted = false;
    auto emit_body = [&](const int G) {      // the walk over one unit: G = 2 pattern groups, or (half units) group 0 alone
    for (int g = 0; g < G; g++) {
       s << "      const long h_" << g << " = h0 + " << 16 * g << " + col;\n      const bool valid_" << g << " = h_" << g << " < hend;\n";
@@ -1233,12 +1251,12 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
    const int NA = p.max_stack + 2;
    for (int g = 0; g < G; g++)
       for (int i = 0; i < NA; i++) s << "      double A" << i << "_" << g << "[5];\n";
-   std::vector<int> freeA;
-   for (int i = NA - 1; i >= 0; i--) freeA.push_back(i);
-   auto alloc = [&]() { int r = freeA.back(); freeA.pop_back(); return r; };
-   auto release = [&](int r) { freeA.push_back(r); };
-   auto name = [&](int a, int g) { return "A" + std::to_string(a) + "_" + std::to_string(g); };
+   JitRegs regs(NA);
+   auto name = [&](const JitArr &a, int g) { return a.name() + "_" + std::to_string(g); };
    const char *LOOP = "_Pragma(\"unroll\") for (int m = 0; m < 5; m++) ";
+   auto mul_popped = [&](JitRegs::Step, const JitArr &out, const JitArr &in) {
+      for (int g = 0; g < G; g++) s << "      " << LOOP << name(out, g) << "[m] = " << name(in, g) << "[m] * " << name(out, g) << "[m];\n";
+   };
    // Tip rows are gathered from global memory: the loads of the tip steps that follow a matrix product are issued BEFORE that
    // product (its 50 MFMAs cover their latency) and nothing else is allowed to move across a step (sched_barrier): left to
    // itself the compiler hoists every tip load of the tile to the top and spills.
@@ -1279,15 +1297,11 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
    };
    emit_loads_after(-1, 3);
    emit_loads_after(0, 2);
-   std::vector<int> slot(256, -1);
-   int cur = -1, imm = 0;
+   int imm = 0;
    for (size_t iop = 0; iop < nops; iop++) {
       const Op &o = p.ops[iop];
-      int out = -1, pop = -1, push = -1, curin = cur;
-      if (o.code == OP_INIT_ONES || o.code == OP_SET_TIP || o.code == OP_SET_TIP2) {
-         if (cur < 0) cur = alloc();
-         curin = cur;
-      }
+      if (o.code == OP_INIT_ONES || o.code == OP_SET_TIP || o.code == OP_SET_TIP2) regs.start_partial();
+      const JitArr curin = regs.cur, out = is_mm(o) ? regs.alloc() : JitArr();
       switch (o.code) {
       case OP_INIT_ONES:
          for (int g = 0; g < G; g++) s << "      " << LOOP << name(curin, g) << "[m] = 1.0;\n";
@@ -1305,10 +1319,8 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
          for (int g = 0; g < G; g++)
             s << "      " << LOOP << name(curin, g) << "[m] = (" << name(curin, g) << "[m] * T" << iop << "a_" << g << "[m]) * T" << iop << "b_" << g << "[m];\n";
          break;
-      case OP_PUSH: slot[o.b] = cur; cur = -1; break;
-      case OP_MATMUL:
-      case OP_MATMUL_POP:
-         pop = mm_pop_slot(o); push = mm_push_slot(o); out = alloc();
+      case OP_PUSH: regs.push(o.b, mul_popped); break;
+      case OP_MATMUL: case OP_MATMUL_POP:
          emit_loads_after(imm, 1);
          emit_loads_after(imm + 1, 2);
          s << "      __builtin_amdgcn_sched_barrier(0);\n";
@@ -1324,14 +1336,8 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
          }
          s << "      __builtin_amdgcn_sched_barrier(0);\n";
          imm++;
-         release(curin);
-         if (pop >= 0) {
-            for (int g = 0; g < G; g++) s << "      " << LOOP << name(out, g) << "[m] = " << name(slot[pop], g) << "[m] * " << name(out, g) << "[m];\n";
-            release(slot[pop]);
-            slot[pop] = -1;
-         }
-         if (push >= 0) { slot[push] = out; cur = -1; }
-         else cur = out;
+         regs.release(curin);
+         regs.finish_product(out, mm_pop_slot(o), mm_push_slot(o), mul_popped);
          break;
       case OP_SCALE:
          for (int g = 0; g < G; g++)
@@ -1341,22 +1347,22 @@ inline std::string jit_generate_m20(const Program &p, int n_tips, int n_codes, i
       case OP_ROOT:
          for (int g = 0; g < G; g++)
             s << "      m20_root(a, " << name(curin, g) << ", pis, lnscale_" << g << ", iclass, h_" << g << ", st == 0 && valid_" << g << ");\n";
-         release(cur);
-         cur = -1;
+         regs.end_partial();
          break;
       default: break;
       }
    }
+   exhausted = exhausted || regs.exhausted;
    };      // emit_body
    s << "      if (half < 0) {\n";
    emit_body(2);
    s << "      } else {\n";
    emit_body(1);
    s << "      }\n";
-   if (proft) s << "      if (a.prof && tid == " << pt << " && ptc < a.prof_stride - 4) { a.prof[(long)blockIdx.x * a.prof_stride + 1 + ptc] = __builtin_amdgcn_s_memrealtime(); a.prof[(long)blockIdx.x * a.prof_stride + a.prof_stride - 1] = __builtin_amdgcn_s_memtime(); }\n      ptc++;\n";
+   if (prof.tiles) s << "      if (a.prof && tid == " << pt << " && ptc < a.prof_stride - 4) { a.prof[(long)blockIdx.x * a.prof_stride + 1 + ptc] = __builtin_amdgcn_s_memrealtime(); a.prof[(long)blockIdx.x * a.prof_stride + a.prof_stride - 1] = __builtin_amdgcn_s_memtime(); }\n      ptc++;\n";
    s << "      u = unext; unext = unext2;\n";
    s << "   }\n}\n";
-   return s.str();
+   return exhausted ? jit_exhausted_source() : s.str();
 }
 
 // ---- small data sets: the cooperative kernel (prune_mfma64_coop) unrolled for one tree, reduction inside (device_common.h, COOPJ_*) ----
@@ -1433,28 +1439,26 @@ inline std::string jit_generate_coop(const Program &p, int n_tips, int n_states 
    top_up();
    const int NA = p.max_stack + 2;
    for (int i = 0; i < NA; i++) s << "   double A" << i << "[4];\n";
-   std::vector<int> freeA;
-   for (int i = NA - 1; i >= 0; i--) freeA.push_back(i);
-   auto alloc = [&]() { int r = freeA.back(); freeA.pop_back(); return r; };
-   auto release = [&](int r) { freeA.push_back(r); };
-   auto name = [&](int r) { return "A" + std::to_string(r); };
-   std::vector<int> slot(256, -1);
-   int cur = -1, xb = 0;
+   JitRegs regs(NA);
+   const JitArr &cur = regs.cur;
+   auto name = [](const JitArr &a) { return a.name(); };
+   int xb = 0;
    const char *LOOP = "_Pragma(\"unroll\") for (int r = 0; r < 4; r++) ";
+   auto mul_popped = [&](JitRegs::Step, const JitArr &out, const JitArr &in) { s << "   " << LOOP << name(out) << "[r] = " << name(in) << "[r] * " << name(out) << "[r];\n"; };
    for (size_t iop = 0; iop < p.ops.size(); iop++) {
       const Op &o = p.ops[iop];
       const int ra = req_of_op_a[iop], rb = req_of_op_b[iop];
       switch (o.code) {
       case OP_INIT_ONES:
-         if (cur < 0) cur = alloc();
+         regs.start_partial();
          s << "   " << LOOP << name(cur) << "[r] = (4 * (4 * wave + r) + q < n) ? 1.0 : 0.0;\n";
          break;
       case OP_INIT_TIP:
-         if (cur < 0) cur = alloc();
+         regs.start_partial();
          s << "   " << LOOP << name(cur) << "[r] = (a.cleandata && 4 * (4 * wave + r) + q == c" << o.a << ") ? 1.0 : 0.0;\n";
          break;
       case OP_SET_TIP:
-         if (cur < 0) cur = alloc();
+         regs.start_partial();
          s << "   " << name(cur) << "[0] = T" << ra << "a.x; " << name(cur) << "[1] = T" << ra << "a.y; " << name(cur) << "[2] = T" << ra << "b.x; " << name(cur) << "[3] = T" << ra << "b.y;\n";
          consumed(ra);
          break;
@@ -1463,7 +1467,7 @@ inline std::string jit_generate_coop(const Program &p, int n_tips, int n_states 
          consumed(ra);
          break;
       case OP_SET_TIP2:
-         if (cur < 0) cur = alloc();
+         regs.start_partial();
          s << "   " << name(cur) << "[0] = T" << ra << "a.x * T" << rb << "a.x; " << name(cur) << "[1] = T" << ra << "a.y * T" << rb << "a.y; "
            << name(cur) << "[2] = T" << ra << "b.x * T" << rb << "b.x; " << name(cur) << "[3] = T" << ra << "b.y * T" << rb << "b.y;\n";
          consumed(ra); consumed(rb);
@@ -1473,24 +1477,14 @@ inline std::string jit_generate_coop(const Program &p, int n_tips, int n_states 
            << name(cur) << "[2] = (" << name(cur) << "[2] * T" << ra << "b.x) * T" << rb << "b.x; " << name(cur) << "[3] = (" << name(cur) << "[3] * T" << ra << "b.y) * T" << rb << "b.y;\n";
          consumed(ra); consumed(rb);
          break;
-      case OP_PUSH:
-         slot[o.b] = cur;
-         cur = -1;
-         break;
-      case OP_MATMUL:
-      case OP_MATMUL_POP: {
-         const int pop = mm_pop_slot(o), push = mm_push_slot(o), out = alloc();
-         s << "   COOPJ_MATVEC(P" << reqs[ra].id << ", " << name(cur) << ", " << name(out) << ", " << xb << ")\n";
+      case OP_PUSH: regs.push(o.b, mul_popped); break;
+      case OP_MATMUL: case OP_MATMUL_POP: {
+         const JitArr in = cur, out = regs.alloc();
+         s << "   COOPJ_MATVEC(P" << reqs[ra].id << ", " << name(in) << ", " << name(out) << ", " << xb << ")\n";
          xb ^= 1;
          consumed(ra);
-         release(cur);
-         if (pop >= 0) {
-            s << "   " << LOOP << name(out) << "[r] = " << name(slot[pop]) << "[r] * " << name(out) << "[r];\n";
-            release(slot[pop]);
-            slot[pop] = -1;
-         }
-         if (push >= 0) { slot[push] = out; cur = -1; }
-         else cur = out;
+         regs.release(in);
+         regs.finish_product(out, mm_pop_slot(o), mm_push_slot(o), mul_popped);
       } break;
       case OP_SCALE:
          s << "   COOPJ_SCALE(" << name(cur) << ")\n";
@@ -1498,155 +1492,14 @@ inline std::string jit_generate_coop(const Program &p, int n_tips, int n_states 
       case OP_ROOT:
          s << "   COOPJ_ROOT(" << name(cur) << ", " << xb << ")\n";
          xb ^= 1;
-         release(cur);
-         cur = -1;
+         regs.end_partial();
          break;
       default: break;
       }
       if (ra >= 0) top_up();
    }
    s << "   }\n   coopj_finish(a, cj_bat, (int)blockIdx.x - cj_bat * cj_nwg, cj_nwg);\n}\n";
-   return s.str();
-}
-
-inline std::string jit_source_dir()
-{
-   if (const char *e = getenv("PAML_AMD_CSRC")) return e;      // (a variant library built somewhere else: tools/build_variant.sh, PAML_AMD_LIB)
-   Dl_info info;
-   if (dladdr((const void *)&jit_source_dir, &info) && info.dli_fname) {
-      std::string so = info.dli_fname;                 // .../paml_amd/lib/libpaml_amd.so
-      const size_t cut = so.rfind('/');
-      const std::string libdir = cut == std::string::npos ? "." : so.substr(0, cut);
-      return libdir + "/../csrc";
-   }
-   return "paml_amd/csrc";
-}
-
-// Compile `src` for gfx950 (works without a GPU).  Returns 0 on success; `log` gets the compiler output.
-// Code objects are kept on disk, keyed by a hash of the generated source, of the header it includes, of the optimisation
-// level and of the hiprtc version: a tree seen before (another run of the same analysis) costs a file read instead of
-// seconds of hiprtc (0.2 - 19 s per topology, profiles/r01_big_trees.jsonl).  Two places are looked at:
-//   <library dir>/jit/         read-only: code objects built together with the library (__graft_entry__.build() fills it for
-//                              the benchmark's trees), so a fresh machine does not start with a compile;
-//   the user's cache           read-write: $PAML_AMD_JIT_CACHE, else $XDG_CACHE_HOME/paml_amd/jit, else $HOME/.cache/paml_amd/jit;
-//                              PAML_AMD_JIT_CACHE=0 (or empty) switches it off.
-inline const char *jit_opt_level() { return "-O3"; }
-
-inline std::string jit_cache_name(const std::string &src)
-{
-   unsigned long long h = 1469598103934665603ull;
-   auto mix = [&](const std::string &t) { for (unsigned char ch : t) { h ^= ch; h *= 1099511628211ull; } };
-   mix(src);
-   {  // the header the source includes is part of the program
-      FILE *f = fopen((jit_source_dir() + "/device_common.h").c_str(), "rb");
-      if (f) { char buf[4096]; size_t n; while ((n = fread(buf, 1, sizeof(buf), f)) > 0) mix(std::string(buf, n)); fclose(f); }
-   }
-   mix(jit_opt_level());
-   int major = 0, minor = 0;
-   (void)hiprtcVersion(&major, &minor);
-   mix("hiprtc" + std::to_string(major) + "." + std::to_string(minor));
-   char name[64];
-   snprintf(name, sizeof(name), "%016llx.gfx950.hsaco", h);
-   return name;
-}
-
-inline bool jit_mkdirs(const std::string &dir)      // mkdir -p without a shell
-{
-   for (size_t i = 1; i <= dir.size(); i++)
-      if (i == dir.size() || dir[i] == '/') {
-         const std::string sub = dir.substr(0, i);
-         if (mkdir(sub.c_str(), 0777) != 0 && errno != EEXIST) return false;
-      }
-   return true;
-}
-
-inline std::string jit_shipped_dir() { return jit_source_dir() + "/../lib/jit"; }
-
-inline std::string jit_user_cache_dir()
-{
-   const char *c = getenv("PAML_AMD_JIT_CACHE");
-   if (c) return (!*c || !strcmp(c, "0")) ? std::string() : std::string(c);
-   if (const char *x = getenv("XDG_CACHE_HOME"))
-      if (*x) return std::string(x) + "/paml_amd/jit";
-   if (const char *hm = getenv("HOME"))
-      if (*hm) return std::string(hm) + "/.cache/paml_amd/jit";
-   return std::string();
-}
-
-inline bool jit_read_file(const std::string &path, std::vector<char> *code)
-{
-   FILE *f = fopen(path.c_str(), "rb");
-   if (!f) return false;
-   fseek(f, 0, SEEK_END);
-   const long n = ftell(f);
-   rewind(f);
-   code->resize(n > 0 ? n : 0);
-   const bool ok = n > 0 && fread(code->data(), 1, n, f) == (size_t)n;
-   fclose(f);
-   return ok;
-}
-
-inline void jit_write_file(const std::string &dir, const std::string &name, const std::vector<char> &code)
-{
-   if (dir.empty() || !jit_mkdirs(dir)) return;
-   const std::string path = dir + "/" + name, tmp = path + ".tmp" + std::to_string((long)getpid());      // write beside, then rename:
-   FILE *f = fopen(tmp.c_str(), "wb");                                                                    // readers never see a partial file
-   if (!f) return;
-   const bool ok = fwrite(code.data(), 1, code.size(), f) == code.size();
-   fclose(f);
-   if (!ok || rename(tmp.c_str(), path.c_str()) != 0) remove(tmp.c_str());
-}
-
-inline int jit_compile_code(const std::string &src, std::vector<char> *code, std::string *log, const char *store_dir = nullptr)
-{
-   const std::string name = jit_cache_name(src), user = jit_user_cache_dir();
-   if (const char *d = getenv("PAML_AMD_JIT_SRC_DIR")) {      // debugging: every source that reaches the compiler (or its cache), by cache name
-      if (FILE *f = fopen((std::string(d) + "/" + name + ".hip").c_str(), "wb")) { fwrite(src.data(), 1, src.size(), f); fclose(f); }
-   }
-   if (!store_dir) {
-      if (jit_read_file(jit_shipped_dir() + "/" + name, code)) return 0;
-      if (!user.empty() && jit_read_file(user + "/" + name, code)) return 0;
-   }
-   hiprtcProgram prog;
-   if (hiprtcCreateProgram(&prog, src.c_str(), "prune_jit.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
-      *log = "hiprtcCreateProgram failed";
-      return -1;
-   }
-   const std::string inc = "-I" + jit_source_dir();
-   std::vector<const char *> opts = {"--offload-arch=gfx950", jit_opt_level(), "-std=c++17", inc.c_str()};
-   const hiprtcResult r = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
-   size_t ls = 0;
-   hiprtcGetProgramLogSize(prog, &ls);
-   if (ls > 1) {
-      log->resize(ls);
-      hiprtcGetProgramLog(prog, &(*log)[0]);
-   }
-   if (r != HIPRTC_SUCCESS) {
-      hiprtcDestroyProgram(&prog);
-      return -1;
-   }
-   size_t cs = 0;
-   hiprtcGetCodeSize(prog, &cs);
-   code->resize(cs);
-   hiprtcGetCode(prog, code->data());
-   hiprtcDestroyProgram(&prog);
-   jit_write_file(store_dir ? std::string(store_dir) : user, name, *code);
-   return 0;
-}
-
-// The code object of `src` if it is already on disk (the library's lib/jit or the user's cache): no compilation.
-inline bool jit_cached_code(const std::string &src, std::vector<char> *code)
-{
-   const std::string name = jit_cache_name(src), user = jit_user_cache_dir();
-   if (jit_read_file(jit_shipped_dir() + "/" + name, code)) return true;
-   return !user.empty() && jit_read_file(user + "/" + name, code);
-}
-
-inline int jit_load_code(const std::vector<char> &code, JitKernel *out)
-{
-   if (hipModuleLoadData(&out->mod, code.data()) != hipSuccess) return -1;
-   if (hipModuleGetFunction(&out->fn, out->mod, "prune_jit") != hipSuccess) return -1;
-   return 0;
+   return regs.exhausted ? jit_exhausted_source() : s.str();
 }
 
 }  // namespace paml_amd
