@@ -344,6 +344,15 @@ int paml_amd_debug_program(int n_tips, int n_nodes, int root, const int *sons_pt
                            const unsigned char *scale_node, int keep_partials, const unsigned char *clean,
                            int *ops_out, int cap, int *max_stack);
 
+/* Host-only: the bookkeeping of paml_amd_eval_branch (paml_amd/csrc/branch_plan.h) played for n_calls calls on a tree given as for
+ * paml_amd_debug_program (one class, no gene rates): call i works on the branch of node_b[i] with the lengths branch[i][n_nodes], and
+ * every call forms what it finds dirty.  Per call: ends_out[i] = (A, B), up_out[i][n_nodes] the orientation towards the branch,
+ * clean_out[i][n_nodes] the internal nodes whose stored partial served as it was.  For the last call also the program of the dirty
+ * subtrees below A, then B (the P / dP / ddP form's), 4 ints per op, at most cap ops.  Returns their number, or a negative error. */
+int paml_amd_debug_branch_plan(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node,
+                               int n_calls, const int *node_b, const double *branch, int *ends_out, int *up_out, unsigned char *clean_out,
+                               int *ops_out, int cap);
+
 /* Host-only: the order in which set_tips keeps the n_codes (> 64) character codes of a table at 21..64 states — order_out[new code] =
  * the caller's code — given the table and the nz codes of z (the per-tree kernel's rows beyond 64 codes).  Returns n_codes, or a
  * negative error. */

@@ -41,6 +41,43 @@ int paml_amd_debug_program(int n_tips, int n_nodes, int root, const int *sons_pt
    return (int)p.ops.size();
 }
 
+int paml_amd_debug_branch_plan(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node,
+                               int n_calls, const int *node_b, const double *branch, int *ends_out, int *up_out, unsigned char *clean_out,
+                               int *ops_out, int cap)
+{
+   TreeDesc T;
+   if (!tree_from_csr(n_tips, n_nodes, root, sons_ptr, sons, scale_node, &T) || n_calls < 1 || !node_b || !branch || !ends_out || !up_out || !clean_out)
+      return PAML_AMD_EINVAL;
+   const Adjacency adj = adjacency(T);
+   BranchCache bc;
+   Program prog;
+   for (int i = 0; i < n_calls; i++) {
+      const double *br = branch + (size_t)i * n_nodes;
+      BranchPlan p;
+      if (node_b[i] < 0 || node_b[i] >= n_nodes || node_b[i] == root || !branch_ends(T, adj, node_b[i], p)) return PAML_AMD_EINVAL;
+      reset_if_stale(bc, n_nodes, 1, std::vector<double>(1, 1.0));
+      invalidate(bc, T, adj, br);
+      orient(bc, T, adj, p);
+      tree_seen_from(T, adj, br, p);
+      ends_out[2 * i] = p.A; ends_out[2 * i + 1] = p.Bn;
+      std::copy(p.up.begin(), p.up.end(), up_out + (size_t)i * n_nodes);
+      std::copy(p.clean.begin(), p.clean.end(), clean_out + (size_t)i * n_nodes);
+      if (i == n_calls - 1) {
+         std::vector<int> roots;
+         for (int rt : {p.A, p.Bn})
+            if (!T.is_leaf(rt) && !p.clean[rt]) roots.push_back(rt);
+         prog = forest_program(p.tr, roots, p.clean.data(), true);
+      }
+      commit(bc, p, n_tips);
+   }
+   if (ops_out)
+      for (int i = 0; i < (int)prog.ops.size() && i < cap; i++) {
+         ops_out[4 * i] = prog.ops[i].code; ops_out[4 * i + 1] = prog.ops[i].a;
+         ops_out[4 * i + 2] = prog.ops[i].b; ops_out[4 * i + 3] = prog.ops[i].c;
+      }
+   return (int)prog.ops.size();
+}
+
 int paml_amd_debug_code_order(int n_states, int n_codes, const int *n_chara, const unsigned char *chara_map, const unsigned char *z,
                               long nz, int *order_out)
 {

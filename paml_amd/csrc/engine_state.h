@@ -5,7 +5,9 @@
 //                       begin_eval, setup_streams, stage_inputs, choose_kernel (-> PruneKernel, below), ensure_buffers, run_pmat,
 //                       prepare_slot, run_prune (a switch on PruneKernel), dump_op_stamps, reduce.  pmat_args / prune_args fill the
 //                       kernels' argument structures for every site, here and in engine_branch.hip
-//   engine_branch.hip   branch-local lnL(t), dlnL, ddlnL on resident partials; node posteriors
+//   engine_branch.hip   branch-local lnL(t), dlnL, ddlnL on resident partials; node posteriors.  paml_amd_eval_branch is a list of phases over
+//                       one struct of shared locals: check_args, size_partials, plan_call (branch_plan.h: the host-only bookkeeping —
+//                       what is current, the orientation, the tree seen from the branch), send_model, eigen_form or pdp_form, read_back
 //   engine_beb.hip      the BEB grid integral
 //   engine_jitdbg.hip   per-tree kernel generation without an engine (tests, build-time prebuild)
 //   engine_compress.hip site-pattern compression on the device (stand-alone)
@@ -37,6 +39,7 @@
 #include "jit_cache.h"
 #include "kernel_args.h"
 #include "program.h"
+#include "branch_plan.h"
 
 namespace paml_amd {
 static_assert(JIT_SCRATCH_BASE == MFMA_RS, "the per-tree kernel addresses the interpreter's overflow-stack scratch");
@@ -319,19 +322,7 @@ struct paml_amd_engine {
    bool want_m20 = false;             // 20 states on v_mfma_f64_4x4x4 (jit_generate_m20) where the tree allows it
    int fused_threads = 256;
    bool pmat_valid = false;           // d_rowmajor holds the P(t) of an evaluation in the tree's own orientation
-   // branch-local evaluation: resident partials on both sides of every edge, re-used from call to call (eval_branch)
-   struct BranchCache {
-      bool valid = false;
-      int K = 0;
-      std::vector<int> up;            // up[v]: the neighbour v's stored partial looks away from
-      std::vector<char> ok;           // the stored partial of internal node v is current
-      std::vector<double> br, gr;     // branch lengths (by lower node) and gene rates the partials were formed with
-      // eigen-basis form (kernels_branch.h): the coefficients c_k of the branch `coef_node` are in d_bl_coef, formed from the current
-      // partials of its two ends — further trial lengths on that branch need no matrix product
-      bool coef_ok = false;
-      int coef_node = -1;
-      std::vector<char> frag_ok;      // per branch label: V / U^T diag(pi) in operand order and the tips' z rows are in d_bl_efrag / d_bl_ztab
-   } bl;
+   BranchCache bl;                    // branch-local evaluation: which resident partials are current (branch_plan.h)
    DevBuf<double> d_bl_partials, d_bl_scalef, d_bl_frag, d_bl_coef, d_bl_efrag, d_bl_ztab, d_bl_etab, d_bl_ecol;
    bool beig_attr_set = false;
    bool bl_gr_sent = false;           // d_gene_rate holds the gene rates of the branch cache (cleared by whoever else writes the buffer)

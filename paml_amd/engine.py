@@ -30,7 +30,7 @@ EXPORTS = [
     "paml_amd_device_count", "paml_amd_set_device", "paml_amd_shard_bounds", "paml_amd_max_ranks", "paml_amd_flush", "paml_amd_eigen_status", "paml_amd_comm_unique_id", "paml_amd_comm_init", "paml_amd_comm_destroy", "paml_amd_comm_info", "paml_amd_comm_library", "paml_amd_comm_stats", "paml_amd_get_partial_sums", "paml_amd_branch_counters", "paml_amd_branch_coef_hits", "paml_amd_branch_refill_kernels", "paml_amd_branch_kernel_ms",
     "paml_amd_jit_prebuild", "paml_amd_profile", "paml_amd_profile_read", "paml_amd_counters", "paml_amd_kernel_name", "paml_amd_debug_program", "paml_amd_debug_jit",
     "paml_amd_cherry_tables", "paml_amd_debug_jit_tables",
-    "paml_amd_debug_code_order",
+    "paml_amd_debug_code_order", "paml_amd_debug_branch_plan",
     "paml_amd_pairset_create", "paml_amd_pairset_destroy", "paml_amd_pairset_get_counts", "paml_amd_pairset_set_pi", "paml_amd_pairset_set_pattern",
     "paml_amd_pairset_eval", "paml_amd_pairset_failed", "paml_amd_pairset_counters",
     "paml_amd_rell_replicates", "paml_amd_rell_info",
@@ -617,6 +617,29 @@ def debug_program(tree, scale_node=None, keep=False, clean=None):
     if nops < 0:
         raise EngineError("debug_program failed (%d)" % nops)
     return [tuple(int(v) for v in r) for r in ops[:nops]], ms.value
+
+
+def debug_branch_plan(tree, calls, scale_node=None):
+    """Host-only: the bookkeeping of eval_branch (paml_amd_debug_branch_plan) played for `calls`, a list of (node_b, branch[n_nodes]),
+    each call forming what it finds dirty.  Returns (ends [n_calls][2] = (A, B), up [n_calls][n_nodes], clean [n_calls][n_nodes], the ops
+    of the last call's program of dirty subtrees as debug_program gives them)."""
+    L = lib()
+    ptr, flat = tree.csr()
+    sc = None if scale_node is None else np.ascontiguousarray(scale_node, dtype=np.uint8)
+    nb = np.ascontiguousarray([c[0] for c in calls], dtype=np.int32)
+    br = np.ascontiguousarray([c[1] for c in calls], dtype=np.float64).reshape(len(calls), tree.n_nodes)
+    ends = np.zeros((len(calls), 2), dtype=np.int32)
+    up = np.zeros((len(calls), tree.n_nodes), dtype=np.int32)
+    clean = np.zeros((len(calls), tree.n_nodes), dtype=np.uint8)
+    cap = 8 * tree.n_nodes + 8
+    ops = np.zeros((cap, 4), dtype=np.int32)
+    L.paml_amd_debug_branch_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    nops = L.paml_amd_debug_branch_plan(tree.n_tips, tree.n_nodes, tree.root, _p(ptr), _p(flat), _p(sc), len(calls), _p(nb), _p(br),
+                                        _p(ends), _p(up), _p(clean), _p(ops), cap)
+    if nops < 0:
+        raise EngineError("debug_branch_plan failed (%d)" % nops)
+    return ends, up, clean, [tuple(int(v) for v in r) for r in ops[:nops]]
 
 
 def debug_code_order(n_states, n_chara, chara_map, z):

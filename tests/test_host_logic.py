@@ -187,6 +187,132 @@ def test_set_node_scale_matches_reference_rule():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# The bookkeeping of eval_branch (paml_amd/csrc/branch_plan.h), played without a GPU through paml_amd_debug_branch_plan, against a
+# brute-force restatement: sides of an edge by graph search on the undirected tree, nothing taken from the planner.
+# ---------------------------------------------------------------------------------------------------------------------
+def _branch_plan_tree(kind):
+    if kind == "tips9":
+        pb = helpers.random_problem(4, 9, 4, seed=21)
+    elif kind == "tips20":
+        pb = helpers.random_problem(4, 20, 4, seed=22)
+    elif kind == "polytomy":
+        pb = helpers.random_problem(4, 11, 4, seed=23, polytomy=True)
+    elif kind == "scaled":
+        pb = helpers.random_problem(4, 20, 4, seed=24, scale_every=4)
+        assert pb.scale_node.sum() >= 2
+    else:      # rooted at a tip, as test_young_ancestor_root_is_tip builds it
+        from paml_amd.problem import Tree
+        for seed in range(8, 40):
+            pb = helpers.random_problem(4, 9, 4, seed=seed)
+            t = pb.tree
+            tip_sons = [s for s in t.sons[t.root] if s < t.n_tips]
+            if tip_sons:
+                sons = [list(s) for s in t.sons]
+                sons[t.root].remove(tip_sons[0])
+                sons[tip_sons[0]] = [t.root]
+                br = t.branch.copy()
+                br[t.root], br[tip_sons[0]] = br[tip_sons[0]], 0
+                pb.tree = Tree(t.n_tips, t.n_nodes, tip_sons[0], sons, br, t.label)
+                break
+    return pb.tree, pb.scale_node
+
+
+def _branch_plan_calls(t, rng):
+    """About 30 calls: every branch in pre-order with the lengths as they are; one length changed per call, at node_b and away from it;
+    all lengths at once; and two more moves."""
+    pre = []
+
+    def walk(i):
+        if i != t.root:
+            pre.append(i)
+        for c in t.sons[i]:
+            walk(c)
+    walk(t.root)
+    br = np.array(t.branch, dtype=float)
+    calls = [(b, br.copy()) for b in pre]
+    edges = [x for x in range(t.n_nodes) if x != t.root]
+    for k in range(10):
+        nb = pre[int(rng.integers(len(pre)))] if k % 3 == 0 else calls[-1][0]
+        x = nb if k % 2 == 0 else int(rng.choice([y for y in edges if y != nb]))
+        br[x] *= 1.5
+        calls.append((nb, br.copy()))
+    br = br * rng.uniform(0.5, 2.0, size=br.size)
+    calls.append((calls[-1][0], br.copy()))
+    calls.append((pre[len(pre) // 2], br.copy()))
+    br[pre[0]] += 0.01
+    calls.append((pre[-1], br.copy()))
+    return calls
+
+
+@pytest.mark.parametrize("kind", ["tips9", "tips20", "polytomy", "tip_root", "scaled"])
+def test_branch_plan_against_brute_force(lib_path, kind):
+    t, scale = _branch_plan_tree(kind)
+    nn, nt = t.n_nodes, t.n_tips
+    father = t.father()
+    nbr = [set(t.sons[v]) | ({int(father[v])} if father[v] >= 0 else set()) for v in range(nn)]
+
+    def side(v, cut):      # the nodes on v's side of the edge (v, cut)
+        seen, todo = {v}, [v]
+        while todo:
+            u = todo.pop()
+            for w in nbr[u]:
+                if w not in seen and not (u == v and w == cut):
+                    seen.add(w)
+                    todo.append(w)
+        return seen
+
+    calls = _branch_plan_calls(t, np.random.default_rng(5))
+    ends, up, clean, _ = engine.debug_branch_plan(t, calls, scale)
+    only_own_length = 0
+    for i, (nb, br) in enumerate(calls):
+        A, Bn = int(father[nb]), nb
+        assert tuple(ends[i]) == (A, Bn)
+        # up[] points along the unique path towards the branch
+        for v in range(nn):
+            want = Bn if v == A else A if v == Bn else [w for w in nbr[v] if A in side(w, v)][0]
+            assert up[i, v] == want, (i, v)
+        if i == 0:
+            assert not clean[i].any()
+            continue
+        moved = [x for x in range(nn) if x != t.root and br[x] != calls[i - 1][1][x]]
+        for v in range(nn):
+            s = side(v, up[i, v])
+            want = v >= nt and up[i, v] == up[i - 1, v] and not any(x in s and father[x] in s for x in moved)
+            assert bool(clean[i, v]) == want, (i, v)
+        if moved == [nb] and calls[i - 1][0] == nb:
+            only_own_length += 1
+            assert clean[i, nt:].all()
+    assert only_own_length >= 2
+
+    # the program of the dirty subtrees, for every prefix of the sequence
+    for k in range(1, len(calls) + 1):
+        e_, up_, clean_, ops = engine.debug_branch_plan(t, calls[:k], scale)
+        assert (up_[-1] == up[k - 1]).all() and (clean_[-1] == clean[k - 1]).all()
+        A, Bn = (int(x) for x in e_[-1])
+        u, cl = up_[-1], clean_[-1]
+        assert ops[-1][0] == OP["END"] and not any(o[0] in (OP["ROOT"], OP["END"]) for o in ops[:-1])
+        mm = [o for o in ops if o[0] in (OP["MATMUL"], OP["MATMUL_POP"])]
+        for cur, nxt in zip(mm, mm[1:]):
+            assert cur[3] == nxt[1]
+        assert not mm or mm[-1][3] == -1
+        dirty = []
+
+        def below(v):      # v is formed by the program, and so is every dirty internal node among its sons in the tree seen from the branch
+            if v >= nt:
+                dirty.append(v)
+            for w in nbr[v] - {int(u[v])}:
+                if len(nbr[w]) > 1 and not cl[w]:
+                    below(w)
+        for end in (A, Bn):
+            if t.sons[end] and not cl[end]:
+                below(end)
+        assert sorted(o[1] for o in ops if o[0] == OP["STORE"]) == sorted(dirty)
+        assert all(cl[o[1]] for o in ops if o[0] == OP["LOAD"])
+        if not cl[nt:].all():
+            assert dirty      # (a dirty node is always reachable from a dirty end)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Static check of the specialised kernel's schedule (jit.h): the generated source is a straight line of building-block
 # calls whose correctness rests on bookkeeping done at generation time — which ring buffer a block sits in, how many
 # DMA pieces may still be in flight at each s_waitcnt, which barrier separates the last reader of a buffer from the
