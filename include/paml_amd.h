@@ -439,6 +439,38 @@ int paml_amd_simulate(paml_amd_engine *e, const double *branch, const double *ge
  * the walk) by HIP events (ms, summed over the batches); either pointer may be NULL. */
 void paml_amd_simulate_info(int *last_batches, double *last_kernel_ms);
 
+/* ---- Ancestral reconstruction at every internal node in one call (AncestralSeqs treesub.c:7071; the definitions and the kernels are
+ * written out in csrc/kernels_ancestral.h).  Both calls are synchronous, build the P(t) an evaluation at (branch[n_nodes],
+ * gene_rate[n_genes] or NULL = 1) would build, by the same kernels, start eval_branch's resident state over, and leave a following
+ * paml_amd_eval its bits.  n_patt is walked gene by gene in batches of what a workspace holds (256 MiB; the environment variable
+ * PAML_AMD_ANC_ARENA_MB gives another size in MiB): never PAML_AMD_ENOMEM because of n_patt or n_query, and a pattern's result has the
+ * same bits whatever batch it falls in.  An engine with a communicator works on its shard's own patterns; nothing is exchanged.
+ * PAML_AMD_EINVAL (with a message) for a null branch or output (post alone may be NULL), n_query < 1 with non-NULL nodes, a queried
+ * node that is a tip, out of range or listed twice, a model or tips not set; PAML_AMD_ENOCONV as the other synchronous entries.
+ *
+ * AncestralMarginal / PostProbNode (treesub.c:6288, 6142) for many nodes at once: one down pass, one outer pass, then every queried
+ * node's posterior — what paml_amd_node_posterior returns for the node, without a pass per node.  K classes, several genes, branch
+ * labels, ambiguity codes, polytomies, scaling nodes, a root that is a tip.  Reversible models only: PAML_AMD_EUNSUPPORTED for a
+ * rate-matrix (UNREST) set, as paml_amd_node_posterior.  best = the lowest state among the maxima of the node's posterior, best_prob
+ * the bits of post[best].  Afterwards paml_amd_get_pmat refuses until the next evaluation, as after paml_amd_node_posterior. */
+int paml_amd_ancestral_marginal(paml_amd_engine *e, const double *branch, const double *gene_rate,
+                                int n_query, const int *nodes /* internal nodes; NULL = all, in node order */,
+                                unsigned char *best   /* [n_query][n_patt] most probable state */,
+                                double *best_prob     /* [n_query][n_patt] its posterior */,
+                                double *post          /* [n_query][n_patt][n_states], or NULL */);
+
+/* AncestralJointPPSG2000 (treesub.c:6964; Pupko et al. 2000), best assignment only, in logarithms (the reference's -log P,
+ * treesub.c:7043-7046: a tree of a few hundred nodes underflows the product).  One class (PAML_AMD_EUNSUPPORTED for K != 1), any number
+ * of genes.  Sums over sons run in the order of the tree's son lists and the lowest state wins among equal maxima.  Afterwards
+ * paml_amd_get_pmat returns the matrices the call used. */
+int paml_amd_ancestral_joint(paml_amd_engine *e, const double *branch, const double *gene_rate,
+                             unsigned char *states /* [n_nodes - n_tips][n_patt], internal nodes in node order */,
+                             double *ln_best       /* [n_patt] log joint probability of data and assignment */);
+
+/* The number of batches the calling thread's last ancestral call walked and the time of its kernels by HIP events (ms, summed over the
+ * batches); either pointer may be NULL. */
+void paml_amd_ancestral_info(int *last_batches, double *last_kernel_ms);
+
 /* ---- Pairwise maximum-likelihood comparisons (codeml runmode = -2; PairwiseCodon codeml.c:4344-4604, Goldman & Yang 1994).
  * The reference takes the ns (ns - 1) / 2 pairs one after the other, each a search over (t, kappa, omega) whose every function call
  * (lfun2dSdN codeml.c:4219-4264) decomposes a rate matrix on one core.  Here a PAIR SET lives on an engine whose tips are clean data

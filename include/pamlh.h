@@ -92,6 +92,7 @@ const double *pamlh_adg_matrix(const pamlh *p);         /* [K][K] auto-discrete-
  * caller frees it with pamlh_free. */
 int pamlh_gene_subset(const pamlh *p, int g, pamlh **out);
 int pamlh_mgene(const pamlh *p);                       /* the Mgene option in effect (0 with one gene) */
+int pamlh_n_classes(const pamlh *p);                   /* site classes of the model as set up (1: none) */
 int pamlh_malpha(const pamlh *p);      /* 1: a gamma shape per gene (Malpha); pamlh_rate() then returns [n_genes][K] */
 int pamlh_genes(const pamlh *p, const int **gene_off, const double **gene_rate, int *n_pi, const int **gene_eigen_of);            /* [K][n_labels] time scale per (class, branch type); NULL = all 1 */
 /* eigen system i: kind (paml_amd.h), and pointers (NULL when not applicable) */
@@ -160,6 +161,12 @@ int pamlh_node_posterior(pamlh *p, int node, double *post);
 /* Joint ancestral reconstruction (Pupko et al. 2000; the reference's "(2) Joint reconstruction" in rst): the most probable
  * assignment of states to all internal nodes per pattern — states[n_patt][n_nodes - n_tips] in node order — and its probability. */
 int pamlh_joint_reconstruction(pamlh *p, int *states, double *prob);
+/* Both reconstructions at every internal node in one engine call each (paml_amd_ancestral_marginal / paml_amd_ancestral_joint), at
+ * the current model state; ni = n_nodes - n_tips internal nodes in node order.  Marginal: best[ni][n_patt] the most probable state,
+ * prob[ni][n_patt] its posterior, post[ni][n_patt][n_states] or NULL.  Joint (one rate class; refused otherwise): states[ni][n_patt] and
+ * ln_best[n_patt] = log Pr(data, assignment) — exp(ln_best - ln f_h) is pamlh_joint_reconstruction's prob. */
+int pamlh_ancestral_marginal(pamlh *p, unsigned char *best, double *prob, double *post);
+int pamlh_ancestral_joint(pamlh *p, unsigned char *states, double *ln_best);
 int pamlh_beb(pamlh *p, const double *x, double *pr_pos, double *mean_w, double *se_w);
 /* BEB under branch-site model A and clade models C / D with two branch types (lfunNSsites_ACD codeml.c:6827):
  * post[nc][n_patt] = posterior of the site classes; nc = 4 for A (classes 0, 1, 2a, 2b: Pr(positive selection on the foreground)

@@ -12,6 +12,7 @@
 //   engine_jitdbg.hip   per-tree kernel generation without an engine (tests, build-time prebuild)
 //   engine_compress.hip site-pattern compression on the device (stand-alone)
 //   engine_simulate.hip alignments drawn under the loaded model (P(t) by launch_pmat, then its own kernels)
+//   engine_ancestral.hip marginal and joint ancestral reconstruction at every internal node (P(t) by launch_pmat, then its own kernels)
 // Built for gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>

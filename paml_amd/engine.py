@@ -35,6 +35,7 @@ EXPORTS = [
     "paml_amd_pairset_eval", "paml_amd_pairset_failed", "paml_amd_pairset_counters",
     "paml_amd_rell_replicates", "paml_amd_rell_info",
     "paml_amd_simulate", "paml_amd_simulate_info",
+    "paml_amd_ancestral_marginal", "paml_amd_ancestral_joint", "paml_amd_ancestral_info",
 ]
 
 
@@ -49,7 +50,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -452,6 +453,31 @@ class Engine:
         self._chk(self._L.paml_amd_simulate(self._h, _p(b), _p(g), n_sites, int(first_site), int(seed) & (2**64 - 1), int(replicate), _p(z), _p(cls), _p(anc)))
         return dict(z=z, cls=cls, anc=anc)
 
+    def ancestral_marginal(self, branch, gene_rate=None, nodes=None, want_post=True):
+        """Marginal reconstruction at many internal nodes in one call (paml_amd_ancestral_marginal): dict(best=[n_query][n_patt] uint8,
+        prob=[n_query][n_patt], post=[n_query][n_patt][n] or None).  nodes None: every internal node, in node order."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        nd = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32)
+        nq = max(self.n_nodes - self.n_tips, 0) if nd is None else len(nd)
+        best = np.zeros((nq, self.n_patt), dtype=np.uint8)
+        prob = np.zeros((nq, self.n_patt))
+        post = np.zeros((nq, self.n_patt, self.n)) if want_post else None
+        self._L.paml_amd_ancestral_marginal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self._L.paml_amd_ancestral_marginal(self._h, _p(b), _p(g), 0 if nd is None else len(nd), _p(nd), _p(best), _p(prob), _p(post)))
+        return dict(best=best, prob=prob, post=post)
+
+    def ancestral_joint(self, branch, gene_rate=None):
+        """Joint reconstruction, best assignment only (paml_amd_ancestral_joint): dict(states=[n_nodes - n_tips][n_patt] uint8,
+        ln_best=[n_patt] log probability of data and assignment).  One class."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        states = np.zeros((max(self.n_nodes - self.n_tips, 0), self.n_patt), dtype=np.uint8)
+        ln_best = np.zeros(self.n_patt)
+        self._L.paml_amd_ancestral_joint.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self._L.paml_amd_ancestral_joint(self._h, _p(b), _p(g), _p(states), _p(ln_best)))
+        return dict(states=states, ln_best=ln_best)
+
     def get_pmat(self, gene, iclass, node):
         P = np.zeros((self.n, self.n))
         self._chk(self._L.paml_amd_get_pmat(self._h, gene, iclass, node, _p(P)))
@@ -750,6 +776,17 @@ def simulate_info():
     L.paml_amd_simulate_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.paml_amd_simulate_info.restype = None
     L.paml_amd_simulate_info(C.byref(nb), C.byref(ms))
+    return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def ancestral_info():
+    """Batches walked by this thread's last Engine.ancestral_marginal / ancestral_joint and the time of its kernels by HIP events
+    (paml_amd_ancestral_info): dict(last_batches, last_kernel_ms)."""
+    L = lib()
+    nb, ms = C.c_int(), C.c_double()
+    L.paml_amd_ancestral_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.paml_amd_ancestral_info.restype = None
+    L.paml_amd_ancestral_info(C.byref(nb), C.byref(ms))
     return dict(last_batches=nb.value, last_kernel_ms=ms.value)
 
 

@@ -1,5 +1,5 @@
 /* pamlh_lnl — command-line driver: one likelihood evaluation of a codeml/baseml analysis on the MI355X.
- *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize] [--ancestral] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
+ *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
  *   (--set "key = value": replaces an option of the control file, e.g. one of the site models of an "NSsites = 0 1 2 7 8" list;
  *    --tree K: the K-th tree of the tree file, 1-based; --all-trees: every tree in turn — the reference's loop, Forestry codeml.c:635 —
  *    each optimised from the control file's initial values, then the comparison table of rell(), treesub.c:5844;
@@ -16,6 +16,7 @@
  * maximum-likelihood search (pamlh_optimize: BFGS with batched finite differences) and the estimates are printed.
  * A control file with runmode = -2 (codeml) is the pairwise comparison instead: the estimates of every pair are printed and 2ML.t,
  * 2ML.dN, 2ML.dS and rst are written into the working directory in the reference's layout (pamlh_pairwise). */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -116,7 +117,7 @@ int main(int argc, char **argv)
    pamlh *p;
    char err[512];
    double x[4096], lnL, *lnf;
-   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0;
+   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0;
    char over[2048] = "";
    const char *sim_out = NULL;
    long sim_sites = 0;
@@ -124,10 +125,11 @@ int main(int argc, char **argv)
    unsigned char comm_id[PAML_AMD_COMM_ID_BYTES];
    int device[MAX_RANKS];
    for (i = 0; i < MAX_RANKS; i++) device[i] = i;
-   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize] [--ancestral] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
+   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
    for (i = 3; i < argc && nx < 4096; i++) {
       if (!strcmp(argv[i], "--optimize")) optimize = 1;
       else if (!strcmp(argv[i], "--ancestral")) ancestral = 1;
+      else if (!strcmp(argv[i], "--ancestral-all")) ancestral_all = 1;
       else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
       else if (!strcmp(argv[i], "--devices") && i + 1 < argc) {      /* the GPU of each rank, e.g. "4,5,6,7" */
          int k = 0;
@@ -211,7 +213,7 @@ int main(int argc, char **argv)
       return 0;
    }
    pamlh_dims(p, NULL, NULL, &npatt, NULL, NULL, NULL, NULL, NULL, &np, &ntime);
-   if (gpus > 0 && (ancestral || pamlh_mgene(p) == 1)) { fprintf(stderr, "error: --gpus gives lnL and estimates; per-site outputs and Mgene = 1 need the whole alignment on one GPU\n"); return 1; }
+   if (gpus > 0 && (ancestral || ancestral_all || pamlh_mgene(p) == 1)) { fprintf(stderr, "error: --gpus gives lnL and estimates; per-site outputs and Mgene = 1 need the whole alignment on one GPU\n"); return 1; }
    if (pamlh_mgene(p) == 1) {      /* separate analyses: every gene on its own (start values: the control file's), lnL summed */
       const int ng = pamlh_genes(p, NULL, NULL, NULL, NULL);
       double sum = 0;
@@ -387,6 +389,43 @@ int main(int argc, char **argv)
          printf("\n");
       }
       free(post); free(best); free(best_p);
+   }
+   if (ancestral_all) {   /* the same marginal table from ONE engine call for all nodes, then (one rate class) the joint reconstruction */
+      static const char *const alpha[3] = {"TCAG", "", "ARNDCQEGHILKMFPSTWYV"};
+      int n, ns, nnode, seqtype_n, n_sites, h, node, ni;
+      const int *pose = pamlh_pose(p, &n_sites);
+      double *best_p;
+      unsigned char *best;
+      pamlh_dims(p, &n, &ns, NULL, &nnode, NULL, NULL, NULL, NULL, NULL, NULL);
+      seqtype_n = n == 4 ? 0 : n == 20 ? 2 : 1;
+      ni = nnode - ns;
+      best = (unsigned char *)malloc((size_t)ni * npatt);
+      best_p = (double *)malloc((size_t)ni * npatt * sizeof(double));
+      if (pamlh_ancestral_marginal(p, best, best_p, NULL)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      printf("\nMarginal reconstruction of ancestral states: site, then for nodes %d..%d the most probable state (probability)\n", ns + 1, nnode);
+      for (h = 0; h < n_sites; h++) {
+         printf("%6d ", h + 1);
+         for (node = ns; node < nnode; node++) {
+            const int b = best[(size_t)(node - ns) * npatt + pose[h]];
+            if (seqtype_n == 1) printf(" %2d(%.3f)", b, best_p[(size_t)(node - ns) * npatt + pose[h]]);      /* codons: index among the sense codons */
+            else printf(" %c(%.3f)", alpha[seqtype_n][b], best_p[(size_t)(node - ns) * npatt + pose[h]]);
+         }
+         printf("\n");
+      }
+      if (pamlh_n_classes(p) == 1) {
+         if (pamlh_ancestral_joint(p, best, best_p)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+         printf("\nJoint reconstruction of ancestral states: site, the states at nodes %d..%d, the probability of the assignment\n", ns + 1, nnode);
+         for (h = 0; h < n_sites; h++) {
+            printf("%6d  ", h + 1);
+            for (node = ns; node < nnode; node++) {
+               const int b = best[(size_t)(node - ns) * npatt + pose[h]];
+               if (seqtype_n == 1) printf(" %2d", b);
+               else printf("%c", alpha[seqtype_n][b]);
+            }
+            printf("  %.3f\n", exp(best_p[pose[h]] - lnf[pose[h]]));
+         }
+      }
+      free(best); free(best_p);
    }
    pamlh_write_lnf(p, "lnf", lnf);
    free(lnf);

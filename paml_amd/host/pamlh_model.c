@@ -1804,6 +1804,7 @@ int pamlh_set_x(pamlh *p, const double *x, int np)
 
 int pamlh_mgene(const pamlh *p) { return p->ngene > 1 ? p->mgene : 0; }
 int pamlh_malpha(const pamlh *p) { return p->malpha; }
+int pamlh_n_classes(const pamlh *p) { return p->K; }
 
 /* Mgene = 1: gene g of the data set as an analysis of its own — its patterns, weights and site map, frequencies counted from
  * its sites, the same tree and options, one gene, its own parameter vector (MultipleGenes / GetSubSeqs in the reference).
@@ -2193,6 +2194,33 @@ int pamlh_joint_reconstruction(pamlh *p, int *states, double *prob)
       }
    }
    free(lnf); free(P); free(L); free(choice); free(best_of); free(order);
+   return 0;
+}
+
+/* Marginal reconstruction at EVERY internal node in one engine call (paml_amd_ancestral_marginal: one down pass and one outer pass
+ * instead of a pass per node) at the current model state: best[ni][npatt] the most probable state, prob[ni][npatt] its posterior,
+ * post[ni][npatt][n] (may be NULL) all of them; ni = nnode - ns internal nodes in node order. */
+int pamlh_ancestral_marginal(pamlh *p, unsigned char *best, double *prob, double *post)
+{
+   double lnL;
+   int rc;
+   if ((rc = pamlh_eval_gpu(p, &lnL, NULL))) return rc;       /* uploads pi, eigen systems and classes of the current state */
+   if ((rc = paml_amd_ancestral_marginal(p->eng, p->branch, p->ngene > 1 ? p->rgene : NULL, 0, NULL, best, prob, post)))
+      return pamlh_fail(p, "%s", paml_amd_last_error(p->eng));
+   return 0;
+}
+
+/* Joint reconstruction on the device, in logarithms (paml_amd_ancestral_joint; AncestralJointPPSG2000 treesub.c:6964): states[ni][npatt]
+ * and ln_best[npatt] = log Pr(data, best assignment); exp(ln_best - ln f_h) is the probability the host routine above reports.  One rate
+ * class, any number of genes. */
+int pamlh_ancestral_joint(pamlh *p, unsigned char *states, double *ln_best)
+{
+   double lnL;
+   int rc;
+   if (p->K != 1) return pamlh_fail(p, "pamlh_ancestral_joint: the joint reconstruction needs a model with one rate class (this one has %d)", p->K);
+   if ((rc = pamlh_eval_gpu(p, &lnL, NULL))) return rc;
+   if ((rc = paml_amd_ancestral_joint(p->eng, p->branch, p->ngene > 1 ? p->rgene : NULL, states, ln_best)))
+      return pamlh_fail(p, "%s", paml_amd_last_error(p->eng));
    return 0;
 }
 

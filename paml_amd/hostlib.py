@@ -446,6 +446,29 @@ class Analysis:
             raise RuntimeError("pamlh_joint_reconstruction: " + self._L.pamlh_error(self._h).decode())
         return st, pr
 
+    def ancestral_marginal(self, x, want_post=True):
+        """Marginal reconstruction at every internal node at x in one engine call (pamlh_ancestral_marginal): dict(best=[ni][n_patt]
+        uint8, prob=[ni][n_patt], post=[ni][n_patt][n] or None)."""
+        self.set_x(x)
+        ni = self.n_nodes - self.n_tips
+        best, prob = np.zeros((ni, self.n_patt), dtype=np.uint8), np.zeros((ni, self.n_patt))
+        post = np.zeros((ni, self.n_patt, self.n)) if want_post else None
+        self._L.pamlh_ancestral_marginal.argtypes = [C.c_void_p] * 4
+        if self._L.pamlh_ancestral_marginal(self._h, best.ctypes.data_as(C.c_void_p), prob.ctypes.data_as(C.c_void_p),
+                                            None if post is None else post.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_ancestral_marginal: " + self._L.pamlh_error(self._h).decode())
+        return dict(best=best, prob=prob, post=post)
+
+    def ancestral_joint(self, x):
+        """Joint reconstruction at x on the device (pamlh_ancestral_joint): dict(states=[ni][n_patt] uint8, ln_best=[n_patt])."""
+        self.set_x(x)
+        ni = self.n_nodes - self.n_tips
+        st, lb = np.zeros((ni, self.n_patt), dtype=np.uint8), np.zeros(self.n_patt)
+        self._L.pamlh_ancestral_joint.argtypes = [C.c_void_p] * 3
+        if self._L.pamlh_ancestral_joint(self._h, st.ctypes.data_as(C.c_void_p), lb.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_ancestral_joint: " + self._L.pamlh_error(self._h).decode())
+        return dict(states=st, ln_best=lb)
+
     def beb_acd(self, x):
         """BEB under branch-site model A (4 site classes: 0, 1, 2a, 2b) or clade model C / D (3) at x: class posteriors per site,
         [nc][n_sites] (pamlh_beb_acd)."""
