@@ -328,7 +328,7 @@ int paml_amd_profile_read(paml_amd_engine *e, double *ms_pmat, double *ms_prune,
 /* Counters mirroring NFunCall / NPMatUVRoot (tools.c:88, printed codeml.c:770). */
 int paml_amd_counters(const paml_amd_engine *e, long *n_eval, long *n_pmat);
 
-/* Cherry tables of the last evaluation.  On large codon data sets (61..64 states, at most 64 character codes, one gene and one
+/* Cherry tables of the last evaluation.  On large codon data sets (60..64 states, at most 64 character codes, one gene and one
  * frequency vector, no PAML_AMD_KEEP_PARTIALS, single evaluations, at most 95 tips — trees whose tip codes fit two LDS blocks of the
  * per-tree kernel —; from PAML_AMD_CHERRY_MIN_PATT = 32768 patterns of this engine on, where per-tree kernels are on)
  * the per-tree kernel replaces the product P(t) . (tipA o tipB) of a cherry — an internal node with two tip sons — by a lookup in a

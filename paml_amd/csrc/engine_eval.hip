@@ -560,10 +560,12 @@ int run_pmat(paml_amd_engine *e, Eval &c, const InlineVec &iv)
       if (!e->ctab_attr_set) {
          HIPCHK(hipFuncSetAttribute((const void *)cherry_table_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
          HIPCHK(hipFuncSetAttribute((const void *)cherry_table_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+         HIPCHK(hipFuncSetAttribute((const void *)cherry_table_kernel<false, 15>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
          e->ctab_attr_set = true;
       }
       const dim3 g((e->n_codes * e->n_codes + 127) / 128, e->n_ctab, c.K);
       if (e->n == 61) hipLaunchKernelGGL(cherry_table_kernel<true>, g, dim3(512), lds, c.ps, ca);
+      else if (e->n == 60) hipLaunchKernelGGL((cherry_table_kernel<false, 15>), g, dim3(512), lds, c.ps, ca);      // (jit_cherry_count: 60 .. 64 states)
       else hipLaunchKernelGGL(cherry_table_kernel<false>, g, dim3(512), lds, c.ps, ca);
    }
    mark_on(e, c.ps);

@@ -196,7 +196,7 @@ struct EnvCfg {
    bool no_coop = false;            // PAML_AMD_COOP=0: small data sets on the gather kernel (one wave per 16-pattern group) instead of prune_mfma64_coop
    bool jit_sync = false, jit_strict = false, no_m20 = false;
    int comm_cus = -1, lanes = 0;
-   // cherry tables of the per-tree 61..64-state kernel (jit.h: OP_LOOKUP).  PAML_AMD_CHERRY_TABLES=0 / 1: never / whatever the number of
+   // cherry tables of the per-tree 60..64-state kernel (jit.h: OP_LOOKUP).  PAML_AMD_CHERRY_TABLES=0 / 1: never / whatever the number of
    // patterns (the other conditions are correctness gates and stay); PAML_AMD_CHERRY_MIN_PATT, PAML_AMD_CHERRY_CAP_MB: the two measured
    // choices — patterns of this engine from which the tables pay, and the most table bytes of one evaluation
    int cherry_tables = -1;

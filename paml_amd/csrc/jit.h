@@ -137,7 +137,7 @@ inline std::string jit_program_key(const Program &p, int n_tips)
    return k.str();
 }
 
-// ---- cherry tables (61..64 states) ------------------------------------------------------------------------------------
+// ---- cherry tables (60..64 states) ------------------------------------------------------------------------------------
 // A cherry's partial tipA[:,ca] o tipB[:,cb] takes at most n_codes^2 values over the whole alignment, and so does its product with
 // P(t_cherry).  cherry_table_kernel (kernels_pmat.h) forms T_c[ca][cb] = P(t_c) . (tipA[:,ca] o tipB[:,cb]) once per evaluation, right
 // behind P(t), with the walk's own building blocks (same bits), and the walk gathers the finished 64-vector: `SET_TIP2 a b` directly
@@ -179,7 +179,7 @@ inline CherryProgram jit_cherry_program(const Program &p, int max_tabs)
 // than four operand blocks per tile.
 inline int jit_cherry_count(const Program &p, int n_tips, int n_states, int n_codes, int K, size_t cap_bytes, int tp = 128)
 {
-   if (n_states < 61 || n_states > 64 || n_codes > 64 || n_codes < 1 || K < 1) return 0;
+   if (n_states < 60 || n_states > 64 || n_codes > 64 || n_codes < 1 || K < 1) return 0;
    if (jit_zplan(p, n_tips, tp).bufs != 2) return 0;
    for (const Op &o : p.ops)
       if (o.code == OP_LOAD || o.code == OP_STORE) return 0;

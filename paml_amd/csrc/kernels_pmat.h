@@ -489,14 +489,15 @@ __global__ __launch_bounds__(256) void pmat_mfma_kernel(PmatArgs a, InlineVec iv
    }
 }
 
-// Cherry tables of the per-tree 61..64-state kernel (jit.h: OP_LOOKUP).  For cherry c = (tip a, tip b, node) of class `cls`,
+// Cherry tables of the per-tree 60..64-state kernel (jit.h: OP_LOOKUP).  For cherry c = (tip a, tip b, node) of class `cls`,
 //   T[ca][cb] = P(t_node) . (tipA[:, ca] o tipB[:, cb])      for every pair of character codes,
 // formed exactly as the walk forms it for a pattern with those codes: the cherry's P block, its column-60 table and the two tip
 // tables come into LDS in the layouts the walk's operand ring holds them in (global memory already has them so, as the ring's DMA
 // sources), a wave takes 16 pairs where the walk takes 16 patterns, and jit_tip2_set, jit_x60 and jit_matvec do the rest: same
 // functions, same operand order, same rank-1 seed, so a table entry has the bits the walk would compute.  Grid: (128-pair tiles,
 // cherries, classes), 8 waves; runs behind P(t) on its stream.  Row layout: jit_lookup_nc (device_common.h).
-template <bool TAIL61>
+// KB: the k-blocks of the walk's products (15 at 60 states, which leave the sixteenth out: the same MFMAs here).
+template <bool TAIL61, int KB = 16>
 __global__ __launch_bounds__(512) void cherry_table_kernel(CherryTabArgs a)
 {
    extern __shared__ __attribute__((aligned(16))) double ct_lds[];
@@ -517,7 +518,7 @@ __global__ __launch_bounds__(512) void cherry_table_kernel(CherryTabArgs a)
    v4d x[4], y[4];
    jit_tip2_set<8>(x, sA, pc / nc, sB, pc % nc, q, lane);
    const double x60 = TAIL61 ? jit_x60(x, lane) : 0.0;
-   jit_matvec<TAIL61, 4, 16>(sP, lane, x, y, JitNoSide(), sC, x60);
+   jit_matvec<TAIL61, 4, KB>(sP, lane, x, y, JitNoSide(), sC, x60);
    if (valid) {
       part2_t *r = (part2_t *)(a.ctab + (((long)cls * a.n_tabs + c) * np + pair) * CHERRY_ROW_WORDS) + q;
 #pragma unroll

@@ -86,11 +86,11 @@ def test_pmat_and_lnl_with_device_eigen_match_the_host_path(K):
     assert np.allclose(l1, l0, rtol=1e-12, atol=0) and np.allclose(d1, d0, rtol=1e-9, atol=1e-8) and np.allclose(dd1, dd0, rtol=1e-9, atol=1e-7)
 
 
-@pytest.mark.parametrize("n", [4, 20, 33, 60])
+@pytest.mark.parametrize("n", [4, 19, 20, 33, 59, 60, 62, 63, 64])
 def test_small_reversible_matrices(n):
     """n = 4 (GTR), n = 20 (a random reversible amino-acid matrix), n = 60 (the sense codons of a mitochondrial code) and an odd order in
-    between: orders 20, 60 (and 61) run the kernel's register form (R^T in one wave's registers, the rounds unrolled), the others its
-    any-order form."""
+    between: orders 19/20, 59/60 and 61/62 run the kernel's register form (R^T in one wave's registers, the rounds unrolled; an odd
+    order is padded by one row to the even one), the others (63 and 64 with the largest LDS footprint) its any-order form."""
     rng = np.random.default_rng(n)
     pb = helpers.random_problem(n, 6, 200, K=1, seed=5)
     eng = engine_for(pb)
@@ -111,7 +111,7 @@ def test_small_reversible_matrices(n):
         assert abs(R[0]) < 1e-13 and np.all(np.diff(R) <= 0)
 
 
-@pytest.mark.parametrize("n", [4, 20, 33, 60, 61])
+@pytest.mark.parametrize("n", [4, 19, 20, 33, 59, 60, 61, 62, 63, 64])
 def test_degenerate_spectra_and_scales(n):
     """What a Jacobi iteration can trip over, in both forms of the kernel: one eigenvalue of multiplicity n - 1 (equal rates, equal
     frequencies) at three scales (x 1, 1e-150, 1e150: the angle formula's squares must neither underflow nor overflow), two groups of
