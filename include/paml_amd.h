@@ -471,6 +471,29 @@ int paml_amd_ancestral_joint(paml_amd_engine *e, const double *branch, const dou
  * batches); either pointer may be NULL. */
 void paml_amd_ancestral_info(int *last_batches, double *last_kernel_ms);
 
+/* ---- The derivative of lnL with respect to every branch length, and the per-pattern scores, in one call (what gradientB and
+ * HessianSKT2004, treesub.c:7241, take 2 np evaluations for; the definition and the kernels are written out in csrc/kernels_gradient.h).
+ * grad[v] is the derivative with respect to branch[v] of exactly the number paml_amd_eval returns at (branch[n_nodes],
+ * gene_rate[n_genes] or NULL = 1), for any rooting and any mix of eigen systems on the branches — the tree is not re-rooted and no
+ * reversibility is assumed, unlike paml_amd_eval_branch.  grad[root] = 0.  scores[v][h] = d log f_h / d branch[v] (the root's row and the
+ * patterns of weight 0: 0), lnf[h] = log f_h, *lnL = sum_h w_h lnf[h] (equal to paml_amd_eval's to rounding, not to the bit).
+ * One down pass, one outer pass that also forms the derivative at every branch; K classes, several genes, branch labels, ambiguity
+ * codes, polytomies, scaling nodes, a root that is a tip; UVROOT, CIJK, K80 and JC69LIKE sets, at most 64 states.  Synchronous; builds
+ * the P(t) an evaluation would build, by the same kernels, starts eval_branch's resident state over, leaves a following paml_amd_eval
+ * its bits, and paml_amd_get_pmat returns the matrices the call used.  n_patt is walked gene by gene in batches of what a workspace
+ * holds (256 MiB; the environment variable PAML_AMD_GRAD_ARENA_MB gives another size in MiB): never PAML_AMD_ENOMEM because of n_patt,
+ * and every result has the same bits whatever the batches and on every call (fixed-order sums, no atomics).
+ * PAML_AMD_EINVAL (with a message) for a null branch, lnL or grad, a model or tips not set; PAML_AMD_EUNSUPPORTED for a rate-matrix
+ * (UNREST) set (its dP needs a matrix product of its own), tips that are not the nodes 0 .. n_tips - 1, more than 64 states, an engine
+ * whose communicator has more than one rank; PAML_AMD_ENOCONV as the other synchronous entries. */
+int paml_amd_gradient(paml_amd_engine *e, const double *branch, const double *gene_rate, double *lnL,
+                      double *grad   /* [n_nodes] */,
+                      double *lnf    /* [n_patt], or NULL */,
+                      double *scores /* [n_nodes][n_patt], or NULL */);
+/* The number of batches the calling thread's last paml_amd_gradient walked and the time of its kernels by HIP events (ms, summed over
+ * the batches); either pointer may be NULL. */
+void paml_amd_gradient_info(int *last_batches, double *last_kernel_ms);
+
 /* ---- Pairwise maximum-likelihood comparisons (codeml runmode = -2; PairwiseCodon codeml.c:4344-4604, Goldman & Yang 1994).
  * The reference takes the ns (ns - 1) / 2 pairs one after the other, each a search over (t, kappa, omega) whose every function call
  * (lfun2dSdN codeml.c:4219-4264) decomposes a rate matrix on one core.  Here a PAIR SET lives on an engine whose tips are clean data

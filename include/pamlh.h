@@ -118,6 +118,23 @@ int pamlh_bounds(const pamlh *p, double *lo, double *hi);
  * differences) and every line search (12 trial steps) evaluated as one batch on the GPU.  x: start in, estimate out.
  * Returns 0 converged, 1 max_iter reached, < 0 error.  n_eval (may be NULL): likelihood evaluations spent. */
 int pamlh_optimize(pamlh *p, double *x, double *lnL, int max_iter, double tol, int verbose, int *n_eval);
+/* The gradient d(+lnL)/dx at x (np entries) and lnL.  The entries of x that are plain branch lengths — the leading ntime ones when
+ * there is no clock and no proportional fix_blength = 3 — come from ONE engine call (paml_amd_gradient: the derivative of the lnL of
+ * the tree as it is rooted, whatever models its branches carry), mapped by pamlh_branch_order; every other entry by the central
+ * differences pamlh_optimize uses, in one batch.  All entries come by differences with rho != 0 (lfunAdG) and with a rate-matrix
+ * (UNREST) model. */
+int pamlh_gradient(pamlh *p, const double *x, double *lnL, double *g);
+/* on != 0: pamlh_optimize takes the branch-length entries of its gradients from that call and batches only the remaining parameters;
+ * the call counts as one evaluation in n_eval.  Off by default: pamlh_optimize then does exactly what it did without it. */
+int pamlh_use_analytic_gradient(pamlh *p, int on);
+/* g[ntime] as pamlh_gradient's leading entries and H[ntime][ntime], H_ij = -sum_h w_h s_i(h) s_j(h) with the analytic per-pattern
+ * scores s_i(h) = d log f_h / d t_i (HessianSKT2004's method 1, treesub.c:7241).  Refused where pamlh_gradient would difference the
+ * branch lengths. */
+int pamlh_branch_hessian(pamlh *p, const double *x, double *g, double *H);
+/* The block the reference writes to rst2 for mcmctree's in.BV (baseml.c:581-596), at x: the number of sequences, the Newick tree with
+ * branch lengths, the ntime lengths (%9.6f), the gradient (an entry with x > 0.0004 and |g| < 0.005 written as 0), the line "Hessian" and
+ * the matrix (%10.4g), from pamlh_branch_hessian.  Refused unless the tree is unrooted (three sons at the root) and there is no clock. */
+int pamlh_write_bv(pamlh *p, const double *x, const char *path);
 
 /* method = 1 of the control file: minB / minbranches (treesub.c:7826, 8039) — the branch lengths are optimised one at a time
  * by Newton steps on the branch-local lnL, dlnL/dt, d2lnL/dt2 (paml_amd_eval_branch; the engine keeps the partials of both

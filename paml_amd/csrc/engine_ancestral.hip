@@ -4,6 +4,7 @@
 // Built for gfx950 only (one of the translation units of libpaml_amd.so, see engine_state.h).
 #include "engine_state.h"
 #include "kernels_ancestral.h"
+#include "ancestral_host.h"
 
 static thread_local int anc_last_batches = 0;
 static thread_local double anc_last_kernel_ms = 0;      // HIP events around the P(t) kernels and every batch's passes, summed
@@ -14,23 +15,7 @@ extern "C" void paml_amd_ancestral_info(int *last_batches, double *last_kernel_m
    if (last_kernel_ms) *last_kernel_ms = anc_last_kernel_ms;
 }
 
-namespace {
-
-// what a call allocates for itself; released on every way out
-struct AncScratch {
-   DevBuf<int> tree, query;
-   DevBuf<double> L, G, SL, SG, post, prob, lnP, lnbest;
-   DevBuf<unsigned char> best, C, state, rootstate;
-   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-   ~AncScratch()
-   {
-      tree.release(); query.release();
-      for (DevBuf<double> *b : {&L, &G, &SL, &SG, &post, &prob, &lnP, &lnbest}) b->release();
-      for (DevBuf<unsigned char> *b : {&best, &C, &state, &rootstate}) b->release();
-      if (ev0) (void)hipEventDestroy(ev0);
-      if (ev1) (void)hipEventDestroy(ev1);
-   }
-};
+namespace paml_amd {
 
 // the tree as one int array: sons_ptr, sons, father, post, pre, scale (AncTree)
 int anc_tree_pack(paml_amd_engine *e, const char *who, AncScratch &w, AncTree *out)
@@ -114,11 +99,11 @@ int anc_pmat(paml_amd_engine *e, const char *who, const double *branch, const do
    return 0;
 }
 
-// patterns per batch: what the workspace holds at `bytes_per_patt`, whole tiles, at least one (PAML_AMD_ANC_ARENA_MB: MiB, default 256)
-long anc_batch(double bytes_per_patt, long n_patt)
+// patterns per batch: what the workspace holds at `bytes_per_patt`, whole tiles, at least one (the variable `env`: MiB, default 256)
+long anc_batch(double bytes_per_patt, long n_patt, const char *env)
 {
    double arena_mb = 256;
-   if (const char *s = getenv("PAML_AMD_ANC_ARENA_MB")) { const double v = atof(s); if (v > 0) arena_mb = v; }
+   if (const char *s = getenv(env)) { const double v = atof(s); if (v > 0) arena_mb = v; }
    long batch = (long)(arena_mb * 1048576.0 / bytes_per_patt) / ANC_JTILE * ANC_JTILE;
    if (batch < ANC_JTILE) batch = (long)(arena_mb * 1048576.0 / bytes_per_patt) / ANC_TILE * ANC_TILE;
    if (batch > (1L << 24)) batch = 1L << 24;
@@ -134,6 +119,10 @@ int anc_common_checks(paml_amd_engine *e, const char *who)
    if (e->n > 64) return fail(e, PAML_AMD_EUNSUPPORTED, std::string(who) + ": more than 64 states");
    return 0;
 }
+
+}  // namespace paml_amd
+
+namespace {
 
 // 4 / 5 / 20 states, the engines that are not on the matrix cores (paml_amd_create: every other state count is KK_MFMA64): the partial in registers
 void anc_launch_lane(KernelKind kk, dim3 grid, hipStream_t st, const AncMargArgs &a, int outer)

@@ -13,6 +13,8 @@
 //   engine_compress.hip site-pattern compression on the device (stand-alone)
 //   engine_simulate.hip alignments drawn under the loaded model (P(t) by launch_pmat, then its own kernels)
 //   engine_ancestral.hip marginal and joint ancestral reconstruction at every internal node (P(t) by launch_pmat, then its own kernels)
+//   engine_gradient.hip  the derivative of lnL with respect to every branch length and the per-pattern scores (P(t) and the down pass as
+//                       engine_ancestral.hip, whose host helpers it shares through ancestral_host.h; then its own kernels)
 // Built for gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -36,6 +36,7 @@ EXPORTS = [
     "paml_amd_rell_replicates", "paml_amd_rell_info",
     "paml_amd_simulate", "paml_amd_simulate_info",
     "paml_amd_ancestral_marginal", "paml_amd_ancestral_joint", "paml_amd_ancestral_info",
+    "paml_amd_gradient", "paml_amd_gradient_info",
 ]
 
 
@@ -50,7 +51,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -478,6 +479,19 @@ class Engine:
         self._chk(self._L.paml_amd_ancestral_joint(self._h, _p(b), _p(g), _p(states), _p(ln_best)))
         return dict(states=states, ln_best=ln_best)
 
+    def gradient(self, branch, gene_rate=None, want_lnf=False, want_scores=False):
+        """The derivative of lnL with respect to every branch length in one call (paml_amd_gradient): dict(lnL, grad=[n_nodes] (the
+        root's entry 0), lnf=[n_patt] or None, scores=[n_nodes][n_patt] d log f_h / d branch[v] or None)."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        lnL = C.c_double()
+        grad = np.zeros(self.n_nodes)
+        lnf = np.zeros(self.n_patt) if want_lnf else None
+        scores = np.zeros((self.n_nodes, self.n_patt)) if want_scores else None
+        self._L.paml_amd_gradient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self._L.paml_amd_gradient(self._h, _p(b), _p(g), C.byref(lnL), _p(grad), _p(lnf), _p(scores)))
+        return dict(lnL=lnL.value, grad=grad, lnf=lnf, scores=scores)
+
     def get_pmat(self, gene, iclass, node):
         P = np.zeros((self.n, self.n))
         self._chk(self._L.paml_amd_get_pmat(self._h, gene, iclass, node, _p(P)))
@@ -787,6 +801,17 @@ def ancestral_info():
     L.paml_amd_ancestral_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.paml_amd_ancestral_info.restype = None
     L.paml_amd_ancestral_info(C.byref(nb), C.byref(ms))
+    return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def gradient_info():
+    """Batches walked by this thread's last Engine.gradient and the time of its kernels by HIP events (paml_amd_gradient_info):
+    dict(last_batches, last_kernel_ms)."""
+    L = lib()
+    nb, ms = C.c_int(), C.c_double()
+    L.paml_amd_gradient_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.paml_amd_gradient_info.restype = None
+    L.paml_amd_gradient_info(C.byref(nb), C.byref(ms))
     return dict(last_batches=nb.value, last_kernel_ms=ms.value)
 
 

@@ -104,6 +104,7 @@ struct pamlh {
    int malpha;               /* Malpha: a gamma shape per gene; rate[] then holds [gene][class] */
    int pairwise;             /* runmode = -2: pairwise comparisons (pamlh_pairwise.c); no tree, no model state */
    int opt_transformed;      /* pamlh_optimize is iterating on transformed proportions (pamlh_opt.c) */
+   int analytic_gradient;    /* pamlh_use_analytic_gradient: pamlh_optimize takes the branch lengths' derivatives from paml_amd_gradient */
    int aadist, n_omega_type;
    signed char omega_class[26][26];
    double aa_dist[26][26];           /* aaDist 1..6 / -1..-6: amino-acid distances over their maximum, by letters (GetDaa codeml.c:3967-3993) */

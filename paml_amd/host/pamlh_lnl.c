@@ -1,5 +1,5 @@
 /* pamlh_lnl — command-line driver: one likelihood evaluation of a codeml/baseml analysis on the MI355X.
- *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
+ *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
  *   (--set "key = value": replaces an option of the control file, e.g. one of the site models of an "NSsites = 0 1 2 7 8" list;
  *    --tree K: the K-th tree of the tree file, 1-based; --all-trees: every tree in turn — the reference's loop, Forestry codeml.c:635 —
  *    each optimised from the control file's initial values, then the comparison table of rell(), treesub.c:5844;
@@ -117,17 +117,19 @@ int main(int argc, char **argv)
    pamlh *p;
    char err[512];
    double x[4096], lnL, *lnf;
-   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0;
+   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0;
    char over[2048] = "";
-   const char *sim_out = NULL;
+   const char *sim_out = NULL, *bv_out = NULL;
    long sim_sites = 0;
    unsigned long long sim_seed = 1;
    unsigned char comm_id[PAML_AMD_COMM_ID_BYTES];
    int device[MAX_RANKS];
    for (i = 0; i < MAX_RANKS; i++) device[i] = i;
-   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
+   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
    for (i = 3; i < argc && nx < 4096; i++) {
       if (!strcmp(argv[i], "--optimize")) optimize = 1;
+      else if (!strcmp(argv[i], "--analytic-gradient")) analytic = 1;      /* with --optimize: the branch lengths' derivatives from one engine call per gradient */
+      else if (!strcmp(argv[i], "--bv") && i + 1 < argc) bv_out = argv[++i];      /* gradient and Hessian of the branch lengths, the reference's rst2 block (mcmctree's in.BV) */
       else if (!strcmp(argv[i], "--ancestral")) ancestral = 1;
       else if (!strcmp(argv[i], "--ancestral-all")) ancestral_all = 1;
       else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
@@ -240,6 +242,7 @@ int main(int argc, char **argv)
    if (!nx) nx = pamlh_read_inx(p, x, 4096);
    if (!nx) nx = pamlh_default_x(p, x, 4096);
    if (nx != np) { fprintf(stderr, "error: the model has %d parameters (ntime %d) but %d values were given\n", np, ntime, nx); return 1; }
+   if (analytic) pamlh_use_analytic_gradient(p, 1);
    if (optimize) {
       /* method = 1 in the control file: minB / minbranches (one branch at a time on the branch-local derivatives) */
       const int method1 = pamlh_method(p) == 1;
@@ -266,6 +269,11 @@ int main(int argc, char **argv)
          }
          free(se);
       }
+   }
+   if (bv_out) {      /* at the vector evaluated or just estimated */
+      if (gpus > 0) { fprintf(stderr, "error: --bv runs on one GPU\n"); return 1; }
+      if (pamlh_write_bv(p, x, bv_out)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      printf("gradient and Hessian of the %d branch lengths -> %s\n", ntime, bv_out);
    }
    if (sim_out) {      /* the data sets of a parametric bootstrap instead of the evaluation */
       int ns = 0, n_pose = 0, r;

@@ -384,12 +384,12 @@ static double dot(const double *a, const double *b, int n)
 /* Central-difference gradient of f = -lnL at x (one batch of <= 2 np points; one-sided where the box is in the way, or where
  * the model rejects the nudged vector — class proportions are iterated untransformed, so next to p0 + p1 = 1 a side can be
  * infeasible and comes back as the -1e300 marker: it is a blocked side, not a value).  Frozen parameters are not nudged. */
-static int gradient(pamlh *p, const double *x, double f0, const double *lo, const double *hi, double *g, double *xs, double *ls, int *n_eval)
+static int gradient_from(pamlh *p, int first, int raw, const double *x, double f0, const double *lo, const double *hi, double *g, double *xs, double *ls, int *n_eval)
 {
    const int n = p->np;
    int i, rc, na = 0;
    int *act = (int *)malloc((n + 1) * sizeof(int));
-   for (i = 0; i < n; i++) {
+   for (i = first; i < n; i++) {
       const double h = 1e-6 * (fabs(x[i]) + 1);
       double *xp, *xm;
       g[i] = 0;
@@ -401,7 +401,7 @@ static int gradient(pamlh *p, const double *x, double f0, const double *lo, cons
       if (x[i] - h >= lo[i]) xm[i] = x[i] - h;
       act[na++] = i;
    }
-   if (na && (rc = batch_eval(p, 2 * na, xs, ls))) { free(act); return rc; }
+   if (na && (rc = raw ? pamlh_eval_batch_gpu(p, 2 * na, xs, ls) : batch_eval(p, 2 * na, xs, ls))) { free(act); return rc; }
    *n_eval += 2 * na;
    for (int a = 0; a < na; a++) {
       const double *xp = xs + (size_t)(2 * a) * n, *xm = xp + n;
@@ -414,6 +414,133 @@ static int gradient(pamlh *p, const double *x, double f0, const double *lo, cons
       }
    }
    free(act);
+   return 0;
+}
+
+/* The analytic branch-length derivatives at x (the model's own variables): d(+lnL)/dx_i of the ntime branch lengths from one
+ * paml_amd_gradient call, mapped by tree.branches order; lnL of the same call; scores (may be NULL) [nnode][npatt] as the engine
+ * returns them.  Returns 1, touching nothing else, where the entries are not plain branch lengths or the engine has no derivative:
+ * a clock, proportional branch lengths (fix_blength = 3), no branch length in x, rho != 0 (lfunAdG: the sites are not independent),
+ * a rate-matrix (UNREST) set.  < 0: an error. */
+static int analytic_branches(pamlh *p, const double *x, double *lnL, double *gb, double *scores)
+{
+   double *gn;
+   int i, rc;
+   if (!p->ntime || p->clock || p->fix_blength == 3) return 1;
+   if ((rc = pamlh_set_x(p, x, p->np))) return rc < 0 ? rc : -1;
+   if (p->adg) return 1;
+   for (i = 0; i < p->n_eigen; i++) if (p->eig[i].kind == PAML_AMD_EIGEN_QMAT) return 1;
+   if ((rc = pamlh_engine_model(p))) return rc < 0 ? rc : -1;
+   gn = (double *)malloc(p->nnode * sizeof(double));
+   rc = paml_amd_gradient(p->eng, p->branch, p->ngene > 1 ? p->rgene : NULL, lnL, gn, NULL, scores);
+   if (rc) { free(gn); pamlh_fail(p, "%s", paml_amd_last_error(p->eng)); return rc < 0 ? rc : -1; }
+   for (i = 0; i < p->ntime; i++) gb[i] = gn[p->branch_node[i]];
+   free(gn);
+   return 0;
+}
+
+/* The optimiser's gradient of f = -lnL in its own variables: all by differences, or — pamlh_use_analytic_gradient, where
+ * analytic_branches serves — the branch lengths from one engine call (counted as one evaluation) and the rest by differences. */
+static int gradient(pamlh *p, const double *x, double f0, const double *lo, const double *hi, double *g, double *xs, double *ls, int *n_eval)
+{
+   int first = 0, i, rc, live = 0;
+   for (i = 0; i < p->ntime; i++) live |= !(p->frozen && p->frozen[i]);      /* (minB holds the branch lengths: nothing to ask the engine for) */
+   if (p->analytic_gradient && !p->clock && live) {
+      double lnL, *xm = (double *)malloc(2 * p->np * sizeof(double)), *gb = xm + p->np;
+      clock_y_to_x(p, x, xm);      /* (no clock: the branch lengths are themselves; proportions come back from their log-ratios) */
+      rc = analytic_branches(p, xm, &lnL, gb, NULL);
+      if (rc == 0) {
+         first = p->ntime;
+         for (i = 0; i < first; i++) g[i] = (p->frozen && p->frozen[i]) ? 0 : -gb[i];
+         (*n_eval)++;
+      }
+      free(xm);
+      if (rc < 0) return rc;
+   }
+   return gradient_from(p, first, 0, x, f0, lo, hi, g, xs, ls, n_eval);
+}
+
+int pamlh_use_analytic_gradient(pamlh *p, int on)
+{
+   if (!p) return -1;
+   p->analytic_gradient = on != 0;
+   return 0;
+}
+
+/* d(+lnL)/dx at x, np entries, and lnL: the plain branch lengths from paml_amd_gradient, every other entry (all of them where
+ * analytic_branches does not serve) by the central differences of the optimiser's gradient, in one batch. */
+int pamlh_gradient(pamlh *p, const double *x, double *lnL, double *g)
+{
+   const int n = p->np;
+   double *lo = (double *)malloc(2 * n * sizeof(double) + 8), *hi = lo + n;
+   double *xs = (double *)malloc(((size_t)2 * n * n + 1) * sizeof(double)), *ls = (double *)malloc((2 * n + 1) * sizeof(double));
+   double *gb = (double *)malloc((p->ntime + 1) * sizeof(double)), l0 = 0, lb = 0;
+   int rc, i, first = 0, ne = 0;
+   if (pamlh_bounds(p, lo, hi)) { rc = pamlh_fail(p, "internal: bounds do not match np"); goto done; }
+   rc = analytic_branches(p, x, &l0, gb, NULL);
+   if (rc < 0) goto done;
+   if (rc == 0) first = p->ntime;
+   /* the base value of the one-sided differences comes from the same entry point as the perturbed points: the gradient call's lnL
+    * equals it to rounding only, and a step of 1e-6 (|x| + 1) would magnify the mismatch */
+   if ((first < n || rc) && (rc = pamlh_eval_batch_gpu(p, 1, x, &lb))) goto done;
+   if (!first) l0 = lb;
+   if ((rc = gradient_from(p, first, 1, x, -lb, lo, hi, g, xs, ls, &ne))) goto done;
+   for (i = 0; i < n; i++) g[i] = i < first ? gb[i] : -g[i];
+   *lnL = l0;
+done:
+   free(lo); free(xs); free(ls); free(gb);
+   return rc;
+}
+
+/* The gradient over the ntime branch lengths and H_ij = -sum_h w_h s_i(h) s_j(h) from the analytic per-pattern scores (what
+ * HessianSKT2004, treesub.c:7241, calls method 1).  g[ntime], H[ntime][ntime]. */
+int pamlh_branch_hessian(pamlh *p, const double *x, double *g, double *H)
+{
+   const int nt = p->ntime, np = p->npatt;
+   double lnL, *sc = (double *)malloc(((size_t)p->nnode * np + 1) * sizeof(double));
+   int i, j, h, rc = analytic_branches(p, x, &lnL, g, sc);
+   if (rc > 0) rc = pamlh_fail(p, "pamlh_branch_hessian: the analytic scores need plain branch lengths in x (no clock, no fix_blength = 3), rho = 0 and no rate-matrix (UNREST) model");
+   if (rc) { free(sc); return rc; }
+   for (i = 0; i < nt; i++)
+      for (j = 0; j <= i; j++) {
+         const double *si = sc + (size_t)p->branch_node[i] * np, *sj = sc + (size_t)p->branch_node[j] * np;
+         double s = 0;
+         for (h = 0; h < np; h++) s += p->w[h] * si[h] * sj[h];
+         H[i * nt + j] = H[j * nt + i] = -s;
+      }
+   free(sc);
+   return 0;
+}
+
+/* The block the reference writes to rst2 for mcmctree's in.BV (baseml.c:581-596) at x: the number of sequences, the tree with its branch
+ * lengths, the ntime lengths, the gradient (entries with x > 0.0004 and |g| < 0.005 set to 0, as there), "Hessian" and the matrix — from
+ * pamlh_branch_hessian.  As the reference: an unrooted tree (three sons at the root) and no clock only. */
+int pamlh_write_bv(pamlh *p, const double *x, const char *path)
+{
+   const int nt = p->ntime;
+   double *g, *H;
+   char *nw;
+   FILE *f;
+   int i, j, rc;
+   if (p->clock || p->sons_ptr[p->root + 1] - p->sons_ptr[p->root] != 3)
+      return pamlh_fail(p, "--bv: the gradient and Hessian of the branch lengths are written for an unrooted tree (three sons at the root) without a clock, as the reference does");
+   g = (double *)malloc(((size_t)nt * (nt + 1) + 1) * sizeof(double)); H = g + nt;
+   if ((rc = pamlh_branch_hessian(p, x, g, H))) { free(g); return rc; }
+   nw = (char *)malloc((size_t)160 * p->nnode + 256);
+   if (pamlh_set_x(p, x, p->np) || pamlh_newick(p, nw, 160 * p->nnode + 256)) { free(g); free(nw); return pamlh_fail(p, "--bv: no tree to write"); }
+   if (!(f = fopen(path, "w"))) { free(g); free(nw); return pamlh_fail(p, "--bv: cannot write %s", path); }
+   fprintf(f, "\n %d\n\n%s\n\n", p->ns, nw);
+   for (i = 0; i < nt; i++) if (x[i] > 0.0004 && fabs(g[i]) < 0.005) g[i] = 0;
+   for (i = 0; i < nt; i++) fprintf(f, " %9.6f", x[i]);
+   fprintf(f, "\n\n");
+   for (i = 0; i < nt; i++) fprintf(f, " %9.6f", g[i]);
+   fprintf(f, "\n\n\nHessian\n\n");
+   for (i = 0; i < nt; i++) {
+      for (j = 0; j < nt; j++) fprintf(f, " %10.4g", H[i * nt + j]);
+      fprintf(f, "\n");
+   }
+   fclose(f);
+   free(g); free(nw);
    return 0;
 }
 

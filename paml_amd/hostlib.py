@@ -335,14 +335,52 @@ class Analysis:
             raise RuntimeError("pamlh_bounds failed")
         return lo, hi
 
-    def optimize(self, x0, max_iter=500, tol=1e-10, verbose=False):
-        """Maximum-likelihood estimation from x0 (pamlh_optimize).  Returns dict(x, lnL, converged, n_eval)."""
+    def optimize(self, x0, max_iter=500, tol=1e-10, verbose=False, analytic_gradient=False):
+        """Maximum-likelihood estimation from x0 (pamlh_optimize).  Returns dict(x, lnL, converged, n_eval).  analytic_gradient: the
+        branch lengths' derivatives from one engine call per gradient (pamlh_use_analytic_gradient; counted as one evaluation)."""
         x = np.ascontiguousarray(x0, dtype=np.float64).copy()
         lnl, nev = C.c_double(), C.c_int()
-        rc = self._L.pamlh_optimize(self._h, x.ctypes.data_as(C.c_void_p), C.byref(lnl), max_iter, tol, int(verbose), C.byref(nev))
+        self._L.pamlh_use_analytic_gradient.argtypes = [C.c_void_p, C.c_int]
+        self._L.pamlh_use_analytic_gradient(self._h, int(bool(analytic_gradient)))
+        try:
+            rc = self._L.pamlh_optimize(self._h, x.ctypes.data_as(C.c_void_p), C.byref(lnl), max_iter, tol, int(verbose), C.byref(nev))
+        finally:
+            self._L.pamlh_use_analytic_gradient(self._h, 0)
         if rc < 0:
             raise RuntimeError("pamlh_optimize: " + self._L.pamlh_error(self._h).decode())
         return dict(x=x, lnL=lnl.value, converged=rc == 0, n_eval=nev.value)
+
+    def write_bv(self, x, path):
+        """The gradient and Hessian of the branch lengths at x in the layout of the reference's rst2 block (pamlh_write_bv)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        self._L.pamlh_write_bv.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
+        if len(x) != self.np or self._L.pamlh_write_bv(self._h, x.ctypes.data_as(C.c_void_p), os.fsencode(str(path))) != 0:
+            raise RuntimeError("pamlh_write_bv: " + self._L.pamlh_error(self._h).decode())
+
+    def branch_order(self):
+        """The node below the i-th branch of x's branch-length block, [n_nodes - 1] (pamlh_branch_order: tree.branches order)."""
+        return _arr(self._L.pamlh_branch_order(self._h), np.int32, self.n_nodes - 1)
+
+    def gradient(self, x):
+        """d lnL / d x at x (pamlh_gradient): dict(lnL, grad=[np]) — the plain branch lengths from one engine call (paml_amd_gradient),
+        the other parameters by central differences in one batch."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        lnl, g = C.c_double(), np.zeros(max(1, self.np))
+        self._L.pamlh_gradient.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]
+        if len(x) != self.np or self._L.pamlh_gradient(self._h, x.ctypes.data_as(C.c_void_p), C.byref(lnl), g.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_gradient: " + self._L.pamlh_error(self._h).decode())
+        return dict(lnL=lnl.value, grad=g[:self.np])
+
+    def branch_hessian(self, x):
+        """dict(grad=[ntime], H=[ntime][ntime]) over the branch lengths at x, H_ij = -sum_h w_h s_i(h) s_j(h) from the analytic
+        per-pattern scores (pamlh_branch_hessian)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        nt = self.ntime
+        g, H = np.zeros(max(1, nt)), np.zeros((max(1, nt), max(1, nt)))
+        self._L.pamlh_branch_hessian.argtypes = [C.c_void_p] * 4
+        if len(x) != self.np or self._L.pamlh_branch_hessian(self._h, x.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), H.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_branch_hessian: " + self._L.pamlh_error(self._h).decode())
+        return dict(grad=g[:nt], H=H[:nt, :nt])
 
     def optimize_minb(self, x0, e0=1e-6, verbose=0):
         """method = 1 (pamlh_optimize_minb): branch lengths one at a time by Newton steps on the branch-local derivatives, the
