@@ -494,6 +494,38 @@ int paml_amd_gradient(paml_amd_engine *e, const double *branch, const double *ge
  * the batches); either pointer may be NULL. */
 void paml_amd_gradient_info(int *last_batches, double *last_kernel_ms);
 
+/* ---- The lnL of every nearest-neighbour-interchange (NNI) neighbour of the tree at the present branch lengths, in one call (the trees
+ * the reference's search, Perturbation treesub.c:4642 on NeighborNNI treespace.c:283, takes one after the other; the definition and the
+ * kernels are written out in csrc/kernels_nni.h).  A swap is (v, s, x): v an internal node that is not the root, s a son of v, x a son
+ * of the father of v other than v.  The subtrees below s and x change places; each keeps the branch above it, and with the branch its
+ * length and its label.  lnL[i] and lnf[i][h] are what paml_amd_eval would return for that tree as rooted at (branch[n_nodes],
+ * gene_rate[n_genes] or NULL = 1) — equal to rounding, not to the bit, and without regard to where the rearranged tree's scaling marks
+ * would sit (the present tree's partials are reused; only the log factors differ).  *lnL0 is the present tree's lnL, taken as
+ * paml_amd_gradient takes it.  One down pass, one outer pass (the gradient's without the derivative), then per swap the products of the
+ * two nodes around the edge: no tree is set and no kernel is built per neighbour.  Everything paml_amd_gradient takes — K classes,
+ * several genes, branch labels, ambiguity codes, polytomies, scaling nodes, a root that is a tip, at most 64 states — and rate-matrix
+ * (UNREST) sets too: only P(t) is used.  Synchronous; builds the P(t) an evaluation would build, by the same kernels, starts
+ * eval_branch's resident state over, leaves a following paml_amd_eval its bits, and paml_amd_get_pmat returns the matrices the call
+ * used.  n_patt is walked gene by gene in batches of what a workspace holds (256 MiB; the environment variable PAML_AMD_NNI_ARENA_MB,
+ * read at every call, gives another size in MiB), and the swaps in groups where one tile of patterns with all of them does not fit:
+ * every output has the same bits for any workspace size, for any place of a swap in the list and on every call (fixed-order sums, no
+ * atomics).  PAML_AMD_EINVAL (with a message starting "nni_scores") for a null branch, swaps, lnL0 or lnL, n_swaps < 1, a v that is a
+ * tip, the root or out of range, an s that is not a son of v, an x that is not a son of the father of v or is v, a model or tips not
+ * set; PAML_AMD_EUNSUPPORTED for tips that are not the nodes 0 .. n_tips - 1, more than 64 states, an engine whose communicator has
+ * more than one rank; PAML_AMD_ENOCONV as the other synchronous entries. */
+int paml_amd_nni_scores(paml_amd_engine *e, const double *branch, const double *gene_rate,
+                        int n_swaps, const int *swaps /* [n_swaps][3] = v, s, x */,
+                        double *lnL0, double *lnL /* [n_swaps] */, double *lnf /* [n_swaps][n_patt], or NULL */);
+/* The number of pattern batches the calling thread's last paml_amd_nni_scores walked and the time of its kernels by HIP events (ms,
+ * summed); either pointer may be NULL. */
+void paml_amd_nni_info(int *last_batches, double *last_kernel_ms);
+/* The canonical list of swaps of a tree given as paml_amd_set_tree takes it, host only (no engine, no device): every (s, x) of every
+ * internal v that is not the root, in node order, s over the sons of v and x over its father's other sons in son-list order.  A v with
+ * two sons under a root with exactly three sons lists its first son only — the other son's swaps are the same unrooted trees — so an
+ * unrooted binary tree of ns tips gets the reference's 2 (ns - 3) neighbours (treesub.c:4687).  Returns the list's length (with swaps =
+ * NULL the length only), or PAML_AMD_EINVAL for a bad tree or a list longer than cap. */
+int paml_amd_nni_list(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, int *swaps /* [cap][3], or NULL */, int cap);
+
 /* ---- Pairwise maximum-likelihood comparisons (codeml runmode = -2; PairwiseCodon codeml.c:4344-4604, Goldman & Yang 1994).
  * The reference takes the ns (ns - 1) / 2 pairs one after the other, each a search over (t, kappa, omega) whose every function call
  * (lfun2dSdN codeml.c:4219-4264) decomposes a rate matrix on one core.  Here a PAIR SET lives on an engine whose tips are clean data

@@ -136,6 +136,29 @@ int pamlh_branch_hessian(pamlh *p, const double *x, double *g, double *H);
  * the matrix (%10.4g), from pamlh_branch_hessian.  Refused unless the tree is unrooted (three sons at the root) and there is no clock. */
 int pamlh_write_bv(pamlh *p, const double *x, const char *path);
 
+/* Nearest-neighbour interchange (NNI) on the analysis's tree (pamlh_nni.c).  A swap is (v, s, x), 0-based nodes: v an internal node that
+ * is not the root, s a son of v, x a son of the father of v other than v; the subtrees below s and x change places and each keeps the
+ * branch above it, so the same parameter vector describes the rearranged tree.  All three are refused by name with a clock (the
+ * reference's search refuses it too, treesub.c:4653), with rho models and for runmode = -2.
+ * pamlh_nni_scores: the canonical list of the tree as it stands (paml_amd_nni_list: 2 (ns - 3) swaps on an unrooted binary tree, the
+ *   reference's neighbours, treesub.c:4687) scored at x in ONE engine call (paml_amd_nni_scores): swaps[*n_swaps][3], lnL[*n_swaps] =
+ *   the neighbours' lnL at the branch lengths and parameters of x, *lnL0 = the present tree's.  With swaps = lnL = NULL only *n_swaps
+ *   is written (host only): the room for the list is the caller's.
+ * pamlh_apply_nni: exchanges the two sons in place in the son lists, marks the scaling nodes as for a tree just read (SetNodeScale
+ *   treesub.c:7177) and sends the tree to the engine again.  Node ids, labels and pamlh_branch_order stay, so the layout of x does not
+ *   change; (v, x, s) afterwards undoes it.
+ * pamlh_nni_search: the hill climb of the reference's runmode = 5 (Perturbation treesub.c:4642).  pamlh_optimize on the present tree;
+ *   then per step one pamlh_nni_scores at the estimates, the neighbours in descending order of their screened lnL, each applied and
+ *   maximised from the present x: the first whose maximised lnL is higher by more than 1e-4 (the reference prints the search's lnL
+ *   with four decimals, treesub.c:4709) is kept, every other is undone.  It ends after a step in which every neighbour was maximised
+ *   and none was better: the final tree is an NNI-local optimum, as the reference's — the screening only decides the order — or after
+ *   max_moves moves (<= 0: no limit).  x: start in, estimates on the final tree out (the model state is left at them: pamlh_newick
+ *   prints the tree found).  stats (NULL or 3 entries): moves, screening calls, neighbours maximised (the starting tree's own
+ *   maximisation not counted).  verbose: every accepted move on stdout. */
+int pamlh_nni_scores(pamlh *p, const double *x, int *n_swaps, int *swaps, double *lnL0, double *lnL);
+int pamlh_apply_nni(pamlh *p, int v, int s, int x);
+int pamlh_nni_search(pamlh *p, double *x, double *lnL, int max_moves, int verbose, int *stats);
+
 /* method = 1 of the control file: minB / minbranches (treesub.c:7826, 8039) — the branch lengths are optimised one at a time
  * by Newton steps on the branch-local lnL, dlnL/dt, d2lnL/dt2 (paml_amd_eval_branch; the engine keeps the partials of both
  * sides of every edge resident, so a step along the tree costs the nodes on the path, not the tree), alternating with BFGS

@@ -1,5 +1,5 @@
 // ancestral_host.h — the host side that the calls walking a down pass and an outer pass over the whole tree share (defined in
-// engine_ancestral.hip; used there and by engine_gradient.hip): the packed tree, P(t) from the evaluation's own builders, the batch size.
+// engine_ancestral.hip; used there, by engine_gradient.hip and by engine_nni.hip): the packed tree, P(t) from the evaluation's own builders, the batch size.
 #pragma once
 #include "engine_state.h"
 

@@ -37,6 +37,7 @@ EXPORTS = [
     "paml_amd_simulate", "paml_amd_simulate_info",
     "paml_amd_ancestral_marginal", "paml_amd_ancestral_joint", "paml_amd_ancestral_info",
     "paml_amd_gradient", "paml_amd_gradient_info",
+    "paml_amd_nni_scores", "paml_amd_nni_info", "paml_amd_nni_list",
 ]
 
 
@@ -51,7 +52,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_nni")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -225,6 +226,7 @@ class Engine:
         sc = None if scale_node is None else np.ascontiguousarray(scale_node, dtype=np.uint8)
         self.n_nodes = tree.n_nodes
         self._chk(self._L.paml_amd_set_tree(self._h, tree.n_nodes, tree.root, _p(ptr), _p(flat), _p(lab), _p(sc)))
+        self._tree_csr = (tree.root, ptr, flat)      # (for nni_scores' canonical list)
 
     def set_pi(self, pi):
         pi = np.ascontiguousarray(np.atleast_2d(pi), dtype=np.float64)
@@ -491,6 +493,24 @@ class Engine:
         self._L.paml_amd_gradient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]
         self._chk(self._L.paml_amd_gradient(self._h, _p(b), _p(g), C.byref(lnL), _p(grad), _p(lnf), _p(scores)))
         return dict(lnL=lnL.value, grad=grad, lnf=lnf, scores=scores)
+
+    def nni_scores(self, branch, gene_rate=None, swaps=None, want_lnf=False):
+        """The lnL of nearest-neighbour-interchange neighbours of the tree at `branch` in one call (paml_amd_nni_scores): dict(lnL0 (the
+        present tree's), swaps=[n_swaps][3] (v, s, x), lnL=[n_swaps], lnf=[n_swaps][n_patt] or None).  swaps None: the canonical list
+        (paml_amd_nni_list) of the tree last set."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        if swaps is None:
+            if getattr(self, "_tree_csr", None) is None:
+                raise EngineError("nni_scores: no tree was set through this object")
+            swaps = nni_list(self.n_tips, self.n_nodes, *self._tree_csr)
+        sw = np.ascontiguousarray(swaps, dtype=np.int32).reshape(-1, 3)
+        lnL0 = C.c_double()
+        lnL = np.zeros(len(sw))
+        lnf = np.zeros((len(sw), self.n_patt)) if want_lnf else None
+        self._L.paml_amd_nni_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
+        self._chk(self._L.paml_amd_nni_scores(self._h, _p(b), _p(g), len(sw), _p(sw), C.byref(lnL0), _p(lnL), _p(lnf)))
+        return dict(lnL0=lnL0.value, swaps=sw, lnL=lnL, lnf=lnf)
 
     def get_pmat(self, gene, iclass, node):
         P = np.zeros((self.n, self.n))
@@ -813,6 +833,31 @@ def gradient_info():
     L.paml_amd_gradient_info.restype = None
     L.paml_amd_gradient_info(C.byref(nb), C.byref(ms))
     return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def nni_info():
+    """Batches walked by this thread's last Engine.nni_scores and the time of its kernels by HIP events (paml_amd_nni_info):
+    dict(last_batches, last_kernel_ms)."""
+    L = lib()
+    nb, ms = C.c_int(), C.c_double()
+    L.paml_amd_nni_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.paml_amd_nni_info.restype = None
+    L.paml_amd_nni_info(C.byref(nb), C.byref(ms))
+    return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def nni_list(n_tips, n_nodes, root, sons_ptr, sons):
+    """The canonical list of NNI swaps of a tree in CSR form (paml_amd_nni_list, host only): int32 [n_swaps][3] = v, s, x."""
+    L = lib()
+    ptr, flat = np.ascontiguousarray(sons_ptr, dtype=np.int32), np.ascontiguousarray(sons, dtype=np.int32)
+    L.paml_amd_nni_list.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    n = L.paml_amd_nni_list(int(n_tips), int(n_nodes), int(root), _p(ptr), _p(flat), None, 0)
+    if n < 0:
+        raise EngineError("paml_amd_nni_list failed (%d): not a tree" % n)
+    sw = np.zeros((n, 3), dtype=np.int32)
+    if n and L.paml_amd_nni_list(int(n_tips), int(n_nodes), int(root), _p(ptr), _p(flat), _p(sw), n) != n:
+        raise EngineError("paml_amd_nni_list: the list changed its length")
+    return sw
 
 
 def rell_replicates(lnf, w, gene_off=None, n_rep=10000, seed=1, arena_mb=None):

@@ -149,6 +149,7 @@ const char *pamlh_genetic_code(int icode);      /* 64 characters, codons in T C 
 double pamlh_optd(const pamlh *p, const char *key, double dflt);
 int pamlh_read_seqs(pamlh *p);
 int pamlh_read_tree(pamlh *p);
+void pamlh_set_node_scale(pamlh *p);      /* SetNodeScale on the tree as it stands -> p->scale */
 int pamlh_fail(pamlh *p, const char *fmt, ...);
 int pamlh_force_host_eigen(void);
 int pamlh_engine_ready(pamlh *p);

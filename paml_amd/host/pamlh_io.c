@@ -633,22 +633,26 @@ int pamlh_read_tree(pamlh *p)
       free(cur);
    }
    free(label2); free(labelled);
-   /* SetNodeScale (treesub.c:7177-7197) */
-   {
-      const int every = p->is_codeml ? (p->seqtype == 1 ? 15 : 50) : 100;
-      int *cnt = (int *)calloc(nn, sizeof(int)), *order = (int *)malloc(nn * sizeof(int)), no = 0, sp = 0;
-      p->scale = (unsigned char *)calloc(nn, 1);
-      stack[sp++] = p->root;     /* post-order via reversed pre-order */
-      while (sp) { int x = stack[--sp], j; order[no++] = x; for (j = p->sons_ptr[x]; j < p->sons_ptr[x + 1]; j++) stack[sp++] = p->sons[j]; }
-      for (i = no - 1; i >= 0; i--) {
-         int x = order[i], j, d = 0;
-         if (p->sons_ptr[x + 1] == p->sons_ptr[x]) continue;
-         for (j = p->sons_ptr[x]; j < p->sons_ptr[x + 1]; j++) { int c = p->sons[j]; d += (p->sons_ptr[c + 1] > p->sons_ptr[c]) ? cnt[c] : 1; }
-         if (x != p->root && d > every) { p->scale[x] = 1; d = 1; }
-         cnt[x] = d;
-      }
-      free(cnt); free(order);
-   }
+   p->scale = (unsigned char *)calloc(nn, 1);
+   pamlh_set_node_scale(p);
    free(stack); free(nson);
    return 0;
+}
+
+/* SetNodeScale (treesub.c:7177-7197) on the tree as it stands (a tree just read; a tree after pamlh_apply_nni): p->scale[nnode] */
+void pamlh_set_node_scale(pamlh *p)
+{
+   const int every = p->is_codeml ? (p->seqtype == 1 ? 15 : 50) : 100, nn = p->nnode;
+   int *cnt = (int *)calloc(nn, sizeof(int)), *order = (int *)malloc(nn * sizeof(int)), *stack = (int *)malloc(nn * sizeof(int)), no = 0, sp = 0, i;
+   memset(p->scale, 0, nn);
+   stack[sp++] = p->root;     /* post-order via reversed pre-order */
+   while (sp) { int x = stack[--sp], j; order[no++] = x; for (j = p->sons_ptr[x]; j < p->sons_ptr[x + 1]; j++) stack[sp++] = p->sons[j]; }
+   for (i = no - 1; i >= 0; i--) {
+      int x = order[i], j, d = 0;
+      if (p->sons_ptr[x + 1] == p->sons_ptr[x]) continue;
+      for (j = p->sons_ptr[x]; j < p->sons_ptr[x + 1]; j++) { int c = p->sons[j]; d += (p->sons_ptr[c + 1] > p->sons_ptr[c]) ? cnt[c] : 1; }
+      if (x != p->root && d > every) { p->scale[x] = 1; d = 1; }
+      cnt[x] = d;
+   }
+   free(cnt); free(order); free(stack);
 }

@@ -1,5 +1,5 @@
 /* pamlh_lnl — command-line driver: one likelihood evaluation of a codeml/baseml analysis on the MI355X.
- *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
+ *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
  *   (--set "key = value": replaces an option of the control file, e.g. one of the site models of an "NSsites = 0 1 2 7 8" list;
  *    --tree K: the K-th tree of the tree file, 1-based; --all-trees: every tree in turn — the reference's loop, Forestry codeml.c:635 —
  *    each optimised from the control file's initial values, then the comparison table of rell(), treesub.c:5844;
@@ -9,6 +9,10 @@
  *    alignment's own length) drawn on the GPU under the model at the parameter vector the driver would otherwise evaluate — the control
  *    file's initial values, in.codeml / in.baseml, the command line's, or the estimates after --optimize — written as sequential PHYLIP
  *    to OUT, or OUT.0000, OUT.0001 ... for R > 1: the parametric bootstrap's data sets, the job of evolver (evolver.c:818))
+ *    --nni-scores: the table of the tree's nearest-neighbour-interchange neighbours (v, s, x: son s of node v changes places with son x
+ *    of v's father), their lnL at the parameter vector from one engine call and the difference to the present tree's;
+ *    --nni-search [--max-moves N]: the NNI hill climb of the reference's runmode = 5 from the tree of the tree file (pamlh_nni_search):
+ *    every accepted move, then the tree found with its estimates and lnL)
  * Reads the control file, the sequence and tree files it names, and the parameter vector from the command line,
  * else from in.codeml / in.baseml beside the ctl (the reference's "-1 x..." single-evaluation recipe, treesub.c:4057),
  * else the ctl's initial values; evaluates lnL through libpaml_amd.so; prints `lnL = ...` like the reference and
@@ -117,7 +121,7 @@ int main(int argc, char **argv)
    pamlh *p;
    char err[512];
    double x[4096], lnL, *lnf;
-   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0;
+   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0;
    char over[2048] = "";
    const char *sim_out = NULL, *bv_out = NULL;
    long sim_sites = 0;
@@ -125,10 +129,13 @@ int main(int argc, char **argv)
    unsigned char comm_id[PAML_AMD_COMM_ID_BYTES];
    int device[MAX_RANKS];
    for (i = 0; i < MAX_RANKS; i++) device[i] = i;
-   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
+   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
    for (i = 3; i < argc && nx < 4096; i++) {
       if (!strcmp(argv[i], "--optimize")) optimize = 1;
       else if (!strcmp(argv[i], "--analytic-gradient")) analytic = 1;      /* with --optimize: the branch lengths' derivatives from one engine call per gradient */
+      else if (!strcmp(argv[i], "--nni-scores")) nni_scores = 1;
+      else if (!strcmp(argv[i], "--nni-search")) nni_search = 1;
+      else if (!strcmp(argv[i], "--max-moves") && i + 1 < argc) max_moves = atoi(argv[++i]);
       else if (!strcmp(argv[i], "--bv") && i + 1 < argc) bv_out = argv[++i];      /* gradient and Hessian of the branch lengths, the reference's rst2 block (mcmctree's in.BV) */
       else if (!strcmp(argv[i], "--ancestral")) ancestral = 1;
       else if (!strcmp(argv[i], "--ancestral-all")) ancestral_all = 1;
@@ -243,6 +250,34 @@ int main(int argc, char **argv)
    if (!nx) nx = pamlh_default_x(p, x, 4096);
    if (nx != np) { fprintf(stderr, "error: the model has %d parameters (ntime %d) but %d values were given\n", np, ntime, nx); return 1; }
    if (analytic) pamlh_use_analytic_gradient(p, 1);
+   if (nni_scores || nni_search) {      /* the neighbours' table at x, or the hill climb from x; instead of the evaluation */
+      int nnode = 0, n = 0, stats[3] = {0, 0, 0};
+      char *nw;
+      if (gpus > 0) { fprintf(stderr, "error: --nni-scores and --nni-search run on one GPU\n"); return 1; }
+      pamlh_dims(p, NULL, NULL, NULL, &nnode, NULL, NULL, NULL, NULL, NULL, NULL);
+      if (nni_scores) {
+         int *sw;
+         double *sc, l0 = 0;
+         if (pamlh_nni_scores(p, NULL, &n, NULL, NULL, NULL)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+         sw = (int *)malloc((size_t)(3 * n + 3) * sizeof(int)); sc = (double *)malloc((n + 1) * sizeof(double));
+         if (pamlh_nni_scores(p, x, &n, sw, &l0, sc)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+         printf("NNI neighbours at the present branch lengths (one engine call): lnL of the present tree = %.6f\n%6s%6s%6s %16s %14s\n", l0, "v", "s", "x", "lnL", "difference");
+         for (i = 0; i < n; i++) printf("%6d%6d%6d %16.6f %14.6f\n", sw[3 * i] + 1, sw[3 * i + 1] + 1, sw[3 * i + 2] + 1, sc[i], sc[i] - l0);
+         free(sw); free(sc);
+      }
+      if (nni_search) {
+         if (pamlh_nni_search(p, x, &lnL, max_moves, 1, stats)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+         printf("NNI search: %d moves, %d screening calls, %d neighbours maximised\n", stats[0], stats[1], stats[2]);
+         nw = (char *)malloc((size_t)160 * nnode + 256);
+         if (!pamlh_newick(p, nw, 160 * nnode + 256)) printf("%s\n", nw);
+         free(nw);
+         printf("x:");
+         for (i = 0; i < np; i++) printf(" %.6f", x[i]);
+         printf("\nlnL  = %.4f\n", lnL);
+      }
+      pamlh_free(p);
+      return 0;
+   }
    if (optimize) {
       /* method = 1 in the control file: minB / minbranches (one branch at a time on the branch-local derivatives) */
       const int method1 = pamlh_method(p) == 1;

@@ -20,7 +20,7 @@ DRIVER_PATH = os.path.join(_HERE, "lib", "pamlh_lnl")
 def build(force=False):
     from . import engine
     engine.build()
-    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
+    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "pamlh.h"))
     if force or not (os.path.exists(LIB_PATH) and os.path.exists(DRIVER_PATH)) or \
             any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
@@ -349,6 +349,38 @@ class Analysis:
         if rc < 0:
             raise RuntimeError("pamlh_optimize: " + self._L.pamlh_error(self._h).decode())
         return dict(x=x, lnL=lnl.value, converged=rc == 0, n_eval=nev.value)
+
+    def nni_scores(self, x):
+        """The lnL of every nearest-neighbour-interchange neighbour of the tree as it stands at x, from one engine call
+        (pamlh_nni_scores): dict(lnL0, swaps=[n_swaps][3] (v, s, x; 0-based nodes), lnL=[n_swaps])."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        n, l0 = C.c_int(), C.c_double()
+        f = self._L.pamlh_nni_scores
+        f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_double), C.c_void_p]
+        if len(x) != self.np or f(self._h, None, C.byref(n), None, None, None) != 0:
+            raise RuntimeError("pamlh_nni_scores: " + self._L.pamlh_error(self._h).decode())
+        swaps, lnl = np.zeros((max(1, n.value), 3), dtype=np.int32), np.zeros(max(1, n.value))
+        if f(self._h, x.ctypes.data_as(C.c_void_p), C.byref(n), swaps.ctypes.data_as(C.c_void_p), C.byref(l0), lnl.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_nni_scores: " + self._L.pamlh_error(self._h).decode())
+        return dict(lnL0=l0.value, swaps=swaps[:n.value], lnL=lnl[:n.value])
+
+    def apply_nni(self, v, s, x):
+        """Exchange son s of v with son x of the father of v on the analysis's tree (pamlh_apply_nni); apply_nni(v, x, s) undoes it."""
+        self._L.pamlh_apply_nni.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        if self._L.pamlh_apply_nni(self._h, int(v), int(s), int(x)) != 0:
+            raise RuntimeError("pamlh_apply_nni: " + self._L.pamlh_error(self._h).decode())
+
+    def nni_search(self, x0, max_moves=0, verbose=False):
+        """NNI hill climb from the tree as it stands (pamlh_nni_search): dict(x, lnL, moves, screening_calls, optimisations, newick)."""
+        x = np.ascontiguousarray(x0, dtype=np.float64).copy()
+        lnl, stats = C.c_double(), (C.c_int * 3)()
+        self._L.pamlh_nni_search.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p]
+        if len(x) != self.np or self._L.pamlh_nni_search(self._h, x.ctypes.data_as(C.c_void_p), C.byref(lnl), int(max_moves), int(bool(verbose)), stats) != 0:
+            raise RuntimeError("pamlh_nni_search: " + self._L.pamlh_error(self._h).decode())
+        buf = C.create_string_buffer(160 * self.n_nodes + 256)
+        self._L.pamlh_newick.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+        newick = buf.value.decode() if self._L.pamlh_newick(self._h, buf, len(buf)) == 0 else None
+        return dict(x=x, lnL=lnl.value, moves=stats[0], screening_calls=stats[1], optimisations=stats[2], newick=newick)
 
     def write_bv(self, x, path):
         """The gradient and Hessian of the branch lengths at x in the layout of the reference's rst2 block (pamlh_write_bv)."""

@@ -38,6 +38,33 @@ class Tree:
                 f[c] = i
         return f
 
+    def nni_swaps(self):
+        """The canonical list of nearest-neighbour-interchange swaps (v, s, x), int32 [n_swaps][3], as paml_amd_nni_list writes it: every
+        internal v that is not the root in node order, s over its sons, x over its father's other sons; a v with two sons under a root
+        with exactly three sons lists its first son only (the other's swaps are the same unrooted trees), so an unrooted binary tree
+        of ns tips has 2 (ns - 3)."""
+        f = self.father()
+        out = []
+        for v in range(self.n_nodes):
+            if v == self.root or f[v] < 0 or not self.sons[v]:
+                continue
+            fa = int(f[v])
+            half = fa == self.root and len(self.sons[fa]) == 3 and len(self.sons[v]) == 2
+            for s in (self.sons[v][:1] if half else self.sons[v]):
+                out += [(v, int(s), int(x)) for x in self.sons[fa] if x != v]
+        return np.asarray(out, dtype=np.int32).reshape(-1, 3)
+
+    def nni(self, v, s, x):
+        """A new Tree with son s of v and son x of the father of v exchanged in place in the two son lists: the subtrees change places,
+        each keeps the branch above it.  Node ids, branch and label are untouched (shared with this tree)."""
+        fa = int(self.father()[v])
+        if v == self.root or fa < 0 or s not in self.sons[v] or x == v or x not in self.sons[fa]:
+            raise ValueError("nni(%d, %d, %d): not a swap of this tree" % (v, s, x))
+        sons = [list(c) for c in self.sons]
+        sons[v][sons[v].index(s)] = int(x)
+        sons[fa][sons[fa].index(x)] = int(s)
+        return Tree(self.n_tips, self.n_nodes, self.root, sons, self.branch, self.label, self.names)
+
     def newick(self, names=None, lengths=True):
         names = names or self.names or [str(i + 1) for i in range(self.n_tips)]
 
