@@ -526,6 +526,33 @@ void paml_amd_nni_info(int *last_batches, double *last_kernel_ms);
  * NULL the length only), or PAML_AMD_EINVAL for a bad tree or a list longer than cap. */
 int paml_amd_nni_list(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, int *swaps /* [cap][3], or NULL */, int cap);
 
+/* ---- Placement: the lnL of the tree with one more tip hung on a branch, for every query, every branch and every pendant length in ONE
+ * call.  The reference's stepwise addition (StepwiseAddition treesub.c:4866 on AddSpecies treesub.c:4592) sets and evaluates one enlarged
+ * tree after the other; the same primitive lies under the regraft half of an SPR move and under placing new sequences on a fitted tree.
+ * An edge is a node v != root (the branch above v, length t_v, label lambda_v).  Placing query q on edge v with split phi in [0, 1] and
+ * pendant length tau makes a new internal node u between v's father and v: the branch above u has length (1 - phi) t_v, the branch above
+ * v has length phi t_v (both labelled lambda_v), and u's second son is the query tip on a branch of length tau labelled pendant_label.
+ * lnL[q][e][j] is what paml_amd_eval returns for that tree as rooted, to rounding (the definition: kernels_place.h); lnL0 is the present
+ * tree's.  qz holds the queries' character codes per pattern, numbered as the table given to paml_amd_set_tips.  edges = NULL means every
+ * non-root node in node order (n_edges must then be n_nodes - 1).  Nothing is re-rooted and no reversibility is assumed; every P(t) comes
+ * from the evaluation's own builder, so every kind of set, class rates, gene rates and Qfactors are served.  Afterwards the engine holds
+ * P(t) of the tree at `branch`, as after paml_amd_nni_scores.  n_patt is walked gene by gene in batches of what a workspace holds (256
+ * MiB; the environment variable PAML_AMD_PLACE_ARENA_MB, read at every call, gives another size in MiB), and the edges in groups where one
+ * tile of patterns with all rows does not fit: every output has the same bits for any workspace size, for any sub-list or order of
+ * queries, edges and pendants and on every call (fixed-order sums, no atomics).  PAML_AMD_EINVAL (with a message starting
+ * "placement_scores") for a null branch, qz, pendant, lnL0 or lnL, n_q, n_edges or n_pend < 1, a code in qz that is >= n_codes or has an
+ * empty state set, an edge that is the root or out of range, phi outside [0, 1], a negative or non-finite pendant, a pendant_label
+ * outside the class tables' labels, a model or tips not set; PAML_AMD_EUNSUPPORTED for tips that are not the nodes 0 .. n_tips - 1, more
+ * than 64 states, an engine whose communicator has more than one rank; PAML_AMD_ENOCONV as the other synchronous entries. */
+int paml_amd_placement_scores(paml_amd_engine *e, const double *branch, const double *gene_rate,
+                              int n_q, const unsigned char *qz /* [n_q][n_patt] */,
+                              int n_edges, const int *edges /* [n_edges] nodes v != root, or NULL */,
+                              int n_pend, const double *pendant /* [n_pend] */, double phi, int pendant_label,
+                              double *lnL0, double *lnL /* [n_q][n_edges][n_pend] */, double *lnf /* [n_q][n_edges][n_pend][n_patt], or NULL */);
+/* The number of pattern batches the calling thread's last paml_amd_placement_scores walked and the time of its kernels by HIP events
+ * (ms, summed); either pointer may be NULL. */
+void paml_amd_placement_info(int *last_batches, double *last_kernel_ms);
+
 /* ---- Pairwise maximum-likelihood comparisons (codeml runmode = -2; PairwiseCodon codeml.c:4344-4604, Goldman & Yang 1994).
  * The reference takes the ns (ns - 1) / 2 pairs one after the other, each a search over (t, kappa, omega) whose every function call
  * (lfun2dSdN codeml.c:4219-4264) decomposes a rate matrix on one core.  Here a PAIR SET lives on an engine whose tips are clean data

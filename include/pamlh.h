@@ -159,6 +159,34 @@ int pamlh_nni_scores(pamlh *p, const double *x, int *n_swaps, int *swaps, double
 int pamlh_apply_nni(pamlh *p, int v, int s, int x);
 int pamlh_nni_search(pamlh *p, double *x, double *lnL, int max_moves, int verbose, int *stats);
 
+/* Query sequences placed on every branch of the analysis's tree (pamlh_place.c): the likelihood of the tree with one more tip hung on
+ * branch e, for every query, every branch and every pendant length of a grid, from ONE engine call (paml_amd_placement_scores) — the
+ * primitive under the reference's stepwise addition (StepwiseAddition treesub.c:4866 on AddSpecies treesub.c:4592, which sets and
+ * evaluates one enlarged tree after the other), under the regraft half of an SPR move and under placing new sequences on a fitted tree.
+ * pamlh_load_placement: pamlh_load_with, except that the tree may name only some of the sequence file's sequences, at least 3, by name
+ *   or by 1-based number in file order.  The sequences absent from the tree are the QUERIES; the tree's sequences become the tips
+ *   0 .. m - 1 in file order.  Site patterns are compressed over all sequences together, so patterns that differ only in a query stay
+ *   apart, with their own weights.  Everything counted from the data (observed frequencies, F3x4, ...) is counted on the tree's sequences
+ *   only: an x estimated without the queries means the same thing here.  With cleandata = 1 a site is dropped if ANY sequence has an
+ *   ambiguity character there, the queries included.  pamlh_load / pamlh_load_with themselves are as they were.
+ * pamlh_n_queries, pamlh_query_name, pamlh_query_codes ([n_queries][npatt] character codes, the tips' table).
+ * pamlh_placement_scores: lnL[n_queries][nbranch][n_pend] of query q hung on the b-th branch of x's branch-length block
+ *   (pamlh_branch_order), the new node at phi of the branch's length above its lower end, with pendant length pendant[j] (branch label 0),
+ *   at the branch lengths and parameters of x; *lnL0 the tree's own lnL.
+ * pamlh_place: per query the best (branch, pendant length) of the grid — best_edge[n_queries] (index into pamlh_branch_order),
+ *   best_pendant, best_lnL — and lwr[n_queries][nbranch], the likelihood weight ratios exp(l_e - logsumexp_e' l_e') with l_e the largest
+ *   lnL of branch e over the grid.  Any output may be NULL.
+ * pamlh_placement_newick: the tree with query q hung on branch `edge`, with the lengths of the last x (written so that they read back
+ *   to the same doubles); cap >= 160 (n_nodes + 2) + 256.
+ * Refused by name: a clock (x holds node ages), rho models, runmode = -2, an analysis without queries, a pattern shard. */
+int pamlh_load_placement(pamlh **out, const char *ctl_path, const char *program, int tree_index, const char *overrides, char *err, int errcap);
+int pamlh_n_queries(const pamlh *p);
+const char *pamlh_query_name(const pamlh *p, int i);
+const unsigned char *pamlh_query_codes(const pamlh *p);
+int pamlh_placement_scores(pamlh *p, const double *x, int n_pend, const double *pendant, double phi, double *lnL0, double *lnL);
+int pamlh_place(pamlh *p, const double *x, int n_pend, const double *pendant, double phi, int *best_edge, double *best_pendant, double *best_lnL, double *lwr);
+int pamlh_placement_newick(pamlh *p, int q, int edge, double phi, double pendant, char *buf, int cap);
+
 /* method = 1 of the control file: minB / minbranches (treesub.c:7826, 8039) — the branch lengths are optimised one at a time
  * by Newton steps on the branch-local lnL, dlnL/dt, d2lnL/dt2 (paml_amd_eval_branch; the engine keeps the partials of both
  * sides of every edge resident, so a step along the tree costs the nodes on the path, not the tree), alternating with BFGS

@@ -1,5 +1,5 @@
 // ancestral_host.h — the host side that the calls walking a down pass and an outer pass over the whole tree share (defined in
-// engine_ancestral.hip; used there, by engine_gradient.hip and by engine_nni.hip): the packed tree, P(t) from the evaluation's own builders, the batch size.
+// engine_ancestral.hip; used there, by engine_gradient.hip, engine_nni.hip and engine_place.hip): the packed tree, P(t) from the evaluation's own builders, the batch size.
 #pragma once
 #include "engine_state.h"
 
@@ -24,7 +24,7 @@ struct AncScratch {
 };
 
 int anc_tree_pack(paml_amd_engine *e, const char *who, AncScratch &w, AncTree *out);
-int anc_pmat(paml_amd_engine *e, const char *who, const double *branch, const double *gene_rate, AncScratch &w);
+int anc_pmat(paml_amd_engine *e, const char *who, const double *branch, const double *gene_rate, AncScratch &w, const int *d_label = nullptr);
 long anc_batch(double bytes_per_patt, long n_patt, const char *env = "PAML_AMD_ANC_ARENA_MB");
 int anc_common_checks(paml_amd_engine *e, const char *who);
 

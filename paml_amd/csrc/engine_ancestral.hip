@@ -58,7 +58,8 @@ int anc_tree_pack(paml_amd_engine *e, const char *who, AncScratch &w, AncTree *o
 }
 
 // P(t) of every (gene, class, node), as an evaluation builds it: same kernels, same arguments (paml_amd_simulate does the same for one gene)
-int anc_pmat(paml_amd_engine *e, const char *who, const double *branch, const double *gene_rate, AncScratch &w)
+// (`d_label`: the nodes' labels on the device; null: the tree's own.  A call may build more than one family of matrices: the events are made once)
+int anc_pmat(paml_amd_engine *e, const char *who, const double *branch, const double *gene_rate, AncScratch &w, const int *d_label)
 {
    const TreeDesc &T = e->tree;
    const int nn = T.n_nodes, K = e->K, G = e->n_genes, n = e->n;
@@ -79,14 +80,14 @@ int anc_pmat(paml_amd_engine *e, const char *who, const double *branch, const do
       HIPCHK(hipStreamSynchronize(st));      // (`gr` is on this stack)
       e->bl_gr_sent = false;
    }
-   HIPCHK(hipEventCreate(&w.ev0));
-   HIPCHK(hipEventCreate(&w.ev1));
+   if (!w.ev0) HIPCHK(hipEventCreate(&w.ev0));
+   if (!w.ev1) HIPCHK(hipEventCreate(&w.ev1));
    if (int rc = ensure_pmat_buffers(e, G * K, false, false)) return rc;
    // (from here on the P(t) buffers are this call's: whatever looked at an earlier evaluation's starts over)
    e->pmat_valid = false;
    e->bl.valid = false;
    HIPCHK(hipEventRecord(w.ev0, st));
-   PmatArgs pa = pmat_args(e, T.root, e->d_label.p, e->kk == KK_MFMA64 ? 1 : 0, nullptr);
+   PmatArgs pa = pmat_args(e, T.root, d_label ? d_label : e->d_label.p, e->kk == KK_MFMA64 ? 1 : 0, nullptr);
    InlineVec iv;
    iv.n_branch = iv.n_rate = 0;
    bool small_pmat = e->kk != KK_MFMA64 && n <= 5;

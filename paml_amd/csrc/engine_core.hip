@@ -171,6 +171,9 @@ int paml_amd_set_tips(paml_amd_engine *e, const unsigned char *z, int cleandata,
    // at s, the others by (cells that hold the code) x (states of its set), descending, so that "missing" and whatever else is frequent
    // sit below 64.  Invisible to the caller: codes only index the tip tables.
    std::vector<unsigned char> zperm;
+   e->code_nch = nch;
+   e->code_new_of.resize(n_codes);
+   for (int c = 0; c < n_codes; c++) e->code_new_of[c] = (unsigned char)c;
    if (e->kk == KK_MFMA64 && n_codes > 64) {
       std::vector<long> cnt(n_codes, 0);
       for (size_t i = 0; i < nz; i++) cnt[z[i]]++;
@@ -185,6 +188,7 @@ int paml_amd_set_tips(paml_amd_engine *e, const unsigned char *z, int cleandata,
       }
       nch.swap(nch2);
       cmap.swap(cmap2);
+      e->code_new_of = new_of;
       zperm.resize(nz);
       for (size_t i = 0; i < nz; i++) zperm[i] = new_of[z[i]];
       z = zperm.data();

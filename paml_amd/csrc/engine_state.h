@@ -15,6 +15,7 @@
 //   engine_ancestral.hip marginal and joint ancestral reconstruction at every internal node (P(t) by launch_pmat, then its own kernels)
 //   engine_gradient.hip  the derivative of lnL with respect to every branch length and the per-pattern scores (P(t) and the down pass as
 //                       engine_ancestral.hip, whose host helpers it shares through ancestral_host.h; then its own kernels)
+//   engine_place.hip    the lnL of the tree with a query tip hung on every branch (the same shared host helpers as engine_nni.hip)
 //   engine_nni.hip      the lnL of every nearest-neighbour-interchange neighbour of the tree (P(t), the down pass and the host helpers as
 //                       engine_gradient.hip; the outer pass without the derivative and the swap pass are its own kernels)
 // Built for gfx950 only.
@@ -341,6 +342,8 @@ struct paml_amd_engine {
    // data
    bool have_tips = false, have_tree = false, have_pi = false, have_classes = false;
    int cleandata = 1, n_codes = 0;
+   std::vector<int> code_nch;                   // set_tips: states in the caller's code c's set
+   std::vector<unsigned char> code_new_of;      // set_tips: the caller's code c -> the engine's own number of it (code_order; else c itself)
    DevBuf<unsigned char> d_z, d_chara_map, d_is_leaf, d_ztiles;
    int zt_bytes = 0;
    DevBuf<int> d_n_chara, d_gene_off, d_label, d_eigen_of, d_b_eigen_of;

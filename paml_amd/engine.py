@@ -38,6 +38,7 @@ EXPORTS = [
     "paml_amd_ancestral_marginal", "paml_amd_ancestral_joint", "paml_amd_ancestral_info",
     "paml_amd_gradient", "paml_amd_gradient_info",
     "paml_amd_nni_scores", "paml_amd_nni_info", "paml_amd_nni_list",
+    "paml_amd_placement_scores", "paml_amd_placement_info",
 ]
 
 
@@ -52,7 +53,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_nni")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_nni", "engine_place")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -512,6 +513,33 @@ class Engine:
         self._chk(self._L.paml_amd_nni_scores(self._h, _p(b), _p(g), len(sw), _p(sw), C.byref(lnL0), _p(lnL), _p(lnf)))
         return dict(lnL0=lnL0.value, swaps=sw, lnL=lnL, lnf=lnf)
 
+    def placement_scores(self, branch, gene_rate=None, queries=None, edges=None, pendant=(0.1,), phi=0.5, pendant_label=0, want_lnf=False):
+        """The lnL of the tree at `branch` with a query tip hung on a branch, for every query, edge and pendant length in one call
+        (paml_amd_placement_scores): dict(lnL0 (the present tree's), edges=[n_edges] (nodes v: the branch above v), lnL=[n_q][n_edges][n_pend],
+        lnf=[n_q][n_edges][n_pend][n_patt] or None).  queries: uint8 [n_q][n_patt] character codes; edges None: every non-root node of the
+        tree last set, in node order.  The new node splits the branch above v into phi t_v (above v) and (1 - phi) t_v."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        if queries is None:
+            raise EngineError("placement_scores: no queries")
+        qz = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.uint8)
+        if qz.ndim != 2 or qz.shape[1] != self.n_patt:
+            raise EngineError("placement_scores: queries must be [n_q][n_patt]")
+        if edges is None:
+            if getattr(self, "_tree_csr", None) is None:
+                raise EngineError("placement_scores: no tree was set through this object")
+            edges = [v for v in range(self.n_nodes) if v != self._tree_csr[0]]
+        ed = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1)
+        pe = np.ascontiguousarray(np.atleast_1d(pendant), dtype=np.float64).reshape(-1)
+        lnL0 = C.c_double()
+        lnL = np.zeros((len(qz), len(ed), len(pe)))
+        lnf = np.zeros((len(qz), len(ed), len(pe), self.n_patt)) if want_lnf else None
+        self._L.paml_amd_placement_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                      C.c_double, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
+        self._chk(self._L.paml_amd_placement_scores(self._h, _p(b), _p(g), len(qz), _p(qz), len(ed), _p(ed), len(pe), _p(pe), float(phi),
+                                                    int(pendant_label), C.byref(lnL0), _p(lnL), _p(lnf)))
+        return dict(lnL0=lnL0.value, edges=ed, lnL=lnL, lnf=lnf)
+
     def get_pmat(self, gene, iclass, node):
         P = np.zeros((self.n, self.n))
         self._chk(self._L.paml_amd_get_pmat(self._h, gene, iclass, node, _p(P)))
@@ -843,6 +871,17 @@ def nni_info():
     L.paml_amd_nni_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.paml_amd_nni_info.restype = None
     L.paml_amd_nni_info(C.byref(nb), C.byref(ms))
+    return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def placement_info():
+    """Batches walked by this thread's last Engine.placement_scores and the time of its kernels by HIP events
+    (paml_amd_placement_info): dict(last_batches, last_kernel_ms)."""
+    L = lib()
+    nb, ms = C.c_int(), C.c_double()
+    L.paml_amd_placement_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.paml_amd_placement_info.restype = None
+    L.paml_amd_placement_info(C.byref(nb), C.byref(ms))
     return dict(last_batches=nb.value, last_kernel_ms=ms.value)
 
 

@@ -102,6 +102,12 @@ struct pamlh {
    int *nh_label, nh_nbtype;   /* nhomo = 5 / fix_kappa = 2: the tree file's '#' labels name the frequency / rate sets; number of branch types */
    int *rate_label, n_brate;   /* clock = 2: rate class of the branch above every node, number of classes */
    int malpha;               /* Malpha: a gamma shape per gene; rate[] then holds [gene][class] */
+   /* placement (pamlh_load_placement, pamlh_place.c): the sequences of the file that the tree does not name are the queries; they stand
+    * apart from the tips, which are the tree's sequences 0 .. ns - 1 in file order */
+   int n_query, ns_file;     /* queries; sequences in the file (0: an ordinary load) */
+   char **query_names;
+   unsigned char *query_z;   /* [n_query][npatt] character codes */
+   int *file_row;            /* [ns_file]: the tip a sequence of the file became, -1 for a query (NULL: an ordinary load) */
    int pairwise;             /* runmode = -2: pairwise comparisons (pamlh_pairwise.c); no tree, no model state */
    int opt_transformed;      /* pamlh_optimize is iterating on transformed proportions (pamlh_opt.c) */
    int analytic_gradient;    /* pamlh_use_analytic_gradient: pamlh_optimize takes the branch lengths' derivatives from paml_amd_gradient */
@@ -159,6 +165,8 @@ int pamlh_x_to_branches(const pamlh *p, const double *x, double *branch);
 void pamlh_dnds_one(const pamlh *p, const double *pi, double kappa, double omega, double t, double ls, double *N, double *S, double *dN, double *dS);
 double pamlh_codon_q(const pamlh *p, const double *pi, double kappa, double omega, double *Q);
 int pamlh_codon_pattern_flags(const pamlh *p, const int **row, const int **col, unsigned char *flags);      /* flags: room for 704 */
+int pamlh_load_impl(pamlh **out, const char *ctl_path, const char *program, int tree_index, const char *overrides, int placement, char *err, int errcap);
+int pamlh_split_queries(pamlh *p);      /* pamlh_place.c: after pamlh_read_seqs, before pamlh_read_tree */
 pamlh *pamlh_state_clone(const pamlh *p);
 void pamlh_state_free(pamlh *q);
 #endif

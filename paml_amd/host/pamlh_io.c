@@ -600,7 +600,7 @@ int pamlh_read_tree(pamlh *p)
             if (!strcmp(name, p->names[i])) { tip = i; break; }
          if (tip < 0) {
             char *e; long v = strtol(name, &e, 10);
-            if (*e == 0 && v >= 1 && v <= ns) tip = (int)v - 1;
+            if (*e == 0 && v >= 1 && v <= (p->file_row ? p->ns_file : ns)) tip = p->file_row ? p->file_row[v - 1] : (int)v - 1;      /* (placement: the number counts the file's sequences) */
          }
          if (tip < 0) { free(buf); return pamlh_fail(p, "species %s in the tree is not in the sequence file", name); }
          if (depth < 1) { free(buf); return pamlh_fail(p, "bad tree"); }

@@ -1,5 +1,5 @@
 /* pamlh_lnl — command-line driver: one likelihood evaluation of a codeml/baseml analysis on the MI355X.
- *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
+ *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
  *   (--set "key = value": replaces an option of the control file, e.g. one of the site models of an "NSsites = 0 1 2 7 8" list;
  *    --tree K: the K-th tree of the tree file, 1-based; --all-trees: every tree in turn — the reference's loop, Forestry codeml.c:635 —
  *    each optimised from the control file's initial values, then the comparison table of rell(), treesub.c:5844;
@@ -13,6 +13,11 @@
  *    of v's father), their lnL at the parameter vector from one engine call and the difference to the present tree's;
  *    --nni-search [--max-moves N]: the NNI hill climb of the reference's runmode = 5 from the tree of the tree file (pamlh_nni_search):
  *    every accepted move, then the tree found with its estimates and lnL)
+ *    --place [--pendant a,b,c] [--split PHI]: the tree of the tree file may name only some of the sequences; the others are queries
+ *    (pamlh_load_placement).  Per query one table row per branch — father..node, the best pendant length of the grid (default 0.05, 0.1,
+ *    0.2, 0.4), the lnL of the tree with the query hung there at PHI (default 0.5) of the branch above the node, the difference to the
+ *    tree's own lnL, the likelihood weight ratio — from one engine call, then the best placement's tree.  The parameter vector is the
+ *    one the driver would evaluate, or the estimates after --optimize on the tree's sequences)
  * Reads the control file, the sequence and tree files it names, and the parameter vector from the command line,
  * else from in.codeml / in.baseml beside the ctl (the reference's "-1 x..." single-evaluation recipe, treesub.c:4057),
  * else the ctl's initial values; evaluates lnL through libpaml_amd.so; prints `lnL = ...` like the reference and
@@ -121,7 +126,8 @@ int main(int argc, char **argv)
    pamlh *p;
    char err[512];
    double x[4096], lnL, *lnf;
-   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0;
+   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0, place = 0, n_pend = 4;
+   double pend[64] = {0.05, 0.1, 0.2, 0.4}, split = 0.5;
    char over[2048] = "";
    const char *sim_out = NULL, *bv_out = NULL;
    long sim_sites = 0;
@@ -129,13 +135,19 @@ int main(int argc, char **argv)
    unsigned char comm_id[PAML_AMD_COMM_ID_BYTES];
    int device[MAX_RANKS];
    for (i = 0; i < MAX_RANKS; i++) device[i] = i;
-   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
+   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
    for (i = 3; i < argc && nx < 4096; i++) {
       if (!strcmp(argv[i], "--optimize")) optimize = 1;
       else if (!strcmp(argv[i], "--analytic-gradient")) analytic = 1;      /* with --optimize: the branch lengths' derivatives from one engine call per gradient */
       else if (!strcmp(argv[i], "--nni-scores")) nni_scores = 1;
       else if (!strcmp(argv[i], "--nni-search")) nni_search = 1;
       else if (!strcmp(argv[i], "--max-moves") && i + 1 < argc) max_moves = atoi(argv[++i]);
+      else if (!strcmp(argv[i], "--place")) place = 1;
+      else if (!strcmp(argv[i], "--pendant") && i + 1 < argc) {      /* the grid of pendant lengths, e.g. "0.05,0.1,0.2" */
+         char *tok = strtok(argv[++i], ",");
+         for (n_pend = 0; tok && n_pend < 64; tok = strtok(NULL, ",")) pend[n_pend++] = atof(tok);
+      }
+      else if (!strcmp(argv[i], "--split") && i + 1 < argc) split = atof(argv[++i]);
       else if (!strcmp(argv[i], "--bv") && i + 1 < argc) bv_out = argv[++i];      /* gradient and Hessian of the branch lengths, the reference's rst2 block (mcmctree's in.BV) */
       else if (!strcmp(argv[i], "--ancestral")) ancestral = 1;
       else if (!strcmp(argv[i], "--ancestral-all")) ancestral_all = 1;
@@ -201,7 +213,8 @@ int main(int argc, char **argv)
       return 0;
    }
    if (gpus > 0 && spawn_ranks(gpus, device, &rank, comm_id)) { fprintf(stderr, "error: could not start %d ranks (GPUs visible: %d; librccl.so.1 present?)\n", gpus, paml_amd_device_count()); return 1; }
-   if (pamlh_load_with(&p, argv[2], argv[1], itree, over, err, sizeof(err))) { fprintf(stderr, "error: %s\n", err); return 1; }
+   if (place && (gpus > 0 || all_trees)) { fprintf(stderr, "error: --place runs on one GPU, on one tree\n"); return 1; }
+   if ((place ? pamlh_load_placement : pamlh_load_with)(&p, argv[2], argv[1], itree, over, err, sizeof(err))) { fprintf(stderr, "error: %s\n", err); return 1; }
    if (gpus > 0 && pamlh_set_shard(p, rank, gpus, comm_id)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
    if (pamlh_is_pairwise(p)) {      /* runmode = -2: all pairs' searches in lock step; 2ML.t, 2ML.dN, 2ML.dS and rst as the reference writes them */
       const int npair = pamlh_pairwise_n(p);
@@ -275,6 +288,43 @@ int main(int argc, char **argv)
          for (i = 0; i < np; i++) printf(" %.6f", x[i]);
          printf("\nlnL  = %.4f\n", lnL);
       }
+      pamlh_free(p);
+      return 0;
+   }
+   if (place) {      /* the queries on every branch at x, or at the estimates on the tree's sequences; instead of the evaluation */
+      const int nq = pamlh_n_queries(p), *order = pamlh_branch_order(p), *sptr = pamlh_sons_ptr(p), *sons = pamlh_sons(p);
+      int nnode = 0, nb, q, e, j, n_eval = 0, *father, *be;
+      double l0 = 0, *sc, *lwr, *bp, *bl;
+      char *nw;
+      pamlh_dims(p, NULL, NULL, NULL, &nnode, NULL, NULL, NULL, NULL, NULL, NULL);
+      nb = nnode - 1;
+      if (optimize && np > 0) {
+         if (pamlh_optimize(p, x, &lnL, 500, 1e-10, 0, &n_eval) < 0) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+         printf("estimates on the tree's sequences after %d likelihood evaluations: lnL = %.6f\nx:", n_eval, lnL);
+         for (i = 0; i < np; i++) printf(" %.6f", x[i]);
+         printf("\n");
+      }
+      father = (int *)malloc(nnode * sizeof(int));
+      for (i = 0; i < nnode; i++) for (j = sptr[i]; j < sptr[i + 1]; j++) father[sons[j]] = i;
+      sc = (double *)malloc((size_t)(nq > 0 ? nq : 1) * nb * n_pend * sizeof(double)); lwr = (double *)malloc((size_t)(nq > 0 ? nq : 1) * nb * sizeof(double));
+      be = (int *)malloc((nq > 0 ? nq : 1) * sizeof(int)); bp = (double *)malloc((nq > 0 ? nq : 1) * sizeof(double)); bl = (double *)malloc((nq > 0 ? nq : 1) * sizeof(double));
+      nw = (char *)malloc((size_t)160 * (nnode + 2) + 256);
+      if (pamlh_placement_scores(p, x, n_pend, pend, split, &l0, sc) || pamlh_place(p, x, n_pend, pend, split, be, bp, bl, lwr)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      printf("placement of %d quer%s on %d branches (one engine call): lnL of the tree = %.6f, split %.4f\n", nq, nq == 1 ? "y" : "ies", nb, l0, split);
+      for (q = 0; q < nq; q++) {
+         printf("\nquery %d (%s)\n%10s %10s %16s %14s %9s\n", q + 1, pamlh_query_name(p, q), "branch", "pendant", "lnL", "difference", "LWR");
+         for (e = 0; e < nb; e++) {
+            const double *row = sc + ((size_t)q * nb + e) * n_pend;
+            char br[32];
+            int mj = 0;
+            for (j = 1; j < n_pend; j++) if (row[j] > row[mj]) mj = j;
+            snprintf(br, sizeof(br), "%d..%d", father[order[e]] + 1, order[e] + 1);
+            printf("%10s %10.6f %16.6f %14.6f %9.6f%s\n", br, pend[mj], row[mj], row[mj] - l0, lwr[(size_t)q * nb + e], e == be[q] ? " *" : "");
+         }
+         if (pamlh_placement_newick(p, q, be[q], split, bp[q], nw, 160 * (nnode + 2) + 256)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+         printf("%s\n", nw);
+      }
+      free(father); free(sc); free(lwr); free(be); free(bp); free(bl); free(nw);
       pamlh_free(p);
       return 0;
    }

@@ -265,6 +265,7 @@ static void aa_as_codon_sets(pamlh *p)
    size_t h;
    for (c = 0; c < 64; c++) if (p->code[c] != '*') from61[n++] = c;
    for (h = 0; h < (size_t)p->ns * p->npatt; h++) p->z[h] = (unsigned char)(n + (p->z[h] < 20 ? p->z[h] : 20));
+   for (h = 0; h < (size_t)p->n_query * p->npatt; h++) p->query_z[h] = (unsigned char)(n + (p->query_z[h] < 20 ? p->query_z[h] : 20));      /* (placement: the queries alike) */
    free(p->n_chara); free(p->chara_map);
    p->n_codes = n + 21;
    p->n_chara = (int *)calloc(p->n_codes, sizeof(int));
@@ -295,6 +296,12 @@ int pamlh_load_tree(pamlh **out, const char *ctl_path, const char *program, int 
  * file that lists several site models ("NSsites = 0 1 2 7 8": the reference runs them one after the other, the insmodel loop codeml.c:657-906) is run here one
  * model per analysis: overrides = "NSsites = 2". */
 int pamlh_load_with(pamlh **out, const char *ctl_path, const char *program, int tree_index, const char *overrides, char *err, int errcap)
+{
+   return pamlh_load_impl(out, ctl_path, program, tree_index, overrides, 0, err, errcap);
+}
+
+/* ... `placement`: the tree may name only some of the sequences; the others become the queries (pamlh_load_placement, pamlh_place.c) */
+int pamlh_load_impl(pamlh **out, const char *ctl_path, const char *program, int tree_index, const char *overrides, int placement, char *err, int errcap)
 {
    pamlh *p = (pamlh *)calloc(1, sizeof(pamlh));
    const char *v, *slash;
@@ -462,6 +469,7 @@ int pamlh_load_with(pamlh **out, const char *ctl_path, const char *program, int 
       if (p->model > UNREST) { rc = pamlh_fail(p, "baseml model %d is not supported", p->model); goto bad; }
    }
    else { rc = pamlh_fail(p, "seqtype %d is not supported", p->seqtype); goto bad; }
+   if (placement && p->pairwise) { rc = pamlh_fail(p, "pamlh_load_placement: runmode = -2 has no tree to place sequences on"); goto bad; }
    if (p->pairwise) {
       /* what PairwiseCodon covers here: one kappa, one omega, codon frequencies from the pair's counts (CodonFreq 0-3) */
       if (p->nssites || p->m2a_rel) { rc = pamlh_fail(p, "runmode = -2: NSsites = %d does not apply to pairwise comparisons (use NSsites = 0)", p->m2a_rel ? 22 : p->nssites); goto bad; }
@@ -481,6 +489,7 @@ int pamlh_load_with(pamlh **out, const char *ctl_path, const char *program, int 
       goto allocate;
    }
    if ((rc = pamlh_read_seqs(p))) goto bad;
+   if (placement && (rc = pamlh_split_queries(p))) goto bad;
    if ((rc = pamlh_read_tree(p))) goto bad;
    if (p->nhomo == 1 && (p->ngene > 1 || p->model < F81 || p->model > REV)) { rc = pamlh_fail(p, "nhomo = 1 needs one gene and a model with base frequencies (F81 ... REV)"); goto bad; }
    if (p->nhomo >= 2) {
@@ -670,6 +679,8 @@ void pamlh_free(pamlh *p)
    if (!p) return;
    if (p->eng) paml_amd_destroy(p->eng);
    if (p->names) for (i = 0; i < p->ns; i++) free(p->names[i]);
+   if (p->query_names) for (i = 0; i < p->n_query; i++) free(p->query_names[i]);
+   free(p->query_names); free(p->query_z); free(p->file_row);
    free(p->names); free(p->z); free(p->w); free(p->raw); free(p->n_chara); free(p->chara_map);
    free(p->rate_label); free(p->nh_label); free(p->tip_age); free(p->age_low);
    free(p->sons_ptr); free(p->sons); free(p->label); free(p->branch_node); free(p->father); free(p->tree_branch); free(p->scale);
@@ -1819,6 +1830,7 @@ int pamlh_gene_subset(const pamlh *p, int g, pamlh **out)
    q = (pamlh *)malloc(sizeof(pamlh));
    *q = *p;
    q->eng = NULL; q->err[0] = 0; q->gene_eigen_of = NULL;
+   q->n_query = q->ns_file = 0; q->query_names = NULL; q->query_z = NULL; q->file_row = NULL;      /* (the queries of a placement load stay with p) */
    q->ngene = 1; q->mgene = 0; q->npatt = np1; q->posG[0] = 0; q->posG[1] = np1;
    q->names = (char **)calloc(p->ns, sizeof(char *));
    for (i = 0; i < p->ns; i++) { q->names[i] = (char *)malloc(strlen(p->names[i]) + 1); strcpy(q->names[i], p->names[i]); }

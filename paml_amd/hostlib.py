@@ -20,7 +20,7 @@ DRIVER_PATH = os.path.join(_HERE, "lib", "pamlh_lnl")
 def build(force=False):
     from . import engine
     engine.build()
-    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
+    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_place.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "pamlh.h"))
     if force or not (os.path.exists(LIB_PATH) and os.path.exists(DRIVER_PATH)) or \
             any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
@@ -115,17 +115,21 @@ def tree_comparison_from_replicates(lnf, w, rep):
 
 
 class Analysis:
-    def __init__(self, ctl_path, program="codeml", tree_index=0, overrides=None):
+    def __init__(self, ctl_path, program="codeml", tree_index=0, overrides=None, placement=False):
+        """placement=True: pamlh_load_placement — the tree may name only some of the sequences, the others are the queries."""
         L = lib()
         h = C.c_void_p()
         err = C.create_string_buffer(512)
-        if L.pamlh_load_with(C.byref(h), os.fsencode(ctl_path), program.encode(), tree_index, overrides.encode() if overrides else None, err, 512) != 0:
+        L.pamlh_load_placement.argtypes = L.pamlh_load_with.argtypes
+        if (L.pamlh_load_placement if placement else L.pamlh_load_with)(C.byref(h), os.fsencode(ctl_path), program.encode(), tree_index, overrides.encode() if overrides else None, err, 512) != 0:
             raise RuntimeError("pamlh_load: " + err.value.decode())
         self._h, self._L = h, L
         d = [C.c_int() for _ in range(10)]
         L.pamlh_dims(h, *[C.byref(v) for v in d])
         (self.n, self.n_tips, self.n_patt, self.n_nodes, self.root, self.n_codes, self.cleandata, self.ls, self.np,
          self.ntime) = [v.value for v in d]
+        L.pamlh_n_queries.argtypes = [C.c_void_p]
+        self.n_queries = int(L.pamlh_n_queries(h))
 
     def is_pairwise(self):
         return bool(self._L.pamlh_is_pairwise(self._h))
@@ -381,6 +385,56 @@ class Analysis:
         self._L.pamlh_newick.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         newick = buf.value.decode() if self._L.pamlh_newick(self._h, buf, len(buf)) == 0 else None
         return dict(x=x, lnL=lnl.value, moves=stats[0], screening_calls=stats[1], optimisations=stats[2], newick=newick)
+
+    def query_names(self):
+        """The names of the sequences the tree leaves out (pamlh_load_placement), in file order."""
+        self._L.pamlh_query_name.restype = C.c_char_p
+        self._L.pamlh_query_name.argtypes = [C.c_void_p, C.c_int]
+        return [self._L.pamlh_query_name(self._h, i).decode() for i in range(self.n_queries)]
+
+    def query_codes(self):
+        """The queries' character codes per site pattern, uint8 [n_queries][n_patt] (pamlh_query_codes)."""
+        self._L.pamlh_query_codes.restype = C.c_void_p
+        self._L.pamlh_query_codes.argtypes = [C.c_void_p]
+        if not self.n_queries:
+            return np.zeros((0, self.n_patt), dtype=np.uint8)
+        return _arr(self._L.pamlh_query_codes(self._h), np.uint8, self.n_queries * self.n_patt).reshape(self.n_queries, self.n_patt)
+
+    def placement_scores(self, x, pendant=(0.1,), phi=0.5):
+        """The lnL of the tree at x with a query hung on a branch, for every query, every branch of x's branch-length block
+        (branch_order()) and every pendant length, from one engine call (pamlh_placement_scores): dict(lnL0, edges=[n_branches] (the node
+        below the branch), lnL=[n_queries][n_branches][n_pend])."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        pe = np.ascontiguousarray(np.atleast_1d(pendant), dtype=np.float64)
+        l0, lnl = C.c_double(), np.zeros((max(1, self.n_queries), self.n_nodes - 1, len(pe)))
+        f = self._L.pamlh_placement_scores
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.c_void_p]
+        if len(x) != self.np or f(self._h, x.ctypes.data_as(C.c_void_p), len(pe), pe.ctypes.data_as(C.c_void_p), float(phi), C.byref(l0), lnl.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_placement_scores: " + self._L.pamlh_error(self._h).decode())
+        return dict(lnL0=l0.value, edges=self.branch_order(), lnL=lnl[:self.n_queries])
+
+    def place(self, x, pendant=(0.1,), phi=0.5):
+        """Per query the best (branch, pendant length) of the grid and the likelihood weight ratios of the branches (pamlh_place):
+        dict(best_edge=[n_queries] (index into branch_order()), best_pendant, best_lnL, lwr=[n_queries][n_branches])."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        pe = np.ascontiguousarray(np.atleast_1d(pendant), dtype=np.float64)
+        nq = max(1, self.n_queries)
+        be, bp, bl, lwr = np.zeros(nq, dtype=np.int32), np.zeros(nq), np.zeros(nq), np.zeros((nq, self.n_nodes - 1))
+        f = self._L.pamlh_place
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if len(x) != self.np or f(self._h, x.ctypes.data_as(C.c_void_p), len(pe), pe.ctypes.data_as(C.c_void_p), float(phi), be.ctypes.data_as(C.c_void_p),
+                                  bp.ctypes.data_as(C.c_void_p), bl.ctypes.data_as(C.c_void_p), lwr.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_place: " + self._L.pamlh_error(self._h).decode())
+        nq = self.n_queries
+        return dict(best_edge=be[:nq], best_pendant=bp[:nq], best_lnL=bl[:nq], lwr=lwr[:nq])
+
+    def placement_newick(self, q, edge, phi=0.5, pendant=0.1):
+        """The tree with query q hung on branch `edge` (index into branch_order()), with the lengths of the last x (pamlh_placement_newick)."""
+        buf = C.create_string_buffer(160 * (self.n_nodes + 2) + 256)
+        self._L.pamlh_placement_newick.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_char_p, C.c_int]
+        if self._L.pamlh_placement_newick(self._h, int(q), int(edge), float(phi), float(pendant), buf, len(buf)) != 0:
+            raise RuntimeError("pamlh_placement_newick: " + self._L.pamlh_error(self._h).decode())
+        return buf.value.decode()
 
     def write_bv(self, x, path):
         """The gradient and Hessian of the branch lengths at x in the layout of the reference's rst2 block (pamlh_write_bv)."""

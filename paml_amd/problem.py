@@ -65,6 +65,32 @@ class Tree:
         sons[fa][sons[fa].index(x)] = int(s)
         return Tree(self.n_tips, self.n_nodes, self.root, sons, self.branch, self.label, self.names)
 
+    def insert_tip(self, v, phi, pendant, label=0):
+        """A new Tree with one more tip hung on the branch above v (what paml_amd_placement_scores scores; the reference's AddSpecies,
+        treesub.c:4592).  The new tip is node n_tips, the old internal nodes move up by one, the new internal node u is the last node.
+        u takes v's place in the son list of v's father and its sons are (v, the new tip); the branch above u has length
+        (1 - phi) t_v, the branch above v phi t_v, both with v's label; the new tip's branch has length `pendant` and label `label`."""
+        fa = int(self.father()[v]) if 0 <= v < self.n_nodes else -1
+        if v == self.root or fa < 0:
+            raise ValueError("insert_tip(%d): the root has no branch above it" % v)
+        if not 0 <= phi <= 1:
+            raise ValueError("insert_tip: phi = %r is outside [0, 1]" % (phi,))
+        nt, nn = self.n_tips, self.n_nodes
+        new = lambda i: i if i < nt else i + 1
+        u = nn + 1
+        sons = [[] for _ in range(nn + 2)]
+        branch, lab = np.zeros(nn + 2), np.zeros(nn + 2, dtype=np.int32)
+        for i in range(nn):
+            sons[new(i)] = [new(int(c)) for c in self.sons[i]]
+            branch[new(i)], lab[new(i)] = self.branch[i], self.label[i]
+        sons[new(fa)][sons[new(fa)].index(new(v))] = u
+        sons[u] = [new(v), nt]
+        branch[u], lab[u] = (1 - phi) * self.branch[v], self.label[v]
+        branch[new(v)] = phi * self.branch[v]
+        branch[nt], lab[nt] = pendant, label
+        names = None if self.names is None else list(self.names[:nt]) + ["query"] + list(self.names[nt + 1:])
+        return Tree(nt + 1, nn + 2, new(self.root), sons, branch, lab, names)
+
     def newick(self, names=None, lengths=True):
         names = names or self.names or [str(i + 1) for i in range(self.n_tips)]
 
