@@ -336,6 +336,10 @@ int paml_amd_counters(const paml_amd_engine *e, long *n_eval, long *n_pmat);
  * looked up (in program order, as many as PAML_AMD_CHERRY_CAP_MB = 192 MB of tables hold over all classes); *bytes: the tables' size.
  * Both 0 when the evaluation ran without.  PAML_AMD_CHERRY_TABLES=0 / 1 switches the tables off / on whatever the number of patterns. */
 int paml_amd_cherry_tables(const paml_amd_engine *e, long *n_tabulated, long *bytes);
+/* Subtree tables of the last evaluation (tables of repeated patterns above the cherries): the nodes tabulated (at most `cap` of them
+ * into nodes[] / u[], sons before fathers, with their numbers of classes), the tables' bytes, the operand blocks the per-tree kernel is
+ * left with per tile (-1: it ran without subtree tables), and how often the engine has computed the classes (once per tips + tree). */
+int paml_amd_subtree_tables(const paml_amd_engine *e, long *n_tabulated, int *nodes, long *u, int cap, long *bytes, long *blocks_left, long *n_computed);
 
 /* Host-only introspection (no GPU needed): the flattened post-order program the engine would run for
  * a tree — 4 ints per op (code, a, b, c; paml_amd/csrc/program.h).  Returns the number of ops (or a
@@ -374,6 +378,24 @@ int paml_amd_debug_jit(int n_tips, int n_nodes, int root, const int *sons_ptr, c
 int paml_amd_debug_jit_tables(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node,
                               int max_tabs, char *text_out, int cap, int *stream_out, int stream_cap, int *n_stream, int *tabs_out,
                               int tabs_cap);
+
+/* Host-only: the classes of the subtree tables for a tree and tip codes z[n_tips][n_patt] (< n_codes): u_out[n_nodes] = the number of
+ * distinct columns of the tips below every internal node below the root (0 elsewhere); cls_out (optional) [n_nodes][n_patt] = each
+ * pattern's class there — dense ranks in order of first occurrence, at a cherry ca * n_codes + cb. */
+int paml_amd_debug_subtree_classes(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *z, long n_patt,
+                                   int n_codes, unsigned int *u_out, unsigned int *cls_out);
+
+/* Host-only: the nodes an engine of these sizes (one gene, K classes, the PAML_AMD_SUBTREE_* / PAML_AMD_CHERRY_* switches of the
+ * environment) tabulates above the cherries for tip codes z[n_tips][n_patt], sons before fathers.  Returns their number. */
+int paml_amd_debug_subtree_select(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node, int n_states,
+                                  int n_codes, int K, const unsigned char *z, long n_patt, int *sel_out, int cap);
+
+/* Host-only: the 60..64-state per-tree kernel with subtree tables of the nodes sel[n_sel] (sons before fathers) beside the cherry tables
+ * of an engine with K classes: its source in text_out — compiled for gfx950 when `compile`, the code object kept in `dir` when given —
+ * and the operand blocks left per tile.  Returns the length of the source, 0 where the table form does not apply or a node of sel
+ * cannot be tabulated, or a negative error (PAML_AMD_EHIP: the compiler's log is in text_out). */
+int paml_amd_debug_jit_subtree(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node, int n_states,
+                               int n_codes, int K, const int *sel, int n_sel, int compile, const char *dir, char *text_out, int cap, int *blocks_left);
 
 /* Host-only (hiprtc cross-compiles without a GPU): compile the per-tree kernel an engine of these sizes would select for this tree
  * and keep the code object in `dir` (the library's read-only lib/jit directory, or a user cache), so that the first evaluation on

@@ -88,6 +88,12 @@ struct PruneArgs {
                                              // kernel's codes beyond the 64 a ring block has rows for (JIT_AMB_OVERFLOW)
    const double *ctab;          // per-tree kernel with cherry tables (jit.h: OP_LOOKUP): [class][n_ctab][n_codes * n_codes][64], else null
    int n_ctab;
+   // ... with subtree tables above the cherries (jit.h: OP_LOOKUP with a class index; kernels_pmat.h: subtree_table_kernel): per class
+   // stab_rows rows of 512 bytes, the tables of the tabulated nodes one behind the other; stab_meta[2 t], [2 t + 1]: first row and number of
+   // rows (u_v) of the table of the walk's lookup t.  The per-pattern class indices travel in the tile's code block (JIT2_IDX).
+   const double *stab;
+   long stab_rows;
+   const int *stab_meta;
 };
 
 __device__ __forceinline__ double root_value(const PruneArgs &a, double f, double lnscale)
@@ -549,6 +555,18 @@ __device__ __forceinline__ void jit_lookup_nc(v4d (&y)[4], const double *tab, in
 #define JIT_CTAB(CLS, C) (a.ctab + ((long)(CLS) * a.n_ctab + (C)) * (long)(JIT_NC * JIT_NC * CHERRY_ROW_WORDS))
 __device__ __forceinline__ void jit_lookup(v4d (&y)[4], const double *tab, int ca, int cb, int q) { jit_lookup_nc(y, tab, ca, cb, q, JIT_NC); }
 #endif
+
+// Subtree tables: row `idx` (the pattern's class at the tabulated node, clamped to the table's u rows like the codes above) of a table in
+// the cherry tables' row layout.
+__device__ __forceinline__ void jit_lookup_row(v4d (&y)[4], const double *tab, int idx, int u, int q)
+{
+   idx = idx < u ? idx : u - 1;
+   const part2_t *r = (const part2_t *)(tab + (long)idx * CHERRY_ROW_WORDS) + q;
+#pragma unroll
+   for (int i = 0; i < 8; i++) { const part2_t v = r[i * 4]; y[i >> 1][(2 * i) & 3] = v.x; y[i >> 1][(2 * i + 1) & 3] = v.y; }
+}
+#define JIT_STAB(CLS, T) (a.stab + ((long)(CLS) * a.stab_rows + as_const(a.stab_meta)[2 * (T)]) * CHERRY_ROW_WORDS)
+#define JIT_STAB_U(T) (as_const(a.stab_meta)[2 * (T) + 1])
 
 __device__ __forceinline__ void jit_init_ones(v4d (&y)[4], int q, int n)
 {
@@ -1354,5 +1372,8 @@ __device__ __forceinline__ void m20_root(const PruneArgs &a, const double (&x)[5
 #define JIT2_PIECE_NT(J, NODE, C) JIT2_PIECE(nPtip + (long)(NODE)*JIT_TIPW, J, C, JIT2_REAL_T)
 #define JIT2_CODE(ZP, TIP) ((int)sZ[zsel * ((ZP)*2048) + (TIP)*JIT_TP + hw])
 #define JIT2_NCODE(ZP, TIP) ((int)sZ[((zsel ^ 1) & (JIT_ZB - 1)) * ((ZP)*2048) + (TIP)*JIT_TP + hw])
+/* a pattern's class index at a tabulated node (subtree tables): three byte rows of the tile's code block behind the weight flags, low byte first */
+#define JIT2_IDX(ZP, ROW) (JIT2_CODE(ZP, ROW) | (JIT2_CODE(ZP, (ROW) + 1) << 8) | (JIT2_CODE(ZP, (ROW) + 2) << 16))
+#define JIT2_NIDX(ZP, ROW) (JIT2_NCODE(ZP, ROW) | (JIT2_NCODE(ZP, (ROW) + 1) << 8) | (JIT2_NCODE(ZP, (ROW) + 2) << 16))
 
 }  // namespace paml_amd

@@ -320,6 +320,7 @@ int eig_refill_jit(paml_amd_engine *e, const BranchEval &c, const EigForm &f, bo
    if (!have) return 0;
    e->kernel = PK_MFMA64_JIT;      // (kernel_name: the last pruning kernel was a per-tree one)
    e->last_ctab_n = e->last_ctab_bytes = 0;      // (... without cherry tables)
+   e->last_stab_n = e->last_stab_bytes = 0; e->last_stab_blocks = -1;
    if (int rc = select_tiles(e, true, 8, true)) return rc;
    const int n_blocks = e->n_tiles * K;
    int overflow = 0;

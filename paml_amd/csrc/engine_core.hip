@@ -212,6 +212,10 @@ int paml_amd_set_tips(paml_amd_engine *e, const unsigned char *z, int cleandata,
    for (int g = 0; g < e->n_genes; g++)
       if (e->gene_off[g + 1] < e->gene_off[g]) return fail(e, PAML_AMD_EINVAL, "set_tips: gene_off must not decrease");      // (a pattern shard may hold nothing of a gene)
    HIPCHK(upload(e->d_z, z, nz, e->stream));
+   // (the subtree tables' classes are computed from the codes, lazily: engine_eval.hip — by the only engines that take such tables)
+   if (e->kk == KK_MFMA64 && e->n_genes == 1 && n_codes <= 64) e->h_z.assign(z, z + nz);
+   else std::vector<unsigned char>().swap(e->h_z);
+   e->tips_gen++;
    HIPCHK(upload(e->d_weights, weights, (size_t)e->n_patt, e->stream));
    HIPCHK(upload(e->d_n_chara, nch.data(), nch.size(), e->stream));
    HIPCHK(upload(e->d_chara_map, cmap.data(), cmap.size(), e->stream));
@@ -273,6 +277,7 @@ int paml_amd_set_tree(paml_amd_engine *e, int n_nodes, int root, const int *sons
    std::vector<unsigned char> leaf(n_nodes);
    for (int i = 0; i < n_nodes; i++) leaf[i] = t.is_leaf(i) ? 1 : 0;
    e->tree = std::move(t);
+   e->tree_gen++;
    HIPCHK(upload(e->d_label, e->tree.label.data(), e->tree.label.size(), e->stream));
    HIPCHK(upload(e->d_is_leaf, leaf.data(), leaf.size(), e->stream));
    HIPCHK(hipStreamSynchronize(e->stream));
@@ -771,6 +776,20 @@ int paml_amd_cherry_tables(const paml_amd_engine *e, long *n_tabulated, long *by
    if (!e) return PAML_AMD_EINVAL;
    if (n_tabulated) *n_tabulated = e->last_ctab_n;
    if (bytes) *bytes = e->last_ctab_bytes;
+   return 0;
+}
+
+int paml_amd_subtree_tables(const paml_amd_engine *e, long *n_tabulated, int *nodes, long *u, int cap, long *bytes, long *blocks_left, long *n_computed)
+{
+   if (!e) return PAML_AMD_EINVAL;
+   if (n_tabulated) *n_tabulated = e->last_stab_n;
+   for (long i = 0; i < e->last_stab_n && i < cap && i < (long)e->sub.sel.size(); i++) {
+      if (nodes) nodes[i] = e->sub.sel[i];
+      if (u) u[i] = (long)e->sub.u[e->sub.sel[i]];
+   }
+   if (bytes) *bytes = e->last_stab_bytes;
+   if (blocks_left) *blocks_left = e->last_stab_blocks;
+   if (n_computed) *n_computed = e->sub.n_computed;
    return 0;
 }
 

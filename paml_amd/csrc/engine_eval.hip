@@ -351,6 +351,108 @@ int stage_inputs(paml_amd_engine *e, Eval &c, InlineVec &iv)
    return 0;
 }
 
+// Subtree tables (jit.h: SubtreeProgram): the classes of the tips + tree, the selection for this class count and these limits and what
+// the builder and the walk read of it on the device — all of it only when one of them changed (Subtree::made_for: a handful of integers
+// compared per evaluation), the classes only after set_tips / set_tree.  e->sub.sel is empty when nothing qualifies.
+static std::string ckey_of(const paml_amd_engine *e, int K, int n, const std::string &pkey)
+{
+   return std::to_string(K) + "k" + std::to_string(n) + "m" + std::to_string(e->n_codes) + "c" + std::to_string(e->env.cherry_cap_mb) + ":" + pkey;
+}
+int ensure_subtree(paml_amd_engine *e, int K, int tp)
+{
+   paml_amd_engine::Subtree &sb = e->sub;
+   // (cherry_gen: the cherry tables' own key — tree, class count, codes, their cap — changed)
+   const paml_amd_engine::Subtree::Key key{e->tips_gen, e->tree_gen, e->cherry_gen, e->env.subtree_cap_mb, e->env.subtree_max_frac, K};
+   if (sb.made_for == key) return 0;
+   if (sb.d_nodes.p) HIPCHK(hipDeviceSynchronize());      // (a new selection: nothing may still read the previous one's tables and indices)
+   const bool same_classes = sb.made_for.tips_gen == key.tips_gen && sb.made_for.tree_gen == key.tree_gen && sb.made_for.frac == key.frac;
+   sb.made_for = key;
+   sb.sel_gen++;
+   const TreeDesc &t = e->tree;
+   if (e->h_z.size() != (size_t)e->n_tips * e->n_patt) {      // (set_tips keeps the codes for the engines this form applies to)
+      sb.sel.clear();
+      sb.sp = SubtreeProgram();
+      sb.made_for.tips_gen = -1;
+      return 0;
+   }
+   if (!same_classes) {      // (the limit is part of the key: classes beyond it are not computed)
+      const double lim_u = e->env.subtree_max_frac * (double)e->n_patt;
+      SubtreeClasses sc = subtree_classes(e->n_tips, t.n_nodes, t.root, t.sons_ptr.data(), t.sons.data(), e->h_z.data(), (long)e->n_patt, (long)e->n_patt,
+                                          e->n_codes, lim_u >= 4e9 ? ~0ull : (uint64_t)std::max(0.0, lim_u));
+      sb.u.swap(sc.u); sb.done.swap(sc.done); sb.cls.swap(sc.cls); sb.son_cls.swap(sc.son_cls);
+      for (int v = 0; v < t.n_nodes; v++)      // (a cherry's classes are ca * n_codes + cb: nothing reads the array again — 8 of the headline's 13)
+         if (sc.cherry[v]) std::vector<unsigned int>().swap(sb.cls[v]);
+      sb.n_computed++;
+   }
+   sb.sel = jit_subtree_select(t, e->cherry.tabs, sb.u, sb.done, e->n_patt, e->env.subtree_max_frac, (size_t)e->env.subtree_cap_mb << 20, K);
+   sb.sp = SubtreeProgram();
+   sb.rows = 0;
+   for (int v : sb.sel)      // (what the builder reads per class: two son rows)
+      if (sb.son_cls[v].size() != 2 * (size_t)sb.u[v]) { sb.sel.clear(); break; }
+   if (sb.sel.empty()) return 0;
+   sb.sp = jit_subtree_program(e->prog, e->cherry_n, t, sb.sel);
+   if (sb.sp.top.empty() || !jit_subtree_zfits(e->n_tips, (int)sb.sp.top.size(), tp)) {      // (the index rows must leave room for two code blocks)
+      sb.sel.clear();
+      sb.sp = SubtreeProgram();
+      return 0;
+   }
+   // the builder's nodes, level by level (sel keeps the order of the report: ascending u), and their classes' rows at the sons
+   const int ns = (int)sb.sp.sub.size();
+   std::vector<int> row0(ns), by_level;
+   for (int i = 0; i < ns; i++) { row0[i] = (int)sb.rows; sb.rows += sb.u[sb.sp.sub[i].node]; }
+   sb.level_first.clear();
+   sb.level_tiles.clear();
+   for (int l = 0; l < sb.sp.levels; l++) {
+      sb.level_first.push_back((int)by_level.size());
+      int tiles = 0;
+      for (int i = 0; i < ns; i++)
+         if (sb.sp.sub[i].level == l) { by_level.push_back(i); tiles = std::max(tiles, (int)((sb.u[sb.sp.sub[i].node] + 127) / 128)); }
+      sb.level_tiles.push_back(tiles);
+   }
+   sb.level_first.push_back((int)by_level.size());
+   std::vector<SubtreeNodeDev> nodes(ns);
+   std::vector<unsigned int> sidx;
+   for (int k = 0; k < ns; k++) {
+      const SubtreeTab &st = sb.sp.sub[by_level[k]];
+      SubtreeNodeDev &nd = nodes[k];
+      nd.node = st.node; nd.u = (int)sb.u[st.node]; nd.row0 = row0[by_level[k]];
+      nd.lkind = st.l.kind; nd.lid = st.l.kind == 2 ? row0[st.l.id] : st.l.id;
+      nd.rkind = st.r.kind; nd.rid = st.r.kind == 2 ? row0[st.r.id] : st.r.id;
+      nd.pad = 0;
+      nd.sidx = (long)sidx.size();
+      sidx.insert(sidx.end(), sb.son_cls[st.node].begin(), sb.son_cls[st.node].end());      // [2][u]
+   }
+   std::vector<int> meta;
+   for (int ti : sb.sp.top) { meta.push_back(row0[ti]); meta.push_back((int)sb.u[sb.sp.sub[ti].node]); }
+   HIPCHK(upload(sb.d_nodes, nodes.data(), nodes.size(), e->stream));
+   HIPCHK(upload(sb.d_sidx, sidx.data(), sidx.size(), e->stream));
+   HIPCHK(upload(sb.d_meta, meta.data(), meta.size(), e->stream));
+   HIPCHK(hipStreamSynchronize(e->stream));
+   return 0;
+}
+
+// The tile blocks of the kernel with subtree tables: the current 128-pattern tile table's, with the class-index rows of the walk's lookups.
+int ensure_subtree_ztiles(paml_amd_engine *e)
+{
+   paml_amd_engine::Subtree &sb = e->sub;
+   if (sb.zt_sel_gen == sb.sel_gen && sb.zt_tiles == e->n_tiles && sb.zt_tile_patt == e->tile_patt) return 0;
+   const int n_top = (int)sb.sp.top.size();
+   std::vector<unsigned int> top((size_t)n_top * e->n_patt);
+   for (int k = 0; k < n_top; k++) {
+      const std::vector<unsigned int> &c = sb.cls[sb.sp.sub[sb.sp.top[k]].node];
+      std::copy(c.begin(), c.end(), top.begin() + (size_t)k * e->n_patt);
+   }
+   sb.zt_bytes = jit_zpieces(jit_subtree_zrows(e->n_tips, n_top), e->tile_patt) * 2048;
+   HIPCHK(upload(sb.d_top_cls, top.data(), top.size(), e->stream));
+   HIPCHK(sb.d_ztiles.ensure((size_t)e->n_tiles * sb.zt_bytes));
+   hipLaunchKernelGGL(sztile_kernel, dim3(e->n_tiles), dim3(e->tile_patt), 0, e->stream, e->d_tiles.p, e->d_gene_off.p, e->d_z.p, (long)e->n_patt, e->d_weights.p,
+                      e->n_tips, sb.zt_bytes, sb.d_ztiles.p, n_top, sb.d_top_cls.p);
+   HIPCHK(hipStreamSynchronize(e->stream));
+   sb.d_top_cls.release();
+   sb.zt_sel_gen = sb.sel_gen; sb.zt_tiles = e->n_tiles; sb.zt_tile_patt = e->tile_patt;
+   return 0;
+}
+
 // The pruning kernel of this evaluation: every obtain_kernel call of an evaluation and the tile tables.  Nonzero (*out untouched) only
 // under PAML_AMD_JIT_STRICT or when the tile tables cannot be built.  21..64 states:
 //   jit    — straight-line kernel specialised for this tree (jit.h), 128 patterns per workgroup
@@ -381,6 +483,7 @@ int choose_kernel(paml_amd_engine *e, const Eval &c, PruneKernel *out)
       bool has_load = false;
       for (const Op &o : e->prog.ops) has_load = has_load || o.code == OP_LOAD;
       e->n_ctab = 0;
+      e->n_stab = 0;
       if (e->jit_enabled && !(has_load && e->n_tips > 207) && (e->n_codes <= 64 || (e->amb_ascending && e->plain_codes >= n)) && jit_supported(e->prog, e->n_tips, e->n_codes, e->n_pi, 6, jw * 16, true)) {
          const std::string pkey = jit_program_key(e->prog, e->n_tips);
          std::string key = "m" + std::to_string(n) + "c" + std::to_string(e->n_codes) + "w" + std::to_string(jw) + ":" + pkey;
@@ -389,15 +492,30 @@ int choose_kernel(paml_amd_engine *e, const Eval &c, PruneKernel *out)
          int n_tab = 0;
          if (e->env.cherry_tables != 0 && G == 1 && e->n_pi == 1 && c.B == 1 && !c.keep && !c.clean && !has_load &&
              (e->env.cherry_tables == 1 || e->n_patt >= e->env.cherry_min_patt)) {
-            const std::string ckey = std::to_string(c.K) + "k" + std::to_string(n) + "m" + std::to_string(e->n_codes) + "c" + std::to_string(e->env.cherry_cap_mb) + ":" + pkey;
+            const std::string ckey = ckey_of(e, c.K, n, pkey);
             if (e->cherry_key != ckey) {      // (a new tree, class count or code table: the count and the table form once)
                e->cherry_n = jit_cherry_count(e->prog, e->n_tips, n, e->n_codes, c.K, (size_t)e->env.cherry_cap_mb << 20, jw * 16);
                e->cherry = e->cherry_n ? jit_cherry_program(e->prog, e->cherry_n) : CherryProgram();
                e->cherry_key = ckey;
+               e->cherry_gen++;
             }
             n_tab = e->cherry_n;
          }
-         if (n_tab) {
+         // Subtree tables above them (jit.h: SubtreeProgram): wherever cherry tables run, unless PAML_AMD_SUBTREE_TABLES=0
+         if (n_tab && e->env.subtree_tables != 0) {
+            if (int r = ensure_subtree(e, c.K, jw * 16)) return r;
+            if (!e->sub.sel.empty()) {
+               std::string skey = "s";
+               for (int v : e->sub.sel) skey += std::to_string(v) + ".";
+               skey += "t" + std::to_string(n_tab) + key;
+               bool ok = false;
+               const int n_top = (int)e->sub.sp.top.size();
+               if (int r = obtain_kernel(e, e->jit_slot, &e->jit, true, skey, [&]() { return jit_generate(e->sub.sp.prog, e->n_tips, n, e->n_codes, &e->sub.sp.tabs, n_top); },
+                                         (e->prog.ops.size() > 120 && !e->jit_forced && !e->env.jit_sync) ? JIT_WAIT_WORKER : JIT_WAIT_CALLER, "tree, subtree tables", &ok)) return r;
+               if (ok) { jit_ok = true; e->n_ctab = n_tab; e->n_stab = (int)e->sub.sel.size(); }
+            }
+         }
+         if (n_tab && !jit_ok) {
             const std::string tkey = "t" + std::to_string(n_tab) + key;
             bool ok = false;
             if (int r = obtain_kernel(e, e->jit_slot, &e->jit, true, tkey, [&]() { return jit_generate(e->cherry.prog, e->n_tips, n, e->n_codes, &e->cherry.tabs); },
@@ -420,6 +538,8 @@ int choose_kernel(paml_amd_engine *e, const Eval &c, PruneKernel *out)
       const bool big_tiles = jit_ok || lean;
       const int want_waves = jit_ok ? jw : (lean ? DMA_WAVES : GATHER_WAVES);
       if (int r = select_tiles(e, big_tiles, want_waves, jit_ok)) return r;
+      if (e->n_stab)
+         if (int r = ensure_subtree_ztiles(e)) return r;
       if (jit_ok || e->mfma_dma) {
          *out = jit_ok ? PK_MFMA64_JIT : PK_MFMA64_STREAM;
          return 0;
@@ -488,11 +608,16 @@ int ensure_buffers(paml_amd_engine *e, Eval &c)
       paml_amd_engine::PSet &sp = e->spare[e->spare_head];      // the set used longest ago
       std::swap(e->d_rowmajor, sp.rowmajor); std::swap(e->d_pint, sp.pint); std::swap(e->d_ptip, sp.ptip); std::swap(e->d_pcol, sp.pcol);
       std::swap(e->d_ctab, sp.ctab);
+      std::swap(e->d_stab, sp.stab);
       std::swap(e->pset, sp.id);
       e->spare_head = (e->spare_head + 1) % (paml_amd_engine::NPSET - 1);
    }
    if (int rc = ensure_pmat_buffers(e, c.psets, e->kk == KK_VALU20 && e->want_m20, e->kk == KK_MFMA64)) return rc;
-   if (e->kernel != PK_MFMA64_JIT) e->n_ctab = 0;
+   if (e->kernel != PK_MFMA64_JIT) e->n_ctab = e->n_stab = 0;
+   e->last_stab_n = e->n_stab;
+   e->last_stab_bytes = e->n_stab ? (long)((size_t)c.K * e->sub.rows * CHERRY_ROW_BYTES) : 0;
+   e->last_stab_blocks = e->n_stab ? (long)(e->sub.sp.prog.stream.size() / 2) : -1;
+   if (e->n_stab) HIPCHK(e->d_stab.ensure((size_t)e->last_stab_bytes / sizeof(double)));
    e->last_ctab_n = e->n_ctab;
    e->last_ctab_bytes = (long)((size_t)c.K * e->n_ctab * cherry_table_bytes(e->n_codes));
    if (e->n_ctab) HIPCHK(e->d_ctab.ensure((size_t)e->last_ctab_bytes / sizeof(double)));
@@ -567,6 +692,27 @@ int run_pmat(paml_amd_engine *e, Eval &c, const InlineVec &iv)
       if (e->n == 61) hipLaunchKernelGGL(cherry_table_kernel<true>, g, dim3(512), lds, c.ps, ca);
       else if (e->n == 60) hipLaunchKernelGGL((cherry_table_kernel<false, 15>), g, dim3(512), lds, c.ps, ca);      // (jit_cherry_count: 60 .. 64 states)
       else hipLaunchKernelGGL(cherry_table_kernel<false>, g, dim3(512), lds, c.ps, ca);
+   }
+   if (e->n_stab) {      // the subtree tables: level by level behind the cherry builder (a level reads the cherry tables and the levels before)
+      const paml_amd_engine::Subtree &sb = e->sub;
+      SubtreeTabArgs sa{};
+      sa.n_codes = e->n_codes; sa.n_nodes = nn; sa.n_ctab = e->n_ctab; sa.tip_words = (long)tip_words(e); sa.stab_rows = sb.rows;
+      sa.pint = e->d_pint.p; sa.ptip = e->d_ptip.p; sa.pcol = e->d_pcol.p; sa.ctab = e->d_ctab.p;
+      sa.nodes = sb.d_nodes.p; sa.sidx = sb.d_sidx.p; sa.stab = e->d_stab.p;
+      const size_t lds = (size_t)(3 * 4096 + 64) * sizeof(double);
+      if (!e->stab_attr_set) {
+         HIPCHK(hipFuncSetAttribute((const void *)subtree_table_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+         HIPCHK(hipFuncSetAttribute((const void *)subtree_table_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+         HIPCHK(hipFuncSetAttribute((const void *)subtree_table_kernel<false, 15>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+         e->stab_attr_set = true;
+      }
+      for (int l = 0; l < sb.sp.levels; l++) {
+         sa.first = sb.level_first[l];
+         const dim3 g(sb.level_tiles[l], sb.level_first[l + 1] - sb.level_first[l], c.K);
+         if (e->n == 61) hipLaunchKernelGGL(subtree_table_kernel<true>, g, dim3(512), lds, c.ps, sa);
+         else if (e->n == 60) hipLaunchKernelGGL((subtree_table_kernel<false, 15>), g, dim3(512), lds, c.ps, sa);
+         else hipLaunchKernelGGL(subtree_table_kernel<false>, g, dim3(512), lds, c.ps, sa);
+      }
    }
    mark_on(e, c.ps);
    if (c.pipe) {      // the pruning kernel (main stream) starts when this P(t) is there
@@ -656,6 +802,10 @@ int run_prune(paml_amd_engine *e, Eval &c)
    if (k == PK_MFMA4X20_JIT) { pr.pint = e->d_pint.p; pr.pcol = e->d_rowmajor.p; }      // (operand-order P(t); the row-major copies for the all-4x4x4 experiment)
    pr.fhK = e->fhk_slot(e->last_fhk).p;
    if (k == PK_MFMA64_JIT && e->n_ctab) { pr.ctab = e->d_ctab.p; pr.n_ctab = e->n_ctab; }      // (this P set's cherry tables)
+   if (k == PK_MFMA64_JIT && e->n_stab) {      // (... its subtree tables, and the tile blocks with the class-index rows)
+      pr.stab = e->d_stab.p; pr.stab_rows = e->sub.rows; pr.stab_meta = e->sub.d_meta.p;
+      pr.ztiles = e->sub.d_ztiles.p; pr.zt_bytes = e->sub.zt_bytes;
+   }
    const int nb = (e->n_patt + e->chunk - 1) / e->chunk;      // the reduction's geometry: chunks of this engine
    if (pk_forms_reduction(k)) {      // (the others leave the partial sums to reduce_stage1)
       pr.Km = c.Km; pr.chunk = e->chunk; pr.first_chunk = e->first_chunk; pr.nb_stride = e->nb_global;

@@ -177,6 +177,94 @@ int paml_amd_debug_jit_tables(int n_tips, int n_nodes, int root, const int *sons
    return n_tab;
 }
 
+// The classes of subtree_classes.h for a tree and tip codes z[n_tips][n_patt], without an engine: u_out[n_nodes] (0: tips, the root),
+// cls_out[n_nodes][n_patt] (optional; rows of nodes without classes are left alone).
+int paml_amd_debug_subtree_classes(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *z, long n_patt,
+                                   int n_codes, unsigned int *u_out, unsigned int *cls_out)
+{
+   TreeDesc t;
+   if (!z || n_patt < 1 || n_codes < 1 || !tree_from_csr(n_tips, n_nodes, root, sons_ptr, sons, nullptr, &t)) return PAML_AMD_EINVAL;
+   for (long i = 0; i < (long)n_tips * n_patt; i++)
+      if (z[i] >= n_codes) return PAML_AMD_EINVAL;
+   const SubtreeClasses sc = subtree_classes(n_tips, n_nodes, root, t.sons_ptr.data(), t.sons.data(), z, n_patt, n_patt, n_codes);
+   for (int v = 0; v < n_nodes; v++) {
+      if (u_out) u_out[v] = sc.u[v];
+      if (cls_out && sc.done[v]) memcpy(cls_out + (long)v * n_patt, sc.cls[v].data(), (size_t)n_patt * sizeof(unsigned int));
+   }
+   return 0;
+}
+
+// The nodes an engine of these sizes (one gene, K classes, the switches of the environment) tabulates above the cherries for tip codes
+// z[n_tips][n_patt]: the classes, then jit_subtree_select with the engine's limits.  Returns their number (sel_out: the first `cap`).
+int paml_amd_debug_subtree_select(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node, int n_states,
+                                  int n_codes, int K, const unsigned char *z, long n_patt, int *sel_out, int cap)
+{
+   TreeDesc t;
+   if (!z || n_patt < 1 || !tree_from_csr(n_tips, n_nodes, root, sons_ptr, sons, scale_node, &t)) return PAML_AMD_EINVAL;
+   const Program p = build_program(t, false, nullptr);
+   if (!jit_supported(p, n_tips, n_codes)) return 0;
+   EnvCfg env;
+   env.read();
+   const int n_tab = env.subtree_tables != 0 ? jit_cherry_count(p, n_tips, n_states, n_codes, K, (size_t)env.cherry_cap_mb << 20) : 0;
+   if (!n_tab) return 0;
+   const CherryProgram cp = jit_cherry_program(p, n_tab);
+   const double lim_u = env.subtree_max_frac * (double)n_patt;
+   const SubtreeClasses sc = subtree_classes(n_tips, n_nodes, root, t.sons_ptr.data(), t.sons.data(), z, n_patt, n_patt, n_codes,
+                                             lim_u >= 4e9 ? ~0ull : (uint64_t)std::max(0.0, lim_u));
+   const std::vector<int> sel = jit_subtree_select(t, cp.tabs, sc.u, sc.done, n_patt, env.subtree_max_frac, (size_t)env.subtree_cap_mb << 20, K);
+   for (int i = 0; i < (int)sel.size() && i < cap; i++)
+      if (sel_out) sel_out[i] = sel[i];
+   return (int)sel.size();
+}
+
+// The per-tree 60..64-state kernel with the subtree tables of the nodes sel[n_sel] (sons before fathers: the engine's selection order; the
+// source depends on the node set, not on the data) beside the cherry tables an engine with K classes builds: its source, compiled for
+// gfx950 when `compile` (into `dir` when given: the library's lib/jit at build time).  *blocks_left: operand blocks left per tile.
+// Returns the length of the source; 0 when the table form does not apply to the tree or a node of sel cannot be tabulated.
+int paml_amd_debug_jit_subtree(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node, int n_states,
+                               int n_codes, int K, const int *sel, int n_sel, int compile, const char *dir, char *text_out, int cap, int *blocks_left)
+{
+   TreeDesc t;
+   if (!sel || n_sel < 1 || !tree_from_csr(n_tips, n_nodes, root, sons_ptr, sons, scale_node, &t)) return PAML_AMD_EINVAL;
+   const Program p = build_program(t, false, nullptr);
+   if (!jit_supported(p, n_tips, n_codes)) return PAML_AMD_EUNSUPPORTED;
+   EnvCfg env;
+   env.read();
+   const int n_tab = jit_cherry_count(p, n_tips, n_states, n_codes, K, (size_t)env.cherry_cap_mb << 20);
+   if (text_out && cap > 0) text_out[0] = 0;
+   if (!n_tab) return 0;
+   // the rules of jit_subtree_select without the data: every node of sel within limits
+   const CherryProgram cp = jit_cherry_program(p, n_tab);
+   std::vector<unsigned int> u(n_nodes, 0);
+   std::vector<char> done(n_nodes, 0);
+   for (int i = 0; i < n_sel; i++) {
+      if (sel[i] < n_tips || sel[i] >= n_nodes) return PAML_AMD_EINVAL;
+      u[sel[i]] = 1 + i;
+      done[sel[i]] = 1;
+   }
+   const std::vector<int> ok = jit_subtree_select(t, cp.tabs, u, done, 1L << 30, 1.0, ~(size_t)0 >> 8, 1);
+   if ((int)ok.size() != n_sel) return 0;
+   const SubtreeProgram sp = jit_subtree_program(p, n_tab, t, ok);
+   if (sp.top.empty() || !jit_subtree_zfits(n_tips, (int)sp.top.size())) return 0;
+   if (blocks_left) *blocks_left = (int)sp.prog.stream.size() / 2;
+   std::string text = jit_generate(sp.prog, n_tips, n_states, n_codes, &sp.tabs, (int)sp.top.size());
+   int rc = (int)text.size();
+   if (compile) {
+      std::vector<char> code;
+      std::string log;
+      if (jit_compile_code(text, &code, &log, (dir && *dir) ? dir : nullptr) != 0) {
+         text = log;
+         rc = PAML_AMD_EHIP;
+      }
+   }
+   if (text_out && cap > 0) {
+      const size_t ncp = std::min((size_t)cap - 1, text.size());
+      memcpy(text_out, text.data(), ncp);
+      text_out[ncp] = 0;
+   }
+   return rc;
+}
+
 int paml_amd_jit_prebuild(int n_states, int n_tips, int n_codes, int K, long n_patt_global, int n_nodes, int root, const int *sons_ptr,
                           const int *sons, const unsigned char *scale_node, const char *dir, char *log_out, int log_cap)
 {

@@ -46,6 +46,7 @@
 #include "kernel_args.h"
 #include "program.h"
 #include "branch_plan.h"
+#include "subtree_classes.h"
 
 namespace paml_amd {
 static_assert(JIT_SCRATCH_BASE == MFMA_RS, "the per-tree kernel addresses the interpreter's overflow-stack scratch");
@@ -206,6 +207,12 @@ struct EnvCfg {
    // choices — patterns of this engine from which the tables pay, and the most table bytes of one evaluation
    int cherry_tables = -1;
    long cherry_min_patt = 32768, cherry_cap_mb = 192;
+   // subtree tables above the cherries (jit.h: SubtreeProgram), wherever cherry tables are on.  PAML_AMD_SUBTREE_TABLES=0 / 1: never / there
+   // (the default); PAML_AMD_SUBTREE_MAX_FRAC: a node is tabulated while its classes are at most this share of the patterns;
+   // PAML_AMD_SUBTREE_CAP_MB: cap on the tables' bytes per P set, all classes of the model together
+   int subtree_tables = -1;
+   double subtree_max_frac = 0.5;
+   long subtree_cap_mb = 2048;
    std::string jit_dump, prof_ops;
    int prof_tid = 0;
    bool prof_tiles = false;      // the dump is a workgroup timeline (jit.h proft) instead of per-op stamps
@@ -226,6 +233,9 @@ struct EnvCfg {
       if (const char *v = getenv("PAML_AMD_CHERRY_TABLES")) cherry_tables = atoi(v) != 0 ? 1 : 0;
       if (const char *v = getenv("PAML_AMD_CHERRY_MIN_PATT")) cherry_min_patt = atol(v);
       if (const char *v = getenv("PAML_AMD_CHERRY_CAP_MB")) cherry_cap_mb = std::max(0L, atol(v));
+      if (const char *v = getenv("PAML_AMD_SUBTREE_TABLES")) subtree_tables = atoi(v) != 0 ? 1 : 0;
+      if (const char *v = getenv("PAML_AMD_SUBTREE_MAX_FRAC")) subtree_max_frac = std::max(0.0, atof(v));
+      if (const char *v = getenv("PAML_AMD_SUBTREE_CAP_MB")) subtree_cap_mb = std::max(0L, atol(v));
       if (const char *v = getenv("PAML_AMD_JIT_DUMP")) jit_dump = v;
       if (const char *v = getenv("PAML_AMD_PROF_OPS")) prof_ops = v;
       if (const char *v = getenv("PAML_AMD_PROF_TID")) prof_tid = atoi(v);
@@ -394,6 +404,41 @@ struct paml_amd_engine {
    int n_ctab = 0;
    bool ctab_attr_set = false;
    long last_ctab_n = 0, last_ctab_bytes = 0;
+   // Subtree tables (jit.h: SubtreeProgram; kernels_pmat.h: subtree_table_kernel).  The classes (subtree_classes.h) are a function of the
+   // tip codes (h_z: the host's copy, kept by set_tips) and the tree: computed on the first evaluation that can use tables and again only
+   // after set_tips / set_tree (tips_gen, tree_gen; n_computed counts), never per evaluation.  `key` = everything the selection depends on.
+   // Device side, uploaded once per selection: the nodes' descriptions and their classes' son rows (builder), first row and u of the walk's
+   // lookups (stab_meta), the tile blocks with the class-index rows; the tables themselves live in the P set (d_stab, rotated with d_ctab).
+   struct Subtree {
+      struct Key {      // what a selection was made for; its first two and frac: what the classes were computed for
+         long tips_gen = -1, tree_gen = -1, cherry_gen = -1, cap_mb = -1;
+         double frac = -1;
+         int K = -1;
+         bool operator==(const Key &o) const { return tips_gen == o.tips_gen && tree_gen == o.tree_gen && cherry_gen == o.cherry_gen && cap_mb == o.cap_mb && frac == o.frac && K == o.K; }
+      } made_for;
+      long sel_gen = 0, zt_sel_gen = -1;      // selections made so far; the one the tile blocks were laid out for (with zt_tiles x zt_tile_patt tiles)
+      int zt_tiles = 0, zt_tile_patt = 0;
+      std::vector<unsigned int> u;            // per node (0: not computed / not an internal node below the root)
+      std::vector<char> done;
+      std::vector<std::vector<unsigned int>> cls, son_cls;      // (kept between the class computation and the selections that read it)
+      std::vector<int> sel;                   // selected nodes, sons before fathers
+      SubtreeProgram sp;
+      std::vector<int> level_first;           // sp.sub sorted by level: first node of every level, then the total
+      std::vector<int> level_tiles;           // 128-class tiles of the level's largest node
+      long rows = 0;                          // rows of all tables, per class of the model
+      long n_computed = 0;
+      int zt_bytes = 0;
+      DevBuf<SubtreeNodeDev> d_nodes;
+      DevBuf<unsigned int> d_sidx, d_top_cls;
+      DevBuf<int> d_meta;
+      DevBuf<unsigned char> d_ztiles;
+   } sub;
+   std::vector<unsigned char> h_z;
+   long tips_gen = 0, tree_gen = 0, cherry_gen = 0;
+   DevBuf<double> d_stab;
+   int n_stab = 0;                            // this evaluation runs with so many subtree tables (0: none)
+   bool stab_attr_set = false;
+   long last_stab_n = 0, last_stab_bytes = 0, last_stab_blocks = -1;
    // Kernels of this engine's OTHER programs, kept loaded (round 6): a keep-partials engine alternates between its full program and the LOAD
    // programs of paml_amd_eval_dirty (com.oldconP: one per set of clean nodes, treespace.c:250), eval_branch between the tree seen from a
    // branch and the ordinary one — the kernel being left is retired here instead of unloaded, and recalled by its key.
@@ -451,7 +496,7 @@ struct paml_amd_engine {
    // the others in `spare`, oldest first from spare_head), so that the side stream can build the P(t) of the evaluations to come
    // while several pruning kernels are in flight (pruning streams, below) — it only has the CUs those leave it.
    static constexpr int NPSET = 6;
-   struct PSet { DevBuf<double> rowmajor, pint, ptip, pcol, ctab; int id = 0; } spare[NPSET - 1];      // (ctab: the set's cherry tables, below)
+   struct PSet { DevBuf<double> rowmajor, pint, ptip, pcol, ctab, stab; int id = 0; } spare[NPSET - 1];      // (ctab: the set's cherry tables, below)
    int spare_head = 0;
    DevBuf<double> d2_branch, d2_gene_rate;
    // The persistent pruning kernels (per-tree MFMA kernel, 20-state matrix-core kernel) hold every CU until their last round of
@@ -585,13 +630,15 @@ struct paml_amd_engine {
       d_eigen.release();
       d_pres.release();
       d_ctab.release();
+      d_stab.release();
+      sub.d_nodes.release(); sub.d_sidx.release(); sub.d_top_cls.release(); sub.d_meta.release(); sub.d_ztiles.release();
       d_eq_q.release(); d_eq_pi.release(); d_eq_scale.release(); d_eq_ptr.release(); d_eq_rc.release(); d_eq_sweeps.release();
       d_pi_plain.release();
       DevBuf<double> *b3[] = {&d_weights, &d_pi, &d_freqK, &d_rate, &d_qfactor, &d_branch, &d_gene_rate, &d_rowmajor,
                               &d_pint, &d_ptip, &d_pcol, &d_fhK, &d_fscale, &d_lnf, &d_b_qfactor, &d_b_freqK, &d_b_rate, &d_beb_f, &d_beb_part, &d_beb_g, &d_beb_out, &d_beb_pcl, &d_adg_all, &d_partial, &d_out, &d_partials, &d_scalef, &d_stack, &d2_branch, &d2_gene_rate, &d_partial_tot, &d_btot,
                               &d_expA, &d_expB, &d_expSA, &d_expSB, &d_deriv, &d_tt, &d_bpartial, &d_bout};
       for (auto b : b3) b->release();
-      for (auto &sp : spare) { sp.rowmajor.release(); sp.pint.release(); sp.ptip.release(); sp.pcol.release(); sp.ctab.release(); }
+      for (auto &sp : spare) { sp.rowmajor.release(); sp.pint.release(); sp.ptip.release(); sp.pcol.release(); sp.ctab.release(); sp.stab.release(); }
       for (int b = 0; b < MAXL - 1; b++) { d_partial_s[b].release(); d_partial_tot_s[b].release(); d_fhK_s[b].release(); }
    }
 };

@@ -192,6 +192,145 @@ inline int jit_cherry_count(const Program &p, int n_tips, int n_states, int n_co
    return 0;
 }
 
+// ---- subtree tables (60..64 states): repeated patterns above the cherries -------------------------------------------------------
+// What holds for a cherry holds one and two levels up, not over all tuples of codes but over the tuples the alignment contains
+// (subtree_classes.h: u_v classes at node v).  subtree_table_kernel (kernels_pmat.h) forms T_v[c] = P(t_v) . (row_l o row_r) for every
+// class c of a selected node v from its sons' rows — a tip's column, a cherry table's row, a subtree table's row —, level by level behind
+// the cherry builder, and the walk's whole op run of v (its sons' steps and lookups and its MATMUL / MATMUL_POP) becomes ONE OP_LOOKUP
+// whose row number is the pattern's class at v.  Only the topmost selected nodes appear in the walk; all cherries are still tabulated
+// (the level above reads them).  Selection and the table form depend on the node set only; the u_v are data and reach the kernels as
+// arguments (PruneArgs::stab_meta), so one compiled kernel serves every alignment with the same selected set.
+constexpr int SUBTREE_TAB_BASE = 1 << 16;      // OP_LOOKUP with c >= this: lookup c - SUBTREE_TAB_BASE of the walk reads a subtree table
+struct SubtreeSon { int kind = 0, id = 0; };      // kind 0: tip `id`; 1: cherry table `id`; 2: subtree table `id` (index into SubtreeProgram::sub)
+struct SubtreeTab { int node = 0, level = 0; SubtreeSon l, r; };
+struct SubtreeProgram {
+   Program prog;                    // the table form: cherries and top-level selected nodes as OP_LOOKUPs
+   std::vector<CherryTab> tabs;     // the cherry tables, as jit_cherry_program numbers them (all built)
+   std::vector<SubtreeTab> sub;     // every selected node, sons before fathers
+   std::vector<int> top;            // lookup t of the walk -> index into sub
+   int levels = 0;
+};
+
+// Nodes to tabulate beside the cherries `tabs`: exactly two sons, each a tip or tabulated, no rescaling at the node, not the root; in
+// ascending u (u_father >= u_son, ties broken by height) while u <= frac x n_patt and K x rows x 512 bytes stay within cap_bytes.
+inline std::vector<int> jit_subtree_select(const TreeDesc &t, const std::vector<CherryTab> &tabs, const std::vector<unsigned int> &u,
+                                           const std::vector<char> &done, long n_patt, double frac, size_t cap_bytes, int K)
+{
+   std::vector<int> sel, cand, height(t.n_nodes, 0), tab_of(t.n_nodes, -1), is_sel(t.n_nodes, 0);
+   for (size_t i = 0; i < tabs.size(); i++) {
+      const int v = tabs[i].node;
+      if (t.sons_ptr[v + 1] - t.sons_ptr[v] == 2 && t.sons[t.sons_ptr[v]] == tabs[i].tip_a && t.sons[t.sons_ptr[v] + 1] == tabs[i].tip_b) tab_of[v] = (int)i;
+   }
+   {  // heights, sons first
+      std::vector<int> order, st(1, t.root);
+      while (!st.empty()) {
+         const int v = st.back();
+         st.pop_back();
+         order.push_back(v);
+         for (int j = t.sons_ptr[v]; j < t.sons_ptr[v + 1]; j++) st.push_back(t.sons[j]);
+      }
+      for (size_t k = order.size(); k-- > 0;)
+         for (int j = t.sons_ptr[order[k]]; j < t.sons_ptr[order[k] + 1]; j++) height[order[k]] = std::max(height[order[k]], height[t.sons[j]] + 1);
+   }
+   // (never a cherry: one that the cherry tables left out — their cap, or their rule of four operand blocks — stays a product, and so
+   //  does everything above it; its class numbers are not dense and it has no son rows)
+   auto cherry = [&](int v) { return t.sons[t.sons_ptr[v]] < t.n_tips && t.sons[t.sons_ptr[v] + 1] < t.n_tips; };
+   for (int v = t.n_tips; v < t.n_nodes; v++)
+      if (v != t.root && done[v] && tab_of[v] < 0 && t.sons_ptr[v + 1] - t.sons_ptr[v] == 2 && !cherry(v) && !(v < (int)t.scale_node.size() && t.scale_node[v]) &&
+          (double)u[v] <= frac * (double)n_patt)
+         cand.push_back(v);
+   std::sort(cand.begin(), cand.end(), [&](int a, int b) { return u[a] != u[b] ? u[a] < u[b] : (height[a] != height[b] ? height[a] < height[b] : a < b); });
+   size_t rows = 0;
+   for (int v : cand) {
+      bool ok = true;
+      for (int j = t.sons_ptr[v]; j < t.sons_ptr[v + 1]; j++) {
+         const int s = t.sons[j];
+         ok = ok && (s < t.n_tips || tab_of[s] >= 0 || is_sel[s]);
+      }
+      if (!ok || (rows + u[v]) * CHERRY_ROW_BYTES * (size_t)K > cap_bytes || u[v] >= (1u << 24)) continue;      // (a class index travels as three bytes)
+      rows += u[v];
+      is_sel[v] = 1;
+      sel.push_back(v);
+   }
+   return sel;
+}
+
+// The table form of `p` with the cherries of jit_cherry_program(p, max_tabs) and the nodes `sel` (jit_subtree_select's order) tabulated.
+inline SubtreeProgram jit_subtree_program(const Program &p, int max_tabs, const TreeDesc &t, const std::vector<int> &sel)
+{
+   SubtreeProgram sp;
+   const std::vector<Op> &o = p.ops;
+   // the cherry tables, by the op that starts them — jit_cherry_program's scan
+   std::vector<int> cherry_at(o.size(), -1), tab_of(t.n_nodes, -1), sub_of(t.n_nodes, -1), father(t.n_nodes, -1);
+   for (size_t i = 0; i + 1 < o.size(); i++)
+      if (o[i].code == OP_SET_TIP2 && (o[i + 1].code == OP_MATMUL || o[i + 1].code == OP_MATMUL_POP) && (int)sp.tabs.size() < max_tabs) {
+         cherry_at[i] = (int)sp.tabs.size();
+         tab_of[o[i + 1].a] = (int)sp.tabs.size();
+         sp.tabs.push_back({o[i].a, o[i].b, o[i + 1].a});
+      }
+   for (int v = 0; v < t.n_nodes; v++)
+      for (int j = t.sons_ptr[v]; j < t.sons_ptr[v + 1]; j++) father[t.sons[j]] = v;
+   for (int v : sel) {
+      SubtreeTab st;
+      st.node = v;
+      SubtreeSon *son[2] = {&st.l, &st.r};
+      for (int j = 0; j < 2; j++) {
+         const int s = t.sons[t.sons_ptr[v] + j];
+         if (s < t.n_tips) *son[j] = {0, s};
+         else if (tab_of[s] >= 0) *son[j] = {1, tab_of[s]};
+         else { *son[j] = {2, sub_of[s]}; st.level = std::max(st.level, sp.sub[sub_of[s]].level + 1); }
+      }
+      sp.levels = std::max(sp.levels, st.level + 1);
+      sub_of[v] = (int)sp.sub.size();
+      sp.sub.push_back(st);
+   }
+   // the op run of every node's product: from the op that starts the partial its MATMUL multiplies to that MATMUL
+   std::vector<int> run_end(o.size(), -1), run_node(o.size(), -1);      // by first op, for the topmost selected nodes
+   {
+      int cur_start = -1;
+      std::vector<int> slot_start(256, -1);
+      for (size_t i = 0; i < o.size(); i++) {
+         switch (o[i].code) {
+         case OP_INIT_ONES: case OP_INIT_TIP: case OP_SET_TIP: case OP_SET_TIP2: case OP_LOAD: cur_start = (int)i; break;
+         case OP_PUSH: slot_start[o[i].b & 255] = cur_start; cur_start = -1; break;
+         case OP_MATMUL: case OP_MATMUL_POP: {
+            const int v = o[i].a, pop = mm_pop_slot(o[i]), push = mm_push_slot(o[i]);
+            if (sub_of[v] >= 0 && cur_start >= 0 && (father[v] < 0 || sub_of[father[v]] < 0)) { run_end[cur_start] = (int)i; run_node[cur_start] = v; }
+            if (pop >= 0) cur_start = slot_start[pop];      // (the father's partial began where the popped one did)
+            if (push >= 0) { slot_start[push] = cur_start; cur_start = -1; }
+         } break;
+         default: break;
+         }
+      }
+   }
+   int max_slot = -1;
+   for (size_t i = 0; i < o.size(); i++) {
+      if (run_end[i] >= 0) {
+         const Op &mm = o[run_end[i]];
+         sp.prog.ops.push_back({OP_LOOKUP, mm.a, mm.b, SUBTREE_TAB_BASE + (int)sp.top.size()});
+         sp.top.push_back(sub_of[run_node[i]]);
+         max_slot = std::max(max_slot, mm_push_slot(mm));
+         i = run_end[i];
+         continue;
+      }
+      if (cherry_at[i] >= 0) {
+         sp.prog.ops.push_back({OP_LOOKUP, o[i + 1].a, o[i + 1].b, cherry_at[i]});
+         max_slot = std::max(max_slot, mm_push_slot(o[i + 1]));
+         i++;
+         continue;
+      }
+      sp.prog.ops.push_back(o[i]);
+      if (o[i].code == OP_MATMUL || o[i].code == OP_MATMUL_POP) { sp.prog.n_matmul++; max_slot = std::max(max_slot, mm_push_slot(o[i])); }
+      if (o[i].code == OP_PUSH) max_slot = std::max(max_slot, o[i].b & 255);
+   }
+   sp.prog.max_stack = std::min(p.max_stack, max_slot + 1);      // (the collapsed runs held the deep slots)
+   finish_program(sp.prog);
+   return sp;
+}
+// the rows of a tile's code block with the class indices of n_top lookups behind the weight flags; they must leave room for two blocks
+inline int jit_subtree_zrows(int n_tips, int n_top) { return n_tips + 3 * n_top; }
+inline bool jit_subtree_zfits(int n_tips, int n_top, int tp = 128) { return jit_lds_fits(jit_subtree_zrows(n_tips, n_top), 2, tp); }
+
 // ---- what the generators share -------------------------------------------------------------------------------------------
 // The profiling switches of the kernel experiments, read once per generation (build() and the tests change them between calls).
 struct JitProf {
@@ -319,11 +458,15 @@ struct JitWalk {
    const int n_tips, n_states, n_codes, first;
    const std::vector<CherryTab> *const tabs;
    const JitProf &prof;
+   const int n_top;      // subtree tables: lookups of the walk that read one (their class indices are rows of the tile's code block)
    static constexpr int waves = 8, TP = waves * 16;
    const int nblk = (int)p.stream.size() / 2;
    const size_t nops = p.ops.size();
    const JitZPlan zpl = jit_zplan(p, n_tips, TP);
-   const int ZP = zpl.ZP, ZR = (ZP * 8 + waves - 1) / waves;      // code block (or piece): 2 KB units; DMA rounds per wave
+   const int ZP = n_top ? jit_zpieces(jit_subtree_zrows(n_tips, n_top), TP) : zpl.ZP, ZR = (ZP * 8 + waves - 1) / waves;      // code block (or piece): 2 KB units; DMA rounds per wave
+   // fewer than four operand blocks left per tile (subtree tables: the headline tree keeps none): the ring never runs more than one tile
+   // ahead, nothing of the next tile is started early, and a tile ends with everything it requested landed — see tile_tail
+   const bool short_form = n_top > 0 && nblk < 4;
    // states beyond n are zero padding: only RB row blocks and KB k-blocks of every P take part (4 and 16 at 61 states)
    const int RB = (n_states + 15) / 16, KB = (n_states + 3) / 4, KB2 = (KB + 1) / 2, NPc = KB2;   // NPc: 16-byte pieces per tip-table row
    const bool fuse_tips = KB2 >= 2;   // cherries gathered under the preceding matmul
@@ -353,7 +496,7 @@ struct JitWalk {
    // one code block only (large trees): it is replaced between tiles, so nothing of the next tile can start early
    const bool zsingle = zpl.bufs == 1, zhalf = zpl.half;
    const bool peel = fuse_tips && nops > 2 && p.ops[0].code == OP_SET_TIP2 && last_mm > 1 && p.ops[1].code != OP_MUL_TIP &&
-                     p.ops[1].code != OP_MUL_TIP2 && !tail_blocks && !zsingle;      // the tile's first cherry is produced by its predecessor, into AS
+                     p.ops[1].code != OP_MUL_TIP2 && !tail_blocks && !zsingle && !short_form;      // the tile's first cherry is produced by its predecessor, into AS
    // cherry tables (OP_LOOKUP): the rows of a lookup are requested LA lookups ahead of their use, so that a product lies between request
    // and use; those of a tile's first lookups under the previous tile's last product (or, in front of the loop, for the first tile),
    // into arrays of their own
@@ -364,7 +507,7 @@ struct JitWalk {
       return at;
    }();
    const int nlk = (int)lk_op.size();
-   const bool lk_cross = nlk > 0 && !peel && !zsingle;      // the first lookups of a tile are requested by its predecessor
+   const bool lk_cross = nlk > 0 && !peel && !zsingle && !short_form;      // the first lookups of a tile are requested by its predecessor
    // (trees that keep three or more partials stacked in registers: one lookup ahead — with two the 23-taxon random tree of the tests
    //  spills 18 VGPRs)
    const int LA = std::min(p.max_stack, JIT_REG_SLOTS) >= 3 ? 1 : JIT_LOOKAHEAD;
@@ -390,8 +533,8 @@ struct JitWalk {
    int lk_issued = 0, lk_seen = 0;           // lookups of this tile requested / consumed so far
    bool lk_next_done = false;                // the next tile's first lookups are requested
 
-   JitWalk(const Program &p_, int n_tips_, int n_states_, int n_codes_, int first_, const std::vector<CherryTab> *tabs_, const JitProf &prof_)
-      : p(p_), n_tips(n_tips_), n_states(n_states_), n_codes(n_codes_), first(first_), tabs(tabs_), prof(prof_) {}
+   JitWalk(const Program &p_, int n_tips_, int n_states_, int n_codes_, int first_, const std::vector<CherryTab> *tabs_, const JitProf &prof_, int n_top_ = 0)
+      : p(p_), n_tips(n_tips_), n_states(n_states_), n_codes(n_codes_), first(first_), tabs(tabs_), prof(prof_), n_top(n_top_) {}
 
    // ---- text of the operands ----
    int n_rounds(int blk) const { return p.stream[2 * (blk % nblk)] ? T_ROUNDS : P_ROUNDS; }
@@ -413,12 +556,19 @@ struct JitWalk {
    std::string lookup_text(int k, bool next) const
    {
       const Op &o = p.ops[lk_op[k]];
+      if (o.c >= SUBTREE_TAB_BASE) {      // a subtree table: the row is the pattern's class, from the index rows behind the weight flags
+         const int tn = o.c - SUBTREE_TAB_BASE;
+         return "jit_lookup_row(" + (next ? JitArr{JitArr::NEXT_LOOKUP, k} : lk_arr[k]).name() + ", JIT_STAB(" + (next ? "n_iclass" : "iclass") + ", " + std::to_string(tn) + "), " +
+                (next ? "JIT2_NIDX(" : "JIT2_IDX(") + std::to_string(ZP) + ", " + std::to_string(n_tips + 1 + 3 * tn) + "), JIT_STAB_U(" + std::to_string(tn) + "), q);";
+      }
       const CherryTab &t = (*tabs)[o.c];
       return "jit_lookup(" + (next ? JitArr{JitArr::NEXT_LOOKUP, k} : lk_arr[k]).name() + ", JIT_CTAB(" + (next ? "n_iclass" : "iclass") + ", " + std::to_string(o.c) +
              "), " + code(t.tip_a, next) + ", " + code(t.tip_b, next) + ", q);";
    }
 
    // ---- the schedule ----
+   // the ring is refilled up to three blocks ahead, and never beyond the next tile's blocks (whose P set is the one known)
+   int ahead() const { return std::min(consumed + 4, 2 * nblk); }
    void issue_now()
    {
       s << "  ";
@@ -456,7 +606,7 @@ struct JitWalk {
          fl.issue({JitItem::MEM, 0}, (int)pend_store.size());
          pend_store.clear();
       }
-      while (issued < consumed + 4) issue_now();
+      while (issued < ahead()) issue_now();
    }
    // a product's block step: arrive, and the refill as a `side` functor that spreads its pieces over the first `iters` k-block pairs
    // of the matmul that follows
@@ -465,7 +615,7 @@ struct JitWalk {
       arrive(1);
       struct Piece { JitItem item; std::string text; };
       std::vector<Piece> pieces;
-      for (; issued < consumed + 4; issued++)
+      for (; issued < ahead(); issued++)
          for (int c4 = 0; c4 < n_pieces(issued); c4++) pieces.push_back({{JitItem::RING, issued}, piece(issued, c4)});
       if (pieces.empty() && pend_store.empty() && pend_lookup.empty()) return "JitNoSide()";
       const int per = pieces.empty() ? 1 : ((int)pieces.size() + iters - 1) / iters;
@@ -571,7 +721,7 @@ struct JitWalk {
          s << "   JIT_WAIT(0); __syncthreads();\n";
          issue_next_lookups();
       }
-      if (zsingle) {      // everything requested so far has to be there when the loop starts: the same state the loop's end leaves
+      if (zsingle || short_form) {      // everything requested so far has to be there when the loop starts: the same state the loop's end leaves
          s << "   JIT_WAIT(0); __syncthreads();\n";
          fl.clear();
       }
@@ -589,6 +739,11 @@ struct JitWalk {
       if (zhalf) s << "   const int cur_tile = n_tile;\n";
       s << "   work += gridDim.x;\n   JIT2_NEXT_SET()\n";
       z_pending = !zsingle;
+      if (short_form) {      // (every tile ends behind a barrier with nothing in flight: the other code buffer is free from here on)
+         s << "   JIT2_ISSUE_Z(" << ZP << ")\n";
+         fl.issue({JitItem::CODES, 0}, ZR);
+         z_pending = false;
+      }
       if (peel) regs.cur = {JitArr::NEXT_CHERRY, 0};
       if (prof.ops) s << "   if (a.prof && tid == a.prof_tid && ptile) a.prof[(long)blockIdx.x * a.prof_stride] = __builtin_amdgcn_s_memtime();\n";
       lk_issued = lk_ncross;
@@ -604,6 +759,10 @@ struct JitWalk {
       if (z_pending) {
          s << "   __syncthreads();\n   JIT2_ISSUE_Z(" << ZP << ")\n";
          fl.issue({JitItem::CODES, 0}, ZR);
+      }
+      if (short_form) {      // the next tile's codes (its lookups read them at its start) and whatever of its blocks is on the way: landed, for every wave
+         s << "   JIT_WAIT(0); __syncthreads();\n";
+         fl.clear();
       }
       if (zsingle) {      // all waves are done with this tile's codes: fetch the next tile's (first piece) over them, and wait (once per tile)
          s << "   __syncthreads();\n   " << issue_z() << "\n   JIT_WAIT(0); __syncthreads();\n";
@@ -768,14 +927,15 @@ struct JitWalk {
 };
 
 // (`tabs`: p is the table form of the tree's program — jit_cherry_program — and these are its tables)
-inline std::string jit_generate(const Program &p, int n_tips, int n_states = 61, int n_codes = 64, const std::vector<CherryTab> *tabs = nullptr)
+// (n_top: p is the table form with subtree tables — jit_subtree_program — and so many of its lookups read one)
+inline std::string jit_generate(const Program &p, int n_tips, int n_states = 61, int n_codes = 64, const std::vector<CherryTab> *tabs = nullptr, int n_top = 0)
 {
    const JitProf prof;
-   int first = 3, got = 3;
-   std::string src = JitWalk(p, n_tips, n_states, n_codes, first, tabs, prof).generate(&got);
+   int first = std::min(3, (int)p.stream.size() / 2), got = first;
+   std::string src = JitWalk(p, n_tips, n_states, n_codes, first, tabs, prof, n_top).generate(&got);
    if (got != first) {
       first = got;
-      src = JitWalk(p, n_tips, n_states, n_codes, first, tabs, prof).generate(&got);
+      src = JitWalk(p, n_tips, n_states, n_codes, first, tabs, prof, n_top).generate(&got);
    }
    if (got != first) return std::string("#error \"jit schedule does not close\"\n");
    return src;

@@ -61,6 +61,22 @@ struct CherryTabArgs {
    double *ctab;                       // [K][n_tabs][n_codes * n_codes][64]
 };
 
+// Subtree tables (kernels_pmat.h: subtree_table_kernel; jit.h: SubtreeProgram) of one evaluation's P(t): one level of tabulated nodes
+struct SubtreeNodeDev {
+   int node, u, row0;                  // the node (its P(t)), its classes, its table's first row within a class's stab_rows
+   int lkind, lid, rkind, rid;         // the sons — kind 0: tip `id`; 1: cherry table `id`; 2: the subtree table whose first row is `id`
+   int pad;
+   long sidx;                          // class c's row at the left son: sidx[this + c], at the right son: sidx[this + u + c]
+};
+struct SubtreeTabArgs {
+   int n_codes, n_nodes, n_ctab, first;   // first: the level's first node in `nodes` (blockIdx.y counts from it)
+   long tip_words, stab_rows;
+   const double *pint, *ptip, *pcol, *ctab;   // this evaluation's P set and its cherry tables
+   const SubtreeNodeDev *nodes;
+   const unsigned int *sidx;
+   double *stab;                          // [K][stab_rows][64]
+};
+
 // Branch lengths and gene rates handed over INSIDE the kernel arguments (single evaluations of trees with up to ~440 nodes):
 // the launch itself carries them, so an evaluation needs no host-to-device copy and no staging buffer to keep alive.
 #define PMAT_INLINE_MAX 440

@@ -526,4 +526,56 @@ __global__ __launch_bounds__(512) void cherry_table_kernel(CherryTabArgs a)
    }
 }
 
+// Subtree tables of the per-tree 60..64-state kernel (jit.h: SubtreeProgram).  cherry_table_kernel with gathered inputs: for node v of
+// the level and class c,   T_v[c] = P(t_v) . (row_l o row_r),   a row being the son's finished table row (of a cherry table or of a subtree
+// table of an earlier level: eight 16-byte loads per lane, the walk's jit_lookup) or the son tip's column from its table in LDS
+// (jit_tip_set / jit_tip_mul), multiplied as the walk multiplies them (a product of two factors: the order does not change the bits),
+// then jit_x60 and jit_matvec with the node's P block and column table in LDS — the walk's functions, so an entry has the bits the walk
+// would compute for a pattern of that class.  A wave takes 16 classes.  Grid: (128-class tiles of the level's largest node, nodes of the
+// level, classes of the model); one launch per level, on the P(t) stream behind the cherry builder.
+template <bool TAIL61, int KB = 16>
+__global__ __launch_bounds__(512) void subtree_table_kernel(SubtreeTabArgs a)
+{
+   extern __shared__ __attribute__((aligned(16))) double st_lds[];
+   double *sP = st_lds, *sA = st_lds + 4096, *sB = st_lds + 8192, *sC = st_lds + 12288;
+   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, hl = lane & 15;
+   const SubtreeNodeDev nd = a.nodes[a.first + blockIdx.y];
+   const int cls = blockIdx.z, nc = a.n_codes;
+   if ((int)blockIdx.x * 128 >= nd.u) return;      // (the grid is the level's largest node's)
+   const long ps = (long)cls * a.n_nodes;
+   const double2 *gP = (const double2 *)(a.pint + (ps + nd.node) * 4096);
+   for (int i = tid; i < 2048; i += 512) ((double2 *)sP)[i] = gP[i];
+   if (nd.lkind == 0) {
+      const double2 *gA = (const double2 *)(a.ptip + (ps + nd.lid) * a.tip_words);
+      for (int i = tid; i < nc * 32; i += 512) ((double2 *)sA)[i] = gA[i];
+   }
+   if (nd.rkind == 0) {
+      const double2 *gB = (const double2 *)(a.ptip + (ps + nd.rid) * a.tip_words);
+      for (int i = tid; i < nc * 32; i += 512) ((double2 *)sB)[i] = gB[i];
+   }
+   if (tid < 64) sC[tid] = TAIL61 ? a.pcol[(ps + nd.node) * 64 + tid] : 0.0;
+   __syncthreads();
+   const int c = blockIdx.x * 128 + wave * 16 + hl;
+   const bool valid = c < nd.u;
+   const int cc = valid ? c : nd.u - 1;      // (every lane computes: the products are wave-wide)
+   const int il = (int)a.sidx[nd.sidx + cc], ir = (int)a.sidx[nd.sidx + nd.u + cc];
+   const double *ctab = a.ctab + (long)cls * a.n_ctab * nc * nc * CHERRY_ROW_WORDS;
+   const double *stab = a.stab + (long)cls * a.stab_rows * CHERRY_ROW_WORDS;
+   v4d x[4], t[4], y[4];
+   if (nd.lkind == 0) jit_tip_set<8>(x, sA, il, q, lane);
+   else jit_lookup_row(x, nd.lkind == 1 ? ctab + (long)nd.lid * nc * nc * CHERRY_ROW_WORDS : stab + (long)nd.lid * CHERRY_ROW_WORDS, il, il + 1, q);
+   if (nd.rkind == 0) jit_tip_mul<8>(x, sB, ir, q, lane);
+   else {
+      jit_lookup_row(t, nd.rkind == 1 ? ctab + (long)nd.rid * nc * nc * CHERRY_ROW_WORDS : stab + (long)nd.rid * CHERRY_ROW_WORDS, ir, ir + 1, q);
+      jit_mul(x, t);
+   }
+   const double x60 = TAIL61 ? jit_x60(x, lane) : 0.0;
+   jit_matvec<TAIL61, 4, KB>(sP, lane, x, y, JitNoSide(), sC, x60);
+   if (valid) {
+      part2_t *r = (part2_t *)(a.stab + (((long)cls * a.stab_rows + nd.row0 + c)) * CHERRY_ROW_WORDS) + q;
+#pragma unroll
+      for (int i = 0; i < 8; i++) r[i * 4] = (part2_t){y[i >> 1][(2 * i) & 3], y[i >> 1][(2 * i + 1) & 3]};
+   }
+}
+
 }  // namespace paml_amd

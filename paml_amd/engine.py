@@ -30,6 +30,7 @@ EXPORTS = [
     "paml_amd_device_count", "paml_amd_set_device", "paml_amd_shard_bounds", "paml_amd_max_ranks", "paml_amd_flush", "paml_amd_eigen_status", "paml_amd_comm_unique_id", "paml_amd_comm_init", "paml_amd_comm_destroy", "paml_amd_comm_info", "paml_amd_comm_library", "paml_amd_comm_stats", "paml_amd_get_partial_sums", "paml_amd_branch_counters", "paml_amd_branch_coef_hits", "paml_amd_branch_refill_kernels", "paml_amd_branch_kernel_ms",
     "paml_amd_jit_prebuild", "paml_amd_profile", "paml_amd_profile_read", "paml_amd_counters", "paml_amd_kernel_name", "paml_amd_debug_program", "paml_amd_debug_jit",
     "paml_amd_cherry_tables", "paml_amd_debug_jit_tables",
+    "paml_amd_subtree_tables", "paml_amd_debug_subtree_classes", "paml_amd_debug_jit_subtree", "paml_amd_debug_subtree_select",
     "paml_amd_debug_code_order", "paml_amd_debug_branch_plan",
     "paml_amd_pairset_create", "paml_amd_pairset_destroy", "paml_amd_pairset_get_counts", "paml_amd_pairset_set_pi", "paml_amd_pairset_set_pattern",
     "paml_amd_pairset_eval", "paml_amd_pairset_failed", "paml_amd_pairset_counters",
@@ -570,6 +571,18 @@ class Engine:
         self._chk(self._L.paml_amd_cherry_tables(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def subtree_tables(self):
+        """Subtree tables of the last evaluation: dict(nodes, u — the nodes tabulated above the cherries and their numbers of classes, sons
+        before fathers —, bytes, blocks_left — operand blocks left per tile, -1 without subtree tables —, n_computed — class computations
+        of this engine so far)."""
+        cap = 256
+        n, by, bl, nc = C.c_long(), C.c_long(), C.c_long(), C.c_long()
+        nodes, u = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int64)
+        self._L.paml_amd_subtree_tables.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.c_void_p, C.c_void_p, C.c_int] + [C.POINTER(C.c_long)] * 3
+        self._chk(self._L.paml_amd_subtree_tables(self._h, C.byref(n), _p(nodes), _p(u), cap, C.byref(by), C.byref(bl), C.byref(nc)))
+        k = min(n.value, cap)
+        return dict(nodes=nodes[:k].tolist(), u=u[:k].tolist(), bytes=by.value, blocks_left=bl.value, n_computed=nc.value)
+
     def counters(self):
         a, b = C.c_long(), C.c_long()
         self._L.paml_amd_counters(self._h, C.byref(a), C.byref(b))
@@ -781,6 +794,62 @@ def debug_jit_tables(tree, scale_node=None, max_tabs=1 << 20):
     if rc < 0:
         raise EngineError("debug_jit_tables failed (%d)" % rc)
     return buf.value.decode(), [tuple(x) for x in stream[:2 * ns.value].reshape(-1, 2)], [tuple(x) for x in tabs[:3 * rc].reshape(-1, 3)]
+
+
+def debug_subtree_classes(tree, z, n_codes, want_classes=False):
+    """Host-only: the subtree classes (csrc/subtree_classes.h) of tip codes z[n_tips][n_patt] on `tree`: u[n_nodes], the number of classes
+    of every internal node below the root (0 elsewhere); with want_classes also cls[n_nodes][n_patt]."""
+    L = lib()
+    ptr, flat = tree.csr()
+    z = np.ascontiguousarray(z, dtype=np.uint8)
+    n_patt = z.shape[1]
+    u = np.zeros(tree.n_nodes, dtype=np.uint32)
+    cls = np.zeros((tree.n_nodes, n_patt), dtype=np.uint32) if want_classes else None
+    L.paml_amd_debug_subtree_classes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p]
+    rc = L.paml_amd_debug_subtree_classes(tree.n_tips, tree.n_nodes, tree.root, _p(ptr), _p(flat), _p(z), n_patt, int(n_codes), _p(u), _p(cls))
+    if rc < 0:
+        raise EngineError("debug_subtree_classes failed (%d)" % rc)
+    return (u, cls) if want_classes else u
+
+
+def debug_subtree_select(tree, z, n_states, n_codes, K=1, scale_node=None):
+    """Host-only: the nodes an engine of these sizes would tabulate above the cherries for tip codes z (the switches of the environment
+    apply), sons before fathers."""
+    L = lib()
+    ptr, flat = tree.csr()
+    z = np.ascontiguousarray(z, dtype=np.uint8)
+    sc = None if scale_node is None else np.ascontiguousarray(scale_node, dtype=np.uint8)
+    sel = np.zeros(tree.n_nodes, dtype=np.int32)
+    L.paml_amd_debug_subtree_select.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long,
+                                                C.c_void_p, C.c_int]
+    n = L.paml_amd_debug_subtree_select(tree.n_tips, tree.n_nodes, tree.root, _p(ptr), _p(flat), _p(sc), int(n_states), int(n_codes), int(K), _p(z), z.shape[1],
+                                        _p(sel), len(sel))
+    if n < 0:
+        raise EngineError("debug_subtree_select failed (%d)" % n)
+    return sel[:n].tolist()
+
+
+def debug_jit_subtree(tree, nodes, n_states=61, n_codes=61, K=1, compile=True, scale_node=None, directory=None):
+    """Host-only: the per-tree kernel with subtree tables of `nodes` (sons before fathers) beside the cherry tables: (source, operand blocks
+    left per tile); compiled for gfx950 when compile=True, into `directory` when given.  ("", None) when the table form does not apply."""
+    L = lib()
+    ptr, flat = tree.csr()
+    sc = None if scale_node is None else np.ascontiguousarray(scale_node, dtype=np.uint8)
+    sel = np.ascontiguousarray(nodes, dtype=np.int32)
+    cap = 1 << 21
+    buf = C.create_string_buffer(cap)
+    left = C.c_int(-1)
+    L.paml_amd_debug_jit_subtree.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    if directory:
+        os.makedirs(directory, exist_ok=True)
+    rc = L.paml_amd_debug_jit_subtree(tree.n_tips, tree.n_nodes, tree.root, _p(ptr), _p(flat), _p(sc), int(n_states), int(n_codes), int(K), _p(sel), len(sel),
+                                      int(bool(compile)), os.fsencode(directory) if directory else None, buf, cap, C.byref(left))
+    if rc < 0:
+        raise EngineError("debug_jit_subtree failed (%d): %s" % (rc, buf.value.decode(errors="replace")[-3000:]))
+    if rc == 0:
+        return "", None
+    return buf.value.decode(), left.value
 
 
 JIT_SHIPPED_DIR = os.path.join(_HERE, "lib", "jit")
