@@ -340,6 +340,10 @@ int paml_amd_cherry_tables(const paml_amd_engine *e, long *n_tabulated, long *by
  * into nodes[] / u[], sons before fathers, with their numbers of classes), the tables' bytes, the operand blocks the per-tree kernel is
  * left with per tile (-1: it ran without subtree tables), and how often the engine has computed the classes (once per tips + tree). */
 int paml_amd_subtree_tables(const paml_amd_engine *e, long *n_tabulated, int *nodes, long *u, int cap, long *bytes, long *blocks_left, long *n_computed);
+/* The pattern order of the walk with subtree tables (the patterns sorted by their classes at the walk's lookups; PAML_AMD_SUBTREE_ORDER=0
+ * switches it off): whether the last evaluation ran with it, how often the engine has computed it (once per tips + tree + selection,
+ * never per evaluation) and the host time of the last computation. */
+int paml_amd_subtree_order(const paml_amd_engine *e, int *in_use, long *n_computed, double *host_seconds);
 
 /* Host-only introspection (no GPU needed): the flattened post-order program the engine would run for
  * a tree — 4 ints per op (code, a, b, c; paml_amd/csrc/program.h).  Returns the number of ops (or a
@@ -384,6 +388,12 @@ int paml_amd_debug_jit_tables(int n_tips, int n_nodes, int root, const int *sons
  * pattern's class there — dense ranks in order of first occurrence, at a cherry ca * n_codes + cb. */
 int paml_amd_debug_subtree_classes(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *z, long n_patt,
                                    int n_codes, unsigned int *u_out, unsigned int *cls_out);
+
+/* Host-only: the pattern order of the walk with subtree tables for n_keys class arrays keys[n_keys][n_patt] (entries < bound[k]):
+ * order_out[position] = pattern, the patterns sorted by their classes, the keys taken smallest bound first (largest_first: the reverse;
+ * as_given: in the order given), ties by pattern number. */
+int paml_amd_debug_subtree_order(int n_keys, const unsigned int *keys, const unsigned int *bound, long n_patt, int largest_first, int as_given,
+                                 unsigned int *order_out);
 
 /* Host-only: the nodes an engine of these sizes (one gene, K classes, the PAML_AMD_SUBTREE_* / PAML_AMD_CHERRY_* switches of the
  * environment) tabulates above the cherries for tip codes z[n_tips][n_patt], sons before fathers.  Returns their number. */

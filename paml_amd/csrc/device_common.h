@@ -94,6 +94,9 @@ struct PruneArgs {
    const double *stab;
    long stab_rows;
    const int *stab_meta;
+   // ... whose tiles hold the patterns in another order (engine_eval.hip: ensure_subtree_ztiles): the pattern of position p is order[p], and
+   // the walk stores its value there.  null: the identity (kernels generated without the order never read it)
+   const int *order;
 };
 
 __device__ __forceinline__ double root_value(const PruneArgs &a, double f, double lnscale)
@@ -1375,5 +1378,9 @@ __device__ __forceinline__ void m20_root(const PruneArgs &a, const double (&x)[5
 /* a pattern's class index at a tabulated node (subtree tables): three byte rows of the tile's code block behind the weight flags, low byte first */
 #define JIT2_IDX(ZP, ROW) (JIT2_CODE(ZP, ROW) | (JIT2_CODE(ZP, (ROW) + 1) << 8) | (JIT2_CODE(ZP, (ROW) + 2) << 16))
 #define JIT2_NIDX(ZP, ROW) (JIT2_NCODE(ZP, ROW) | (JIT2_NCODE(ZP, (ROW) + 1) << 8) | (JIT2_NCODE(ZP, (ROW) + 2) << 16))
+/* the pattern a lane's position stands for (PruneArgs::order), requested at the tile's head: 64 contiguous bytes per wave, long landed when
+ * the root stores.  The load is NOT entered in the generator's in-flight list: the hardware then holds one operation more than the list
+ * says, which makes a counted wait stricter, never laxer, wherever the compiler places the load. */
+#define JIT2_ORDER() const int hs = as_const(a.order)[valid ? h : h0];
 
 }  // namespace paml_amd

@@ -793,6 +793,15 @@ int paml_amd_subtree_tables(const paml_amd_engine *e, long *n_tabulated, int *no
    return 0;
 }
 
+int paml_amd_subtree_order(const paml_amd_engine *e, int *in_use, long *n_computed, double *host_seconds)
+{
+   if (!e) return PAML_AMD_EINVAL;
+   if (in_use) *in_use = (e->last_stab_n && e->sub.ordered) ? 1 : 0;
+   if (n_computed) *n_computed = e->sub.n_order_computed;
+   if (host_seconds) *host_seconds = e->sub.order_host_s;
+   return 0;
+}
+
 int paml_amd_counters(const paml_amd_engine *e, long *n_eval, long *n_pmat)
 {
    if (!e) return PAML_AMD_EINVAL;

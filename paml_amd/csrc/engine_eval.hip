@@ -402,14 +402,43 @@ int ensure_subtree(paml_amd_engine *e, int K, int tp)
    for (int i = 0; i < ns; i++) { row0[i] = (int)sb.rows; sb.rows += sb.u[sb.sp.sub[i].node]; }
    sb.level_first.clear();
    sb.level_tiles.clear();
+   sb.level_small.clear();
    for (int l = 0; l < sb.sp.levels; l++) {
       sb.level_first.push_back((int)by_level.size());
       int tiles = 0;
+      bool tip_son = false;
       for (int i = 0; i < ns; i++)
-         if (sb.sp.sub[i].level == l) { by_level.push_back(i); tiles = std::max(tiles, (int)((sb.u[sb.sp.sub[i].node] + 127) / 128)); }
+         if (sb.sp.sub[i].level == l) {
+            by_level.push_back(i);
+            tiles = std::max(tiles, (int)((sb.u[sb.sp.sub[i].node] + 127) / 128));
+            tip_son = tip_son || sb.sp.sub[i].l.kind == 0 || sb.sp.sub[i].r.kind == 0;
+         }
       sb.level_tiles.push_back(tiles);
+      sb.level_small.push_back(tip_son ? 0 : 1);
    }
    sb.level_first.push_back((int)by_level.size());
+   // rows in son order (unless PAML_AMD_SUBTREE_ROWS=0): class c of a table sits at the rank of (left son row, right son row) — sons
+   // before fathers, so a father sorts by its sons' final rows — and a builder tile's gathers, and a sorted walk's, land on neighbouring
+   // rows.  A row's bits do not depend on where it is stored; the classes themselves (sb.cls, the report) keep their numbering.
+   sb.rowmap.assign(ns, std::vector<unsigned int>());
+   std::vector<std::vector<unsigned int>> son_rows(ns);      // [2][u] by ROW of the table, the sons as rows of theirs
+   for (int i = 0; i < ns; i++) {
+      const SubtreeTab &st = sb.sp.sub[i];
+      const size_t u = sb.u[st.node];
+      const std::vector<unsigned int> &sc = sb.son_cls[st.node];
+      std::vector<unsigned int> l(sc.begin(), sc.begin() + u), r(sc.begin() + u, sc.end());
+      if (st.l.kind == 2 && !sb.rowmap[st.l.id].empty()) for (unsigned int &x : l) x = sb.rowmap[st.l.id][x];
+      if (st.r.kind == 2 && !sb.rowmap[st.r.id].empty()) for (unsigned int &x : r) x = sb.rowmap[st.r.id][x];
+      son_rows[i].resize(2 * u);
+      if (e->env.subtree_rows) {
+         std::vector<unsigned int> by(u);
+         for (size_t c = 0; c < u; c++) by[c] = (unsigned int)c;
+         std::sort(by.begin(), by.end(), [&](unsigned int a, unsigned int b) { return l[a] != l[b] ? l[a] < l[b] : (r[a] != r[b] ? r[a] < r[b] : a < b); });
+         sb.rowmap[i].resize(u);
+         for (size_t row = 0; row < u; row++) { sb.rowmap[i][by[row]] = (unsigned int)row; son_rows[i][row] = l[by[row]]; son_rows[i][u + row] = r[by[row]]; }
+      }
+      else { std::copy(l.begin(), l.end(), son_rows[i].begin()); std::copy(r.begin(), r.end(), son_rows[i].begin() + u); }
+   }
    std::vector<SubtreeNodeDev> nodes(ns);
    std::vector<unsigned int> sidx;
    for (int k = 0; k < ns; k++) {
@@ -420,7 +449,7 @@ int ensure_subtree(paml_amd_engine *e, int K, int tp)
       nd.rkind = st.r.kind; nd.rid = st.r.kind == 2 ? row0[st.r.id] : st.r.id;
       nd.pad = 0;
       nd.sidx = (long)sidx.size();
-      sidx.insert(sidx.end(), sb.son_cls[st.node].begin(), sb.son_cls[st.node].end());      // [2][u]
+      sidx.insert(sidx.end(), son_rows[by_level[k]].begin(), son_rows[by_level[k]].end());      // [2][u]
    }
    std::vector<int> meta;
    for (int ti : sb.sp.top) { meta.push_back(row0[ti]); meta.push_back((int)sb.u[sb.sp.sub[ti].node]); }
@@ -432,6 +461,8 @@ int ensure_subtree(paml_amd_engine *e, int K, int tp)
 }
 
 // The tile blocks of the kernel with subtree tables: the current 128-pattern tile table's, with the class-index rows of the walk's lookups.
+// Unless PAML_AMD_SUBTREE_ORDER=0 a tile holds the patterns order[first .. first + 127] of subtree_pattern_order (subtree_classes.h) over the
+// classes of all the walk's lookups — subtree tables and cherry tables alike —, computed here once per selection, never per evaluation.
 int ensure_subtree_ztiles(paml_amd_engine *e)
 {
    paml_amd_engine::Subtree &sb = e->sub;
@@ -439,14 +470,37 @@ int ensure_subtree_ztiles(paml_amd_engine *e)
    const int n_top = (int)sb.sp.top.size();
    std::vector<unsigned int> top((size_t)n_top * e->n_patt);
    for (int k = 0; k < n_top; k++) {
-      const std::vector<unsigned int> &c = sb.cls[sb.sp.sub[sb.sp.top[k]].node];
-      std::copy(c.begin(), c.end(), top.begin() + (size_t)k * e->n_patt);
+      const std::vector<unsigned int> &c = sb.cls[sb.sp.sub[sb.sp.top[k]].node], &rm = sb.rowmap[sb.sp.top[k]];
+      if (rm.empty()) std::copy(c.begin(), c.end(), top.begin() + (size_t)k * e->n_patt);
+      else for (long h = 0; h < e->n_patt; h++) top[(size_t)k * e->n_patt + h] = rm[c[h]];
+   }
+   sb.ordered = e->env.subtree_order != 0;
+   if (sb.ordered && sb.order_sel_gen != sb.sel_gen) {
+      const auto t0 = std::chrono::steady_clock::now();
+      std::vector<const unsigned int *> keys;
+      std::vector<unsigned int> bound;
+      for (int k = 0; k < n_top; k++) { keys.push_back(top.data() + (size_t)k * e->n_patt); bound.push_back(sb.u[sb.sp.sub[sb.sp.top[k]].node]); }
+      std::vector<std::vector<unsigned int>> cherry_cls;      // the walk's cherry lookups: row ca * n_codes + cb
+      for (const Op &o : sb.sp.prog.ops)
+         if (o.code == OP_LOOKUP && o.c < SUBTREE_TAB_BASE) {
+            const CherryTab &ct = sb.sp.tabs[o.c];
+            const unsigned char *za = e->h_z.data() + (size_t)ct.tip_a * e->n_patt, *zb = e->h_z.data() + (size_t)ct.tip_b * e->n_patt;
+            cherry_cls.emplace_back(e->n_patt);
+            for (long h = 0; h < e->n_patt; h++) cherry_cls.back()[h] = (unsigned int)za[h] * e->n_codes + zb[h];
+         }
+      for (const std::vector<unsigned int> &c : cherry_cls) { keys.push_back(c.data()); bound.push_back((unsigned int)(e->n_codes * e->n_codes)); }
+      const std::vector<unsigned int> order = subtree_pattern_order(keys, bound, subtree_order_sequence(bound, e->env.subtree_order == 2), (long)e->n_patt);
+      sb.order_host_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      HIPCHK(upload(sb.d_order, (const int *)order.data(), order.size(), e->stream));
+      HIPCHK(hipStreamSynchronize(e->stream));      // (the host array goes)
+      sb.order_sel_gen = sb.sel_gen;
+      sb.n_order_computed++;
    }
    sb.zt_bytes = jit_zpieces(jit_subtree_zrows(e->n_tips, n_top), e->tile_patt) * 2048;
    HIPCHK(upload(sb.d_top_cls, top.data(), top.size(), e->stream));
    HIPCHK(sb.d_ztiles.ensure((size_t)e->n_tiles * sb.zt_bytes));
    hipLaunchKernelGGL(sztile_kernel, dim3(e->n_tiles), dim3(e->tile_patt), 0, e->stream, e->d_tiles.p, e->d_gene_off.p, e->d_z.p, (long)e->n_patt, e->d_weights.p,
-                      e->n_tips, sb.zt_bytes, sb.d_ztiles.p, n_top, sb.d_top_cls.p);
+                      e->n_tips, sb.zt_bytes, sb.d_ztiles.p, n_top, sb.d_top_cls.p, sb.ordered ? sb.d_order.p : nullptr);
    HIPCHK(hipStreamSynchronize(e->stream));
    sb.d_top_cls.release();
    sb.zt_sel_gen = sb.sel_gen; sb.zt_tiles = e->n_tiles; sb.zt_tile_patt = e->tile_patt;
@@ -508,9 +562,11 @@ int choose_kernel(paml_amd_engine *e, const Eval &c, PruneKernel *out)
                std::string skey = "s";
                for (int v : e->sub.sel) skey += std::to_string(v) + ".";
                skey += "t" + std::to_string(n_tab) + key;
+               const bool ordered = e->env.subtree_order != 0;      // (the walk stores at order[position]: another kernel)
+               if (ordered) skey = "o" + skey;
                bool ok = false;
                const int n_top = (int)e->sub.sp.top.size();
-               if (int r = obtain_kernel(e, e->jit_slot, &e->jit, true, skey, [&]() { return jit_generate(e->sub.sp.prog, e->n_tips, n, e->n_codes, &e->sub.sp.tabs, n_top); },
+               if (int r = obtain_kernel(e, e->jit_slot, &e->jit, true, skey, [&]() { return jit_generate(e->sub.sp.prog, e->n_tips, n, e->n_codes, &e->sub.sp.tabs, n_top, ordered); },
                                          (e->prog.ops.size() > 120 && !e->jit_forced && !e->env.jit_sync) ? JIT_WAIT_WORKER : JIT_WAIT_CALLER, "tree, subtree tables", &ok)) return r;
                if (ok) { jit_ok = true; e->n_ctab = n_tab; e->n_stab = (int)e->sub.sel.size(); }
             }
@@ -699,15 +755,18 @@ int run_pmat(paml_amd_engine *e, Eval &c, const InlineVec &iv)
       sa.n_codes = e->n_codes; sa.n_nodes = nn; sa.n_ctab = e->n_ctab; sa.tip_words = (long)tip_words(e); sa.stab_rows = sb.rows;
       sa.pint = e->d_pint.p; sa.ptip = e->d_ptip.p; sa.pcol = e->d_pcol.p; sa.ctab = e->d_ctab.p;
       sa.nodes = sb.d_nodes.p; sa.sidx = sb.d_sidx.p; sa.stab = e->d_stab.p;
-      const size_t lds = (size_t)(3 * 4096 + 64) * sizeof(double);
+      // (a level none of whose nodes has a tip son: the P block and the column table only, several workgroups per CU)
+      const size_t lds_full = (size_t)(3 * 4096 + 64) * sizeof(double), lds_small = (size_t)(4096 + 64) * sizeof(double);
       if (!e->stab_attr_set) {
-         HIPCHK(hipFuncSetAttribute((const void *)subtree_table_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-         HIPCHK(hipFuncSetAttribute((const void *)subtree_table_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-         HIPCHK(hipFuncSetAttribute((const void *)subtree_table_kernel<false, 15>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+         HIPCHK(hipFuncSetAttribute((const void *)subtree_table_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_full));
+         HIPCHK(hipFuncSetAttribute((const void *)subtree_table_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_full));
+         HIPCHK(hipFuncSetAttribute((const void *)subtree_table_kernel<false, 15>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_full));
          e->stab_attr_set = true;
       }
       for (int l = 0; l < sb.sp.levels; l++) {
          sa.first = sb.level_first[l];
+         sa.small = sb.level_small[l] ? 1 : 0;
+         const size_t lds = sa.small ? lds_small : lds_full;
          const dim3 g(sb.level_tiles[l], sb.level_first[l + 1] - sb.level_first[l], c.K);
          if (e->n == 61) hipLaunchKernelGGL(subtree_table_kernel<true>, g, dim3(512), lds, c.ps, sa);
          else if (e->n == 60) hipLaunchKernelGGL((subtree_table_kernel<false, 15>), g, dim3(512), lds, c.ps, sa);
@@ -805,6 +864,7 @@ int run_prune(paml_amd_engine *e, Eval &c)
    if (k == PK_MFMA64_JIT && e->n_stab) {      // (... its subtree tables, and the tile blocks with the class-index rows)
       pr.stab = e->d_stab.p; pr.stab_rows = e->sub.rows; pr.stab_meta = e->sub.d_meta.p;
       pr.ztiles = e->sub.d_ztiles.p; pr.zt_bytes = e->sub.zt_bytes;
+      pr.order = e->sub.ordered ? e->sub.d_order.p : nullptr;
    }
    const int nb = (e->n_patt + e->chunk - 1) / e->chunk;      // the reduction's geometry: chunks of this engine
    if (pk_forms_reduction(k)) {      // (the others leave the partial sums to reduce_stage1)

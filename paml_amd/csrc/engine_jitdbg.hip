@@ -194,6 +194,24 @@ int paml_amd_debug_subtree_classes(int n_tips, int n_nodes, int root, const int 
    return 0;
 }
 
+// subtree_pattern_order (subtree_classes.h) for n_keys class arrays keys[n_keys][n_patt] with bound[k] > every entry of keys[k]: the
+// engine's sequence of the keys (largest_first: the other one), or the keys in the order given (as_given).  order_out[n_patt].
+int paml_amd_debug_subtree_order(int n_keys, const unsigned int *keys, const unsigned int *bound, long n_patt, int largest_first, int as_given,
+                                 unsigned int *order_out)
+{
+   if (n_keys < 0 || n_patt < 1 || (n_keys && (!keys || !bound)) || !order_out) return PAML_AMD_EINVAL;
+   std::vector<const unsigned int *> k(n_keys);
+   std::vector<unsigned int> b(n_keys);
+   std::vector<int> seq(n_keys);
+   for (int i = 0; i < n_keys; i++) { k[i] = keys + (long)i * n_patt; b[i] = bound[i]; seq[i] = i; }
+   for (long i = 0; i < (long)n_keys * n_patt; i++)
+      if (keys[i] >= bound[i / n_patt]) return PAML_AMD_EINVAL;
+   if (!as_given) seq = subtree_order_sequence(b, largest_first != 0);
+   const std::vector<unsigned int> order = subtree_pattern_order(k, b, seq, n_patt);
+   memcpy(order_out, order.data(), (size_t)n_patt * sizeof(unsigned int));
+   return 0;
+}
+
 // The nodes an engine of these sizes (one gene, K classes, the switches of the environment) tabulates above the cherries for tip codes
 // z[n_tips][n_patt]: the classes, then jit_subtree_select with the engine's limits.  Returns their number (sel_out: the first `cap`).
 int paml_amd_debug_subtree_select(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node, int n_states,
@@ -247,7 +265,7 @@ int paml_amd_debug_jit_subtree(int n_tips, int n_nodes, int root, const int *son
    const SubtreeProgram sp = jit_subtree_program(p, n_tab, t, ok);
    if (sp.top.empty() || !jit_subtree_zfits(n_tips, (int)sp.top.size())) return 0;
    if (blocks_left) *blocks_left = (int)sp.prog.stream.size() / 2;
-   std::string text = jit_generate(sp.prog, n_tips, n_states, n_codes, &sp.tabs, (int)sp.top.size());
+   std::string text = jit_generate(sp.prog, n_tips, n_states, n_codes, &sp.tabs, (int)sp.top.size(), env.subtree_order != 0);      // (the engine's form)
    int rc = (int)text.size();
    if (compile) {
       std::vector<char> code;

@@ -213,6 +213,11 @@ struct EnvCfg {
    int subtree_tables = -1;
    double subtree_max_frac = 0.5;
    long subtree_cap_mb = 2048;
+   // the tabulated walk visits the patterns sorted by their classes (subtree_classes.h: subtree_pattern_order) wherever
+   // subtree tables run.  PAML_AMD_SUBTREE_ORDER=0: the alignment's order; 1 (the default): smallest table first; 2: largest table first
+   // (measurements)
+   int subtree_order = 1;
+   int subtree_rows = 1;      // a table's rows lie in lexicographic order of (left son row, right son row); PAML_AMD_SUBTREE_ROWS=0: in order of first occurrence
    std::string jit_dump, prof_ops;
    int prof_tid = 0;
    bool prof_tiles = false;      // the dump is a workgroup timeline (jit.h proft) instead of per-op stamps
@@ -236,6 +241,8 @@ struct EnvCfg {
       if (const char *v = getenv("PAML_AMD_SUBTREE_TABLES")) subtree_tables = atoi(v) != 0 ? 1 : 0;
       if (const char *v = getenv("PAML_AMD_SUBTREE_MAX_FRAC")) subtree_max_frac = std::max(0.0, atof(v));
       if (const char *v = getenv("PAML_AMD_SUBTREE_CAP_MB")) subtree_cap_mb = std::max(0L, atol(v));
+      if (const char *v = getenv("PAML_AMD_SUBTREE_ORDER")) subtree_order = std::max(0, std::min(2, atoi(v)));
+      if (const char *v = getenv("PAML_AMD_SUBTREE_ROWS")) subtree_rows = atoi(v) != 0 ? 1 : 0;
       if (const char *v = getenv("PAML_AMD_JIT_DUMP")) jit_dump = v;
       if (const char *v = getenv("PAML_AMD_PROF_OPS")) prof_ops = v;
       if (const char *v = getenv("PAML_AMD_PROF_TID")) prof_tid = atoi(v);
@@ -427,6 +434,13 @@ struct paml_amd_engine {
       std::vector<int> level_tiles;           // 128-class tiles of the level's largest node
       long rows = 0;                          // rows of all tables, per class of the model
       long n_computed = 0;
+      long n_order_computed = 0;              // pattern orders computed so far (once per selection)
+      bool ordered = false;                   // the tile blocks hold the patterns in the order d_order (else: the alignment's order)
+      std::vector<std::vector<unsigned int>> rowmap;      // per sp.sub entry: class -> row of its table (empty: the class number itself)
+      std::vector<char> level_small;          // no node of the level has a tip son: the builder's LDS is the P block and the column table
+      DevBuf<int> d_order;                    // [n_patt]: position -> pattern
+      long order_sel_gen = -1;                // the selection d_order was computed for
+      double order_host_s = 0;                // host time of the last order computation
       int zt_bytes = 0;
       DevBuf<SubtreeNodeDev> d_nodes;
       DevBuf<unsigned int> d_sidx, d_top_cls;
@@ -631,7 +645,7 @@ struct paml_amd_engine {
       d_pres.release();
       d_ctab.release();
       d_stab.release();
-      sub.d_nodes.release(); sub.d_sidx.release(); sub.d_top_cls.release(); sub.d_meta.release(); sub.d_ztiles.release();
+      sub.d_nodes.release(); sub.d_sidx.release(); sub.d_top_cls.release(); sub.d_meta.release(); sub.d_ztiles.release(); sub.d_order.release();
       d_eq_q.release(); d_eq_pi.release(); d_eq_scale.release(); d_eq_ptr.release(); d_eq_rc.release(); d_eq_sweeps.release();
       d_pi_plain.release();
       DevBuf<double> *b3[] = {&d_weights, &d_pi, &d_freqK, &d_rate, &d_qfactor, &d_branch, &d_gene_rate, &d_rowmajor,

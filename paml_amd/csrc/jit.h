@@ -459,6 +459,7 @@ struct JitWalk {
    const std::vector<CherryTab> *const tabs;
    const JitProf &prof;
    const int n_top;      // subtree tables: lookups of the walk that read one (their class indices are rows of the tile's code block)
+   const bool ordered;   // ... and the tiles hold the patterns in the order PruneArgs::order: the root stores at order[position]
    static constexpr int waves = 8, TP = waves * 16;
    const int nblk = (int)p.stream.size() / 2;
    const size_t nops = p.ops.size();
@@ -533,8 +534,8 @@ struct JitWalk {
    int lk_issued = 0, lk_seen = 0;           // lookups of this tile requested / consumed so far
    bool lk_next_done = false;                // the next tile's first lookups are requested
 
-   JitWalk(const Program &p_, int n_tips_, int n_states_, int n_codes_, int first_, const std::vector<CherryTab> *tabs_, const JitProf &prof_, int n_top_ = 0)
-      : p(p_), n_tips(n_tips_), n_states(n_states_), n_codes(n_codes_), first(first_), tabs(tabs_), prof(prof_), n_top(n_top_) {}
+   JitWalk(const Program &p_, int n_tips_, int n_states_, int n_codes_, int first_, const std::vector<CherryTab> *tabs_, const JitProf &prof_, int n_top_ = 0, bool ordered_ = false)
+      : p(p_), n_tips(n_tips_), n_states(n_states_), n_codes(n_codes_), first(first_), tabs(tabs_), prof(prof_), n_top(n_top_), ordered(ordered_ && n_top_ > 0) {}
 
    // ---- text of the operands ----
    int n_rounds(int blk) const { return p.stream[2 * (blk % nblk)] ? T_ROUNDS : P_ROUNDS; }
@@ -734,6 +735,7 @@ struct JitWalk {
       if (prof.tiles) s << "   int ptc = 0; if (a.prof && tid == 0) { a.prof[(long)blockIdx.x * a.prof_stride] = __builtin_amdgcn_s_memrealtime(); a.prof[(long)blockIdx.x * a.prof_stride + a.prof_stride - 2] = __builtin_amdgcn_s_memtime(); }\n";
       s << "   int ptile = 1;\n   for (;; ptile = 0) {\n";
       s << "   JIT2_ADVANCE(" << nblk << ")\n";
+      if (ordered) s << "   JIT2_ORDER()\n";
       // (n_tile is still this tile's number here; the groups of a tile's waves that start past its gene's end belong to nobody: not stored)
       if (resident) s << "   const int tg0 = as_const(a.tile_group0)[n_tile];\n   const bool wave_in = h0 + wave * 16 < hend;\n";
       if (zhalf) s << "   const int cur_tile = n_tile;\n";
@@ -893,7 +895,7 @@ struct JitWalk {
       if (resident)
          s << "   if (a.keep && a.n_scale) { lnscale = 0; if (valid) for (int k_ = 0; k_ < a.n_scale; k_++) lnscale += a.scalef[((long)iclass * a.n_scale + k_) * a.n_patt + h]; }\n";
       s << "   jit_root_lds(a, " << regs.cur.name() << ", lnscale, sPi + (a.n_pi > 1 ? gene : 0) * 64, " << code(n_tips)
-        << ", iclass, q, h, valid);\n";
+        << ", iclass, q, " << (ordered ? "hs" : "h") << ", valid);\n";
       regs.end_partial();
    }
 
@@ -927,15 +929,17 @@ struct JitWalk {
 };
 
 // (`tabs`: p is the table form of the tree's program — jit_cherry_program — and these are its tables)
-// (n_top: p is the table form with subtree tables — jit_subtree_program — and so many of its lookups read one)
-inline std::string jit_generate(const Program &p, int n_tips, int n_states = 61, int n_codes = 64, const std::vector<CherryTab> *tabs = nullptr, int n_top = 0)
+// (n_top: p is the table form with subtree tables — jit_subtree_program — and so many of its lookups read one; ordered: its tiles hold the
+//  patterns in the order PruneArgs::order)
+inline std::string jit_generate(const Program &p, int n_tips, int n_states = 61, int n_codes = 64, const std::vector<CherryTab> *tabs = nullptr, int n_top = 0,
+                                bool ordered = false)
 {
    const JitProf prof;
    int first = std::min(3, (int)p.stream.size() / 2), got = first;
-   std::string src = JitWalk(p, n_tips, n_states, n_codes, first, tabs, prof, n_top).generate(&got);
+   std::string src = JitWalk(p, n_tips, n_states, n_codes, first, tabs, prof, n_top, ordered).generate(&got);
    if (got != first) {
       first = got;
-      src = JitWalk(p, n_tips, n_states, n_codes, first, tabs, prof, n_top).generate(&got);
+      src = JitWalk(p, n_tips, n_states, n_codes, first, tabs, prof, n_top, ordered).generate(&got);
    }
    if (got != first) return std::string("#error \"jit schedule does not close\"\n");
    return src;

@@ -70,6 +70,7 @@ struct SubtreeNodeDev {
 };
 struct SubtreeTabArgs {
    int n_codes, n_nodes, n_ctab, first;   // first: the level's first node in `nodes` (blockIdx.y counts from it)
+   int small;                             // no node of the level has a tip son: the LDS holds the P block and the column table only
    long tip_words, stab_rows;
    const double *pint, *ptip, *pcol, *ctab;   // this evaluation's P set and its cherry tables
    const SubtreeNodeDev *nodes;

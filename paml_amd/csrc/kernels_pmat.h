@@ -533,11 +533,16 @@ __global__ __launch_bounds__(512) void cherry_table_kernel(CherryTabArgs a)
 // then jit_x60 and jit_matvec with the node's P block and column table in LDS — the walk's functions, so an entry has the bits the walk
 // would compute for a pattern of that class.  A wave takes 16 classes.  Grid: (128-class tiles of the level's largest node, nodes of the
 // level, classes of the model); one launch per level, on the P(t) stream behind the cherry builder.
+// LDS: the P block, two tip tables and the column table — or, for a level none of whose nodes has a tip son (a.small), the P block and the
+// column table only: 33 KB instead of 97, so that several workgroups fit on a CU (100 VGPRs at 61 states: four waves per SIMD, two
+// workgroups).  A workgroup that takes several tiles of its node with the next tile's rows requested under the current tile's product
+// was measured and left out: its 214 VGPRs allow one workgroup per CU and none beside the walk's, and although a level ran faster alone
+// (41 against 50 us) the headline step was slower with it, 0.265 against 0.247 ms (profiles/pattern_order_bench.txt).
 template <bool TAIL61, int KB = 16>
 __global__ __launch_bounds__(512) void subtree_table_kernel(SubtreeTabArgs a)
 {
    extern __shared__ __attribute__((aligned(16))) double st_lds[];
-   double *sP = st_lds, *sA = st_lds + 4096, *sB = st_lds + 8192, *sC = st_lds + 12288;
+   double *sP = st_lds, *sA = st_lds + 4096, *sB = st_lds + 8192, *sC = st_lds + (a.small ? 4096 : 12288);
    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, hl = lane & 15;
    const SubtreeNodeDev nd = a.nodes[a.first + blockIdx.y];
    const int cls = blockIdx.z, nc = a.n_codes;

@@ -789,22 +789,25 @@ __global__ __launch_bounds__(256) void ztile_kernel(const int2 *tiles, const int
 
 // The tile blocks of the per-tree kernel with subtree tables (jit.h: SubtreeProgram): ztile_kernel's rows in tip order, one block, and
 // behind the weight flags three byte rows per lookup of the walk that reads a subtree table — the pattern's class at that node
-// (top_cls[t][n_patt]), low byte first; patterns past the tile's gene read as class 0.
+// (top_cls[t][n_patt]), low byte first; patterns past the tile's gene read as class 0.  order (null: the identity): slot i of the tile
+// holds pattern order[first + i] — the walk stores that pattern's value at its own place (PruneArgs::order).
 __global__ __launch_bounds__(256) void sztile_kernel(const int2 *tiles, const int *gene_off, const unsigned char *z, long z_stride, const double *weights,
-                                                     int n_tips, int zt_bytes, unsigned char *out, int n_top, const unsigned int *top_cls)
+                                                     int n_tips, int zt_bytes, unsigned char *out, int n_top, const unsigned int *top_cls, const int *order)
 {
    const int t = blockIdx.x, i = threadIdx.x, tp = blockDim.x;
-   const int g = tiles[t].x, h = tiles[t].y + i, hend = gene_off[g + 1];
+   const int g = tiles[t].x, pos = tiles[t].y + i, hend = gene_off[g + 1];
+   const bool in = pos < hend;
+   const int h = in ? (order ? order[pos] : pos) : 0;
    unsigned char *o = out + (long)t * zt_bytes;
    for (int k = i; k < zt_bytes; k += tp) o[k] = 0;
    __syncthreads();
    for (int r = 0; r <= n_tips; r++) {
       unsigned char v = 0;
-      if (h < hend) v = r < n_tips ? z[r * z_stride + h] : (unsigned char)(weights[h] > 0 ? 1 : 0);
+      if (in) v = r < n_tips ? z[r * z_stride + h] : (unsigned char)(weights[h] > 0 ? 1 : 0);
       o[(long)r * tp + i] = v;
    }
    for (int k = 0; k < n_top; k++) {
-      const unsigned int c = h < hend ? top_cls[(long)k * z_stride + h] : 0u;
+      const unsigned int c = in ? top_cls[(long)k * z_stride + h] : 0u;
       for (int b = 0; b < 3; b++) o[(long)(n_tips + 1 + 3 * k + b) * tp + i] = (unsigned char)((c >> (8 * b)) & 255u);
    }
 }

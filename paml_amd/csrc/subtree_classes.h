@@ -10,6 +10,7 @@
 // tree), never per evaluation.
 #pragma once
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 namespace paml_amd {
@@ -125,6 +126,39 @@ inline SubtreeClasses subtree_classes(int n_tips, int n_nodes, int root, const i
       sc.done[v] = 1;
    }
    return sc;
+}
+
+// The order the tabulated walk visits the patterns in (kernels_prune.h: sztile_kernel; jit.h: the table form's root).  The walk gathers one
+// table row per lookup and pattern; patterns of one class read the same row, so neighbours in this order should share classes.  keys[k]
+// [n_patt] are the class arrays of the walk's lookups, bound[k] > every entry of keys[k]; the result is the lexicographic sort of the
+// patterns by (keys[seq[0]], keys[seq[1]], ...), ties broken by the pattern number: order[position] = pattern, a permutation of
+// 0 .. n_patt - 1 and a function of its arguments alone.  One stable counting sort per key, the last of the sequence first.
+inline std::vector<uint32_t> subtree_pattern_order(const std::vector<const uint32_t *> &keys, const std::vector<uint32_t> &bound, const std::vector<int> &seq,
+                                                   long n_patt)
+{
+   std::vector<uint32_t> order(n_patt > 0 ? n_patt : 0), next(order.size());
+   for (long h = 0; h < n_patt; h++) order[h] = (uint32_t)h;
+   for (size_t s = seq.size(); s-- > 0;) {
+      const uint32_t *key = keys[seq[s]];
+      std::vector<uint32_t> start((size_t)bound[seq[s]] + 1, 0);
+      for (long h = 0; h < n_patt; h++) start[(size_t)key[h] + 1]++;
+      for (size_t c = 1; c < start.size(); c++) start[c] += start[c - 1];
+      for (long i = 0; i < n_patt; i++) next[start[key[order[i]]]++] = order[i];
+      order.swap(next);
+   }
+   return order;
+}
+
+// The sequence of the keys: by ascending number of classes (the smallest table first: its rows change least often along the order, the
+// largest table's rows are then met in runs inside every run of the others), equal counts in the order given; `largest_first` reverses it.
+inline std::vector<int> subtree_order_sequence(const std::vector<uint32_t> &n_classes, bool largest_first = false)
+{
+   std::vector<int> seq(n_classes.size());
+   for (size_t i = 0; i < seq.size(); i++) seq[i] = (int)i;
+   for (size_t i = 1; i < seq.size(); i++)      // (insertion sort: a handful of keys, stable)
+      for (size_t j = i; j > 0 && (largest_first ? n_classes[seq[j]] > n_classes[seq[j - 1]] : n_classes[seq[j]] < n_classes[seq[j - 1]]); j--)
+         std::swap(seq[j], seq[j - 1]);
+   return seq;
 }
 
 }  // namespace paml_amd

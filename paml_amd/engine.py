@@ -30,7 +30,7 @@ EXPORTS = [
     "paml_amd_device_count", "paml_amd_set_device", "paml_amd_shard_bounds", "paml_amd_max_ranks", "paml_amd_flush", "paml_amd_eigen_status", "paml_amd_comm_unique_id", "paml_amd_comm_init", "paml_amd_comm_destroy", "paml_amd_comm_info", "paml_amd_comm_library", "paml_amd_comm_stats", "paml_amd_get_partial_sums", "paml_amd_branch_counters", "paml_amd_branch_coef_hits", "paml_amd_branch_refill_kernels", "paml_amd_branch_kernel_ms",
     "paml_amd_jit_prebuild", "paml_amd_profile", "paml_amd_profile_read", "paml_amd_counters", "paml_amd_kernel_name", "paml_amd_debug_program", "paml_amd_debug_jit",
     "paml_amd_cherry_tables", "paml_amd_debug_jit_tables",
-    "paml_amd_subtree_tables", "paml_amd_debug_subtree_classes", "paml_amd_debug_jit_subtree", "paml_amd_debug_subtree_select",
+    "paml_amd_subtree_tables", "paml_amd_subtree_order", "paml_amd_debug_subtree_order", "paml_amd_debug_subtree_classes", "paml_amd_debug_jit_subtree", "paml_amd_debug_subtree_select",
     "paml_amd_debug_code_order", "paml_amd_debug_branch_plan",
     "paml_amd_pairset_create", "paml_amd_pairset_destroy", "paml_amd_pairset_get_counts", "paml_amd_pairset_set_pi", "paml_amd_pairset_set_pattern",
     "paml_amd_pairset_eval", "paml_amd_pairset_failed", "paml_amd_pairset_counters",
@@ -583,6 +583,14 @@ class Engine:
         k = min(n.value, cap)
         return dict(nodes=nodes[:k].tolist(), u=u[:k].tolist(), bytes=by.value, blocks_left=bl.value, n_computed=nc.value)
 
+    def subtree_order(self):
+        """The pattern order of the walk with subtree tables: dict(in_use — the last evaluation ran with it —, n_computed — order
+        computations of this engine so far —, host_seconds of the last one)."""
+        use, nc, sec = C.c_int(), C.c_long(), C.c_double()
+        self._L.paml_amd_subtree_order.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_double)]
+        self._chk(self._L.paml_amd_subtree_order(self._h, C.byref(use), C.byref(nc), C.byref(sec)))
+        return dict(in_use=bool(use.value), n_computed=nc.value, host_seconds=sec.value)
+
     def counters(self):
         a, b = C.c_long(), C.c_long()
         self._L.paml_amd_counters(self._h, C.byref(a), C.byref(b))
@@ -810,6 +818,20 @@ def debug_subtree_classes(tree, z, n_codes, want_classes=False):
     if rc < 0:
         raise EngineError("debug_subtree_classes failed (%d)" % rc)
     return (u, cls) if want_classes else u
+
+
+def debug_subtree_order(keys, bound, largest_first=False, as_given=False):
+    """Host-only: the pattern order (csrc/subtree_classes.h: subtree_pattern_order) for class arrays keys[n_keys][n_patt] below bound[n_keys]:
+    order[position] = pattern, sorted by the engine's sequence of the keys (or, as_given, by the keys in the order given)."""
+    L = lib()
+    keys = np.ascontiguousarray(keys, dtype=np.uint32)
+    bound = np.ascontiguousarray(bound, dtype=np.uint32)
+    out = np.zeros(keys.shape[1], dtype=np.uint32)
+    L.paml_amd_debug_subtree_order.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]
+    rc = L.paml_amd_debug_subtree_order(keys.shape[0], _p(keys), _p(bound), keys.shape[1], int(largest_first), int(as_given), _p(out))
+    if rc < 0:
+        raise EngineError("debug_subtree_order failed (%d)" % rc)
+    return out
 
 
 def debug_subtree_select(tree, z, n_states, n_codes, K=1, scale_node=None):
