@@ -585,6 +585,41 @@ int paml_amd_placement_scores(paml_amd_engine *e, const double *branch, const do
  * (ms, summed); either pointer may be NULL. */
 void paml_amd_placement_info(int *last_batches, double *last_kernel_ms);
 
+/* ---- Subtree prune and regraft: the lnL of every requested SPR neighbour of the tree at the present branch lengths in ONE call.  A move
+ * is (s, x) with a split phi in [0, 1]: f = father(s), g = father(f), c = the other son of f.  The subtree below s leaves with f; c takes
+ * f's place under g on a branch of length t_c + t_f with c's label; f takes x's place under x's father with the sons (x, s), the branch
+ * above f has length (1 - phi) t_x and x's label, the branch above x phi t_x.  Node ids, n_nodes and the root stay and the tree's length is
+ * unchanged.  A move is valid when s is not the root, f is not the root and has exactly two sons, x is not the root, not f, not c (the same
+ * topology) and not in the subtree below s.  Out of scope: pruning the side of a branch that holds the root (it would reverse branches),
+ * and a prune whose father is the root or a polytomy.  lnL[i] and lnf[i][h] are what paml_amd_eval returns for the rearranged tree as
+ * rooted, to rounding, without regard to where that tree's own scaling marks would sit (the definition: kernels_spr.h); *lnL0 is the
+ * present tree's lnL, taken as paml_amd_gradient takes it.  One down pass and one outer pass, then per pruned s the products up the path
+ * from g to the root, the outward chain over the nodes that lead to its targets, and two products and one dot product per target: no tree
+ * is set and no kernel is built per neighbour.  Everything paml_amd_nni_scores takes is served — K classes, several genes, branch labels,
+ * ambiguity codes, polytomies elsewhere in the tree, scaling nodes, a root that is a tip, at most 64 states, rate-matrix (UNREST) sets —
+ * and the side effects are the same: the engine holds P(t) of the tree at `branch` afterwards, eval_branch's resident state starts over,
+ * a following paml_amd_eval keeps its bits.  n_patt is walked gene by gene in batches of what a workspace holds (256 MiB; the environment
+ * variable PAML_AMD_SPR_ARENA_MB, read at every call, gives another size in MiB).  The moves are walked in groups of whole s in two
+ * cases: where one tile of patterns with the rows of all moves does not fit, and where those rows would leave a batch less than half
+ * the patterns that the partials alone allow (a list of many moves would otherwise cut the batches short).  Every output has the same
+ * bits for any workspace size, for any sub-list or order of the moves and on every call (fixed-order sums, no atomics).
+ * PAML_AMD_EINVAL (with a message starting "spr_scores", naming "move i" for a bad move)
+ * for a null branch, moves, lnL0 or lnL, n_moves < 1, phi outside [0, 1] or not finite, a move that is not valid or names a node out of
+ * range, a model or tips not set; PAML_AMD_EUNSUPPORTED for tips that are not the nodes 0 .. n_tips - 1, more than 64 states, an engine
+ * whose communicator has more than one rank; PAML_AMD_ENOCONV as the other synchronous entries. */
+int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, const double *gene_rate,
+                        int n_moves, const int *moves /* [n_moves][2] = s, x */, double phi,
+                        double *lnL0, double *lnL /* [n_moves] */, double *lnf /* [n_moves][n_patt], or NULL */);
+/* The number of pattern batches the calling thread's last paml_amd_spr_scores walked and the time of its kernels by HIP events (ms,
+ * summed); either pointer may be NULL. */
+void paml_amd_spr_info(int *last_batches, double *last_kernel_ms);
+/* The canonical list of moves of a tree given as paml_amd_set_tree takes it, host only (no engine, no device): every valid (s, x) with
+ * d(s, x) <= radius (radius <= 0: no limit), s in node order and x in node order within s.  d is the number of branches, in the tree
+ * without s and f, on the shortest chain of branches from the merged branch above c to the branch above x, x's counted and c's not:
+ * adjacent branches have d = 1, and the trees of the radius-1 list are the NNI neighbours.  Returns the list's length (with moves = NULL
+ * the length only), or PAML_AMD_EINVAL for a bad tree or a list longer than cap. */
+int paml_amd_spr_list(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, int radius, int *moves /* [cap][2], or NULL */, int cap);
+
 /* ---- Pairwise maximum-likelihood comparisons (codeml runmode = -2; PairwiseCodon codeml.c:4344-4604, Goldman & Yang 1994).
  * The reference takes the ns (ns - 1) / 2 pairs one after the other, each a search over (t, kappa, omega) whose every function call
  * (lfun2dSdN codeml.c:4219-4264) decomposes a rate matrix on one core.  Here a PAIR SET lives on an engine whose tips are clean data

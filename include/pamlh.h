@@ -159,6 +159,30 @@ int pamlh_nni_scores(pamlh *p, const double *x, int *n_swaps, int *swaps, double
 int pamlh_apply_nni(pamlh *p, int v, int s, int x);
 int pamlh_nni_search(pamlh *p, double *x, double *lnL, int max_moves, int verbose, int *stats);
 
+/* Subtree prune and regraft (SPR) on the analysis's tree (pamlh_spr.c).  A move is (s, x), 0-based nodes, with a split phi in [0, 1]
+ * (the definition: paml_amd_spr_scores, include/paml_amd.h): the subtree below s leaves with its father f; c, the other son of f, takes
+ * f's place on a branch of length t_c + t_f; f takes x's place with the sons (x, s), the branch above f has length (1 - phi) t_x and x's
+ * label, the branch above x phi t_x.  Valid: s and its father are not the root, the father has exactly two sons, x is not the root, not
+ * f, not c and not below s; pruning the side of a branch that holds the root is out of scope.  All three are refused by name with a
+ * clock, with rho models and for runmode = -2, as the NNI calls.
+ * pamlh_spr_scores: the canonical list of the tree as it stands within `radius` branches of the pruned place (paml_amd_spr_list; <= 0:
+ *   no limit) scored at x in ONE engine call (paml_amd_spr_scores): moves[*n_moves][2], lnL[*n_moves], *lnL0 = the present tree's.  With
+ *   moves = lnL = NULL only *n_moves is written (host only): the room for the list is the caller's.
+ * pamlh_apply_spr: edits son lists, fathers and label[f] in place and rewrites in xvec the three branch lengths of the definition (at c,
+ *   f and x); marks the scaling nodes as for a tree just read and sends the tree to the engine again.  Node ids and pamlh_branch_order
+ *   stay, so the layout of x does not change.  Afterwards the move (s, c) brings the topology back (and with phi = t_c / (t_c + t_f) the
+ *   three lengths).  Refused where the branch lengths are not parameters (fix_blength).
+ * pamlh_spr_search: pamlh_optimize on the present tree; then per step one pamlh_spr_scores (radius, phi = 0.5) at the estimates, the
+ *   candidates in descending order of their screened lnL, at most one per distinct unrooted topology and at most `top` of them (<= 0:
+ *   all), each applied and maximised: the first whose maximised lnL is higher by more than 1e-4 is kept, every other is undone from a
+ *   saved copy of the tree and of x.  It ends after a step in which none of the tried candidates was better, or after max_moves moves
+ *   (<= 0: no limit).  x: start in, estimates on the final tree out.  stats (NULL or 3 entries): moves, screening calls, neighbours
+ *   maximised.  verbose: every accepted move on stdout.  On an error inside a step the candidate is undone too: the analysis is left on
+ *   the last tree the search kept, x holds its estimates, and *lnL and stats are written.  The search keeps no state outside the call. */
+int pamlh_spr_scores(pamlh *p, const double *x, int radius, double phi, int *n_moves, int *moves, double *lnL0, double *lnL);
+int pamlh_apply_spr(pamlh *p, int s, int x, double phi, double *xvec);
+int pamlh_spr_search(pamlh *p, double *x, double *lnL, int radius, int top, int max_moves, int verbose, int *stats);
+
 /* Query sequences placed on every branch of the analysis's tree (pamlh_place.c): the likelihood of the tree with one more tip hung on
  * branch e, for every query, every branch and every pendant length of a grid, from ONE engine call (paml_amd_placement_scores) — the
  * primitive under the reference's stepwise addition (StepwiseAddition treesub.c:4866 on AddSpecies treesub.c:4592, which sets and

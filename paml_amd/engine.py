@@ -40,6 +40,7 @@ EXPORTS = [
     "paml_amd_gradient", "paml_amd_gradient_info",
     "paml_amd_nni_scores", "paml_amd_nni_info", "paml_amd_nni_list",
     "paml_amd_placement_scores", "paml_amd_placement_info",
+    "paml_amd_spr_scores", "paml_amd_spr_info", "paml_amd_spr_list",
 ]
 
 
@@ -54,7 +55,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_nni", "engine_place")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_nni", "engine_place", "engine_spr")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -541,6 +542,25 @@ class Engine:
                                                     int(pendant_label), C.byref(lnL0), _p(lnL), _p(lnf)))
         return dict(lnL0=lnL0.value, edges=ed, lnL=lnL, lnf=lnf)
 
+    def spr_scores(self, branch, gene_rate=None, moves=None, radius=0, phi=0.5, want_lnf=False):
+        """The lnL of subtree-prune-and-regraft neighbours of the tree at `branch` in one call (paml_amd_spr_scores): dict(lnL0 (the
+        present tree's), moves=[n_moves][2] (s, x), lnL=[n_moves], lnf=[n_moves][n_patt] or None).  The subtree below s is hung on the
+        branch above x, which the new node splits into phi t_x (above x) and (1 - phi) t_x (Tree.spr).  moves None: the canonical list
+        (paml_amd_spr_list) of the tree last set, within `radius` branches (radius <= 0: no limit)."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        if moves is None:
+            if getattr(self, "_tree_csr", None) is None:
+                raise EngineError("spr_scores: no tree was set through this object")
+            moves = spr_list(self.n_tips, self.n_nodes, *self._tree_csr, radius=radius)
+        mv = np.ascontiguousarray(moves, dtype=np.int32).reshape(-1, 2)
+        lnL0 = C.c_double()
+        lnL = np.zeros(len(mv))
+        lnf = np.zeros((len(mv), self.n_patt)) if want_lnf else None
+        self._L.paml_amd_spr_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
+        self._chk(self._L.paml_amd_spr_scores(self._h, _p(b), _p(g), len(mv), _p(mv), float(phi), C.byref(lnL0), _p(lnL), _p(lnf)))
+        return dict(lnL0=lnL0.value, moves=mv, lnL=lnL, lnf=lnf)
+
     def get_pmat(self, gene, iclass, node):
         P = np.zeros((self.n, self.n))
         self._chk(self._L.paml_amd_get_pmat(self._h, gene, iclass, node, _p(P)))
@@ -974,6 +994,32 @@ def placement_info():
     L.paml_amd_placement_info.restype = None
     L.paml_amd_placement_info(C.byref(nb), C.byref(ms))
     return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def spr_info():
+    """Batches walked by this thread's last Engine.spr_scores and the time of its kernels by HIP events (paml_amd_spr_info):
+    dict(last_batches, last_kernel_ms)."""
+    L = lib()
+    nb, ms = C.c_int(), C.c_double()
+    L.paml_amd_spr_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.paml_amd_spr_info.restype = None
+    L.paml_amd_spr_info(C.byref(nb), C.byref(ms))
+    return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def spr_list(n_tips, n_nodes, root, sons_ptr, sons, radius=0):
+    """The canonical list of SPR moves of a tree in CSR form (paml_amd_spr_list, host only): int32 [n_moves][2] = s, x, the target
+    branches within `radius` branches of the merged one (radius <= 0: no limit)."""
+    L = lib()
+    ptr, flat = np.ascontiguousarray(sons_ptr, dtype=np.int32), np.ascontiguousarray(sons, dtype=np.int32)
+    L.paml_amd_spr_list.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    n = L.paml_amd_spr_list(int(n_tips), int(n_nodes), int(root), _p(ptr), _p(flat), int(radius), None, 0)
+    if n < 0:
+        raise EngineError("paml_amd_spr_list failed (%d): not a tree" % n)
+    mv = np.zeros((n, 2), dtype=np.int32)
+    if n and L.paml_amd_spr_list(int(n_tips), int(n_nodes), int(root), _p(ptr), _p(flat), int(radius), _p(mv), n) != n:
+        raise EngineError("paml_amd_spr_list: the list changed its length")
+    return mv
 
 
 def nni_list(n_tips, n_nodes, root, sons_ptr, sons):

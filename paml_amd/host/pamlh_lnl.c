@@ -1,5 +1,5 @@
 /* pamlh_lnl — command-line driver: one likelihood evaluation of a codeml/baseml analysis on the MI355X.
- *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
+ *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
  *   (--set "key = value": replaces an option of the control file, e.g. one of the site models of an "NSsites = 0 1 2 7 8" list;
  *    --tree K: the K-th tree of the tree file, 1-based; --all-trees: every tree in turn — the reference's loop, Forestry codeml.c:635 —
  *    each optimised from the control file's initial values, then the comparison table of rell(), treesub.c:5844;
@@ -13,6 +13,11 @@
  *    of v's father), their lnL at the parameter vector from one engine call and the difference to the present tree's;
  *    --nni-search [--max-moves N]: the NNI hill climb of the reference's runmode = 5 from the tree of the tree file (pamlh_nni_search):
  *    every accepted move, then the tree found with its estimates and lnL)
+ *    --spr-scores [--radius R] [--split PHI]: the table of the tree's subtree-prune-and-regraft neighbours (s, x: the subtree below node s
+ *    regrafted on the branch above node x, which the new node splits at PHI) within R branches (default: no limit), their lnL at the
+ *    parameter vector from one engine call and the difference to the present tree's;
+ *    --spr-search [--radius R] [--top N] [--max-moves N]: the SPR hill climb from the tree of the tree file (pamlh_spr_search), at most N
+ *    candidates maximised per step: every accepted move, then the tree found with its estimates and lnL
  *    --place [--pendant a,b,c] [--split PHI]: the tree of the tree file may name only some of the sequences; the others are queries
  *    (pamlh_load_placement).  Per query one table row per branch — father..node, the best pendant length of the grid (default 0.05, 0.1,
  *    0.2, 0.4), the lnL of the tree with the query hung there at PHI (default 0.5) of the branch above the node, the difference to the
@@ -126,7 +131,7 @@ int main(int argc, char **argv)
    pamlh *p;
    char err[512];
    double x[4096], lnL, *lnf;
-   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0, place = 0, n_pend = 4;
+   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0, spr_scores = 0, spr_search = 0, radius = 0, top = 0, place = 0, n_pend = 4;
    double pend[64] = {0.05, 0.1, 0.2, 0.4}, split = 0.5;
    char over[2048] = "";
    const char *sim_out = NULL, *bv_out = NULL;
@@ -135,13 +140,17 @@ int main(int argc, char **argv)
    unsigned char comm_id[PAML_AMD_COMM_ID_BYTES];
    int device[MAX_RANKS];
    for (i = 0; i < MAX_RANKS; i++) device[i] = i;
-   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
+   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
    for (i = 3; i < argc && nx < 4096; i++) {
       if (!strcmp(argv[i], "--optimize")) optimize = 1;
       else if (!strcmp(argv[i], "--analytic-gradient")) analytic = 1;      /* with --optimize: the branch lengths' derivatives from one engine call per gradient */
       else if (!strcmp(argv[i], "--nni-scores")) nni_scores = 1;
       else if (!strcmp(argv[i], "--nni-search")) nni_search = 1;
       else if (!strcmp(argv[i], "--max-moves") && i + 1 < argc) max_moves = atoi(argv[++i]);
+      else if (!strcmp(argv[i], "--spr-scores")) spr_scores = 1;
+      else if (!strcmp(argv[i], "--spr-search")) spr_search = 1;
+      else if (!strcmp(argv[i], "--radius") && i + 1 < argc) radius = atoi(argv[++i]);
+      else if (!strcmp(argv[i], "--top") && i + 1 < argc) top = atoi(argv[++i]);
       else if (!strcmp(argv[i], "--place")) place = 1;
       else if (!strcmp(argv[i], "--pendant") && i + 1 < argc) {      /* the grid of pendant lengths, e.g. "0.05,0.1,0.2" */
          char *tok = strtok(argv[++i], ",");
@@ -281,6 +290,34 @@ int main(int argc, char **argv)
       if (nni_search) {
          if (pamlh_nni_search(p, x, &lnL, max_moves, 1, stats)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
          printf("NNI search: %d moves, %d screening calls, %d neighbours maximised\n", stats[0], stats[1], stats[2]);
+         nw = (char *)malloc((size_t)160 * nnode + 256);
+         if (!pamlh_newick(p, nw, 160 * nnode + 256)) printf("%s\n", nw);
+         free(nw);
+         printf("x:");
+         for (i = 0; i < np; i++) printf(" %.6f", x[i]);
+         printf("\nlnL  = %.4f\n", lnL);
+      }
+      pamlh_free(p);
+      return 0;
+   }
+   if (spr_scores || spr_search) {      /* the SPR neighbours' table at x, or the hill climb from x; instead of the evaluation */
+      int nnode = 0, n = 0, stats[3] = {0, 0, 0};
+      char *nw;
+      if (gpus > 0) { fprintf(stderr, "error: --spr-scores and --spr-search run on one GPU\n"); return 1; }
+      pamlh_dims(p, NULL, NULL, NULL, &nnode, NULL, NULL, NULL, NULL, NULL, NULL);
+      if (spr_scores) {
+         int *mv;
+         double *sc, l0 = 0;
+         if (pamlh_spr_scores(p, NULL, radius, split, &n, NULL, NULL, NULL)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+         mv = (int *)malloc((size_t)(2 * n + 2) * sizeof(int)); sc = (double *)malloc((n + 1) * sizeof(double));
+         if (pamlh_spr_scores(p, x, radius, split, &n, mv, &l0, sc)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+         printf("SPR neighbours at the present branch lengths (one engine call, split %g): lnL of the present tree = %.6f\n%6s%6s %16s %14s\n", split, l0, "s", "x", "lnL", "difference");
+         for (i = 0; i < n; i++) printf("%6d%6d %16.6f %14.6f\n", mv[2 * i] + 1, mv[2 * i + 1] + 1, sc[i], sc[i] - l0);
+         free(mv); free(sc);
+      }
+      if (spr_search) {
+         if (pamlh_spr_search(p, x, &lnL, radius, top, max_moves, 1, stats)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+         printf("SPR search: %d moves, %d screening calls, %d neighbours maximised\n", stats[0], stats[1], stats[2]);
          nw = (char *)malloc((size_t)160 * nnode + 256);
          if (!pamlh_newick(p, nw, 160 * nnode + 256)) printf("%s\n", nw);
          free(nw);

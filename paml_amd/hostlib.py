@@ -20,7 +20,7 @@ DRIVER_PATH = os.path.join(_HERE, "lib", "pamlh_lnl")
 def build(force=False):
     from . import engine
     engine.build()
-    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_place.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
+    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_place.c", "pamlh_spr.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "pamlh.h"))
     if force or not (os.path.exists(LIB_PATH) and os.path.exists(DRIVER_PATH)) or \
             any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
@@ -381,6 +381,41 @@ class Analysis:
         self._L.pamlh_nni_search.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p]
         if len(x) != self.np or self._L.pamlh_nni_search(self._h, x.ctypes.data_as(C.c_void_p), C.byref(lnl), int(max_moves), int(bool(verbose)), stats) != 0:
             raise RuntimeError("pamlh_nni_search: " + self._L.pamlh_error(self._h).decode())
+        buf = C.create_string_buffer(160 * self.n_nodes + 256)
+        self._L.pamlh_newick.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+        newick = buf.value.decode() if self._L.pamlh_newick(self._h, buf, len(buf)) == 0 else None
+        return dict(x=x, lnL=lnl.value, moves=stats[0], screening_calls=stats[1], optimisations=stats[2], newick=newick)
+
+    def spr_scores(self, x, radius=0, phi=0.5):
+        """The lnL of every subtree-prune-and-regraft neighbour of the tree as it stands within `radius` branches (<= 0: no limit) at x,
+        from one engine call (pamlh_spr_scores): dict(lnL0, moves=[n_moves][2] (s, x; 0-based nodes), lnL=[n_moves])."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        n, l0 = C.c_int(), C.c_double()
+        f = self._L.pamlh_spr_scores
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_double), C.c_void_p]
+        if len(x) != self.np or f(self._h, None, int(radius), float(phi), C.byref(n), None, None, None) != 0:
+            raise RuntimeError("pamlh_spr_scores: " + self._L.pamlh_error(self._h).decode())
+        moves, lnl = np.zeros((max(1, n.value), 2), dtype=np.int32), np.zeros(max(1, n.value))
+        if f(self._h, x.ctypes.data_as(C.c_void_p), int(radius), float(phi), C.byref(n), moves.ctypes.data_as(C.c_void_p), C.byref(l0), lnl.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_spr_scores: " + self._L.pamlh_error(self._h).decode())
+        return dict(lnL0=l0.value, moves=moves[:n.value], lnL=lnl[:n.value])
+
+    def apply_spr(self, s, x, phi, xvec):
+        """Prune the subtree below s and regraft it on the branch above x on the analysis's tree (pamlh_apply_spr); returns the parameter
+        vector with the three branch lengths the move changes rewritten."""
+        xv = np.ascontiguousarray(xvec, dtype=np.float64).copy()
+        self._L.pamlh_apply_spr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
+        if len(xv) != self.np or self._L.pamlh_apply_spr(self._h, int(s), int(x), float(phi), xv.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_apply_spr: " + self._L.pamlh_error(self._h).decode())
+        return xv
+
+    def spr_search(self, x0, radius=0, top=0, max_moves=0, verbose=False):
+        """SPR hill climb from the tree as it stands (pamlh_spr_search): dict(x, lnL, moves, screening_calls, optimisations, newick)."""
+        x = np.ascontiguousarray(x0, dtype=np.float64).copy()
+        lnl, stats = C.c_double(), (C.c_int * 3)()
+        self._L.pamlh_spr_search.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        if len(x) != self.np or self._L.pamlh_spr_search(self._h, x.ctypes.data_as(C.c_void_p), C.byref(lnl), int(radius), int(top), int(max_moves), int(bool(verbose)), stats) != 0:
+            raise RuntimeError("pamlh_spr_search: " + self._L.pamlh_error(self._h).decode())
         buf = C.create_string_buffer(160 * self.n_nodes + 256)
         self._L.pamlh_newick.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         newick = buf.value.decode() if self._L.pamlh_newick(self._h, buf, len(buf)) == 0 else None

@@ -65,6 +65,94 @@ class Tree:
         sons[fa][sons[fa].index(x)] = int(s)
         return Tree(self.n_tips, self.n_nodes, self.root, sons, self.branch, self.label, self.names)
 
+    def _spr_parts(self, s, x=None):
+        """(f, g, c, below) of pruning s: f the father of s, g the father of f, c the other son of f, below[u]: u lies in the subtree
+        below s, s included.  ValueError naming what makes the prune, or the move (s, x) when x is given, invalid (the definition at the
+        top of paml_amd/csrc/kernels_spr.h)."""
+        fa, nn = self.father(), self.n_nodes
+        who = "spr(%s, %s): " % (s, x)
+        if not 0 <= s < nn or (x is not None and not 0 <= x < nn):
+            raise ValueError(who + "a node is out of range")
+        if s == self.root or fa[s] < 0:
+            raise ValueError(who + "%d is the root" % s)
+        f = int(fa[s])
+        if f == self.root or fa[f] < 0:
+            raise ValueError(who + "the father of %d is the root" % s)
+        if len(self.sons[f]) != 2:
+            raise ValueError(who + "the father of %d does not have exactly two sons" % s)
+        c = int(self.sons[f][0] if self.sons[f][1] == s else self.sons[f][1])
+        below = np.zeros(nn, dtype=bool)
+        stack = [int(s)]
+        while stack:
+            u = stack.pop()
+            below[u] = True
+            stack += [int(v) for v in self.sons[u]]
+        if x is not None:
+            if x == self.root:
+                raise ValueError(who + "%d is the root" % x)
+            if x == f:
+                raise ValueError(who + "%d is the father of %d" % (x, s))
+            if x == c:
+                raise ValueError(who + "%d is the sibling of %d: the same topology" % (x, s))
+            if below[x]:
+                raise ValueError(who + "%d lies in the subtree below %d" % (x, s))
+        return f, int(fa[f]), c, below
+
+    def spr(self, s, x, phi=0.5):
+        """A new Tree with the subtree below s pruned and regrafted on the branch above x (what paml_amd_spr_scores scores).  f = the
+        father of s travels with it: c, the other son of f, takes f's place in the son list of g = the father of f on a branch of length
+        t_c + t_f with c's label; f takes x's place in the son list of x's father with sons (x, s), the branch above f has length
+        (1 - phi) t_x and x's label, the branch above x phi t_x.  Node ids, n_nodes and the root stay; branch and label are new arrays."""
+        s, x = int(s), int(x)
+        f, g, c, _ = self._spr_parts(s, x)
+        if not 0 <= phi <= 1:
+            raise ValueError("spr: phi = %r is outside [0, 1]" % (phi,))
+        sons = [[int(u) for u in l] for l in self.sons]
+        branch, label = np.array(self.branch, dtype=np.float64), np.array(self.label, dtype=np.int32)
+        sons[g][sons[g].index(f)] = c
+        branch[c] = self.branch[c] + self.branch[f]
+        fx = next(i for i, l in enumerate(sons) if x in l and i != f)      # (x's father in the tree without s and f)
+        sons[fx][sons[fx].index(x)] = f
+        sons[f] = [x, s]
+        tx = branch[x]
+        branch[f], branch[x] = (1 - phi) * tx, phi * tx
+        label[f] = label[x]
+        return Tree(self.n_tips, self.n_nodes, self.root, sons, branch, label, self.names)
+
+    def spr_moves(self, radius=0):
+        """The canonical list of subtree-prune-and-regraft moves (s, x), int32 [n_moves][2], as paml_amd_spr_list writes it: every valid
+        move with s in node order and x in node order within s, whose target branch lies within `radius` branches of the merged branch
+        above c in the tree without s and f (radius <= 0: no limit; adjacent branches have distance 1)."""
+        fa, nn = self.father(), self.n_nodes
+        out = []
+        for s in range(nn):
+            try:
+                f, g, c, below = self._spr_parts(s)
+            except ValueError:
+                continue
+            # the nodes' distances from the merged branch (its ends g and c: 0) in the tree without s and f
+            nb = [[] for _ in range(nn)]
+            for u in range(nn):
+                if u != self.root and u != f and not below[u]:
+                    pu = g if u == c else int(fa[u])
+                    nb[u].append(pu)
+                    nb[pu].append(u)
+            dist = np.full(nn, nn + 1)
+            dist[g] = dist[c] = 0
+            queue = [g, c]
+            while queue:
+                u = queue.pop(0)
+                for v in nb[u]:
+                    if dist[v] > dist[u] + 1:
+                        dist[v] = dist[u] + 1
+                        queue.append(v)
+            for x in range(nn):
+                if x == self.root or x == f or x == c or below[x]:
+                    continue
+                if radius <= 0 or min(dist[int(fa[x])], dist[x]) + 1 <= radius:
+                    out.append((s, x))
+        return np.asarray(out, dtype=np.int32).reshape(-1, 2)
+
     def insert_tip(self, v, phi, pendant, label=0):
         """A new Tree with one more tip hung on the branch above v (what paml_amd_placement_scores scores; the reference's AddSpecies,
         treesub.c:4592).  The new tip is node n_tips, the old internal nodes move up by one, the new internal node u is the last node.
