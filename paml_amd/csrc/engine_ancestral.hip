@@ -1,21 +1,143 @@
 // engine_ancestral.hip — ancestral reconstruction at every internal node in one call: marginal (AncestralMarginal / PostProbNode,
-// treesub.c:6288, 6142) and joint (AncestralJointPPSG2000 treesub.c:6964); the definitions and the kernels in kernels_ancestral.h.
-// P(t) comes from the evaluation's own builders (launch_pmat, engine_eval.hip).
+// treesub.c:6288, 6142) and joint (AncestralJointPPSG2000 treesub.c:6964); the definitions in kernels_ancestral.h, the kernels here.
+// P(t) comes from the evaluation's own builders (launch_pmat, engine_eval.hip).  Also the host side every whole-tree call shares
+// (ancestral_host.h).
 // Built for gfx950 only (one of the translation units of libpaml_amd.so, see engine_state.h).
 #include "engine_state.h"
 #include "kernels_ancestral.h"
 #include "ancestral_host.h"
 
-static thread_local int anc_last_batches = 0;
-static thread_local double anc_last_kernel_ms = 0;      // HIP events around the P(t) kernels and every batch's passes, summed
+static thread_local AncCallInfo anc_info;
 
-extern "C" void paml_amd_ancestral_info(int *last_batches, double *last_kernel_ms)
-{
-   if (last_batches) *last_batches = anc_last_batches;
-   if (last_kernel_ms) *last_kernel_ms = anc_last_kernel_ms;
-}
+extern "C" void paml_amd_ancestral_info(int *last_batches, double *last_kernel_ms) { anc_info.read(last_batches, last_kernel_ms); }
 
 namespace paml_amd {
+
+// lnP = log(max(P, 1e-300)) of n_p entries, then lnpi of n_q
+__global__ __launch_bounds__(256) void anc_log_kernel(const double *P, long n_p, const double *pi, long n_q, double *lnP, double *lnpi)
+{
+   const long i = (long)blockIdx.x * 256 + threadIdx.x;
+   if (i < n_p) lnP[i] = log(fmax(P[i], 1e-300));
+   else if (i < n_p + n_q) lnpi[i - n_p] = log(fmax(pi[i - n_p], 1e-300));
+}
+
+// one pattern per lane: grid (patterns / 256, K)
+template <int N> __global__ __launch_bounds__(256) void anc_lane_kernel(AncMargArgs a, int outer)
+{
+   const long p = (long)blockIdx.x * 256 + threadIdx.x;
+   if (p >= a.nb) return;
+   if (outer) anc_lane_outer<N>(a, blockIdx.y, p);
+   else anc_lane_down<N>(a, blockIdx.y, p);
+}
+
+// grid (patterns / 256, n_query)
+__global__ __launch_bounds__(256) void anc_posterior_kernel(AncMargArgs a)
+{
+   const long p = (long)blockIdx.x * 256 + threadIdx.x;
+   if (p >= a.nb) return;
+   anc_posterior(a, blockIdx.y, p);
+}
+
+// grid (stride / ANC_TILE, K); outer = 0: the down pass, 1: the outer pass
+__global__ __launch_bounds__(256) void anc_mfma_kernel(AncMargArgs a, int outer)
+{
+   __shared__ __attribute__((aligned(16))) double sP[4096];
+   const AncTree &t = a.t;
+   const int tid = threadIdx.x, lane = tid & 63, n = a.n;
+   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+   const int q = lane >> 4, k = blockIdx.y;
+   const AncMfma w{sP, lane, wave, q};
+   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
+   const bool valid = p < a.nb;
+   const long pc = valid ? p : a.nb - 1;
+   const long pset = (long)a.gene * a.K + k;
+   if (!outer) {
+      for (int i = 0; i < t.n_post; i++) {
+         const int v = t.post[i];
+         if (v < t.n_tips) continue;
+         double x[16], ls = 0;
+#pragma unroll
+         for (int m = 0; m < 16; m++) x[m] = 4 * m + q < n ? 1.0 : 0.0;
+         for (int j = t.sons_ptr[v]; j < t.sons_ptr[v + 1]; j++) anc_mfma_mul_son(a, w, k, g16, pc, t.sons[j], x, &ls);
+         if (a.scaled && t.scale[v]) {
+            const double mx = anc_mfma_max(x);
+            if (mx < 1e-300) {
+#pragma unroll
+               for (int m = 0; m < 16; m++) x[m] = 4 * m + q < n ? 1.0 : 0.0;
+               ls += -800;
+            }
+            else {
+#pragma unroll
+               for (int m = 0; m < 16; m++) x[m] /= mx;
+               ls += log(mx);
+            }
+         }
+         const int vi = v - t.n_tips;
+         part_store(a.L + (((long)k * t.n_int + vi) * (a.stride >> 4) + g16) * 1024, lane, x);
+         if (q == 0) a.SL[((long)k * t.n_int + vi) * a.stride + p] = ls;      // (p < stride: the padding takes the lanes past the end)
+      }
+      return;
+   }
+   if (t.root >= t.n_tips) {
+      const int ri = t.root - t.n_tips;
+      double x[16];
+#pragma unroll
+      for (int m = 0; m < 16; m++) x[m] = 4 * m + q < n ? 1.0 : 0.0;
+      part_store(a.G + (((long)k * t.n_int + ri) * (a.stride >> 4) + g16) * 1024, lane, x);
+      if (q == 0) a.SG[((long)k * t.n_int + ri) * a.stride + p] = 0;
+   }
+   for (int i = 0; i < t.n_pre; i++) {
+      const int v = t.pre[i], f = t.father[v], vi = v - t.n_tips;
+      double h[16], ls = 0;
+      __syncthreads();      // (SG of the father was stored by the pattern's q = 0 lane: a workgroup-scope fence before the other lanes read it)
+      if (f >= t.n_tips) {
+         const int fi = f - t.n_tips;
+         part_load(a.G + (((long)k * t.n_int + fi) * (a.stride >> 4) + g16) * 1024, lane, h);      // (this lane's own stores)
+         ls = a.SG[((long)k * t.n_int + fi) * a.stride + pc];
+      }
+      else {
+         const unsigned long long mask = a.code_mask[a.z[(long)f * a.z_stride + a.h0 + pc]];
+#pragma unroll
+         for (int m = 0; m < 16; m++) h[m] = (mask >> (4 * m + q)) & 1ull ? 1.0 : 0.0;
+      }
+      for (int j = t.sons_ptr[f]; j < t.sons_ptr[f + 1]; j++)
+         if (t.sons[j] != v) anc_mfma_mul_son(a, w, k, g16, pc, t.sons[j], h, &ls);
+      v4d acc[4];
+      w.product(a.pint + (pset * t.n_nodes + v) * 4096, h, acc);
+      double g[16];
+#pragma unroll
+      for (int m = 0; m < 16; m++) g[m] = acc[m >> 2][m & 3];
+      if (a.scaled) {
+         const double mx = anc_mfma_max(g);
+         if (mx > 0) {
+#pragma unroll
+            for (int m = 0; m < 16; m++) g[m] /= mx;
+            ls += log(mx);
+         }
+      }
+      part_store(a.G + (((long)k * t.n_int + vi) * (a.stride >> 4) + g16) * 1024, lane, g);
+      if (q == 0) a.SG[((long)k * t.n_int + vi) * a.stride + p] = ls;
+   }
+}
+
+// joint: grid (patterns / ANC_JTILE); dynamic LDS: the node's n^2 doubles (n <= 64: 32 KB at most)
+__global__ __launch_bounds__(ANC_JTILE) void anc_joint_kernel(AncJointArgs a)
+{
+   extern __shared__ __attribute__((aligned(16))) double anc_lds[];
+   const AncTree &t = a.t;
+   const int tid = threadIdx.x, n2 = a.n * a.n;
+   const long p = (long)blockIdx.x * ANC_JTILE + tid;
+   const bool on = p < a.nb;      // (lanes past the end keep to the barriers and touch no memory)
+   for (int i = 0; i + 1 < t.n_post; i++) {      // (the root is the last entry)
+      const int v = t.post[i];
+      const double *lnPv = a.lnP + ((long)a.gene * t.n_nodes + v) * n2;
+      __syncthreads();      // (the previous node's table is no longer read)
+      for (int idx = tid; idx < n2; idx += ANC_JTILE) anc_lds[idx] = lnPv[idx];
+      __syncthreads();
+      if (on) anc_joint_up(a, v, p, anc_lds);
+   }
+   if (on) anc_joint_root_down(a, p);
+}
 
 // the tree as one int array: sons_ptr, sons, father, post, pre, scale (AncTree)
 int anc_tree_pack(paml_amd_engine *e, const char *who, AncScratch &w, AncTree *out)
@@ -100,17 +222,116 @@ int anc_pmat(paml_amd_engine *e, const char *who, const double *branch, const do
    return 0;
 }
 
-// patterns per batch: what the workspace holds at `bytes_per_patt`, whole tiles, at least one (the variable `env`: MiB, default 256)
-long anc_batch(double bytes_per_patt, long n_patt, const char *env)
+// the end of what a call queued behind anc_pmat's ev0: waited for, its kernel time added to the call's, then the builder's verdict
+int anc_pmat_wait(paml_amd_engine *e, AncScratch &w)
+{
+   HIPCHK(hipEventRecord(w.ev1, e->stream));
+   HIPCHK(w.lap(e->stream));
+   return eigen_fail_check(e);
+}
+
+// anc_pmat, waited for
+int anc_pmat_waited(paml_amd_engine *e, const char *who, const double *branch, const double *gene_rate, AncScratch &w, const int *d_label)
+{
+   if (int rc = anc_pmat(e, who, branch, gene_rate, w, d_label)) return rc;
+   return anc_pmat_wait(e, w);
+}
+
+// Keeps what the kernels need of the builder's present output before the builder runs again, waited for.  Matrix cores: the A-operand
+// blocks with the tips' column tables (pint with ptip) and / or the transposed blocks of every node but the root (PT); a null buffer:
+// not kept.  Lanes: the row-major matrices (P).
+int anc_keep_pmat(paml_amd_engine *e, DevBuf<double> *pint, DevBuf<double> *ptip, DevBuf<double> *PT, DevBuf<double> &P)
+{
+   const int nn = e->tree.n_nodes, n = e->n;
+   const size_t psets = (size_t)e->n_genes * e->K, pn = psets * nn, tw = tip_words(e);
+   hipStream_t st = e->stream;
+   if (e->kk != KK_MFMA64) {
+      HIPCHK(P.ensure(pn * n * n));
+      HIPCHK(hipMemcpyAsync(P.p, e->d_rowmajor.p, pn * n * n * 8, hipMemcpyDeviceToDevice, st));
+   }
+   else {
+      if (pint) {
+         HIPCHK(pint->ensure(pn * 4096));
+         HIPCHK(ptip->ensure(pn * tw));
+      }
+      if (PT) HIPCHK(PT->ensure(pn * 4096));
+      if (pint) {
+         HIPCHK(hipMemcpyAsync(pint->p, e->d_pint.p, pn * 4096 * 8, hipMemcpyDeviceToDevice, st));
+         HIPCHK(hipMemcpyAsync(ptip->p, e->d_ptip.p, pn * tw * 8, hipMemcpyDeviceToDevice, st));
+      }
+      if (PT) {
+         hipLaunchKernelGGL(nni_pt_all_kernel, dim3(nn, (unsigned)psets), dim3(256), 0, st, (const double *)e->d_rowmajor.p, PT->p, n, nn, e->tree.root);
+         HIPCHK(hipGetLastError());
+      }
+   }
+   HIPCHK(hipStreamSynchronize(st));
+   return 0;
+}
+
+// the workspace a call may take, in MiB (the variable `env`; default 256)
+double anc_arena_mb(const char *env)
 {
    double arena_mb = 256;
    if (const char *s = getenv(env)) { const double v = atof(s); if (v > 0) arena_mb = v; }
+   return arena_mb;
+}
+
+// patterns per batch: what the workspace holds at `bytes_per_patt`, whole tiles, at least one
+long anc_batch(double bytes_per_patt, long n_patt, const char *env)
+{
+   const double arena_mb = anc_arena_mb(env);
    long batch = (long)(arena_mb * 1048576.0 / bytes_per_patt) / ANC_JTILE * ANC_JTILE;
    if (batch < ANC_JTILE) batch = (long)(arena_mb * 1048576.0 / bytes_per_patt) / ANC_TILE * ANC_TILE;
    if (batch > (1L << 24)) batch = 1L << 24;
    if (batch < ANC_TILE) batch = ANC_TILE;
    const long all = (n_patt + ANC_TILE - 1) / ANC_TILE * ANC_TILE;
    return batch > all ? all : batch;
+}
+
+// the batch workspace, in the order listed: the batch is halved until all of it fits
+int anc_alloc(paml_amd_engine *e, const char *who, std::initializer_list<AncBatchBuf> bufs, long *batch)
+{
+   for (;;) {
+      bool ok = true;
+      for (const AncBatchBuf &b : bufs) ok = ok && b.buf->ensure(b.per_patt * *batch) == hipSuccess;
+      if (ok) return 0;
+      (void)hipGetLastError();
+      for (const AncBatchBuf &b : bufs) b.buf->release();      // (ensure only grows: the retry starts from nothing)
+      if (*batch <= ANC_TILE) return fail(e, PAML_AMD_ENOMEM, std::string(who) + ": no device memory for one tile of patterns");
+      *batch = (*batch / 2 + ANC_TILE - 1) / ANC_TILE * ANC_TILE;
+   }
+}
+
+// what the down pass and the outer passes read of the engine, and the call's partials (the batch itself is the batch loop's to name)
+void anc_fill(const paml_amd_engine *e, const AncScratch &w, long batch, AncMargArgs &m)
+{
+   m.n = e->n; m.K = e->K; m.scaled = e->tree.n_scale > 0 ? 1 : 0; m.n_pi = e->n_pi; m.stride = batch;
+   m.z = e->d_z.p; m.z_stride = e->n_patt; m.code_mask = e->d_code_mask.p;
+   m.P = e->d_rowmajor.p; m.pint = e->d_pint.p; m.ptip = e->d_ptip.p; m.tip_words = (long)tip_words(e);
+   m.pi = e->d_pi_plain.p; m.freqK = e->d_freqK.p;
+   m.L = w.L.p; m.G = w.G.p; m.SL = w.SL.p; m.SG = w.SG.p; m.mfma = e->kk == KK_MFMA64 ? 1 : 0;
+}
+
+// chunks of GRAD_CHUNK patterns counted from each gene's first pattern (a batch is whole chunks of one gene): [g] = gene g's first
+// chunk, [n_genes] = the chunks of the engine
+std::vector<long> anc_chunk_base(const paml_amd_engine *e)
+{
+   std::vector<long> chunk_base(e->n_genes + 1, 0);
+   for (int g = 0; g < e->n_genes; g++) chunk_base[g + 1] = chunk_base[g] + (e->gene_off[g + 1] - e->gene_off[g] + GRAD_CHUNK - 1) / GRAD_CHUNK;
+   return chunk_base;
+}
+
+// out[i] = the chunks of row i of `partial` added in a fixed order (grad_total_kernel), for out.size() rows: downloaded and waited for
+int anc_totals(paml_amd_engine *e, AncScratch &w, const double *partial, long n_chunks, double *d_out, std::vector<double> &out)
+{
+   hipStream_t st = e->stream;
+   HIPCHK(hipEventRecord(w.ev0, st));
+   hipLaunchKernelGGL(grad_total_kernel, dim3((unsigned)out.size()), dim3(256), 0, st, partial, n_chunks, d_out);
+   HIPCHK(hipGetLastError());
+   HIPCHK(hipEventRecord(w.ev1, st));
+   HIPCHK(hipMemcpyAsync(out.data(), d_out, out.size() * 8, hipMemcpyDeviceToHost, st));
+   HIPCHK(w.lap(st));
+   return 0;
 }
 
 int anc_common_checks(paml_amd_engine *e, const char *who)
@@ -123,24 +344,11 @@ int anc_common_checks(paml_amd_engine *e, const char *who)
 
 }  // namespace paml_amd
 
-namespace {
-
-// 4 / 5 / 20 states, the engines that are not on the matrix cores (paml_amd_create: every other state count is KK_MFMA64): the partial in registers
-void anc_launch_lane(KernelKind kk, dim3 grid, hipStream_t st, const AncMargArgs &a, int outer)
-{
-   if (kk == KK_VALU4) hipLaunchKernelGGL(anc_lane_kernel<4>, grid, dim3(256), 0, st, a, outer);
-   else if (kk == KK_VALU5) hipLaunchKernelGGL(anc_lane_kernel<5>, grid, dim3(256), 0, st, a, outer);
-   else hipLaunchKernelGGL(anc_lane_kernel<20>, grid, dim3(256), 0, st, a, outer);
-}
-
-}  // namespace
-
 extern "C" int paml_amd_ancestral_marginal(paml_amd_engine *e, const double *branch, const double *gene_rate, int n_query, const int *nodes,
                                            unsigned char *best, double *best_prob, double *post)
 {
    enter(e);
-   anc_last_batches = 0;
-   anc_last_kernel_ms = 0;
+   anc_info = AncCallInfo{};
    const char *who = "ancestral_marginal";
    if (!e || !branch || !best || !best_prob) return fail(e, PAML_AMD_EINVAL, "ancestral_marginal: null argument");
    if (int rc = anc_common_checks(e, who)) return rc;
@@ -167,16 +375,12 @@ extern "C" int paml_amd_ancestral_marginal(paml_amd_engine *e, const double *bra
          return fail(e, PAML_AMD_EUNSUPPORTED, "ancestral_marginal: moving the root needs a reversible model");
    const bool mfma = e->kk == KK_MFMA64;
    hipStream_t st = e->stream;
-   AncScratch w;
+   AncScratch w(anc_info);
    AncMargArgs a{};
    if (int rc = anc_tree_pack(e, who, w, &a.t)) return rc;
    HIPCHK(upload(w.query, query.data(), query.size(), st));
    HIPCHK(hipStreamSynchronize(st));
-   if (int rc = anc_pmat(e, who, branch, gene_rate, w)) return rc;
-   HIPCHK(hipEventRecord(w.ev1, st));
-   HIPCHK(hipStreamSynchronize(st));
-   if (int rc = eigen_fail_check(e)) return rc;
-   { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); anc_last_kernel_ms += ms; }
+   if (int rc = anc_pmat_waited(e, who, branch, gene_rate, w)) return rc;
 
    const int ns = mfma ? 64 : n;      // doubles a partial takes per pattern
    const double per_patt = 2.0 * K * n_int * (ns + 1) * 8 + (double)nq * (n * 8 + 9);
@@ -191,11 +395,8 @@ extern "C" int paml_amd_ancestral_marginal(paml_amd_engine *e, const double *bra
       if (batch <= ANC_TILE) return fail(e, PAML_AMD_ENOMEM, "ancestral_marginal: no device memory for one tile of patterns");
       batch = (batch / 2 + ANC_TILE - 1) / ANC_TILE * ANC_TILE;
    }
-   a.n = n; a.K = K; a.scaled = T.n_scale > 0 ? 1 : 0; a.n_pi = e->n_pi; a.n_query = nq; a.stride = batch;
-   a.z = e->d_z.p; a.z_stride = e->n_patt; a.code_mask = e->d_code_mask.p;
-   a.P = e->d_rowmajor.p; a.pint = e->d_pint.p; a.ptip = e->d_ptip.p; a.tip_words = (long)tip_words(e);
-   a.pi = e->d_pi_plain.p; a.freqK = e->d_freqK.p; a.query = w.query.p;
-   a.L = w.L.p; a.G = w.G.p; a.SL = w.SL.p; a.SG = w.SG.p; a.post = w.post.p; a.best_prob = w.prob.p; a.best = w.best.p; a.mfma = mfma ? 1 : 0;
+   anc_fill(e, w, batch, a);
+   a.n_query = nq; a.query = w.query.p; a.post = w.post.p; a.best_prob = w.prob.p; a.best = w.best.p;
    const long n_patt = e->n_patt;
    for (int g = 0; g < G; g++)
       for (long h0 = e->gene_off[g]; h0 < e->gene_off[g + 1]; h0 += batch) {
@@ -204,7 +405,7 @@ extern "C" int paml_amd_ancestral_marginal(paml_amd_engine *e, const double *bra
          HIPCHK(hipEventRecord(w.ev0, st));
          for (int outer = 0; outer < 2; outer++) {
             if (mfma) hipLaunchKernelGGL(anc_mfma_kernel, dim3((unsigned)((nb + ANC_TILE - 1) / ANC_TILE), K), dim3(256), 0, st, a, outer);
-            else anc_launch_lane(e->kk, dim3((unsigned)((nb + 255) / 256), K), st, a, outer);
+            else anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(anc_lane_kernel<N()>, dim3((unsigned)((nb + 255) / 256), K), dim3(256), 0, st, a, outer); });
             HIPCHK(hipGetLastError());
          }
          hipLaunchKernelGGL(anc_posterior_kernel, dim3((unsigned)((nb + 255) / 256), nq), dim3(256), 0, st, a);
@@ -217,9 +418,8 @@ extern "C" int paml_amd_ancestral_marginal(paml_amd_engine *e, const double *bra
             if (post)
                HIPCHK(hipMemcpyAsync(post + ((size_t)qi * n_patt + h0) * n, w.post.p + (size_t)qi * batch * n, (size_t)nb * n * 8, hipMemcpyDeviceToHost, st));
          }
-         HIPCHK(hipStreamSynchronize(st));
-         { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); anc_last_kernel_ms += ms; }
-         anc_last_batches++;
+         HIPCHK(w.lap(st));
+         anc_info.batches++;
       }
    return 0;
 }
@@ -227,8 +427,7 @@ extern "C" int paml_amd_ancestral_marginal(paml_amd_engine *e, const double *bra
 extern "C" int paml_amd_ancestral_joint(paml_amd_engine *e, const double *branch, const double *gene_rate, unsigned char *states, double *ln_best)
 {
    enter(e);
-   anc_last_batches = 0;
-   anc_last_kernel_ms = 0;
+   anc_info = AncCallInfo{};
    const char *who = "ancestral_joint";
    if (!e || !branch || !states || !ln_best) return fail(e, PAML_AMD_EINVAL, "ancestral_joint: null argument");
    if (int rc = anc_common_checks(e, who)) return rc;
@@ -237,7 +436,7 @@ extern "C" int paml_amd_ancestral_joint(paml_amd_engine *e, const double *branch
    const int nn = T.n_nodes, n = e->n, G = e->n_genes, n_tips = e->n_tips, n_int = nn - n_tips;
    if (n_int < 1) return fail(e, PAML_AMD_EINVAL, "ancestral_joint: the tree has no internal node");
    hipStream_t st = e->stream;
-   AncScratch w;
+   AncScratch w(anc_info);
    AncJointArgs a{};
    if (int rc = anc_tree_pack(e, who, w, &a.t)) return rc;
    if (int rc = anc_pmat(e, who, branch, gene_rate, w)) return rc;
@@ -245,11 +444,8 @@ extern "C" int paml_amd_ancestral_joint(paml_amd_engine *e, const double *branch
    HIPCHK(w.lnP.ensure((size_t)(n_p + n_q)));
    hipLaunchKernelGGL(anc_log_kernel, dim3((unsigned)((n_p + n_q + 255) / 256)), dim3(256), 0, st, (const double *)e->d_rowmajor.p, n_p, (const double *)e->d_pi_plain.p, n_q, w.lnP.p, w.lnP.p + n_p);
    HIPCHK(hipGetLastError());
-   HIPCHK(hipEventRecord(w.ev1, st));
-   HIPCHK(hipStreamSynchronize(st));
-   if (int rc = eigen_fail_check(e)) return rc;
+   if (int rc = anc_pmat_wait(e, w)) return rc;
    e->pmat_valid = true;
-   { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); anc_last_kernel_ms += ms; }
 
    const double per_patt = (double)n_int * n * 9 + n_int + 1 + 8;
    long batch = anc_batch(per_patt, e->n_patt);
@@ -279,9 +475,8 @@ extern "C" int paml_amd_ancestral_joint(paml_amd_engine *e, const double *branch
          for (int vi = 0; vi < n_int; vi++)
             HIPCHK(hipMemcpyAsync(states + (size_t)vi * n_patt + h0, w.state.p + (size_t)vi * batch, (size_t)nb, hipMemcpyDeviceToHost, st));
          HIPCHK(hipMemcpyAsync(ln_best + h0, w.lnbest.p, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-         HIPCHK(hipStreamSynchronize(st));
-         { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); anc_last_kernel_ms += ms; }
-         anc_last_batches++;
+         HIPCHK(w.lap(st));
+         anc_info.batches++;
       }
    return 0;
 }

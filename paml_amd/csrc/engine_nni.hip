@@ -1,5 +1,5 @@
 // engine_nni.hip — the lnL of every nearest-neighbour-interchange neighbour of the tree at the present branch lengths in one call
-// (paml_amd_nni_scores) and the canonical list of swaps (paml_amd_nni_list, host only); the definition and the kernels in kernels_nni.h.
+// (paml_amd_nni_scores) and the canonical list of swaps (paml_amd_nni_list, host only); the definition in kernels_nni.h, the kernels here.
 // P(t) comes from the evaluation's own builders (anc_pmat, engine_ancestral.hip), the down pass is the ancestral module's, the outer
 // pass is the gradient's without the derivative.
 // Built for gfx950 only (one of the translation units of libpaml_amd.so, see engine_state.h).
@@ -7,14 +7,168 @@
 #include "kernels_nni.h"
 #include "ancestral_host.h"
 
-static thread_local int nni_last_batches = 0;
-static thread_local double nni_last_kernel_ms = 0;      // HIP events around the P(t) kernels and every batch's passes, summed
+static thread_local AncCallInfo nni_info;
 
-extern "C" void paml_amd_nni_info(int *last_batches, double *last_kernel_ms)
+extern "C" void paml_amd_nni_info(int *last_batches, double *last_kernel_ms) { nni_info.read(last_batches, last_kernel_ms); }
+
+namespace paml_amd {
+
+// P_v^T of every (parameter set, internal node) in the A-operand order (the index formula of grad_pmat_kernel): grid (n_nodes, gene x class)
+__global__ __launch_bounds__(256) void nni_pt_kernel(const double *P, double *PT, int n, int n_nodes, int n_tips, int root)
 {
-   if (last_batches) *last_batches = nni_last_batches;
-   if (last_kernel_ms) *last_kernel_ms = nni_last_kernel_ms;
+   const int node = blockIdx.x;
+   if (node == root || node < n_tips) return;
+   const long slot = (long)blockIdx.y * n_nodes + node;
+   const double *Pv = P + slot * n * n;
+   double *tf = PT + slot * 4096;
+   for (int idx = threadIdx.x; idx < 4096; idx += 256) {
+      const int e = idx & 1, lane = (idx >> 1) & 63, jb = (idx >> 7) & 3, kb2 = idx >> 9;
+      const int r = jb * 16 + (lane & 15), c = 4 * (2 * kb2 + e) + (lane >> 4);
+      tf[idx] = r < n && c < n ? Pv[c * n + r] : 0.0;
+   }
 }
+
+// P_v^T of every (parameter set, node other than the root) in the A-operand order (the index formula of nni_pt_kernel, which leaves
+// the tips out): grid (n_nodes, gene x class)
+__global__ __launch_bounds__(256) void nni_pt_all_kernel(const double *P, double *PT, int n, int n_nodes, int root)
+{
+   const int node = blockIdx.x;
+   if (node == root) return;
+   const long slot = (long)blockIdx.y * n_nodes + node;
+   const double *Pv = P + slot * n * n;
+   double *tf = PT + slot * 4096;
+   for (int idx = threadIdx.x; idx < 4096; idx += 256) {
+      const int e = idx & 1, lane = (idx >> 1) & 63, jb = (idx >> 7) & 3, kb2 = idx >> 9;
+      const int r = jb * 16 + (lane & 15), c = 4 * (2 * kb2 + e) + (lane >> 4);
+      tf[idx] = r < n && c < n ? Pv[c * n + r] : 0.0;
+   }
+}
+
+// one pattern per lane, the swap pass: grid (patterns / 256, K, swaps of the group)
+template <int N> __global__ __launch_bounds__(256) void nni_lane_swap_kernel(NniArgs a)
+{
+   const long p = (long)blockIdx.x * 256 + threadIdx.x;
+   if (p >= a.m.nb) return;
+   nni_lane_swap<N>(a, blockIdx.y, p, blockIdx.z);
+}
+
+// Matrix cores, the outer pass without the derivative (grad_mfma_kernel's walk over the internal nodes, then ref_node when it is a tip):
+// lane = q * 16 + pattern, register m = state 4 m + q.  Grid (stride / ANC_TILE, K).
+__global__ __launch_bounds__(256) void nni_mfma_outer_kernel(NniArgs a)
+{
+   __shared__ __attribute__((aligned(16))) double sP[4096];
+   const AncMargArgs &m = a.m;
+   const AncTree &t = m.t;
+   const int tid = threadIdx.x, lane = tid & 63, n = m.n;
+   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+   const int q = lane >> 4, k = blockIdx.y;
+   const AncMfma w{sP, lane, wave, q};
+   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
+   const long pc = p < m.nb ? p : m.nb - 1;      // (lanes past the batch's end read the last pattern and write into the padding: p < stride)
+   const long pset = (long)m.gene * m.K + k;
+   if (t.root >= t.n_tips) {
+      const double *pi = m.pi + (long)(m.n_pi > 1 ? m.gene : 0) * n;
+      const int ri = t.root - t.n_tips;
+      double x[16];
+#pragma unroll
+      for (int i = 0; i < 16; i++) x[i] = 4 * i + q < n ? pi[4 * i + q] : 0.0;
+      part_store(m.G + (((long)k * t.n_int + ri) * (m.stride >> 4) + g16) * 1024, lane, x);
+      if (q == 0) m.SG[((long)k * t.n_int + ri) * m.stride + p] = 0;
+   }
+   const int n_walk = t.n_pre + (a.ref_node < t.n_tips ? 1 : 0);
+   for (int i = 0; i < n_walk; i++) {
+      const int v = i < t.n_pre ? t.pre[i] : a.ref_node;
+      const int f = t.father[v];
+      double h[16], ls;
+      __syncthreads();      // (SG of the father was stored by the pattern's q = 0 lane: a workgroup-scope fence before the other lanes read it)
+      nni_mfma_father(m, k, g16, pc, lane, q, f, h, &ls);
+      for (int j = t.sons_ptr[f]; j < t.sons_ptr[f + 1]; j++)
+         if (t.sons[j] != v) anc_mfma_mul_son(m, w, k, g16, pc, t.sons[j], h, &ls);
+      const long oi = nni_out_idx(a, k, a.cap, p);
+      double x[16], y[16];
+      if (v < t.n_tips) {      // ref_node, a tip: P_v L_v from the tip's column table
+         double2 tv[8];
+         tip_gather(m.ptip + pset * t.n_nodes * m.tip_words, m.tip_words, v, (int)m.z[(long)v * m.z_stride + m.h0 + pc], q, tv);
+#pragma unroll
+         for (int j = 0; j < 8; j++) { y[2 * j] = tv[j].x; y[2 * j + 1] = tv[j].y; }
+         const double den = grad_mfma_dot(h, y);
+         if (q == 0) { a.f[oi] = den; a.sig[oi] = ls; }
+         continue;
+      }
+      const int vi = v - t.n_tips;
+      v4d acc[4];
+      w.product(a.PT + (pset * t.n_nodes + v) * 4096, h, acc);      // A_v = P_v^T H_v
+#pragma unroll
+      for (int j = 0; j < 16; j++) y[j] = acc[j >> 2][j & 3];
+      if (v == a.ref_node) {      // (uniform over the workgroup) sum_x A_v(x) L_v(x) before A_v is rescaled, as grad_mfma_kernel
+         part_load(m.L + (((long)k * t.n_int + vi) * (m.stride >> 4) + g16) * 1024, lane, x);
+         const double den = grad_mfma_dot(y, x);
+         if (q == 0) { a.f[oi] = den; a.sig[oi] = ls + m.SL[((long)k * t.n_int + vi) * m.stride + pc]; }
+      }
+      if (m.scaled) {
+         const double mx = anc_mfma_max(y);
+         if (mx > 0) {
+#pragma unroll
+            for (int j = 0; j < 16; j++) y[j] /= mx;
+            ls += log(mx);
+         }
+      }
+      part_store(m.G + (((long)k * t.n_int + vi) * (m.stride >> 4) + g16) * 1024, lane, y);
+      if (q == 0) m.SG[((long)k * t.n_int + vi) * m.stride + p] = ls;
+   }
+}
+
+// Matrix cores, the swap pass: four waves own ANC_TILE patterns of one class and loop over the group's swaps.  Grid (stride / ANC_TILE, K).
+__global__ __launch_bounds__(256) void nni_mfma_kernel(NniArgs a)
+{
+   __shared__ __attribute__((aligned(16))) double sP[4096];
+   const AncMargArgs &m = a.m;
+   const AncTree &t = m.t;
+   const int tid = threadIdx.x, lane = tid & 63, n = m.n;
+   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+   const int q = lane >> 4, k = blockIdx.y;
+   const AncMfma w{sP, lane, wave, q};
+   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
+   const long pc = p < m.nb ? p : m.nb - 1;      // (lanes past the batch's end read the last pattern and write into the padding: p < stride)
+   const long pset = (long)m.gene * m.K + k;
+   for (int i = 0; i < a.n_group; i++) {
+      const int *sw = a.swaps + 3L * (a.swap0 + i);
+      const int v = sw[0], s = sw[1], x = sw[2], f = t.father[v];
+      double h[16], l[16], ls;
+      nni_mfma_father(m, k, g16, pc, lane, q, f, h, &ls);
+      anc_mfma_mul_son(m, w, k, g16, pc, s, h, &ls);
+      for (int j = t.sons_ptr[f]; j < t.sons_ptr[f + 1]; j++)
+         if (t.sons[j] != v && t.sons[j] != x) anc_mfma_mul_son(m, w, k, g16, pc, t.sons[j], h, &ls);
+#pragma unroll
+      for (int j = 0; j < 16; j++) l[j] = 4 * j + q < n ? 1.0 : 0.0;
+      anc_mfma_mul_son(m, w, k, g16, pc, x, l, &ls);
+      for (int j = t.sons_ptr[v]; j < t.sons_ptr[v + 1]; j++)
+         if (t.sons[j] != s) anc_mfma_mul_son(m, w, k, g16, pc, t.sons[j], l, &ls);
+      v4d acc[4];
+      w.product(m.pint + (pset * t.n_nodes + v) * 4096, l, acc);
+      double y[16];
+#pragma unroll
+      for (int j = 0; j < 16; j++) y[j] = acc[j >> 2][j & 3];
+      const double fk = grad_mfma_dot(h, y);
+      const long oi = nni_out_idx(a, k, i, p);
+      if (q == 0) { a.f[oi] = fk; a.sig[oi] = ls; }
+   }
+}
+
+// the classes of every (row, pattern) and the chunks' sums: grid (stride / 256, rows); a wave = one chunk of GRAD_CHUNK patterns
+__global__ __launch_bounds__(256) void nni_combine_kernel(NniArgs a)
+{
+   const long p = (long)blockIdx.x * 256 + threadIdx.x;
+   const bool present = (int)blockIdx.y == a.n_group;      // (a batch's first group is launched with a row more: the present tree)
+   const int row = present ? a.cap : (int)blockIdx.y;
+   double acc = p < a.m.nb ? nni_combine(a, row, p) : 0.0;
+#pragma unroll
+   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+   const long chunk = a.chunk0 + (p >> 6);
+   const long out_row = present ? a.n_swaps : a.swap0 + row;
+   if ((threadIdx.x & 63) == 0 && (p & ~63L) < a.m.nb) a.partial[out_row * a.n_chunks + chunk] = acc;
+}
+}  // namespace paml_amd
 
 // The canonical list, in node order: every (s, x) of every internal v that is not the root, s over v's sons and x over its father's
 // other sons, both in son-list order.  A binary v under a root with exactly three sons lists its first son only: there (s1, x1) and
@@ -49,6 +203,7 @@ extern "C" int paml_amd_nni_list(int n_tips, int n_nodes, int root, const int *s
 namespace {
 
 struct NniScratch : AncScratch {
+   using AncScratch::AncScratch;
    DevBuf<double> PT, f, sig, lnf, partial, out;
    DevBuf<int> swaps;
    ~NniScratch()
@@ -58,28 +213,13 @@ struct NniScratch : AncScratch {
    }
 };
 
-void nni_launch_lane(KernelKind kk, dim3 grid, hipStream_t st, const NniArgs &a, int pass)
-{
-   if (kk == KK_VALU4) hipLaunchKernelGGL(nni_lane_kernel<4>, grid, dim3(256), 0, st, a, pass);
-   else if (kk == KK_VALU5) hipLaunchKernelGGL(nni_lane_kernel<5>, grid, dim3(256), 0, st, a, pass);
-   else hipLaunchKernelGGL(nni_lane_kernel<20>, grid, dim3(256), 0, st, a, pass);
-}
-
-void nni_launch_lane_swap(KernelKind kk, dim3 grid, hipStream_t st, const NniArgs &a)
-{
-   if (kk == KK_VALU4) hipLaunchKernelGGL(nni_lane_swap_kernel<4>, grid, dim3(256), 0, st, a);
-   else if (kk == KK_VALU5) hipLaunchKernelGGL(nni_lane_swap_kernel<5>, grid, dim3(256), 0, st, a);
-   else hipLaunchKernelGGL(nni_lane_swap_kernel<20>, grid, dim3(256), 0, st, a);
-}
-
 }  // namespace
 
 extern "C" int paml_amd_nni_scores(paml_amd_engine *e, const double *branch, const double *gene_rate, int n_swaps, const int *swaps, double *lnL0,
                                    double *lnL, double *lnf)
 {
    enter(e);
-   nni_last_batches = 0;
-   nni_last_kernel_ms = 0;
+   nni_info = AncCallInfo{};
    const char *who = "nni_scores";
    if (!e || !branch || !swaps || !lnL0 || !lnL) return fail(e, PAML_AMD_EINVAL, "nni_scores: null argument");
    if (n_swaps < 1) return fail(e, PAML_AMD_EINVAL, "nni_scores: n_swaps < 1");
@@ -109,7 +249,7 @@ extern "C" int paml_amd_nni_scores(paml_amd_engine *e, const double *branch, con
    }
    const bool mfma = e->kk == KK_MFMA64;
    hipStream_t st = e->stream;
-   NniScratch w;
+   NniScratch w(nni_info);
    NniArgs a{};
    AncMargArgs &m = a.m;
    if (int rc = anc_tree_pack(e, who, w, &m.t)) return rc;
@@ -120,15 +260,10 @@ extern "C" int paml_amd_nni_scores(paml_amd_engine *e, const double *branch, con
       HIPCHK(hipGetLastError());
    }
    HIPCHK(upload(w.swaps, swaps, (size_t)3 * n_swaps, st));
-   HIPCHK(hipEventRecord(w.ev1, st));
-   HIPCHK(hipStreamSynchronize(st));
-   if (int rc = eigen_fail_check(e)) return rc;
+   if (int rc = anc_pmat_wait(e, w)) return rc;
    e->pmat_valid = true;      // (d_rowmajor holds every branch's P(t) in the tree's own orientation, as after the gradient)
-   { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); nni_last_kernel_ms += ms; }
 
-   // chunks of GRAD_CHUNK patterns counted from each gene's first pattern: a batch is whole chunks of one gene
-   std::vector<long> chunk_base(G + 1, 0);
-   for (int g = 0; g < G; g++) chunk_base[g + 1] = chunk_base[g] + (e->gene_off[g + 1] - e->gene_off[g] + GRAD_CHUNK - 1) / GRAD_CHUNK;
+   const std::vector<long> chunk_base = anc_chunk_base(e);
    const long n_chunks = chunk_base[G];
    HIPCHK(w.partial.ensure((size_t)(n_swaps + 1) * std::max<long>(n_chunks, 1)));
    HIPCHK(w.out.ensure((size_t)n_swaps + 1));
@@ -136,83 +271,41 @@ extern "C" int paml_amd_nni_scores(paml_amd_engine *e, const double *branch, con
    // the workspace per pattern: the partials and the messages, then (2 K + 1) doubles per row (the swaps of a group and the present tree)
    const int ns = mfma ? 64 : n;      // doubles a partial takes per pattern
    const double fixed = 2.0 * K * n_int * (ns + 1) * 8, per_row = (2.0 * K + 1) * 8;
-   double arena_mb = 256;
-   if (const char *s = getenv("PAML_AMD_NNI_ARENA_MB")) { const double v = atof(s); if (v > 0) arena_mb = v; }
+   const double arena_mb = anc_arena_mb("PAML_AMD_NNI_ARENA_MB");
    int cap = n_swaps;
    if ((fixed + per_row * (n_swaps + 1)) * ANC_TILE > arena_mb * 1048576.0)      // one tile with all swaps does not fit: groups of swaps
       cap = (int)std::min<double>(n_swaps, std::max(1.0, floor((arena_mb * 1048576.0 / ANC_TILE - fixed) / per_row) - 1));
    cap = std::min(cap, 65535);      // (the lanes' swap pass has a grid row per swap)
    long batch = anc_batch(fixed + per_row * (cap + 1), e->n_patt, "PAML_AMD_NNI_ARENA_MB");
-   for (;;) {      // halve the batch until it fits
-      const size_t part = (size_t)K * n_int * ns * batch, sc = (size_t)K * n_int * batch, rows = (size_t)K * (cap + 1) * batch;
-      if (w.L.ensure(part) == hipSuccess && w.G.ensure(part) == hipSuccess && w.SL.ensure(sc) == hipSuccess && w.SG.ensure(sc) == hipSuccess &&
-          w.f.ensure(rows) == hipSuccess && w.sig.ensure(rows) == hipSuccess && w.lnf.ensure((size_t)(cap + 1) * batch) == hipSuccess)
-         break;
-      (void)hipGetLastError();
-      for (DevBuf<double> *b : {&w.L, &w.G, &w.SL, &w.SG, &w.f, &w.sig, &w.lnf}) b->release();      // (ensure only grows: the retry starts from nothing)
-      if (batch <= ANC_TILE) return fail(e, PAML_AMD_ENOMEM, "nni_scores: no device memory for one tile of patterns");
-      batch = (batch / 2 + ANC_TILE - 1) / ANC_TILE * ANC_TILE;
+   {
+      const size_t part = (size_t)K * n_int * ns, sc = (size_t)K * n_int, rows = (size_t)K * (cap + 1);
+      if (int rc = anc_alloc(e, who, {{&w.L, part}, {&w.G, part}, {&w.SL, sc}, {&w.SG, sc}, {&w.f, rows}, {&w.sig, rows}, {&w.lnf, (size_t)cap + 1}}, &batch)) return rc;
    }
-   m.n = n; m.K = K; m.scaled = T.n_scale > 0 ? 1 : 0; m.n_pi = e->n_pi; m.stride = batch;
-   m.z = e->d_z.p; m.z_stride = e->n_patt; m.code_mask = e->d_code_mask.p;
-   m.P = e->d_rowmajor.p; m.pint = e->d_pint.p; m.ptip = e->d_ptip.p; m.tip_words = (long)tip_words(e);
-   m.pi = e->d_pi_plain.p; m.freqK = e->d_freqK.p;
-   m.L = w.L.p; m.G = w.G.p; m.SL = w.SL.p; m.SG = w.SG.p; m.mfma = mfma ? 1 : 0;
+   anc_fill(e, w, batch, m);
    a.PT = w.PT.p; a.swaps = w.swaps.p; a.cap = cap; a.n_swaps = n_swaps; a.f = w.f.p; a.sig = w.sig.p; a.weights = e->d_weights.p;
    a.lnf = w.lnf.p; a.partial = w.partial.p; a.n_chunks = n_chunks;
    a.ref_node = T.sons[T.sons_ptr[T.root]];
    const long n_patt = e->n_patt;
-   for (int g = 0; g < G; g++)
-      for (long h0 = e->gene_off[g]; h0 < e->gene_off[g + 1]; h0 += batch) {
-         const long nb = std::min<long>(batch, e->gene_off[g + 1] - h0);
-         m.gene = g; m.h0 = h0; m.nb = nb;
-         a.chunk0 = chunk_base[g] + (h0 - e->gene_off[g]) / GRAD_CHUNK;
-         a.swap0 = 0; a.n_group = 0;
-         const dim3 tiles((unsigned)((nb + ANC_TILE - 1) / ANC_TILE), K), lanes((unsigned)((nb + 255) / 256), K);
-         HIPCHK(hipEventRecord(w.ev0, st));
-         if (mfma) {
-            hipLaunchKernelGGL(nni_unit_anc_mfma_kernel, tiles, dim3(256), 0, st, m, 0);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(nni_mfma_outer_kernel, tiles, dim3(256), 0, st, a);
-            HIPCHK(hipGetLastError());
-         }
-         else
-            for (int pass = 0; pass < 2; pass++) {
-               nni_launch_lane(e->kk, lanes, st, a, pass);
-               HIPCHK(hipGetLastError());
-            }
-         HIPCHK(hipEventRecord(w.ev1, st));
-         for (int s0 = 0; s0 < n_swaps; s0 += cap) {
-            const int ng = std::min(cap, n_swaps - s0);
-            a.swap0 = s0; a.n_group = ng;
-            if (s0) {      // (the batch's first group is timed with its down and outer passes)
-               HIPCHK(hipStreamSynchronize(st));
-               { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); nni_last_kernel_ms += ms; }
-               HIPCHK(hipEventRecord(w.ev0, st));
-            }
-            if (mfma) hipLaunchKernelGGL(nni_mfma_kernel, tiles, dim3(256), 0, st, a);
-            else nni_launch_lane_swap(e->kk, dim3(lanes.x, K, ng), st, a);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(nni_combine_kernel, dim3(lanes.x, ng + (s0 == 0 ? 1 : 0)), dim3(256), 0, st, a);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(w.ev1, st));
-            // the group's rows to the caller's [n_swaps][n_patt]: one plain copy per swap
-            if (lnf)
-               for (int i = 0; i < ng; i++)
-                  HIPCHK(hipMemcpyAsync(lnf + (size_t)(s0 + i) * n_patt + h0, w.lnf.p + (size_t)i * batch, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-         }
-         HIPCHK(hipStreamSynchronize(st));
-         { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); nni_last_kernel_ms += ms; }
-         nni_last_batches++;
-      }
-   HIPCHK(hipEventRecord(w.ev0, st));
-   hipLaunchKernelGGL(nni_unit_grad_total_kernel, dim3(n_swaps + 1), dim3(256), 0, st, (const double *)w.partial.p, n_chunks, w.out.p);
-   HIPCHK(hipGetLastError());
-   HIPCHK(hipEventRecord(w.ev1, st));
+   auto group = [&](int gi) { a.swap0 = gi * cap; a.n_group = std::min(cap, n_swaps - a.swap0); };      // groups of `cap` swaps in list order
+   if (int rc = anc_score_batches(
+          e, w, a, chunk_base, batch, (n_swaps + cap - 1) / cap,
+          [&](dim3 lanes, int pass) { anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(nni_lane_kernel<N()>, lanes, dim3(256), 0, st, a, pass); }); },
+          [](dim3) {},      // (the present tree's row is combined with the batch's first group)
+          [&](int gi, dim3 tiles, dim3 lanes) {
+             group(gi);
+             if (mfma) hipLaunchKernelGGL(nni_mfma_kernel, tiles, dim3(256), 0, st, a);
+             else anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(nni_lane_swap_kernel<N()>, dim3(lanes.x, K, a.n_group), dim3(256), 0, st, a); });
+          },
+          [&](int gi, dim3 lanes) { hipLaunchKernelGGL(nni_combine_kernel, dim3(lanes.x, a.n_group + (gi == 0 ? 1 : 0)), dim3(256), 0, st, a); },
+          [&](int, long h0, long nb) {      // the group's rows to the caller's [n_swaps][n_patt]: one plain copy per swap
+             if (lnf)
+                for (int i = 0; i < a.n_group; i++)
+                   HIPCHK(hipMemcpyAsync(lnf + (size_t)(a.swap0 + i) * n_patt + h0, w.lnf.p + (size_t)i * batch, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+             return 0;
+          }))
+      return rc;
    std::vector<double> out((size_t)n_swaps + 1);
-   HIPCHK(hipMemcpyAsync(out.data(), w.out.p, ((size_t)n_swaps + 1) * 8, hipMemcpyDeviceToHost, st));
-   HIPCHK(hipStreamSynchronize(st));
-   { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); nni_last_kernel_ms += ms; }
+   if (int rc = anc_totals(e, w, w.partial.p, n_chunks, w.out.p, out)) return rc;
    for (int i = 0; i < n_swaps; i++) lnL[i] = out[i];
    *lnL0 = out[n_swaps];
    return 0;

@@ -1,5 +1,5 @@
 // engine_place.hip — the lnL of the tree with one more tip hung on branch e, for every query sequence, every branch and every pendant
-// length, in one call (paml_amd_placement_scores); the definition and the kernels in kernels_place.h.
+// length, in one call (paml_amd_placement_scores); the definition in kernels_place.h, the kernels here.
 // Every P(t) comes from the evaluation's own builders (anc_pmat, engine_ancestral.hip), which run once per family of lengths: the upper
 // parts (1 - phi) t_v, the lower parts phi t_v, the pendant lengths (in the slots of the tips, every node labelled pendant_label), and last
 // the tree's own lengths, so that d_rowmajor and pmat_valid are left as after paml_amd_nni_scores.  The down pass is the ancestral
@@ -9,18 +9,107 @@
 #include "kernels_place.h"
 #include "ancestral_host.h"
 
-static thread_local int place_last_batches = 0;
-static thread_local double place_last_kernel_ms = 0;      // HIP events around the P(t) kernels and every batch's passes, summed
+static thread_local AncCallInfo place_info;
 
-extern "C" void paml_amd_placement_info(int *last_batches, double *last_kernel_ms)
+extern "C" void paml_amd_placement_info(int *last_batches, double *last_kernel_ms) { place_info.read(last_batches, last_kernel_ms); }
+
+namespace paml_amd {
+
+// one (pattern, class, edge) per lane: grid (patterns / 256, K, edges of the group)
+template <int N> __global__ __launch_bounds__(256) void place_lane_edge_kernel(PlaceArgs a)
 {
-   if (last_batches) *last_batches = place_last_batches;
-   if (last_kernel_ms) *last_kernel_ms = place_last_kernel_ms;
+   const long p = (long)blockIdx.x * 256 + threadIdx.x;
+   if (p >= a.o.m.nb) return;
+   place_lane_edge<N>(a, blockIdx.y, p, blockIdx.z);
 }
+
+// Matrix cores: four waves own ANC_TILE patterns of one class and loop over the group's edges; lane = q * 16 + pattern, register m =
+// state 4 m + q.  Per edge: H_v, one product with P_v^T((1 - phi) t), one product with P_v(phi t) (a tip: a gather from its column
+// table), W_v in registers; per (query, pendant) one gather from the pendant's column table and one dot product.  Grid (stride / ANC_TILE, K).
+__global__ __launch_bounds__(256) void place_mfma_kernel(PlaceArgs a)
+{
+   __shared__ __attribute__((aligned(16))) double sP[4096];
+   const AncMargArgs &m = a.o.m;
+   const AncTree &t = m.t;
+   const int tid = threadIdx.x, lane = tid & 63;
+   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+   const int q = lane >> 4, k = blockIdx.y;
+   const AncMfma w{sP, lane, wave, q};
+   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
+   const long pc = p < m.nb ? p : m.nb - 1;      // (lanes past the batch's end read the last pattern and write into the padding: p < stride)
+   const long pset = (long)m.gene * m.K + k;
+   const double *tabs = a.ptip_pend + pset * a.n_pend * m.tip_words;
+   for (int i = 0; i < a.n_group; i++) {
+      const int v = a.edges[a.edge0 + i], f = t.father[v];
+      double h[16], u[16], ls;
+      nni_mfma_father(m, k, g16, pc, lane, q, f, h, &ls);
+      for (int j = t.sons_ptr[f]; j < t.sons_ptr[f + 1]; j++)
+         if (t.sons[j] != v) anc_mfma_mul_son(m, w, k, g16, pc, t.sons[j], h, &ls);
+      const long slot = pset * t.n_nodes + v;
+      v4d acc[4];
+      w.product(a.PTup + slot * 4096, h, acc);      // U_v = P_v((1 - phi) t)^T H_v
+#pragma unroll
+      for (int j = 0; j < 16; j++) u[j] = acc[j >> 2][j & 3];
+      if (v < t.n_tips) {      // (uniform over the workgroup) D_v of a tip: its column table of P_v(phi t)
+         double2 tv[8];
+         tip_gather(a.ptip_dn + pset * t.n_nodes * m.tip_words, m.tip_words, v, (int)m.z[(long)v * m.z_stride + m.h0 + pc], q, tv);
+#pragma unroll
+         for (int j = 0; j < 8; j++) { u[2 * j] *= tv[j].x; u[2 * j + 1] *= tv[j].y; }
+      }
+      else {
+         const int vi = v - t.n_tips;
+         double x[16];
+         part_load(m.L + (((long)k * t.n_int + vi) * (m.stride >> 4) + g16) * 1024, lane, x);
+         w.product(a.pint_dn + slot * 4096, x, acc);      // D_v = P_v(phi t) L_v
+#pragma unroll
+         for (int j = 0; j < 16; j++) u[j] *= acc[j >> 2][j & 3];
+         ls += m.SL[((long)k * t.n_int + vi) * m.stride + pc];
+      }
+      for (int qi = 0; qi < a.n_q; qi++) {
+         const int code = (int)a.qz[(long)qi * m.z_stride + m.h0 + pc];
+         for (int j = 0; j < a.n_pend; j++) {
+            double2 tv[8];
+            tip_gather(tabs, m.tip_words, j, code, q, tv);
+            double y[16];
+#pragma unroll
+            for (int c = 0; c < 8; c++) { y[2 * c] = tv[c].x; y[2 * c + 1] = tv[c].y; }
+            const double fk = grad_mfma_dot(u, y);
+            const long oi = place_out_idx(a, k, place_row(a, i, qi, j), p);
+            if (q == 0) { a.f[oi] = fk; a.sig[oi] = ls; }
+         }
+      }
+   }
+}
+
+// the classes of every (row, pattern) and the chunks' sums: grid (stride / 256, rows of the slice); a wave = one chunk of GRAD_CHUNK
+// patterns.  row0: the slice's first row (a grid has 65535 rows at most)
+__global__ __launch_bounds__(256) void place_combine_kernel(PlaceArgs a, long row0)
+{
+   const long p = (long)blockIdx.x * 256 + threadIdx.x;
+   const long row = row0 + blockIdx.y;
+   double acc = p < a.o.m.nb ? place_combine(a, row, p) : 0.0;
+#pragma unroll
+   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+   const long chunk = a.o.chunk0 + (p >> 6);
+   if ((threadIdx.x & 63) == 0 && (p & ~63L) < a.o.m.nb) a.partial[place_out_row(a, row) * a.o.n_chunks + chunk] = acc;
+}
+
+// the present tree's row (the outer pass left f_hk and sigma in o.f / o.sig): grid (stride / 256)
+__global__ __launch_bounds__(256) void place_present_kernel(PlaceArgs a)
+{
+   const long p = (long)blockIdx.x * 256 + threadIdx.x;
+   double acc = p < a.o.m.nb ? nni_combine(a.o, 0, p) : 0.0;
+#pragma unroll
+   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+   const long chunk = a.o.chunk0 + (p >> 6);
+   if ((threadIdx.x & 63) == 0 && (p & ~63L) < a.o.m.nb) a.partial[(long)a.n_q * a.n_edges * a.n_pend * a.o.n_chunks + chunk] = acc;
+}
+}  // namespace paml_amd
 
 namespace {
 
 struct PlaceScratch : AncScratch {
+   using AncScratch::AncScratch;
    DevBuf<double> PT, Pup, Pdn, PTup, pint_dn, ptip_dn, Ppend, ptip_pend, f0, sig0, lnf0, f, sig, lnf, partial, out;
    DevBuf<int> edges, lab;
    DevBuf<unsigned char> qz;
@@ -31,33 +120,6 @@ struct PlaceScratch : AncScratch {
    }
 };
 
-void place_launch_lane(KernelKind kk, dim3 grid, hipStream_t st, const PlaceArgs &a, int pass)
-{
-   if (kk == KK_VALU4) hipLaunchKernelGGL(place_lane_kernel<4>, grid, dim3(256), 0, st, a, pass);
-   else if (kk == KK_VALU5) hipLaunchKernelGGL(place_lane_kernel<5>, grid, dim3(256), 0, st, a, pass);
-   else hipLaunchKernelGGL(place_lane_kernel<20>, grid, dim3(256), 0, st, a, pass);
-}
-
-void place_launch_lane_edge(KernelKind kk, dim3 grid, hipStream_t st, const PlaceArgs &a)
-{
-   if (kk == KK_VALU4) hipLaunchKernelGGL(place_lane_edge_kernel<4>, grid, dim3(256), 0, st, a);
-   else if (kk == KK_VALU5) hipLaunchKernelGGL(place_lane_edge_kernel<5>, grid, dim3(256), 0, st, a);
-   else hipLaunchKernelGGL(place_lane_edge_kernel<20>, grid, dim3(256), 0, st, a);
-}
-
-// the builder's P(t) at `branch` (labels `d_label`, null: the tree's), waited for; its kernel time is added to the call's
-int place_pmat(paml_amd_engine *e, const char *who, const double *branch, const double *gene_rate, PlaceScratch &w, const int *d_label)
-{
-   if (int rc = anc_pmat(e, who, branch, gene_rate, w, d_label)) return rc;
-   HIPCHK(hipEventRecord(w.ev1, e->stream));
-   HIPCHK(hipStreamSynchronize(e->stream));
-   if (int rc = eigen_fail_check(e)) return rc;
-   float ms = 0;
-   HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1));
-   place_last_kernel_ms += ms;
-   return 0;
-}
-
 }  // namespace
 
 extern "C" int paml_amd_placement_scores(paml_amd_engine *e, const double *branch, const double *gene_rate, int n_q, const unsigned char *qz,
@@ -65,8 +127,7 @@ extern "C" int paml_amd_placement_scores(paml_amd_engine *e, const double *branc
                                          double *lnL0, double *lnL, double *lnf)
 {
    enter(e);
-   place_last_batches = 0;
-   place_last_kernel_ms = 0;
+   place_info = AncCallInfo{};
    const char *who = "placement_scores";
    if (!e || !branch || !qz || !pendant || !lnL0 || !lnL) return fail(e, PAML_AMD_EINVAL, "placement_scores: null argument");
    if (n_q < 1) return fail(e, PAML_AMD_EINVAL, "placement_scores: n_q < 1");
@@ -116,7 +177,7 @@ extern "C" int paml_amd_placement_scores(paml_amd_engine *e, const double *branc
 
    const bool mfma = e->kk == KK_MFMA64;
    hipStream_t st = e->stream;
-   PlaceScratch w;
+   PlaceScratch w(place_info);
    PlaceArgs a{};
    NniArgs &o = a.o;
    AncMargArgs &m = o.m;
@@ -126,31 +187,11 @@ extern "C" int paml_amd_placement_scores(paml_amd_engine *e, const double *branc
       // the upper and the lower part of every branch
       std::vector<double> b(nn);
       for (int v = 0; v < nn; v++) b[v] = (1 - phi) * branch[v];
-      if (int rc = place_pmat(e, who, b.data(), gene_rate, w, nullptr)) return rc;
-      if (mfma) {
-         HIPCHK(w.PTup.ensure(pn * 4096));
-         hipLaunchKernelGGL(place_pt_kernel, dim3(nn, (unsigned)psets), dim3(256), 0, st, (const double *)e->d_rowmajor.p, w.PTup.p, n, nn, T.root);
-         HIPCHK(hipGetLastError());
-         HIPCHK(hipStreamSynchronize(st));
-      }
-      else {
-         HIPCHK(w.Pup.ensure(pn * nn2));
-         HIPCHK(hipMemcpyAsync(w.Pup.p, e->d_rowmajor.p, pn * nn2 * 8, hipMemcpyDeviceToDevice, st));
-         HIPCHK(hipStreamSynchronize(st));
-      }
+      if (int rc = anc_pmat_waited(e, who, b.data(), gene_rate, w)) return rc;
+      if (int rc = anc_keep_pmat(e, nullptr, nullptr, &w.PTup, w.Pup)) return rc;
       for (int v = 0; v < nn; v++) b[v] = phi * branch[v];
-      if (int rc = place_pmat(e, who, b.data(), gene_rate, w, nullptr)) return rc;
-      if (mfma) {
-         HIPCHK(w.pint_dn.ensure(pn * 4096));
-         HIPCHK(w.ptip_dn.ensure(pn * tw));
-         HIPCHK(hipMemcpyAsync(w.pint_dn.p, e->d_pint.p, pn * 4096 * 8, hipMemcpyDeviceToDevice, st));
-         HIPCHK(hipMemcpyAsync(w.ptip_dn.p, e->d_ptip.p, pn * tw * 8, hipMemcpyDeviceToDevice, st));
-      }
-      else {
-         HIPCHK(w.Pdn.ensure(pn * nn2));
-         HIPCHK(hipMemcpyAsync(w.Pdn.p, e->d_rowmajor.p, pn * nn2 * 8, hipMemcpyDeviceToDevice, st));
-      }
-      HIPCHK(hipStreamSynchronize(st));
+      if (int rc = anc_pmat_waited(e, who, b.data(), gene_rate, w)) return rc;
+      if (int rc = anc_keep_pmat(e, &w.pint_dn, &w.ptip_dn, nullptr, w.Pdn)) return rc;
       // the pendant lengths, as many per run of the builder as the tree has tips
       std::vector<int> lab(nn, pendant_label);
       HIPCHK(upload(w.lab, lab.data(), lab.size(), st));
@@ -161,7 +202,7 @@ extern "C" int paml_amd_placement_scores(paml_amd_engine *e, const double *branc
          const int nj = std::min<int>((int)slots.size(), n_pend - j0);
          std::fill(b.begin(), b.end(), 0.0);
          for (int j = 0; j < nj; j++) b[slots[j]] = pendant[j0 + j];
-         if (int rc = place_pmat(e, who, b.data(), gene_rate, w, w.lab.p)) return rc;
+         if (int rc = anc_pmat_waited(e, who, b.data(), gene_rate, w, w.lab.p)) return rc;
          for (size_t ps = 0; ps < psets; ps++)
             for (int j = 0; j < nj; j++) {
                const size_t from = ps * nn + slots[j], to = ps * n_pend + j0 + j;
@@ -175,20 +216,15 @@ extern "C" int paml_amd_placement_scores(paml_amd_engine *e, const double *branc
    if (int rc = anc_pmat(e, who, branch, gene_rate, w)) return rc;
    if (mfma) {
       HIPCHK(w.PT.ensure(pn * 4096));
-      hipLaunchKernelGGL(place_unit_nni_pt_kernel, dim3(nn, (unsigned)psets), dim3(256), 0, st, (const double *)e->d_rowmajor.p, w.PT.p, n, nn, n_tips, T.root);
+      hipLaunchKernelGGL(nni_pt_kernel, dim3(nn, (unsigned)psets), dim3(256), 0, st, (const double *)e->d_rowmajor.p, w.PT.p, n, nn, n_tips, T.root);
       HIPCHK(hipGetLastError());
    }
    HIPCHK(upload(w.edges, edge_list.data(), edge_list.size(), st));
    HIPCHK(upload(w.qz, qcodes.data(), qcodes.size(), st));
-   HIPCHK(hipEventRecord(w.ev1, st));
-   HIPCHK(hipStreamSynchronize(st));
-   if (int rc = eigen_fail_check(e)) return rc;
+   if (int rc = anc_pmat_wait(e, w)) return rc;
    e->pmat_valid = true;      // (d_rowmajor holds every branch's P(t) in the tree's own orientation, as after the gradient)
-   { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); place_last_kernel_ms += ms; }
 
-   // chunks of GRAD_CHUNK patterns counted from each gene's first pattern: a batch is whole chunks of one gene
-   std::vector<long> chunk_base(G + 1, 0);
-   for (int g = 0; g < G; g++) chunk_base[g + 1] = chunk_base[g] + (e->gene_off[g + 1] - e->gene_off[g] + GRAD_CHUNK - 1) / GRAD_CHUNK;
+   const std::vector<long> chunk_base = anc_chunk_base(e);
    const long n_chunks = chunk_base[G];
    const long rows_edge = (long)n_q * n_pend, n_rows = rows_edge * n_edges;
    HIPCHK(w.partial.ensure((size_t)(n_rows + 1) * std::max<long>(n_chunks, 1)));
@@ -197,90 +233,51 @@ extern "C" int paml_amd_placement_scores(paml_amd_engine *e, const double *branc
    // the workspace per pattern: the partials and the messages, then (2 K + 1) doubles per row (the present tree's, and n_q n_pend per edge of a group)
    const int ns = mfma ? 64 : n;      // doubles a partial takes per pattern
    const double fixed = 2.0 * K * n_int * (ns + 1) * 8 + (2.0 * K + 1) * 8, per_edge = (2.0 * K + 1) * 8 * rows_edge;
-   double arena_mb = 256;
-   if (const char *s = getenv("PAML_AMD_PLACE_ARENA_MB")) { const double v = atof(s); if (v > 0) arena_mb = v; }
+   const double arena_mb = anc_arena_mb("PAML_AMD_PLACE_ARENA_MB");
    int cap = n_edges;
    if ((fixed + per_edge * n_edges) * ANC_TILE > arena_mb * 1048576.0)      // one tile with all rows does not fit: groups of edges
       cap = (int)std::min<double>(n_edges, std::max(1.0, floor((arena_mb * 1048576.0 / ANC_TILE - fixed) / per_edge)));
    cap = std::min(cap, 65535);      // (the lanes' edge pass has a grid layer per edge)
    long batch = anc_batch(fixed + per_edge * cap, n_patt, "PAML_AMD_PLACE_ARENA_MB");
-   for (;;) {      // halve the batch until it fits
-      const size_t part = (size_t)K * n_int * ns * batch, sc = (size_t)K * n_int * batch, rows = (size_t)K * cap * rows_edge * batch;
-      if (w.L.ensure(part) == hipSuccess && w.G.ensure(part) == hipSuccess && w.SL.ensure(sc) == hipSuccess && w.SG.ensure(sc) == hipSuccess &&
-          w.f0.ensure((size_t)K * batch) == hipSuccess && w.sig0.ensure((size_t)K * batch) == hipSuccess && w.lnf0.ensure((size_t)batch) == hipSuccess &&
-          w.f.ensure(rows) == hipSuccess && w.sig.ensure(rows) == hipSuccess && w.lnf.ensure((size_t)cap * rows_edge * batch) == hipSuccess)
-         break;
-      (void)hipGetLastError();
-      for (DevBuf<double> *b : {&w.L, &w.G, &w.SL, &w.SG, &w.f0, &w.sig0, &w.lnf0, &w.f, &w.sig, &w.lnf}) b->release();      // (ensure only grows: the retry starts from nothing)
-      if (batch <= ANC_TILE) return fail(e, PAML_AMD_ENOMEM, "placement_scores: no device memory for one tile of patterns");
-      batch = (batch / 2 + ANC_TILE - 1) / ANC_TILE * ANC_TILE;
+   {
+      const size_t part = (size_t)K * n_int * ns, sc = (size_t)K * n_int, rows = (size_t)K * cap * rows_edge;
+      if (int rc = anc_alloc(e, who, {{&w.L, part}, {&w.G, part}, {&w.SL, sc}, {&w.SG, sc}, {&w.f0, (size_t)K}, {&w.sig0, (size_t)K}, {&w.lnf0, 1},
+                                      {&w.f, rows}, {&w.sig, rows}, {&w.lnf, (size_t)cap * rows_edge}}, &batch))
+         return rc;
    }
-   m.n = n; m.K = K; m.scaled = T.n_scale > 0 ? 1 : 0; m.n_pi = e->n_pi; m.stride = batch;
-   m.z = e->d_z.p; m.z_stride = n_patt; m.code_mask = e->d_code_mask.p;
-   m.P = e->d_rowmajor.p; m.pint = e->d_pint.p; m.ptip = e->d_ptip.p; m.tip_words = (long)tw;
-   m.pi = e->d_pi_plain.p; m.freqK = e->d_freqK.p;
-   m.L = w.L.p; m.G = w.G.p; m.SL = w.SL.p; m.SG = w.SG.p; m.mfma = mfma ? 1 : 0;
+   anc_fill(e, w, batch, m);
    o.PT = w.PT.p; o.cap = 0; o.f = w.f0.p; o.sig = w.sig0.p; o.weights = e->d_weights.p; o.lnf = w.lnf0.p; o.n_chunks = n_chunks;
    o.ref_node = T.sons[T.sons_ptr[T.root]];
    a.Pup = w.Pup.p; a.Pdn = w.Pdn.p; a.PTup = w.PTup.p; a.pint_dn = w.pint_dn.p; a.ptip_dn = w.ptip_dn.p; a.Ppend = w.Ppend.p; a.ptip_pend = w.ptip_pend.p;
    a.qz = w.qz.p; a.edges = w.edges.p; a.n_q = n_q; a.n_pend = n_pend; a.n_edges = n_edges; a.cap = cap;
    a.f = w.f.p; a.sig = w.sig.p; a.lnf = w.lnf.p; a.partial = w.partial.p;
-   for (int g = 0; g < G; g++)
-      for (long h0 = e->gene_off[g]; h0 < e->gene_off[g + 1]; h0 += batch) {
-         const long nb = std::min<long>(batch, e->gene_off[g + 1] - h0);
-         m.gene = g; m.h0 = h0; m.nb = nb;
-         o.chunk0 = chunk_base[g] + (h0 - e->gene_off[g]) / GRAD_CHUNK;
-         a.edge0 = 0; a.n_group = 0;
-         const dim3 tiles((unsigned)((nb + ANC_TILE - 1) / ANC_TILE), K), lanes((unsigned)((nb + 255) / 256), K);
-         HIPCHK(hipEventRecord(w.ev0, st));
-         if (mfma) {
-            hipLaunchKernelGGL(place_unit_anc_mfma_kernel, tiles, dim3(256), 0, st, m, 0);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(place_unit_nni_mfma_outer_kernel, tiles, dim3(256), 0, st, o);
-            HIPCHK(hipGetLastError());
-         }
-         else
-            for (int pass = 0; pass < 2; pass++) {
-               place_launch_lane(e->kk, lanes, st, a, pass);
-               HIPCHK(hipGetLastError());
-            }
-         hipLaunchKernelGGL(place_present_kernel, dim3(lanes.x), dim3(256), 0, st, a);
-         HIPCHK(hipGetLastError());
-         HIPCHK(hipEventRecord(w.ev1, st));
-         for (int e0 = 0; e0 < n_edges; e0 += cap) {
-            const int ng = std::min(cap, n_edges - e0);
-            a.edge0 = e0; a.n_group = ng;
-            if (e0) {      // (the batch's first group is timed with its down and outer passes)
-               HIPCHK(hipStreamSynchronize(st));
-               { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); place_last_kernel_ms += ms; }
-               HIPCHK(hipEventRecord(w.ev0, st));
-            }
-            if (mfma) hipLaunchKernelGGL(place_mfma_kernel, tiles, dim3(256), 0, st, a);
-            else place_launch_lane_edge(e->kk, dim3(lanes.x, K, ng), st, a);
-            HIPCHK(hipGetLastError());
-            const long rows = rows_edge * ng;
-            for (long r0 = 0; r0 < rows; r0 += 65535) {
-               hipLaunchKernelGGL(place_combine_kernel, dim3(lanes.x, (unsigned)std::min<long>(65535, rows - r0)), dim3(256), 0, st, a, r0);
-               HIPCHK(hipGetLastError());
-            }
-            HIPCHK(hipEventRecord(w.ev1, st));
-            // the group's rows to the caller's [n_q][n_edges][n_pend][n_patt]: one plain copy per row
-            if (lnf)
-               for (long r = 0; r < rows; r++)
-                  HIPCHK(hipMemcpyAsync(lnf + (size_t)place_out_row(a, r) * n_patt + h0, w.lnf.p + (size_t)r * batch, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-         }
-         HIPCHK(hipStreamSynchronize(st));
-         { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); place_last_kernel_ms += ms; }
-         place_last_batches++;
-      }
-   HIPCHK(hipEventRecord(w.ev0, st));
-   hipLaunchKernelGGL(place_unit_grad_total_kernel, dim3((unsigned)(n_rows + 1)), dim3(256), 0, st, (const double *)w.partial.p, n_chunks, w.out.p);
-   HIPCHK(hipGetLastError());
-   HIPCHK(hipEventRecord(w.ev1, st));
+   auto group = [&](int gi) { a.edge0 = gi * cap; a.n_group = std::min(cap, n_edges - a.edge0); };      // groups of `cap` edges in list order
+   if (int rc = anc_score_batches(
+          e, w, o, chunk_base, batch, (n_edges + cap - 1) / cap,
+          [&](dim3 lanes, int pass) { anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(nni_lane_kernel<N()>, lanes, dim3(256), 0, st, o, pass); }); },
+          [&](dim3 lanes) {
+             a.edge0 = 0; a.n_group = 0;
+             hipLaunchKernelGGL(place_present_kernel, dim3(lanes.x), dim3(256), 0, st, a);
+          },
+          [&](int gi, dim3 tiles, dim3 lanes) {
+             group(gi);
+             if (mfma) hipLaunchKernelGGL(place_mfma_kernel, tiles, dim3(256), 0, st, a);
+             else anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(place_lane_edge_kernel<N()>, dim3(lanes.x, K, a.n_group), dim3(256), 0, st, a); });
+          },
+          [&](int, dim3 lanes) {      // (a grid has 65535 rows at most)
+             const long rows = rows_edge * a.n_group;
+             for (long r0 = 0; r0 < rows; r0 += 65535)
+                hipLaunchKernelGGL(place_combine_kernel, dim3(lanes.x, (unsigned)std::min<long>(65535, rows - r0)), dim3(256), 0, st, a, r0);
+          },
+          [&](int, long h0, long nb) {      // the group's rows to the caller's [n_q][n_edges][n_pend][n_patt]: one plain copy per row
+             if (lnf)
+                for (long r = 0; r < rows_edge * a.n_group; r++)
+                   HIPCHK(hipMemcpyAsync(lnf + (size_t)place_out_row(a, r) * n_patt + h0, w.lnf.p + (size_t)r * batch, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+             return 0;
+          }))
+      return rc;
    std::vector<double> out((size_t)n_rows + 1);
-   HIPCHK(hipMemcpyAsync(out.data(), w.out.p, ((size_t)n_rows + 1) * 8, hipMemcpyDeviceToHost, st));
-   HIPCHK(hipStreamSynchronize(st));
-   { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); place_last_kernel_ms += ms; }
+   if (int rc = anc_totals(e, w, w.partial.p, n_chunks, w.out.p, out)) return rc;
    for (long i = 0; i < n_rows; i++) lnL[i] = out[i];
    *lnL0 = out[n_rows];
    return 0;

@@ -1,5 +1,5 @@
 // engine_spr.hip — the lnL of every requested subtree-prune-and-regraft neighbour of the tree at the present branch lengths in one call
-// (paml_amd_spr_scores) and the canonical list of moves (paml_amd_spr_list, host only); the definition and the kernels in kernels_spr.h,
+// (paml_amd_spr_scores) and the canonical list of moves (paml_amd_spr_list, host only); the definition in kernels_spr.h, the kernels here,
 // the lists of steps in spr_plan.h.
 // Every P(t) comes from the evaluation's own builder (anc_pmat, engine_ancestral.hip), which runs once per family of lengths on a branch
 // vector of the tree's size with the tree's own labels: the upper parts (1 - phi) t_v, the lower parts phi t_v, the merged lengths
@@ -10,14 +10,94 @@
 #include "kernels_spr.h"
 #include "ancestral_host.h"
 
-static thread_local int spr_last_batches = 0;
-static thread_local double spr_last_kernel_ms = 0;      // HIP events around the P(t) kernels and every batch's passes, summed
+static thread_local AncCallInfo spr_info;
 
-extern "C" void paml_amd_spr_info(int *last_batches, double *last_kernel_ms)
+extern "C" void paml_amd_spr_info(int *last_batches, double *last_kernel_ms) { spr_info.read(last_batches, last_kernel_ms); }
+
+namespace paml_amd {
+
+// one pattern per lane: grid (patterns / 256, K); pass 0: the down pass, 1: the outer pass, 2: the group's prunes
+template <int N> __global__ __launch_bounds__(256) void spr_lane_kernel(SprArgs a, int pass)
 {
-   if (last_batches) *last_batches = spr_last_batches;
-   if (last_kernel_ms) *last_kernel_ms = spr_last_kernel_ms;
+   const long p = (long)blockIdx.x * 256 + threadIdx.x;
+   if (p >= a.o.m.nb) return;
+   if (pass == 0) anc_lane_down<N>(a.o.m, blockIdx.y, p);
+   else if (pass == 1) nni_lane_outer<N>(a.o, blockIdx.y, p);
+   else
+      for (int ip = a.prune0; ip < a.prune0 + a.n_prunes; ip++) spr_lane_prune<N>(a, blockIdx.y, p, ip);
 }
+
+// Matrix cores: four waves own ANC_TILE patterns of one class and loop over the group's prunes and their steps; lane = q * 16 + pattern,
+// register m = state 4 m + q.  Every branch below is uniform over the workgroup (the steps are the same for all patterns), so the
+// barriers inside the products are met by all four waves.  Grid (stride / ANC_TILE, K).
+__global__ __launch_bounds__(256) void spr_mfma_kernel(SprArgs a)
+{
+   __shared__ __attribute__((aligned(16))) double sP[4096];
+   const AncMargArgs &m = a.o.m;
+   const AncTree &t = m.t;
+   const int tid = threadIdx.x, lane = tid & 63, n = m.n;
+   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+   const int q = lane >> 4, k = blockIdx.y;
+   const AncMfma w{sP, lane, wave, q};
+   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
+   const long pc = p < m.nb ? p : m.nb - 1;      // (lanes past the batch's end read the last pattern and write into the padding: p < stride)
+   const long pset = (long)m.gene * m.K + k;
+   const long part = (long)k * t.n_int * (m.stride >> 4) + g16, sc = (long)k * t.n_int * m.stride;      // (+ node * (stride >> 4), * 1024; + node * stride)
+   for (int ip = a.prune0; ip < a.prune0 + a.n_prunes; ip++) {
+      const int *pr = a.prunes + (long)SPR_PRUNE_INTS * ip;
+      double ms[16], ls_s = 0;      // P_s L_s, once per s
+#pragma unroll
+      for (int j = 0; j < 16; j++) ms[j] = 4 * j + q < n ? 1.0 : 0.0;
+      spr_mfma_mul(m, w, m.pint, m.ptip, m.L, m.SL, k, g16, pc, pr[0], ms, &ls_s);
+      for (int is = pr[1]; is < pr[1] + pr[2]; is++) {
+         const int *st = a.steps + (long)SPR_STEP_INTS * is;
+         const int op = st[0], node = st[1];
+         double h[16], ls = 0;
+         __syncthreads();      // (SLp / SAp of an earlier step were stored by the pattern's q = 0 lane: a workgroup-scope fence before the other lanes read them)
+         if (st[2] == SPR_HEAD_ONES) {
+#pragma unroll
+            for (int j = 0; j < 16; j++) h[j] = 4 * j + q < n ? 1.0 : 0.0;
+         }
+         else if (st[2] == SPR_HEAD_PRESENT) nni_mfma_father(m, k, g16, pc, lane, q, st[3], h, &ls);
+         else {
+            const int fi = st[3] - t.n_tips;
+            part_load(a.Ap + (part + (long)fi * (m.stride >> 4)) * 1024, lane, h);      // (this lane's own stores)
+            ls = a.SAp[sc + (long)fi * m.stride + pc];
+         }
+         for (int j = st[4]; j < st[4] + st[5]; j++) {
+            const int kind = a.factors[2 * j], u = a.factors[2 * j + 1];
+            if (kind == SPR_FAC_PRESENT) spr_mfma_mul(m, w, m.pint, m.ptip, m.L, m.SL, k, g16, pc, u, h, &ls);
+            else if (kind == SPR_FAC_MERGED) spr_mfma_mul(m, w, a.pint_m, a.ptip_m, m.L, m.SL, k, g16, pc, u, h, &ls);
+            else spr_mfma_mul(m, w, m.pint, m.ptip, a.Lp, a.SLp, k, g16, pc, u, h, &ls);
+         }
+         const long slot = pset * t.n_nodes + node;
+         if (op == SPR_UP) {
+            const int vi = node - t.n_tips;
+            spr_mfma_rescale(m, h, &ls);
+            part_store(a.Lp + (part + (long)vi * (m.stride >> 4)) * 1024, lane, h);
+            if (q == 0) a.SLp[sc + (long)vi * m.stride + p] = ls;
+            continue;
+         }
+         v4d acc[4];
+         w.product((op == SPR_OUT ? (st[6] ? a.PTm : a.o.PT) : a.PTup) + slot * 4096, h, acc);      // P^T H'
+         double u[16];
+#pragma unroll
+         for (int j = 0; j < 16; j++) u[j] = acc[j >> 2][j & 3];
+         if (op == SPR_OUT) {
+            const int vi = node - t.n_tips;
+            spr_mfma_rescale(m, u, &ls);
+            part_store(a.Ap + (part + (long)vi * (m.stride >> 4)) * 1024, lane, u);
+            if (q == 0) a.SAp[sc + (long)vi * m.stride + p] = ls;
+            continue;
+         }
+         spr_mfma_mul(m, w, a.pint_dn, a.ptip_dn, st[6] ? a.Lp : m.L, st[6] ? a.SLp : m.SL, k, g16, pc, node, u, &ls);      // W
+         const double fk = grad_mfma_dot(u, ms);
+         const long oi = nni_out_idx(a.o, k, st[7] - a.o.swap0, p);
+         if (q == 0) { a.o.f[oi] = fk; a.o.sig[oi] = ls + ls_s; }
+      }
+   }
+}
+}  // namespace paml_amd
 
 extern "C" int paml_amd_spr_list(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, int radius, int *moves, int cap)
 {
@@ -29,6 +109,7 @@ extern "C" int paml_amd_spr_list(int n_tips, int n_nodes, int root, const int *s
 namespace {
 
 struct SprScratch : AncScratch {
+   using AncScratch::AncScratch;
    DevBuf<double> PT, Pup, Pdn, Pm, PTup, pint_dn, ptip_dn, pint_m, ptip_m, PTm, Lp, Ap, SLp, SAp, f, sig, lnf, partial, out;
    DevBuf<int> plan;
    ~SprScratch()
@@ -38,34 +119,13 @@ struct SprScratch : AncScratch {
    }
 };
 
-void spr_launch_lane(KernelKind kk, dim3 grid, hipStream_t st, const SprArgs &a, int pass)
-{
-   if (kk == KK_VALU4) hipLaunchKernelGGL(spr_lane_kernel<4>, grid, dim3(256), 0, st, a, pass);
-   else if (kk == KK_VALU5) hipLaunchKernelGGL(spr_lane_kernel<5>, grid, dim3(256), 0, st, a, pass);
-   else hipLaunchKernelGGL(spr_lane_kernel<20>, grid, dim3(256), 0, st, a, pass);
-}
-
-// the builder's P(t) at `branch` with the tree's labels, waited for; its kernel time is added to the call's
-int spr_pmat(paml_amd_engine *e, const char *who, const double *branch, const double *gene_rate, SprScratch &w)
-{
-   if (int rc = anc_pmat(e, who, branch, gene_rate, w)) return rc;
-   HIPCHK(hipEventRecord(w.ev1, e->stream));
-   HIPCHK(hipStreamSynchronize(e->stream));
-   if (int rc = eigen_fail_check(e)) return rc;
-   float ms = 0;
-   HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1));
-   spr_last_kernel_ms += ms;
-   return 0;
-}
-
 }  // namespace
 
 extern "C" int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, const double *gene_rate, int n_moves, const int *moves, double phi,
                                    double *lnL0, double *lnL, double *lnf)
 {
    enter(e);
-   spr_last_batches = 0;
-   spr_last_kernel_ms = 0;
+   spr_info = AncCallInfo{};
    const char *who = "spr_scores";
    if (!e || !branch || !moves || !lnL0 || !lnL) return fail(e, PAML_AMD_EINVAL, "spr_scores: null argument");
    if (n_moves < 1) return fail(e, PAML_AMD_EINVAL, "spr_scores: n_moves < 1");
@@ -88,62 +148,29 @@ extern "C" int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, con
 
    const bool mfma = e->kk == KK_MFMA64;
    hipStream_t st = e->stream;
-   SprScratch w;
+   SprScratch w(spr_info);
    SprArgs a{};
    NniArgs &o = a.o;
    AncMargArgs &m = o.m;
    if (int rc = anc_tree_pack(e, who, w, &m.t)) return rc;
-   const size_t psets = (size_t)G * K, pn = psets * nn, nn2 = (size_t)n * n, tw = tip_words(e);
    {
-      // one run of the builder per family; what the kernels need of it is copied before the next run
+      // one run of the builder per family; what the kernels need of it is kept before the next run
       std::vector<double> b(nn);
       for (int v = 0; v < nn; v++) b[v] = (1 - phi) * branch[v];
-      if (int rc = spr_pmat(e, who, b.data(), gene_rate, w)) return rc;
-      if (mfma) {
-         HIPCHK(w.PTup.ensure(pn * 4096));
-         hipLaunchKernelGGL(spr_pt_kernel, dim3(nn, (unsigned)psets), dim3(256), 0, st, (const double *)e->d_rowmajor.p, w.PTup.p, n, nn, T.root);
-         HIPCHK(hipGetLastError());
-      }
-      else {
-         HIPCHK(w.Pup.ensure(pn * nn2));
-         HIPCHK(hipMemcpyAsync(w.Pup.p, e->d_rowmajor.p, pn * nn2 * 8, hipMemcpyDeviceToDevice, st));
-      }
-      HIPCHK(hipStreamSynchronize(st));
+      if (int rc = anc_pmat_waited(e, who, b.data(), gene_rate, w)) return rc;
+      if (int rc = anc_keep_pmat(e, nullptr, nullptr, &w.PTup, w.Pup)) return rc;
       for (int v = 0; v < nn; v++) b[v] = phi * branch[v];
-      if (int rc = spr_pmat(e, who, b.data(), gene_rate, w)) return rc;
-      if (mfma) {
-         HIPCHK(w.pint_dn.ensure(pn * 4096));
-         HIPCHK(w.ptip_dn.ensure(pn * tw));
-         HIPCHK(hipMemcpyAsync(w.pint_dn.p, e->d_pint.p, pn * 4096 * 8, hipMemcpyDeviceToDevice, st));
-         HIPCHK(hipMemcpyAsync(w.ptip_dn.p, e->d_ptip.p, pn * tw * 8, hipMemcpyDeviceToDevice, st));
-      }
-      else {
-         HIPCHK(w.Pdn.ensure(pn * nn2));
-         HIPCHK(hipMemcpyAsync(w.Pdn.p, e->d_rowmajor.p, pn * nn2 * 8, hipMemcpyDeviceToDevice, st));
-      }
-      HIPCHK(hipStreamSynchronize(st));
+      if (int rc = anc_pmat_waited(e, who, b.data(), gene_rate, w)) return rc;
+      if (int rc = anc_keep_pmat(e, &w.pint_dn, &w.ptip_dn, nullptr, w.Pdn)) return rc;
       for (int v = 0; v < nn; v++) b[v] = branch[v] + (father[v] >= 0 && father[v] != T.root ? branch[father[v]] : 0.0);
-      if (int rc = spr_pmat(e, who, b.data(), gene_rate, w)) return rc;
-      if (mfma) {
-         HIPCHK(w.pint_m.ensure(pn * 4096));
-         HIPCHK(w.ptip_m.ensure(pn * tw));
-         HIPCHK(w.PTm.ensure(pn * 4096));
-         HIPCHK(hipMemcpyAsync(w.pint_m.p, e->d_pint.p, pn * 4096 * 8, hipMemcpyDeviceToDevice, st));
-         HIPCHK(hipMemcpyAsync(w.ptip_m.p, e->d_ptip.p, pn * tw * 8, hipMemcpyDeviceToDevice, st));
-         hipLaunchKernelGGL(spr_pt_kernel, dim3(nn, (unsigned)psets), dim3(256), 0, st, (const double *)e->d_rowmajor.p, w.PTm.p, n, nn, T.root);
-         HIPCHK(hipGetLastError());
-      }
-      else {
-         HIPCHK(w.Pm.ensure(pn * nn2));
-         HIPCHK(hipMemcpyAsync(w.Pm.p, e->d_rowmajor.p, pn * nn2 * 8, hipMemcpyDeviceToDevice, st));
-      }
-      HIPCHK(hipStreamSynchronize(st));
+      if (int rc = anc_pmat_waited(e, who, b.data(), gene_rate, w)) return rc;
+      if (int rc = anc_keep_pmat(e, &w.pint_m, &w.ptip_m, &w.PTm, w.Pm)) return rc;
    }
    // the tree's own lengths last: what the passes read, and what the engine keeps
    if (int rc = anc_pmat(e, who, branch, gene_rate, w)) return rc;
    if (mfma) {
-      HIPCHK(w.PT.ensure(pn * 4096));
-      hipLaunchKernelGGL(spr_pt_kernel, dim3(nn, (unsigned)psets), dim3(256), 0, st, (const double *)e->d_rowmajor.p, w.PT.p, n, nn, T.root);
+      HIPCHK(w.PT.ensure((size_t)G * K * nn * 4096));
+      hipLaunchKernelGGL(nni_pt_all_kernel, dim3(nn, (unsigned)(G * K)), dim3(256), 0, st, (const double *)e->d_rowmajor.p, w.PT.p, n, nn, T.root);
       HIPCHK(hipGetLastError());
    }
    const size_t o_steps = plan.prunes.size(), o_factors = o_steps + plan.steps.size();
@@ -153,16 +180,11 @@ extern "C" int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, con
       pack.insert(pack.end(), plan.factors.begin(), plan.factors.end());
       pack.push_back(0);      // (a list without factors still has a buffer)
       HIPCHK(upload(w.plan, pack.data(), pack.size(), st));
-      HIPCHK(hipEventRecord(w.ev1, st));
-      HIPCHK(hipStreamSynchronize(st));      // (`pack` is on this stack)
+      if (int rc = anc_pmat_wait(e, w)) return rc;      // (`pack` is on this stack)
    }
-   if (int rc = eigen_fail_check(e)) return rc;
    e->pmat_valid = true;      // (d_rowmajor holds every branch's P(t) in the tree's own orientation, as after the gradient)
-   { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); spr_last_kernel_ms += ms; }
 
-   // chunks of GRAD_CHUNK patterns counted from each gene's first pattern: a batch is whole chunks of one gene
-   std::vector<long> chunk_base(G + 1, 0);
-   for (int g = 0; g < G; g++) chunk_base[g + 1] = chunk_base[g] + (e->gene_off[g + 1] - e->gene_off[g] + GRAD_CHUNK - 1) / GRAD_CHUNK;
+   const std::vector<long> chunk_base = anc_chunk_base(e);
    const long n_chunks = chunk_base[G];
    HIPCHK(w.partial.ensure((size_t)(n_moves + 1) * std::max<long>(n_chunks, 1)));
    HIPCHK(w.out.ensure((size_t)n_moves + 1));
@@ -171,8 +193,7 @@ extern "C" int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, con
    // group and the present tree)
    const int ns = mfma ? 64 : n;      // doubles a partial takes per pattern
    const double fixed = 4.0 * K * n_int * (ns + 1) * 8, per_row = (2.0 * K + 1) * 8;
-   double arena_mb = 256;
-   if (const char *s = getenv("PAML_AMD_SPR_ARENA_MB")) { const double v = atof(s); if (v > 0) arena_mb = v; }
+   const double arena_mb = anc_arena_mb("PAML_AMD_SPR_ARENA_MB");
    int cap = n_moves;
    const double all_patt = (double)((n_patt + ANC_TILE - 1) / ANC_TILE * ANC_TILE);
    if ((fixed + per_row * (n_moves + 1)) * all_patt > arena_mb * 1048576.0)      // batches of patterns: the rows take no more of the workspace than
@@ -192,22 +213,13 @@ extern "C" int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, con
       group_first.push_back(plan.n_prunes());
    }
    long batch = anc_batch(fixed + per_row * (cap + 1), n_patt, "PAML_AMD_SPR_ARENA_MB");
-   for (;;) {      // halve the batch until it fits
-      const size_t part = (size_t)K * n_int * ns * batch, sc = (size_t)K * n_int * batch, rows = (size_t)K * (cap + 1) * batch;
-      if (w.L.ensure(part) == hipSuccess && w.G.ensure(part) == hipSuccess && w.SL.ensure(sc) == hipSuccess && w.SG.ensure(sc) == hipSuccess &&
-          w.Lp.ensure(part) == hipSuccess && w.Ap.ensure(part) == hipSuccess && w.SLp.ensure(sc) == hipSuccess && w.SAp.ensure(sc) == hipSuccess &&
-          w.f.ensure(rows) == hipSuccess && w.sig.ensure(rows) == hipSuccess && w.lnf.ensure((size_t)(cap + 1) * batch) == hipSuccess)
-         break;
-      (void)hipGetLastError();
-      for (DevBuf<double> *b : {&w.L, &w.G, &w.SL, &w.SG, &w.Lp, &w.Ap, &w.SLp, &w.SAp, &w.f, &w.sig, &w.lnf}) b->release();      // (ensure only grows: the retry starts from nothing)
-      if (batch <= ANC_TILE) return fail(e, PAML_AMD_ENOMEM, "spr_scores: no device memory for one tile of patterns");
-      batch = (batch / 2 + ANC_TILE - 1) / ANC_TILE * ANC_TILE;
+   {
+      const size_t part = (size_t)K * n_int * ns, sc = (size_t)K * n_int, rows = (size_t)K * (cap + 1);
+      if (int rc = anc_alloc(e, who, {{&w.L, part}, {&w.G, part}, {&w.SL, sc}, {&w.SG, sc}, {&w.Lp, part}, {&w.Ap, part}, {&w.SLp, sc}, {&w.SAp, sc},
+                                      {&w.f, rows}, {&w.sig, rows}, {&w.lnf, (size_t)cap + 1}}, &batch))
+         return rc;
    }
-   m.n = n; m.K = K; m.scaled = T.n_scale > 0 ? 1 : 0; m.n_pi = e->n_pi; m.stride = batch;
-   m.z = e->d_z.p; m.z_stride = n_patt; m.code_mask = e->d_code_mask.p;
-   m.P = e->d_rowmajor.p; m.pint = e->d_pint.p; m.ptip = e->d_ptip.p; m.tip_words = (long)tw;
-   m.pi = e->d_pi_plain.p; m.freqK = e->d_freqK.p;
-   m.L = w.L.p; m.G = w.G.p; m.SL = w.SL.p; m.SG = w.SG.p; m.mfma = mfma ? 1 : 0;
+   anc_fill(e, w, batch, m);
    o.PT = w.PT.p; o.cap = cap; o.n_swaps = n_moves; o.f = w.f.p; o.sig = w.sig.p; o.weights = e->d_weights.p;
    o.lnf = w.lnf.p; o.partial = w.partial.p; o.n_chunks = n_chunks;
    o.ref_node = T.sons[T.sons_ptr[T.root]];
@@ -215,60 +227,31 @@ extern "C" int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, con
    a.pint_m = w.pint_m.p; a.ptip_m = w.ptip_m.p; a.PTm = w.PTm.p;
    a.prunes = w.plan.p; a.steps = w.plan.p + o_steps; a.factors = w.plan.p + o_factors;
    a.Lp = w.Lp.p; a.Ap = w.Ap.p; a.SLp = w.SLp.p; a.SAp = w.SAp.p;
-   for (int g = 0; g < G; g++)
-      for (long h0 = e->gene_off[g]; h0 < e->gene_off[g + 1]; h0 += batch) {
-         const long nb = std::min<long>(batch, e->gene_off[g + 1] - h0);
-         m.gene = g; m.h0 = h0; m.nb = nb;
-         o.chunk0 = chunk_base[g] + (h0 - e->gene_off[g]) / GRAD_CHUNK;
-         o.swap0 = 0; o.n_group = 0;
-         const dim3 tiles((unsigned)((nb + ANC_TILE - 1) / ANC_TILE), K), lanes((unsigned)((nb + 255) / 256), K);
-         HIPCHK(hipEventRecord(w.ev0, st));
-         if (mfma) {
-            hipLaunchKernelGGL(spr_unit_anc_mfma_kernel, tiles, dim3(256), 0, st, m, 0);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(spr_unit_nni_mfma_outer_kernel, tiles, dim3(256), 0, st, o);
-            HIPCHK(hipGetLastError());
-         }
-         else
-            for (int pass = 0; pass < 2; pass++) {
-               spr_launch_lane(e->kk, lanes, st, a, pass);
-               HIPCHK(hipGetLastError());
-            }
-         HIPCHK(hipEventRecord(w.ev1, st));
-         for (size_t gi = 0; gi + 1 < group_first.size(); gi++) {
-            const int ip0 = group_first[gi], ip1 = group_first[gi + 1];
-            const int r0 = plan.prunes[SPR_PRUNE_INTS * ip0 + 3], r1 = ip1 < plan.n_prunes() ? plan.prunes[SPR_PRUNE_INTS * ip1 + 3] : n_moves;
-            const int ng = r1 - r0;
-            a.prune0 = ip0; a.n_prunes = ip1 - ip0;
-            o.swap0 = r0; o.n_group = ng;
-            if (gi) {      // (the batch's first group is timed with its down and outer passes)
-               HIPCHK(hipStreamSynchronize(st));
-               { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); spr_last_kernel_ms += ms; }
-               HIPCHK(hipEventRecord(w.ev0, st));
-            }
-            if (mfma) hipLaunchKernelGGL(spr_mfma_kernel, tiles, dim3(256), 0, st, a);
-            else spr_launch_lane(e->kk, lanes, st, a, 2);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(spr_unit_nni_combine_kernel, dim3(lanes.x, ng + (gi == 0 ? 1 : 0)), dim3(256), 0, st, o);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(w.ev1, st));
-            // the group's rows to the caller's [n_moves][n_patt]: one plain copy per move
-            if (lnf)
-               for (int i = 0; i < ng; i++)
-                  HIPCHK(hipMemcpyAsync(lnf + (size_t)plan.order[r0 + i] * n_patt + h0, w.lnf.p + (size_t)i * batch, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-         }
-         HIPCHK(hipStreamSynchronize(st));
-         { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); spr_last_kernel_ms += ms; }
-         spr_last_batches++;
-      }
-   HIPCHK(hipEventRecord(w.ev0, st));
-   hipLaunchKernelGGL(spr_unit_grad_total_kernel, dim3(n_moves + 1), dim3(256), 0, st, (const double *)w.partial.p, n_chunks, w.out.p);
-   HIPCHK(hipGetLastError());
-   HIPCHK(hipEventRecord(w.ev1, st));
+   auto lane_pass = [&](dim3 lanes, int pass) { anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(spr_lane_kernel<N()>, lanes, dim3(256), 0, st, a, pass); }); };
+   auto group = [&](int gi) {      // the prunes group_first[gi] .. group_first[gi + 1] and their rows
+      const int ip0 = group_first[gi], ip1 = group_first[gi + 1];
+      a.prune0 = ip0; a.n_prunes = ip1 - ip0;
+      o.swap0 = plan.prunes[SPR_PRUNE_INTS * ip0 + 3];
+      o.n_group = (ip1 < plan.n_prunes() ? plan.prunes[SPR_PRUNE_INTS * ip1 + 3] : n_moves) - o.swap0;
+   };
+   if (int rc = anc_score_batches(
+          e, w, o, chunk_base, batch, (int)group_first.size() - 1, lane_pass,
+          [](dim3) {},      // (the present tree's row is combined with the batch's first group)
+          [&](int gi, dim3 tiles, dim3 lanes) {
+             group(gi);
+             if (mfma) hipLaunchKernelGGL(spr_mfma_kernel, tiles, dim3(256), 0, st, a);
+             else lane_pass(lanes, 2);
+          },
+          [&](int gi, dim3 lanes) { hipLaunchKernelGGL(nni_combine_kernel, dim3(lanes.x, o.n_group + (gi == 0 ? 1 : 0)), dim3(256), 0, st, o); },
+          [&](int, long h0, long nb) {      // the group's rows to the caller's [n_moves][n_patt]: one plain copy per move
+             if (lnf)
+                for (int i = 0; i < o.n_group; i++)
+                   HIPCHK(hipMemcpyAsync(lnf + (size_t)plan.order[o.swap0 + i] * n_patt + h0, w.lnf.p + (size_t)i * batch, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+             return 0;
+          }))
+      return rc;
    std::vector<double> out((size_t)n_moves + 1);
-   HIPCHK(hipMemcpyAsync(out.data(), w.out.p, ((size_t)n_moves + 1) * 8, hipMemcpyDeviceToHost, st));
-   HIPCHK(hipStreamSynchronize(st));
-   { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, w.ev0, w.ev1)); spr_last_kernel_ms += ms; }
+   if (int rc = anc_totals(e, w, w.partial.p, n_chunks, w.out.p, out)) return rc;
    for (int i = 0; i < n_moves; i++) lnL[plan.order[i]] = out[i];
    *lnL0 = out[n_moves];
    return 0;

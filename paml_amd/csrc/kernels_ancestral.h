@@ -325,32 +325,12 @@ ANC_HD void anc_joint_root_down(const AncJointArgs &a, long p)
 }
 
 #ifndef ANC_HOST_ONLY
-// ---- kernels ------------------------------------------------------------------------------------------------------------------------
+// ---- kernels: defined in engine_ancestral.hip, launched from any unit of the library ---------------------------------------------
 
-// lnP = log(max(P, 1e-300)) of n_p entries, then lnpi of n_q
-__global__ __launch_bounds__(256) void anc_log_kernel(const double *P, long n_p, const double *pi, long n_q, double *lnP, double *lnpi)
-{
-   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-   if (i < n_p) lnP[i] = log(fmax(P[i], 1e-300));
-   else if (i < n_p + n_q) lnpi[i - n_p] = log(fmax(pi[i - n_p], 1e-300));
-}
-
-// one pattern per lane: grid (patterns / 256, K)
-template <int N> __global__ __launch_bounds__(256) void anc_lane_kernel(AncMargArgs a, int outer)
-{
-   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-   if (p >= a.nb) return;
-   if (outer) anc_lane_outer<N>(a, blockIdx.y, p);
-   else anc_lane_down<N>(a, blockIdx.y, p);
-}
-
-// grid (patterns / 256, n_query)
-__global__ __launch_bounds__(256) void anc_posterior_kernel(AncMargArgs a)
-{
-   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-   if (p >= a.nb) return;
-   anc_posterior(a, blockIdx.y, p);
-}
+__global__ void anc_log_kernel(const double *P, long n_p, const double *pi, long n_q, double *lnP, double *lnpi);
+__global__ void anc_posterior_kernel(AncMargArgs a);
+__global__ void anc_mfma_kernel(AncMargArgs a, int outer);
+__global__ void anc_joint_kernel(AncJointArgs a);
 
 // Matrix cores: a workgroup of four waves owns ANC_TILE patterns of one class, sixteen per wave; lane = q * 16 + pattern, register m of a
 // partial = state 4 m + q (the pruning kernels' layout).  A product stages the branch's P(t) block (A-operand order, 32 KB) in LDS.
@@ -401,106 +381,6 @@ __device__ __forceinline__ double anc_mfma_max(const double (&x)[16])      // ov
    return o > mx ? o : mx;
 }
 
-// grid (stride / ANC_TILE, K); outer = 0: the down pass, 1: the outer pass
-__global__ __launch_bounds__(256) void anc_mfma_kernel(AncMargArgs a, int outer)
-{
-   __shared__ __attribute__((aligned(16))) double sP[4096];
-   const AncTree &t = a.t;
-   const int tid = threadIdx.x, lane = tid & 63, n = a.n;
-   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-   const int q = lane >> 4, k = blockIdx.y;
-   const AncMfma w{sP, lane, wave, q};
-   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
-   const bool valid = p < a.nb;
-   const long pc = valid ? p : a.nb - 1;
-   const long pset = (long)a.gene * a.K + k;
-   if (!outer) {
-      for (int i = 0; i < t.n_post; i++) {
-         const int v = t.post[i];
-         if (v < t.n_tips) continue;
-         double x[16], ls = 0;
-#pragma unroll
-         for (int m = 0; m < 16; m++) x[m] = 4 * m + q < n ? 1.0 : 0.0;
-         for (int j = t.sons_ptr[v]; j < t.sons_ptr[v + 1]; j++) anc_mfma_mul_son(a, w, k, g16, pc, t.sons[j], x, &ls);
-         if (a.scaled && t.scale[v]) {
-            const double mx = anc_mfma_max(x);
-            if (mx < 1e-300) {
-#pragma unroll
-               for (int m = 0; m < 16; m++) x[m] = 4 * m + q < n ? 1.0 : 0.0;
-               ls += -800;
-            }
-            else {
-#pragma unroll
-               for (int m = 0; m < 16; m++) x[m] /= mx;
-               ls += log(mx);
-            }
-         }
-         const int vi = v - t.n_tips;
-         part_store(a.L + (((long)k * t.n_int + vi) * (a.stride >> 4) + g16) * 1024, lane, x);
-         if (q == 0) a.SL[((long)k * t.n_int + vi) * a.stride + p] = ls;      // (p < stride: the padding takes the lanes past the end)
-      }
-      return;
-   }
-   if (t.root >= t.n_tips) {
-      const int ri = t.root - t.n_tips;
-      double x[16];
-#pragma unroll
-      for (int m = 0; m < 16; m++) x[m] = 4 * m + q < n ? 1.0 : 0.0;
-      part_store(a.G + (((long)k * t.n_int + ri) * (a.stride >> 4) + g16) * 1024, lane, x);
-      if (q == 0) a.SG[((long)k * t.n_int + ri) * a.stride + p] = 0;
-   }
-   for (int i = 0; i < t.n_pre; i++) {
-      const int v = t.pre[i], f = t.father[v], vi = v - t.n_tips;
-      double h[16], ls = 0;
-      __syncthreads();      // (SG of the father was stored by the pattern's q = 0 lane: a workgroup-scope fence before the other lanes read it)
-      if (f >= t.n_tips) {
-         const int fi = f - t.n_tips;
-         part_load(a.G + (((long)k * t.n_int + fi) * (a.stride >> 4) + g16) * 1024, lane, h);      // (this lane's own stores)
-         ls = a.SG[((long)k * t.n_int + fi) * a.stride + pc];
-      }
-      else {
-         const unsigned long long mask = a.code_mask[a.z[(long)f * a.z_stride + a.h0 + pc]];
-#pragma unroll
-         for (int m = 0; m < 16; m++) h[m] = (mask >> (4 * m + q)) & 1ull ? 1.0 : 0.0;
-      }
-      for (int j = t.sons_ptr[f]; j < t.sons_ptr[f + 1]; j++)
-         if (t.sons[j] != v) anc_mfma_mul_son(a, w, k, g16, pc, t.sons[j], h, &ls);
-      v4d acc[4];
-      w.product(a.pint + (pset * t.n_nodes + v) * 4096, h, acc);
-      double g[16];
-#pragma unroll
-      for (int m = 0; m < 16; m++) g[m] = acc[m >> 2][m & 3];
-      if (a.scaled) {
-         const double mx = anc_mfma_max(g);
-         if (mx > 0) {
-#pragma unroll
-            for (int m = 0; m < 16; m++) g[m] /= mx;
-            ls += log(mx);
-         }
-      }
-      part_store(a.G + (((long)k * t.n_int + vi) * (a.stride >> 4) + g16) * 1024, lane, g);
-      if (q == 0) a.SG[((long)k * t.n_int + vi) * a.stride + p] = ls;
-   }
-}
-
-// joint: grid (patterns / ANC_JTILE); dynamic LDS: the node's n^2 doubles (n <= 64: 32 KB at most)
-__global__ __launch_bounds__(ANC_JTILE) void anc_joint_kernel(AncJointArgs a)
-{
-   extern __shared__ __attribute__((aligned(16))) double anc_lds[];
-   const AncTree &t = a.t;
-   const int tid = threadIdx.x, n2 = a.n * a.n;
-   const long p = (long)blockIdx.x * ANC_JTILE + tid;
-   const bool on = p < a.nb;      // (lanes past the end keep to the barriers and touch no memory)
-   for (int i = 0; i + 1 < t.n_post; i++) {      // (the root is the last entry)
-      const int v = t.post[i];
-      const double *lnPv = a.lnP + ((long)a.gene * t.n_nodes + v) * n2;
-      __syncthreads();      // (the previous node's table is no longer read)
-      for (int idx = tid; idx < n2; idx += ANC_JTILE) anc_lds[idx] = lnPv[idx];
-      __syncthreads();
-      if (on) anc_joint_up(a, v, p, anc_lds);
-   }
-   if (on) anc_joint_root_down(a, p);
-}
 #endif
 
 }  // namespace paml_amd

@@ -32,26 +32,7 @@
 #include "kernels_gradient.h"
 #define NNI_HD inline
 #else
-// kernels_ancestral.h and kernels_gradient.h define their plain kernels wherever they are included and a __global__ function has one
-// home: the copies of this translation unit get names of their own (as at the top of kernels_gradient.h)
-#define anc_log_kernel nni_unit_anc_log_kernel
-#define anc_posterior_kernel nni_unit_anc_posterior_kernel
-#define anc_mfma_kernel nni_unit_anc_mfma_kernel
-#define anc_joint_kernel nni_unit_anc_joint_kernel
-#include "kernels_ancestral.h"
-#undef anc_log_kernel
-#undef anc_posterior_kernel
-#undef anc_mfma_kernel
-#undef anc_joint_kernel
-#define grad_pmat_kernel nni_unit_grad_pmat_kernel
-#define grad_mfma_kernel nni_unit_grad_mfma_kernel
-#define grad_combine_kernel nni_unit_grad_combine_kernel
-#define grad_total_kernel nni_unit_grad_total_kernel
 #include "kernels_gradient.h"
-#undef grad_pmat_kernel
-#undef grad_mfma_kernel
-#undef grad_combine_kernel
-#undef grad_total_kernel
 #define NNI_HD __host__ __device__ __forceinline__
 #endif
 
@@ -197,38 +178,21 @@ NNI_HD double nni_combine(const NniArgs &a, int row, long p)
 }
 
 #ifndef NNI_HOST_ONLY
-// ---- kernels ------------------------------------------------------------------------------------------------------------------------
+// ---- kernels: defined in engine_nni.hip, launched from any unit of the library ---------------------------------------------------
 
-// P_v^T of every (parameter set, internal node) in the A-operand order (the index formula of grad_pmat_kernel): grid (n_nodes, gene x class)
-__global__ __launch_bounds__(256) void nni_pt_kernel(const double *P, double *PT, int n, int n_nodes, int n_tips, int root)
-{
-   const int node = blockIdx.x;
-   if (node == root || node < n_tips) return;
-   const long slot = (long)blockIdx.y * n_nodes + node;
-   const double *Pv = P + slot * n * n;
-   double *tf = PT + slot * 4096;
-   for (int idx = threadIdx.x; idx < 4096; idx += 256) {
-      const int e = idx & 1, lane = (idx >> 1) & 63, jb = (idx >> 7) & 3, kb2 = idx >> 9;
-      const int r = jb * 16 + (lane & 15), c = 4 * (2 * kb2 + e) + (lane >> 4);
-      tf[idx] = r < n && c < n ? Pv[c * n + r] : 0.0;
-   }
-}
+__global__ void nni_pt_kernel(const double *P, double *PT, int n, int n_nodes, int n_tips, int root);
+__global__ void nni_pt_all_kernel(const double *P, double *PT, int n, int n_nodes, int root);
+__global__ void nni_mfma_outer_kernel(NniArgs a);
+__global__ void nni_mfma_kernel(NniArgs a);
+__global__ void nni_combine_kernel(NniArgs a);
 
-// one pattern per lane: grid (patterns / 256, K); pass 0: the down pass, 1: the outer pass
+// one pattern per lane: grid (patterns / 256, K); pass 0: the down pass, 1: the outer pass (the placement call launches it too)
 template <int N> __global__ __launch_bounds__(256) void nni_lane_kernel(NniArgs a, int pass)
 {
    const long p = (long)blockIdx.x * 256 + threadIdx.x;
    if (p >= a.m.nb) return;
    if (pass) nni_lane_outer<N>(a, blockIdx.y, p);
    else anc_lane_down<N>(a.m, blockIdx.y, p);
-}
-
-// one pattern per lane, the swap pass: grid (patterns / 256, K, swaps of the group)
-template <int N> __global__ __launch_bounds__(256) void nni_lane_swap_kernel(NniArgs a)
-{
-   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-   if (p >= a.m.nb) return;
-   nni_lane_swap<N>(a, blockIdx.y, p, blockIdx.z);
 }
 
 // A_f of the pattern's lanes (pi o the indicator under a root that is a tip) and its log factor
@@ -248,122 +212,6 @@ __device__ __forceinline__ void nni_mfma_father(const AncMargArgs &m, int k, lon
    *ls = 0;
 }
 
-// Matrix cores, the outer pass without the derivative (grad_mfma_kernel's walk over the internal nodes, then ref_node when it is a tip):
-// lane = q * 16 + pattern, register m = state 4 m + q.  Grid (stride / ANC_TILE, K).
-__global__ __launch_bounds__(256) void nni_mfma_outer_kernel(NniArgs a)
-{
-   __shared__ __attribute__((aligned(16))) double sP[4096];
-   const AncMargArgs &m = a.m;
-   const AncTree &t = m.t;
-   const int tid = threadIdx.x, lane = tid & 63, n = m.n;
-   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-   const int q = lane >> 4, k = blockIdx.y;
-   const AncMfma w{sP, lane, wave, q};
-   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
-   const long pc = p < m.nb ? p : m.nb - 1;      // (lanes past the batch's end read the last pattern and write into the padding: p < stride)
-   const long pset = (long)m.gene * m.K + k;
-   if (t.root >= t.n_tips) {
-      const double *pi = m.pi + (long)(m.n_pi > 1 ? m.gene : 0) * n;
-      const int ri = t.root - t.n_tips;
-      double x[16];
-#pragma unroll
-      for (int i = 0; i < 16; i++) x[i] = 4 * i + q < n ? pi[4 * i + q] : 0.0;
-      part_store(m.G + (((long)k * t.n_int + ri) * (m.stride >> 4) + g16) * 1024, lane, x);
-      if (q == 0) m.SG[((long)k * t.n_int + ri) * m.stride + p] = 0;
-   }
-   const int n_walk = t.n_pre + (a.ref_node < t.n_tips ? 1 : 0);
-   for (int i = 0; i < n_walk; i++) {
-      const int v = i < t.n_pre ? t.pre[i] : a.ref_node;
-      const int f = t.father[v];
-      double h[16], ls;
-      __syncthreads();      // (SG of the father was stored by the pattern's q = 0 lane: a workgroup-scope fence before the other lanes read it)
-      nni_mfma_father(m, k, g16, pc, lane, q, f, h, &ls);
-      for (int j = t.sons_ptr[f]; j < t.sons_ptr[f + 1]; j++)
-         if (t.sons[j] != v) anc_mfma_mul_son(m, w, k, g16, pc, t.sons[j], h, &ls);
-      const long oi = nni_out_idx(a, k, a.cap, p);
-      double x[16], y[16];
-      if (v < t.n_tips) {      // ref_node, a tip: P_v L_v from the tip's column table
-         double2 tv[8];
-         tip_gather(m.ptip + pset * t.n_nodes * m.tip_words, m.tip_words, v, (int)m.z[(long)v * m.z_stride + m.h0 + pc], q, tv);
-#pragma unroll
-         for (int j = 0; j < 8; j++) { y[2 * j] = tv[j].x; y[2 * j + 1] = tv[j].y; }
-         const double den = grad_mfma_dot(h, y);
-         if (q == 0) { a.f[oi] = den; a.sig[oi] = ls; }
-         continue;
-      }
-      const int vi = v - t.n_tips;
-      v4d acc[4];
-      w.product(a.PT + (pset * t.n_nodes + v) * 4096, h, acc);      // A_v = P_v^T H_v
-#pragma unroll
-      for (int j = 0; j < 16; j++) y[j] = acc[j >> 2][j & 3];
-      if (v == a.ref_node) {      // (uniform over the workgroup) sum_x A_v(x) L_v(x) before A_v is rescaled, as grad_mfma_kernel
-         part_load(m.L + (((long)k * t.n_int + vi) * (m.stride >> 4) + g16) * 1024, lane, x);
-         const double den = grad_mfma_dot(y, x);
-         if (q == 0) { a.f[oi] = den; a.sig[oi] = ls + m.SL[((long)k * t.n_int + vi) * m.stride + pc]; }
-      }
-      if (m.scaled) {
-         const double mx = anc_mfma_max(y);
-         if (mx > 0) {
-#pragma unroll
-            for (int j = 0; j < 16; j++) y[j] /= mx;
-            ls += log(mx);
-         }
-      }
-      part_store(m.G + (((long)k * t.n_int + vi) * (m.stride >> 4) + g16) * 1024, lane, y);
-      if (q == 0) m.SG[((long)k * t.n_int + vi) * m.stride + p] = ls;
-   }
-}
-
-// Matrix cores, the swap pass: four waves own ANC_TILE patterns of one class and loop over the group's swaps.  Grid (stride / ANC_TILE, K).
-__global__ __launch_bounds__(256) void nni_mfma_kernel(NniArgs a)
-{
-   __shared__ __attribute__((aligned(16))) double sP[4096];
-   const AncMargArgs &m = a.m;
-   const AncTree &t = m.t;
-   const int tid = threadIdx.x, lane = tid & 63, n = m.n;
-   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-   const int q = lane >> 4, k = blockIdx.y;
-   const AncMfma w{sP, lane, wave, q};
-   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
-   const long pc = p < m.nb ? p : m.nb - 1;      // (lanes past the batch's end read the last pattern and write into the padding: p < stride)
-   const long pset = (long)m.gene * m.K + k;
-   for (int i = 0; i < a.n_group; i++) {
-      const int *sw = a.swaps + 3L * (a.swap0 + i);
-      const int v = sw[0], s = sw[1], x = sw[2], f = t.father[v];
-      double h[16], l[16], ls;
-      nni_mfma_father(m, k, g16, pc, lane, q, f, h, &ls);
-      anc_mfma_mul_son(m, w, k, g16, pc, s, h, &ls);
-      for (int j = t.sons_ptr[f]; j < t.sons_ptr[f + 1]; j++)
-         if (t.sons[j] != v && t.sons[j] != x) anc_mfma_mul_son(m, w, k, g16, pc, t.sons[j], h, &ls);
-#pragma unroll
-      for (int j = 0; j < 16; j++) l[j] = 4 * j + q < n ? 1.0 : 0.0;
-      anc_mfma_mul_son(m, w, k, g16, pc, x, l, &ls);
-      for (int j = t.sons_ptr[v]; j < t.sons_ptr[v + 1]; j++)
-         if (t.sons[j] != s) anc_mfma_mul_son(m, w, k, g16, pc, t.sons[j], l, &ls);
-      v4d acc[4];
-      w.product(m.pint + (pset * t.n_nodes + v) * 4096, l, acc);
-      double y[16];
-#pragma unroll
-      for (int j = 0; j < 16; j++) y[j] = acc[j >> 2][j & 3];
-      const double fk = grad_mfma_dot(h, y);
-      const long oi = nni_out_idx(a, k, i, p);
-      if (q == 0) { a.f[oi] = fk; a.sig[oi] = ls; }
-   }
-}
-
-// the classes of every (row, pattern) and the chunks' sums: grid (stride / 256, rows); a wave = one chunk of GRAD_CHUNK patterns
-__global__ __launch_bounds__(256) void nni_combine_kernel(NniArgs a)
-{
-   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-   const bool present = (int)blockIdx.y == a.n_group;      // (a batch's first group is launched with a row more: the present tree)
-   const int row = present ? a.cap : (int)blockIdx.y;
-   double acc = p < a.m.nb ? nni_combine(a, row, p) : 0.0;
-#pragma unroll
-   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-   const long chunk = a.chunk0 + (p >> 6);
-   const long out_row = present ? a.n_swaps : a.swap0 + row;
-   if ((threadIdx.x & 63) == 0 && (p & ~63L) < a.m.nb) a.partial[out_row * a.n_chunks + chunk] = acc;
-}
 #endif
 
 }  // namespace paml_amd

@@ -39,36 +39,7 @@
 #include "kernels_nni.h"
 #define PLACE_HD inline
 #else
-// the plain kernels of the three headers below are defined wherever they are included and a __global__ function has one home: the copies
-// of this translation unit get names of their own (as at the top of kernels_gradient.h and kernels_nni.h, whose own includes of the
-// headers already seen here then add nothing)
-#define anc_log_kernel place_unit_anc_log_kernel
-#define anc_posterior_kernel place_unit_anc_posterior_kernel
-#define anc_mfma_kernel place_unit_anc_mfma_kernel
-#define anc_joint_kernel place_unit_anc_joint_kernel
-#include "kernels_ancestral.h"
-#undef anc_log_kernel
-#undef anc_posterior_kernel
-#undef anc_mfma_kernel
-#undef anc_joint_kernel
-#define grad_pmat_kernel place_unit_grad_pmat_kernel
-#define grad_mfma_kernel place_unit_grad_mfma_kernel
-#define grad_combine_kernel place_unit_grad_combine_kernel
-#define grad_total_kernel place_unit_grad_total_kernel
-#include "kernels_gradient.h"
-#undef grad_pmat_kernel
-#undef grad_mfma_kernel
-#undef grad_combine_kernel
-#undef grad_total_kernel
-#define nni_pt_kernel place_unit_nni_pt_kernel
-#define nni_mfma_outer_kernel place_unit_nni_mfma_outer_kernel
-#define nni_mfma_kernel place_unit_nni_mfma_kernel
-#define nni_combine_kernel place_unit_nni_combine_kernel
 #include "kernels_nni.h"
-#undef nni_pt_kernel
-#undef nni_mfma_outer_kernel
-#undef nni_mfma_kernel
-#undef nni_combine_kernel
 #define PLACE_HD __host__ __device__ __forceinline__
 #endif
 
@@ -164,122 +135,11 @@ PLACE_HD double place_combine(const PlaceArgs &a, long row, long p)
 }
 
 #ifndef PLACE_HOST_ONLY
-// ---- kernels ------------------------------------------------------------------------------------------------------------------------
+// ---- kernels: defined in engine_place.hip ------------------------------------------------------------------------------------------
 
-// P_v^T of every (parameter set, node other than the root) in the A-operand order (the index formula of nni_pt_kernel, which leaves
-// the tips out): grid (n_nodes, gene x class)
-__global__ __launch_bounds__(256) void place_pt_kernel(const double *P, double *PT, int n, int n_nodes, int root)
-{
-   const int node = blockIdx.x;
-   if (node == root) return;
-   const long slot = (long)blockIdx.y * n_nodes + node;
-   const double *Pv = P + slot * n * n;
-   double *tf = PT + slot * 4096;
-   for (int idx = threadIdx.x; idx < 4096; idx += 256) {
-      const int e = idx & 1, lane = (idx >> 1) & 63, jb = (idx >> 7) & 3, kb2 = idx >> 9;
-      const int r = jb * 16 + (lane & 15), c = 4 * (2 * kb2 + e) + (lane >> 4);
-      tf[idx] = r < n && c < n ? Pv[c * n + r] : 0.0;
-   }
-}
-
-// one pattern per lane: grid (patterns / 256, K); pass 0: the down pass, 1: the outer pass
-template <int N> __global__ __launch_bounds__(256) void place_lane_kernel(PlaceArgs a, int pass)
-{
-   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-   if (p >= a.o.m.nb) return;
-   if (pass) nni_lane_outer<N>(a.o, blockIdx.y, p);
-   else anc_lane_down<N>(a.o.m, blockIdx.y, p);
-}
-
-// one (pattern, class, edge) per lane: grid (patterns / 256, K, edges of the group)
-template <int N> __global__ __launch_bounds__(256) void place_lane_edge_kernel(PlaceArgs a)
-{
-   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-   if (p >= a.o.m.nb) return;
-   place_lane_edge<N>(a, blockIdx.y, p, blockIdx.z);
-}
-
-// Matrix cores: four waves own ANC_TILE patterns of one class and loop over the group's edges; lane = q * 16 + pattern, register m =
-// state 4 m + q.  Per edge: H_v, one product with P_v^T((1 - phi) t), one product with P_v(phi t) (a tip: a gather from its column
-// table), W_v in registers; per (query, pendant) one gather from the pendant's column table and one dot product.  Grid (stride / ANC_TILE, K).
-__global__ __launch_bounds__(256) void place_mfma_kernel(PlaceArgs a)
-{
-   __shared__ __attribute__((aligned(16))) double sP[4096];
-   const AncMargArgs &m = a.o.m;
-   const AncTree &t = m.t;
-   const int tid = threadIdx.x, lane = tid & 63;
-   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-   const int q = lane >> 4, k = blockIdx.y;
-   const AncMfma w{sP, lane, wave, q};
-   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
-   const long pc = p < m.nb ? p : m.nb - 1;      // (lanes past the batch's end read the last pattern and write into the padding: p < stride)
-   const long pset = (long)m.gene * m.K + k;
-   const double *tabs = a.ptip_pend + pset * a.n_pend * m.tip_words;
-   for (int i = 0; i < a.n_group; i++) {
-      const int v = a.edges[a.edge0 + i], f = t.father[v];
-      double h[16], u[16], ls;
-      nni_mfma_father(m, k, g16, pc, lane, q, f, h, &ls);
-      for (int j = t.sons_ptr[f]; j < t.sons_ptr[f + 1]; j++)
-         if (t.sons[j] != v) anc_mfma_mul_son(m, w, k, g16, pc, t.sons[j], h, &ls);
-      const long slot = pset * t.n_nodes + v;
-      v4d acc[4];
-      w.product(a.PTup + slot * 4096, h, acc);      // U_v = P_v((1 - phi) t)^T H_v
-#pragma unroll
-      for (int j = 0; j < 16; j++) u[j] = acc[j >> 2][j & 3];
-      if (v < t.n_tips) {      // (uniform over the workgroup) D_v of a tip: its column table of P_v(phi t)
-         double2 tv[8];
-         tip_gather(a.ptip_dn + pset * t.n_nodes * m.tip_words, m.tip_words, v, (int)m.z[(long)v * m.z_stride + m.h0 + pc], q, tv);
-#pragma unroll
-         for (int j = 0; j < 8; j++) { u[2 * j] *= tv[j].x; u[2 * j + 1] *= tv[j].y; }
-      }
-      else {
-         const int vi = v - t.n_tips;
-         double x[16];
-         part_load(m.L + (((long)k * t.n_int + vi) * (m.stride >> 4) + g16) * 1024, lane, x);
-         w.product(a.pint_dn + slot * 4096, x, acc);      // D_v = P_v(phi t) L_v
-#pragma unroll
-         for (int j = 0; j < 16; j++) u[j] *= acc[j >> 2][j & 3];
-         ls += m.SL[((long)k * t.n_int + vi) * m.stride + pc];
-      }
-      for (int qi = 0; qi < a.n_q; qi++) {
-         const int code = (int)a.qz[(long)qi * m.z_stride + m.h0 + pc];
-         for (int j = 0; j < a.n_pend; j++) {
-            double2 tv[8];
-            tip_gather(tabs, m.tip_words, j, code, q, tv);
-            double y[16];
-#pragma unroll
-            for (int c = 0; c < 8; c++) { y[2 * c] = tv[c].x; y[2 * c + 1] = tv[c].y; }
-            const double fk = grad_mfma_dot(u, y);
-            const long oi = place_out_idx(a, k, place_row(a, i, qi, j), p);
-            if (q == 0) { a.f[oi] = fk; a.sig[oi] = ls; }
-         }
-      }
-   }
-}
-
-// the classes of every (row, pattern) and the chunks' sums: grid (stride / 256, rows of the slice); a wave = one chunk of GRAD_CHUNK
-// patterns.  row0: the slice's first row (a grid has 65535 rows at most)
-__global__ __launch_bounds__(256) void place_combine_kernel(PlaceArgs a, long row0)
-{
-   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-   const long row = row0 + blockIdx.y;
-   double acc = p < a.o.m.nb ? place_combine(a, row, p) : 0.0;
-#pragma unroll
-   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-   const long chunk = a.o.chunk0 + (p >> 6);
-   if ((threadIdx.x & 63) == 0 && (p & ~63L) < a.o.m.nb) a.partial[place_out_row(a, row) * a.o.n_chunks + chunk] = acc;
-}
-
-// the present tree's row (the outer pass left f_hk and sigma in o.f / o.sig): grid (stride / 256)
-__global__ __launch_bounds__(256) void place_present_kernel(PlaceArgs a)
-{
-   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-   double acc = p < a.o.m.nb ? nni_combine(a.o, 0, p) : 0.0;
-#pragma unroll
-   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-   const long chunk = a.o.chunk0 + (p >> 6);
-   if ((threadIdx.x & 63) == 0 && (p & ~63L) < a.o.m.nb) a.partial[(long)a.n_q * a.n_edges * a.n_pend * a.o.n_chunks + chunk] = acc;
-}
+__global__ void place_mfma_kernel(PlaceArgs a);
+__global__ void place_combine_kernel(PlaceArgs a, long row0);
+__global__ void place_present_kernel(PlaceArgs a);
 #endif
 
 }  // namespace paml_amd

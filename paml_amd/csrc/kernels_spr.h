@@ -50,35 +50,7 @@
 #include "kernels_nni.h"
 #define SPR_HD inline
 #else
-// the plain kernels of the three headers below are defined wherever they are included and a __global__ function has one home: the copies
-// of this translation unit get names of their own (as at the top of kernels_gradient.h, kernels_nni.h and kernels_place.h)
-#define anc_log_kernel spr_unit_anc_log_kernel
-#define anc_posterior_kernel spr_unit_anc_posterior_kernel
-#define anc_mfma_kernel spr_unit_anc_mfma_kernel
-#define anc_joint_kernel spr_unit_anc_joint_kernel
-#include "kernels_ancestral.h"
-#undef anc_log_kernel
-#undef anc_posterior_kernel
-#undef anc_mfma_kernel
-#undef anc_joint_kernel
-#define grad_pmat_kernel spr_unit_grad_pmat_kernel
-#define grad_mfma_kernel spr_unit_grad_mfma_kernel
-#define grad_combine_kernel spr_unit_grad_combine_kernel
-#define grad_total_kernel spr_unit_grad_total_kernel
-#include "kernels_gradient.h"
-#undef grad_pmat_kernel
-#undef grad_mfma_kernel
-#undef grad_combine_kernel
-#undef grad_total_kernel
-#define nni_pt_kernel spr_unit_nni_pt_kernel
-#define nni_mfma_outer_kernel spr_unit_nni_mfma_outer_kernel
-#define nni_mfma_kernel spr_unit_nni_mfma_kernel
-#define nni_combine_kernel spr_unit_nni_combine_kernel
 #include "kernels_nni.h"
-#undef nni_pt_kernel
-#undef nni_mfma_outer_kernel
-#undef nni_mfma_kernel
-#undef nni_combine_kernel
 #define SPR_HD __host__ __device__ __forceinline__
 #endif
 #include "spr_plan.h"
@@ -190,34 +162,9 @@ template <int N> SPR_HD void spr_lane_prune(const SprArgs &a, int k, long p, int
 }
 
 #ifndef SPR_HOST_ONLY
-// ---- kernels ------------------------------------------------------------------------------------------------------------------------
+// ---- kernels: defined in engine_spr.hip --------------------------------------------------------------------------------------------
 
-// P_v^T of every (parameter set, node other than the root) in the A-operand order (the index formula of nni_pt_kernel, which leaves
-// the tips out): grid (n_nodes, gene x class)
-__global__ __launch_bounds__(256) void spr_pt_kernel(const double *P, double *PT, int n, int n_nodes, int root)
-{
-   const int node = blockIdx.x;
-   if (node == root) return;
-   const long slot = (long)blockIdx.y * n_nodes + node;
-   const double *Pv = P + slot * n * n;
-   double *tf = PT + slot * 4096;
-   for (int idx = threadIdx.x; idx < 4096; idx += 256) {
-      const int e = idx & 1, lane = (idx >> 1) & 63, jb = (idx >> 7) & 3, kb2 = idx >> 9;
-      const int r = jb * 16 + (lane & 15), c = 4 * (2 * kb2 + e) + (lane >> 4);
-      tf[idx] = r < n && c < n ? Pv[c * n + r] : 0.0;
-   }
-}
-
-// one pattern per lane: grid (patterns / 256, K); pass 0: the down pass, 1: the outer pass, 2: the group's prunes
-template <int N> __global__ __launch_bounds__(256) void spr_lane_kernel(SprArgs a, int pass)
-{
-   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-   if (p >= a.o.m.nb) return;
-   if (pass == 0) anc_lane_down<N>(a.o.m, blockIdx.y, p);
-   else if (pass == 1) nni_lane_outer<N>(a.o, blockIdx.y, p);
-   else
-      for (int ip = a.prune0; ip < a.prune0 + a.n_prunes; ip++) spr_lane_prune<N>(a, blockIdx.y, p, ip);
-}
+__global__ void spr_mfma_kernel(SprArgs a);
 
 // x *= P L of `node` with the given matrices (A-operand blocks of internal nodes, column tables of tips) and partials
 __device__ __forceinline__ void spr_mfma_mul(const AncMargArgs &m, const AncMfma &w, const double *pint, const double *ptip, const double *Lb, const double *SLb, int k,
@@ -253,76 +200,6 @@ __device__ __forceinline__ void spr_mfma_rescale(const AncMargArgs &m, double (&
    }
 }
 
-// Matrix cores: four waves own ANC_TILE patterns of one class and loop over the group's prunes and their steps; lane = q * 16 + pattern,
-// register m = state 4 m + q.  Every branch below is uniform over the workgroup (the steps are the same for all patterns), so the
-// barriers inside the products are met by all four waves.  Grid (stride / ANC_TILE, K).
-__global__ __launch_bounds__(256) void spr_mfma_kernel(SprArgs a)
-{
-   __shared__ __attribute__((aligned(16))) double sP[4096];
-   const AncMargArgs &m = a.o.m;
-   const AncTree &t = m.t;
-   const int tid = threadIdx.x, lane = tid & 63, n = m.n;
-   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-   const int q = lane >> 4, k = blockIdx.y;
-   const AncMfma w{sP, lane, wave, q};
-   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
-   const long pc = p < m.nb ? p : m.nb - 1;      // (lanes past the batch's end read the last pattern and write into the padding: p < stride)
-   const long pset = (long)m.gene * m.K + k;
-   const long part = (long)k * t.n_int * (m.stride >> 4) + g16, sc = (long)k * t.n_int * m.stride;      // (+ node * (stride >> 4), * 1024; + node * stride)
-   for (int ip = a.prune0; ip < a.prune0 + a.n_prunes; ip++) {
-      const int *pr = a.prunes + (long)SPR_PRUNE_INTS * ip;
-      double ms[16], ls_s = 0;      // P_s L_s, once per s
-#pragma unroll
-      for (int j = 0; j < 16; j++) ms[j] = 4 * j + q < n ? 1.0 : 0.0;
-      spr_mfma_mul(m, w, m.pint, m.ptip, m.L, m.SL, k, g16, pc, pr[0], ms, &ls_s);
-      for (int is = pr[1]; is < pr[1] + pr[2]; is++) {
-         const int *st = a.steps + (long)SPR_STEP_INTS * is;
-         const int op = st[0], node = st[1];
-         double h[16], ls = 0;
-         __syncthreads();      // (SLp / SAp of an earlier step were stored by the pattern's q = 0 lane: a workgroup-scope fence before the other lanes read them)
-         if (st[2] == SPR_HEAD_ONES) {
-#pragma unroll
-            for (int j = 0; j < 16; j++) h[j] = 4 * j + q < n ? 1.0 : 0.0;
-         }
-         else if (st[2] == SPR_HEAD_PRESENT) nni_mfma_father(m, k, g16, pc, lane, q, st[3], h, &ls);
-         else {
-            const int fi = st[3] - t.n_tips;
-            part_load(a.Ap + (part + (long)fi * (m.stride >> 4)) * 1024, lane, h);      // (this lane's own stores)
-            ls = a.SAp[sc + (long)fi * m.stride + pc];
-         }
-         for (int j = st[4]; j < st[4] + st[5]; j++) {
-            const int kind = a.factors[2 * j], u = a.factors[2 * j + 1];
-            if (kind == SPR_FAC_PRESENT) spr_mfma_mul(m, w, m.pint, m.ptip, m.L, m.SL, k, g16, pc, u, h, &ls);
-            else if (kind == SPR_FAC_MERGED) spr_mfma_mul(m, w, a.pint_m, a.ptip_m, m.L, m.SL, k, g16, pc, u, h, &ls);
-            else spr_mfma_mul(m, w, m.pint, m.ptip, a.Lp, a.SLp, k, g16, pc, u, h, &ls);
-         }
-         const long slot = pset * t.n_nodes + node;
-         if (op == SPR_UP) {
-            const int vi = node - t.n_tips;
-            spr_mfma_rescale(m, h, &ls);
-            part_store(a.Lp + (part + (long)vi * (m.stride >> 4)) * 1024, lane, h);
-            if (q == 0) a.SLp[sc + (long)vi * m.stride + p] = ls;
-            continue;
-         }
-         v4d acc[4];
-         w.product((op == SPR_OUT ? (st[6] ? a.PTm : a.o.PT) : a.PTup) + slot * 4096, h, acc);      // P^T H'
-         double u[16];
-#pragma unroll
-         for (int j = 0; j < 16; j++) u[j] = acc[j >> 2][j & 3];
-         if (op == SPR_OUT) {
-            const int vi = node - t.n_tips;
-            spr_mfma_rescale(m, u, &ls);
-            part_store(a.Ap + (part + (long)vi * (m.stride >> 4)) * 1024, lane, u);
-            if (q == 0) a.SAp[sc + (long)vi * m.stride + p] = ls;
-            continue;
-         }
-         spr_mfma_mul(m, w, a.pint_dn, a.ptip_dn, st[6] ? a.Lp : m.L, st[6] ? a.SLp : m.SL, k, g16, pc, node, u, &ls);      // W
-         const double fk = grad_mfma_dot(u, ms);
-         const long oi = nni_out_idx(a.o, k, st[7] - a.o.swap0, p);
-         if (q == 0) { a.o.f[oi] = fk; a.o.sig[oi] = ls + ls_s; }
-      }
-   }
-}
 #endif
 
 }  // namespace paml_amd
