@@ -558,6 +558,44 @@ void paml_amd_nni_info(int *last_batches, double *last_kernel_ms);
  * NULL the length only), or PAML_AMD_EINVAL for a bad tree or a list longer than cap. */
 int paml_amd_nni_list(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, int *swaps /* [cap][3], or NULL */, int cap);
 
+/* ---- Edge scores: the lnL of a configuration of an internal edge at trial lengths of the five branches around it, with the first and
+ * second derivative along one of them, for all rows in ONE call: the device primitive under the approximate likelihood-ratio test of a
+ * branch (aLRT, Anisimova & Gascuel 2006; its SH-like form, Guindon et al. 2010), which maximises the present resolution of an edge and
+ * its two NNI alternatives over the five branches around it with everything else held fixed.  A row is (v, s, x, u): (v, s, x) is the
+ * swap of paml_amd_nni_scores, or s = x = -1 for the present configuration of the edge above v.  A branch is named by the node below it
+ * and keeps its length and label through the swap.  ovr_node names up to five branches (-1: unused) whose lengths are taken from ovr_t
+ * instead of branch: v, the father f of v if f is not the root, any son of v, any son of f other than v.  u is -1 or one of the row's
+ * override nodes: d1[i] is the derivative of lnL[i] with respect to the length of the branch above u at the given lengths and d2[i] the
+ * second derivative; for u = -1 both are 0 and no derivative matrices are built.  lnL[i] and lnf[i][h] are what paml_amd_eval would
+ * return for the rearranged tree with the override lengths written into branch, to rounding (the definition is written out in
+ * csrc/kernels_edge.h; no reversibility is assumed and nothing is re-rooted); *lnL0 is the present tree's lnL at `branch`, taken as
+ * paml_amd_nni_scores takes it.  No tree is set and no kernel is built per row.  K classes, several genes, branch labels, ambiguity
+ * codes, polytomies elsewhere, scaling nodes, a root that is a tip, at most 64 states.  Synchronous; leaves a following paml_amd_eval,
+ * paml_amd_gradient, paml_amd_nni_scores, paml_amd_placement_scores and paml_amd_spr_scores their results, and paml_amd_get_pmat
+ * afterwards returns the tree's own matrices at `branch`.  n_patt is walked gene by gene in batches of what a workspace holds (256 MiB;
+ * the environment variable PAML_AMD_EDGE_ARENA_MB, read at every call, gives another size in MiB), and the rows in groups where one tile
+ * of patterns with all of them does not fit: every output has the same bits for any workspace size, for any sub-list or order of the
+ * rows and on every call (fixed-order sums, no atomics).  PAML_AMD_EINVAL (with a message starting "edge_scores" that names the row)
+ * for a null argument other than gene_rate and lnf, n_rows < 1, a bad v, s or x as paml_amd_nni_scores, an override node outside the
+ * edge's neighbourhood or listed twice, f listed when it is the root, a u that is not among the row's override nodes, a model or tips
+ * not set; PAML_AMD_EUNSUPPORTED for rate-matrix (UNREST) sets (as paml_amd_gradient), tips that are not the nodes 0 .. n_tips - 1, more
+ * than 64 states, an engine whose communicator has more than one rank; PAML_AMD_ENOCONV as the other synchronous entries. */
+int paml_amd_edge_scores(paml_amd_engine *e, const double *branch, const double *gene_rate,
+                         int n_rows, const int *rows /* [n_rows][4] = v, s, x, u */,
+                         const int *ovr_node /* [n_rows][5], -1 = unused */, const double *ovr_t /* [n_rows][5] */,
+                         double *lnL0, double *lnL, double *d1, double *d2 /* [n_rows] each */, double *lnf /* [n_rows][n_patt], or NULL */);
+/* The number of pattern batches the calling thread's last paml_amd_edge_scores walked and the time of its kernels by HIP events (ms,
+ * summed); either pointer may be NULL. */
+void paml_amd_edge_info(int *last_batches, double *last_kernel_ms);
+/* The edges of a tree (given as paml_amd_set_tree takes it) that have three configurations, host only: every internal v that is not the
+ * root, has exactly two sons (s1, s2) and whose father f is either a non-root node with two sons (v, c) or a root with exactly three
+ * sons (v, c1, c2), in node order.  Per edge: the present configuration (v, -1, -1) and the two swaps paml_amd_nni_list gives for that
+ * v — (s1, c), (s2, c), or (s1, c1), (s1, c2) under the root — and the five branches around it: s1, s2, v, then c and f, or c1 and c2.
+ * Edges next to a polytomy or under a root with two sons are not listed.  Returns the count (with edges = five = NULL the count only),
+ * or PAML_AMD_EINVAL for a bad tree or a list longer than cap. */
+int paml_amd_edge_list(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons,
+                       int *edges /* [cap][3][3] = per edge three (v, s, x), or NULL */, int *five /* [cap][5], or NULL */, int cap);
+
 /* ---- Placement: the lnL of the tree with one more tip hung on a branch, for every query, every branch and every pendant length in ONE
  * call.  The reference's stepwise addition (StepwiseAddition treesub.c:4866 on AddSpecies treesub.c:4592) sets and evaluates one enlarged
  * tree after the other; the same primitive lies under the regraft half of an SPR move and under placing new sequences on a fitted tree.

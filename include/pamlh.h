@@ -159,6 +159,36 @@ int pamlh_nni_scores(pamlh *p, const double *x, int *n_swaps, int *swaps, double
 int pamlh_apply_nni(pamlh *p, int v, int s, int x);
 int pamlh_nni_search(pamlh *p, double *x, double *lnL, int max_moves, int verbose, int *stats);
 
+/* Branch supports by the approximate likelihood-ratio test in its SH-like form (pamlh_support.c; aLRT: Anisimova & Gascuel 2006, the
+ * non-parametric SH-like support: Guindon et al. 2010).  An edge is the branch above an internal node v with two sons whose father is a
+ * non-root node with two sons or a root with three (paml_amd_edge_list); its three configurations are the present one and its two NNI
+ * alternatives; the five branches around it are s1, s2, v, then c and f, or c1 and c2 (include/paml_amd.h).
+ * pamlh_edge_list: edges[*n_edges][3][3] and five[*n_edges][5] of the tree as it stands; both NULL: the count only.
+ * pamlh_edge_optimize: all 3 n_edges rows are maximised over their five lengths in lock step at the parameters of x, everything else
+ *   held fixed, the present configuration treated like the other two; ONE paml_amd_edge_scores call per step gives every row's lnL, d1
+ *   and d2 at its own lengths.  A cyclic, safeguarded Newton iteration: per sweep the five roles in turn; per role one call for the
+ *   derivatives at the accepted lengths and at most 4 calls at trial lengths; a row takes -d1 / d2 where d2 < 0, otherwise doubles
+ *   (d1 > 0) or halves (d1 < 0) the length; a step is clipped to [4e-6, 50], the bounds pamlh_optimize uses, and halved while the next
+ *   call shows the row's lnL fell; no damping.  It ends after a sweep in which no row gained more than 1e-6 or after 30 sweeps; a row
+ *   that gained no more than 1e-6 in a sweep is finished and stays in the calls with u = -1.  t5_out[n_edges][3][5] (in the order of
+ *   five), l_out[n_edges][3]; stats (NULL or 3 entries): sweeps, engine calls, rows with a length at a bound.
+ * pamlh_edge_lnf: lnL[n_edges][3] and lnf[n_edges][3][npatt] of every configuration at the lengths t5 and the parameters of x: one call.
+ * pamlh_branch_supports: the list, the optimisation, one last call with the per-pattern values of all rows; delta = 2 (l0 - max(l1,
+ *   l2)); the replicate sums from paml_amd_rell_replicates over the 3 n_edges rows (genes respected); the table arithmetic of
+ *   pamlh_branch_supports_from_replicates.  edge_node[*n_edges] = v, l3[*n_edges][3]; all four NULL: the count only.
+ * pamlh_branch_supports_from_replicates (host only): rep[n_rep][3 n_edges]; per row its mean over the replicates is subtracted (the
+ *   centring of the S-H column of the tree comparison); per edge and replicate delta*_r = 2 (largest - second largest of the three
+ *   centred sums); support = #{r : delta*_r < delta} / n_rep, and 0 where delta <= 0 (a better NNI neighbour exists).
+ * pamlh_newick_supports: pamlh_newick with the supports as the labels of the internal nodes (buf needs 80 bytes per node + 128).
+ * Refused by name: a clock, rho models, runmode = -2, fix_blength = 2 or 3 (the branch lengths are not parameters), a tree whose root
+ * has two sons.  Not done here: parameters other than the five lengths, chi-square-based aLRT P values, edges next to polytomies. */
+int pamlh_edge_list(pamlh *p, int *n_edges, int *edges, int *five);
+int pamlh_edge_optimize(pamlh *p, const double *x, int n_edges, const int *edges, const int *five, double *t5_out, double *l_out, int *stats);
+int pamlh_edge_lnf(pamlh *p, const double *x, int n_edges, const int *edges, const int *five, const double *t5, double *lnL, double *lnf);
+int pamlh_branch_supports(pamlh *p, const double *x, int n_rep, unsigned long long seed, int *n_edges, int *edge_node, double *delta, double *support, double *l3);
+int pamlh_branch_supports_from_replicates(int n_edges, int n_rep, const double *rep, const double *l3, double *delta, double *support);
+int pamlh_newick_supports(const pamlh *p, int n_edges, const int *edge_node, const double *support, char *buf, int cap);
+
 /* Subtree prune and regraft (SPR) on the analysis's tree (pamlh_spr.c).  A move is (s, x), 0-based nodes, with a split phi in [0, 1]
  * (the definition: paml_amd_spr_scores, include/paml_amd.h): the subtree below s leaves with its father f; c, the other son of f, takes
  * f's place on a branch of length t_c + t_f; f takes x's place with the sons (x, s), the branch above f has length (1 - phi) t_x and x's

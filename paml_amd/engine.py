@@ -39,6 +39,7 @@ EXPORTS = [
     "paml_amd_ancestral_marginal", "paml_amd_ancestral_joint", "paml_amd_ancestral_info",
     "paml_amd_gradient", "paml_amd_gradient_info",
     "paml_amd_nni_scores", "paml_amd_nni_info", "paml_amd_nni_list",
+    "paml_amd_edge_scores", "paml_amd_edge_info", "paml_amd_edge_list",
     "paml_amd_placement_scores", "paml_amd_placement_info",
     "paml_amd_spr_scores", "paml_amd_spr_info", "paml_amd_spr_list",
 ]
@@ -55,7 +56,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_nni", "engine_place", "engine_spr")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_nni", "engine_place", "engine_spr", "engine_edge")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -514,6 +515,28 @@ class Engine:
         self._L.paml_amd_nni_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
         self._chk(self._L.paml_amd_nni_scores(self._h, _p(b), _p(g), len(sw), _p(sw), C.byref(lnL0), _p(lnL), _p(lnf)))
         return dict(lnL0=lnL0.value, swaps=sw, lnL=lnL, lnf=lnf)
+
+    def edge_scores(self, branch, gene_rate=None, rows=None, ovr_node=None, ovr_t=None, want_lnf=False):
+        """The lnL of configurations of internal edges at trial lengths of the five branches around them, with the first and second
+        derivative along one of them, in one call (paml_amd_edge_scores): dict(lnL0 (the present tree's at `branch`), lnL, d1, d2 =
+        [n_rows], lnf=[n_rows][n_patt] or None).  rows: int [n_rows][4] = v, s, x, u (s = x = -1: the present configuration; u = -1: no
+        derivative); ovr_node: int [n_rows][5] (-1: unused) and ovr_t: [n_rows][5], the branches whose lengths replace `branch`'s."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        if rows is None or ovr_node is None or ovr_t is None:
+            raise EngineError("edge_scores: rows, ovr_node and ovr_t are needed")
+        rw = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 4)
+        on = np.ascontiguousarray(ovr_node, dtype=np.int32).reshape(-1, 5)
+        ot = np.ascontiguousarray(ovr_t, dtype=np.float64).reshape(-1, 5)
+        if not (len(rw) == len(on) == len(ot)):
+            raise EngineError("edge_scores: rows, ovr_node and ovr_t differ in length")
+        lnL0 = C.c_double()
+        lnL, d1, d2 = np.zeros(len(rw)), np.zeros(len(rw)), np.zeros(len(rw))
+        lnf = np.zeros((len(rw), self.n_patt)) if want_lnf else None
+        self._L.paml_amd_edge_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self._L.paml_amd_edge_scores(self._h, _p(b), _p(g), len(rw), _p(rw), _p(on), _p(ot), C.byref(lnL0), _p(lnL), _p(d1), _p(d2), _p(lnf)))
+        return dict(lnL0=lnL0.value, lnL=lnL, d1=d1, d2=d2, lnf=lnf)
 
     def placement_scores(self, branch, gene_rate=None, queries=None, edges=None, pendant=(0.1,), phi=0.5, pendant_label=0, want_lnf=False):
         """The lnL of the tree at `branch` with a query tip hung on a branch, for every query, edge and pendant length in one call
@@ -983,6 +1006,34 @@ def nni_info():
     L.paml_amd_nni_info.restype = None
     L.paml_amd_nni_info(C.byref(nb), C.byref(ms))
     return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def edge_info():
+    """Batches walked by this thread's last Engine.edge_scores and the time of its kernels by HIP events (paml_amd_edge_info):
+    dict(last_batches, last_kernel_ms)."""
+    L = lib()
+    nb, ms = C.c_int(), C.c_double()
+    L.paml_amd_edge_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.paml_amd_edge_info.restype = None
+    L.paml_amd_edge_info(C.byref(nb), C.byref(ms))
+    return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def edge_list(tree):
+    """The edges of `tree` (a problem.Tree) that have three configurations (paml_amd_edge_list, host only): (edges int32 [n_edges][3][3] =
+    per edge the present configuration (v, -1, -1) and its two swaps (v, s, x); five int32 [n_edges][5] = the branches around it)."""
+    L = lib()
+    ptr = np.zeros(tree.n_nodes + 1, dtype=np.int32)
+    ptr[1:] = np.cumsum([len(s) for s in tree.sons])
+    flat = np.ascontiguousarray([c for s in tree.sons for c in s], dtype=np.int32)
+    L.paml_amd_edge_list.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    n = L.paml_amd_edge_list(int(tree.n_tips), int(tree.n_nodes), int(tree.root), _p(ptr), _p(flat), None, None, 0)
+    if n < 0:
+        raise EngineError("paml_amd_edge_list failed (%d): not a tree" % n)
+    edges, five = np.zeros((n, 3, 3), dtype=np.int32), np.zeros((n, 5), dtype=np.int32)
+    if n and L.paml_amd_edge_list(int(tree.n_tips), int(tree.n_nodes), int(tree.root), _p(ptr), _p(flat), _p(edges), _p(five), n) != n:
+        raise EngineError("paml_amd_edge_list: the list changed its length")
+    return edges, five
 
 
 def placement_info():

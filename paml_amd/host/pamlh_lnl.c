@@ -1,5 +1,5 @@
 /* pamlh_lnl — command-line driver: one likelihood evaluation of a codeml/baseml analysis on the MI355X.
- *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
+ *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
  *   (--set "key = value": replaces an option of the control file, e.g. one of the site models of an "NSsites = 0 1 2 7 8" list;
  *    --tree K: the K-th tree of the tree file, 1-based; --all-trees: every tree in turn — the reference's loop, Forestry codeml.c:635 —
  *    each optimised from the control file's initial values, then the comparison table of rell(), treesub.c:5844;
@@ -13,6 +13,11 @@
  *    of v's father), their lnL at the parameter vector from one engine call and the difference to the present tree's;
  *    --nni-search [--max-moves N]: the NNI hill climb of the reference's runmode = 5 from the tree of the tree file (pamlh_nni_search):
  *    every accepted move, then the tree found with its estimates and lnL)
+ *    --branch-supports [--replicates N] [--seed S]: the SH-like aLRT support of every internal branch that has three configurations
+ *    (pamlh_branch_supports) at the parameter vector, or at the estimates after --optimize: one row per branch — father..node, the lnL
+ *    of the present resolution and of its two NNI alternatives, each maximised over the five branches around the edge, delta = 2 (l0 -
+ *    max(l1, l2)) and the support from N (default 1000) RELL replicates drawn on the GPU — then the tree with the supports as
+ *    internal-node labels;
  *    --spr-scores [--radius R] [--split PHI]: the table of the tree's subtree-prune-and-regraft neighbours (s, x: the subtree below node s
  *    regrafted on the branch above node x, which the new node splits at PHI) within R branches (default: no limit), their lnL at the
  *    parameter vector from one engine call and the difference to the present tree's;
@@ -131,7 +136,7 @@ int main(int argc, char **argv)
    pamlh *p;
    char err[512];
    double x[4096], lnL, *lnf;
-   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0, spr_scores = 0, spr_search = 0, radius = 0, top = 0, place = 0, n_pend = 4;
+   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0, spr_scores = 0, spr_search = 0, radius = 0, top = 0, place = 0, n_pend = 4, supports = 0;
    double pend[64] = {0.05, 0.1, 0.2, 0.4}, split = 0.5;
    char over[2048] = "";
    const char *sim_out = NULL, *bv_out = NULL;
@@ -140,11 +145,12 @@ int main(int argc, char **argv)
    unsigned char comm_id[PAML_AMD_COMM_ID_BYTES];
    int device[MAX_RANKS];
    for (i = 0; i < MAX_RANKS; i++) device[i] = i;
-   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
+   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
    for (i = 3; i < argc && nx < 4096; i++) {
       if (!strcmp(argv[i], "--optimize")) optimize = 1;
       else if (!strcmp(argv[i], "--analytic-gradient")) analytic = 1;      /* with --optimize: the branch lengths' derivatives from one engine call per gradient */
       else if (!strcmp(argv[i], "--nni-scores")) nni_scores = 1;
+      else if (!strcmp(argv[i], "--branch-supports")) supports = 1;      /* SH-like aLRT supports of the internal branches (N replicates, default 1000; --seed S) */
       else if (!strcmp(argv[i], "--nni-search")) nni_search = 1;
       else if (!strcmp(argv[i], "--max-moves") && i + 1 < argc) max_moves = atoi(argv[++i]);
       else if (!strcmp(argv[i], "--spr-scores")) spr_scores = 1;
@@ -272,6 +278,34 @@ int main(int argc, char **argv)
    if (!nx) nx = pamlh_default_x(p, x, 4096);
    if (nx != np) { fprintf(stderr, "error: the model has %d parameters (ntime %d) but %d values were given\n", np, ntime, nx); return 1; }
    if (analytic) pamlh_use_analytic_gradient(p, 1);
+   if (supports) {      /* SH-like aLRT supports of the internal branches at x (after --optimize: at the estimates); instead of the evaluation */
+      int nnode = 0, n = 0, n_eval = 0, *node, *fa_of;
+      double *delta, *sup, *l3;
+      char *nw;
+      if (gpus > 0) { fprintf(stderr, "error: --branch-supports runs on one GPU\n"); return 1; }
+      pamlh_dims(p, NULL, NULL, NULL, &nnode, NULL, NULL, NULL, NULL, NULL, NULL);
+      if (optimize && pamlh_optimize(p, x, &lnL, 500, 1e-10, 0, &n_eval) < 0) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      if (pamlh_branch_supports(p, NULL, 0, 0, &n, NULL, NULL, NULL, NULL)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      node = (int *)malloc((n + 1) * sizeof(int)); delta = (double *)malloc((n + 1) * sizeof(double)); sup = (double *)malloc((n + 1) * sizeof(double));
+      l3 = (double *)malloc((size_t)(3 * n + 3) * sizeof(double));
+      if (pamlh_branch_supports(p, x, replicates > 0 ? replicates : 1000, sim_seed, &n, node, delta, sup, l3)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      fa_of = (int *)malloc(nnode * sizeof(int));
+      {
+         const int *sp = pamlh_sons_ptr(p), *so = pamlh_sons(p);
+         int v, j;
+         for (v = 0; v < nnode; v++) fa_of[v] = -1;
+         for (v = 0; v < nnode; v++)
+            for (j = sp[v]; j < sp[v + 1]; j++) fa_of[so[j]] = v;
+      }
+      printf("Branch supports (SH-like aLRT, %d replicates, seed %llu): every configuration maximised over the five branches around the edge\n%10s %16s %16s %16s %12s %9s\n",
+             replicates > 0 ? replicates : 1000, sim_seed, "branch", "l0", "l1", "l2", "delta", "support");
+      for (i = 0; i < n; i++) printf("%4d..%-4d %16.6f %16.6f %16.6f %12.6f %9.3f\n", fa_of[node[i]] + 1, node[i] + 1, l3[3 * i], l3[3 * i + 1], l3[3 * i + 2], delta[i], sup[i]);
+      nw = (char *)malloc((size_t)160 * nnode + 256);
+      if (!pamlh_newick_supports(p, n, node, sup, nw, 160 * nnode + 256)) printf("%s\n", nw);
+      free(nw); free(node); free(delta); free(sup); free(l3); free(fa_of);
+      pamlh_free(p);
+      return 0;
+   }
    if (nni_scores || nni_search) {      /* the neighbours' table at x, or the hill climb from x; instead of the evaluation */
       int nnode = 0, n = 0, stats[3] = {0, 0, 0};
       char *nw;

@@ -20,7 +20,7 @@ DRIVER_PATH = os.path.join(_HERE, "lib", "pamlh_lnl")
 def build(force=False):
     from . import engine
     engine.build()
-    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_place.c", "pamlh_spr.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
+    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_place.c", "pamlh_spr.c", "pamlh_support.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "pamlh.h"))
     if force or not (os.path.exists(LIB_PATH) and os.path.exists(DRIVER_PATH)) or \
             any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
@@ -95,6 +95,23 @@ def tree_comparison(lnf, w, gene_off=None, n_rep=0, seed=1, device=False):
     if rc != 0:
         raise RuntimeError("pamlh_tree_comparison: bad arguments")
     return dict(zip(("li", "dli", "se", "pKH", "pSH", "pRELL"), out), best=best.value)
+
+
+def branch_supports_from_replicates(rep, l3):
+    """delta = 2 (l0 - max(l1, l2)) and the SH-like support of every edge from the replicate sums of its three configurations
+    (pamlh_branch_supports_from_replicates, host only): rep [n_rep][3 n_edges], l3 [n_edges][3] -> (delta, support)."""
+    L = lib()
+    rep = np.ascontiguousarray(rep, dtype=np.float64)
+    l3 = np.ascontiguousarray(l3, dtype=np.float64).reshape(-1, 3)
+    n = len(l3)
+    if rep.ndim != 2 or rep.shape[1] != 3 * n:
+        raise ValueError("branch_supports_from_replicates: rep must be [n_rep][3 n_edges]")
+    delta, sup = np.zeros(n), np.zeros(n)
+    L.pamlh_branch_supports_from_replicates.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if L.pamlh_branch_supports_from_replicates(n, rep.shape[0], rep.ctypes.data_as(C.c_void_p), l3.ctypes.data_as(C.c_void_p), delta.ctypes.data_as(C.c_void_p),
+                                               sup.ctypes.data_as(C.c_void_p)) != 0:
+        raise ValueError("branch_supports_from_replicates: bad arguments")
+    return delta, sup
 
 
 def tree_comparison_from_replicates(lnf, w, rep):
@@ -367,6 +384,84 @@ class Analysis:
         if f(self._h, x.ctypes.data_as(C.c_void_p), C.byref(n), swaps.ctypes.data_as(C.c_void_p), C.byref(l0), lnl.ctypes.data_as(C.c_void_p)) != 0:
             raise RuntimeError("pamlh_nni_scores: " + self._L.pamlh_error(self._h).decode())
         return dict(lnL0=l0.value, swaps=swaps[:n.value], lnL=lnl[:n.value])
+
+    def edge_list(self):
+        """The edges of the tree as it stands that have three configurations (pamlh_edge_list -> paml_amd_edge_list): (edges int32
+        [n_edges][3][3] = per edge the present configuration (v, -1, -1) and its two swaps, five int32 [n_edges][5])."""
+        n = C.c_int()
+        f = self._L.pamlh_edge_list
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
+        if f(self._h, C.byref(n), None, None) != 0:
+            raise RuntimeError("pamlh_edge_list: " + self._L.pamlh_error(self._h).decode())
+        edges, five = np.zeros((max(1, n.value), 3, 3), dtype=np.int32), np.zeros((max(1, n.value), 5), dtype=np.int32)
+        if f(self._h, C.byref(n), edges.ctypes.data_as(C.c_void_p), five.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_edge_list: " + self._L.pamlh_error(self._h).decode())
+        return edges[:n.value], five[:n.value]
+
+    def edge_optimize(self, x, edges=None, five=None):
+        """Every configuration of every edge maximised over the five branches around it at the parameters of x, in lock step, one
+        engine call per Newton step (pamlh_edge_optimize): dict(edges, five, t5=[n_edges][3][5] the maximising lengths in the order of
+        five, lnL=[n_edges][3], sweeps, calls, rows_at_bound).  edges, five None: edge_list()."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if edges is None or five is None:
+            edges, five = self.edge_list()
+        edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 3, 3)
+        five = np.ascontiguousarray(five, dtype=np.int32).reshape(-1, 5)
+        n = len(edges)
+        t5, l3, stats = np.zeros((n, 3, 5)), np.zeros((n, 3)), (C.c_int * 3)()
+        f = self._L.pamlh_edge_optimize
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if len(x) != self.np or len(five) != n or f(self._h, x.ctypes.data_as(C.c_void_p), n, edges.ctypes.data_as(C.c_void_p), five.ctypes.data_as(C.c_void_p),
+                                                   t5.ctypes.data_as(C.c_void_p), l3.ctypes.data_as(C.c_void_p), stats) != 0:
+            raise RuntimeError("pamlh_edge_optimize: " + self._L.pamlh_error(self._h).decode())
+        return dict(edges=edges, five=five, t5=t5, lnL=l3, sweeps=stats[0], calls=stats[1], rows_at_bound=stats[2])
+
+    def edge_lnf(self, x, edges, five, t5):
+        """lnL [n_edges][3] and lnf [n_edges][3][n_patt] of every configuration at the lengths t5 [n_edges][3][5] and the parameters of
+        x, from one engine call (pamlh_edge_lnf)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 3, 3)
+        five = np.ascontiguousarray(five, dtype=np.int32).reshape(-1, 5)
+        t5 = np.ascontiguousarray(t5, dtype=np.float64).reshape(-1, 3, 5)
+        n = len(edges)
+        l3, lnf = np.zeros((n, 3)), np.zeros((n, 3, self.n_patt))
+        f = self._L.pamlh_edge_lnf
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if len(x) != self.np or len(five) != n or len(t5) != n or f(self._h, x.ctypes.data_as(C.c_void_p), n, edges.ctypes.data_as(C.c_void_p), five.ctypes.data_as(C.c_void_p),
+                                                                  t5.ctypes.data_as(C.c_void_p), l3.ctypes.data_as(C.c_void_p), lnf.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_edge_lnf: " + self._L.pamlh_error(self._h).decode())
+        return l3, lnf
+
+    def lnL(self, x):
+        """lnL at x: one evaluation on the GPU (eval_gpu without the per-pattern values)."""
+        return self.eval_gpu(x, want_lnf=False)[0]
+
+    def branch_supports(self, x, n_rep=1000, seed=1):
+        """SH-like aLRT supports of the internal branches of the tree as it stands at the parameters of x (pamlh_branch_supports):
+        dict(edge_node=[n_edges] (the branch above that node), delta, support=[n_edges], lnL=[n_edges][3], newick (the supports as
+        internal-node labels))."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        n = C.c_int()
+        f = self._L.pamlh_branch_supports
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_ulonglong, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if len(x) != self.np or f(self._h, None, int(n_rep), int(seed), C.byref(n), None, None, None, None) != 0:
+            raise RuntimeError("pamlh_branch_supports: " + self._L.pamlh_error(self._h).decode())
+        m = max(1, n.value)
+        node, delta, sup, l3 = np.zeros(m, dtype=np.int32), np.zeros(m), np.zeros(m), np.zeros((m, 3))
+        if f(self._h, x.ctypes.data_as(C.c_void_p), int(n_rep), int(seed), C.byref(n), node.ctypes.data_as(C.c_void_p), delta.ctypes.data_as(C.c_void_p),
+             sup.ctypes.data_as(C.c_void_p), l3.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_branch_supports: " + self._L.pamlh_error(self._h).decode())
+        m = n.value
+        buf = C.create_string_buffer(160 * self.n_nodes + 256)
+        self._L.pamlh_newick_supports.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+        self._L.pamlh_newick_supports(self._h, m, node.ctypes.data_as(C.c_void_p), sup.ctypes.data_as(C.c_void_p), buf, len(buf))
+        return dict(edge_node=node[:m], delta=delta[:m], support=sup[:m], lnL=l3[:m], newick=buf.value.decode())
+
+    @staticmethod
+    def branch_supports_from_replicates(rep, l3):
+        """The table arithmetic of branch_supports, host only (pamlh_branch_supports_from_replicates): rep [n_rep][3 n_edges] replicate
+        sums, l3 [n_edges][3] -> (delta [n_edges], support [n_edges])."""
+        return branch_supports_from_replicates(rep, l3)
 
     def apply_nni(self, v, s, x):
         """Exchange son s of v with son x of the father of v on the analysis's tree (pamlh_apply_nni); apply_nni(v, x, s) undoes it."""

@@ -54,6 +54,30 @@ class Tree:
                 out += [(v, int(s), int(x)) for x in self.sons[fa] if x != v]
         return np.asarray(out, dtype=np.int32).reshape(-1, 3)
 
+    def edge_configs(self):
+        """The edges that have three configurations, as paml_amd_edge_list writes them: (edges int32 [n_edges][3][3], five int32
+        [n_edges][5]).  Every internal v that is not the root, has exactly two sons (s1, s2) and whose father f is a non-root node with
+        two sons (v, c) or a root with exactly three sons (v, c1, c2), in node order: the present configuration (v, -1, -1) and the two
+        swaps nni_swaps gives for that v, and the five branches s1, s2, v, then c and f, or c1 and c2."""
+        f = self.father()
+        edges, five = [], []
+        for v in range(self.n_nodes):
+            if v == self.root or f[v] < 0 or len(self.sons[v]) != 2:
+                continue
+            fa = int(f[v])
+            nf = len(self.sons[fa])
+            if not ((fa != self.root and nf == 2) or (fa == self.root and nf == 3)):
+                continue
+            c = [int(u) for u in self.sons[fa] if u != v]
+            s1, s2 = (int(u) for u in self.sons[v])
+            if nf == 2:
+                edges.append([(v, -1, -1), (v, s1, c[0]), (v, s2, c[0])])
+                five.append([s1, s2, v, c[0], fa])
+            else:
+                edges.append([(v, -1, -1), (v, s1, c[0]), (v, s1, c[1])])
+                five.append([s1, s2, v, c[0], c[1]])
+        return np.asarray(edges, dtype=np.int32).reshape(-1, 3, 3), np.asarray(five, dtype=np.int32).reshape(-1, 5)
+
     def nni(self, v, s, x):
         """A new Tree with son s of v and son x of the father of v exchanged in place in the two son lists: the subtrees change places,
         each keeps the branch above it.  Node ids, branch and label are untouched (shared with this tree)."""
