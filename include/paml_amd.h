@@ -526,6 +526,36 @@ int paml_amd_gradient(paml_amd_engine *e, const double *branch, const double *ge
  * the batches); either pointer may be NULL. */
 void paml_amd_gradient_info(int *last_batches, double *last_kernel_ms);
 
+/* ---- The derivative of lnL with respect to every INPUT of the engine in one call: what a chain rule on the host needs to give
+ * d lnL / d (any model parameter) without an evaluation or a decomposition per parameter (the definition and the kernels are written out
+ * in csrc/kernels_modelgrad.h).  lnL is the number paml_amd_gradient returns at (branch, gene_rate), a function of
+ *   tau_gkv = branch[v] x gene rate x class rate x Qfactor (UVROOT sets; 1 otherwise), the effective length in P_v = exp(A tau);
+ *   A of every eigen set: U diag(Root) V as paml_amd_set_eigen_uvroot or the qrev_batch calls left them (after their scale);
+ *     sum_r Root_r Cijk[.][.][r] of a CIJK set; the closed forms of K80 and JC69LIKE (the matrices whose exponential those sets take);
+ *   freqK, and the root frequency vectors (paml_amd_set_pi).
+ * g_eff[g][k][v] = d lnL / d tau_gkv (the root's entries 0): sum_{g,k} g_eff[g][k][v] d tau_gkv / d branch[v] is paml_amd_gradient's
+ * grad[v].  g_freqK[k] = sum_h w_h f_hk / f_h.  g_pi[i][x] = d lnL / d pi_i[x] of the root's vector as it enters the root sum only
+ * (a root that is a tip: zero outside the tip's state set).  g_A[set][a][b] = d lnL / d A_ab with every element of A taken as
+ * independent, summed over the (gene, class, branch) that use the set.  W[g][k][v][y][x] = d lnL / d P_v(y, x) of that (gene, class):
+ * the weighted outer products the other outputs are pulled back from, for parity checks.  Any of the five may be NULL.
+ * Takes what paml_amd_gradient takes and leaves the engine as it does; the workspace is 256 MiB or PAML_AMD_MODELGRAD_ARENA_MB.  Every
+ * result has the same bits whatever the batches and on every call: W is summed over segments of paml_amd_model_gradient_segment()
+ * patterns counted from each gene's first pattern, a segment cut by a batch border is carried on in the same accumulator, and finished
+ * segments are added in segment order (no atomics).  PAML_AMD_EINVAL for a null branch or lnL, a model or tips not set;
+ * PAML_AMD_EUNSUPPORTED for a rate-matrix (UNREST) set, more than 64 states, an engine whose communicator has more than one rank.
+ * (The auto-discrete-gamma correlation rho is not an engine input: paml_amd_eval_adg has no counterpart here.) */
+int paml_amd_model_gradient(paml_amd_engine *e, const double *branch, const double *gene_rate, double *lnL,
+                            double *g_eff   /* [n_genes][K][n_nodes], or NULL */,
+                            double *g_freqK /* [K], or NULL */,
+                            double *g_pi    /* [n_pi][n], or NULL */,
+                            double *g_A     /* [n_eigen][n][n], or NULL */,
+                            double *W       /* [n_genes][K][n_nodes][n][n], or NULL */);
+/* The number of batches the calling thread's last paml_amd_model_gradient walked and the time of its kernels by HIP events (ms). */
+void paml_amd_model_gradient_info(int *last_batches, double *last_kernel_ms);
+/* Patterns per summation segment of W; the sizes of g_pi and g_A: the engine's root frequency vectors and eigen sets. */
+int paml_amd_model_gradient_segment(void);
+int paml_amd_model_gradient_sizes(paml_amd_engine *e, int *n_pi, int *n_eigen);
+
 /* ---- The lnL of every nearest-neighbour-interchange (NNI) neighbour of the tree at the present branch lengths, in one call (the trees
  * the reference's search, Perturbation treesub.c:4642 on NeighborNNI treespace.c:283, takes one after the other; the definition and the
  * kernels are written out in csrc/kernels_nni.h).  A swap is (v, s, x): v an internal node that is not the root, s a son of v, x a son

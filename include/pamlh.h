@@ -127,6 +127,17 @@ int pamlh_gradient(pamlh *p, const double *x, double *lnL, double *g);
 /* on != 0: pamlh_optimize takes the branch-length entries of its gradients from that call and batches only the remaining parameters;
  * the call counts as one evaluation in n_eval.  Off by default: pamlh_optimize then does exactly what it did without it. */
 int pamlh_use_analytic_gradient(pamlh *p, int on);
+/* on = 2: every entry of pamlh_optimize's gradients comes from pamlh_gradient_full (one engine call per gradient, counted as one
+ * evaluation); where that call does not serve, what on = 1 does.
+ * pamlh_rate_matrix: A[n][n], the matrix the engine exponentiates (P = exp(A tau)) for eigen set `set` of the present model state.
+ * pamlh_gradient_full: d(+lnL)/dx at x (np entries) and lnL from ONE paml_amd_model_gradient call and a chain rule on the host: the
+ * engine inputs the state would install at x +- h e_i (rate matrices, effective lengths, freqK, root frequencies; pamlh_set_x only, no
+ * evaluation and no device decomposition per parameter) are differenced (a Richardson pair of central differences at 1e-3 (1 + |x_i|)
+ * and half of it; h = 1e-6 (1 + |x_i|), one-sided where needed, next to the box) and contracted with the engine's
+ * derivatives.  The state is left at x.  Returns 1, touching nothing, where pamlh_gradient differences the branch lengths (a clock,
+ * fix_blength = 3, rho != 0, a rate-matrix (UNREST) model). */
+int pamlh_rate_matrix(pamlh *p, int set, double *A);
+int pamlh_gradient_full(pamlh *p, const double *x, double *lnL, double *g);
 /* g[ntime] as pamlh_gradient's leading entries and H[ntime][ntime], H_ij = -sum_h w_h s_i(h) s_j(h) with the analytic per-pattern
  * scores s_i(h) = d log f_h / d t_i (HessianSKT2004's method 1, treesub.c:7241).  Refused where pamlh_gradient would difference the
  * branch lengths. */

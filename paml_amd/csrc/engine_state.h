@@ -15,6 +15,8 @@
 //   engine_ancestral.hip marginal and joint ancestral reconstruction at every internal node (P(t) by launch_pmat, then its own kernels)
 //   engine_gradient.hip  the derivative of lnL with respect to every branch length and the per-pattern scores (P(t) and the down pass as
 //                       engine_ancestral.hip, whose host helpers it shares through ancestral_host.h; then its own kernels)
+//   engine_modelgrad.hip the derivative of lnL with respect to every input of the engine (rate matrices, effective lengths, freqK, root
+//                       frequencies) in one call: the outer pass that stores H_v, the weighted outer products, the pull-back
 //   engine_place.hip    the lnL of the tree with a query tip hung on every branch (the same shared host helpers as engine_nni.hip)
 //   engine_nni.hip      the lnL of every nearest-neighbour-interchange neighbour of the tree (P(t), the down pass and the host helpers as
 //                       engine_gradient.hip; the outer pass without the derivative and the swap pass are its own kernels)

@@ -38,6 +38,7 @@ EXPORTS = [
     "paml_amd_simulate", "paml_amd_simulate_info",
     "paml_amd_ancestral_marginal", "paml_amd_ancestral_joint", "paml_amd_ancestral_info",
     "paml_amd_gradient", "paml_amd_gradient_info",
+    "paml_amd_model_gradient", "paml_amd_model_gradient_info", "paml_amd_model_gradient_segment", "paml_amd_model_gradient_sizes",
     "paml_amd_nni_scores", "paml_amd_nni_info", "paml_amd_nni_list",
     "paml_amd_edge_scores", "paml_amd_edge_info", "paml_amd_edge_list",
     "paml_amd_placement_scores", "paml_amd_placement_info",
@@ -56,7 +57,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_nni", "engine_place", "engine_spr", "engine_edge")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_modelgrad", "engine_nni", "engine_place", "engine_spr", "engine_edge")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -497,6 +498,26 @@ class Engine:
         self._L.paml_amd_gradient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]
         self._chk(self._L.paml_amd_gradient(self._h, _p(b), _p(g), C.byref(lnL), _p(grad), _p(lnf), _p(scores)))
         return dict(lnL=lnL.value, grad=grad, lnf=lnf, scores=scores)
+
+    def model_gradient(self, branch, gene_rate=None, want_pairs=False):
+        """The derivative of lnL with respect to every input of the engine in one call (paml_amd_model_gradient): dict(lnL,
+        g_eff=[n_genes][K][n_nodes] d lnL / d (effective length), g_freqK=[K], g_pi=[n_pi][n], g_A=[n_eigen][n][n] d lnL / d A_ab of every
+        set's rate matrix (every element independent), W=[n_genes][K][n_nodes][n][n] d lnL / d P_v(y, x) with want_pairs, else None)."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        lnL = C.c_double()
+        n, K = self.n, self.K
+        g_eff = np.zeros((self.n_genes, K, self.n_nodes))
+        g_freqK = np.zeros(K)
+        n_pi, n_eigen = C.c_int(), C.c_int()
+        self._L.paml_amd_model_gradient_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        self._chk(self._L.paml_amd_model_gradient_sizes(self._h, C.byref(n_pi), C.byref(n_eigen)))
+        g_pi = np.zeros((n_pi.value, n))
+        g_A = np.zeros((n_eigen.value, n, n))
+        W = np.zeros((self.n_genes, K, self.n_nodes, n, n)) if want_pairs else None
+        self._L.paml_amd_model_gradient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)] + [C.c_void_p] * 5
+        self._chk(self._L.paml_amd_model_gradient(self._h, _p(b), _p(g), C.byref(lnL), _p(g_eff), _p(g_freqK), _p(g_pi), _p(g_A), _p(W)))
+        return dict(lnL=lnL.value, g_eff=g_eff, g_freqK=g_freqK, g_pi=g_pi, g_A=g_A, W=W)
 
     def nni_scores(self, branch, gene_rate=None, swaps=None, want_lnf=False):
         """The lnL of nearest-neighbour-interchange neighbours of the tree at `branch` in one call (paml_amd_nni_scores): dict(lnL0 (the
@@ -995,6 +1016,17 @@ def gradient_info():
     L.paml_amd_gradient_info.restype = None
     L.paml_amd_gradient_info(C.byref(nb), C.byref(ms))
     return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def model_gradient_info():
+    """Batches walked by this thread's last Engine.model_gradient and the time of its kernels by HIP events
+    (paml_amd_model_gradient_info): dict(last_batches, last_kernel_ms, segment = the patterns of one summation segment of W)."""
+    L = lib()
+    nb, ms = C.c_int(), C.c_double()
+    L.paml_amd_model_gradient_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.paml_amd_model_gradient_info.restype = None
+    L.paml_amd_model_gradient_info(C.byref(nb), C.byref(ms))
+    return dict(last_batches=nb.value, last_kernel_ms=ms.value, segment=int(L.paml_amd_model_gradient_segment()))
 
 
 def nni_info():

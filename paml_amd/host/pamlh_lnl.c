@@ -1,5 +1,5 @@
 /* pamlh_lnl — command-line driver: one likelihood evaluation of a codeml/baseml analysis on the MI355X.
- *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
+ *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient | --analytic-gradient-all]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
  *   (--set "key = value": replaces an option of the control file, e.g. one of the site models of an "NSsites = 0 1 2 7 8" list;
  *    --tree K: the K-th tree of the tree file, 1-based; --all-trees: every tree in turn — the reference's loop, Forestry codeml.c:635 —
  *    each optimised from the control file's initial values, then the comparison table of rell(), treesub.c:5844;
@@ -145,9 +145,10 @@ int main(int argc, char **argv)
    unsigned char comm_id[PAML_AMD_COMM_ID_BYTES];
    int device[MAX_RANKS];
    for (i = 0; i < MAX_RANKS; i++) device[i] = i;
-   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
+   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient | --analytic-gradient-all]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
    for (i = 3; i < argc && nx < 4096; i++) {
       if (!strcmp(argv[i], "--optimize")) optimize = 1;
+      else if (!strcmp(argv[i], "--analytic-gradient-all")) analytic = 2;  /* with --optimize: every parameter's derivative from one engine call per gradient */
       else if (!strcmp(argv[i], "--analytic-gradient")) analytic = 1;      /* with --optimize: the branch lengths' derivatives from one engine call per gradient */
       else if (!strcmp(argv[i], "--nni-scores")) nni_scores = 1;
       else if (!strcmp(argv[i], "--branch-supports")) supports = 1;      /* SH-like aLRT supports of the internal branches (N replicates, default 1000; --seed S) */
@@ -277,7 +278,7 @@ int main(int argc, char **argv)
    if (!nx) nx = pamlh_read_inx(p, x, 4096);
    if (!nx) nx = pamlh_default_x(p, x, 4096);
    if (nx != np) { fprintf(stderr, "error: the model has %d parameters (ntime %d) but %d values were given\n", np, ntime, nx); return 1; }
-   if (analytic) pamlh_use_analytic_gradient(p, 1);
+   if (analytic) pamlh_use_analytic_gradient(p, analytic);
    if (supports) {      /* SH-like aLRT supports of the internal branches at x (after --optimize: at the estimates); instead of the evaluation */
       int nnode = 0, n = 0, n_eval = 0, *node, *fa_of;
       double *delta, *sup, *l3;

@@ -445,6 +445,23 @@ static int gradient(pamlh *p, const double *x, double f0, const double *lo, cons
 {
    int first = 0, i, rc, live = 0;
    for (i = 0; i < p->ntime; i++) live |= !(p->frozen && p->frozen[i]);      /* (minB holds the branch lengths: nothing to ask the engine for) */
+   if (p->analytic_gradient == 2 && !p->clock) {      /* every entry from one engine call (pamlh_gradient_full), counted as one evaluation */
+      double lnL, *xm = (double *)malloc(2 * p->np * sizeof(double)), *gx = xm + p->np;
+      clock_y_to_x(p, x, xm);
+      rc = pamlh_gradient_full(p, xm, &lnL, gx);
+      if (rc == 0) {
+         int start[PAMLH_MAXEIG + 4], len[PAMLH_MAXEIG + 4], ng = p->opt_transformed ? pamlh_simplex_groups(p, start, len, PAMLH_MAXEIG + 4) : 0, gi;
+         for (gi = 0; gi < ng; gi++) {      /* proportions iterated as log-ratios: d p_j / d y_i = p_j (delta_ij - p_i) */
+            double s = 0;
+            for (i = 0; i < len[gi]; i++) s += gx[start[gi] + i] * xm[start[gi] + i];
+            for (i = 0; i < len[gi]; i++) gx[start[gi] + i] = xm[start[gi] + i] * (gx[start[gi] + i] - s);
+         }
+         for (i = 0; i < p->np; i++) g[i] = (p->frozen && p->frozen[i]) ? 0 : -gx[i];
+         (*n_eval)++;
+      }
+      free(xm);
+      if (rc <= 0) return rc;
+   }
    if (p->analytic_gradient && !p->clock && live) {
       double lnL, *xm = (double *)malloc(2 * p->np * sizeof(double)), *gb = xm + p->np;
       clock_y_to_x(p, x, xm);      /* (no clock: the branch lengths are themselves; proportions come back from their log-ratios) */
@@ -463,8 +480,168 @@ static int gradient(pamlh *p, const double *x, double f0, const double *lo, cons
 int pamlh_use_analytic_gradient(pamlh *p, int on)
 {
    if (!p) return -1;
-   p->analytic_gradient = on != 0;
+   p->analytic_gradient = on == 2 ? 2 : on != 0;
    return 0;
+}
+
+/* The matrix the engine exponentiates for eigen set `set` of the present model state, A[n][n] (P = exp(A tau)): a reversible matrix
+ * waiting for its decomposition: Q / scale; U diag(Root) V; sum_r Root_r Cijk[.][.][r]; the closed forms of K80 and JC69-like. */
+int pamlh_rate_matrix(pamlh *p, int set, double *A)
+{
+   int i, j, k, n;
+   const pamlh_eig *e;
+   if (!p || !A || set < 0 || set >= p->n_eigen) return p ? pamlh_fail(p, "pamlh_rate_matrix: no eigen set %d", set) : -1;
+   n = p->n;
+   e = &p->eig[set];
+   if (e->kind == PAML_AMD_EIGEN_UVROOT && e->lazy && e->Q) {
+      for (i = 0; i < n * n; i++) A[i] = e->Q[i] / e->scale;
+   }
+   else if (e->kind == PAML_AMD_EIGEN_UVROOT) {
+      for (i = 0; i < n; i++)
+         for (j = 0; j < n; j++) {
+            double s = 0;
+            for (k = 0; k < n; k++) s += e->U[i * n + k] * e->Root[k] * e->V[k * n + j];
+            A[i * n + j] = s;
+         }
+   }
+   else if (e->kind == PAML_AMD_EIGEN_CIJK) {
+      for (i = 0; i < n * n; i++) {
+         double s = 0;
+         for (k = 0; k < e->nR; k++) s += e->Cijk[(size_t)i * e->nR + k] * e->Root[k];
+         A[i] = s;
+      }
+   }
+   else if (e->kind == PAML_AMD_EIGEN_K80 || e->kind == PAML_AMD_EIGEN_JC69LIKE) {
+      const int k80 = e->kind == PAML_AMD_EIGEN_K80;
+      for (i = 0; i < n; i++) {
+         double row = 0;
+         for (j = 0; j < n; j++) {
+            const double v = i == j ? 0 : k80 ? ((i ^ j) == 1 ? e->kappa : 1.0) / (e->kappa + 2) : 1.0 / (n - 1);
+            A[i * n + j] = v;
+            row += v;
+         }
+         A[i * n + i] = -row;
+      }
+   }
+   else return pamlh_fail(p, "pamlh_rate_matrix: a rate-matrix (UNREST) set is its own matrix; not served here");
+   return 0;
+}
+
+/* The engine inputs the present model state would install, one after the other in s: A of every set [n_eigen][n][n], the effective
+ * lengths tau[ngene][K][nnode] = branch x rgene x rate x qfactor (qfactor: UVROOT sets, where the state uses it), freqK[K], pi[n_pi][n]. */
+static size_t full_snapshot_size(const pamlh *p)
+{
+   return (size_t)p->n_eigen * p->n * p->n + (size_t)p->ngene * p->K * p->nnode + p->K + (size_t)p->n_pi * p->n;
+}
+/* d tau / d branch[v] of (gene g, class k): rgene x class rate x qfactor */
+static double full_tau_base(const pamlh *p, int g, int k, int v)
+{
+   const int G = p->ngene, K = p->K;
+   const int *eo = G > 1 ? p->gene_eigen_of : p->eigen_of;
+   const int lab = p->label ? p->label[v] : 0, set = eo[((G > 1 ? g * K : 0) + k) * p->n_labels + lab];
+   const double qf = p->use_qf && p->eig[set].kind == PAML_AMD_EIGEN_UVROOT ? p->qfactor[k * p->n_labels + lab] : 1.0;
+   return (G > 1 ? p->rgene[g] : 1.0) * p->rate[(p->malpha ? g * K : 0) + k] * qf;
+}
+static int full_snapshot(pamlh *p, double *s)
+{
+   const int n = p->n, K = p->K, G = p->ngene, nn = p->nnode;
+   int i, g, k, v, rc;
+   for (i = 0; i < p->n_eigen; i++)
+      if ((rc = pamlh_rate_matrix(p, i, s + (size_t)i * n * n))) return rc;
+   s += (size_t)p->n_eigen * n * n;
+   for (g = 0; g < G; g++)
+      for (k = 0; k < K; k++)
+         for (v = 0; v < nn; v++) s[((size_t)g * K + k) * nn + v] = v == p->root ? 0.0 : p->branch[v] * full_tau_base(p, g, k, v);
+   s += (size_t)G * K * nn;
+   memcpy(s, p->freqK, K * sizeof(double));
+   memcpy(s + K, p->pi, (size_t)p->n_pi * n * sizeof(double));
+   return 0;
+}
+
+/* d(+lnL)/dx at x, np entries, and lnL, from ONE engine call (paml_amd_model_gradient) and a chain rule on the host: for every
+ * parameter the engine inputs the model state would install at x +- h e_i (pamlh_set_x only: no evaluation, no decomposition on the
+ * device) are differenced — they are O(1) smooth functions of x: a Richardson pair of central differences at 1e-3 (1 + |x_i|) and half
+ * of it; next to the box or an infeasible side h = 1e-6 (1 + |x_i|), one-sided where it has to be — and contracted with the engine's
+ * derivatives with respect to those inputs.  The state is set back to x.  Returns 1, touching
+ * nothing, where pamlh_gradient's engine call does not serve either (a clock, fix_blength = 3, rho != 0, a rate-matrix (UNREST) set). */
+int pamlh_gradient_full(pamlh *p, const double *x, double *lnL, double *g)
+{
+   int n, np, i, rc, n_pi = 0, n_eig = 0;
+   size_t ns, o_tau, j;
+   double *lo = NULL, *hi, *xt = NULL, *s0 = NULL, *sp, *sm, *d = NULL, *gA = NULL;
+   if (!p || !x || !lnL || !g) return -1;
+   n = p->n; np = p->np;
+   if (!p->ntime || p->clock || p->fix_blength == 3) return 1;
+   if ((rc = pamlh_set_x(p, x, np))) return rc < 0 ? rc : -1;
+   if (p->adg) return 1;
+   for (i = 0; i < p->n_eigen; i++) if (p->eig[i].kind == PAML_AMD_EIGEN_QMAT) return 1;
+   if ((rc = pamlh_engine_model(p))) return rc < 0 ? rc : -1;
+   if (paml_amd_model_gradient_sizes(p->eng, &n_pi, &n_eig) || n_pi != p->n_pi || n_eig < p->n_eigen)
+      return pamlh_fail(p, "pamlh_gradient_full: the engine holds %d frequency vectors and %d eigen sets, the model state %d and %d", n_pi, n_eig, p->n_pi, p->n_eigen);
+   ns = full_snapshot_size(p);
+   o_tau = (size_t)p->n_eigen * n * n;
+   /* d: the engine's derivatives in the snapshot's order (the engine may hold sets past the model's own from an earlier state: their
+    * blocks of g_A are zero and are not read) */
+   d = (double *)calloc(ns + 1, sizeof(double));
+   gA = (double *)calloc((size_t)n_eig * n * n + 1, sizeof(double));
+   lo = (double *)malloc(2 * np * sizeof(double) + 8); hi = lo + np;
+   xt = (double *)malloc(np * sizeof(double) + 8);
+   s0 = (double *)malloc(3 * ns * sizeof(double) + 8); sp = s0 + ns; sm = sp + ns;
+   if (pamlh_bounds(p, lo, hi)) { rc = pamlh_fail(p, "internal: bounds do not match np"); goto done; }
+   rc = paml_amd_model_gradient(p->eng, p->branch, p->ngene > 1 ? p->rgene : NULL, lnL, d + o_tau, d + o_tau + (size_t)p->ngene * p->K * p->nnode,
+                                d + o_tau + (size_t)p->ngene * p->K * p->nnode + p->K, gA, NULL);
+   if (rc) { pamlh_fail(p, "%s", paml_amd_last_error(p->eng)); rc = rc < 0 ? rc : -1; goto done; }
+   memcpy(d, gA, o_tau * sizeof(double));
+   if ((rc = full_snapshot(p, s0))) goto done;
+   for (i = 0; i < np; i++) {
+      const double h = 1e-6 * (fabs(x[i]) + 1);
+      double vp = x[i], vm = x[i], acc = 0;
+      const double *a = s0, *b = s0;
+      g[i] = 0;
+      if (p->frozen && p->frozen[i]) continue;
+      if (i < p->ntime) {      /* a plain branch length: tau is linear in it */
+         const int node = p->branch_node[i];
+         int gg, k;
+         for (gg = 0; gg < p->ngene; gg++)
+            for (k = 0; k < p->K; k++) acc += d[o_tau + ((size_t)gg * p->K + k) * p->nnode + node] * full_tau_base(p, gg, k, node);
+         g[i] = acc;
+         continue;
+      }
+      memcpy(xt, x, np * sizeof(double));
+      {
+         /* Richardson pair of central differences of the inputs at H and H / 2, H = 1e-3 (1 + |x_i|): truncation O(H^4), and the
+          * rounding of an input (~1e-16) is divided by 1e-3, not 1e-6 — summed over n^2 elements against g_A of ~1e3 the short step
+          * alone left ~1e-5 of the derivative.  d acc / d x_i = (4 D(H/2) - D(H)) / 3. */
+         const double H = 1e-3 * (fabs(x[i]) + 1);
+         double D[2] = {0, 0};
+         int lev, ok = x[i] + H <= hi[i] && x[i] - H >= lo[i];
+         for (lev = 0; lev < 2 && ok; lev++) {
+            const double hh = lev ? H / 2 : H;
+            xt[i] = x[i] + hh;
+            ok = pamlh_set_x(p, xt, np) == 0 && pamlh_model_feasible(p) && full_snapshot_size(p) == ns && !full_snapshot(p, sp);
+            xt[i] = x[i] - hh;
+            ok = ok && pamlh_set_x(p, xt, np) == 0 && pamlh_model_feasible(p) && full_snapshot_size(p) == ns && !full_snapshot(p, sm);
+            if (ok) {
+               for (j = 0, acc = 0; j < ns; j++) acc += d[j] * (sp[j] - sm[j]);
+               D[lev] = acc / (2 * hh);
+            }
+         }
+         if (ok) { g[i] = (4 * D[1] - D[0]) / 3; continue; }
+         acc = 0;
+      }
+      /* next to the box or to an infeasible side: the short step, one-sided where it has to be */
+      xt[i] = x[i];
+      if (x[i] + h <= hi[i]) { xt[i] = x[i] + h; if (pamlh_set_x(p, xt, np) == 0 && pamlh_model_feasible(p) && full_snapshot_size(p) == ns && !full_snapshot(p, sp)) { vp = xt[i]; a = sp; } }
+      if (x[i] - h >= lo[i]) { xt[i] = x[i] - h; if (pamlh_set_x(p, xt, np) == 0 && pamlh_model_feasible(p) && full_snapshot_size(p) == ns && !full_snapshot(p, sm)) { vm = xt[i]; b = sm; } }
+      if (!(vp > vm)) continue;
+      for (j = 0; j < ns; j++) acc += d[j] * (a[j] - b[j]);
+      g[i] = acc / (vp - vm);
+   }
+   rc = pamlh_set_x(p, x, np);
+   if (rc) rc = rc < 0 ? rc : -1;
+done:
+   free(d); free(gA); free(lo); free(xt); free(s0);
+   return rc;
 }
 
 /* d(+lnL)/dx at x, np entries, and lnL: the plain branch lengths from paml_amd_gradient, every other entry (all of them where

@@ -357,12 +357,13 @@ class Analysis:
         return lo, hi
 
     def optimize(self, x0, max_iter=500, tol=1e-10, verbose=False, analytic_gradient=False):
-        """Maximum-likelihood estimation from x0 (pamlh_optimize).  Returns dict(x, lnL, converged, n_eval).  analytic_gradient: the
-        branch lengths' derivatives from one engine call per gradient (pamlh_use_analytic_gradient; counted as one evaluation)."""
+        """Maximum-likelihood estimation from x0 (pamlh_optimize).  Returns dict(x, lnL, converged, n_eval).  analytic_gradient: True or 1:
+        the branch lengths' derivatives from one engine call per gradient (pamlh_use_analytic_gradient; counted as one evaluation); 2:
+        every parameter's from one engine call per gradient (pamlh_gradient_full)."""
         x = np.ascontiguousarray(x0, dtype=np.float64).copy()
         lnl, nev = C.c_double(), C.c_int()
         self._L.pamlh_use_analytic_gradient.argtypes = [C.c_void_p, C.c_int]
-        self._L.pamlh_use_analytic_gradient(self._h, int(bool(analytic_gradient)))
+        self._L.pamlh_use_analytic_gradient(self._h, 2 if analytic_gradient == 2 else int(bool(analytic_gradient)))
         try:
             rc = self._L.pamlh_optimize(self._h, x.ctypes.data_as(C.c_void_p), C.byref(lnl), max_iter, tol, int(verbose), C.byref(nev))
         finally:
@@ -586,6 +587,25 @@ class Analysis:
         if len(x) != self.np or self._L.pamlh_gradient(self._h, x.ctypes.data_as(C.c_void_p), C.byref(lnl), g.ctypes.data_as(C.c_void_p)) != 0:
             raise RuntimeError("pamlh_gradient: " + self._L.pamlh_error(self._h).decode())
         return dict(lnL=lnl.value, grad=g[:self.np])
+
+    def gradient_full(self, x):
+        """d lnL / d x at x from ONE engine call and a chain rule on the host (pamlh_gradient_full): dict(lnL, grad=[np]), or None where
+        the call does not serve (a clock, fix_blength = 3, rho != 0, UNREST)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        lnl, g = C.c_double(), np.zeros(max(1, self.np))
+        self._L.pamlh_gradient_full.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]
+        rc = -1 if len(x) != self.np else self._L.pamlh_gradient_full(self._h, x.ctypes.data_as(C.c_void_p), C.byref(lnl), g.ctypes.data_as(C.c_void_p))
+        if rc < 0:
+            raise RuntimeError("pamlh_gradient_full: " + self._L.pamlh_error(self._h).decode())
+        return None if rc else dict(lnL=lnl.value, grad=g[:self.np])
+
+    def rate_matrix(self, set_id):
+        """A[n][n]: the matrix the engine exponentiates for eigen set set_id of the present model state (pamlh_rate_matrix)."""
+        A = np.zeros((self.n, self.n))
+        self._L.pamlh_rate_matrix.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        if self._L.pamlh_rate_matrix(self._h, int(set_id), A.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_rate_matrix: " + self._L.pamlh_error(self._h).decode())
+        return A
 
     def branch_hessian(self, x):
         """dict(grad=[ntime], H=[ntime][ntime]) over the branch lengths at x, H_ij = -sum_h w_h s_i(h) s_j(h) from the analytic
