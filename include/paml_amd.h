@@ -344,6 +344,11 @@ int paml_amd_subtree_tables(const paml_amd_engine *e, long *n_tabulated, int *no
  * switches it off): whether the last evaluation ran with it, how often the engine has computed it (once per tips + tree + selection,
  * never per evaluation) and the host time of the last computation. */
 int paml_amd_subtree_order(const paml_amd_engine *e, int *in_use, long *n_computed, double *host_seconds);
+/* The gathering walk (a table form that is lookups and the root only runs on a kernel that fetches every distinct table row of a tile
+ * once into LDS; PAML_AMD_GATHER_WALK=0, read at every evaluation, keeps the generated walk): whether the last evaluation ran on it, the
+ * tiles and distinct rows (per class of the model) of its layout, the most rows of a tile (R), how often the engine has laid the tiles
+ * out (once per tips + tree + selection, never per evaluation) and the host time of the last layout. */
+int paml_amd_gather_walk(const paml_amd_engine *e, int *in_use, long *n_tiles, long *n_rows, int *R, long *n_computed, double *host_seconds);
 
 /* Host-only introspection (no GPU needed): the flattened post-order program the engine would run for
  * a tree — 4 ints per op (code, a, b, c; paml_amd/csrc/program.h).  Returns the number of ops (or a
@@ -394,6 +399,13 @@ int paml_amd_debug_subtree_classes(int n_tips, int n_nodes, int root, const int 
  * as_given: in the order given), ties by pattern number. */
 int paml_amd_debug_subtree_order(int n_keys, const unsigned int *keys, const unsigned int *bound, long n_patt, int largest_first, int as_given,
                                  unsigned int *order_out);
+
+/* Host-only: the tiles of the gathering walk (paml_amd/csrc/gather_tiles.h) for n_keys (1 .. 4) row arrays keys[n_keys][n_patt] (entries
+ * < bound[k]) along order[position] = pattern (null: the identity), at most R (n_keys .. 160) distinct rows per tile, with the weight
+ * flags wflag[n_patt] (null: all 1): the blocks the kernel reads, one per tile, into blocks_out (at most cap_bytes; null: none).  Returns
+ * the bytes of one block, or a negative error; *n_tiles, *n_rows: tiles and distinct rows in all. */
+int paml_amd_debug_gather_tiles(int n_keys, const unsigned int *keys, const unsigned int *bound, const unsigned int *order, const unsigned char *wflag,
+                                long n_patt, int R, unsigned char *blocks_out, long cap_bytes, long *n_tiles, long *n_rows);
 
 /* Host-only: the nodes an engine of these sizes (one gene, K classes, the PAML_AMD_SUBTREE_* / PAML_AMD_CHERRY_* switches of the
  * environment) tabulates above the cherries for tip codes z[n_tips][n_patt], sons before fathers.  Returns their number. */

@@ -97,6 +97,12 @@ struct PruneArgs {
    // ... whose tiles hold the patterns in another order (engine_eval.hip: ensure_subtree_ztiles): the pattern of position p is order[p], and
    // the walk stores its value there.  null: the identity (kernels generated without the order never read it)
    const int *order;
+   // the gathering walk (kernels_prune.h: gather_walk_kernel; gather_tiles.h: the blocks' layout): a table form that is lookups and the root
+   // only.  gw_desc: one block of gw_desc_bytes per tile (rows at most gw_R); lookup k reads subtree table gw_id[k] of stab_meta
+   // (gw_kind[k] = 0) or cherry table gw_id[k] (1); every lookup but the first is multiplied by the product of those before it
+   const unsigned char *gw_desc;
+   int gw_tiles, gw_desc_bytes, gw_R;
+   int gw_kind[4], gw_id[4];
 };
 
 __device__ __forceinline__ double root_value(const PruneArgs &a, double f, double lnscale)

@@ -213,8 +213,12 @@ int paml_amd_set_tips(paml_amd_engine *e, const unsigned char *z, int cleandata,
       if (e->gene_off[g + 1] < e->gene_off[g]) return fail(e, PAML_AMD_EINVAL, "set_tips: gene_off must not decrease");      // (a pattern shard may hold nothing of a gene)
    HIPCHK(upload(e->d_z, z, nz, e->stream));
    // (the subtree tables' classes are computed from the codes, lazily: engine_eval.hip — by the only engines that take such tables)
-   if (e->kk == KK_MFMA64 && e->n_genes == 1 && n_codes <= 64) e->h_z.assign(z, z + nz);
-   else std::vector<unsigned char>().swap(e->h_z);
+   if (e->kk == KK_MFMA64 && e->n_genes == 1 && n_codes <= 64) {
+      e->h_z.assign(z, z + nz);
+      e->h_wflag.resize(e->n_patt);
+      for (long h = 0; h < e->n_patt; h++) e->h_wflag[h] = weights[h] > 0 ? 1 : 0;
+   }
+   else { std::vector<unsigned char>().swap(e->h_z); std::vector<unsigned char>().swap(e->h_wflag); }
    e->tips_gen++;
    HIPCHK(upload(e->d_weights, weights, (size_t)e->n_patt, e->stream));
    HIPCHK(upload(e->d_n_chara, nch.data(), nch.size(), e->stream));
@@ -799,6 +803,18 @@ int paml_amd_subtree_order(const paml_amd_engine *e, int *in_use, long *n_comput
    if (in_use) *in_use = (e->last_stab_n && e->sub.ordered) ? 1 : 0;
    if (n_computed) *n_computed = e->sub.n_order_computed;
    if (host_seconds) *host_seconds = e->sub.order_host_s;
+   return 0;
+}
+
+int paml_amd_gather_walk(const paml_amd_engine *e, int *in_use, long *n_tiles, long *n_rows, int *R, long *n_computed, double *host_seconds)
+{
+   if (!e) return PAML_AMD_EINVAL;
+   if (in_use) *in_use = (e->last_stab_n && e->last_gw) ? 1 : 0;
+   if (n_tiles) *n_tiles = e->sub.gw_tiles;
+   if (n_rows) *n_rows = e->sub.gw_rows;
+   if (R) *R = e->sub.gw_R;
+   if (n_computed) *n_computed = e->sub.gw_computed;
+   if (host_seconds) *host_seconds = e->sub.gw_host_s;
    return 0;
 }
 

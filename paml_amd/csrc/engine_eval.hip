@@ -492,7 +492,8 @@ int ensure_subtree_ztiles(paml_amd_engine *e)
       const std::vector<unsigned int> order = subtree_pattern_order(keys, bound, subtree_order_sequence(bound, e->env.subtree_order == 2), (long)e->n_patt);
       sb.order_host_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       HIPCHK(upload(sb.d_order, (const int *)order.data(), order.size(), e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));      // (the host array goes)
+      HIPCHK(hipStreamSynchronize(e->stream));
+      sb.h_order = order;      // (kept for the gathering walk's tiles, which are cut along it)
       sb.order_sel_gen = sb.sel_gen;
       sb.n_order_computed++;
    }
@@ -504,6 +505,94 @@ int ensure_subtree_ztiles(paml_amd_engine *e)
    HIPCHK(hipStreamSynchronize(e->stream));
    sb.d_top_cls.release();
    sb.zt_sel_gen = sb.sel_gen; sb.zt_tiles = e->n_tiles; sb.zt_tile_patt = e->tile_patt;
+   return 0;
+}
+
+// The gathering walk (kernels_prune.h: gather_walk_kernel) serves a table form that is lookups, their multiplications into the stack slot
+// and the root only: two to four lookups, no operand block, no rescaling.  PAML_AMD_GATHER_WALK=0 keeps the generated walk (read per
+// evaluation: the tests flip it on one engine); the generated kernel is acquired either way.
+static bool gather_walk_wanted()
+{
+   const char *v = getenv("PAML_AMD_GATHER_WALK");
+   return !v || atoi(v) != 0;
+}
+static void gather_walk_plan(paml_amd_engine *e)
+{
+   paml_amd_engine::Subtree &sb = e->sub;
+   if (sb.gw_plan_gen == sb.sel_gen) return;
+   sb.gw_plan_gen = sb.sel_gen;
+   sb.gw_ok = false;
+   sb.gw_nlk = 0;
+   const Program &p = sb.sp.prog;
+   if (!p.stream.empty() || e->tree.n_scale || e->n_pi != 1 || e->n_genes != 1 || e->h_wflag.size() != (size_t)e->n_patt) return;
+   // the shape: the first lookup is pushed to a stack slot; every later one pops that slot — jit_mul(lookup, slot) — and is pushed there
+   // again, but the last, which stays the partial the root reads
+   bool have_cur = false, rooted = false;
+   int n = 0, slot = -1;
+   for (const Op &o : p.ops) {
+      if (o.code == OP_END) break;
+      if (o.code == OP_ROOT) {
+         if (!have_cur || rooted) return;
+         rooted = true;
+         continue;
+      }
+      if (o.code != OP_LOOKUP || rooted || have_cur || n == GATHER_MAX_LOOKUPS) return;
+      const int pop = mm_pop_slot(o), push = mm_push_slot(o);
+      if (n == 0 ? (pop >= 0 || push < 0) : (pop != slot || (push >= 0 && push != slot))) return;
+      if (n == 0) slot = push;
+      have_cur = push < 0;
+      const bool sub = o.c >= SUBTREE_TAB_BASE;
+      const long rows = sub ? (long)sb.u[sb.sp.sub[sb.sp.top[o.c - SUBTREE_TAB_BASE]].node] : (long)e->n_codes * e->n_codes;
+      if (rows < 1 || rows * (long)CHERRY_ROW_BYTES >= (1L << 31)) return;      // (a row's byte offset is a 32-bit buffer offset)
+      sb.gw_kind[n] = sub ? 0 : 1; sb.gw_id[n] = sub ? o.c - SUBTREE_TAB_BASE : o.c;
+      n++;
+   }
+   if (!rooted || n < 2) return;
+   sb.gw_nlk = n;
+   sb.gw_ok = true;
+}
+
+// Its tiles (gather_tiles.h): cut along the pattern order the tile blocks of the generated walk use, laid out and uploaded once per
+// selection — so only after set_tips, set_tree or a new selection —, when the switch first asks for them.
+int ensure_gather_tiles(paml_amd_engine *e)
+{
+   paml_amd_engine::Subtree &sb = e->sub;
+   gather_walk_plan(e);
+   if (!sb.gw_ok) return 0;
+   const int R = e->env.gather_R;
+   if (sb.gw_sel_gen == sb.sel_gen && sb.gw_R == R && sb.gw_ordered == sb.ordered) return 0;
+   if (sb.d_gw_desc.p) HIPCHK(hipDeviceSynchronize());      // (nothing may still read the previous selection's blocks)
+   const auto t0 = std::chrono::steady_clock::now();
+   const long np = e->n_patt;
+   std::vector<std::vector<unsigned int>> cls(sb.gw_nlk, std::vector<unsigned int>(np));
+   std::vector<const unsigned int *> keys;
+   std::vector<unsigned int> bound;
+   for (int k = 0; k < sb.gw_nlk; k++) {
+      if (sb.gw_kind[k] == 0) {      // the pattern's class at the tabulated node, as a row of its table, clamped as jit_lookup_row clamps
+         const int ti = sb.sp.top[sb.gw_id[k]];
+         const std::vector<unsigned int> &c = sb.cls[sb.sp.sub[ti].node], &rm = sb.rowmap[ti];
+         const unsigned int u = sb.u[sb.sp.sub[ti].node];
+         for (long h = 0; h < np; h++) cls[k][h] = std::min(rm.empty() ? c[h] : rm[c[h]], u - 1);
+         bound.push_back(u);
+      }
+      else {      // a cherry table's row ca * n_codes + cb, the codes clamped as jit_lookup_nc clamps them
+         const CherryTab &ct = sb.sp.tabs[sb.gw_id[k]];
+         const unsigned char *za = e->h_z.data() + (size_t)ct.tip_a * np, *zb = e->h_z.data() + (size_t)ct.tip_b * np;
+         const unsigned int nc = (unsigned int)e->n_codes;
+         for (long h = 0; h < np; h++) cls[k][h] = std::min((unsigned int)za[h], nc - 1) * nc + std::min((unsigned int)zb[h], nc - 1);
+         bound.push_back(nc * nc);
+      }
+      keys.push_back(cls[k].data());
+   }
+   const bool ordered = sb.ordered && sb.h_order.size() == (size_t)np;
+   const unsigned int *order = ordered ? sb.h_order.data() : nullptr;
+   const GatherTiles g = gather_tiles(keys, bound, order, np, R);
+   const std::vector<unsigned char> blocks = gather_tiles_pack(g, order, e->h_wflag.data(), np);
+   sb.gw_host_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+   HIPCHK(upload(sb.d_gw_desc, blocks.data(), blocks.size(), e->stream));
+   HIPCHK(hipStreamSynchronize(e->stream));
+   sb.gw_tiles = (long)g.n_tiles(); sb.gw_rows = g.total_rows(); sb.gw_R = R; sb.gw_sel_gen = sb.sel_gen; sb.gw_ordered = sb.ordered;
+   sb.gw_computed++;
    return 0;
 }
 
@@ -596,6 +685,8 @@ int choose_kernel(paml_amd_engine *e, const Eval &c, PruneKernel *out)
       if (int r = select_tiles(e, big_tiles, want_waves, jit_ok)) return r;
       if (e->n_stab)
          if (int r = ensure_subtree_ztiles(e)) return r;
+      if (e->n_stab && jit_ok && gather_walk_wanted() && e->env.prof_ops.empty() && !e->env.prof_tiles)
+         if (int r = ensure_gather_tiles(e)) return r;
       if (jit_ok || e->mfma_dma) {
          *out = jit_ok ? PK_MFMA64_JIT : PK_MFMA64_STREAM;
          return 0;
@@ -866,6 +957,16 @@ int run_prune(paml_amd_engine *e, Eval &c)
       pr.ztiles = e->sub.d_ztiles.p; pr.zt_bytes = e->sub.zt_bytes;
       pr.order = e->sub.ordered ? e->sub.d_order.p : nullptr;
    }
+   // the gathering walk in the generated walk's place, where the table form is lookups and the root only and its tiles are laid out for
+   // this selection (choose_kernel); everything around the launch stays
+   const paml_amd_engine::Subtree &gsb = e->sub;
+   const bool gather = k == PK_MFMA64_JIT && e->n_stab && !bs && gather_walk_wanted() && e->env.prof_ops.empty() && !e->env.prof_tiles && gsb.gw_ok &&
+                       gsb.gw_sel_gen == gsb.sel_gen && gsb.gw_ordered == gsb.ordered && gsb.gw_tiles > 0 && gsb.d_gw_desc.p;
+   e->last_gw = gather;
+   if (gather) {
+      pr.gw_desc = gsb.d_gw_desc.p; pr.gw_tiles = (int)gsb.gw_tiles; pr.gw_desc_bytes = gather_desc_bytes(gsb.gw_R); pr.gw_R = gsb.gw_R;
+      for (int i = 0; i < 4; i++) { pr.gw_kind[i] = gsb.gw_kind[i]; pr.gw_id[i] = gsb.gw_id[i]; }
+   }
    const int nb = (e->n_patt + e->chunk - 1) / e->chunk;      // the reduction's geometry: chunks of this engine
    if (pk_forms_reduction(k)) {      // (the others leave the partial sums to reduce_stage1)
       pr.Km = c.Km; pr.chunk = e->chunk; pr.first_chunk = e->first_chunk; pr.nb_stride = e->nb_global;
@@ -905,6 +1006,20 @@ int run_prune(paml_amd_engine *e, Eval &c)
    hipStream_t const ms = c.ms;
    switch (k) {
    case PK_MFMA64_JIT:      // persistent: one 130 KB-LDS workgroup per CU walks the tiles
+      if (gather) {
+         const size_t lds = gather_walk_lds_bytes(pr.gw_R);
+         if (!e->gw_attr_set) {
+            HIPCHK(hipFuncSetAttribute((const void *)gather_walk_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gather_walk_lds_bytes(128)));
+            HIPCHK(hipFuncSetAttribute((const void *)gather_walk_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gather_walk_lds_bytes(128)));
+            HIPCHK(hipFuncSetAttribute((const void *)gather_walk_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gather_walk_lds_bytes(128)));
+            e->gw_attr_set = true;
+         }
+         const dim3 gg(std::min(pr.gw_tiles * K, cus)), gb(512);
+         if (gsb.gw_nlk == 2) hipLaunchKernelGGL(gather_walk_kernel<2>, gg, gb, lds, ms, pr);
+         else if (gsb.gw_nlk == 3) hipLaunchKernelGGL(gather_walk_kernel<3>, gg, gb, lds, ms, pr);
+         else hipLaunchKernelGGL(gather_walk_kernel<4>, gg, gb, lds, ms, pr);
+         break;
+      }
       HIPCHK(hipModuleLaunchKernel(e->jit.fn, std::min(n_blocks, cus), 1, 1, e->mfma_waves * 64, 1, 1, 0, ms, params, nullptr));
       break;
    case PK_MFMA64_STREAM:

@@ -212,6 +212,32 @@ int paml_amd_debug_subtree_order(int n_keys, const unsigned int *keys, const uns
    return 0;
 }
 
+// gather_tiles + gather_tiles_pack (gather_tiles.h) for n_keys row arrays keys[n_keys][n_patt] below bound[n_keys]: the kernel's blocks.
+int paml_amd_debug_gather_tiles(int n_keys, const unsigned int *keys, const unsigned int *bound, const unsigned int *order, const unsigned char *wflag,
+                                long n_patt, int R, unsigned char *blocks_out, long cap_bytes, long *n_tiles, long *n_rows)
+{
+   if (n_keys < 1 || n_keys > GATHER_MAX_LOOKUPS || n_patt < 1 || !keys || !bound || R < n_keys || R > GATHER_R_MAX) return PAML_AMD_EINVAL;
+   std::vector<const unsigned int *> k(n_keys);
+   std::vector<unsigned int> b(bound, bound + n_keys);
+   for (int i = 0; i < n_keys; i++) k[i] = keys + (long)i * n_patt;
+   for (long i = 0; i < (long)n_keys * n_patt; i++)
+      if (keys[i] >= bound[i / n_patt]) return PAML_AMD_EINVAL;
+   if (order) {      // a permutation
+      std::vector<char> seen(n_patt, 0);
+      for (long i = 0; i < n_patt; i++) {
+         if (order[i] >= (unsigned long)n_patt || seen[order[i]]) return PAML_AMD_EINVAL;
+         seen[order[i]] = 1;
+      }
+   }
+   const GatherTiles g = gather_tiles(k, b, order, n_patt, R);
+   const std::vector<unsigned char> ones(wflag ? 0 : n_patt, 1);
+   const std::vector<unsigned char> blocks = gather_tiles_pack(g, order, wflag ? wflag : ones.data(), n_patt);
+   if (n_tiles) *n_tiles = (long)g.n_tiles();
+   if (n_rows) *n_rows = g.total_rows();
+   if (blocks_out) memcpy(blocks_out, blocks.data(), std::min((size_t)std::max(0L, cap_bytes), blocks.size()));
+   return gather_desc_bytes(R);
+}
+
 // The nodes an engine of these sizes (one gene, K classes, the switches of the environment) tabulates above the cherries for tip codes
 // z[n_tips][n_patt]: the classes, then jit_subtree_select with the engine's limits.  Returns their number (sel_out: the first `cap`).
 int paml_amd_debug_subtree_select(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node, int n_states,

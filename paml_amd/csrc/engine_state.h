@@ -49,6 +49,7 @@
 #include "program.h"
 #include "branch_plan.h"
 #include "subtree_classes.h"
+#include "gather_tiles.h"
 
 namespace paml_amd {
 static_assert(JIT_SCRATCH_BASE == MFMA_RS, "the per-tree kernel addresses the interpreter's overflow-stack scratch");
@@ -219,6 +220,10 @@ struct EnvCfg {
    // subtree tables run.  PAML_AMD_SUBTREE_ORDER=0: the alignment's order; 1 (the default): smallest table first; 2: largest table first
    // (measurements)
    int subtree_order = 1;
+   // a table form that is lookups and the root only runs on gather_walk_kernel (kernels_prune.h) instead of the generated
+   // walk.  PAML_AMD_GATHER_WALK=0 / 1 is read at every evaluation (gather_walk_wanted): the generated kernel is acquired either way.
+   // PAML_AMD_GATHER_R: most distinct rows of a tile (8 .. 128; DESIGN 4 B (xiv) has the measurements behind the default)
+   int gather_R = 128;
    int subtree_rows = 1;      // a table's rows lie in lexicographic order of (left son row, right son row); PAML_AMD_SUBTREE_ROWS=0: in order of first occurrence
    std::string jit_dump, prof_ops;
    int prof_tid = 0;
@@ -245,6 +250,7 @@ struct EnvCfg {
       if (const char *v = getenv("PAML_AMD_SUBTREE_CAP_MB")) subtree_cap_mb = std::max(0L, atol(v));
       if (const char *v = getenv("PAML_AMD_SUBTREE_ORDER")) subtree_order = std::max(0, std::min(2, atoi(v)));
       if (const char *v = getenv("PAML_AMD_SUBTREE_ROWS")) subtree_rows = atoi(v) != 0 ? 1 : 0;
+      if (const char *v = getenv("PAML_AMD_GATHER_R")) gather_R = std::max(8, std::min(128, atoi(v))) & ~1;
       if (const char *v = getenv("PAML_AMD_JIT_DUMP")) jit_dump = v;
       if (const char *v = getenv("PAML_AMD_PROF_OPS")) prof_ops = v;
       if (const char *v = getenv("PAML_AMD_PROF_TID")) prof_tid = atoi(v);
@@ -448,8 +454,17 @@ struct paml_amd_engine {
       DevBuf<unsigned int> d_sidx, d_top_cls;
       DevBuf<int> d_meta;
       DevBuf<unsigned char> d_ztiles;
+      // the gathering walk (gather_tiles.h; kernels_prune.h: gather_walk_kernel): the tiles with their distinct rows, for the selection
+      // gw_sel_gen; gw_ok: the table form is lookups and the root only (gather_walk_plan), with the lookups' tables
+      std::vector<unsigned int> h_order;      // d_order's host copy (the blocks are laid out when the switch first asks for them)
+      DevBuf<unsigned char> d_gw_desc;
+      long gw_sel_gen = -1, gw_plan_gen = -1, gw_tiles = 0, gw_rows = 0, gw_computed = 0;
+      int gw_R = 0, gw_nlk = 0, gw_kind[4] = {0, 0, 0, 0}, gw_id[4] = {0, 0, 0, 0};
+      bool gw_ok = false, gw_ordered = false;
+      double gw_host_s = 0;
    } sub;
-   std::vector<unsigned char> h_z;
+   bool gw_attr_set = false, last_gw = false;      // gather_walk_kernel's LDS attribute is set; the last evaluation ran on it
+   std::vector<unsigned char> h_z, h_wflag;        // (h_wflag: weight > 0, kept with h_z)
    long tips_gen = 0, tree_gen = 0, cherry_gen = 0;
    DevBuf<double> d_stab;
    int n_stab = 0;                            // this evaluation runs with so many subtree tables (0: none)
@@ -647,7 +662,7 @@ struct paml_amd_engine {
       d_pres.release();
       d_ctab.release();
       d_stab.release();
-      sub.d_nodes.release(); sub.d_sidx.release(); sub.d_top_cls.release(); sub.d_meta.release(); sub.d_ztiles.release(); sub.d_order.release();
+      sub.d_nodes.release(); sub.d_sidx.release(); sub.d_top_cls.release(); sub.d_meta.release(); sub.d_ztiles.release(); sub.d_order.release(); sub.d_gw_desc.release();
       d_eq_q.release(); d_eq_pi.release(); d_eq_scale.release(); d_eq_ptr.release(); d_eq_rc.release(); d_eq_sweeps.release();
       d_pi_plain.release();
       DevBuf<double> *b3[] = {&d_weights, &d_pi, &d_freqK, &d_rate, &d_qfactor, &d_branch, &d_gene_rate, &d_rowmajor,

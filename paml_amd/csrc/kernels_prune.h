@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "gather_tiles.h"
 #include "kernel_args.h"
 
 namespace paml_amd {
@@ -809,6 +810,140 @@ __global__ __launch_bounds__(256) void sztile_kernel(const int2 *tiles, const in
    for (int k = 0; k < n_top; k++) {
       const unsigned int c = in ? top_cls[(long)k * z_stride + h] : 0u;
       for (int b = 0; b < 3; b++) o[(long)(n_tips + 1 + 3 * k + b) * tp + i] = (unsigned char)((c >> (8 * b)) & 255u);
+   }
+}
+
+// ---- the gathering walk: a table form that is lookups and the root only (the headline: three subtree tables; any tree whose root's sons
+// are all tabulated) ----------------------------------------------------------------------------------------------------------------------
+// The generated walk (jit.h, short form) asks for a pattern's rows lane by lane: a wave instruction of jit_lookup_row touches sixteen rows,
+// 64 bytes of each, every row is asked for by every pattern that reads it, and a tile ends with nothing in flight.  Here a tile comes with
+// the list of its DISTINCT rows (gather_tiles.h; at most gw_R of them), and the workgroup — one per CU, persistent over the (tile, class)
+// work items, class-major like the generated walk — fetches every one of them once, whole: 32 lanes x 16 bytes are a row, a wave
+// instruction (LDS-DMA with a per-lane source offset) brings the rows of two neighbouring slots into one 1 KB piece of the row buffer, all
+// eight waves load.  Two row buffers: while tile t is computed from one, tile t + 1's rows are on their way into the other and tile t + 2's
+// block of lists into the third of three block buffers.  A stage ends with ONE s_waitcnt vmcnt(0) and ONE barrier: no counted waits,
+// nothing depends on where the compiler puts a load.  (A third row buffer would buy nothing in this form: the stage's wait drains
+// everything that was requested, whatever buffer it goes to.)
+// LDS image: a ds_read_b128 is served in lane groups of sixteen — eight patterns of one q and eight of its neighbour q ^ 1 — that read the
+// same offset of different rows; bank = (address / 4) mod 64, so rows a multiple of 256 bytes apart would all meet on one bank.  Piece j
+// (slots 2 j and 2 j + 1) lies at j x GW_PIECE_BYTES = 1024 + 64, and the odd slot's row is stored with its 16-byte chunks c at c ^ 2
+// (the DMA's source offset does that; the reader asks for q ^ 2): the 16-byte bank column of (slot s, element pair i, q) is
+// 2 s + (q & 1) for q < 2 and 2 (s ^ 1) + (q & 1) for the others (+ 4 i, mod 16).  The two q of a lane group never meet, and two slots
+// meet only when they are a multiple of 8 apart — a run of the sorted order, which reads neighbouring slots, is conflict-free.  Inside a
+// row the tables' layout [element pair][q][16 bytes] stays, so a pattern reads what jit_lookup_row reads, and the arithmetic is the
+// generated walk's call for call: jit_mul by the popped slot, lookup after lookup, then jit_root_lds — same bits.
+// Registers: 60.  (A form that interpreted the program's pop / push slots at run time and asked for all rows of a pattern at once took
+// 246 and ran the walk in 0.112 ms against this one's 0.088; with two row buffers of R = 128 the kernel has a CU's LDS to itself either
+// way: the builders of the next evaluation, which shared the CUs with the generated walk, wait for its end — DESIGN 4 B (xiv).)
+constexpr int GW_PIECE_BYTES = 1024 + 64;
+constexpr int GW_DESC_BUFS = 3;
+constexpr size_t gather_walk_lds_bytes(int R) { return (size_t)2 * (gather_desc_slots(R) / 2) * GW_PIECE_BYTES + (size_t)GW_DESC_BUFS * gather_desc_bytes(R) + 64 * sizeof(double); }
+
+// dma16 (device_common.h) with the LDS address — wave-uniform, but a loop's induction variable to the compiler — made a scalar explicitly
+__device__ __forceinline__ void gw_dma16(__amdgpu_buffer_rsrc_t r, const void *lds, int voff)
+{
+   const unsigned la = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(__attribute__((address_space(3))) const char *)lds);
+   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" : : "s"(la), "v"(voff), "s"(r) : "memory", "m0");
+}
+
+// (launch bounds: 512 threads; the second figure is HIP's — waves per SIMD the compiler must leave room for, here four, i.e. at most 128
+//  VGPRs — not CUDA's blocks per multiprocessor.  The kernel needs 60 - 63; the bound only keeps a later change from growing it unseen.)
+template <int NLK>
+__global__ __launch_bounds__(512, 4) void gather_walk_kernel(PruneArgs a)
+{
+   extern __shared__ __attribute__((aligned(16))) unsigned char gw_smem[];
+   const int R = a.gw_R, DB = a.gw_desc_bytes, RB = (gather_desc_slots(R) / 2) * GW_PIECE_BYTES;
+   unsigned char *const rowbuf = gw_smem;                       // [2][RB]
+   unsigned char *const descbuf = gw_smem + 2 * RB;             // [GW_DESC_BUFS][DB]
+   double *const sPi = (double *)(descbuf + GW_DESC_BUFS * DB); // [4][16]
+   const int tid = threadIdx.x, lane = tid & 63;
+   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+   const int q = lane >> 4, hl = lane & 15, p = wave * 16 + hl;
+   const int total = a.gw_tiles * a.K, step = gridDim.x;
+   if ((int)blockIdx.x >= total) return;
+   if (tid < 64) sPi[tid] = a.pi[tid];
+   const int nc2 = a.n_codes * a.n_codes;
+
+   // a tile's block of lists -> block buffer d (256-byte pieces, one per wave)
+   auto issue_desc = [&](int work, int d) {
+      const int tile = work % a.gw_tiles;
+      if (wave * 256 < DB) dma4(make_rsrc(a.gw_desc + (long)tile * DB, DB), descbuf + d * DB + wave * 256, lane * 4, wave * 256);
+   };
+   // the distinct rows of the tile whose block has landed in buffer d -> row buffer b: piece j by wave j & 7
+   auto issue_rows = [&](int work, int d, int b) {
+      const int iclass = work / a.gw_tiles;
+      const int *head = (const int *)(descbuf + d * DB);
+      const unsigned int *rows = (const unsigned int *)(descbuf + d * DB + 32);
+      const int s1 = __builtin_amdgcn_readfirstlane(head[2]), s2 = __builtin_amdgcn_readfirstlane(head[3]), s3 = __builtin_amdgcn_readfirstlane(head[4]);
+      int ns = __builtin_amdgcn_readfirstlane(head[5]);
+      ns = ns < gather_desc_slots(R) ? ns : (gather_desc_slots(R) & ~1);      // (never past the row buffer, whatever the block says)
+      const double *tab[NLK];
+      unsigned int bytes[NLK];
+#pragma unroll
+      for (int k = 0; k < NLK; k++) {
+         if (a.gw_kind[k]) { tab[k] = a.ctab + ((long)iclass * a.n_ctab + a.gw_id[k]) * (long)nc2 * CHERRY_ROW_WORDS; bytes[k] = (unsigned int)nc2 * 512u; }
+         else { tab[k] = JIT_STAB(iclass, a.gw_id[k]); bytes[k] = (unsigned int)JIT_STAB_U(a.gw_id[k]) * 512u; }
+      }
+      for (int j = wave; 2 * j < ns; j += 8) {
+         const int k = (2 * j >= s1) + (2 * j >= s2) + (2 * j >= s3);      // wave-uniform: the lists start at even slots
+         const double *t = tab[0];
+         unsigned int nb = bytes[0];
+#pragma unroll
+         for (int kk = 1; kk < NLK; kk++)
+            if (k == kk) { t = tab[kk]; nb = bytes[kk]; }
+         const unsigned int row = rows[2 * j + (lane >> 5)];
+         // (a row past its table's end reads zeros: the descriptor's bound, not the list, guards the address)
+         gw_dma16(make_rsrc(t, nb), rowbuf + b * RB + j * GW_PIECE_BYTES, (int)(row * 512u + (unsigned int)((lane & 31) ^ ((lane >> 5) << 1)) * 16u));
+      }
+   };
+   auto landed = [&]() {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+   };
+
+   int work = blockIdx.x;
+   issue_desc(work, 0);
+   landed();
+   issue_rows(work, 0, 0);
+   if (work + step < total) issue_desc(work + step, 1);
+   landed();
+   for (int t = 0; work < total; work += step, t++) {
+      const int d = t % GW_DESC_BUFS, b = t & 1;
+      if (work + step < total) issue_rows(work + step, (t + 1) % GW_DESC_BUFS, b ^ 1);
+      if (work + 2 * step < total) issue_desc(work + 2 * step, (t + 2) % GW_DESC_BUFS);
+      {
+         const int iclass = work / a.gw_tiles;
+         const unsigned char *D = descbuf + d * DB;
+         const int np = ((const int *)D)[1];
+         const bool valid = p < np;
+         const unsigned char *rb = rowbuf + b * RB;
+         // the rows of a pattern, in the layout jit_lookup_row delivers
+         auto row_of = [&](int k, v4d (&x)[4]) {
+            const int s = D[gather_desc_off_slot(R) + k * GATHER_TILE_PATT + p];
+            const unsigned char *r = rb + (s >> 1) * GW_PIECE_BYTES + (s & 1) * 512 + (q ^ ((s & 1) << 1)) * 16;
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+               const part2_t v = *(const part2_t *)(r + i * 64);
+               x[i >> 1][(2 * i) & 3] = v.x;
+               x[i >> 1][(2 * i + 1) & 3] = v.y;
+            }
+         };
+         const int flag = D[gather_desc_off_flag(R) + p];
+         const int hs = ((const int *)(D + gather_desc_off_patt(R)))[p];
+         // the program (engine_eval.hip: gather_walk_plan admits this shape only): the first lookup goes to a stack slot, every later one
+         // is multiplied by the slot — jit_mul(lookup, slot): y = s * y — and takes its place; the last one is the partial the root reads
+         v4d cur[4];
+         row_of(0, cur);
+#pragma unroll
+         for (int k = 1; k < NLK; k++) {
+            v4d x[4];
+            row_of(k, x);
+            jit_mul(x, cur);
+            jit_copy(cur, x);
+         }
+         jit_root_lds(a, cur, 0.0, sPi, flag, iclass, q, hs, valid);
+      }
+      landed();
    }
 }
 

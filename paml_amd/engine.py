@@ -31,6 +31,7 @@ EXPORTS = [
     "paml_amd_jit_prebuild", "paml_amd_profile", "paml_amd_profile_read", "paml_amd_counters", "paml_amd_kernel_name", "paml_amd_debug_program", "paml_amd_debug_jit",
     "paml_amd_cherry_tables", "paml_amd_debug_jit_tables",
     "paml_amd_subtree_tables", "paml_amd_subtree_order", "paml_amd_debug_subtree_order", "paml_amd_debug_subtree_classes", "paml_amd_debug_jit_subtree", "paml_amd_debug_subtree_select",
+    "paml_amd_gather_walk", "paml_amd_debug_gather_tiles",
     "paml_amd_debug_code_order", "paml_amd_debug_branch_plan",
     "paml_amd_pairset_create", "paml_amd_pairset_destroy", "paml_amd_pairset_get_counts", "paml_amd_pairset_set_pi", "paml_amd_pairset_set_pattern",
     "paml_amd_pairset_eval", "paml_amd_pairset_failed", "paml_amd_pairset_counters",
@@ -655,6 +656,16 @@ class Engine:
         self._chk(self._L.paml_amd_subtree_order(self._h, C.byref(use), C.byref(nc), C.byref(sec)))
         return dict(in_use=bool(use.value), n_computed=nc.value, host_seconds=sec.value)
 
+    def gather_walk(self):
+        """The gathering walk (csrc/kernels_prune.h: gather_walk_kernel): dict(in_use — the last evaluation ran on it —, tiles, rows — of
+        its layout, the distinct rows per class of the model —, R — the most rows of a tile —, n_computed — layouts of this engine so
+        far —, host_seconds of the last one)."""
+        use, nt, nr, r, nc, sec = C.c_int(), C.c_long(), C.c_long(), C.c_int(), C.c_long(), C.c_double()
+        self._L.paml_amd_gather_walk.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int), C.POINTER(C.c_long),
+                                                 C.POINTER(C.c_double)]
+        self._chk(self._L.paml_amd_gather_walk(self._h, C.byref(use), C.byref(nt), C.byref(nr), C.byref(r), C.byref(nc), C.byref(sec)))
+        return dict(in_use=bool(use.value), tiles=nt.value, rows=nr.value, R=r.value, n_computed=nc.value, host_seconds=sec.value)
+
     def counters(self):
         a, b = C.c_long(), C.c_long()
         self._L.paml_amd_counters(self._h, C.byref(a), C.byref(b))
@@ -896,6 +907,42 @@ def debug_subtree_order(keys, bound, largest_first=False, as_given=False):
     if rc < 0:
         raise EngineError("debug_subtree_order failed (%d)" % rc)
     return out
+
+
+def debug_gather_tiles(keys, bound, order=None, wflag=None, R=128):
+    """Host-only: the tiles of the gathering walk (csrc/gather_tiles.h) for row arrays keys[n_keys][n_patt] below bound[n_keys] along
+    order[position] = pattern (None: the identity): a list of dicts, one per tile — first, count, rows (one list per key), slot
+    [n_keys][count] (into that key's list), flag[count], patt[count] — decoded from the blocks the kernel reads, and the number of
+    distinct rows in all."""
+    L = lib()
+    keys = np.ascontiguousarray(keys, dtype=np.uint32)
+    bound = np.ascontiguousarray(bound, dtype=np.uint32)
+    nk, n_patt = keys.shape
+    order = None if order is None else np.ascontiguousarray(order, dtype=np.uint32)
+    wflag = None if wflag is None else np.ascontiguousarray(wflag, dtype=np.uint8)
+    L.paml_amd_debug_gather_tiles.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long,
+                                              C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    nt, nr = C.c_long(), C.c_long()
+    db = L.paml_amd_debug_gather_tiles(nk, _p(keys), _p(bound), _p(order), _p(wflag), n_patt, int(R), None, 0, C.byref(nt), C.byref(nr))
+    if db < 0:
+        raise EngineError("debug_gather_tiles failed (%d)" % db)
+    blocks = np.zeros(nt.value * db, dtype=np.uint8)
+    L.paml_amd_debug_gather_tiles(nk, _p(keys), _p(bound), _p(order), _p(wflag), n_patt, int(R), _p(blocks), blocks.size, C.byref(nt), C.byref(nr))
+    off_slot = 32 + 4 * (R + 4)
+    tiles = []
+    for t in range(nt.value):
+        d = blocks[t * db:(t + 1) * db]
+        head = d[:32].view(np.int32)
+        rows = d[32:off_slot].view(np.uint32)
+        start = [0, int(head[2]), int(head[3]), int(head[4]), int(head[5])]
+        count = int(head[1])
+        slot = d[off_slot:off_slot + 512].reshape(4, 128)
+        tiles.append(dict(first=int(head[0]), count=count, slots=int(head[5]), start=start[:nk],
+                          rows=[rows[start[k]:start[k + 1]].tolist() for k in range(nk)],
+                          slot=np.stack([slot[k, :count].astype(np.int64) - start[k] for k in range(nk)]), slot_tail=slot[:nk, count:].copy(),
+                          flag=d[off_slot + 512:off_slot + 640][:count].copy(), flag_tail=d[off_slot + 512:off_slot + 640][count:].copy(),
+                          patt=d[off_slot + 640:off_slot + 640 + 512].view(np.int32)[:count].copy()))
+    return tiles, nr.value
 
 
 def debug_subtree_select(tree, z, n_states, n_codes, K=1, scale_node=None):
