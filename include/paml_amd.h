@@ -538,6 +538,22 @@ int paml_amd_gradient(paml_amd_engine *e, const double *branch, const double *ge
  * the batches); either pointer may be NULL. */
 void paml_amd_gradient_info(int *last_batches, double *last_kernel_ms);
 
+/* ---- lnL, its derivative and its SECOND derivative along every branch length in one call: what a Newton step on all branches at once
+ * needs (the definition and the kernels are written out in csrc/kernels_curvature.h).  curv[v] = d^2 lnL / d branch[v]^2 of exactly the
+ * number paml_amd_eval returns, for any rooting and any mix of eigen systems — the diagonal of the Hessian over the branch lengths; the
+ * cross derivatives are not formed.  curv[root] = 0, a pattern of weight 0 contributes nothing.  *lnL, grad[] and lnf[] have the bytes
+ * paml_amd_gradient returns on the same engine and inputs: the same statements run, plus one product and one dot product per non-root
+ * node.  Takes what paml_amd_gradient takes and leaves the engine as it does (paml_amd_get_pmat afterwards returns the matrices the
+ * call used); the workspace is 256 MiB or PAML_AMD_CURV_ARENA_MB (read at every call), and every result has the same bytes whatever
+ * the batches and on every call.  PAML_AMD_EINVAL for a null branch, lnL, grad or curv, a model or tips not set; PAML_AMD_EUNSUPPORTED
+ * for a rate-matrix (UNREST) set, more than 64 states, an engine whose communicator has more than one rank. */
+int paml_amd_curvature(paml_amd_engine *e, const double *branch, const double *gene_rate, double *lnL,
+                       double *grad /* [n_nodes] */,
+                       double *curv /* [n_nodes] */,
+                       double *lnf  /* [n_patt], or NULL */);
+/* The number of batches the calling thread's last paml_amd_curvature walked and the time of its kernels by HIP events (ms). */
+void paml_amd_curvature_info(int *last_batches, double *last_kernel_ms);
+
 /* ---- The derivative of lnL with respect to every INPUT of the engine in one call: what a chain rule on the host needs to give
  * d lnL / d (any model parameter) without an evaluation or a decomposition per parameter (the definition and the kernels are written out
  * in csrc/kernels_modelgrad.h).  lnL is the number paml_amd_gradient returns at (branch, gene_rate), a function of

@@ -261,6 +261,25 @@ int pamlh_method(const pamlh *p);      /* the control file's `method` */
 int pamlh_minbranches(pamlh *p, double *x, double e, double *lnL, int verbose);
 int pamlh_optimize_minb(pamlh *p, double *x, double *lnL, double e0, int verbose, int *n_eval);
 
+/* ---- Newton steps on every branch length at once (pamlh_newton.c), from the engine call that returns lnL, the gradient and the curvature
+ * along every branch (paml_amd_curvature): a sweep is ONE engine call, where a pamlh_minbranches sweep is at least 2 (n - 1).
+ * pamlh_curvature: lnL at x and, over x's branch-length block (pamlh_branch_order, ntime entries), g = d lnL / d t and h = d2 lnL / d t2
+ *   — the diagonal of the Hessian of the tree as it is rooted; one engine call.
+ * pamlh_newton_branches: maximises over the branch block with the rest of x held.  Per sweep and branch the step -g / h where h < 0,
+ *   otherwise a step of the gradient's sign of the size of the current length (0.01 for a shorter one), capped by a trust factor per
+ *   branch and clipped to the box of pamlh_bounds; the next sweep's call is also the test of the step: if lnL fell the previous lengths
+ *   are restored and every trust factor is halved (quartered where the gradient changed sign), if not they grow back.  Ends when an
+ *   accepted sweep gained less than e with max |step| < sqrt(e), or after max_sweeps sweeps.  lnL never decreases from entry to exit; x
+ *   returns the best lengths seen, *lnL their lnL, stats[3] (may be NULL) the sweeps, the engine calls and the rejected sweeps.
+ *   verbose: a line per sweep on stderr.
+ * pamlh_optimize_newton: the alternation of pamlh_optimize_minb with pamlh_newton_branches in the place of pamlh_minbranches; BFGS on
+ *   the other parameters unchanged.  n_eval: the evaluations of the parameter steps plus one per engine call of the branch steps.
+ * Refused by name, as pamlh_gradient declines them: a clock (x holds ages), fix_blength = 2 / 3, rho != 0, a rate-matrix (UNREST) model,
+ * a pattern shard. */
+int pamlh_curvature(pamlh *p, const double *x, double *lnL, double *g, double *h);
+int pamlh_newton_branches(pamlh *p, double *x, double e, int max_sweeps, double *lnL, int verbose, int *stats);
+int pamlh_optimize_newton(pamlh *p, double *x, double *lnL, double e0, int verbose, int *n_eval);
+
 /* Standard errors of the estimates (getSE = 1).  method 0: HessianSKT2004 (treesub.c:7241), the outer product of per-pattern
  * scores that the reference's programs print; method 1: observed information from central second differences of lnL
  * (Hessian() tools.c:5984).  Either way all perturbed evaluations are one batch.  se[np] (-1: not available, e.g. a parameter

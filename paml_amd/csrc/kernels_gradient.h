@@ -29,6 +29,10 @@
 // two genes) in a fixed butterfly; grad_total_kernel adds a row's chunks in a fixed order (red_total256).  Nothing depends on the batch a
 // pattern falls in.  Ordinary vector stores only; no atomics.
 //
+// The bodies take a compile-time switch, CURV: false is this call; true adds the second derivative along every branch (paml_amd_curvature,
+// kernels_curvature.h) — one more product and one more dot product per non-root node, and a row of the combination per node.  Everything
+// the switch adds stands inside `if constexpr (CURV)`: the arithmetic of lnL and grad is the same statements in both.
+//
 // The per-lane bodies (grad_lane_*, grad_combine) are plain functions of (arguments, class or node, pattern): a host program calls them in
 // a loop (GRAD_HOST_ONLY: no HIP at all; tools/gradient_host_check.cpp), which is how they are run under the host sanitizers.
 #pragma once
@@ -59,6 +63,9 @@ struct GradArgs {
    double *partial;           // [n_nodes + 1][n_chunks]: the chunks' sums of w s_v; row n_nodes: of w lnf
    long chunk0, n_chunks;     // the batch's first chunk; chunks of the whole engine
    int ref_node;              // the root's first son: where lnf is taken
+   // CURV only (kernels_curvature.h); partial is then [2 n_nodes + 1][n_chunks]: w s_v, w c_v, w lnf, and scores is not written
+   const double *d2P;         // as dP
+   double *cur;               // [K][n_nodes][stride]: e_vk
 };
 
 GRAD_HD long grad_out_idx(const GradArgs &a, int k, int v, long p) { return ((long)k * a.m.t.n_nodes + v) * a.m.stride + p; }
@@ -76,7 +83,7 @@ template <int N> GRAD_HD void grad_lane_root(const GradArgs &a, int k, long p)
 }
 
 // node v (not the root) of pattern p, class k: H_v, the two sums, and A_v of an internal v.  The father's A is there already.
-template <int N> GRAD_HD void grad_lane_node(const GradArgs &a, int k, long p, int v)
+template <int N, bool CURV = false> GRAD_HD void grad_lane_node(const GradArgs &a, int k, long p, int v)
 {
    const AncMargArgs &m = a.m;
    const AncTree &t = m.t;
@@ -113,6 +120,12 @@ template <int N> GRAD_HD void grad_lane_node(const GradArgs &a, int k, long p, i
    const long oi = grad_out_idx(a, k, v, p);
    a.num[oi] = num;
    a.den[oi] = den;
+   if constexpr (CURV) {
+      double cur = 0;
+      anc_lane_matvec<N>(a.d2P + (pset * t.n_nodes + v) * (N * N), x, y);
+      for (int c = 0; c < N; c++) cur += h[c] * y[c];
+      a.cur[oi] = cur;
+   }
    if (v < t.n_tips) {
       a.sig[oi] = ls;
       return;
@@ -138,24 +151,27 @@ template <int N> GRAD_HD void grad_lane_node(const GradArgs &a, int k, long p, i
 }
 
 // the outer + derivative pass of pattern p, class k: the internal nodes father first, then the tips
-template <int N> GRAD_HD void grad_lane_outer(const GradArgs &a, int k, long p)
+template <int N, bool CURV = false> GRAD_HD void grad_lane_outer(const GradArgs &a, int k, long p)
 {
    const AncTree &t = a.m.t;
    grad_lane_root<N>(a, k, p);
-   for (int i = 0; i < t.n_pre; i++) grad_lane_node<N>(a, k, p, t.pre[i]);
+   for (int i = 0; i < t.n_pre; i++) grad_lane_node<N, CURV>(a, k, p, t.pre[i]);
    for (int v = 0; v < t.n_tips; v++)
-      if (v != t.root) grad_lane_node<N>(a, k, p, v);
+      if (v != t.root) grad_lane_node<N, CURV>(a, k, p, v);
 }
 
 // the classes of node v (v = n_nodes: ln f_h, at ref_node) at pattern p: stores the score (the root, a pattern of weight 0: 0) or lnf;
-// returns the pattern's term of the weighted sum
-GRAD_HD double grad_combine(const GradArgs &a, int v, long p)
+// returns the pattern's term of the weighted sum.  CURV: the rows are 0 .. n_nodes - 1 the scores (not stored), n_nodes .. 2 n_nodes - 1
+// the curvatures c_v(h) = sum_k rho_k e_vk / sum_k rho_k f_vk - s_v(h)^2, 2 n_nodes ln f_h
+template <bool CURV = false> GRAD_HD double grad_combine(const GradArgs &a, int row, long p)
 {
    const AncMargArgs &m = a.m;
-   const bool want_lnf = v == m.t.n_nodes;
+   const int nn = m.t.n_nodes;
+   const bool want_lnf = row == (CURV ? 2 * nn : nn), want_cur = CURV && !want_lnf && row >= nn;
+   const int v = want_cur ? row - nn : row;
    const double w = a.weights[m.h0 + p];
    if (!want_lnf && (v == m.t.root || !(w > 0))) {
-      a.scores[(long)v * m.stride + p] = 0;
+      if constexpr (!CURV) a.scores[(long)v * m.stride + p] = 0;
       return 0;
    }
    const int node = want_lnf ? a.ref_node : v;
@@ -164,12 +180,14 @@ GRAD_HD double grad_combine(const GradArgs &a, int v, long p)
       const double s = a.sig[grad_out_idx(a, k, node, p)];
       smax = s > smax ? s : smax;
    }
-   double num = 0, den = 0;
+   double num = 0, den = 0, cur = 0;
    for (int k = 0; k < m.K; k++) {
       const long oi = grad_out_idx(a, k, node, p);
       const double c = m.freqK[k] * exp(a.sig[oi] - smax);
       num += c * a.num[oi];
       den += c * a.den[oi];
+      if constexpr (CURV)
+         if (want_cur) cur += c * a.cur[oi];
    }
    if (want_lnf) {
       const double lf = log(den) + smax;
@@ -177,12 +195,16 @@ GRAD_HD double grad_combine(const GradArgs &a, int v, long p)
       return w > 0 ? w * lf : 0.0;
    }
    const double s = num / den;
-   a.scores[(long)v * m.stride + p] = s;
+   if constexpr (CURV) {
+      if (want_cur) return w * (cur / den - s * s);
+   }
+   else a.scores[(long)v * m.stride + p] = s;
    return w * s;
 }
 
 #ifndef GRAD_HOST_ONLY
-// ---- kernels: defined in engine_gradient.hip, launched from any unit of the library ----------------------------------------------
+// ---- kernels: defined in engine_gradient.hip, launched from any unit of the library; their bodies here, for the CURV instantiations of
+// ---- engine_curvature.hip ------------------------------------------------------------------------------------------------------------
 
 struct GradPmatArgs {
    int n, K, n_nodes, n_tips, root, n_labels, rate_gs, mfma;
@@ -191,6 +213,7 @@ struct GradPmatArgs {
    const double *branch, *rate, *gene_rate, *qfactor;
    const double *P;           // the evaluation's P(t), row-major [pset][n_nodes][n * n]
    double *dP, *PT;           // GradArgs::dP, GradArgs::PT
+   double *d2P;               // CURV only: GradArgs::d2P
 };
 
 __global__ void grad_pmat_kernel(GradPmatArgs a);
@@ -206,6 +229,204 @@ __device__ __forceinline__ double grad_mfma_dot(const double (&u)[16], const dou
    s += __shfl_xor(s, 16);
    s += __shfl_xor(s, 32);
    return s;
+}
+
+// dP (CURV: and d^2P) of every (parameter set, node): grid (n_nodes, gene x class), 256 threads; sE, sM: 64 doubles of LDS each.  The
+// formulas are pmat_deriv_kernel's, term for term.
+template <bool CURV> __device__ __forceinline__ void grad_pmat_body(const GradPmatArgs &a, double *sE, double *sM)
+{
+   const int node = blockIdx.x, pset = blockIdx.y, n = a.n;
+   if (node == a.root) return;
+   const int gene = pset / a.K, iclass = pset % a.K, lab = a.label[node];
+   const EigenDev es = a.eigen[a.eigen_of[(gene * a.K + iclass) * a.n_labels + lab]];
+   const double t = a.branch[node];
+   const double qf = es.kind == PAML_AMD_EIGEN_UVROOT ? a.qfactor[iclass * a.n_labels + lab] : 1.0;
+   const double base = a.gene_rate[gene] * a.rate[gene * a.rate_gs + iclass] * qf;
+   const int nroot = es.kind == PAML_AMD_EIGEN_CIJK ? es.nR : n;
+   const bool closed = es.kind == PAML_AMD_EIGEN_K80 || es.kind == PAML_AMD_EIGEN_JC69LIKE, k80 = es.kind == PAML_AMD_EIGEN_K80;
+   double m1 = 0, m2 = 0, e1 = 0, e2 = 0;
+   if (closed) {
+      m1 = base * (k80 ? -4 / (es.kappa + 2) : -(double)n / (n - 1));
+      m2 = base * (k80 ? -2 * (es.kappa + 1) / (es.kappa + 2) : 0.0);
+      e1 = exp(t * m1);
+      e2 = k80 ? exp(t * m2) : 0.0;
+   }
+   else {
+      for (int k = threadIdx.x; k < nroot; k += 256) {
+         const double mu = base * es.Root[k];
+         sM[k] = mu;
+         sE[k] = k ? exp(t * mu) : 1.0;
+      }
+      __syncthreads();
+   }
+   auto entry = [&](int i, int j) -> double {
+      if (closed) {
+         double c1, c2;
+         if (k80) { c1 = (i == j || (i ^ j) == 1) ? 0.25 : -0.25; c2 = i == j ? 0.5 : ((i ^ j) == 1 ? -0.5 : 0.0); }
+         else { c1 = i == j ? 1 - 1.0 / n : -1.0 / n; c2 = 0; }
+         return c1 * e1 * m1 + c2 * e2 * m2;
+      }
+      double dp = 0;
+      for (int k = 1; k < nroot; k++) {
+         const double c0 = es.kind == PAML_AMD_EIGEN_CIJK ? es.Cijk[((long)i * n + j) * nroot + k] * sE[k] : (es.U[i * n + k] * sE[k]) * es.V[k * n + j];
+         dp += c0 * sM[k];
+      }
+      return dp;
+   };
+   // (CURV: d2P in loops of its own after dP's, so that dP's statements are compiled as they are without it — the same bytes of dP, and
+   //  with them of grad, in both instantiations)
+   auto entry2 = [&](int i, int j) -> double {
+      if (closed) {
+         double c1, c2;
+         if (k80) { c1 = (i == j || (i ^ j) == 1) ? 0.25 : -0.25; c2 = i == j ? 0.5 : ((i ^ j) == 1 ? -0.5 : 0.0); }
+         else { c1 = i == j ? 1 - 1.0 / n : -1.0 / n; c2 = 0; }
+         return c1 * e1 * m1 * m1 + c2 * e2 * m2 * m2;
+      }
+      double ddp = 0;
+      for (int k = 1; k < nroot; k++) {
+         const double c0 = es.kind == PAML_AMD_EIGEN_CIJK ? es.Cijk[((long)i * n + j) * nroot + k] * sE[k] : (es.U[i * n + k] * sE[k]) * es.V[k * n + j];
+         ddp += c0 * sM[k] * sM[k];
+      }
+      return ddp;
+   };
+   const long slot = (long)pset * a.n_nodes + node;
+   if (!a.mfma) {
+      double *dP = a.dP + slot * n * n;
+      for (int idx = threadIdx.x; idx < n * n; idx += 256) dP[idx] = entry(idx / n, idx % n);
+      if constexpr (CURV)
+         for (int idx = threadIdx.x; idx < n * n; idx += 256) a.d2P[slot * n * n + idx] = entry2(idx / n, idx % n);
+      return;
+   }
+   // A-operand order: element ((kb2*4 + jb)*64 + lane)*2 + e  =  M[jb*16 + (lane&15)][4*(2*kb2+e) + (lane>>4)], zero padded
+   const double *P = a.P + slot * n * n;
+   double *df = a.dP + slot * 4096, *tf = a.PT + slot * 4096;
+   for (int idx = threadIdx.x; idx < 4096; idx += 256) {
+      const int e = idx & 1, lane = (idx >> 1) & 63, jb = (idx >> 7) & 3, kb2 = idx >> 9;
+      const int r = jb * 16 + (lane & 15), c = 4 * (2 * kb2 + e) + (lane >> 4);
+      const bool in = r < n && c < n;
+      df[idx] = in ? entry(r, c) : 0.0;
+      if (node >= a.n_tips) tf[idx] = in ? P[c * n + r] : 0.0;
+   }
+   if constexpr (CURV)
+      for (int idx = threadIdx.x; idx < 4096; idx += 256) {
+         const int e = idx & 1, lane = (idx >> 1) & 63, jb = (idx >> 7) & 3, kb2 = idx >> 9;
+         const int r = jb * 16 + (lane & 15), c = 4 * (2 * kb2 + e) + (lane >> 4);
+         a.d2P[slot * 4096 + idx] = r < n && c < n ? entry2(r, c) : 0.0;
+      }
+}
+
+// Matrix cores, the outer + derivative pass: a workgroup of four waves owns ANC_TILE patterns of one class, as anc_mfma_kernel (whose
+// down pass runs first): lane = q * 16 + pattern, register m = state 4 m + q.  Grid (stride / ANC_TILE, K); sP: 4096 doubles of LDS.
+// CURV: the d^2P product goes through the same x -> acc -> y as the dP product did, after its dot product is taken.
+template <bool CURV> __device__ __forceinline__ void grad_mfma_body(const GradArgs &a, double *sP)
+{
+   const AncMargArgs &m = a.m;
+   const AncTree &t = m.t;
+   const int tid = threadIdx.x, lane = tid & 63, n = m.n;
+   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+   const int q = lane >> 4, k = blockIdx.y;
+   const AncMfma w{sP, lane, wave, q};
+   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
+   const long pc = p < m.nb ? p : m.nb - 1;      // (lanes past the batch's end read the last pattern and write into the padding: p < stride)
+   const long pset = (long)m.gene * m.K + k;
+   const double *pi = m.pi + (long)(m.n_pi > 1 ? m.gene : 0) * n;
+   if (t.root >= t.n_tips) {
+      const int ri = t.root - t.n_tips;
+      double x[16];
+#pragma unroll
+      for (int i = 0; i < 16; i++) x[i] = 4 * i + q < n ? pi[4 * i + q] : 0.0;
+      part_store(m.G + (((long)k * t.n_int + ri) * (m.stride >> 4) + g16) * 1024, lane, x);
+      if (q == 0) m.SG[((long)k * t.n_int + ri) * m.stride + p] = 0;
+   }
+   const int n_walk = t.n_pre + t.n_tips;
+   for (int i = 0; i < n_walk; i++) {
+      const int v = i < t.n_pre ? t.pre[i] : i - t.n_pre;      // the internal nodes father first, then the tips
+      if (v == t.root) continue;
+      const int f = t.father[v];
+      double h[16], ls = 0;
+      __syncthreads();      // (SG of the father was stored by the pattern's q = 0 lane: a workgroup-scope fence before the other lanes read it)
+      if (f >= t.n_tips) {
+         const int fi = f - t.n_tips;
+         part_load(m.G + (((long)k * t.n_int + fi) * (m.stride >> 4) + g16) * 1024, lane, h);      // (this lane's own stores)
+         ls = m.SG[((long)k * t.n_int + fi) * m.stride + pc];
+      }
+      else {
+         const unsigned long long mask = m.code_mask[m.z[(long)f * m.z_stride + m.h0 + pc]];
+#pragma unroll
+         for (int j = 0; j < 16; j++) h[j] = (4 * j + q < n && ((mask >> (4 * j + q)) & 1ull)) ? pi[4 * j + q] : 0.0;
+      }
+      for (int j = t.sons_ptr[f]; j < t.sons_ptr[f + 1]; j++)
+         if (t.sons[j] != v) anc_mfma_mul_son(m, w, k, g16, pc, t.sons[j], h, &ls);
+      const long slot = pset * t.n_nodes + v;
+      const long oi = grad_out_idx(a, k, v, p);
+      double x[16], y[16];
+      v4d acc[4];
+      if (v < t.n_tips) {
+         const int code = (int)m.z[(long)v * m.z_stride + m.h0 + pc];
+         const unsigned long long mask = m.code_mask[code];
+#pragma unroll
+         for (int j = 0; j < 16; j++) x[j] = (mask >> (4 * j + q)) & 1ull ? 1.0 : 0.0;
+         w.product(a.dP + slot * 4096, x, acc);
+#pragma unroll
+         for (int j = 0; j < 16; j++) y[j] = acc[j >> 2][j & 3];
+         const double num = grad_mfma_dot(h, y);
+         if constexpr (CURV) {
+            w.product(a.d2P + slot * 4096, x, acc);
+#pragma unroll
+            for (int j = 0; j < 16; j++) y[j] = acc[j >> 2][j & 3];
+            const double cur = grad_mfma_dot(h, y);
+            if (q == 0) a.cur[oi] = cur;
+         }
+         double2 tv[8];
+         tip_gather(m.ptip + pset * t.n_nodes * m.tip_words, m.tip_words, v, code, q, tv);
+#pragma unroll
+         for (int j = 0; j < 8; j++) { y[2 * j] = tv[j].x; y[2 * j + 1] = tv[j].y; }
+         const double den = grad_mfma_dot(h, y);
+         if (q == 0) { a.num[oi] = num; a.den[oi] = den; a.sig[oi] = ls; }
+         continue;
+      }
+      const int vi = v - t.n_tips;
+      part_load(m.L + (((long)k * t.n_int + vi) * (m.stride >> 4) + g16) * 1024, lane, x);
+      w.product(a.dP + slot * 4096, x, acc);
+#pragma unroll
+      for (int j = 0; j < 16; j++) y[j] = acc[j >> 2][j & 3];
+      const double num = grad_mfma_dot(h, y);
+      if constexpr (CURV) {
+         w.product(a.d2P + slot * 4096, x, acc);
+#pragma unroll
+         for (int j = 0; j < 16; j++) y[j] = acc[j >> 2][j & 3];
+         const double cur = grad_mfma_dot(h, y);
+         if (q == 0) a.cur[oi] = cur;
+      }
+      w.product(a.PT + slot * 4096, h, acc);      // A_v = P_v^T H_v
+#pragma unroll
+      for (int j = 0; j < 16; j++) y[j] = acc[j >> 2][j & 3];
+      const double den = grad_mfma_dot(y, x);
+      if (q == 0) { a.num[oi] = num; a.den[oi] = den; a.sig[oi] = ls + m.SL[((long)k * t.n_int + vi) * m.stride + pc]; }
+      if (m.scaled) {
+         const double mx = anc_mfma_max(y);
+         if (mx > 0) {
+#pragma unroll
+            for (int j = 0; j < 16; j++) y[j] /= mx;
+            ls += log(mx);
+         }
+      }
+      part_store(m.G + (((long)k * t.n_int + vi) * (m.stride >> 4) + g16) * 1024, lane, y);
+      if (q == 0) m.SG[((long)k * t.n_int + vi) * m.stride + p] = ls;
+   }
+}
+
+// the classes of every (row, pattern) and the chunks' sums: grid (stride / 256, rows), rows = n_nodes + 1 (CURV: 2 n_nodes + 1); a wave =
+// one chunk of GRAD_CHUNK patterns
+template <bool CURV> __device__ __forceinline__ void grad_combine_body(const GradArgs &a)
+{
+   const long p = (long)blockIdx.x * 256 + threadIdx.x;
+   const int v = blockIdx.y;
+   double acc = p < a.m.nb ? grad_combine<CURV>(a, v, p) : 0.0;
+#pragma unroll
+   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+   const long chunk = a.chunk0 + (p >> 6);
+   if ((threadIdx.x & 63) == 0 && (p & ~63L) < a.m.nb) a.partial[(long)v * a.n_chunks + chunk] = acc;
 }
 
 #endif

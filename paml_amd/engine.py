@@ -39,6 +39,7 @@ EXPORTS = [
     "paml_amd_simulate", "paml_amd_simulate_info",
     "paml_amd_ancestral_marginal", "paml_amd_ancestral_joint", "paml_amd_ancestral_info",
     "paml_amd_gradient", "paml_amd_gradient_info",
+    "paml_amd_curvature", "paml_amd_curvature_info",
     "paml_amd_model_gradient", "paml_amd_model_gradient_info", "paml_amd_model_gradient_segment", "paml_amd_model_gradient_sizes",
     "paml_amd_nni_scores", "paml_amd_nni_info", "paml_amd_nni_list",
     "paml_amd_edge_scores", "paml_amd_edge_info", "paml_amd_edge_list",
@@ -58,7 +59,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_modelgrad", "engine_nni", "engine_place", "engine_spr", "engine_edge")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_curvature", "engine_modelgrad", "engine_nni", "engine_place", "engine_spr", "engine_edge")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -499,6 +500,19 @@ class Engine:
         self._L.paml_amd_gradient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]
         self._chk(self._L.paml_amd_gradient(self._h, _p(b), _p(g), C.byref(lnL), _p(grad), _p(lnf), _p(scores)))
         return dict(lnL=lnL.value, grad=grad, lnf=lnf, scores=scores)
+
+    def curvature(self, branch, gene_rate=None, want_lnf=False):
+        """lnL, its derivative and its second derivative along every branch length in one call (paml_amd_curvature): dict(lnL,
+        grad=[n_nodes], curv=[n_nodes] d^2 lnL / d branch[v]^2 (the root's entries 0), lnf=[n_patt] or None).  lnL, grad and lnf have
+        the bytes Engine.gradient returns."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        lnL = C.c_double()
+        grad, curv = np.zeros(self.n_nodes), np.zeros(self.n_nodes)
+        lnf = np.zeros(self.n_patt) if want_lnf else None
+        self._L.paml_amd_curvature.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self._L.paml_amd_curvature(self._h, _p(b), _p(g), C.byref(lnL), _p(grad), _p(curv), _p(lnf)))
+        return dict(lnL=lnL.value, grad=grad, curv=curv, lnf=lnf)
 
     def model_gradient(self, branch, gene_rate=None, want_pairs=False):
         """The derivative of lnL with respect to every input of the engine in one call (paml_amd_model_gradient): dict(lnL,
@@ -1062,6 +1076,17 @@ def gradient_info():
     L.paml_amd_gradient_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.paml_amd_gradient_info.restype = None
     L.paml_amd_gradient_info(C.byref(nb), C.byref(ms))
+    return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def curvature_info():
+    """Batches walked by this thread's last Engine.curvature and the time of its kernels by HIP events (paml_amd_curvature_info):
+    dict(last_batches, last_kernel_ms)."""
+    L = lib()
+    nb, ms = C.c_int(), C.c_double()
+    L.paml_amd_curvature_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.paml_amd_curvature_info.restype = None
+    L.paml_amd_curvature_info(C.byref(nb), C.byref(ms))
     return dict(last_batches=nb.value, last_kernel_ms=ms.value)
 
 

@@ -20,7 +20,7 @@ DRIVER_PATH = os.path.join(_HERE, "lib", "pamlh_lnl")
 def build(force=False):
     from . import engine
     engine.build()
-    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_place.c", "pamlh_spr.c", "pamlh_support.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
+    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_place.c", "pamlh_spr.c", "pamlh_support.c", "pamlh_newton.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "pamlh.h"))
     if force or not (os.path.exists(LIB_PATH) and os.path.exists(DRIVER_PATH)) or \
             any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
@@ -635,6 +635,56 @@ class Analysis:
         L.paml_amd_branch_counters.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]
         L.paml_amd_branch_counters(C.c_void_p(self._L.pamlh_engine_handle(self._h)), C.byref(a), C.byref(b))
         return dict(x=x, lnL=lnl.value, converged=rc == 0, n_eval=nev.value, branch_calls=a.value, nodes_recomputed=b.value)
+
+    def curvature(self, x):
+        """lnL at x and, over x's branch-length block (branch_order), the gradient and the curvature d2 lnL / d t2 along every branch
+        from one engine call (pamlh_curvature -> paml_amd_curvature): dict(lnL, grad=[ntime], curv=[ntime])."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        nt = self.ntime
+        lnl, g, h = C.c_double(), np.zeros(max(1, nt)), np.zeros(max(1, nt))
+        self._L.pamlh_curvature.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
+        if len(x) != self.np or self._L.pamlh_curvature(self._h, x.ctypes.data_as(C.c_void_p), C.byref(lnl), g.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_curvature: " + self._L.pamlh_error(self._h).decode())
+        return dict(lnL=lnl.value, grad=g[:nt], curv=h[:nt])
+
+    def newton_branches(self, x, e=1e-8, max_sweeps=50, verbose=0):
+        """Maximises lnL over x's branch-length block by Newton steps on every branch at once, one engine call per sweep, the rest of x
+        held (pamlh_newton_branches).  Returns dict(x, lnL, sweeps, calls, rejected)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).copy()
+        lnl, st = C.c_double(), (C.c_int * 3)()
+        self._L.pamlh_newton_branches.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p]
+        if len(x) != self.np or self._L.pamlh_newton_branches(self._h, x.ctypes.data_as(C.c_void_p), float(e), int(max_sweeps), C.byref(lnl), int(verbose), st) != 0:
+            raise RuntimeError("pamlh_newton_branches: " + self._L.pamlh_error(self._h).decode())
+        return dict(x=x, lnL=lnl.value, sweeps=st[0], calls=st[1], rejected=st[2])
+
+    def minbranches(self, x, e=1e-8, verbose=0):
+        """One run of the branch-at-a-time Newton cycles over x's branch-length block, the rest of x held (pamlh_minbranches, method = 1's
+        inner step).  Returns dict(x, lnL, branch_calls = the paml_amd_eval_branch calls it made)."""
+        from . import engine
+        x = np.ascontiguousarray(x, dtype=np.float64).copy()
+        lnl, a0, a1, b = C.c_double(), C.c_long(), C.c_long(), C.c_long()
+        self._L.pamlh_engine_handle.restype = C.c_void_p
+        self._L.pamlh_engine_handle.argtypes = [C.c_void_p]
+        L = engine.lib()
+        L.paml_amd_branch_counters.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+        self.eval_gpu(x, want_lnf=False)      # (the engine exists from here on)
+        L.paml_amd_branch_counters(C.c_void_p(self._L.pamlh_engine_handle(self._h)), C.byref(a0), C.byref(b))
+        self._L.pamlh_minbranches.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.c_int]
+        if len(x) != self.np or self._L.pamlh_minbranches(self._h, x.ctypes.data_as(C.c_void_p), float(e), C.byref(lnl), int(verbose)) != 0:
+            raise RuntimeError("pamlh_minbranches: " + self._L.pamlh_error(self._h).decode())
+        L.paml_amd_branch_counters(C.c_void_p(self._L.pamlh_engine_handle(self._h)), C.byref(a1), C.byref(b))
+        return dict(x=x, lnL=lnl.value, branch_calls=a1.value - a0.value)
+
+    def optimize_newton(self, x0, e0=1e-6, verbose=0):
+        """pamlh_optimize_newton: the alternation of optimize_minb with newton_branches in the place of the branch-at-a-time steps.
+        Returns dict(x, lnL, converged, n_eval)."""
+        x = np.ascontiguousarray(x0, dtype=np.float64).copy()
+        lnl, nev = C.c_double(), C.c_int()
+        self._L.pamlh_optimize_newton.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(C.c_int)]
+        rc = -1 if len(x) != self.np else self._L.pamlh_optimize_newton(self._h, x.ctypes.data_as(C.c_void_p), C.byref(lnl), float(e0), int(verbose), C.byref(nev))
+        if rc < 0:
+            raise RuntimeError("pamlh_optimize_newton: " + self._L.pamlh_error(self._h).decode())
+        return dict(x=x, lnL=lnl.value, converged=rc == 0, n_eval=nev.value)
 
     def lnpd_locus(self, age, rgene=1.0, rate=None, model_changed=True):
         """mcmctree's lnpD_locus on the GPU (pamlh_lnpd_locus): lnL for node ages age[n_nodes] and a locus rate / branch rates."""
