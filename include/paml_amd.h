@@ -554,6 +554,29 @@ int paml_amd_curvature(paml_amd_engine *e, const double *branch, const double *g
 /* The number of batches the calling thread's last paml_amd_curvature walked and the time of its kernels by HIP events (ms). */
 void paml_amd_curvature_info(int *last_batches, double *last_kernel_ms);
 
+/* ---- lnL, its gradient and its HESSIAN over all branch lengths in one call (the definition and the kernels are written out in
+ * csrc/kernels_hessian.h, the lists of steps in csrc/hessian_plan.h).  hess[u][v] = d^2 lnL / d branch[u] d branch[v] of exactly the
+ * number paml_amd_eval returns, for any rooting and any mix of eigen systems.  Per source branch u, D_u = dP_u L_u is carried up the path
+ * to the root (L'_a, giving the pairs with u's ancestors as H_a . dP_a L'_a) and outwards through modified outer messages (H'_w, giving
+ * the unrelated pairs as H'_w . dP_w L_w); with m_uvk these sums,  hess[u][v] = sum_h w_h (sum_k freqK_k m_uvk / f_h - s_u(h) s_v(h)).
+ * Every unordered pair is computed once (the lower node of an ancestor pair, else the smaller node number, is the source) and mirrored,
+ * so hess is exactly symmetric; the diagonal has the bytes of paml_amd_curvature's curv, *lnL, grad[] and lnf[] those of
+ * paml_amd_gradient; the root's row and column are 0; a pattern of weight 0 contributes nothing.
+ * nodes = NULL, n_list = 0: every node, hess is [n_nodes][n_nodes].  Otherwise hess is [n_list][n_list] in the order of the list, and
+ * an entry has the same bytes whatever else is listed.  Takes what paml_amd_curvature takes and leaves the engine as it does; the
+ * workspace is 256 MiB or PAML_AMD_HESS_ARENA_MB (read at every call), and every result has the same bytes whatever the batches and
+ * the groups of sources, and on every call.  PAML_AMD_EINVAL for a null branch, lnL, grad or hess, a model or tips not set, an entry of
+ * nodes that is out of range, the root or repeated; PAML_AMD_EUNSUPPORTED for a rate-matrix (UNREST) set, more than 64 states, an
+ * engine whose communicator has more than one rank.  Every message starts with "hessian:". */
+int paml_amd_hessian(paml_amd_engine *e, const double *branch, const double *gene_rate,
+                     const int *nodes, int n_list,
+                     double *lnL,
+                     double *grad /* [n_nodes] */,
+                     double *hess /* [n_nodes][n_nodes], or [n_list][n_list] */,
+                     double *lnf  /* [n_patt], or NULL */);
+/* The number of batches the calling thread's last paml_amd_hessian walked and the time of its kernels by HIP events (ms). */
+void paml_amd_hessian_info(int *last_batches, double *last_kernel_ms);
+
 /* ---- The derivative of lnL with respect to every INPUT of the engine in one call: what a chain rule on the host needs to give
  * d lnL / d (any model parameter) without an evaluation or a decomposition per parameter (the definition and the kernels are written out
  * in csrc/kernels_modelgrad.h).  lnL is the number paml_amd_gradient returns at (branch, gene_rate), a function of

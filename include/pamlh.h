@@ -280,6 +280,25 @@ int pamlh_curvature(pamlh *p, const double *x, double *lnL, double *g, double *h
 int pamlh_newton_branches(pamlh *p, double *x, double e, int max_sweeps, double *lnL, int verbose, int *stats);
 int pamlh_optimize_newton(pamlh *p, double *x, double *lnL, double e0, int verbose, int *n_eval);
 
+/* ---- The exact Hessian of lnL over the branch lengths on the host (pamlh_hessian.c), from the engine call that returns lnL, the gradient
+ * and every second derivative d2 lnL / d t_i d t_j (paml_amd_hessian).  Everything here is opt-in; pamlh_branch_hessian, pamlh_write_bv,
+ * pamlh_standard_errors, pamlh_newton_branches and the optimisers are as they were.
+ * pamlh_branch_hessian_exact: lnL at x, g[ntime] and H[ntime][ntime] over x's branch-length block (pamlh_branch_order); one engine call.
+ *   Where pamlh_branch_hessian returns minus the outer product of the scores (an estimate of the information), this is the Hessian itself.
+ * pamlh_write_bv_exact: the block pamlh_write_bv writes for mcmctree's in.BV, with this Hessian.
+ * pamlh_standard_errors_exact: the observed information over all free parameters — branch x branch from the call, branch x model
+ *   parameter from central differences of the branch gradient (two gradient calls per model parameter), model x model from
+ *   pamlh_standard_errors method 1's stencil restricted to the model parameters — inverted as a whole; the parameters method 1 leaves
+ *   out at a bound are left out and get se = -1.  hess (may be NULL): the information matrix, np x np.
+ * pamlh_newton_full: pamlh_newton_branches with the step from the whole block, (-H + lambda I) d = g by Cholesky on the branches that
+ *   can move, lambda raised from 0 until the factorisation succeeds; the same trust factors, clipping, accept / reject rule, ending and
+ *   stats.  One engine call per sweep; lnL never decreases.
+ * Refused by name, as pamlh_curvature refuses them: a clock, fix_blength = 2 / 3, rho != 0, a rate-matrix (UNREST) model, a pattern shard. */
+int pamlh_branch_hessian_exact(pamlh *p, const double *x, double *lnL, double *g, double *H);
+int pamlh_write_bv_exact(pamlh *p, const double *x, const char *path);
+int pamlh_standard_errors_exact(pamlh *p, const double *x, double *se, double *hess);
+int pamlh_newton_full(pamlh *p, double *x, double e, int max_sweeps, double *lnL, int verbose, int *stats);
+
 /* Standard errors of the estimates (getSE = 1).  method 0: HessianSKT2004 (treesub.c:7241), the outer product of per-pattern
  * scores that the reference's programs print; method 1: observed information from central second differences of lnL
  * (Hessian() tools.c:5984).  Either way all perturbed evaluations are one batch.  se[np] (-1: not available, e.g. a parameter

@@ -19,15 +19,6 @@ __global__ __launch_bounds__(256) void curv_pmat_kernel(GradPmatArgs a)
    grad_pmat_body<true>(a, sE, sM);
 }
 
-// one pattern per lane: grid (patterns / 256, K); pass 0: the down pass, 1: the outer pass with both derivatives
-template <int N> __global__ __launch_bounds__(256) void curv_lane_kernel(GradArgs a, int pass)
-{
-   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-   if (p >= a.m.nb) return;
-   if (pass) grad_lane_outer<N, true>(a, blockIdx.y, p);
-   else anc_lane_down<N>(a.m, blockIdx.y, p);
-}
-
 // matrix cores: grid (stride / ANC_TILE, K), after anc_mfma_kernel's down pass
 __global__ __launch_bounds__(256) void curv_mfma_kernel(GradArgs a)
 {

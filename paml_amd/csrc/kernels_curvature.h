@@ -41,6 +41,15 @@ inline double curv_bytes_per_pattern(int K, int n_int, int n_nodes, int n_s) { r
 __global__ void curv_pmat_kernel(GradPmatArgs a);
 __global__ void curv_mfma_kernel(GradArgs a);
 __global__ void curv_combine_kernel(GradArgs a);
+
+// one pattern per lane: grid (patterns / 256, K); pass 0: the down pass, 1: the outer pass with both derivatives (the Hessian call launches it too)
+template <int N> __global__ __launch_bounds__(256) void curv_lane_kernel(GradArgs a, int pass)
+{
+   const long p = (long)blockIdx.x * 256 + threadIdx.x;
+   if (p >= a.m.nb) return;
+   if (pass) grad_lane_outer<N, true>(a, blockIdx.y, p);
+   else anc_lane_down<N>(a.m, blockIdx.y, p);
+}
 #endif
 
 }  // namespace paml_amd

@@ -40,6 +40,7 @@ EXPORTS = [
     "paml_amd_ancestral_marginal", "paml_amd_ancestral_joint", "paml_amd_ancestral_info",
     "paml_amd_gradient", "paml_amd_gradient_info",
     "paml_amd_curvature", "paml_amd_curvature_info",
+    "paml_amd_hessian", "paml_amd_hessian_info",
     "paml_amd_model_gradient", "paml_amd_model_gradient_info", "paml_amd_model_gradient_segment", "paml_amd_model_gradient_sizes",
     "paml_amd_nni_scores", "paml_amd_nni_info", "paml_amd_nni_list",
     "paml_amd_edge_scores", "paml_amd_edge_info", "paml_amd_edge_list",
@@ -59,7 +60,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_curvature", "engine_modelgrad", "engine_nni", "engine_place", "engine_spr", "engine_edge")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_curvature", "engine_hessian", "engine_modelgrad", "engine_nni", "engine_place", "engine_spr", "engine_edge")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -513,6 +514,22 @@ class Engine:
         self._L.paml_amd_curvature.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]
         self._chk(self._L.paml_amd_curvature(self._h, _p(b), _p(g), C.byref(lnL), _p(grad), _p(curv), _p(lnf)))
         return dict(lnL=lnL.value, grad=grad, curv=curv, lnf=lnf)
+
+    def hessian(self, branch, gene_rate=None, nodes=None, want_lnf=False):
+        """lnL, its gradient and its Hessian over all branch lengths in one call (paml_amd_hessian): dict(lnL, grad=[n_nodes],
+        hess=[n_nodes][n_nodes] d^2 lnL / d branch[u] d branch[v] (the root's row and column 0) or, with a list of `nodes`,
+        [len(nodes)][len(nodes)] in the list's order, lnf=[n_patt] or None).  lnL, grad and lnf have the bytes Engine.gradient returns,
+        the diagonal those of Engine.curvature's curv; hess equals its transpose."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        nl = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32)
+        dim = self.n_nodes if nl is None else len(nl)
+        lnL = C.c_double()
+        grad, hess = np.zeros(self.n_nodes), np.zeros((dim, dim))
+        lnf = np.zeros(self.n_patt) if want_lnf else None
+        self._L.paml_amd_hessian.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self._L.paml_amd_hessian(self._h, _p(b), _p(g), _p(nl), 0 if nl is None else len(nl), C.byref(lnL), _p(grad), _p(hess), _p(lnf)))
+        return dict(lnL=lnL.value, grad=grad, hess=hess, lnf=lnf)
 
     def model_gradient(self, branch, gene_rate=None, want_pairs=False):
         """The derivative of lnL with respect to every input of the engine in one call (paml_amd_model_gradient): dict(lnL,
@@ -1087,6 +1104,17 @@ def curvature_info():
     L.paml_amd_curvature_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.paml_amd_curvature_info.restype = None
     L.paml_amd_curvature_info(C.byref(nb), C.byref(ms))
+    return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def hessian_info():
+    """Batches walked by this thread's last Engine.hessian and the time of its kernels by HIP events (paml_amd_hessian_info):
+    dict(last_batches, last_kernel_ms)."""
+    L = lib()
+    nb, ms = C.c_int(), C.c_double()
+    L.paml_amd_hessian_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.paml_amd_hessian_info.restype = None
+    L.paml_amd_hessian_info(C.byref(nb), C.byref(ms))
     return dict(last_batches=nb.value, last_kernel_ms=ms.value)
 
 

@@ -1,5 +1,5 @@
 /* pamlh_lnl — command-line driver: one likelihood evaluation of a codeml/baseml analysis on the MI355X.
- *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient | --analytic-gradient-all | --newton-branches]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
+ *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient | --analytic-gradient-all | --newton-branches] [--newton-full]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE [--exact-hessian]] [--se-exact] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
  *   (--set "key = value": replaces an option of the control file, e.g. one of the site models of an "NSsites = 0 1 2 7 8" list;
  *    --tree K: the K-th tree of the tree file, 1-based; --all-trees: every tree in turn — the reference's loop, Forestry codeml.c:635 —
  *    each optimised from the control file's initial values, then the comparison table of rell(), treesub.c:5844;
@@ -136,7 +136,7 @@ int main(int argc, char **argv)
    pamlh *p;
    char err[512];
    double x[4096], lnL, *lnf;
-   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0, spr_scores = 0, spr_search = 0, radius = 0, top = 0, place = 0, n_pend = 4, supports = 0, newton = 0;
+   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0, spr_scores = 0, spr_search = 0, radius = 0, top = 0, place = 0, n_pend = 4, supports = 0, newton = 0, newton_full = 0, exact_hessian = 0, se_exact = 0;
    double pend[64] = {0.05, 0.1, 0.2, 0.4}, split = 0.5;
    char over[2048] = "";
    const char *sim_out = NULL, *bv_out = NULL;
@@ -145,12 +145,15 @@ int main(int argc, char **argv)
    unsigned char comm_id[PAML_AMD_COMM_ID_BYTES];
    int device[MAX_RANKS];
    for (i = 0; i < MAX_RANKS; i++) device[i] = i;
-   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient | --analytic-gradient-all | --newton-branches]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
+   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient | --analytic-gradient-all | --newton-branches] [--newton-full]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
    for (i = 3; i < argc && nx < 4096; i++) {
       if (!strcmp(argv[i], "--optimize")) optimize = 1;
       else if (!strcmp(argv[i], "--analytic-gradient-all")) analytic = 2;  /* with --optimize: every parameter's derivative from one engine call per gradient */
       else if (!strcmp(argv[i], "--analytic-gradient")) analytic = 1;      /* with --optimize: the branch lengths' derivatives from one engine call per gradient */
       else if (!strcmp(argv[i], "--newton-branches")) newton = 1;          /* with --optimize: the branch lengths by Newton steps on every branch at once, one engine call per sweep (pamlh_optimize_newton); prints the sweeps */
+      else if (!strcmp(argv[i], "--newton-full")) newton_full = 1;         /* with --optimize: first the branch lengths by Newton steps from the whole Hessian block, one engine call per sweep (pamlh_newton_full), the other parameters held; prints the sweeps; then the optimiser chosen */
+      else if (!strcmp(argv[i], "--exact-hessian")) exact_hessian = 1;     /* with --bv: the Hessian itself from one engine call (pamlh_write_bv_exact), not the outer product of scores */
+      else if (!strcmp(argv[i], "--se-exact")) se_exact = 1;               /* standard errors from the observed information with the exact branch block (pamlh_standard_errors_exact) */
       else if (!strcmp(argv[i], "--nni-scores")) nni_scores = 1;
       else if (!strcmp(argv[i], "--branch-supports")) supports = 1;      /* SH-like aLRT supports of the internal branches (N replicates, default 1000; --seed S) */
       else if (!strcmp(argv[i], "--nni-search")) nni_search = 1;
@@ -404,7 +407,13 @@ int main(int argc, char **argv)
    if (optimize) {
       /* method = 1 in the control file: minB / minbranches (one branch at a time on the branch-local derivatives) */
       const int method1 = pamlh_method(p) == 1;
-      int n_eval = 0, rc = newton    ? pamlh_optimize_newton(p, x, &lnL, 1e-6, 2, &n_eval)
+      int n_eval = 0, rc;
+      if (newton_full) {
+         int st[3] = {0, 0, 0};
+         if (pamlh_newton_full(p, x, 1e-8, 50, &lnL, 1, st)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+         printf("newton-full: lnL %.6f after %d sweeps (%d engine calls, %d rejected)\n", lnL, st[0], st[1], st[2]);
+      }
+      rc = newton    ? pamlh_optimize_newton(p, x, &lnL, 1e-6, 2, &n_eval)
                            : method1 ? pamlh_optimize_minb(p, x, &lnL, 1e-6, 1, &n_eval)
                                      : pamlh_optimize(p, x, &lnL, 500, 1e-10, 1, &n_eval);
       if (rc < 0) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
@@ -432,8 +441,17 @@ int main(int argc, char **argv)
    }
    if (bv_out) {      /* at the vector evaluated or just estimated */
       if (gpus > 0) { fprintf(stderr, "error: --bv runs on one GPU\n"); return 1; }
-      if (pamlh_write_bv(p, x, bv_out)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      if (exact_hessian ? pamlh_write_bv_exact(p, x, bv_out) : pamlh_write_bv(p, x, bv_out)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
       printf("gradient and Hessian of the %d branch lengths -> %s\n", ntime, bv_out);
+   }
+   if (se_exact) {      /* at the vector evaluated or just estimated */
+      double *se = (double *)malloc((np + 1) * sizeof(double));
+      if (gpus > 0) { fprintf(stderr, "error: --se-exact runs on one GPU\n"); return 1; }
+      if (pamlh_standard_errors_exact(p, x, se, NULL)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      printf("SEs for parameters (observed information, exact branch block):\n ");
+      for (i = 0; i < np; i++) printf(" %.6f", se[i]);
+      printf("\n");
+      free(se);
    }
    if (sim_out) {      /* the data sets of a parametric bootstrap instead of the evaluation */
       int ns = 0, n_pose = 0, r;

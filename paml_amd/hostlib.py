@@ -20,7 +20,7 @@ DRIVER_PATH = os.path.join(_HERE, "lib", "pamlh_lnl")
 def build(force=False):
     from . import engine
     engine.build()
-    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_place.c", "pamlh_spr.c", "pamlh_support.c", "pamlh_newton.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
+    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_place.c", "pamlh_spr.c", "pamlh_support.c", "pamlh_newton.c", "pamlh_hessian.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "pamlh.h"))
     if force or not (os.path.exists(LIB_PATH) and os.path.exists(DRIVER_PATH)) or \
             any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
@@ -685,6 +685,47 @@ class Analysis:
         if rc < 0:
             raise RuntimeError("pamlh_optimize_newton: " + self._L.pamlh_error(self._h).decode())
         return dict(x=x, lnL=lnl.value, converged=rc == 0, n_eval=nev.value)
+
+    def branch_hessian_exact(self, x):
+        """lnL at x, the gradient and the Hessian d2 lnL / d t_i d t_j over x's branch-length block (branch_order) from one engine call
+        (pamlh_branch_hessian_exact -> paml_amd_hessian): dict(lnL, grad=[ntime], H=[ntime][ntime])."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        nt = self.ntime
+        lnl, g, H = C.c_double(), np.zeros(max(1, nt)), np.zeros((max(1, nt), max(1, nt)))
+        self._L.pamlh_branch_hessian_exact.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
+        if len(x) != self.np or self._L.pamlh_branch_hessian_exact(self._h, x.ctypes.data_as(C.c_void_p), C.byref(lnl), g.ctypes.data_as(C.c_void_p),
+                                                                   H.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_branch_hessian_exact: " + self._L.pamlh_error(self._h).decode())
+        return dict(lnL=lnl.value, grad=g[:nt], H=H.reshape(-1)[:nt * nt].reshape(nt, nt))
+
+    def write_bv_exact(self, x, path):
+        """write_bv's block with the exact Hessian of branch_hessian_exact (pamlh_write_bv_exact)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        self._L.pamlh_write_bv_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
+        if len(x) != self.np or self._L.pamlh_write_bv_exact(self._h, x.ctypes.data_as(C.c_void_p), os.fsencode(str(path))) != 0:
+            raise RuntimeError("pamlh_write_bv_exact: " + self._L.pamlh_error(self._h).decode())
+
+    def standard_errors_exact(self, x):
+        """Standard errors from the observed information over all free parameters (pamlh_standard_errors_exact): branch x branch from one
+        engine call, branch x model parameter from differences of the branch gradient, model x model from method 1's stencil.
+        Returns dict(se=[np] (-1: left out at a bound), hess=[np][np] the information matrix)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        n = self.np
+        se, H = np.zeros(max(1, n)), np.zeros((max(1, n), max(1, n)))
+        self._L.pamlh_standard_errors_exact.argtypes = [C.c_void_p] * 4
+        if len(x) != n or self._L.pamlh_standard_errors_exact(self._h, x.ctypes.data_as(C.c_void_p), se.ctypes.data_as(C.c_void_p), H.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_standard_errors_exact: " + self._L.pamlh_error(self._h).decode())
+        return dict(se=se[:n], hess=H.reshape(-1)[:n * n].reshape(n, n))
+
+    def newton_full(self, x, e=1e-8, max_sweeps=50, verbose=0):
+        """newton_branches with the step from the whole Hessian block, one engine call per sweep (pamlh_newton_full).  Returns dict(x, lnL,
+        sweeps, calls, rejected)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).copy()
+        lnl, st = C.c_double(), (C.c_int * 3)()
+        self._L.pamlh_newton_full.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p]
+        if len(x) != self.np or self._L.pamlh_newton_full(self._h, x.ctypes.data_as(C.c_void_p), float(e), int(max_sweeps), C.byref(lnl), int(verbose), st) != 0:
+            raise RuntimeError("pamlh_newton_full: " + self._L.pamlh_error(self._h).decode())
+        return dict(x=x, lnL=lnl.value, sweeps=st[0], calls=st[1], rejected=st[2])
 
     def lnpd_locus(self, age, rgene=1.0, rate=None, model_changed=True):
         """mcmctree's lnpD_locus on the GPU (pamlh_lnpd_locus): lnL for node ages age[n_nodes] and a locus rate / branch rates."""
