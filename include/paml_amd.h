@@ -607,6 +607,30 @@ void paml_amd_model_gradient_info(int *last_batches, double *last_kernel_ms);
 int paml_amd_model_gradient_segment(void);
 int paml_amd_model_gradient_sizes(paml_amd_engine *e, int *n_pi, int *n_eigen);
 
+/* ---- Posterior expected numbers of labelled substitutions and expected dwell times, per branch and per pattern, in one call (the
+ * definition and the kernels are written out in csrc/kernels_counts.h).  A label l is an n x n matrix of real weights M_l: off the
+ * diagonal M_l[a][b] weights every jump a -> b, on it M_l[a][a] rewards the time spent in a, in units of branch[v].  With A and tau of
+ * the branch above v as in paml_amd_model_gradient, B_l = A o M_l off the diagonal and (B_l)_aa = M_l[a][a] branch[v] / tau,
+ *   n_lv(h) = E[ labelled jumps + rewards on the branch above v | pattern h ]
+ *           = sum_k rho_k H_v^T (int_0^tau e^{Au} B_l e^{A(tau-u)} du) L_v / sum_k rho_k f_vk      (the classes by their posterior)
+ * counts[l][i] = sum_h w_h n_lv(h), site_counts[l][i][h] = n_lv(h) (0 where w_h = 0), v = nodes[i].  nodes == NULL: every node in node
+ * order, n_query is not read, the arrays have n_nodes columns and the root's are 0.  The identity as a label returns branch[v] at every
+ * pattern; the all-ones off-diagonal label the expected number of substitutions.  Nothing is re-rooted and no reversibility is assumed.
+ * *lnL has the bytes paml_amd_model_gradient returns on the same engine and inputs, whose passes these are; lnf[] is those passes' ln f_h.
+ * Takes what paml_amd_gradient takes and leaves the engine as it does; the workspace is 256 MiB or PAML_AMD_COUNTS_ARENA_MB (read at
+ * every call).  Every result has the same bytes whatever the batches, for any sub-list or order of the labels and of the nodes, and on
+ * every call (no atomics).  PAML_AMD_EINVAL for a null branch, labels, lnL or counts, a model or tips not set, n_lab outside
+ * 1 .. 16, a label entry that is not finite, a queried node that is the root, out of range or listed
+ * twice; PAML_AMD_EUNSUPPORTED for a rate-matrix (UNREST) set, more than 64 states, an engine whose communicator has more than one rank. */
+int paml_amd_subst_counts(paml_amd_engine *e, const double *branch, const double *gene_rate,
+                          int n_lab, const double *labels /* [n_lab][n][n] */,
+                          int n_query, const int *nodes   /* non-root nodes; NULL = all, node order */,
+                          double *lnL, double *counts     /* [n_lab][n_query] */,
+                          double *site_counts             /* [n_lab][n_query][n_patt], or NULL */,
+                          double *lnf                     /* [n_patt], or NULL */);
+/* The number of batches the calling thread's last paml_amd_subst_counts walked and the time of its kernels by HIP events (ms). */
+void paml_amd_subst_counts_info(int *last_batches, double *last_kernel_ms);
+
 /* ---- The lnL of every nearest-neighbour-interchange (NNI) neighbour of the tree at the present branch lengths, in one call (the trees
  * the reference's search, Perturbation treesub.c:4642 on NeighborNNI treespace.c:283, takes one after the other; the definition and the
  * kernels are written out in csrc/kernels_nni.h).  A swap is (v, s, x): v an internal node that is not the root, s a son of v, x a son

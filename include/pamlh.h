@@ -299,6 +299,21 @@ int pamlh_write_bv_exact(pamlh *p, const double *x, const char *path);
 int pamlh_standard_errors_exact(pamlh *p, const double *x, double *se, double *hess);
 int pamlh_newton_full(pamlh *p, double *x, double e, int max_sweeps, double *lnL, int verbose, int *stats);
 
+/* ---- Posterior expected numbers of labelled substitutions per branch and per site (pamlh_counts.c), from the engine call that returns
+ * them for every branch and pattern at once (paml_amd_subst_counts): multiple hits and the uncertainty of the ancestral states are
+ * integrated over, where the "changes along branches" of a reconstruction counts the differences between two reconstructed sequences.
+ * A label is an n x n matrix of weights: off the diagonal of the jumps a -> b, on it of the time spent in a (in units of the branch length).
+ * pamlh_count_labels: the labels that go with the analysis's data type.  kind NULL or "standard": codons "synonymous", "nonsynonymous"
+ *   by the analysis's genetic code; nucleotides "transitions", "transversions"; amino acids "changes".  kind "total": every jump;
+ *   kind "dwell": the identity, whose count is the branch length.  *n_lab: how many; M (may be NULL): room for [*n_lab][n][n], two
+ *   at most; names (may be NULL): room for *n_lab names of 32 characters.
+ * pamlh_subst_counts: counts[n_lab][ntime] at x over x's branch-length block (pamlh_branch_order), summed over the alignment's sites;
+ *   site_counts (may be NULL): [n_lab][ntime][sites] per site of the alignment (pamlh_pose: the patterns' values expanded).  One engine
+ *   call; the state is left at x.
+ * Refused by name, as pamlh_curvature refuses them: a clock, fix_blength = 2 / 3, rho != 0, a rate-matrix (UNREST) model, a pattern shard. */
+int pamlh_count_labels(pamlh *p, const char *kind, int *n_lab, double *M, char (*names)[32]);
+int pamlh_subst_counts(pamlh *p, const double *x, int n_lab, const double *M, double *counts, double *site_counts);
+
 /* Standard errors of the estimates (getSE = 1).  method 0: HessianSKT2004 (treesub.c:7241), the outer product of per-pattern
  * scores that the reference's programs print; method 1: observed information from central second differences of lnL
  * (Hessian() tools.c:5984).  Either way all perturbed evaluations are one batch.  se[np] (-1: not available, e.g. a parameter

@@ -244,25 +244,6 @@ __global__ __launch_bounds__(256) void mg_add_kernel(double *W, const double *Wp
    W[i] = s;
 }
 
-// the spectral projector r of a CIJK / K80 / JC69-like set and its eigenvalue
-__device__ __forceinline__ double mg_proj(const EigenDev &es, int n, int r, int i, int j)
-{
-   if (es.kind == PAML_AMD_EIGEN_CIJK) return es.Cijk[((long)i * n + j) * es.nR + r];
-   if (es.kind == PAML_AMD_EIGEN_K80) {
-      if (r == 0) return 0.25;
-      if (r == 1) return (i == j || (i ^ j) == 1) ? 0.25 : -0.25;
-      return i == j ? 0.5 : ((i ^ j) == 1 ? -0.5 : 0.0);
-   }
-   return r == 0 ? 1.0 / n : (i == j ? 1 - 1.0 / n : -1.0 / n);
-}
-__device__ __forceinline__ double mg_lambda(const EigenDev &es, int n, int r)
-{
-   if (es.kind == PAML_AMD_EIGEN_CIJK || es.kind == PAML_AMD_EIGEN_UVROOT) return es.Root[r];
-   if (r == 0) return 0.0;
-   if (es.kind == PAML_AMD_EIGEN_K80) return r == 1 ? -4 / (es.kappa + 2) : -2 * (es.kappa + 1) / (es.kappa + 2);
-   return -(double)n / (n - 1);
-}
-
 __device__ __forceinline__ double mg_block_sum(double s, double *sw4)
 {
 #pragma unroll

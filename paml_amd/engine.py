@@ -42,6 +42,7 @@ EXPORTS = [
     "paml_amd_curvature", "paml_amd_curvature_info",
     "paml_amd_hessian", "paml_amd_hessian_info",
     "paml_amd_model_gradient", "paml_amd_model_gradient_info", "paml_amd_model_gradient_segment", "paml_amd_model_gradient_sizes",
+    "paml_amd_subst_counts", "paml_amd_subst_counts_info",
     "paml_amd_nni_scores", "paml_amd_nni_info", "paml_amd_nni_list",
     "paml_amd_edge_scores", "paml_amd_edge_info", "paml_amd_edge_list",
     "paml_amd_placement_scores", "paml_amd_placement_info",
@@ -60,7 +61,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_curvature", "engine_hessian", "engine_modelgrad", "engine_nni", "engine_place", "engine_spr", "engine_edge")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_curvature", "engine_hessian", "engine_modelgrad", "engine_counts", "engine_nni", "engine_place", "engine_spr", "engine_edge")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -550,6 +551,31 @@ class Engine:
         self._L.paml_amd_model_gradient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)] + [C.c_void_p] * 5
         self._chk(self._L.paml_amd_model_gradient(self._h, _p(b), _p(g), C.byref(lnL), _p(g_eff), _p(g_freqK), _p(g_pi), _p(g_A), _p(W)))
         return dict(lnL=lnL.value, g_eff=g_eff, g_freqK=g_freqK, g_pi=g_pi, g_A=g_A, W=W)
+
+    def subst_counts(self, branch, gene_rate=None, labels=None, nodes=None, want_sites=False, want_lnf=False):
+        """Posterior expected labelled substitution counts and dwell times on every branch in one call (paml_amd_subst_counts):
+        dict(lnL, counts=[n_lab][n_nodes] (the root's entries 0) or, with a list of non-root `nodes`, [n_lab][len(nodes)] in the list's
+        order, site_counts=the same with a last axis [n_patt] or None, lnf=[n_patt] or None).  labels: [n_lab][n][n] weights, off the
+        diagonal of the jumps a -> b, on it of the time spent in a (in units of branch[v])."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        if labels is None:
+            raise EngineError("subst_counts: no labels")
+        M = np.ascontiguousarray(labels, dtype=np.float64)
+        if M.ndim == 2:
+            M = M[None]
+        if M.ndim != 3 or M.shape[1:] != (self.n, self.n):
+            raise EngineError("subst_counts: labels must be [n_lab][%d][%d]" % (self.n, self.n))
+        nd = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32)
+        nq = self.n_nodes if nd is None else len(nd)
+        lnL = C.c_double()
+        counts = np.zeros((len(M), nq))
+        sites = np.zeros((len(M), nq, self.n_patt)) if want_sites else None
+        lnf = np.zeros(self.n_patt) if want_lnf else None
+        self._L.paml_amd_subst_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double),
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self._L.paml_amd_subst_counts(self._h, _p(b), _p(g), len(M), _p(M), 0 if nd is None else len(nd), _p(nd), C.byref(lnL), _p(counts), _p(sites), _p(lnf)))
+        return dict(lnL=lnL.value, counts=counts, site_counts=sites, lnf=lnf)
 
     def nni_scores(self, branch, gene_rate=None, swaps=None, want_lnf=False):
         """The lnL of nearest-neighbour-interchange neighbours of the tree at `branch` in one call (paml_amd_nni_scores): dict(lnL0 (the
@@ -1116,6 +1142,23 @@ def hessian_info():
     L.paml_amd_hessian_info.restype = None
     L.paml_amd_hessian_info(C.byref(nb), C.byref(ms))
     return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def subst_counts_info():
+    """Batches walked by this thread's last Engine.subst_counts and the time of its kernels by HIP events (paml_amd_subst_counts_info):
+    dict(last_batches, last_kernel_ms)."""
+    L = lib()
+    nb, ms = C.c_int(), C.c_double()
+    L.paml_amd_subst_counts_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.paml_amd_subst_counts_info.restype = None
+    L.paml_amd_subst_counts_info(C.byref(nb), C.byref(ms))
+    return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def counts_bytes_per_pattern(K, n_int, n_nodes, ns, n_lab, n_query):
+    """Bytes of batch workspace paml_amd_subst_counts takes per pattern (counts_bytes_per_pattern, csrc/kernels_counts.h); ns: the states
+    of a stored partial, 64 on the matrix cores."""
+    return 8.0 * (2.0 * K * n_int * (ns + 1) + K * n_nodes * ns + 2.0 * K * n_nodes + K * (ns + 2) + (2.0 + K) + n_lab * n_query)
 
 
 def model_gradient_info():

@@ -1,5 +1,5 @@
 /* pamlh_lnl — command-line driver: one likelihood evaluation of a codeml/baseml analysis on the MI355X.
- *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient | --analytic-gradient-all | --newton-branches] [--newton-full]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE [--exact-hessian]] [--se-exact] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
+ *   usage: pamlh_lnl <codeml|baseml> <file.ctl> [--optimize [--analytic-gradient | --analytic-gradient-all | --newton-branches] [--newton-full]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE [--exact-hessian]] [--se-exact] [--subst-counts [--per-site]] [--ancestral | --ancestral-all] [--gpus N [--devices a,b,...]] [--tree K] [x0 x1 ...]
  *   (--set "key = value": replaces an option of the control file, e.g. one of the site models of an "NSsites = 0 1 2 7 8" list;
  *    --tree K: the K-th tree of the tree file, 1-based; --all-trees: every tree in turn — the reference's loop, Forestry codeml.c:635 —
  *    each optimised from the control file's initial values, then the comparison table of rell(), treesub.c:5844;
@@ -28,6 +28,10 @@
  *    0.2, 0.4), the lnL of the tree with the query hung there at PHI (default 0.5) of the branch above the node, the difference to the
  *    tree's own lnL, the likelihood weight ratio — from one engine call, then the best placement's tree.  The parameter vector is the
  *    one the driver would evaluate, or the estimates after --optimize on the tree's sequences)
+ *    --subst-counts [--per-site]: after the evaluation (or the estimates of --optimize), the posterior expected numbers of substitutions
+ *    on every branch from one engine call (pamlh_subst_counts): one row per branch — father..node, t, then a column per label of the
+ *    data type (codons: synonymous, nonsynonymous; nucleotides: transitions, transversions; amino acids: changes) and the total;
+ *    --per-site adds, per label, the table site x branch
  * Reads the control file, the sequence and tree files it names, and the parameter vector from the command line,
  * else from in.codeml / in.baseml beside the ctl (the reference's "-1 x..." single-evaluation recipe, treesub.c:4057),
  * else the ctl's initial values; evaluates lnL through libpaml_amd.so; prints `lnL = ...` like the reference and
@@ -136,7 +140,7 @@ int main(int argc, char **argv)
    pamlh *p;
    char err[512];
    double x[4096], lnL, *lnf;
-   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0, spr_scores = 0, spr_search = 0, radius = 0, top = 0, place = 0, n_pend = 4, supports = 0, newton = 0, newton_full = 0, exact_hessian = 0, se_exact = 0;
+   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0, spr_scores = 0, spr_search = 0, radius = 0, top = 0, place = 0, n_pend = 4, supports = 0, newton = 0, newton_full = 0, exact_hessian = 0, se_exact = 0, subst_counts = 0, per_site = 0;
    double pend[64] = {0.05, 0.1, 0.2, 0.4}, split = 0.5;
    char over[2048] = "";
    const char *sim_out = NULL, *bv_out = NULL;
@@ -145,7 +149,7 @@ int main(int argc, char **argv)
    unsigned char comm_id[PAML_AMD_COMM_ID_BYTES];
    int device[MAX_RANKS];
    for (i = 0; i < MAX_RANKS; i++) device[i] = i;
-   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient | --analytic-gradient-all | --newton-branches] [--newton-full]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
+   if (argc < 3) { fprintf(stderr, "usage: %s <codeml|baseml> <ctl> [--optimize [--analytic-gradient | --analytic-gradient-all | --newton-branches] [--newton-full]] [--nni-scores | --nni-search [--max-moves N]] [--branch-supports [--replicates N] [--seed S]] [--spr-scores [--radius R] [--split PHI] | --spr-search [--radius R] [--top N] [--max-moves N]] [--place [--pendant a,b,c] [--split PHI]] [--bv FILE] [--subst-counts [--per-site]] [--ancestral | --ancestral-all] [--gpus N] [--tree K | --all-trees [--rell-gpu [--replicates N]]] [--simulate OUT [--sites N] [--seed S] [--replicates R]] [--set 'key = value'] [x...]\n", argv[0]); return 2; }
    for (i = 3; i < argc && nx < 4096; i++) {
       if (!strcmp(argv[i], "--optimize")) optimize = 1;
       else if (!strcmp(argv[i], "--analytic-gradient-all")) analytic = 2;  /* with --optimize: every parameter's derivative from one engine call per gradient */
@@ -154,6 +158,8 @@ int main(int argc, char **argv)
       else if (!strcmp(argv[i], "--newton-full")) newton_full = 1;         /* with --optimize: first the branch lengths by Newton steps from the whole Hessian block, one engine call per sweep (pamlh_newton_full), the other parameters held; prints the sweeps; then the optimiser chosen */
       else if (!strcmp(argv[i], "--exact-hessian")) exact_hessian = 1;     /* with --bv: the Hessian itself from one engine call (pamlh_write_bv_exact), not the outer product of scores */
       else if (!strcmp(argv[i], "--se-exact")) se_exact = 1;               /* standard errors from the observed information with the exact branch block (pamlh_standard_errors_exact) */
+      else if (!strcmp(argv[i], "--subst-counts")) subst_counts = 1;       /* posterior expected substitution counts per branch (pamlh_subst_counts) */
+      else if (!strcmp(argv[i], "--per-site")) per_site = 1;               /* with --subst-counts: the site x branch table of every label as well */
       else if (!strcmp(argv[i], "--nni-scores")) nni_scores = 1;
       else if (!strcmp(argv[i], "--branch-supports")) supports = 1;      /* SH-like aLRT supports of the internal branches (N replicates, default 1000; --seed S) */
       else if (!strcmp(argv[i], "--nni-search")) nni_search = 1;
@@ -452,6 +458,43 @@ int main(int argc, char **argv)
       for (i = 0; i < np; i++) printf(" %.6f", se[i]);
       printf("\n");
       free(se);
+   }
+   if (subst_counts) {      /* at the vector evaluated or just estimated */
+      const int *order = pamlh_branch_order(p), *sptr = pamlh_sons_ptr(p), *sons = pamlh_sons(p);
+      int n = 0, nnode = 0, nl = 0, one = 0, n_sites = 0, l, b, h, j, *father;
+      char names[3][32];
+      double *M, *cnt, *site = NULL;
+      if (gpus > 0) { fprintf(stderr, "error: --subst-counts runs on one GPU\n"); return 1; }
+      pamlh_dims(p, &n, NULL, NULL, &nnode, NULL, NULL, NULL, NULL, NULL, NULL);
+      pamlh_pose(p, &n_sites);
+      M = (double *)malloc((size_t)3 * n * n * sizeof(double));
+      if (pamlh_count_labels(p, NULL, &nl, M, names) || pamlh_count_labels(p, "total", &one, M + (size_t)nl * n * n, names + nl)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      nl += one;
+      cnt = (double *)malloc((size_t)nl * (ntime + 1) * sizeof(double));
+      if (per_site) site = (double *)malloc((size_t)nl * (ntime + 1) * (n_sites + 1) * sizeof(double));
+      if (pamlh_subst_counts(p, x, nl, M, cnt, site)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      father = (int *)malloc(nnode * sizeof(int));
+      for (b = 0; b < nnode; b++) father[b] = -1;
+      for (b = 0; b < nnode; b++) for (j = sptr[b]; j < sptr[b + 1]; j++) father[sons[j]] = b;
+      printf("\nExpected numbers of substitutions for each branch (posterior means given the data, one engine call)\n\n%10s %10s", "branch", "t");
+      for (l = 0; l < nl; l++) printf(" %15s", names[l]);
+      printf("\n\n");
+      for (b = 0; b < ntime; b++) {
+         char br[32];
+         snprintf(br, sizeof(br), "%d..%d", father[order[b]] + 1, order[b] + 1);
+         printf("%10s %10.6f", br, x[b]);
+         for (l = 0; l < nl; l++) printf(" %15.6f", cnt[(size_t)l * ntime + b]);
+         printf("\n");
+      }
+      for (l = 0; per_site && l < nl; l++) {
+         printf("\nExpected %s substitutions: site, then the branches in the order above\n", names[l]);
+         for (h = 0; h < n_sites; h++) {
+            printf("%6d", h + 1);
+            for (b = 0; b < ntime; b++) printf(" %9.6f", site[((size_t)l * ntime + b) * n_sites + h]);
+            printf("\n");
+         }
+      }
+      free(M); free(cnt); free(site); free(father);
    }
    if (sim_out) {      /* the data sets of a parametric bootstrap instead of the evaluation */
       int ns = 0, n_pose = 0, r;

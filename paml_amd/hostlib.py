@@ -20,7 +20,7 @@ DRIVER_PATH = os.path.join(_HERE, "lib", "pamlh_lnl")
 def build(force=False):
     from . import engine
     engine.build()
-    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_place.c", "pamlh_spr.c", "pamlh_support.c", "pamlh_newton.c", "pamlh_hessian.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
+    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_place.c", "pamlh_spr.c", "pamlh_support.c", "pamlh_newton.c", "pamlh_hessian.c", "pamlh_counts.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "pamlh.h"))
     if force or not (os.path.exists(LIB_PATH) and os.path.exists(DRIVER_PATH)) or \
             any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
@@ -646,6 +646,36 @@ class Analysis:
         if len(x) != self.np or self._L.pamlh_curvature(self._h, x.ctypes.data_as(C.c_void_p), C.byref(lnl), g.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p)) != 0:
             raise RuntimeError("pamlh_curvature: " + self._L.pamlh_error(self._h).decode())
         return dict(lnL=lnl.value, grad=g[:nt], curv=h[:nt])
+
+    def count_labels(self, kind=None):
+        """The substitution labels that go with the analysis's data type (pamlh_count_labels): (names, M[n_lab][n][n]).  kind None or
+        "standard": synonymous / nonsynonymous (codons, by the genetic code), transitions / transversions (nucleotides), changes (amino
+        acids); "total": every jump; "dwell": the identity, whose count is the branch length."""
+        nl = C.c_int()
+        M = np.zeros((2, self.n, self.n))
+        names = ((C.c_char * 32) * 2)()
+        self._L.pamlh_count_labels.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
+        if self._L.pamlh_count_labels(self._h, None if kind is None else kind.encode(), C.byref(nl), M.ctypes.data_as(C.c_void_p), names) != 0:
+            raise RuntimeError("pamlh_count_labels: " + self._L.pamlh_error(self._h).decode())
+        return [names[i].value.decode() for i in range(nl.value)], M[:nl.value].copy()
+
+    def subst_counts(self, x, labels=None, per_site=False):
+        """Posterior expected labelled substitution counts at x over x's branch-length block (branch_order) from one engine call
+        (pamlh_subst_counts -> paml_amd_subst_counts): dict(names, counts=[n_lab][ntime] summed over the alignment's sites,
+        site_counts=[n_lab][ntime][sites] with per_site, else None).  labels None: the standard set of count_labels()."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        names = None
+        if labels is None:
+            names, labels = self.count_labels()
+        M = np.ascontiguousarray(labels, dtype=np.float64).reshape(-1, self.n, self.n)
+        nt = self.ntime
+        counts = np.zeros((len(M), max(1, nt)))
+        sites = np.zeros((len(M), max(1, nt), len(self.pose()))) if per_site else None
+        self._L.pamlh_subst_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        if len(x) != self.np or self._L.pamlh_subst_counts(self._h, x.ctypes.data_as(C.c_void_p), len(M), M.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                                                           None if sites is None else sites.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_subst_counts: " + self._L.pamlh_error(self._h).decode())
+        return dict(names=names, counts=counts[:, :nt], site_counts=None if sites is None else sites[:, :nt])
 
     def newton_branches(self, x, e=1e-8, max_sweeps=50, verbose=0):
         """Maximises lnL over x's branch-length block by Newton steps on every branch at once, one engine call per sweep, the rest of x
