@@ -139,7 +139,10 @@ int paml_amd_set_tips(paml_amd_engine *e, const unsigned char *z, int cleandata,
 int paml_amd_set_tree(paml_amd_engine *e, int n_nodes, int root, const int *sons_ptr, const int *sons,
                       const int *label, const unsigned char *scale_node);
 
-/* com.pi (n_pi = 1) or com.piG per gene (n_pi = n_genes), row-major [n_pi][n_states]. */
+/* com.pi (n_pi = 1) or com.piG per gene (n_pi = n_genes), row-major [n_pi][n_states].  Callable at any time, also with another n_pi
+ * than before: every later call reads the new vector.  The branch-local state of paml_amd_eval_branch (resident partials, eigen-basis
+ * coefficients and operand fragments, which hold pi) starts over; the resident partials of PAML_AMD_KEEP_PARTIALS, P(t) and the per-tree
+ * kernels do not depend on pi and stay. */
 int paml_amd_set_pi(paml_amd_engine *e, int n_pi, const double *pi);
 
 /* The same decomposition done ON THE DEVICE, for a batch of reversible rate matrices at once — what eigenQREV (tools.c:5023-5110,

@@ -311,6 +311,9 @@ int paml_amd_set_pi(paml_amd_engine *e, int n_pi, const double *pi)
    HIPCHK(hipStreamSynchronize(e->stream));
    e->n_pi = n_pi;
    e->have_pi = true;
+   // (the eigen-basis form of eval_branch keeps pi inside its operand fragments, tip rows and branch coefficients — frag_ok, coef_ok:
+   //  they start over.  The resident partials, P(t) and the per-tree kernels hold nothing of pi: it is read at the root sum.)
+   e->bl.valid = false;
    return 0;
 }
 
