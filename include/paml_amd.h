@@ -422,6 +422,11 @@ int paml_amd_debug_subtree_select(int n_tips, int n_nodes, int root, const int *
 int paml_amd_debug_jit_subtree(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons, const unsigned char *scale_node, int n_states,
                                int n_codes, int K, const int *sel, int n_sel, int compile, const char *dir, char *text_out, int cap, int *blocks_left);
 
+/* Bytes of device memory the library's own buffers (the engines', the pair sets', the scratch of calls in progress) hold at this moment,
+ * over the whole process: what a call allocated for itself is gone when it returns, and everything of an engine when it is destroyed.
+ * (The tests' check on both; not a measure of the device's free memory.) */
+long long paml_amd_debug_device_bytes(void);
+
 /* Host-only (hiprtc cross-compiles without a GPU): compile the per-tree kernel an engine of these sizes would select for this tree
  * and keep the code object in `dir` (the library's read-only lib/jit directory, or a user cache), so that the first evaluation on
  * a fresh machine does not start with seconds of compilation.  n_patt_global fixes the reduction chunk the 4 / 5-state kernel is

@@ -21,13 +21,13 @@ struct AncCallInfo {
    }
 };
 
-// what a call allocates for itself; released on every way out
+// what a call allocates for itself; released on every way out (the members free themselves, dev_buf.h: so do those a call's own struct adds)
 struct AncScratch {
    AncCallInfo &info;
    DevBuf<int> tree, query;
    DevBuf<double> L, G, SL, SG, post, prob, lnP, lnbest;
    DevBuf<unsigned char> best, C, state, rootstate;
-   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+   DevEvent ev0, ev1;
    explicit AncScratch(AncCallInfo &i) : info(i) {}
    // waits for the stream and adds the time between ev0 and ev1 to the call's
    hipError_t lap(hipStream_t st)
@@ -38,20 +38,27 @@ struct AncScratch {
       info.kernel_ms += ms;
       return r;
    }
-   ~AncScratch()
+};
+
+// a buffer of the batch workspace, of any element type, and the elements it holds per pattern of the batch
+struct AncBatchBuf {
+   void *buf;
+   size_t per_patt;
+   hipError_t (*ensure)(void *, size_t);
+   void (*release)(void *);
+   template <class T>
+   AncBatchBuf(DevBuf<T> *b, size_t per)
+      : buf(b), per_patt(per), ensure([](void *p, size_t n) { return ((DevBuf<T> *)p)->ensure(n); }), release([](void *p) { ((DevBuf<T> *)p)->release(); })
    {
-      tree.release(); query.release();
-      for (DevBuf<double> *b : {&L, &G, &SL, &SG, &post, &prob, &lnP, &lnbest}) b->release();
-      for (DevBuf<unsigned char> *b : {&best, &C, &state, &rootstate}) b->release();
-      if (ev0) (void)hipEventDestroy(ev0);
-      if (ev1) (void)hipEventDestroy(ev1);
    }
 };
 
-// a buffer of the batch workspace and the doubles it holds per pattern of the batch
-struct AncBatchBuf {
-   DevBuf<double> *buf;
-   size_t per_patt;
+// a batch of the batch loop: patterns [h0, h0 + nb) of `gene`, and the two grids over them (x: tiles of ANC_TILE patterns / blocks of 256
+// lanes; y: the classes)
+struct AncBatch {
+   int gene;
+   long h0, nb;
+   dim3 tiles, lanes;
 };
 
 int anc_tree_pack(paml_amd_engine *e, const char *who, AncScratch &w, AncTree *out);
@@ -66,6 +73,8 @@ void anc_fill(const paml_amd_engine *e, const AncScratch &w, long batch, AncMarg
 std::vector<long> anc_chunk_base(const paml_amd_engine *e);
 int anc_totals(paml_amd_engine *e, AncScratch &w, const double *partial, long n_chunks, double *d_out, std::vector<double> &out);
 int anc_common_checks(paml_amd_engine *e, const char *who);
+int anc_begin(paml_amd_engine *e, const char *who, const char *unrest_reason);
+int grad_dpmat(paml_amd_engine *e, DevBuf<double> &dP, DevBuf<double> *d2P, DevBuf<double> &PT);
 
 // 4 / 5 / 20 states, the engines that are not on the matrix cores (paml_amd_create: every other state count is KK_MFMA64): f(N) with the
 // state count a compile-time constant, for the lane kernels' template argument
@@ -76,56 +85,83 @@ template <class F> void anc_lanes(KernelKind kk, F &&f)
    else f(std::integral_constant<int, 20>{});
 }
 
-// The batch loop of the score calls (NNI, placement, SPR).  Per gene and batch of patterns: the down pass and the outer pass of the
-// present tree (matrix cores: anc_mfma_kernel and nni_mfma_outer_kernel; lanes: the caller's kernel, lane_pass(lanes, pass)), the caller's
-// kernel for the present tree's row if it has one (present(lanes)), then per group of rows the caller's row kernel (rows(gi, tiles,
-// lanes), which also names the group in its arguments), its combining kernel (combine(gi, lanes)) and its copies to the caller's arrays
-// (copy_out(gi, h0, nb), an error code).  A batch's first group is timed with its down and outer passes, every other by itself.
-template <class LanePass, class Present, class Rows, class Combine, class CopyOut>
-int anc_score_batches(paml_amd_engine *e, AncScratch &w, NniArgs &o, const std::vector<long> &chunk_base, long batch, int n_groups, LanePass lane_pass, Present present,
-                      Rows rows, Combine combine, CopyOut copy_out)
+// The batch loop of every whole-tree call.  Per gene and batch of patterns, in this order: the batch named in `m` (gene, h0, nb; any
+// argument structure with these members; AncMargArgs where the call has the two passes) and in *chunk0 (its first chunk of GRAD_CHUNK
+// patterns, counted as anc_chunk_base counts; null: the call has no chunks); ev0; the down pass and the outer pass of the present tree —
+// matrix cores: anc_mfma_kernel at 0 and the caller's kernel (mfma_outer(b)), lanes: the caller's kernel at pass 0 and 1 (lane_pass(b,
+// pass)); both null: a call without the two passes —; the caller's other launches (rest(b), an error code); ev1; the caller's copies
+// out (copy_out(b), an error code); the wait that adds the time between the events to the call's; the batch counted.  A callback that
+// keeps per-batch bookkeeping in the kernels' arguments does it before its first launch (paml_amd_model_gradient's `place`).
+template <class A, class MfmaOuter, class LanePass, class Rest, class CopyOut>
+int anc_batches(paml_amd_engine *e, AncScratch &w, A &m, long *chunk0, long batch, MfmaOuter mfma_outer, LanePass lane_pass, Rest rest, CopyOut copy_out)
 {
-   AncMargArgs &m = o.m;
-   const bool mfma = e->kk == KK_MFMA64;
    hipStream_t st = e->stream;
+   std::vector<long> chunk_base;
+   if (chunk0) chunk_base = anc_chunk_base(e);
    for (int g = 0; g < e->n_genes; g++)
       for (long h0 = e->gene_off[g]; h0 < e->gene_off[g + 1]; h0 += batch) {
          const long nb = std::min<long>(batch, e->gene_off[g + 1] - h0);
          m.gene = g; m.h0 = h0; m.nb = nb;
-         o.chunk0 = chunk_base[g] + (h0 - e->gene_off[g]) / GRAD_CHUNK;
-         o.swap0 = 0; o.n_group = 0;
-         const dim3 tiles((unsigned)((nb + ANC_TILE - 1) / ANC_TILE), m.K), lanes((unsigned)((nb + 255) / 256), m.K);
+         if (chunk0) *chunk0 = chunk_base[g] + (h0 - e->gene_off[g]) / GRAD_CHUNK;
+         const AncBatch b{g, h0, nb, dim3((unsigned)((nb + ANC_TILE - 1) / ANC_TILE), e->K), dim3((unsigned)((nb + 255) / 256), e->K)};
          HIPCHK(hipEventRecord(w.ev0, st));
-         if (mfma) {
-            hipLaunchKernelGGL(anc_mfma_kernel, tiles, dim3(256), 0, st, m, 0);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(nni_mfma_outer_kernel, tiles, dim3(256), 0, st, o);
-            HIPCHK(hipGetLastError());
-         }
-         else
-            for (int pass = 0; pass < 2; pass++) {
-               lane_pass(lanes, pass);
+         if constexpr (!std::is_same_v<MfmaOuter, std::nullptr_t>) {
+            if (e->kk == KK_MFMA64) {
+               hipLaunchKernelGGL(anc_mfma_kernel, b.tiles, dim3(256), 0, st, m, 0);
+               HIPCHK(hipGetLastError());
+               mfma_outer(b);
                HIPCHK(hipGetLastError());
             }
-         present(lanes);
-         HIPCHK(hipGetLastError());
+            else
+               for (int pass = 0; pass < 2; pass++) {
+                  lane_pass(b, pass);
+                  HIPCHK(hipGetLastError());
+               }
+         }
+         if (int rc = rest(b)) return rc;
          HIPCHK(hipEventRecord(w.ev1, st));
+         if (int rc = copy_out(b)) return rc;
+         HIPCHK(w.lap(st));
+         w.info.batches++;
+      }
+   return 0;
+}
+
+// The batch loop of the score calls (NNI, placement, SPR), on anc_batches.  The outer pass of the present tree is nni_mfma_outer_kernel
+// (matrix cores) or the caller's kernel, lane_pass(lanes, pass); then the caller's kernel for the present tree's row if it has one
+// (present(lanes)); then, as the batch's copies out, per group of rows the caller's row kernel (rows(gi, tiles, lanes), which also names
+// the group in its arguments), its combining kernel (combine(gi, lanes)) and its copies to the caller's arrays (copy_out(gi, h0, nb), an
+// error code).  A batch's first group is timed with its down and outer passes, every other by itself.
+template <class LanePass, class Present, class Rows, class Combine, class CopyOut>
+int anc_score_batches(paml_amd_engine *e, AncScratch &w, NniArgs &o, long batch, int n_groups, LanePass lane_pass, Present present, Rows rows, Combine combine,
+                      CopyOut copy_out)
+{
+   hipStream_t st = e->stream;
+   o.swap0 = 0; o.n_group = 0;      // (the passes and the present tree's row run with no group named)
+   return anc_batches(
+      e, w, o.m, &o.chunk0, batch, [&](const AncBatch &b) { hipLaunchKernelGGL(nni_mfma_outer_kernel, b.tiles, dim3(256), 0, st, o); },
+      [&](const AncBatch &b, int pass) { lane_pass(b.lanes, pass); },
+      [&](const AncBatch &b) {
+         present(b.lanes);
+         HIPCHK(hipGetLastError());
+         return 0;
+      },
+      [&](const AncBatch &b) {
          for (int gi = 0; gi < n_groups; gi++) {
             if (gi) {
                HIPCHK(w.lap(st));
                HIPCHK(hipEventRecord(w.ev0, st));
             }
-            rows(gi, tiles, lanes);
+            rows(gi, b.tiles, b.lanes);
             HIPCHK(hipGetLastError());
-            combine(gi, lanes);
+            combine(gi, b.lanes);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(w.ev1, st));
-            if (int rc = copy_out(gi, h0, nb)) return rc;
+            if (int rc = copy_out(gi, b.h0, b.nb)) return rc;
          }
-         HIPCHK(w.lap(st));
-         w.info.batches++;
-      }
-   return 0;
+         o.swap0 = 0; o.n_group = 0;
+         return 0;
+      });
 }
 
 }  // namespace paml_amd

@@ -5,6 +5,7 @@
 // Built for gfx950 only (one of the translation units of libpaml_amd.so, see engine_state.h).
 #include "engine_state.h"
 #include "kernels_ancestral.h"
+#include "kernels_curvature.h"
 #include "ancestral_host.h"
 
 static thread_local AncCallInfo anc_info;
@@ -202,8 +203,8 @@ int anc_pmat(paml_amd_engine *e, const char *who, const double *branch, const do
       HIPCHK(hipStreamSynchronize(st));      // (`gr` is on this stack)
       e->bl_gr_sent = false;
    }
-   if (!w.ev0) HIPCHK(hipEventCreate(&w.ev0));
-   if (!w.ev1) HIPCHK(hipEventCreate(&w.ev1));
+   HIPCHK(w.ev0.ensure());
+   HIPCHK(w.ev1.ensure());
    if (int rc = ensure_pmat_buffers(e, G * K, false, false)) return rc;
    // (from here on the P(t) buffers are this call's: whatever looked at an earlier evaluation's starts over)
    e->pmat_valid = false;
@@ -293,10 +294,10 @@ int anc_alloc(paml_amd_engine *e, const char *who, std::initializer_list<AncBatc
 {
    for (;;) {
       bool ok = true;
-      for (const AncBatchBuf &b : bufs) ok = ok && b.buf->ensure(b.per_patt * *batch) == hipSuccess;
+      for (const AncBatchBuf &b : bufs) ok = ok && b.ensure(b.buf, b.per_patt * *batch) == hipSuccess;
       if (ok) return 0;
       (void)hipGetLastError();
-      for (const AncBatchBuf &b : bufs) b.buf->release();      // (ensure only grows: the retry starts from nothing)
+      for (const AncBatchBuf &b : bufs) b.release(b.buf);      // (ensure only grows: the retry starts from nothing)
       if (*batch <= ANC_TILE) return fail(e, PAML_AMD_ENOMEM, std::string(who) + ": no device memory for one tile of patterns");
       *batch = (*batch / 2 + ANC_TILE - 1) / ANC_TILE * ANC_TILE;
    }
@@ -342,6 +343,40 @@ int anc_common_checks(paml_amd_engine *e, const char *who)
    return 0;
 }
 
+
+// What the derivative calls refuse before they allocate, in this order: anc_common_checks, more than one rank, a rate-matrix (UNREST)
+// set with the caller's sentence for it (`unrest_reason`; null: such sets are allowed), a tree without a branch.
+int anc_begin(paml_amd_engine *e, const char *who, const char *unrest_reason)
+{
+   if (int rc = anc_common_checks(e, who)) return rc;
+   if (e->world > 1) return fail(e, PAML_AMD_EUNSUPPORTED, std::string(who) + ": one rank only (this engine's communicator has " + std::to_string(e->world) + ")");
+   for (size_t i = 0; unrest_reason && i < e->eigen.size(); i++)
+      if (e->eigen[i].kind == PAML_AMD_EIGEN_QMAT) return fail(e, PAML_AMD_EUNSUPPORTED, std::string(who) + ": " + unrest_reason);
+   if (e->tree.n_nodes < 2) return fail(e, PAML_AMD_EINVAL, std::string(who) + ": the tree has no branch");
+   return 0;
+}
+
+// dP (and d2P when asked for: curv_pmat_kernel instead of grad_pmat_kernel) of every (parameter set, node) behind anc_pmat's P(t), and on
+// the matrix cores P^T: the buffers sized, one launch
+int grad_dpmat(paml_amd_engine *e, DevBuf<double> &dP, DevBuf<double> *d2P, DevBuf<double> &PT)
+{
+   const int nn = e->tree.n_nodes, n = e->n, K = e->K, G = e->n_genes;
+   const bool mfma = e->kk == KK_MFMA64;
+   const size_t pn = (size_t)G * K * nn, each = mfma ? 4096 : (size_t)n * n;
+   HIPCHK(dP.ensure(pn * each));
+   if (d2P) HIPCHK(d2P->ensure(pn * each));
+   if (mfma) HIPCHK(PT.ensure(pn * 4096));
+   GradPmatArgs ga{};
+   ga.n = n; ga.K = K; ga.n_nodes = nn; ga.n_tips = e->n_tips; ga.root = e->tree.root; ga.n_labels = e->n_labels; ga.rate_gs = e->rate_per_gene ? K : 0; ga.mfma = mfma ? 1 : 0;
+   ga.label = e->d_label.p; ga.eigen_of = e->d_eigen_of.p; ga.eigen = e->d_eigen.p;
+   ga.branch = e->d_branch.p; ga.rate = e->d_rate.p; ga.gene_rate = e->d_gene_rate.p; ga.qfactor = e->d_qfactor.p;
+   ga.P = e->d_rowmajor.p; ga.dP = dP.p; ga.PT = PT.p; ga.d2P = d2P ? d2P->p : nullptr;
+   if (d2P) hipLaunchKernelGGL(curv_pmat_kernel, dim3(nn, G * K), dim3(256), 0, e->stream, ga);
+   else hipLaunchKernelGGL(grad_pmat_kernel, dim3(nn, G * K), dim3(256), 0, e->stream, ga);
+   HIPCHK(hipGetLastError());
+   return 0;
+}
+
 }  // namespace paml_amd
 
 extern "C" int paml_amd_ancestral_marginal(paml_amd_engine *e, const double *branch, const double *gene_rate, int n_query, const int *nodes,
@@ -353,7 +388,7 @@ extern "C" int paml_amd_ancestral_marginal(paml_amd_engine *e, const double *bra
    if (!e || !branch || !best || !best_prob) return fail(e, PAML_AMD_EINVAL, "ancestral_marginal: null argument");
    if (int rc = anc_common_checks(e, who)) return rc;
    const TreeDesc &T = e->tree;
-   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, n_tips = e->n_tips, n_int = nn - n_tips;
+   const int nn = T.n_nodes, n = e->n, K = e->K, n_tips = e->n_tips, n_int = nn - n_tips;
    std::vector<int> query;
    if (nodes) {
       if (n_query < 1) return fail(e, PAML_AMD_EINVAL, "ancestral_marginal: n_query = " + std::to_string(n_query) + " < 1");
@@ -385,43 +420,30 @@ extern "C" int paml_amd_ancestral_marginal(paml_amd_engine *e, const double *bra
    const int ns = mfma ? 64 : n;      // doubles a partial takes per pattern
    const double per_patt = 2.0 * K * n_int * (ns + 1) * 8 + (double)nq * (n * 8 + 9);
    long batch = anc_batch(per_patt, e->n_patt);
-   for (;;) {      // halve the batch until it fits
-      const size_t part = (size_t)K * n_int * ns * batch, sc = (size_t)K * n_int * batch;
-      if (w.L.ensure(part) == hipSuccess && w.G.ensure(part) == hipSuccess && w.SL.ensure(sc) == hipSuccess && w.SG.ensure(sc) == hipSuccess &&
-          w.post.ensure((size_t)nq * batch * n) == hipSuccess && w.prob.ensure((size_t)nq * batch) == hipSuccess && w.best.ensure((size_t)nq * batch) == hipSuccess)
-         break;
-      (void)hipGetLastError();
-      w.L.release(); w.G.release(); w.post.release();
-      if (batch <= ANC_TILE) return fail(e, PAML_AMD_ENOMEM, "ancestral_marginal: no device memory for one tile of patterns");
-      batch = (batch / 2 + ANC_TILE - 1) / ANC_TILE * ANC_TILE;
+   {
+      const size_t part = (size_t)K * n_int * ns, sc = (size_t)K * n_int;
+      if (int rc = anc_alloc(e, who, {{&w.L, part}, {&w.G, part}, {&w.SL, sc}, {&w.SG, sc}, {&w.post, (size_t)nq * n}, {&w.prob, (size_t)nq}, {&w.best, (size_t)nq}}, &batch)) return rc;
    }
    anc_fill(e, w, batch, a);
    a.n_query = nq; a.query = w.query.p; a.post = w.post.p; a.best_prob = w.prob.p; a.best = w.best.p;
    const long n_patt = e->n_patt;
-   for (int g = 0; g < G; g++)
-      for (long h0 = e->gene_off[g]; h0 < e->gene_off[g + 1]; h0 += batch) {
-         const long nb = std::min<long>(batch, e->gene_off[g + 1] - h0);
-         a.gene = g; a.h0 = h0; a.nb = nb;
-         HIPCHK(hipEventRecord(w.ev0, st));
-         for (int outer = 0; outer < 2; outer++) {
-            if (mfma) hipLaunchKernelGGL(anc_mfma_kernel, dim3((unsigned)((nb + ANC_TILE - 1) / ANC_TILE), K), dim3(256), 0, st, a, outer);
-            else anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(anc_lane_kernel<N()>, dim3((unsigned)((nb + 255) / 256), K), dim3(256), 0, st, a, outer); });
-            HIPCHK(hipGetLastError());
-         }
-         hipLaunchKernelGGL(anc_posterior_kernel, dim3((unsigned)((nb + 255) / 256), nq), dim3(256), 0, st, a);
+   return anc_batches(
+      e, w, a, nullptr, batch, [&](const AncBatch &b) { hipLaunchKernelGGL(anc_mfma_kernel, b.tiles, dim3(256), 0, st, a, 1); },
+      [&](const AncBatch &b, int pass) { anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(anc_lane_kernel<N()>, b.lanes, dim3(256), 0, st, a, pass); }); },
+      [&](const AncBatch &b) {
+         hipLaunchKernelGGL(anc_posterior_kernel, dim3(b.lanes.x, nq), dim3(256), 0, st, a);
          HIPCHK(hipGetLastError());
-         HIPCHK(hipEventRecord(w.ev1, st));
-         // the batch's rows to the caller's [n_query][n_patt]( [n] ): one plain copy per queried node (no pitch that n_patt could outgrow)
+         return 0;
+      },
+      [&](const AncBatch &b) {      // the batch's rows to the caller's [n_query][n_patt]( [n] ): one plain copy per queried node (no pitch that n_patt could outgrow)
          for (int qi = 0; qi < nq; qi++) {
-            HIPCHK(hipMemcpyAsync(best + (size_t)qi * n_patt + h0, w.best.p + (size_t)qi * batch, (size_t)nb, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(best_prob + (size_t)qi * n_patt + h0, w.prob.p + (size_t)qi * batch, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(best + (size_t)qi * n_patt + b.h0, w.best.p + (size_t)qi * batch, (size_t)b.nb, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(best_prob + (size_t)qi * n_patt + b.h0, w.prob.p + (size_t)qi * batch, (size_t)b.nb * 8, hipMemcpyDeviceToHost, st));
             if (post)
-               HIPCHK(hipMemcpyAsync(post + ((size_t)qi * n_patt + h0) * n, w.post.p + (size_t)qi * batch * n, (size_t)nb * n * 8, hipMemcpyDeviceToHost, st));
+               HIPCHK(hipMemcpyAsync(post + ((size_t)qi * n_patt + b.h0) * n, w.post.p + (size_t)qi * batch * n, (size_t)b.nb * n * 8, hipMemcpyDeviceToHost, st));
          }
-         HIPCHK(w.lap(st));
-         anc_info.batches++;
-      }
-   return 0;
+         return 0;
+      });
 }
 
 extern "C" int paml_amd_ancestral_joint(paml_amd_engine *e, const double *branch, const double *gene_rate, unsigned char *states, double *ln_best)
@@ -449,34 +471,23 @@ extern "C" int paml_amd_ancestral_joint(paml_amd_engine *e, const double *branch
 
    const double per_patt = (double)n_int * n * 9 + n_int + 1 + 8;
    long batch = anc_batch(per_patt, e->n_patt);
-   for (;;) {      // halve the batch until it fits
-      if (w.L.ensure((size_t)n_int * n * batch) == hipSuccess && w.C.ensure((size_t)n_int * n * batch) == hipSuccess &&
-          w.state.ensure((size_t)n_int * batch) == hipSuccess && w.rootstate.ensure((size_t)batch) == hipSuccess && w.lnbest.ensure((size_t)batch) == hipSuccess)
-         break;
-      (void)hipGetLastError();
-      w.L.release(); w.C.release();
-      if (batch <= ANC_TILE) return fail(e, PAML_AMD_ENOMEM, "ancestral_joint: no device memory for one tile of patterns");
-      batch = (batch / 2 + ANC_TILE - 1) / ANC_TILE * ANC_TILE;
-   }
+   if (int rc = anc_alloc(e, who, {{&w.L, (size_t)n_int * n}, {&w.C, (size_t)n_int * n}, {&w.state, (size_t)n_int}, {&w.rootstate, 1}, {&w.lnbest, 1}}, &batch)) return rc;
    a.n = n; a.stride = batch; a.z = e->d_z.p; a.z_stride = e->n_patt; a.code_mask = e->d_code_mask.p;
    a.lnP = w.lnP.p; a.L = w.L.p; a.C = w.C.p; a.state = w.state.p; a.rootstate = w.rootstate.p; a.ln_best = w.lnbest.p;
    const long n_patt = e->n_patt;
    const size_t lds = (size_t)n * n * sizeof(double);
-   for (int g = 0; g < G; g++)
-      for (long h0 = e->gene_off[g]; h0 < e->gene_off[g + 1]; h0 += batch) {
-         const long nb = std::min<long>(batch, e->gene_off[g + 1] - h0);
-         a.gene = g; a.h0 = h0; a.nb = nb;
-         a.lnpi = w.lnP.p + n_p + (long)(e->n_pi > 1 ? g : 0) * n;
-         const dim3 grid((unsigned)((nb + ANC_JTILE - 1) / ANC_JTILE));
-         HIPCHK(hipEventRecord(w.ev0, st));
-         hipLaunchKernelGGL(anc_joint_kernel, grid, dim3(ANC_JTILE), lds, st, a);
+   return anc_batches(
+      e, w, a, nullptr, batch, nullptr, nullptr,      // (one kernel walks the tree up and down: no two passes)
+      [&](const AncBatch &b) {
+         a.lnpi = w.lnP.p + n_p + (long)(e->n_pi > 1 ? b.gene : 0) * n;
+         hipLaunchKernelGGL(anc_joint_kernel, dim3((unsigned)((b.nb + ANC_JTILE - 1) / ANC_JTILE)), dim3(ANC_JTILE), lds, st, a);
          HIPCHK(hipGetLastError());
-         HIPCHK(hipEventRecord(w.ev1, st));
+         return 0;
+      },
+      [&](const AncBatch &b) {
          for (int vi = 0; vi < n_int; vi++)
-            HIPCHK(hipMemcpyAsync(states + (size_t)vi * n_patt + h0, w.state.p + (size_t)vi * batch, (size_t)nb, hipMemcpyDeviceToHost, st));
-         HIPCHK(hipMemcpyAsync(ln_best + h0, w.lnbest.p, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-         HIPCHK(w.lap(st));
-         anc_info.batches++;
-      }
-   return 0;
+            HIPCHK(hipMemcpyAsync(states + (size_t)vi * n_patt + b.h0, w.state.p + (size_t)vi * batch, (size_t)b.nb, hipMemcpyDeviceToHost, st));
+         HIPCHK(hipMemcpyAsync(ln_best + b.h0, w.lnbest.p, (size_t)b.nb * 8, hipMemcpyDeviceToHost, st));
+         return 0;
+      });
 }

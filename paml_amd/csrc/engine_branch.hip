@@ -420,8 +420,7 @@ int eigen_form(paml_amd_engine *e, const BranchEval &c)
    const bool feval = !f.hit && c.K == 1 && c.n_t <= BEIG_NT;
    e->bk_timed = false;
    if (e->profiling) {
-      for (hipEvent_t &ev : e->ev_bk)
-         if (!ev) HIPCHK(hipEventCreate(&ev));
+      for (DevEvent &ev : e->ev_bk) HIPCHK(ev.ensure());
       HIPCHK(hipEventRecord(e->ev_bk[0], st));
    }
    if (!f.hit) {

@@ -94,20 +94,11 @@ int paml_amd_create(paml_amd_engine **out, int n_states, int n_tips, int n_patt,
 void paml_amd_destroy(paml_amd_engine *e)
 {
    if (!e) return;
-   (void)hipStreamSynchronize(e->stream);
-   for (hipStream_t s : e->sb)
-      if (s) {
-         (void)hipStreamSynchronize(s);
-         (void)hipStreamDestroy(s);
-      }
-   if (e->s2) {
-      (void)hipStreamSynchronize(e->s2);
-      (void)hipStreamDestroy(e->s2);
-      for (hipEvent_t ev : {e->ev_entry[0], e->ev_entry[1], e->ev_pmat}) if (ev) (void)hipEventDestroy(ev);
-      for (hipEvent_t ev : e->ev_setread) if (ev) (void)hipEventDestroy(ev);
-   }
+   (void)hipStreamSynchronize(e->stream);      // (the caller's stream; the engine's own are the destructor's)
    delete e;
 }
+
+long long paml_amd_debug_device_bytes(void) { return dev_buf_bytes.load(); }
 
 // e == NULL: the message of the calling thread's last failed stand-alone entry (paml_amd_rell_replicates)
 const char *paml_amd_standalone_error(void);      // engine_rell.hip; "" when there is none
@@ -768,7 +759,7 @@ int paml_amd_profile_read(paml_amd_engine *e, double *ms_pmat, double *ms_prune,
          float ms = 0;
          if (hipEventElapsedTime(&ms, e->ev_used[i + 2 * k], e->ev_used[i + 2 * k + 1]) == hipSuccess) acc[k] += ms;
       }
-   for (auto ev : e->ev_used) e->ev_pool.push_back(ev);
+   for (DevEvent &ev : e->ev_used) e->ev_pool.push_back(std::move(ev));
    e->ev_used.clear();
    if (ms_pmat) *ms_pmat = acc[0];
    if (ms_prune) *ms_prune = acc[1];

@@ -256,10 +256,6 @@ namespace {
 struct CountsScratch : AncScratch {
    using AncScratch::AncScratch;
    DevBuf<double> PT, H, den, sig, R, SR, croot, rows, lnf, partial, out, M, I, site;
-   ~CountsScratch()
-   {
-      for (DevBuf<double> *b : {&PT, &H, &den, &sig, &R, &SR, &croot, &rows, &lnf, &partial, &out, &M, &I, &site}) b->release();
-   }
 };
 
 }  // namespace
@@ -271,14 +267,9 @@ extern "C" int paml_amd_subst_counts(paml_amd_engine *e, const double *branch, c
    counts_info = AncCallInfo{};
    const char *who = "subst_counts";
    if (!e || !branch || !labels || !lnL || !counts) return fail(e, PAML_AMD_EINVAL, "subst_counts: null argument");
-   if (int rc = anc_common_checks(e, who)) return rc;
-   if (e->world > 1) return fail(e, PAML_AMD_EUNSUPPORTED, "subst_counts: one rank only (this engine's communicator has " + std::to_string(e->world) + ")");
-   for (size_t i = 0; i < e->eigen.size(); i++)
-      if (e->eigen[i].kind == PAML_AMD_EIGEN_QMAT)
-         return fail(e, PAML_AMD_EUNSUPPORTED, "subst_counts: a rate-matrix (UNREST) set has no spectral form for the integral of the label matrices");
+   if (int rc = anc_begin(e, who, "a rate-matrix (UNREST) set has no spectral form for the integral of the label matrices")) return rc;
    const TreeDesc &T = e->tree;
-   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, n_tips = e->n_tips, n_int = nn - n_tips;
-   if (nn < 2) return fail(e, PAML_AMD_EINVAL, "subst_counts: the tree has no branch");
+   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, n_int = nn - e->n_tips;
    if (n_lab < 1 || n_lab > COUNTS_MAX_LABELS)
       return fail(e, PAML_AMD_EINVAL, "subst_counts: n_lab = " + std::to_string(n_lab) + " is not in 1 .. " + std::to_string(COUNTS_MAX_LABELS));
    for (size_t i = 0; i < (size_t)n_lab * n * n; i++)
@@ -331,8 +322,7 @@ extern "C" int paml_amd_subst_counts(paml_amd_engine *e, const double *branch, c
    if (int rc = anc_pmat_wait(e, w)) return rc;      // (also: `query` and the caller's labels are read)
    e->pmat_valid = true;      // (d_rowmajor holds every branch's P(t) in the tree's own orientation, as after paml_amd_gradient)
 
-   const std::vector<long> chunk_base = anc_chunk_base(e);
-   const long n_chunks = chunk_base[G];
+   const long n_chunks = anc_chunk_base(e)[G];
    const int ns = mfma ? 64 : n;
    HIPCHK(w.partial.ensure((size_t)(1 + n_rows) * std::max<long>(n_chunks, 1)));
    HIPCHK(w.out.ensure((size_t)1 + n_rows));
@@ -349,48 +339,37 @@ extern "C" int paml_amd_subst_counts(paml_amd_engine *e, const double *branch, c
    a.I = w.I.p; a.nodes = w.query.p; a.n_query = nq; a.n_lab = n_lab; a.site = w.site.p;
    if (site_counts && !nodes)      // (the root's rows)
       for (int l = 0; l < n_lab; l++) std::fill_n(site_counts + ((size_t)l * nn + T.root) * e->n_patt, (size_t)e->n_patt, 0.0);
-   for (int g = 0; g < G; g++)
-      for (long h0 = e->gene_off[g]; h0 < e->gene_off[g + 1]; h0 += batch) {
-         const long nb = std::min<long>(batch, e->gene_off[g + 1] - h0);
-         m.gene = g; m.h0 = h0; m.nb = nb;
-         ga.chunk0 = chunk_base[g] + (h0 - e->gene_off[g]) / GRAD_CHUNK;
-         const unsigned lanes = (unsigned)((nb + 255) / 256), tiles = (unsigned)((nb + ANC_TILE - 1) / ANC_TILE);
-         HIPCHK(hipEventRecord(w.ev0, st));
-         if (mfma) {
-            hipLaunchKernelGGL(anc_mfma_kernel, dim3(tiles, K), dim3(256), 0, st, m, 0);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(mg_mfma_outer_kernel, dim3(tiles, K), dim3(256), 0, st, ga);
-            HIPCHK(hipGetLastError());
-         }
-         else
-            for (int pass = 0; pass < 2; pass++) {
-               anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(counts_pass_kernel<N()>, dim3(lanes, K), dim3(256), 0, st, ga, pass); });
-               HIPCHK(hipGetLastError());
-            }
-         hipLaunchKernelGGL(counts_scalar_kernel, dim3(lanes), dim3(256), 0, st, ga);
-         HIPCHK(hipGetLastError());
-         hipLaunchKernelGGL(mg_rows_kernel, dim3(lanes, 1), dim3(256), 0, st, ga);      // (row 0: w lnf)
-         HIPCHK(hipGetLastError());
-         if (mfma) hipLaunchKernelGGL(counts_mfma_kernel, dim3(tiles, nq), dim3(256), 0, st, a);
-         else anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(counts_lane_kernel<N()>, dim3(lanes, nq), dim3(256), 0, st, a); });
-         HIPCHK(hipGetLastError());
-         hipLaunchKernelGGL(counts_rows_kernel, dim3(lanes, n_rows), dim3(256), 0, st, a);
-         HIPCHK(hipGetLastError());
-         HIPCHK(hipEventRecord(w.ev1, st));
-         if (lnf) HIPCHK(hipMemcpyAsync(lnf + h0, w.lnf.p, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-         if (site_counts)      // runs of rows that are consecutive on both sides, one strided copy each
-            for (int r0 = 0; r0 < n_rows;) {
-               const int l0 = r0 / nq, q0 = r0 % nq;
-               const long d0 = (long)l0 * n_out + col[q0];
-               int r1 = r0 + 1;
-               while (r1 < n_rows && (long)(r1 / nq) * n_out + col[r1 % nq] == d0 + (r1 - r0)) r1++;
-               HIPCHK(hipMemcpy2DAsync(site_counts + (size_t)d0 * e->n_patt + h0, (size_t)e->n_patt * 8, w.site.p + (size_t)r0 * batch, (size_t)batch * 8, (size_t)nb * 8,
-                                       (size_t)(r1 - r0), hipMemcpyDeviceToHost, st));
-               r0 = r1;
-            }
-         HIPCHK(w.lap(st));
-         counts_info.batches++;
-      }
+   if (int rc = anc_batches(
+          e, w, m, &ga.chunk0, batch, [&](const AncBatch &b) { hipLaunchKernelGGL(mg_mfma_outer_kernel, b.tiles, dim3(256), 0, st, ga); },
+          [&](const AncBatch &b, int pass) { anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(counts_pass_kernel<N()>, b.lanes, dim3(256), 0, st, ga, pass); }); },
+          [&](const AncBatch &b) {
+             const unsigned lanes = b.lanes.x;
+             hipLaunchKernelGGL(counts_scalar_kernel, dim3(lanes), dim3(256), 0, st, ga);
+             HIPCHK(hipGetLastError());
+             hipLaunchKernelGGL(mg_rows_kernel, dim3(lanes, 1), dim3(256), 0, st, ga);      // (row 0: w lnf)
+             HIPCHK(hipGetLastError());
+             if (mfma) hipLaunchKernelGGL(counts_mfma_kernel, dim3(b.tiles.x, nq), dim3(256), 0, st, a);
+             else anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(counts_lane_kernel<N()>, dim3(lanes, nq), dim3(256), 0, st, a); });
+             HIPCHK(hipGetLastError());
+             hipLaunchKernelGGL(counts_rows_kernel, dim3(lanes, n_rows), dim3(256), 0, st, a);
+             HIPCHK(hipGetLastError());
+             return 0;
+          },
+          [&](const AncBatch &b) {
+             if (lnf) HIPCHK(hipMemcpyAsync(lnf + b.h0, w.lnf.p, (size_t)b.nb * 8, hipMemcpyDeviceToHost, st));
+             if (site_counts)      // runs of rows that are consecutive on both sides, one strided copy each
+                for (int r0 = 0; r0 < n_rows;) {
+                   const int l0 = r0 / nq, q0 = r0 % nq;
+                   const long d0 = (long)l0 * n_out + col[q0];
+                   int r1 = r0 + 1;
+                   while (r1 < n_rows && (long)(r1 / nq) * n_out + col[r1 % nq] == d0 + (r1 - r0)) r1++;
+                   HIPCHK(hipMemcpy2DAsync(site_counts + (size_t)d0 * e->n_patt + b.h0, (size_t)e->n_patt * 8, w.site.p + (size_t)r0 * batch, (size_t)batch * 8, (size_t)b.nb * 8,
+                                           (size_t)(r1 - r0), hipMemcpyDeviceToHost, st));
+                   r0 = r1;
+                }
+             return 0;
+          }))
+      return rc;
    std::vector<double> out((size_t)1 + n_rows);
    if (int rc = anc_totals(e, w, w.partial.p, n_chunks, w.out.p, out)) return rc;
    *lnL = out[0];

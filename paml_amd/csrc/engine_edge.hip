@@ -288,11 +288,6 @@ struct EdgeScratch : AncScratch {
    using AncScratch::AncScratch;
    DevBuf<double> PT, OM, ovr_t, f, f1, f2, sig, lnf, g1, g2, partial, out;
    DevBuf<int> rows, ovr_node;
-   ~EdgeScratch()
-   {
-      for (DevBuf<double> *b : {&PT, &OM, &ovr_t, &f, &f1, &f2, &sig, &lnf, &g1, &g2, &partial, &out}) b->release();
-      rows.release(); ovr_node.release();
-   }
 };
 
 }  // namespace
@@ -406,7 +401,7 @@ extern "C" int paml_amd_edge_scores(paml_amd_engine *e, const double *branch, co
    const long n_patt = e->n_patt;
    auto group = [&](int gi) { o.swap0 = gi * cap; o.n_group = std::min(cap, n_rows - o.swap0); };      // groups of `cap` rows in list order
    if (int rc = anc_score_batches(
-          e, w, o, chunk_base, batch, (n_rows + cap - 1) / cap,
+          e, w, o, batch, (n_rows + cap - 1) / cap,
           [&](dim3 lanes, int pass) { anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(nni_lane_kernel<N()>, lanes, dim3(256), 0, st, o, pass); }); },
           [](dim3) {},      // (the present tree's row is combined with the batch's first group)
           [&](int gi, dim3 tiles, dim3 lanes) {

@@ -262,12 +262,12 @@ int setup_streams(paml_amd_engine *e, Eval &c)
       if (int rc = ensure_side_stream(e)) return rc;
    c.ms = c.lane ? e->sb[c.lane - 1] : e->stream;
    if (c.want_pipe && !e->s2) {
-      for (hipEvent_t &ev : e->ev_setread) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      for (DevEvent &ev : e->ev_setread) HIPCHK(ev.ensure(hipEventDisableTiming));
       for (int i = 0; i < paml_amd_engine::NPSET - 1; i++) e->spare[i].id = i + 1;
       HIPCHK(create_engine_stream(&e->s2));
-      HIPCHK(hipEventCreateWithFlags(&e->ev_entry[0], hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&e->ev_entry[1], hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&e->ev_pmat, hipEventDisableTiming));
+      HIPCHK(e->ev_entry[0].ensure(hipEventDisableTiming));
+      HIPCHK(e->ev_entry[1].ensure(hipEventDisableTiming));
+      HIPCHK(e->ev_pmat.ensure(hipEventDisableTiming));
    }
    c.ps = e->stream;
    if (c.pipe) {
@@ -915,8 +915,8 @@ int prepare_slot(paml_amd_engine *e, Eval &c)
    c.slot = (c.side_total || c.offload) ? e->red_slot : 0;
    if (e->comm_stats && !e->st_part[0])
       for (int i = 0; i < paml_amd_engine::NSTAT; i++) {
-         HIPCHK(hipEventCreate(&e->st_part[i])); HIPCHK(hipEventCreate(&e->st_done[i]));
-         HIPCHK(hipEventCreate(&e->st_w0[i])); HIPCHK(hipEventCreate(&e->st_w1[i]));
+         HIPCHK(e->st_part[i].ensure()); HIPCHK(e->st_done[i].ensure());
+         HIPCHK(e->st_w0[i].ensure()); HIPCHK(e->st_w1[i].ensure());
       }
    if (e->comm_stats) e->st_waited[e->st_count % paml_amd_engine::NSTAT] = false;
    DevBuf<double> &dpart = e->part_slot(c.slot);

@@ -50,10 +50,6 @@ namespace {
 struct GradScratch : AncScratch {
    using AncScratch::AncScratch;
    DevBuf<double> dP, PT, num, den, sig, scores, lnf, partial, out;
-   ~GradScratch()
-   {
-      for (DevBuf<double> *b : {&dP, &PT, &num, &den, &sig, &scores, &lnf, &partial, &out}) b->release();
-   }
 };
 
 }  // namespace
@@ -64,14 +60,9 @@ extern "C" int paml_amd_gradient(paml_amd_engine *e, const double *branch, const
    grad_info = AncCallInfo{};
    const char *who = "gradient";
    if (!e || !branch || !lnL || !grad) return fail(e, PAML_AMD_EINVAL, "gradient: null argument");
-   if (int rc = anc_common_checks(e, who)) return rc;
-   if (e->world > 1) return fail(e, PAML_AMD_EUNSUPPORTED, "gradient: one rank only (this engine's communicator has " + std::to_string(e->world) + ")");
-   for (size_t i = 0; i < e->eigen.size(); i++)
-      if (e->eigen[i].kind == PAML_AMD_EIGEN_QMAT)
-         return fail(e, PAML_AMD_EUNSUPPORTED, "gradient: the derivative of a rate-matrix (UNREST) set's P(t) needs a matrix product of its own");
+   if (int rc = anc_begin(e, who, "the derivative of a rate-matrix (UNREST) set's P(t) needs a matrix product of its own")) return rc;
    const TreeDesc &T = e->tree;
-   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, n_tips = e->n_tips, n_int = nn - n_tips;
-   if (nn < 2) return fail(e, PAML_AMD_EINVAL, "gradient: the tree has no branch");
+   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, n_int = nn - e->n_tips;
    const bool mfma = e->kk == KK_MFMA64;
    hipStream_t st = e->stream;
    GradScratch w(grad_info);
@@ -79,23 +70,11 @@ extern "C" int paml_amd_gradient(paml_amd_engine *e, const double *branch, const
    AncMargArgs &m = a.m;
    if (int rc = anc_tree_pack(e, who, w, &m.t)) return rc;
    if (int rc = anc_pmat(e, who, branch, gene_rate, w)) return rc;
-   {
-      const size_t pn = (size_t)G * K * nn;
-      HIPCHK(w.dP.ensure(pn * (mfma ? 4096 : n * n)));
-      if (mfma) HIPCHK(w.PT.ensure(pn * 4096));
-      GradPmatArgs ga{};
-      ga.n = n; ga.K = K; ga.n_nodes = nn; ga.n_tips = n_tips; ga.root = T.root; ga.n_labels = e->n_labels; ga.rate_gs = e->rate_per_gene ? K : 0; ga.mfma = mfma ? 1 : 0;
-      ga.label = e->d_label.p; ga.eigen_of = e->d_eigen_of.p; ga.eigen = e->d_eigen.p;
-      ga.branch = e->d_branch.p; ga.rate = e->d_rate.p; ga.gene_rate = e->d_gene_rate.p; ga.qfactor = e->d_qfactor.p;
-      ga.P = e->d_rowmajor.p; ga.dP = w.dP.p; ga.PT = w.PT.p;
-      hipLaunchKernelGGL(grad_pmat_kernel, dim3(nn, G * K), dim3(256), 0, st, ga);
-      HIPCHK(hipGetLastError());
-   }
+   if (int rc = grad_dpmat(e, w.dP, nullptr, w.PT)) return rc;
    if (int rc = anc_pmat_wait(e, w)) return rc;
    e->pmat_valid = true;      // (d_rowmajor holds every branch's P(t) in the tree's own orientation, as after the joint reconstruction)
 
-   const std::vector<long> chunk_base = anc_chunk_base(e);
-   const long n_chunks = chunk_base[G];
+   const long n_chunks = anc_chunk_base(e)[G];
    HIPCHK(w.partial.ensure((size_t)(nn + 1) * std::max<long>(n_chunks, 1)));
    HIPCHK(w.out.ensure((size_t)nn + 1));
 
@@ -112,35 +91,22 @@ extern "C" int paml_amd_gradient(paml_amd_engine *e, const double *branch, const
    a.scores = w.scores.p; a.lnf = w.lnf.p; a.partial = w.partial.p; a.n_chunks = n_chunks;
    a.ref_node = T.sons[T.sons_ptr[T.root]];
    const long n_patt = e->n_patt;
-   for (int g = 0; g < G; g++)
-      for (long h0 = e->gene_off[g]; h0 < e->gene_off[g + 1]; h0 += batch) {
-         const long nb = std::min<long>(batch, e->gene_off[g + 1] - h0);
-         m.gene = g; m.h0 = h0; m.nb = nb;
-         a.chunk0 = chunk_base[g] + (h0 - e->gene_off[g]) / GRAD_CHUNK;
-         HIPCHK(hipEventRecord(w.ev0, st));
-         if (mfma) {
-            const dim3 grid((unsigned)((nb + ANC_TILE - 1) / ANC_TILE), K);
-            hipLaunchKernelGGL(anc_mfma_kernel, grid, dim3(256), 0, st, m, 0);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(grad_mfma_kernel, grid, dim3(256), 0, st, a);
-            HIPCHK(hipGetLastError());
-         }
-         else
-            for (int pass = 0; pass < 2; pass++) {
-               anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(grad_lane_kernel<N()>, dim3((unsigned)((nb + 255) / 256), K), dim3(256), 0, st, a, pass); });
-               HIPCHK(hipGetLastError());
-            }
-         hipLaunchKernelGGL(grad_combine_kernel, dim3((unsigned)((nb + 255) / 256), nn + 1), dim3(256), 0, st, a);
-         HIPCHK(hipGetLastError());
-         HIPCHK(hipEventRecord(w.ev1, st));
-         // the batch's rows to the caller's [n_nodes][n_patt]: one plain copy per node
-         if (scores)
-            for (int v = 0; v < nn; v++)
-               HIPCHK(hipMemcpyAsync(scores + (size_t)v * n_patt + h0, w.scores.p + (size_t)v * batch, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-         if (lnf) HIPCHK(hipMemcpyAsync(lnf + h0, w.lnf.p, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-         HIPCHK(w.lap(st));
-         grad_info.batches++;
-      }
+   if (int rc = anc_batches(
+          e, w, m, &a.chunk0, batch, [&](const AncBatch &b) { hipLaunchKernelGGL(grad_mfma_kernel, b.tiles, dim3(256), 0, st, a); },
+          [&](const AncBatch &b, int pass) { anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(grad_lane_kernel<N()>, b.lanes, dim3(256), 0, st, a, pass); }); },
+          [&](const AncBatch &b) {
+             hipLaunchKernelGGL(grad_combine_kernel, dim3(b.lanes.x, nn + 1), dim3(256), 0, st, a);
+             HIPCHK(hipGetLastError());
+             return 0;
+          },
+          [&](const AncBatch &b) {      // the batch's rows to the caller's [n_nodes][n_patt]: one plain copy per node
+             if (scores)
+                for (int v = 0; v < nn; v++)
+                   HIPCHK(hipMemcpyAsync(scores + (size_t)v * n_patt + b.h0, w.scores.p + (size_t)v * batch, (size_t)b.nb * 8, hipMemcpyDeviceToHost, st));
+             if (lnf) HIPCHK(hipMemcpyAsync(lnf + b.h0, w.lnf.p, (size_t)b.nb * 8, hipMemcpyDeviceToHost, st));
+             return 0;
+          }))
+      return rc;
    std::vector<double> out((size_t)nn + 1);
    if (int rc = anc_totals(e, w, w.partial.p, n_chunks, w.out.p, out)) return rc;
    for (int v = 0; v < nn; v++) grad[v] = v == T.root ? 0.0 : out[v];

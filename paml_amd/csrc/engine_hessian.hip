@@ -129,11 +129,6 @@ struct HessScratch : AncScratch {
    using AncScratch::AncScratch;
    DevBuf<double> dP, d2P, PT, num, den, cur, sig, lnf, scores, partial, out, Lp, Ap, SLp, SAp, mm, msig, part, total;
    DevBuf<int> plan;
-   ~HessScratch()
-   {
-      for (DevBuf<double> *b : {&dP, &d2P, &PT, &num, &den, &cur, &sig, &lnf, &scores, &partial, &out, &Lp, &Ap, &SLp, &SAp, &mm, &msig, &part, &total}) b->release();
-      plan.release();
-   }
 };
 
 }  // namespace
@@ -147,14 +142,9 @@ extern "C" int paml_amd_hessian(paml_amd_engine *e, const double *branch, const 
    if (!e || !branch || !lnL || !grad || !hess) return fail(e, PAML_AMD_EINVAL, "hessian: null argument");
    if (!(e->have_tips && e->have_tree && e->have_pi && e->have_classes) || e->eigen.empty())
       return fail(e, PAML_AMD_EINVAL, "hessian: called before set_tips/set_tree/set_pi/set_classes/set_eigen");
-   if (int rc = anc_common_checks(e, who)) return rc;
-   if (e->world > 1) return fail(e, PAML_AMD_EUNSUPPORTED, "hessian: one rank only (this engine's communicator has " + std::to_string(e->world) + ")");
-   for (size_t i = 0; i < e->eigen.size(); i++)
-      if (e->eigen[i].kind == PAML_AMD_EIGEN_QMAT)
-         return fail(e, PAML_AMD_EUNSUPPORTED, "hessian: the derivatives of a rate-matrix (UNREST) set's P(t) need matrix products of their own");
+   if (int rc = anc_begin(e, who, "the derivatives of a rate-matrix (UNREST) set's P(t) need matrix products of their own")) return rc;
    const TreeDesc &T = e->tree;
    const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, n_tips = e->n_tips, n_int = nn - n_tips;
-   if (nn < 2) return fail(e, PAML_AMD_EINVAL, "hessian: the tree has no branch");
    if (nn > 65535) return fail(e, PAML_AMD_EUNSUPPORTED, "hessian: more than 65535 nodes");
    if ((nodes == nullptr) != (n_list == 0) || n_list < 0) return fail(e, PAML_AMD_EINVAL, "hessian: nodes and n_list do not agree (NULL, 0: every node)");
    const HessTreeView view{n_tips, nn, T.root, T.sons_ptr.data(), T.sons.data()};
@@ -180,19 +170,7 @@ extern "C" int paml_amd_hessian(paml_amd_engine *e, const double *branch, const 
    AncMargArgs &m = ga.m;
    if (int rc = anc_tree_pack(e, who, w, &m.t)) return rc;
    if (int rc = anc_pmat(e, who, branch, gene_rate, w)) return rc;
-   {
-      const size_t pn = (size_t)G * K * nn, each = mfma ? 4096 : (size_t)n * n;
-      HIPCHK(w.dP.ensure(pn * each));
-      HIPCHK(w.d2P.ensure(pn * each));
-      if (mfma) HIPCHK(w.PT.ensure(pn * 4096));
-      GradPmatArgs pa{};
-      pa.n = n; pa.K = K; pa.n_nodes = nn; pa.n_tips = n_tips; pa.root = T.root; pa.n_labels = e->n_labels; pa.rate_gs = e->rate_per_gene ? K : 0; pa.mfma = mfma ? 1 : 0;
-      pa.label = e->d_label.p; pa.eigen_of = e->d_eigen_of.p; pa.eigen = e->d_eigen.p;
-      pa.branch = e->d_branch.p; pa.rate = e->d_rate.p; pa.gene_rate = e->d_gene_rate.p; pa.qfactor = e->d_qfactor.p;
-      pa.P = e->d_rowmajor.p; pa.dP = w.dP.p; pa.PT = w.PT.p; pa.d2P = w.d2P.p;
-      hipLaunchKernelGGL(curv_pmat_kernel, dim3(nn, G * K), dim3(256), 0, st, pa);
-      HIPCHK(hipGetLastError());
-   }
+   if (int rc = grad_dpmat(e, w.dP, &w.d2P, w.PT)) return rc;
    const size_t o_steps = plan.sources.size(), o_factors = o_steps + plan.steps.size(), o_pairs = o_factors + plan.factors.size();
    {
       std::vector<int> pack(plan.sources);
@@ -205,8 +183,7 @@ extern "C" int paml_amd_hessian(paml_amd_engine *e, const double *branch, const 
    }
    e->pmat_valid = true;      // (d_rowmajor holds every branch's P(t) in the tree's own orientation, as after paml_amd_gradient)
 
-   const std::vector<long> chunk_base = anc_chunk_base(e);
-   const long n_chunks = chunk_base[G];
+   const long n_chunks = anc_chunk_base(e)[G];
    const int rows = 2 * nn + 1;      // w s_v, w c_v, w lnf: the curvature's rows
    HIPCHK(w.partial.ensure((size_t)rows * std::max<long>(n_chunks, 1)));
    HIPCHK(w.out.ensure((size_t)rows));
@@ -249,46 +226,34 @@ extern "C" int paml_amd_hessian(paml_amd_engine *e, const double *branch, const 
    ga.ref_node = T.sons[T.sons_ptr[T.root]];
    a.sources = w.plan.p; a.steps = w.plan.p + o_steps; a.factors = w.plan.p + o_factors; a.pairs = w.plan.p + o_pairs;
    a.cap = cap; a.Lp = w.Lp.p; a.Ap = w.Ap.p; a.SLp = w.SLp.p; a.SAp = w.SAp.p; a.mm = w.mm.p; a.msig = w.msig.p; a.part = w.part.p; a.total = w.total.p;
-   for (int g = 0; g < G; g++)
-      for (long h0 = e->gene_off[g]; h0 < e->gene_off[g + 1]; h0 += batch) {
-         const long nb = std::min<long>(batch, e->gene_off[g + 1] - h0);
-         m.gene = g; m.h0 = h0; m.nb = nb;
-         ga.chunk0 = chunk_base[g] + (h0 - e->gene_off[g]) / GRAD_CHUNK;
-         const dim3 tiles((unsigned)((nb + ANC_TILE - 1) / ANC_TILE), K), lanes((unsigned)((nb + 255) / 256), K);
-         HIPCHK(hipEventRecord(w.ev0, st));
-         if (mfma) {
-            hipLaunchKernelGGL(anc_mfma_kernel, tiles, dim3(256), 0, st, m, 0);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(curv_mfma_kernel, tiles, dim3(256), 0, st, ga);
-            HIPCHK(hipGetLastError());
-         }
-         else
-            for (int pass = 0; pass < 2; pass++) {
-               anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(curv_lane_kernel<N()>, lanes, dim3(256), 0, st, ga, pass); });
-               HIPCHK(hipGetLastError());
-            }
-         hipLaunchKernelGGL(curv_combine_kernel, dim3(lanes.x, rows), dim3(256), 0, st, ga);
-         HIPCHK(hipGetLastError());
-         hipLaunchKernelGGL(hess_score_kernel, dim3(lanes.x, nn), dim3(256), 0, st, a);
-         HIPCHK(hipGetLastError());
-         for (int gi = 0; gi < n_groups; gi++) {
-            const int is0 = group_first[gi], is1 = group_first[gi + 1];
-            a.source0 = is0; a.n_sources = is1 - is0;
-            a.row0 = plan.sources[HESS_SOURCE_INTS * is0 + 3];
-            a.n_group = (is1 < plan.n_sources() ? plan.sources[HESS_SOURCE_INTS * is1 + 3] : n_pairs) - a.row0;
-            if (mfma) hipLaunchKernelGGL(hess_mfma_kernel, tiles, dim3(256), 0, st, a);
-            else anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(hess_lane_kernel<N()>, lanes, dim3(256), 0, st, a); });
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(hess_combine_kernel, dim3(lanes.x, a.n_group), dim3(256), 0, st, a);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(hess_total_kernel, dim3((unsigned)((a.n_group + 255) / 256)), dim3(256), 0, st, a, (int)((nb + GRAD_CHUNK - 1) / GRAD_CHUNK));
-            HIPCHK(hipGetLastError());
-         }
-         HIPCHK(hipEventRecord(w.ev1, st));
-         if (lnf) HIPCHK(hipMemcpyAsync(lnf + h0, w.lnf.p, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-         HIPCHK(w.lap(st));
-         hess_info.batches++;
-      }
+   if (int rc = anc_batches(
+          e, w, m, &ga.chunk0, batch, [&](const AncBatch &b) { hipLaunchKernelGGL(curv_mfma_kernel, b.tiles, dim3(256), 0, st, ga); },
+          [&](const AncBatch &b, int pass) { anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(curv_lane_kernel<N()>, b.lanes, dim3(256), 0, st, ga, pass); }); },
+          [&](const AncBatch &b) {
+             hipLaunchKernelGGL(curv_combine_kernel, dim3(b.lanes.x, rows), dim3(256), 0, st, ga);
+             HIPCHK(hipGetLastError());
+             hipLaunchKernelGGL(hess_score_kernel, dim3(b.lanes.x, nn), dim3(256), 0, st, a);
+             HIPCHK(hipGetLastError());
+             for (int gi = 0; gi < n_groups; gi++) {
+                const int is0 = group_first[gi], is1 = group_first[gi + 1];
+                a.source0 = is0; a.n_sources = is1 - is0;
+                a.row0 = plan.sources[HESS_SOURCE_INTS * is0 + 3];
+                a.n_group = (is1 < plan.n_sources() ? plan.sources[HESS_SOURCE_INTS * is1 + 3] : n_pairs) - a.row0;
+                if (mfma) hipLaunchKernelGGL(hess_mfma_kernel, b.tiles, dim3(256), 0, st, a);
+                else anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(hess_lane_kernel<N()>, b.lanes, dim3(256), 0, st, a); });
+                HIPCHK(hipGetLastError());
+                hipLaunchKernelGGL(hess_combine_kernel, dim3(b.lanes.x, a.n_group), dim3(256), 0, st, a);
+                HIPCHK(hipGetLastError());
+                hipLaunchKernelGGL(hess_total_kernel, dim3((unsigned)((a.n_group + 255) / 256)), dim3(256), 0, st, a, (int)((b.nb + GRAD_CHUNK - 1) / GRAD_CHUNK));
+                HIPCHK(hipGetLastError());
+             }
+             return 0;
+          },
+          [&](const AncBatch &b) {
+             if (lnf) HIPCHK(hipMemcpyAsync(lnf + b.h0, w.lnf.p, (size_t)b.nb * 8, hipMemcpyDeviceToHost, st));
+             return 0;
+          }))
+      return rc;
    std::vector<double> out((size_t)rows), total((size_t)std::max(n_pairs, 1));
    HIPCHK(hipMemcpyAsync(total.data(), w.total.p, total.size() * 8, hipMemcpyDeviceToHost, st));
    if (int rc = anc_totals(e, w, w.partial.p, n_chunks, w.out.p, out)) return rc;

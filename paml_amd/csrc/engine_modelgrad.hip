@@ -398,10 +398,6 @@ namespace {
 struct ModelGradScratch : AncScratch {
    using AncScratch::AncScratch;
    DevBuf<double> PT, H, den, sig, coef, R, SR, croot, rows, lnf, partial, out, carry, Wpart, W, GA, geff, gA;
-   ~ModelGradScratch()
-   {
-      for (DevBuf<double> *b : {&PT, &H, &den, &sig, &coef, &R, &SR, &croot, &rows, &lnf, &partial, &out, &carry, &Wpart, &W, &GA, &geff, &gA}) b->release();
-   }
 };
 
 }  // namespace
@@ -413,14 +409,9 @@ extern "C" int paml_amd_model_gradient(paml_amd_engine *e, const double *branch,
    mg_info = AncCallInfo{};
    const char *who = "model_gradient";
    if (!e || !branch || !lnL) return fail(e, PAML_AMD_EINVAL, "model_gradient: null argument");
-   if (int rc = anc_common_checks(e, who)) return rc;
-   if (e->world > 1) return fail(e, PAML_AMD_EUNSUPPORTED, "model_gradient: one rank only (this engine's communicator has " + std::to_string(e->world) + ")");
-   for (size_t i = 0; i < e->eigen.size(); i++)
-      if (e->eigen[i].kind == PAML_AMD_EIGEN_QMAT)
-         return fail(e, PAML_AMD_EUNSUPPORTED, "model_gradient: a rate-matrix (UNREST) set has no spectral form to pull the derivative back through");
+   if (int rc = anc_begin(e, who, "a rate-matrix (UNREST) set has no spectral form to pull the derivative back through")) return rc;
    const TreeDesc &T = e->tree;
-   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, n_tips = e->n_tips, n_int = nn - n_tips, n_eigen = (int)e->eigen.size();
-   if (nn < 2) return fail(e, PAML_AMD_EINVAL, "model_gradient: the tree has no branch");
+   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, n_int = nn - e->n_tips, n_eigen = (int)e->eigen.size();
    const bool mfma = e->kk == KK_MFMA64;
    hipStream_t st = e->stream;
    ModelGradScratch w(mg_info);
@@ -437,7 +428,7 @@ extern "C" int paml_amd_model_gradient(paml_amd_engine *e, const double *branch,
    if (int rc = anc_pmat_wait(e, w)) return rc;
    e->pmat_valid = true;      // (d_rowmajor holds every branch's P(t) in the tree's own orientation, as after paml_amd_gradient)
 
-   const std::vector<long> chunk_base = anc_chunk_base(e);
+   const std::vector<long> chunk_base = anc_chunk_base(e);      // (also read below: the genes' ranges of chunks, for g_pi)
    const long n_chunks = chunk_base[G];
    const int n_rows = 1 + K + n, ns = mfma ? 64 : n, wn = mfma ? 4096 : n * n;
    const long per_seg = (long)K * nn * wn;
@@ -468,45 +459,42 @@ extern "C" int paml_amd_model_gradient(paml_amd_engine *e, const double *branch,
    a.PT = w.PT.p; a.H = w.H.p; a.den = w.den.p; a.sig = w.sig.p; a.coef = w.coef.p; a.R = w.R.p; a.SR = w.SR.p; a.croot = w.croot.p; a.rows = w.rows.p;
    a.lnf = w.lnf.p; a.weights = e->d_weights.p; a.partial = w.partial.p; a.n_chunks = n_chunks; a.ref_node = T.sons[T.sons_ptr[T.root]];
    a.ld = mfma ? 64 : n; a.wn = wn; a.Wpart = w.Wpart.p;
-   int flip = 0;
-   for (int g = 0; g < G; g++)
-      for (long h0 = e->gene_off[g]; h0 < e->gene_off[g + 1]; h0 += batch) {
-         const long nb = std::min<long>(batch, e->gene_off[g + 1] - h0);
-         m.gene = g; m.h0 = h0; m.nb = nb;
-         a.chunk0 = chunk_base[g] + (h0 - e->gene_off[g]) / GRAD_CHUNK;
-         a.off0 = h0 - e->gene_off[g]; a.gene_len = e->gene_off[g + 1] - e->gene_off[g];
-         a.carry_in = w.carry.p + (size_t)flip * per_seg; a.carry_out = w.carry.p + (size_t)(flip ^ 1) * per_seg;
-         flip ^= 1;
-         const int n_segs = (int)((a.off0 + nb - 1) / MODELGRAD_SEG - a.off0 / MODELGRAD_SEG + 1);
-         const int n_finished = mg_segment(a, n_segs - 1).finished ? n_segs : n_segs - 1;
-         HIPCHK(hipEventRecord(w.ev0, st));
-         if (mfma) {
-            const dim3 grid((unsigned)((nb + ANC_TILE - 1) / ANC_TILE), K);
-            hipLaunchKernelGGL(anc_mfma_kernel, grid, dim3(256), 0, st, m, 0);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(mg_mfma_outer_kernel, grid, dim3(256), 0, st, a);
-            HIPCHK(hipGetLastError());
-         }
-         else
-            for (int pass = 0; pass < 2; pass++) {
-               anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(mg_lane_kernel<N()>, dim3((unsigned)((nb + 255) / 256), K), dim3(256), 0, st, a, pass); });
-               HIPCHK(hipGetLastError());
-            }
-         hipLaunchKernelGGL(mg_coef_kernel, dim3((unsigned)((nb + 255) / 256), nn + 1), dim3(256), 0, st, a);
-         HIPCHK(hipGetLastError());
-         hipLaunchKernelGGL(mg_rows_kernel, dim3((unsigned)((nb + 255) / 256), n_rows), dim3(256), 0, st, a);
-         HIPCHK(hipGetLastError());
-         if (mfma) hipLaunchKernelGGL(mg_w_mfma_kernel, dim3(n_segs, K * nn), dim3(256), 0, st, a);
-         else anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(mg_w_lane_kernel<N()>, dim3(n_segs, K * nn), dim3(64), 0, st, a); });
-         HIPCHK(hipGetLastError());
-         if (n_finished > 0) {
-            hipLaunchKernelGGL(mg_add_kernel, dim3((unsigned)((per_seg + 255) / 256)), dim3(256), 0, st, w.W.p + (size_t)g * per_seg, (const double *)w.Wpart.p, per_seg, n_finished);
-            HIPCHK(hipGetLastError());
-         }
-         HIPCHK(hipEventRecord(w.ev1, st));
-         HIPCHK(w.lap(st));
-         mg_info.batches++;
-      }
+   // the batch's place in its gene, the carry's two halves and the segments it touches: set by whichever launch comes first of those whose
+   // arguments hold them
+   int flip = 0, n_segs = 0, n_finished = 0;
+   auto place = [&](const AncBatch &b) {
+      a.off0 = b.h0 - e->gene_off[b.gene]; a.gene_len = e->gene_off[b.gene + 1] - e->gene_off[b.gene];
+      a.carry_in = w.carry.p + (size_t)flip * per_seg; a.carry_out = w.carry.p + (size_t)(flip ^ 1) * per_seg;
+      flip ^= 1;
+      n_segs = (int)((a.off0 + b.nb - 1) / MODELGRAD_SEG - a.off0 / MODELGRAD_SEG + 1);
+      n_finished = mg_segment(a, n_segs - 1).finished ? n_segs : n_segs - 1;
+   };
+   if (int rc = anc_batches(
+          e, w, m, &a.chunk0, batch,
+          [&](const AncBatch &b) {
+             place(b);
+             hipLaunchKernelGGL(mg_mfma_outer_kernel, b.tiles, dim3(256), 0, st, a);
+          },
+          [&](const AncBatch &b, int pass) {
+             if (pass == 0) place(b);
+             anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(mg_lane_kernel<N()>, b.lanes, dim3(256), 0, st, a, pass); });
+          },
+          [&](const AncBatch &b) {
+             hipLaunchKernelGGL(mg_coef_kernel, dim3(b.lanes.x, nn + 1), dim3(256), 0, st, a);
+             HIPCHK(hipGetLastError());
+             hipLaunchKernelGGL(mg_rows_kernel, dim3(b.lanes.x, n_rows), dim3(256), 0, st, a);
+             HIPCHK(hipGetLastError());
+             if (mfma) hipLaunchKernelGGL(mg_w_mfma_kernel, dim3(n_segs, K * nn), dim3(256), 0, st, a);
+             else anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(mg_w_lane_kernel<N()>, dim3(n_segs, K * nn), dim3(64), 0, st, a); });
+             HIPCHK(hipGetLastError());
+             if (n_finished > 0) {
+                hipLaunchKernelGGL(mg_add_kernel, dim3((unsigned)((per_seg + 255) / 256)), dim3(256), 0, st, w.W.p + (size_t)b.gene * per_seg, (const double *)w.Wpart.p, per_seg, n_finished);
+                HIPCHK(hipGetLastError());
+             }
+             return 0;
+          },
+          [](const AncBatch &) { return 0; }))      // (nothing is copied out per batch)
+      return rc;
 
    // the pull-back through every branch's spectral form, the sets' sums, the scalar rows' totals
    ModelGradPullArgs pa{};

@@ -206,11 +206,6 @@ struct NniScratch : AncScratch {
    using AncScratch::AncScratch;
    DevBuf<double> PT, f, sig, lnf, partial, out;
    DevBuf<int> swaps;
-   ~NniScratch()
-   {
-      for (DevBuf<double> *b : {&PT, &f, &sig, &lnf, &partial, &out}) b->release();
-      swaps.release();
-   }
 };
 
 }  // namespace
@@ -288,7 +283,7 @@ extern "C" int paml_amd_nni_scores(paml_amd_engine *e, const double *branch, con
    const long n_patt = e->n_patt;
    auto group = [&](int gi) { a.swap0 = gi * cap; a.n_group = std::min(cap, n_swaps - a.swap0); };      // groups of `cap` swaps in list order
    if (int rc = anc_score_batches(
-          e, w, a, chunk_base, batch, (n_swaps + cap - 1) / cap,
+          e, w, a, batch, (n_swaps + cap - 1) / cap,
           [&](dim3 lanes, int pass) { anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(nni_lane_kernel<N()>, lanes, dim3(256), 0, st, a, pass); }); },
           [](dim3) {},      // (the present tree's row is combined with the batch's first group)
           [&](int gi, dim3 tiles, dim3 lanes) {

@@ -34,8 +34,6 @@ struct paml_amd_pairset {
 
    ~paml_amd_pairset()
    {
-      d_seq.release(); d_rc.release(); d_sweeps.release(); d_flags.release(); d_fp.release(); d_ls.release(); d_pi.release();
-      d_uvr.release(); d_vals.release(); d_pi_slot.release(); d_scale.release(); d_lnl.release(); d_ptr.release(); d_dec.release(); d_elem.release();
       if (h_dec) (void)hipHostFree(h_dec);
       if (h_elem) (void)hipHostFree(h_elem);
       if (h_lnl) (void)hipHostFree(h_lnl);

@@ -113,11 +113,6 @@ struct PlaceScratch : AncScratch {
    DevBuf<double> PT, Pup, Pdn, PTup, pint_dn, ptip_dn, Ppend, ptip_pend, f0, sig0, lnf0, f, sig, lnf, partial, out;
    DevBuf<int> edges, lab;
    DevBuf<unsigned char> qz;
-   ~PlaceScratch()
-   {
-      for (DevBuf<double> *b : {&PT, &Pup, &Pdn, &PTup, &pint_dn, &ptip_dn, &Ppend, &ptip_pend, &f0, &sig0, &lnf0, &f, &sig, &lnf, &partial, &out}) b->release();
-      edges.release(); lab.release(); qz.release();
-   }
 };
 
 }  // namespace
@@ -253,7 +248,7 @@ extern "C" int paml_amd_placement_scores(paml_amd_engine *e, const double *branc
    a.f = w.f.p; a.sig = w.sig.p; a.lnf = w.lnf.p; a.partial = w.partial.p;
    auto group = [&](int gi) { a.edge0 = gi * cap; a.n_group = std::min(cap, n_edges - a.edge0); };      // groups of `cap` edges in list order
    if (int rc = anc_score_batches(
-          e, w, o, chunk_base, batch, (n_edges + cap - 1) / cap,
+          e, w, o, batch, (n_edges + cap - 1) / cap,
           [&](dim3 lanes, int pass) { anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(nni_lane_kernel<N()>, lanes, dim3(256), 0, st, o, pass); }); },
           [&](dim3 lanes) {
              a.edge0 = 0; a.n_group = 0;

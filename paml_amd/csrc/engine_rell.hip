@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/paml_amd.h"
+#include "dev_buf.h"
 #include "kernels_rell.h"
 
 using namespace paml_amd;
@@ -84,66 +85,57 @@ extern "C" int paml_amd_rell_replicates(int n_trees, int n_patt, const double *w
    if (batch > n_rep) batch = n_rep;
    if (batch < 1) batch = 1;
 
-   double *d_lnf = nullptr, *d_tab = nullptr, *d_part = nullptr, *d_rep = nullptr;
-   int *d_w = nullptr, *d_end = nullptr, *d_sums = nullptr, *d_site = nullptr, *d_soff = nullptr;
-   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-   int rc = 0;
-#define RELLCHK(call) do { if ((call) != hipSuccess) { rc = rell_fail(PAML_AMD_EHIP, "rell_replicates: HIP error at line %ld", __LINE__); goto done; } } while (0)
-#define RELLMEM(call, what) do { if ((call) != hipSuccess) { (void)hipGetLastError(); rc = rell_fail(PAML_AMD_ENOMEM, "rell_replicates: no device memory for " what); goto done; } } while (0)
-   RELLMEM(hipMalloc(&d_tab, (size_t)n_patt * t_pad * sizeof(double)), "the lnf table");
-   RELLMEM(hipMalloc(&d_site, (size_t)ls * sizeof(int)), "the site list");
-   RELLMEM(hipMalloc(&d_w, (size_t)n_patt * sizeof(int)), "the weights");
-   RELLMEM(hipMalloc(&d_end, (size_t)n_patt * sizeof(int)), "the weights");
-   RELLMEM(hipMalloc(&d_sums, (size_t)n_tiles * sizeof(int)), "the weights");
-   RELLMEM(hipMalloc(&d_soff, ((size_t)n_genes + 1) * sizeof(int)), "the gene offsets");
-   RELLMEM(hipMalloc(&d_lnf, (size_t)n_patt * n_trees * sizeof(double)), "lnf");
-   RELLCHK(hipMemcpy(d_lnf, lnf, (size_t)n_patt * n_trees * sizeof(double), hipMemcpyHostToDevice));
-   RELLCHK(hipMemcpy(d_w, wi.data(), (size_t)n_patt * sizeof(int), hipMemcpyHostToDevice));
-   RELLCHK(hipMemcpy(d_soff, soff.data(), ((size_t)n_genes + 1) * sizeof(int), hipMemcpyHostToDevice));
-   hipLaunchKernelGGL(rell_transpose, dim3((n_patt + RELL_THREADS - 1) / RELL_THREADS), dim3(RELL_THREADS), 0, 0, d_lnf, n_trees, n_patt, t_pad, d_tab);
-   hipLaunchKernelGGL(rell_tile_sums, dim3(n_tiles), dim3(RELL_THREADS), 0, 0, d_w, n_patt, d_sums);
-   hipLaunchKernelGGL(rell_scan_tiles, dim3(1), dim3(1024), 0, 0, d_sums, n_tiles);
-   hipLaunchKernelGGL(rell_tile_scan, dim3(n_tiles), dim3(RELL_THREADS), 0, 0, d_w, d_sums, n_patt, d_end);
-   hipLaunchKernelGGL(rell_fill_sites, dim3((unsigned)((ls + RELL_THREADS - 1) / RELL_THREADS)), dim3(RELL_THREADS), 0, 0, d_end, n_patt, (int)ls, d_site);
+   DevBuf<double> d_lnf, d_tab, d_part, d_rep;
+   DevBuf<int> d_w, d_end, d_sums, d_site, d_soff;
+   DevEvent ev0, ev1;
+#define RELLCHK(call) do { if ((call) != hipSuccess) return rell_fail(PAML_AMD_EHIP, "rell_replicates: HIP error at line %ld", __LINE__); } while (0)
+#define RELLMEM(call, what) do { if ((call) != hipSuccess) { (void)hipGetLastError(); return rell_fail(PAML_AMD_ENOMEM, "rell_replicates: no device memory for " what); } } while (0)
+   RELLMEM(d_tab.ensure((size_t)n_patt * t_pad), "the lnf table");
+   RELLMEM(d_site.ensure((size_t)ls), "the site list");
+   RELLMEM(d_w.ensure((size_t)n_patt), "the weights");
+   RELLMEM(d_end.ensure((size_t)n_patt), "the weights");
+   RELLMEM(d_sums.ensure((size_t)n_tiles), "the weights");
+   RELLMEM(d_soff.ensure((size_t)n_genes + 1), "the gene offsets");
+   RELLMEM(d_lnf.ensure((size_t)n_patt * n_trees), "lnf");
+   RELLCHK(hipMemcpy(d_lnf.p, lnf, (size_t)n_patt * n_trees * sizeof(double), hipMemcpyHostToDevice));
+   RELLCHK(hipMemcpy(d_w.p, wi.data(), (size_t)n_patt * sizeof(int), hipMemcpyHostToDevice));
+   RELLCHK(hipMemcpy(d_soff.p, soff.data(), ((size_t)n_genes + 1) * sizeof(int), hipMemcpyHostToDevice));
+   hipLaunchKernelGGL(rell_transpose, dim3((n_patt + RELL_THREADS - 1) / RELL_THREADS), dim3(RELL_THREADS), 0, 0, d_lnf.p, n_trees, n_patt, t_pad, d_tab.p);
+   hipLaunchKernelGGL(rell_tile_sums, dim3(n_tiles), dim3(RELL_THREADS), 0, 0, d_w.p, n_patt, d_sums.p);
+   hipLaunchKernelGGL(rell_scan_tiles, dim3(1), dim3(1024), 0, 0, d_sums.p, n_tiles);
+   hipLaunchKernelGGL(rell_tile_scan, dim3(n_tiles), dim3(RELL_THREADS), 0, 0, d_w.p, d_sums.p, n_patt, d_end.p);
+   hipLaunchKernelGGL(rell_fill_sites, dim3((unsigned)((ls + RELL_THREADS - 1) / RELL_THREADS)), dim3(RELL_THREADS), 0, 0, d_end.p, n_patt, (int)ls, d_site.p);
    RELLCHK(hipGetLastError());
    RELLCHK(hipDeviceSynchronize());
-   (void)hipFree(d_lnf); d_lnf = nullptr;
+   d_lnf.release();
    // the workspace: halve the batch until it fits
    for (;;) {
-      if (hipMalloc(&d_part, (size_t)batch * n_chunks * t_pad * sizeof(double)) == hipSuccess &&
-          hipMalloc(&d_rep, (size_t)batch * n_trees * sizeof(double)) == hipSuccess) break;
+      if (d_part.ensure((size_t)batch * n_chunks * t_pad) == hipSuccess && d_rep.ensure((size_t)batch * n_trees) == hipSuccess) break;
       (void)hipGetLastError();
-      (void)hipFree(d_part); d_part = nullptr;
-      if (batch == 1) { rc = rell_fail(PAML_AMD_ENOMEM, "rell_replicates: no device memory for the chunk sums of one replicate"); goto done; }
+      d_part.release();
+      if (batch == 1) return rell_fail(PAML_AMD_ENOMEM, "rell_replicates: no device memory for the chunk sums of one replicate");
       batch = (batch + 1) / 2;
    }
-   RELLCHK(hipEventCreate(&ev0)); RELLCHK(hipEventCreate(&ev1));
+   RELLCHK(ev0.ensure()); RELLCHK(ev1.ensure());
    for (long r0 = 0; r0 < n_rep; r0 += batch) {
       const long nb = n_rep - r0 < batch ? n_rep - r0 : batch;
       RellArgs a{};
-      a.tab = d_tab; a.site = d_site; a.soff = d_soff; a.part = d_part; a.seed = seed;
+      a.tab = d_tab.p; a.site = d_site.p; a.soff = d_soff.p; a.part = d_part.p; a.seed = seed;
       a.ls = (int)ls; a.n_genes = n_genes; a.n_chunks = n_chunks; a.t_pad = t_pad; a.rep0 = (int)r0; a.n_items = nb * n_chunks;
       RELLCHK(hipEventRecord(ev0, 0));
       const dim3 grid((unsigned)((a.n_items + RELL_THREADS / 64 - 1) / (RELL_THREADS / 64)), (unsigned)n_tb);
       if (tb == 2) hipLaunchKernelGGL(rell_chunk_sums<2>, grid, dim3(RELL_THREADS), 0, 0, a);
       else if (tb == 4) hipLaunchKernelGGL(rell_chunk_sums<4>, grid, dim3(RELL_THREADS), 0, 0, a);
       else hipLaunchKernelGGL(rell_chunk_sums<8>, grid, dim3(RELL_THREADS), 0, 0, a);
-      hipLaunchKernelGGL(rell_sum_chunks, dim3((unsigned)((nb * n_trees + RELL_THREADS - 1) / RELL_THREADS)), dim3(RELL_THREADS), 0, 0, d_part, (int)nb, n_chunks,
-                         t_pad, n_trees, d_rep);
+      hipLaunchKernelGGL(rell_sum_chunks, dim3((unsigned)((nb * n_trees + RELL_THREADS - 1) / RELL_THREADS)), dim3(RELL_THREADS), 0, 0, d_part.p, (int)nb, n_chunks,
+                         t_pad, n_trees, d_rep.p);
       RELLCHK(hipGetLastError());
       RELLCHK(hipEventRecord(ev1, 0));
-      RELLCHK(hipMemcpy(rep + (size_t)r0 * n_trees, d_rep, (size_t)nb * n_trees * sizeof(double), hipMemcpyDeviceToHost));
+      RELLCHK(hipMemcpy(rep + (size_t)r0 * n_trees, d_rep.p, (size_t)nb * n_trees * sizeof(double), hipMemcpyDeviceToHost));
       { float ms = 0; RELLCHK(hipEventElapsedTime(&ms, ev0, ev1)); rell_last_kernel_ms += ms; }
       rell_last_batches++;
    }
-done:
 #undef RELLCHK
 #undef RELLMEM
-   {
-      void *bufs[] = {d_lnf, d_tab, d_part, d_rep, d_w, d_end, d_sums, d_site, d_soff};
-      for (void *b : bufs) (void)hipFree(b);
-      if (ev0) (void)hipEventDestroy(ev0);
-      if (ev1) (void)hipEventDestroy(ev1);
-   }
-   return rc;
+   return 0;
 }

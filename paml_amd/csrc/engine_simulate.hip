@@ -20,13 +20,7 @@ struct SimScratch {
    DevBuf<double> cdf;
    DevBuf<unsigned char> last, state, cls;
    DevBuf<int2> order;
-   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-   ~SimScratch()
-   {
-      cdf.release(); last.release(); state.release(); cls.release(); order.release();
-      if (ev0) (void)hipEventDestroy(ev0);
-      if (ev1) (void)hipEventDestroy(ev1);
-   }
+   DevEvent ev0, ev1;
 };
 
 }  // namespace
@@ -83,8 +77,8 @@ extern "C" int paml_amd_simulate(paml_amd_engine *e, const double *branch, const
       e->bl_gr_sent = false;
    }
    SimScratch w;
-   HIPCHK(hipEventCreate(&w.ev0));
-   HIPCHK(hipEventCreate(&w.ev1));
+   HIPCHK(w.ev0.ensure());
+   HIPCHK(w.ev1.ensure());
    if (int rc = ensure_pmat_buffers(e, K, false, false)) return rc;
    // (from here on the P(t) buffers are this call's: whatever looked at an earlier evaluation's starts over)
    e->pmat_valid = false;

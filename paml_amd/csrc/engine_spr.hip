@@ -112,11 +112,6 @@ struct SprScratch : AncScratch {
    using AncScratch::AncScratch;
    DevBuf<double> PT, Pup, Pdn, Pm, PTup, pint_dn, ptip_dn, pint_m, ptip_m, PTm, Lp, Ap, SLp, SAp, f, sig, lnf, partial, out;
    DevBuf<int> plan;
-   ~SprScratch()
-   {
-      for (DevBuf<double> *b : {&PT, &Pup, &Pdn, &Pm, &PTup, &pint_dn, &ptip_dn, &pint_m, &ptip_m, &PTm, &Lp, &Ap, &SLp, &SAp, &f, &sig, &lnf, &partial, &out}) b->release();
-      plan.release();
-   }
 };
 
 }  // namespace
@@ -235,7 +230,7 @@ extern "C" int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, con
       o.n_group = (ip1 < plan.n_prunes() ? plan.prunes[SPR_PRUNE_INTS * ip1 + 3] : n_moves) - o.swap0;
    };
    if (int rc = anc_score_batches(
-          e, w, o, chunk_base, batch, (int)group_first.size() - 1, lane_pass,
+          e, w, o, batch, (int)group_first.size() - 1, lane_pass,
           [](dim3) {},      // (the present tree's row is combined with the batch's first group)
           [&](int gi, dim3 tiles, dim3 lanes) {
              group(gi);

@@ -20,6 +20,11 @@
 //   engine_place.hip    the lnL of the tree with a query tip hung on every branch (the same shared host helpers as engine_nni.hip)
 //   engine_nni.hip      the lnL of every nearest-neighbour-interchange neighbour of the tree (P(t), the down pass and the host helpers as
 //                       engine_gradient.hip; the outer pass without the derivative and the swap pass are its own kernels)
+// Ownership: every device buffer is a DevBuf and every event a DevEvent (dev_buf.h), freed by its destructor — the engine's as members
+// of paml_amd_engine, a call's own as members of its scratch struct (AncScratch and its kin) — so nothing here lists buffers to free.
+// Teardown is ~paml_amd_engine alone: streams, communicator, pinned blocks, the profiling dump, modules; the members go after its body.
+// The host side the whole-tree calls share (refusals, P(t) and its derivatives, the batch workspace, the one batch loop anc_batches) is
+// ancestral_host.h, defined in engine_ancestral.hip.
 // Built for gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,6 +55,7 @@
 #include "branch_plan.h"
 #include "subtree_classes.h"
 #include "gather_tiles.h"
+#include "dev_buf.h"
 
 namespace paml_amd {
 static_assert(JIT_SCRATCH_BASE == MFMA_RS, "the per-tree kernel addresses the interpreter's overflow-stack scratch");
@@ -69,34 +75,12 @@ constexpr int DMA_WAVES = 8;           // mfma64 "stream" kernel: 128 patterns p
 constexpr int GATHER_WAVES = 4;        // mfma64 "gather" kernel: 64 patterns per workgroup, 2 per CU
 constexpr int VALU_MAXD_SMALL = 16, VALU_MAXD_20 = 8;
 
-template <typename T>
-struct DevBuf {
-   T *p = nullptr;
-   size_t cap = 0;
-   hipError_t ensure(size_t n)
-   {
-      if (n <= cap) return hipSuccess;
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      cap = 0;
-      hipError_t e = hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T));
-      if (e == hipSuccess) cap = n;
-      return e;
-   }
-   void release()
-   {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      cap = 0;
-   }
-};
-
 // Pinned host arena for the small per-evaluation inputs, so the H2D copies are truly asynchronous and
 // the source stays valid until an event says the copies are done.
 struct Staging {
    char *p = nullptr;
    size_t cap = 0, used = 0;
-   hipEvent_t ev = nullptr;
+   DevEvent ev;
    bool pending = false;
    hipError_t begin(size_t need)
    {
@@ -108,7 +92,7 @@ struct Staging {
          if (r != hipSuccess) return r;
          cap = need * 2;
       }
-      if (!ev) { hipError_t r = hipEventCreateWithFlags(&ev, hipEventDisableTiming); if (r != hipSuccess) return r; }
+      if (hipError_t r = ev.ensure(hipEventDisableTiming); r != hipSuccess) return r;
       used = 0;
       return hipSuccess;
    }
@@ -128,12 +112,10 @@ struct Staging {
       return r != hipSuccess ? r : hipMemcpyAsync(b.p, put(src, n), n * sizeof(T), hipMemcpyHostToDevice, s);
    }
    hipError_t end(hipStream_t s) { pending = true; return hipEventRecord(ev, s); }
-   void release()
+   ~Staging()
    {
-      if (pending && ev) (void)hipEventSynchronize(ev);
+      if (pending && ev) (void)hipEventSynchronize(ev);      // (the pinned block is the source of copies that may still be queued)
       if (p) (void)hipHostFree(p);
-      if (ev) (void)hipEventDestroy(ev);
-      p = nullptr; ev = nullptr; cap = 0; pending = false;
    }
 };
 
@@ -316,7 +298,7 @@ struct paml_amd_engine {
    hipStream_t sc = nullptr;
    static constexpr int MAXL = 4;     // slots of (class likelihoods, partial sums, all-reduced copy): the evaluations in flight
    int n_lanes = 2;                   // ... in use (PAML_AMD_LANES), taken in rotation
-   hipEvent_t ev_part[MAXL] = {}, ev_done[MAXL] = {};
+   DevEvent ev_part[MAXL], ev_done[MAXL];
    // Two facts per slot.  done_pending: an exchange step queued on `sc` may still be reading the slot's buffers — whoever writes the
    // slot next makes ITS stream wait for ev_done (wait_slot in launch_eval).  join_pending: the caller's stream has not been made to
    // wait for that total yet (paml_amd_flush / enter).  A flush in the middle of a run clears only the second: the slot's next
@@ -327,7 +309,7 @@ struct paml_amd_engine {
    // stream sat in front of its slot's previous exchange.  Off by default (timed events cost a few microseconds each).
    static constexpr int NSTAT = 64;
    bool comm_stats = false;
-   hipEvent_t st_part[NSTAT] = {}, st_done[NSTAT] = {}, st_w0[NSTAT] = {}, st_w1[NSTAT] = {};
+   DevEvent st_part[NSTAT], st_done[NSTAT], st_w0[NSTAT], st_w1[NSTAT];
    bool st_waited[NSTAT] = {};
    long st_count = 0;
    int red_slot = 0, last_slot = 0, last_fhk = 0;      // last_fhk: the class-likelihood buffer the last evaluation wrote (fhk_slot)
@@ -357,7 +339,7 @@ struct paml_amd_engine {
    DevBuf<double> d_bl_partials, d_bl_scalef, d_bl_frag, d_bl_coef, d_bl_efrag, d_bl_ztab, d_bl_etab, d_bl_ecol;
    bool beig_attr_set = false;
    bool bl_gr_sent = false;           // d_gene_rate holds the gene rates of the branch cache (cleared by whoever else writes the buffer)
-   hipEvent_t ev_bk[2] = {};          // paml_amd_profile on: around the contraction kernel(s) of the last eval_branch (paml_amd_branch_kernel_ms)
+   DevEvent ev_bk[2];              // paml_amd_profile on: around the contraction kernel(s) of the last eval_branch (paml_amd_branch_kernel_ms)
    bool bk_timed = false;
    long n_branch_coef_hits = 0;      // eval_branch calls served from the stored coefficients
    long n_branch_refill_jit = 0;     // eval_branch calls whose forest of dirty subtrees ran on a per-tree kernel (a refill, engine_branch.hip)
@@ -520,7 +502,7 @@ struct paml_amd_engine {
    // call switches the fast path off until the next eval_device has run in order.
    bool pipe_ok = false;
    hipStream_t s2 = nullptr;
-   hipEvent_t ev_entry[2] = {nullptr, nullptr}, ev_pmat = nullptr;
+   DevEvent ev_entry[2], ev_pmat;
    int entry_sel = 0;
    bool have_prev_entry = false;
    // P(t) storage of the runs of eval_device calls: NPSET sets in rotation (the current one in d_rowmajor / d_pint / d_ptip / d_pcol,
@@ -538,7 +520,7 @@ struct paml_amd_engine {
    // Same kernels, same arguments, same bits; PAML_AMD_DUAL=0 goes back to one stream.  ev_setread[s]: the last pruning kernel
    // that read P set s so far (all the side stream waits for before it overwrites the set: P(t) runs up to two evaluations ahead).
    hipStream_t sb[MAXL - 1] = {};      // pruning streams of lanes 1 .. (lane 0: the engine's stream)
-   hipEvent_t ev_setread[NPSET] = {};
+   DevEvent ev_setread[NPSET];
    bool setread_rec[NPSET] = {};
    int pset = 0;                 // id of the current P set (spare[].id: of the others)
    bool dual_ok = false, dual_run = false;      // dual_run: the run's first two-stream evaluation (which still waits for the run's uploads) is behind us
@@ -599,27 +581,24 @@ struct paml_amd_engine {
 
    // profiling
    bool profiling = false;
-   std::vector<hipEvent_t> ev_pool;
-   std::vector<hipEvent_t> ev_used;   // sextuples per eval
+   std::vector<DevEvent> ev_pool;
+   std::vector<DevEvent> ev_used;   // sextuples per eval
    long prof_evals = 0;
    long n_eval = 0, n_pmat = 0;
 
+   // The whole of teardown.  Streams first: nothing of this engine may still run when what it reads goes.  The members (every DevBuf and
+   // DevEvent, the staging block) are destroyed after this body, so device memory is freed last.
    ~paml_amd_engine()
    {
-      for (auto &e : eigen) { e.U.release(); e.V.release(); e.Root.release(); e.Cijk.release(); }
-      stage.release();
+      for (hipStream_t s : sb)
+         if (s) (void)hipStreamSynchronize(s);
+      if (s2) (void)hipStreamSynchronize(s2);
       if (sc) (void)hipStreamSynchronize(sc);      // (no collective may still be in flight when its communicator goes)
       if (comm && rccl().CommDestroy) (void)rccl().CommDestroy(comm);
+      for (hipStream_t s : sb)
+         if (s) (void)hipStreamDestroy(s);
+      if (s2) (void)hipStreamDestroy(s2);
       if (sc) (void)hipStreamDestroy(sc);
-      for (int b = 0; b < MAXL; b++) {
-         if (ev_part[b]) (void)hipEventDestroy(ev_part[b]);
-         if (ev_done[b]) (void)hipEventDestroy(ev_done[b]);
-      }
-      for (hipEvent_t ev : ev_bk)
-         if (ev) (void)hipEventDestroy(ev);
-      for (int i = 0; i < NSTAT; i++)
-         for (hipEvent_t ev : {st_part[i], st_done[i], st_w0[i], st_w1[i]})
-            if (ev) (void)hipEventDestroy(ev);
       if (h_out) (void)hipHostFree(h_out);
       if (h_eig_fail) (void)hipHostFree(h_eig_fail);
       for (int ln = 0; ln < MAXL && d_prof && env.prof_tiles && prof_words; ln++) {      // the last launch's workgroup timeline (of each pruning stream: <dump>, <dump>.1 ..)
@@ -639,38 +618,6 @@ struct paml_amd_engine {
       for (JitKernel &k : jit_pool)
          if (k.mod) (void)hipModuleUnload(k.mod);
       if (jit_coop.mod) (void)hipModuleUnload(jit_coop.mod);
-      for (auto ev : ev_pool) (void)hipEventDestroy(ev);
-      for (auto ev : ev_used) (void)hipEventDestroy(ev);
-      DevBuf<unsigned char> *b1[] = {&d_z, &d_chara_map, &d_is_leaf, &d_ztiles};
-      for (auto b : b1) b->release();
-      DevBuf<int> *b2[] = {&d_n_chara, &d_gene_off, &d_label, &d_eigen_of, &d_b_eigen_of, &d_beb_iw};
-      for (auto b : b2) b->release();
-      d_tiles.release();
-      d_tiles_full.release();
-      d_tile_group0.release();
-      tile_stash.tiles.release(); tile_stash.group0.release(); tile_stash.ztip_of.release(); tile_stash.ztiles.release();
-      d_ztip_of.release();
-      d_zpm.release();
-      d_red_counter.release();
-      d_bl_partials.release(); d_bl_scalef.release(); d_bl_frag.release(); d_code_mask.release();
-      d_bl_coef.release(); d_bl_efrag.release(); d_bl_ztab.release(); d_bl_etab.release(); d_bl_ecol.release();
-      d_ops.release();
-      d_ops_tmp.release();
-      d_label_eff.release();
-      d_stream.release();
-      d_eigen.release();
-      d_pres.release();
-      d_ctab.release();
-      d_stab.release();
-      sub.d_nodes.release(); sub.d_sidx.release(); sub.d_top_cls.release(); sub.d_meta.release(); sub.d_ztiles.release(); sub.d_order.release(); sub.d_gw_desc.release();
-      d_eq_q.release(); d_eq_pi.release(); d_eq_scale.release(); d_eq_ptr.release(); d_eq_rc.release(); d_eq_sweeps.release();
-      d_pi_plain.release();
-      DevBuf<double> *b3[] = {&d_weights, &d_pi, &d_freqK, &d_rate, &d_qfactor, &d_branch, &d_gene_rate, &d_rowmajor,
-                              &d_pint, &d_ptip, &d_pcol, &d_fhK, &d_fscale, &d_lnf, &d_b_qfactor, &d_b_freqK, &d_b_rate, &d_beb_f, &d_beb_part, &d_beb_g, &d_beb_out, &d_beb_pcl, &d_adg_all, &d_partial, &d_out, &d_partials, &d_scalef, &d_stack, &d2_branch, &d2_gene_rate, &d_partial_tot, &d_btot,
-                              &d_expA, &d_expB, &d_expSA, &d_expSB, &d_deriv, &d_tt, &d_bpartial, &d_bout};
-      for (auto b : b3) b->release();
-      for (auto &sp : spare) { sp.rowmajor.release(); sp.pint.release(); sp.ptip.release(); sp.pcol.release(); sp.ctab.release(); sp.stab.release(); }
-      for (int b = 0; b < MAXL - 1; b++) { d_partial_s[b].release(); d_partial_tot_s[b].release(); d_fhK_s[b].release(); }
    }
 };
 
@@ -733,15 +680,15 @@ inline std::vector<int> code_order(int n, int n_codes, const int *nch, const uns
 
 inline hipEvent_t get_event(paml_amd_engine *e)
 {
-   hipEvent_t ev;
+   DevEvent ev;
    if (!e->ev_pool.empty()) {
-      ev = e->ev_pool.back();
+      ev = std::move(e->ev_pool.back());
       e->ev_pool.pop_back();
    }
-   else if (hipEventCreate(&ev) != hipSuccess)
+   else if (ev.ensure() != hipSuccess)
       return nullptr;
-   e->ev_used.push_back(ev);
-   return ev;
+   e->ev_used.push_back(std::move(ev));
+   return e->ev_used.back();
 }
 
 inline void mark_on(paml_amd_engine *e, hipStream_t s)
@@ -775,8 +722,7 @@ inline int ensure_side_stream(paml_amd_engine *e)
    hipStream_t sc = nullptr;
    if (create_engine_stream(&sc) != hipSuccess) return fail(e, PAML_AMD_EHIP, "hipStreamCreate(side stream)");
    for (int b = 0; b < paml_amd_engine::MAXL; b++)
-      if ((!e->ev_part[b] && hipEventCreateWithFlags(&e->ev_part[b], hipEventDisableTiming) != hipSuccess) ||
-          (!e->ev_done[b] && hipEventCreateWithFlags(&e->ev_done[b], hipEventDisableTiming) != hipSuccess)) {
+      if (e->ev_part[b].ensure(hipEventDisableTiming) != hipSuccess || e->ev_done[b].ensure(hipEventDisableTiming) != hipSuccess) {
          (void)hipStreamDestroy(sc);      // (a later call starts over: `sc` is only published with all its events)
          return fail(e, PAML_AMD_EHIP, "hipEventCreate(side stream)");
       }

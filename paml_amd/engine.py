@@ -32,7 +32,7 @@ EXPORTS = [
     "paml_amd_cherry_tables", "paml_amd_debug_jit_tables",
     "paml_amd_subtree_tables", "paml_amd_subtree_order", "paml_amd_debug_subtree_order", "paml_amd_debug_subtree_classes", "paml_amd_debug_jit_subtree", "paml_amd_debug_subtree_select",
     "paml_amd_gather_walk", "paml_amd_debug_gather_tiles",
-    "paml_amd_debug_code_order", "paml_amd_debug_branch_plan",
+    "paml_amd_debug_code_order", "paml_amd_debug_branch_plan", "paml_amd_debug_device_bytes",
     "paml_amd_pairset_create", "paml_amd_pairset_destroy", "paml_amd_pairset_get_counts", "paml_amd_pairset_set_pi", "paml_amd_pairset_set_pattern",
     "paml_amd_pairset_eval", "paml_amd_pairset_failed", "paml_amd_pairset_counters",
     "paml_amd_rell_replicates", "paml_amd_rell_info",
