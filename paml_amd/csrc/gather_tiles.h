@@ -16,7 +16,7 @@ namespace paml_amd {
 
 constexpr int GATHER_TILE_PATT = 128;      // patterns per tile at most: 8 waves x 16
 constexpr int GATHER_MAX_LOOKUPS = 4;
-constexpr int GATHER_R_MAX = 160;          // (a slot is one byte; the kernel's LDS holds two row buffers)
+constexpr int GATHER_R_MAX = 160;          // (a slot is one byte; the kernel's LDS holds two row buffers of R <= 128)
 
 struct GatherTiles {
    int n_lookups = 0, R = 0;

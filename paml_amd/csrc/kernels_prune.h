@@ -822,8 +822,11 @@ __global__ __launch_bounds__(256) void sztile_kernel(const int2 *tiles, const in
 // instruction (LDS-DMA with a per-lane source offset) brings the rows of two neighbouring slots into one 1 KB piece of the row buffer, all
 // eight waves load.  Two row buffers: while tile t is computed from one, tile t + 1's rows are on their way into the other and tile t + 2's
 // block of lists into the third of three block buffers.  A stage ends with ONE s_waitcnt vmcnt(0) and ONE barrier: no counted waits,
-// nothing depends on where the compiler puts a load.  (A third row buffer would buy nothing in this form: the stage's wait drains
-// everything that was requested, whatever buffer it goes to.)
+// nothing depends on where the compiler puts a load.  (A third row buffer buys nothing in this form, where every wave loads every tile:
+// the stage's wait drains everything the wave requested, whatever buffer it goes to.  A form that dealt the tiles to two halves of the
+// workgroup — vmcnt is per wave — did keep two tiles in flight with three row buffers of R = 90 and hid the memory's latency completely,
+// and was still slower: a stage is bound by the instructions its waves execute, not by memory.  DESIGN 4 B (xv); that form is not in
+// the tree.)
 // LDS image: a ds_read_b128 is served in lane groups of sixteen — eight patterns of one q and eight of its neighbour q ^ 1 — that read the
 // same offset of different rows; bank = (address / 4) mod 64, so rows a multiple of 256 bytes apart would all meet on one bank.  Piece j
 // (slots 2 j and 2 j + 1) lies at j x GW_PIECE_BYTES = 1024 + 64, and the odd slot's row is stored with its 16-byte chunks c at c ^ 2
@@ -869,7 +872,14 @@ __global__ __launch_bounds__(512, 4) void gather_walk_kernel(PruneArgs a)
       const int tile = work % a.gw_tiles;
       if (wave * 256 < DB) dma4(make_rsrc(a.gw_desc + (long)tile * DB, DB), descbuf + d * DB + wave * 256, lane * 4, wave * 256);
    };
-   // the distinct rows of the tile whose block has landed in buffer d -> row buffer b: piece j by wave j & 7
+   // the distinct rows of the tile whose block has landed in buffer d -> row buffer b: piece j by wave j & 7.  The requests are half of
+   // what a wave executes per tile, and the kernel is bound by that, not by memory, so they are kept short: the tables'
+   // buffer descriptors are made when the class changes, not per tile; the lists are walked one after the other (they start at even slots,
+   // so a piece belongs to one list and one table), which leaves no table to choose per piece; and the list entry of the wave's NEXT piece
+   // is read ahead of the request for this one — a request is a memory barrier to the compiler, so an entry read between two of them would
+   // cost an LDS round trip per piece.
+   __amdgpu_buffer_rsrc_t trs[NLK];
+   int tcls = -1;
    auto issue_rows = [&](int work, int d, int b) {
       const int iclass = work / a.gw_tiles;
       const int *head = (const int *)(descbuf + d * DB);
@@ -877,23 +887,29 @@ __global__ __launch_bounds__(512, 4) void gather_walk_kernel(PruneArgs a)
       const int s1 = __builtin_amdgcn_readfirstlane(head[2]), s2 = __builtin_amdgcn_readfirstlane(head[3]), s3 = __builtin_amdgcn_readfirstlane(head[4]);
       int ns = __builtin_amdgcn_readfirstlane(head[5]);
       ns = ns < gather_desc_slots(R) ? ns : (gather_desc_slots(R) & ~1);      // (never past the row buffer, whatever the block says)
-      const double *tab[NLK];
-      unsigned int bytes[NLK];
+      if (iclass != tcls) {
+         tcls = iclass;
 #pragma unroll
-      for (int k = 0; k < NLK; k++) {
-         if (a.gw_kind[k]) { tab[k] = a.ctab + ((long)iclass * a.n_ctab + a.gw_id[k]) * (long)nc2 * CHERRY_ROW_WORDS; bytes[k] = (unsigned int)nc2 * 512u; }
-         else { tab[k] = JIT_STAB(iclass, a.gw_id[k]); bytes[k] = (unsigned int)JIT_STAB_U(a.gw_id[k]) * 512u; }
+         for (int k = 0; k < NLK; k++) {
+            // (a row past its table's end reads zeros: the descriptor's bound, not the list, guards the address)
+            if (a.gw_kind[k]) trs[k] = make_rsrc(a.ctab + ((long)iclass * a.n_ctab + a.gw_id[k]) * (long)nc2 * CHERRY_ROW_WORDS, (unsigned int)nc2 * 512u);
+            else trs[k] = make_rsrc(JIT_STAB(iclass, a.gw_id[k]), (unsigned int)JIT_STAB_U(a.gw_id[k]) * 512u);
+         }
       }
-      for (int j = wave; 2 * j < ns; j += 8) {
-         const int k = (2 * j >= s1) + (2 * j >= s2) + (2 * j >= s3);      // wave-uniform: the lists start at even slots
-         const double *t = tab[0];
-         unsigned int nb = bytes[0];
+      const unsigned int lane_off = (unsigned int)((lane & 31) ^ ((lane >> 5) << 1)) * 16u;
+      unsigned char *const rbuf = rowbuf + b * RB;
 #pragma unroll
-         for (int kk = 1; kk < NLK; kk++)
-            if (k == kk) { t = tab[kk]; nb = bytes[kk]; }
-         const unsigned int row = rows[2 * j + (lane >> 5)];
-         // (a row past its table's end reads zeros: the descriptor's bound, not the list, guards the address)
-         gw_dma16(make_rsrc(t, nb), rowbuf + b * RB + j * GW_PIECE_BYTES, (int)(row * 512u + (unsigned int)((lane & 31) ^ ((lane >> 5) << 1)) * 16u));
+      for (int k = 0; k < NLK; k++) {      // list k: the slots lo .. hi - 1
+         const int lo = k == 0 ? 0 : (k == 1 ? s1 : (k == 2 ? s2 : s3));
+         int hi = k == NLK - 1 ? ns : (k == 0 ? s1 : (k == 1 ? s2 : s3));
+         hi = hi < ns ? hi : ns;
+         int j = (lo >> 1) + ((wave - (lo >> 1)) & 7);      // the wave's first piece of this list: j = wave mod 8, as before
+         unsigned int ahead = rows[(2 * j < hi ? 2 * j : 0) + (lane >> 5)];
+         for (; 2 * j < hi; j += 8) {
+            const unsigned int row = ahead;
+            ahead = rows[(2 * (j + 8) < hi ? 2 * (j + 8) : 0) + (lane >> 5)];
+            gw_dma16(trs[k], rbuf + j * GW_PIECE_BYTES, (int)(row * 512u + lane_off));
+         }
       }
    };
    auto landed = [&]() {
