@@ -709,6 +709,35 @@ void paml_amd_edge_info(int *last_batches, double *last_kernel_ms);
 int paml_amd_edge_list(int n_tips, int n_nodes, int root, const int *sons_ptr, const int *sons,
                        int *edges /* [cap][3][3] = per edge three (v, s, x), or NULL */, int *five /* [cap][5], or NULL */, int cap);
 
+/* ---- Relabel scores: the lnL of the tree with the label of ONE branch changed, for all (branch, label) rows in ONE call: the device
+ * primitive under a scan of every branch as the foreground of a branch-site or branch model.  Row (v, l) is the present tree — with
+ * the labels of base_label where it is given, otherwise the tree's own — with the label of the branch above v set to l; v is any node
+ * other than the root, tips included.  lnL[i] and lnf[i][h] are what paml_amd_eval would return for that tree at `branch`, to rounding
+ * (the definition is written out in csrc/kernels_relabel.h); *lnL0 is the present tree's lnL, taken as paml_amd_nni_scores takes it.
+ * lnfk[i][k][h] is the log of the likelihood of pattern h given class k, WITHOUT freqK (-inf where it is not positive), and lnfk0[k][h]
+ * the same of the present tree: what a host needs to re-mix the class proportions without another call.  A class whose eigen set and
+ * Qfactor are the same under l as under the branch's present label (for the pattern's gene) is not computed: its lnfk row has the bits
+ * of lnfk0[k]; a row in which no class changes has the bits of the present tree's lnf, and lnL[i] those of *lnL0.  No tree is set and no
+ * kernel is built per row.  K classes, several genes, ambiguity codes, polytomies, scaling nodes, a root that is a tip, at most 64
+ * states.  Synchronous; leaves a following paml_amd_eval, paml_amd_gradient, paml_amd_nni_scores, paml_amd_placement_scores,
+ * paml_amd_spr_scores and paml_amd_edge_scores their results, and paml_amd_get_pmat afterwards returns the tree's own matrices at
+ * `branch`.  n_patt is walked gene by gene in batches of what a workspace holds (256 MiB; the environment variable
+ * PAML_AMD_RELABEL_ARENA_MB, read at every call, gives another size in MiB), and the rows in groups where one tile of patterns with all
+ * of them does not fit: every output has the same bits for any workspace size, for any sub-list or order of the rows and on every call
+ * (fixed-order sums, no atomics).  PAML_AMD_EINVAL (with a message starting "relabel_scores" that names the row) for a null branch,
+ * rows, lnL0 or lnL, n_rows < 1, a v that is the root or out of range, a label outside [0, n_labels) in a row or in base_label, lnfk
+ * without lnfk0 or the reverse, a model or tips not set; PAML_AMD_EUNSUPPORTED for rate-matrix (UNREST) sets (as paml_amd_edge_scores),
+ * tips that are not the nodes 0 .. n_tips - 1, more than 64 states, an engine whose communicator has more than one rank;
+ * PAML_AMD_ENOCONV as the other synchronous entries. */
+int paml_amd_relabel_scores(paml_amd_engine *e, const double *branch, const double *gene_rate,
+                            const int *base_label /* [n_nodes], or NULL = the tree's labels */,
+                            int n_rows, const int *rows /* [n_rows][2] = v, label */,
+                            double *lnL0, double *lnL /* [n_rows] */, double *lnf /* [n_rows][n_patt], or NULL */,
+                            double *lnfk0 /* [K][n_patt], or NULL */, double *lnfk /* [n_rows][K][n_patt], or NULL */);
+/* The number of pattern batches the calling thread's last paml_amd_relabel_scores walked and the time of its kernels by HIP events (ms,
+ * summed); either pointer may be NULL. */
+void paml_amd_relabel_info(int *last_batches, double *last_kernel_ms);
+
 /* ---- Placement: the lnL of the tree with one more tip hung on a branch, for every query, every branch and every pendant length in ONE
  * call.  The reference's stepwise addition (StepwiseAddition treesub.c:4866 on AddSpecies treesub.c:4592) sets and evaluates one enlarged
  * tree after the other; the same primitive lies under the regraft half of an SPR move and under placing new sequences on a fitted tree.

@@ -314,6 +314,32 @@ int pamlh_newton_full(pamlh *p, double *x, double e, int max_sweeps, double *lnL
 int pamlh_count_labels(pamlh *p, const char *kind, int *n_lab, double *M, char (*names)[32]);
 int pamlh_subst_counts(pamlh *p, const double *x, int n_lab, const double *M, double *counts, double *site_counts);
 
+/* ---- Every branch as the foreground of branch-site model A in turn (pamlh_scan.c; codeml model = 2, NSsites = 2, fix_omega = 0), from
+ * ONE engine call (paml_amd_relabel_scores) instead of a tree file, a model set-up and a search per branch.  Model A gives a branch type
+ * the time scale Qfactor_bg = 1 / mr(kappa, r w0 + 1 - r) or Qfactor_fg = 1 / mr(kappa, p0 w0 + p1 + (1 - p0 - p1) w2), r = p0 / (p0 + p1):
+ * with the EFFECTIVE lengths tau_v = t_v Qfactor held fixed the four class likelihoods do not depend on the proportions, so re-mixing
+ * them on the host is an exact point of model A (pamlh_foreground_point gives its parameter vector); the lengths, kappa and w0 are not
+ * maximised again.
+ * pamlh_mixture_max (host only, no engine): maximises sum_h w_h log(s r f0 + s (1 - r) f1 + (1 - s) r f2a + (1 - s)(1 - r) f2b) over
+ *   (s, r) in [1e-6, 1 - 1e-6]^2 from (s0, r0): EM steps, then a safeguarded projected Newton iteration; lnL never decreases.  lnf4[4][n_patt]
+ *   are logs (-inf allowed), rescaled per pattern.  *p0 = s r, *p1 = s (1 - r).
+ * pamlh_foreground_scan: omega2[n_grid] ascending with omega2[0] = 1; lnL, p0, p1 are [*n_br][n_grid], delta and best [*n_br], node
+ *   [*n_br] = every non-root node in node order.  From x it takes kappa, w0, the branch lengths and (p0, p1); the tree's own '#' labels
+ *   and x's w2 are not used; tau_v = t_v Qfactor_bg(r_x) for EVERY branch.  delta = 2 (max_{g >= 1} lnL - lnL at g = 0), best that g;
+ *   *lnL_base the mixture without a foreground class (s -> 1).  With node = lnL = NULL only *n_br is written.  The tree's labels and the
+ *   engine's model are left as they were.
+ * pamlh_foreground_point: the model-A parameter vector, in x's layout, of a row for the tree with `node` as the only foreground branch:
+ *   t'_u = tau_u / Qfactor_bg(r') (u != node), t'_node = tau_node / Qfactor_fg(p0, p1, omega2), kappa and w0 from x, then p0, p1, omega2.
+ *   Not clamped into pamlh_bounds.
+ * pamlh_set_foreground: label 1 on the branch above `node` and 0 elsewhere, in place (as pamlh_apply_nni changes the tree in place);
+ *   pamlh_newick then prints #1 there.
+ * Refused by name: models other than branch-site A, fix_omega = 1, a clock, rho, several genes, a pattern shard. */
+int pamlh_mixture_max(int n_patt, const double *w, const double *lnf4 /* [4][n_patt] logs */, double s0, double r0, double *p0, double *p1, double *lnL);
+int pamlh_foreground_scan(pamlh *p, const double *x, int n_grid, const double *omega2, int *n_br, int *node, double *lnL_base, double *lnL, double *p0,
+                          double *p1, double *delta, int *best);
+int pamlh_foreground_point(pamlh *p, const double *x, int node, double omega2, double p0, double p1, double *xA);
+int pamlh_set_foreground(pamlh *p, int node);
+
 /* Standard errors of the estimates (getSE = 1).  method 0: HessianSKT2004 (treesub.c:7241), the outer product of per-pattern
  * scores that the reference's programs print; method 1: observed information from central second differences of lnL
  * (Hessian() tools.c:5984).  Either way all perturbed evaluations are one batch.  se[np] (-1: not available, e.g. a parameter

@@ -14,77 +14,18 @@ extern "C" void paml_amd_edge_info(int *last_batches, double *last_kernel_ms) { 
 namespace paml_amd {
 
 // P(t) of every (row, override slot, parameter set), and dP, d^2P for the slot of u: grid (rows x 5, gene x class).  The formulas are
-// pmat_deriv_kernel's, term for term.  Matrix cores: the A-operand order (the index formula of grad_pmat_kernel), transposed for f.
+// pmat_deriv_kernel's, term for term (edge_pmat_fill, kernels_edge.h).  Matrix cores: the A-operand order, transposed for f.
 __global__ __launch_bounds__(256) void edge_pmat_kernel(EdgePmatArgs a)
 {
    const GradPmatArgs &g = a.g;
-   const int row = blockIdx.x / EDGE_SLOTS, slot = blockIdx.x % EDGE_SLOTS, pset = blockIdx.y, n = g.n;
+   const int row = blockIdx.x / EDGE_SLOTS, slot = blockIdx.x % EDGE_SLOTS, pset = blockIdx.y;
    const int node = a.ovr_node[(long)row * EDGE_SLOTS + slot];
    if (node < 0) return;
    const bool with_d = node == a.rows[4L * row + 3], transposed = g.mfma && node == a.father[a.rows[4L * row]];
-   const int gene = pset / g.K, iclass = pset % g.K, lab = g.label[node];
-   const EigenDev es = g.eigen[g.eigen_of[(gene * g.K + iclass) * g.n_labels + lab]];
-   const double t = a.ovr_t[(long)row * EDGE_SLOTS + slot];
-   const double qf = es.kind == PAML_AMD_EIGEN_UVROOT ? g.qfactor[iclass * g.n_labels + lab] : 1.0;
-   const double base = g.gene_rate[gene] * g.rate[gene * g.rate_gs + iclass] * qf;
-   const int nroot = es.kind == PAML_AMD_EIGEN_CIJK ? es.nR : n;
-   const bool closed = es.kind == PAML_AMD_EIGEN_K80 || es.kind == PAML_AMD_EIGEN_JC69LIKE, k80 = es.kind == PAML_AMD_EIGEN_K80;
    __shared__ double sE[64], sM[64];
-   double m1 = 0, m2 = 0, e1 = 0, e2 = 0;
-   if (closed) {
-      m1 = base * (k80 ? -4 / (es.kappa + 2) : -(double)n / (n - 1));
-      m2 = base * (k80 ? -2 * (es.kappa + 1) / (es.kappa + 2) : 0.0);
-      e1 = exp(t * m1);
-      e2 = k80 ? exp(t * m2) : 0.0;
-   }
-   else {
-      for (int k = threadIdx.x; k < nroot; k += 256) {
-         const double mu = base * es.Root[k];
-         sM[k] = mu;
-         sE[k] = k ? exp(t * mu) : 1.0;
-      }
-      __syncthreads();
-   }
-   auto entry = [&](int i, int j, double (&out)[3]) {
-      if (closed) {
-         double c1, c2;      // P = 1/n + c1 e1 + c2 e2
-         if (k80) { c1 = (i == j || (i ^ j) == 1) ? 0.25 : -0.25; c2 = i == j ? 0.5 : ((i ^ j) == 1 ? -0.5 : 0.0); }
-         else { c1 = i == j ? 1 - 1.0 / n : -1.0 / n; c2 = 0; }
-         out[0] = 1.0 / n + c1 * e1 + c2 * e2;
-         out[1] = c1 * e1 * m1 + c2 * e2 * m2;
-         out[2] = c1 * e1 * m1 * m1 + c2 * e2 * m2 * m2;
-         return;
-      }
-      double p = 0, dp = 0, ddp = 0;
-      for (int k = 0; k < nroot; k++) {
-         const double c0 = es.kind == PAML_AMD_EIGEN_CIJK ? es.Cijk[((long)i * n + j) * nroot + k] * sE[k] : (es.U[i * n + k] * sE[k]) * es.V[k * n + j];
-         p += c0;
-         if (k) {
-            dp += c0 * sM[k];
-            ddp += c0 * sM[k] * sM[k];
-         }
-      }
-      out[0] = p; out[1] = dp; out[2] = ddp;
-   };
    double *P = a.OM + (((long)row * a.psets + pset) * EDGE_MATS + slot) * a.msz;
    double *dP = a.OM + (((long)row * a.psets + pset) * EDGE_MATS + EDGE_SLOTS) * a.msz, *ddP = dP + a.msz;
-   const int total = g.mfma ? 4096 : n * n;
-   for (int idx = threadIdx.x; idx < total; idx += 256) {
-      int r, c;
-      if (g.mfma) {      // element ((kb2*4 + jb)*64 + lane)*2 + e  =  M[jb*16 + (lane&15)][4*(2*kb2+e) + (lane>>4)], zero padded
-         const int e = idx & 1, lane = (idx >> 1) & 63, jb = (idx >> 7) & 3, kb2 = idx >> 9;
-         r = jb * 16 + (lane & 15);
-         c = 4 * (2 * kb2 + e) + (lane >> 4);
-      }
-      else { r = idx / n; c = idx % n; }
-      double out[3] = {0, 0, 0};
-      if (r < n && c < n) {
-         if (transposed) entry(c, r, out);
-         else entry(r, c, out);
-      }
-      P[idx] = out[0];
-      if (with_d) { dP[idx] = out[1]; ddP[idx] = out[2]; }
-   }
+   edge_pmat_fill<true>(g, pset, g.label[node], a.ovr_t[(long)row * EDGE_SLOTS + slot], with_d, transposed, sE, sM, P, dP, ddP);
 }
 
 // one pattern per lane, the row pass: grid (patterns / 256, K, rows of the group)

@@ -204,6 +204,78 @@ struct EdgePmatArgs {
    int psets;
 };
 
+// P(t) of parameter set `pset` under branch label `lab` at length t, and with D its first and second derivative (stored when with_d),
+// by a workgroup of 256: n x n row-major, or 4096 doubles in the A-operand order (the index formula of grad_pmat_kernel; `transposed`:
+// of P^T).  mu_k = gene rate x class rate x Qfactor x Root_k; UVROOT, CIJK, K80 and JC69-like sets.  sE, sM: 64 doubles of LDS each.
+// Shared by edge_pmat_kernel and relabel_pmat_kernel (D = false: no derivative term is formed).
+template <bool D>
+__device__ __forceinline__ void edge_pmat_fill(const GradPmatArgs &g, int pset, int lab, double t, bool with_d, bool transposed, double *sE, double *sM, double *P,
+                                               double *dP, double *ddP)
+{
+   const int n = g.n, gene = pset / g.K, iclass = pset % g.K;
+   const EigenDev es = g.eigen[g.eigen_of[(gene * g.K + iclass) * g.n_labels + lab]];
+   const double qf = es.kind == PAML_AMD_EIGEN_UVROOT ? g.qfactor[iclass * g.n_labels + lab] : 1.0;
+   const double base = g.gene_rate[gene] * g.rate[gene * g.rate_gs + iclass] * qf;
+   const int nroot = es.kind == PAML_AMD_EIGEN_CIJK ? es.nR : n;
+   const bool closed = es.kind == PAML_AMD_EIGEN_K80 || es.kind == PAML_AMD_EIGEN_JC69LIKE, k80 = es.kind == PAML_AMD_EIGEN_K80;
+   double m1 = 0, m2 = 0, e1 = 0, e2 = 0;
+   if (closed) {
+      m1 = base * (k80 ? -4 / (es.kappa + 2) : -(double)n / (n - 1));
+      m2 = base * (k80 ? -2 * (es.kappa + 1) / (es.kappa + 2) : 0.0);
+      e1 = exp(t * m1);
+      e2 = k80 ? exp(t * m2) : 0.0;
+   }
+   else {
+      for (int k = threadIdx.x; k < nroot; k += 256) {
+         const double mu = base * es.Root[k];
+         sM[k] = mu;
+         sE[k] = k ? exp(t * mu) : 1.0;
+      }
+      __syncthreads();
+   }
+   auto entry = [&](int i, int j, double (&out)[3]) {
+      if (closed) {
+         double c1, c2;      // P = 1/n + c1 e1 + c2 e2
+         if (k80) { c1 = (i == j || (i ^ j) == 1) ? 0.25 : -0.25; c2 = i == j ? 0.5 : ((i ^ j) == 1 ? -0.5 : 0.0); }
+         else { c1 = i == j ? 1 - 1.0 / n : -1.0 / n; c2 = 0; }
+         out[0] = 1.0 / n + c1 * e1 + c2 * e2;
+         if constexpr (D) {
+            out[1] = c1 * e1 * m1 + c2 * e2 * m2;
+            out[2] = c1 * e1 * m1 * m1 + c2 * e2 * m2 * m2;
+         }
+         return;
+      }
+      double p = 0, dp = 0, ddp = 0;
+      for (int k = 0; k < nroot; k++) {
+         const double c0 = es.kind == PAML_AMD_EIGEN_CIJK ? es.Cijk[((long)i * n + j) * nroot + k] * sE[k] : (es.U[i * n + k] * sE[k]) * es.V[k * n + j];
+         p += c0;
+         if constexpr (D)
+            if (k) {
+               dp += c0 * sM[k];
+               ddp += c0 * sM[k] * sM[k];
+            }
+      }
+      out[0] = p; out[1] = dp; out[2] = ddp;
+   };
+   const int total = g.mfma ? 4096 : n * n;
+   for (int idx = threadIdx.x; idx < total; idx += 256) {
+      int r, c;
+      if (g.mfma) {      // element ((kb2*4 + jb)*64 + lane)*2 + e  =  M[jb*16 + (lane&15)][4*(2*kb2+e) + (lane>>4)], zero padded
+         const int e = idx & 1, lane = (idx >> 1) & 63, jb = (idx >> 7) & 3, kb2 = idx >> 9;
+         r = jb * 16 + (lane & 15);
+         c = 4 * (2 * kb2 + e) + (lane >> 4);
+      }
+      else { r = idx / n; c = idx % n; }
+      double out[3] = {0, 0, 0};
+      if (r < n && c < n) {
+         if (transposed) entry(c, r, out);
+         else entry(r, c, out);
+      }
+      P[idx] = out[0];
+      if (D && with_d) { dP[idx] = out[1]; ddP[idx] = out[2]; }
+   }
+}
+
 __global__ void edge_pmat_kernel(EdgePmatArgs a);
 __global__ void edge_mfma_kernel(EdgeArgs a);
 __global__ void edge_combine_kernel(EdgeArgs a);

@@ -45,6 +45,7 @@ EXPORTS = [
     "paml_amd_subst_counts", "paml_amd_subst_counts_info",
     "paml_amd_nni_scores", "paml_amd_nni_info", "paml_amd_nni_list",
     "paml_amd_edge_scores", "paml_amd_edge_info", "paml_amd_edge_list",
+    "paml_amd_relabel_scores", "paml_amd_relabel_info",
     "paml_amd_placement_scores", "paml_amd_placement_info",
     "paml_amd_spr_scores", "paml_amd_spr_info", "paml_amd_spr_list",
 ]
@@ -61,7 +62,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_curvature", "engine_hessian", "engine_modelgrad", "engine_counts", "engine_nni", "engine_place", "engine_spr", "engine_edge")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_curvature", "engine_hessian", "engine_modelgrad", "engine_counts", "engine_nni", "engine_place", "engine_spr", "engine_edge", "engine_relabel")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -269,6 +270,7 @@ class Engine:
         q = None if qfactor is None else np.ascontiguousarray(qfactor, dtype=np.float64)
         self.K = K
         self._chk(self._L.paml_amd_set_classes(self._h, int(mode), K, _p(f), _p(r), n_labels, _p(eo), _p(q)))
+        self.n_labels = n_labels
 
     def load(self, pb: Problem):
         """Upload everything a Problem holds (tips, tree, pi, eigen systems, classes)."""
@@ -616,6 +618,32 @@ class Engine:
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         self._chk(self._L.paml_amd_edge_scores(self._h, _p(b), _p(g), len(rw), _p(rw), _p(on), _p(ot), C.byref(lnL0), _p(lnL), _p(d1), _p(d2), _p(lnf)))
         return dict(lnL0=lnL0.value, lnL=lnL, d1=d1, d2=d2, lnf=lnf)
+
+    def relabel_scores(self, branch, gene_rate=None, rows=None, base_label=None, want_lnf=False, want_classes=False):
+        """The lnL of the tree at `branch` with the label of one branch changed, for every (node, label) row in one call
+        (paml_amd_relabel_scores): dict(lnL0 (the present tree's), rows=[n_rows][2] (v, label), lnL=[n_rows], lnf=[n_rows][n_patt] or
+        None, lnfk0=[K][n_patt] and lnfk=[n_rows][K][n_patt] with want_classes (the logs of the class-conditional likelihoods, without
+        freqK), else None).  rows None: every non-root node of the tree last set with every label of the class table, in node order.
+        base_label: int [n_nodes], the labels the rows start from instead of the tree's own."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        if rows is None:
+            if getattr(self, "_tree_csr", None) is None or getattr(self, "n_labels", None) is None:
+                raise EngineError("relabel_scores: no tree or no class table was set through this object")
+            rows = [(v, l) for v in range(self.n_nodes) if v != self._tree_csr[0] for l in range(self.n_labels)]
+        rw = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 2)
+        bl = None if base_label is None else np.ascontiguousarray(base_label, dtype=np.int32)
+        if bl is not None and bl.shape != (self.n_nodes,):
+            raise EngineError("relabel_scores: base_label must be [n_nodes]")
+        lnL0 = C.c_double()
+        lnL = np.zeros(len(rw))
+        lnf = np.zeros((len(rw), self.n_patt)) if want_lnf else None
+        lnfk0 = np.zeros((self.K, self.n_patt)) if want_classes else None
+        lnfk = np.zeros((len(rw), self.K, self.n_patt)) if want_classes else None
+        self._L.paml_amd_relabel_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double),
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self._L.paml_amd_relabel_scores(self._h, _p(b), _p(g), _p(bl), len(rw), _p(rw), C.byref(lnL0), _p(lnL), _p(lnf), _p(lnfk0), _p(lnfk)))
+        return dict(lnL0=lnL0.value, rows=rw, lnL=lnL, lnf=lnf, lnfk0=lnfk0, lnfk=lnfk)
 
     def placement_scores(self, branch, gene_rate=None, queries=None, edges=None, pendant=(0.1,), phi=0.5, pendant_label=0, want_lnf=False):
         """The lnL of the tree at `branch` with a query tip hung on a branch, for every query, edge and pendant length in one call
@@ -1191,6 +1219,17 @@ def edge_info():
     L.paml_amd_edge_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.paml_amd_edge_info.restype = None
     L.paml_amd_edge_info(C.byref(nb), C.byref(ms))
+    return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def relabel_info():
+    """Batches walked by this thread's last Engine.relabel_scores and the time of its kernels by HIP events (paml_amd_relabel_info):
+    dict(last_batches, last_kernel_ms)."""
+    L = lib()
+    nb, ms = C.c_int(), C.c_double()
+    L.paml_amd_relabel_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.paml_amd_relabel_info.restype = None
+    L.paml_amd_relabel_info(C.byref(nb), C.byref(ms))
     return dict(last_batches=nb.value, last_kernel_ms=ms.value)
 
 

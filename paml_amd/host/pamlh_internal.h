@@ -164,6 +164,7 @@ int pamlh_model_feasible(const pamlh *p);
 int pamlh_x_to_branches(const pamlh *p, const double *x, double *branch);
 void pamlh_dnds_one(const pamlh *p, const double *pi, double kappa, double omega, double t, double ls, double *N, double *S, double *dN, double *dS);
 double pamlh_codon_q(const pamlh *p, const double *pi, double kappa, double omega, double *Q);
+void pamlh_set_eig_uvroot(pamlh *p, int i, const double *Q, const double *pi, double scale);      /* eigen system i of the model state: Q / scale, decomposed on the device or on demand */
 int pamlh_codon_pattern_flags(const pamlh *p, const int **row, const int **col, unsigned char *flags);      /* flags: room for 704 */
 int pamlh_load_impl(pamlh **out, const char *ctl_path, const char *program, int tree_index, const char *overrides, int placement, char *err, int errcap);
 int pamlh_split_queries(pamlh *p);      /* pamlh_place.c: after pamlh_read_seqs, before pamlh_read_tree */

@@ -140,6 +140,8 @@ int main(int argc, char **argv)
    pamlh *p;
    char err[512];
    double x[4096], lnL, *lnf;
+   int fg_scan = 0, fg_ngrid = 0;
+   double fg_grid[64];
    int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0, spr_scores = 0, spr_search = 0, radius = 0, top = 0, place = 0, n_pend = 4, supports = 0, newton = 0, newton_full = 0, exact_hessian = 0, se_exact = 0, subst_counts = 0, per_site = 0;
    double pend[64] = {0.05, 0.1, 0.2, 0.4}, split = 0.5;
    char over[2048] = "";
@@ -161,6 +163,11 @@ int main(int argc, char **argv)
       else if (!strcmp(argv[i], "--subst-counts")) subst_counts = 1;       /* posterior expected substitution counts per branch (pamlh_subst_counts) */
       else if (!strcmp(argv[i], "--per-site")) per_site = 1;               /* with --subst-counts: the site x branch table of every label as well */
       else if (!strcmp(argv[i], "--nni-scores")) nni_scores = 1;
+      else if (!strcmp(argv[i], "--foreground-scan")) fg_scan = 1;        /* every branch as the foreground of branch-site model A in turn, one engine call (pamlh_foreground_scan); --top N: the N best maximised */
+      else if (!strcmp(argv[i], "--omega-grid") && i + 1 < argc) {      /* the grid of w2, ascending from 1, e.g. "1,2,5,20" */
+         char *s2 = argv[++i];
+         for (fg_ngrid = 0; fg_ngrid < 64 && *s2; ) { fg_grid[fg_ngrid++] = strtod(s2, &s2); if (*s2 == ',') s2++; else break; }
+      }
       else if (!strcmp(argv[i], "--branch-supports")) supports = 1;      /* SH-like aLRT supports of the internal branches (N replicates, default 1000; --seed S) */
       else if (!strcmp(argv[i], "--nni-search")) nni_search = 1;
       else if (!strcmp(argv[i], "--max-moves") && i + 1 < argc) max_moves = atoi(argv[++i]);
@@ -314,6 +321,61 @@ int main(int argc, char **argv)
       nw = (char *)malloc((size_t)160 * nnode + 256);
       if (!pamlh_newick_supports(p, n, node, sup, nw, 160 * nnode + 256)) printf("%s\n", nw);
       free(nw); free(node); free(delta); free(sup); free(l3); free(fa_of);
+      pamlh_free(p);
+      return 0;
+   }
+   if (fg_scan) {      /* the foreground scan at x (after --optimize: at the estimates); instead of the evaluation */
+      static const double dflt[9] = {1, 1.5, 2, 3, 5, 8, 12, 20, 50};
+      int nnode = 0, nb = 0, n_eval = 0, *node, *best, *fa_of, *lab0, *order, j, k;
+      double base = 0, *sl, *sp0, *sp1, *delta, *xa, *lo, *hi;
+      char *nw;
+      if (gpus > 0) { fprintf(stderr, "error: --foreground-scan runs on one GPU\n"); return 1; }
+      if (!fg_ngrid) { memcpy(fg_grid, dflt, sizeof(dflt)); fg_ngrid = 9; }
+      pamlh_dims(p, NULL, NULL, NULL, &nnode, NULL, NULL, NULL, NULL, NULL, NULL);
+      if (pamlh_foreground_scan(p, NULL, 0, NULL, &nb, NULL, NULL, NULL, NULL, NULL, NULL, NULL)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      if (optimize && pamlh_optimize(p, x, &lnL, 500, 1e-10, 0, &n_eval) < 0) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      node = (int *)malloc(nb * sizeof(int)); best = (int *)malloc(nb * sizeof(int)); order = (int *)malloc(nb * sizeof(int));
+      fa_of = (int *)malloc(nnode * sizeof(int)); lab0 = (int *)malloc(nnode * sizeof(int));
+      sl = (double *)malloc((size_t)nb * fg_ngrid * sizeof(double)); sp0 = (double *)malloc((size_t)nb * fg_ngrid * sizeof(double));
+      sp1 = (double *)malloc((size_t)nb * fg_ngrid * sizeof(double)); delta = (double *)malloc(nb * sizeof(double));
+      xa = (double *)malloc((np + 1) * sizeof(double)); lo = (double *)malloc((np + 1) * sizeof(double)); hi = (double *)malloc((np + 1) * sizeof(double));
+      memcpy(lab0, pamlh_labels(p), nnode * sizeof(int));
+      if (pamlh_foreground_scan(p, x, fg_ngrid, fg_grid, &nb, node, &base, sl, sp0, sp1, delta, best)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      {
+         const int *sp = pamlh_sons_ptr(p), *so = pamlh_sons(p);
+         int v;
+         for (v = 0; v < nnode; v++) fa_of[v] = -1;
+         for (v = 0; v < nnode; v++)
+            for (j = sp[v]; j < sp[v + 1]; j++) fa_of[so[j]] = v;
+      }
+      printf("Foreground scan (branch-site model A, one engine call, %d branches x %d values of w2): lnL without a foreground class = %.6f\n%10s %10s %10s %10s %16s %12s\n",
+             nb, fg_ngrid, base, "branch", "w2", "p0", "p1", "lnL", "delta");
+      for (i = 0; i < nb; i++) {
+         const int g = best[i];
+         printf("%4d..%-4d %10.4f %10.6f %10.6f %16.6f %12.6f\n", fa_of[node[i]] + 1, node[i] + 1, fg_grid[g], sp0[i * fg_ngrid + g], sp1[i * fg_ngrid + g], sl[i * fg_ngrid + g], delta[i]);
+      }
+      for (i = 0; i < nb; i++) order[i] = i;
+      for (i = 0; i < nb; i++)      /* descending delta, ties in node order */
+         for (j = i + 1; j < nb; j++)
+            if (delta[order[j]] > delta[order[i]]) { k = order[i]; order[i] = order[j]; order[j] = k; }
+      pamlh_bounds(p, lo, hi);
+      nw = (char *)malloc((size_t)160 * nnode + 256);
+      for (k = 0; k < top && k < nb && delta[order[k]] > 0; k++) {      /* the best branches maximised as the foreground, from the scan's point */
+         const int b = order[k], g = best[b];
+         double l1 = 0;
+         if (pamlh_foreground_point(p, x, node[b], fg_grid[g], sp0[b * fg_ngrid + g], sp1[b * fg_ngrid + g], xa) || pamlh_set_foreground(p, node[b])) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+         for (j = 0; j < np; j++) xa[j] = xa[j] < lo[j] ? lo[j] : xa[j] > hi[j] ? hi[j] : xa[j];
+         if (pamlh_optimize(p, xa, &l1, 500, 1e-10, 0, &n_eval) < 0) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+         printf("foreground %d..%d maximised from the scan's point (lnL %.6f): lnL = %.6f\nx:", fa_of[node[b]] + 1, node[b] + 1, sl[b * fg_ngrid + g], l1);
+         for (j = 0; j < np; j++) printf(" %.6f", xa[j]);
+         printf("\n");
+         if (!pamlh_newick(p, nw, 160 * nnode + 256)) printf("%s\n", nw);
+      }
+      if (top > 0) {      /* the tree's own labels again */
+         for (j = 0; j < nnode && lab0[j] != 1; j++) ;
+         if (j < nnode && pamlh_set_foreground(p, j)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+      }
+      free(nw); free(node); free(best); free(order); free(fa_of); free(lab0); free(sl); free(sp0); free(sp1); free(delta); free(xa); free(lo); free(hi);
       pamlh_free(p);
       return 0;
    }

@@ -2472,6 +2472,7 @@ void pamlh_dnds_one(const pamlh *p, const double *pi, double kappa, double omega
 /* the codon rate matrix (unscaled; returns the mean rate) and the elements it can have with their kinds, for the pairwise comparisons
  * (pamlh_pairwise.c): row / col as paml_amd_set_eigen_qrev_batch_sparse takes them, flags bit 0 = transition, bit 1 = nonsynonymous */
 double pamlh_codon_q(const pamlh *p, const double *pi, double kappa, double omega, double *Q) { return codon_q_pi(p, pi, kappa, omega, Q); }
+void pamlh_set_eig_uvroot(pamlh *p, int i, const double *Q, const double *pi, double scale) { set_eig_uvroot(p, i, Q, pi, scale); }      /* (pamlh_scan.c installs a model of its own) */
 int pamlh_codon_pattern_flags(const pamlh *p, const int **row, const int **col, unsigned char *flags)
 {
    const codon_pairs_t *cp = codon_pairs(p);

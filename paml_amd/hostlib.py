@@ -20,7 +20,7 @@ DRIVER_PATH = os.path.join(_HERE, "lib", "pamlh_lnl")
 def build(force=False):
     from . import engine
     engine.build()
-    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_place.c", "pamlh_spr.c", "pamlh_support.c", "pamlh_newton.c", "pamlh_hessian.c", "pamlh_counts.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
+    srcs = [os.path.join(_HERE, "host", f) for f in ("pamlh_num.c", "pamlh_io.c", "pamlh_model.c", "pamlh_opt.c", "pamlh_pairwise.c", "pamlh_simulate.c", "pamlh_nni.c", "pamlh_place.c", "pamlh_spr.c", "pamlh_support.c", "pamlh_newton.c", "pamlh_hessian.c", "pamlh_counts.c", "pamlh_scan.c", "pamlh_lnl.c", "pamlh_internal.h", "Makefile")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "pamlh.h"))
     if force or not (os.path.exists(LIB_PATH) and os.path.exists(DRIVER_PATH)) or \
             any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
@@ -71,6 +71,24 @@ def lib():
 
 def _arr(ptr, dtype, n):
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=(n,)).copy()
+
+
+DEFAULT_OMEGA2_GRID = (1, 1.5, 2, 3, 5, 8, 12, 20, 50)
+
+
+def mixture_max(w, lnf4, s0=0.5, r0=0.5):
+    """pamlh_mixture_max, host only: the proportions of branch-site model A's four site classes at fixed class likelihoods.  w pattern
+    counts, lnf4 [4][n_patt] the logs of f0, f1, f2a, f2b (-inf allowed); start (s0, r0) = (p0 + p1, p0 / (p0 + p1)) -> dict(p0, p1, lnL)."""
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    f = np.ascontiguousarray(lnf4, dtype=np.float64)
+    if f.shape != (4, len(w)):
+        raise ValueError("mixture_max: lnf4 must be [4][%d]" % len(w))
+    L = lib()
+    L.pamlh_mixture_max.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double] + [C.POINTER(C.c_double)] * 3
+    p0, p1, lnl = C.c_double(), C.c_double(), C.c_double()
+    if L.pamlh_mixture_max(len(w), w.ctypes.data_as(C.c_void_p), f.ctypes.data_as(C.c_void_p), float(s0), float(r0), C.byref(p0), C.byref(p1), C.byref(lnl)) != 0:
+        raise RuntimeError("pamlh_mixture_max: bad arguments, or a pattern of weight > 0 without a likelihood under any class")
+    return dict(p0=p0.value, p1=p1.value, lnL=lnl.value)
 
 
 def tree_comparison(lnf, w, gene_off=None, n_rep=0, seed=1, device=False):
@@ -469,6 +487,50 @@ class Analysis:
         self._L.pamlh_apply_nni.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         if self._L.pamlh_apply_nni(self._h, int(v), int(s), int(x)) != 0:
             raise RuntimeError("pamlh_apply_nni: " + self._L.pamlh_error(self._h).decode())
+
+    def foreground_scan(self, x, omega2=None):
+        """Every non-root branch as the only foreground branch of branch-site model A, at every omega2 of an ascending grid that starts
+        at 1 (pamlh_foreground_scan; one engine call): dict(node=[n_br], omega2=[n_grid], lnL_base, lnL, p0, p1 = [n_br][n_grid],
+        delta=[n_br] = 2 (max over omega2 > 1 - the value at omega2 = 1), best=[n_br] the grid index of that maximum)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        grid = np.ascontiguousarray(DEFAULT_OMEGA2_GRID if omega2 is None else omega2, dtype=np.float64)
+        f = self._L.pamlh_foreground_scan
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_double)] + [C.c_void_p] * 5
+        n, base = C.c_int(), C.c_double()
+        if len(x) != self.np or f(self._h, None, 0, None, C.byref(n), None, None, None, None, None, None, None) != 0:
+            raise RuntimeError("pamlh_foreground_scan: " + self._L.pamlh_error(self._h).decode())
+        nb, ng = n.value, len(grid)
+        node, best = np.zeros(nb, dtype=np.int32), np.zeros(nb, dtype=np.int32)
+        lnl, p0, p1, delta = np.zeros((nb, ng)), np.zeros((nb, ng)), np.zeros((nb, ng)), np.zeros(nb)
+        q = lambda a: a.ctypes.data_as(C.c_void_p)
+        if f(self._h, q(x), ng, q(grid), C.byref(n), q(node), C.byref(base), q(lnl), q(p0), q(p1), q(delta), q(best)) != 0:
+            raise RuntimeError("pamlh_foreground_scan: " + self._L.pamlh_error(self._h).decode())
+        return dict(node=node, omega2=grid, lnL_base=base.value, lnL=lnl, p0=p0, p1=p1, delta=delta, best=best)
+
+    def foreground_point(self, x, node, omega2, p0, p1):
+        """The model-A parameter vector of a row of foreground_scan, in x's layout, for the tree with `node` as the only foreground
+        branch (pamlh_foreground_point); not clamped into bounds()."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        xa = np.zeros(self.np)
+        f = self._L.pamlh_foreground_point
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p]
+        if len(x) != self.np or f(self._h, x.ctypes.data_as(C.c_void_p), int(node), float(omega2), float(p0), float(p1), xa.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("pamlh_foreground_point: " + self._L.pamlh_error(self._h).decode())
+        return xa
+
+    def set_foreground(self, node):
+        """Label 1 on the branch above `node` and 0 elsewhere, on the analysis's tree in place (pamlh_set_foreground)."""
+        self._L.pamlh_set_foreground.argtypes = [C.c_void_p, C.c_int]
+        if self._L.pamlh_set_foreground(self._h, int(node)) != 0:
+            raise RuntimeError("pamlh_set_foreground: " + self._L.pamlh_error(self._h).decode())
+
+    def newick(self):
+        """The tree with the branch lengths of the last set_x and its '#' labels (pamlh_newick)."""
+        buf = C.create_string_buffer(160 * self.n_nodes + 256)
+        self._L.pamlh_newick.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+        if self._L.pamlh_newick(self._h, buf, len(buf)) != 0:
+            raise RuntimeError("pamlh_newick failed")
+        return buf.value.decode()
 
     def nni_search(self, x0, max_moves=0, verbose=False):
         """NNI hill climb from the tree as it stands (pamlh_nni_search): dict(x, lnL, moves, screening_calls, optimisations, newick)."""

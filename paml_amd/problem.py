@@ -89,6 +89,15 @@ class Tree:
         sons[fa][sons[fa].index(x)] = int(s)
         return Tree(self.n_tips, self.n_nodes, self.root, sons, self.branch, self.label, self.names)
 
+    def relabelled(self, v, label):
+        """A new Tree with the label of the branch above v set to `label` (what paml_amd_relabel_scores scores).  Everything else is
+        shared with this tree; label is a new array."""
+        if not 0 <= v < self.n_nodes or v == self.root or self.father()[v] < 0:
+            raise ValueError("relabelled(%s): the root or no node of this tree" % (v,))
+        lab = np.array(self.label, dtype=np.int32)
+        lab[v] = int(label)
+        return Tree(self.n_tips, self.n_nodes, self.root, self.sons, self.branch, lab, self.names)
+
     def _spr_parts(self, s, x=None):
         """(f, g, c, below) of pruning s: f the father of s, g the father of f, c the other son of f, below[u]: u lies in the subtree
         below s, s included.  ValueError naming what makes the prune, or the move (s, x) when x is given, invalid (the definition at the
