@@ -663,20 +663,28 @@ __device__ __forceinline__ double jit_scale(v4d (&y)[4], int q, int n)   // Node
    return log(mx);
 }
 
-// Root stage with pi and the weight flag already in LDS (no vector-memory loads whose wait would drain the ring's DMAs).
-__device__ __forceinline__ void jit_root_lds(const PruneArgs &a, const v4d (&x)[4], double lnscale, const double *spi, int flag, int iclass,
-                                             int q, int h, bool valid)
+// The root's value of a pattern, in every lane of the pattern's four: pi . x over the lane's sixteen states (pq: the lane's slice of pi,
+// spi + q * 16 — a pointer into LDS or an array in registers), the two butterflies, the floor and the weight flag.
+template <class PQ>
+__device__ __forceinline__ double jit_root_value(const PruneArgs &a, const v4d (&x)[4], const PQ &pq, int flag)
 {
-   const double *pq = spi + q * 16;
    double f = 0;
 #pragma unroll
    for (int m = 0; m < 16; m++) f = fma(pq[m], x[m >> 2][m & 3], f);
    f += __shfl_xor(f, 16);
    f += __shfl_xor(f, 32);
+   // fx_r treesub.c:7731-7749 / lfun 7782-7798: the floor here, log + scale factors in the reduction kernel
+   if (f <= 0) f = (a.mode == PAML_AMD_MODE_LFUN ? 1e-80 : 1e-300);
+   return flag ? f : 0.0;
+}
+
+// Root stage with pi and the weight flag already in LDS (no vector-memory loads whose wait would drain the ring's DMAs).
+__device__ __forceinline__ void jit_root_lds(const PruneArgs &a, const v4d (&x)[4], double lnscale, const double *spi, int flag, int iclass,
+                                             int q, int h, bool valid)
+{
+   const double f = jit_root_value(a, x, spi + q * 16, flag);
    if (q == 0 && valid) {
-      // fx_r treesub.c:7731-7749 / lfun 7782-7798: the floor here, log + scale factors in the reduction kernel
-      if (f <= 0) f = (a.mode == PAML_AMD_MODE_LFUN ? 1e-80 : 1e-300);
-      a.fhK[(long)iclass * a.n_patt + h] = flag ? f : 0.0;
+      a.fhK[(long)iclass * a.n_patt + h] = f;
       if (a.n_scale) a.fscale[(long)iclass * a.n_patt + h] = lnscale;
    }
 }

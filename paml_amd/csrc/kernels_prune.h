@@ -834,10 +834,14 @@ __global__ __launch_bounds__(256) void sztile_kernel(const int2 *tiles, const in
 // 2 s + (q & 1) for q < 2 and 2 (s ^ 1) + (q & 1) for the others (+ 4 i, mod 16).  The two q of a lane group never meet, and two slots
 // meet only when they are a multiple of 8 apart — a run of the sorted order, which reads neighbouring slots, is conflict-free.  Inside a
 // row the tables' layout [element pair][q][16 bytes] stays, so a pattern reads what jit_lookup_row reads, and the arithmetic is the
-// generated walk's call for call: jit_mul by the popped slot, lookup after lookup, then jit_root_lds — same bits.
-// Registers: 60.  (A form that interpreted the program's pop / push slots at run time and asked for all rows of a pattern at once took
-// 246 and ran the walk in 0.112 ms against this one's 0.088; with two row buffers of R = 128 the kernel has a CU's LDS to itself either
-// way: the builders of the next evaluation, which shared the CUs with the generated walk, wait for its end — DESIGN 4 B (xiv).)
+// generated walk's call for call: jit_mul by the popped slot, lookup after lookup, then jit_root_lds's value (jit_root_value) — same bits.
+// Between two barriers a stage is one serial chain per wave, so nothing that can be had earlier stays on it: the
+// result of tile t is stored at the head of stage t + 1, pi sits in registers, tile, class and buffer numbers are counters.
+// Registers: 96 (two lookups), 99 (three, four), 32 of them pi; nothing spills.  (A form that interpreted the program's pop / push slots
+// at run time and asked for all rows of a pattern at once took 246 and ran the walk in 0.112 ms against 0.088 for this one as it was
+// then; with two row buffers of R = 128 the kernel has a CU's LDS to itself either way: the builders of the next evaluation, which
+// shared the CUs with the generated walk, wait for its end — DESIGN 4 B (xiv).  The last 64 doubles of the LDS size held pi until (xvi)
+// and are unused.)
 constexpr int GW_PIECE_BYTES = 1024 + 64;
 constexpr int GW_DESC_BUFS = 3;
 constexpr size_t gather_walk_lds_bytes(int R) { return (size_t)2 * (gather_desc_slots(R) / 2) * GW_PIECE_BYTES + (size_t)GW_DESC_BUFS * gather_desc_bytes(R) + 64 * sizeof(double); }
@@ -850,7 +854,7 @@ __device__ __forceinline__ void gw_dma16(__amdgpu_buffer_rsrc_t r, const void *l
 }
 
 // (launch bounds: 512 threads; the second figure is HIP's — waves per SIMD the compiler must leave room for, here four, i.e. at most 128
-//  VGPRs — not CUDA's blocks per multiprocessor.  The kernel needs 60 - 63; the bound only keeps a later change from growing it unseen.)
+//  VGPRs — not CUDA's blocks per multiprocessor.  The kernel needs 96 - 99; the bound only keeps a later change from growing it unseen.)
 template <int NLK>
 __global__ __launch_bounds__(512, 4) void gather_walk_kernel(PruneArgs a)
 {
@@ -858,18 +862,20 @@ __global__ __launch_bounds__(512, 4) void gather_walk_kernel(PruneArgs a)
    const int R = a.gw_R, DB = a.gw_desc_bytes, RB = (gather_desc_slots(R) / 2) * GW_PIECE_BYTES;
    unsigned char *const rowbuf = gw_smem;                       // [2][RB]
    unsigned char *const descbuf = gw_smem + 2 * RB;             // [GW_DESC_BUFS][DB]
-   double *const sPi = (double *)(descbuf + GW_DESC_BUFS * DB); // [4][16]
    const int tid = threadIdx.x, lane = tid & 63;
    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
    const int q = lane >> 4, hl = lane & 15, p = wave * 16 + hl;
    const int total = a.gw_tiles * a.K, step = gridDim.x;
    if ((int)blockIdx.x >= total) return;
-   if (tid < 64) sPi[tid] = a.pi[tid];
+   // the lane's sixteen pi, read once: in LDS they were eight ds_read2_b64 per tile inside the root's FMA chain (the compiler cannot move a
+   // read across the requests, which are memory barriers to it) — two thirds of what the tile's row reads cost the LDS array
+   double pq[16];
+#pragma unroll
+   for (int m = 0; m < 16; m++) pq[m] = a.pi[q * 16 + m];
    const int nc2 = a.n_codes * a.n_codes;
 
    // a tile's block of lists -> block buffer d (256-byte pieces, one per wave)
-   auto issue_desc = [&](int work, int d) {
-      const int tile = work % a.gw_tiles;
+   auto issue_desc = [&](int tile, int d) {
       if (wave * 256 < DB) dma4(make_rsrc(a.gw_desc + (long)tile * DB, DB), descbuf + d * DB + wave * 256, lane * 4, wave * 256);
    };
    // the distinct rows of the tile whose block has landed in buffer d -> row buffer b: piece j by wave j & 7.  The requests are half of
@@ -880,8 +886,7 @@ __global__ __launch_bounds__(512, 4) void gather_walk_kernel(PruneArgs a)
    // cost an LDS round trip per piece.
    __amdgpu_buffer_rsrc_t trs[NLK];
    int tcls = -1;
-   auto issue_rows = [&](int work, int d, int b) {
-      const int iclass = work / a.gw_tiles;
+   auto issue_rows = [&](int iclass, int d, int b) {
       const int *head = (const int *)(descbuf + d * DB);
       const unsigned int *rows = (const unsigned int *)(descbuf + d * DB + 32);
       const int s1 = __builtin_amdgcn_readfirstlane(head[2]), s2 = __builtin_amdgcn_readfirstlane(head[3]), s3 = __builtin_amdgcn_readfirstlane(head[4]);
@@ -917,25 +922,63 @@ __global__ __launch_bounds__(512, 4) void gather_walk_kernel(PruneArgs a)
       __syncthreads();
    };
 
+   // The work items work, work + step and work + 2 step as counters that advance with the loop, no division per stage: c0 is the class of
+   // the item computed, c1 that of the next one (its rows are requested), (t2, c2) tile and class of the one after (its block is); d0,
+   // d1, d2 the block buffers of the three, b the row buffer of the first.
+   const int nt = a.gw_tiles, dq = step / nt, dr = step % nt;
    int work = blockIdx.x;
-   issue_desc(work, 0);
+   int t2 = work % nt, c2 = work / nt;
+   auto advance = [&]() {
+      t2 += dr;
+      c2 += dq;
+      if (t2 >= nt) { t2 -= nt; c2++; }
+   };
+   int c0 = c2;
+   issue_desc(t2, 0);
+   advance();
+   int c1 = c2;
    landed();
-   issue_rows(work, 0, 0);
-   if (work + step < total) issue_desc(work + step, 1);
+#pragma unroll
+   for (int m = 0; m < 16; m++) asm volatile("" : "+v"(pq[m]));      // (pi has arrived here, in front of the loop: no wait of the compiler's inside it)
+   issue_rows(c0, 0, 0);
+   if (work + step < total) issue_desc(t2, 1);
+   advance();
    landed();
-   for (int t = 0; work < total; work += step, t++) {
-      const int d = t % GW_DESC_BUFS, b = t & 1;
-      if (work + step < total) issue_rows(work + step, (t + 1) % GW_DESC_BUFS, b ^ 1);
-      if (work + 2 * step < total) issue_desc(work + 2 * step, (t + 2) % GW_DESC_BUFS);
+   int d0 = 0, d1 = 1, d2 = 2, b = 0;
+   // A tile's result leaves at the head of the NEXT stage, in front of that stage's requests: vmcnt counts stores with the loads and
+   // retires in issue order, so a store behind the root's FMA chain and butterflies would hold the stage's closing wait — the whole
+   // workgroup — for its acknowledgement; issued here it is older than every request and has a stage to be acknowledged in.  What
+   // travels across the barrier is tile t's own: the value (floored, flag-masked), its pattern, its class and who stores.
+   double f_out = 0;
+   int h_out = 0, c_out = 0;
+   bool st_out = false;
+   auto store_out = [&]() {
+      if (st_out) {
+         a.fhK[(long)c_out * a.n_patt + h_out] = f_out;
+         if (a.n_scale) a.fscale[(long)c_out * a.n_patt + h_out] = 0.0;
+      }
+   };
+   // a pattern's part of a block: its slot per lookup, its weight flag, its place in the output
+   int slot[NLK], flag, hs;
+   bool valid;
+   auto read_patt = [&](int d) {
+      const unsigned char *D = descbuf + d * DB;
+      valid = p < ((const int *)D)[1];
+#pragma unroll
+      for (int k = 0; k < NLK; k++) slot[k] = D[gather_desc_off_slot(R) + k * GATHER_TILE_PATT + p];
+      flag = D[gather_desc_off_flag(R) + p];
+      hs = ((const int *)(D + gather_desc_off_patt(R)))[p];
+   };
+   for (; work < total; work += step) {
+      store_out();
+      if (work + step < total) issue_rows(c1, d1, b ^ 1);
+      if (work + 2 * step < total) issue_desc(t2, d2);
       {
-         const int iclass = work / a.gw_tiles;
-         const unsigned char *D = descbuf + d * DB;
-         const int np = ((const int *)D)[1];
-         const bool valid = p < np;
+         read_patt(d0);
          const unsigned char *rb = rowbuf + b * RB;
          // the rows of a pattern, in the layout jit_lookup_row delivers
          auto row_of = [&](int k, v4d (&x)[4]) {
-            const int s = D[gather_desc_off_slot(R) + k * GATHER_TILE_PATT + p];
+            const int s = slot[k];
             const unsigned char *r = rb + (s >> 1) * GW_PIECE_BYTES + (s & 1) * 512 + (q ^ ((s & 1) << 1)) * 16;
 #pragma unroll
             for (int i = 0; i < 8; i++) {
@@ -944,8 +987,6 @@ __global__ __launch_bounds__(512, 4) void gather_walk_kernel(PruneArgs a)
                x[i >> 1][(2 * i + 1) & 3] = v.y;
             }
          };
-         const int flag = D[gather_desc_off_flag(R) + p];
-         const int hs = ((const int *)(D + gather_desc_off_patt(R)))[p];
          // the program (engine_eval.hip: gather_walk_plan admits this shape only): the first lookup goes to a stack slot, every later one
          // is multiplied by the slot — jit_mul(lookup, slot): y = s * y — and takes its place; the last one is the partial the root reads
          v4d cur[4];
@@ -957,10 +998,22 @@ __global__ __launch_bounds__(512, 4) void gather_walk_kernel(PruneArgs a)
             jit_mul(x, cur);
             jit_copy(cur, x);
          }
-         jit_root_lds(a, cur, 0.0, sPi, flag, iclass, q, hs, valid);
+         f_out = jit_root_value(a, cur, pq, flag);      // (jit_root_lds's value; its store is store_out)
+         h_out = hs;
+         c_out = c0;
+         st_out = q == 0 && valid;
       }
       landed();
+      c0 = c1;
+      c1 = c2;
+      advance();
+      const int d = d0;
+      d0 = d1;
+      d1 = d2;
+      d2 = d;
+      b ^= 1;
    }
+   store_out();
 }
 
 // Tip codes pattern-major for the fused one-pattern-per-lane kernels: row h = zw dwords, byte t = code of tip t.
