@@ -765,6 +765,38 @@ int paml_amd_placement_scores(paml_amd_engine *e, const double *branch, const do
  * (ms, summed); either pointer may be NULL. */
 void paml_amd_placement_info(int *last_batches, double *last_kernel_ms);
 
+/* ---- Attachment at free lengths: the lnL of the tree with a query tip hung on a branch at the row's own lengths of the three branches
+ * that meet at the new node, with the first and second derivative along one of them, for many rows in ONE call: what a maximum-likelihood
+ * placement (the maximum over the proximal, the distal and the pendant length) is iterated on, where paml_amd_placement_scores gives a
+ * grid.  Row (q, v, role) with t3 = (t_up, t_dn, t_pend): v any node but the root, tips included; the new node u sits between v's father
+ * and v; the branch above u has length t_up and the branch above v has length t_dn (both labelled as v's branch; t_up + t_dn need not be
+ * branch[v]); query q hangs below u on a branch of length t_pend labelled pendant_label.  lnL[i] is what paml_amd_eval returns for that
+ * tree as rooted, to rounding (the definition: kernels_attach.h); d1[i], d2[i] are its first and second derivative along the branch named
+ * by role (0: up, 1: dn, 2: pendant) at those lengths, both 0 for role -1; lnL0 is the present tree's, taken as paml_amd_nni_scores takes
+ * it.  qz holds the queries' character codes per pattern, numbered as the table given to paml_amd_set_tips; only the queries that a row
+ * names are read.  Nothing is re-rooted and no reversibility is assumed; class rates, gene rates, Qfactors, branch labels, ambiguity
+ * codes, polytomies, scaling nodes and a root that is a tip are served, up to 64 states.  Synchronous; leaves a following paml_amd_eval,
+ * paml_amd_gradient, paml_amd_nni_scores, paml_amd_placement_scores, paml_amd_spr_scores, paml_amd_edge_scores and
+ * paml_amd_relabel_scores their results and paml_amd_get_pmat the matrices of the tree at `branch`.  n_patt is walked gene by gene in
+ * batches of what a workspace holds (256 MiB; the environment variable PAML_AMD_ATTACH_ARENA_MB, read at every call, gives another size
+ * in MiB), and the rows in groups where one tile of patterns with all rows does not fit: every output has the same bits for any workspace
+ * size, for any sub-list or order of the rows and of the queries and on every call (fixed-order sums, no atomics).  Beside the workspace
+ * a row takes five matrices per (gene, class), and on the matrix cores four column tables.  PAML_AMD_EINVAL (with a message starting
+ * "attach_scores" that names the row) for a null argument other than gene_rate and lnf, n_q or n_rows < 1, a q out of range, a v that is
+ * the root or out of range, a role outside -1 .. 2, a negative or non-finite length, a code of a named query that is >= n_codes or has
+ * an empty state set, a pendant_label outside the class tables' labels, a model or tips not set; PAML_AMD_EUNSUPPORTED for rate-matrix
+ * (UNREST) sets (as paml_amd_edge_scores), tips that are not the nodes 0 .. n_tips - 1, more than 64 states, an engine whose communicator
+ * has more than one rank; PAML_AMD_ENOCONV as the other synchronous entries. */
+int paml_amd_attach_scores(paml_amd_engine *e, const double *branch, const double *gene_rate,
+                           int n_q, const unsigned char *qz /* [n_q][n_patt] */,
+                           int n_rows, const int *rows /* [n_rows][3] = q, v, role */,
+                           const double *t3 /* [n_rows][3] = t_up, t_dn, t_pend */, int pendant_label,
+                           double *lnL0, double *lnL, double *d1, double *d2 /* [n_rows] each */,
+                           double *lnf /* [n_rows][n_patt], or NULL */);
+/* The number of pattern batches the calling thread's last paml_amd_attach_scores walked and the time of its kernels by HIP events (ms,
+ * summed); either pointer may be NULL. */
+void paml_amd_attach_info(int *last_batches, double *last_kernel_ms);
+
 /* ---- Subtree prune and regraft: the lnL of every requested SPR neighbour of the tree at the present branch lengths in ONE call.  A move
  * is (s, x) with a split phi in [0, 1]: f = father(s), g = father(f), c = the other son of f.  The subtree below s leaves with f; c takes
  * f's place under g on a branch of length t_c + t_f with c's label; f takes x's place under x's father with the sons (x, s), the branch

@@ -252,6 +252,34 @@ int pamlh_placement_scores(pamlh *p, const double *x, int n_pend, const double *
 int pamlh_place(pamlh *p, const double *x, int n_pend, const double *pendant, double phi, int *best_edge, double *best_pendant, double *best_lnL, double *lwr);
 int pamlh_placement_newick(pamlh *p, int q, int edge, double phi, double pendant, char *buf, int cap);
 
+/* Maximum-likelihood placement (pamlh_place.c): the grid above scores one split for all branches and a list of pendant lengths; here
+ * the three branches that meet at the new node — the part above it (t_up), the part above the branch's lower node (t_dn), the query's
+ * (t_pend) — are free, and a (query, branch) row is maximised over them, as EPA and pplacer do and as the reference's AddSpecies ends
+ * once the enlarged tree is optimised.  Everything else (the other branch lengths, the model) is held at x.
+ * pamlh_attach_scores: one engine call (paml_amd_attach_scores) at x's branch-length block: lnL[i], d1[i], d2[i] of query q[i] hung on
+ *   the edge[i]-th branch of pamlh_branch_order at the lengths t3[i] = (t_up, t_dn, t_pend), the derivatives along the branch role[i]
+ *   names (-1: none, both 0; 0: up; 1: dn; 2: pendant); *lnL0 the tree's own lnL.
+ * pamlh_place_optimize: all rows are maximised over their three lengths in lock step, started at t3 (in: the start, clipped to the box
+ *   of pamlh_bounds for a branch length, 4e-6 .. 50; out: the maximum) — the cyclic, safeguarded Newton iteration of pamlh_edge_optimize
+ *   with the roles up, dn, pendant: per role one call at the accepted lengths and at most 4 at trial lengths (Newton's step where
+ *   d2 < 0, otherwise the length doubled or halved along the gradient; a trial whose lnL fell is halved from the accepted length), ONE
+ *   engine call per step for every unfinished row; a row is finished after a sweep that gained it no more than 1e-6; at most 30 sweeps.
+ *   No row's lnL ever falls.  lnL[n_rows]: the maxima; stats[3] (or NULL) = sweeps, engine calls, rows that ended with a length at a bound.
+ * pamlh_place_ml: pamlh_placement_scores on the grid first; per query the `keep` best branches of the grid (keep <= 0: all; best
+ *   first), each started at ((1 - phi) t_v, phi t_v, its best grid pendant) and maximised by pamlh_place_optimize; lwr[i] = the
+ *   likelihood weight ratio over the query's kept, maximised rows.  Outputs (room for n_queries x nbranch rows each, 3 per row in t3):
+ *   rows_q, rows_edge (index into pamlh_branch_order), t3, lnL, lwr; *n_rows = n_queries x the branches kept, the queries in order.
+ * pamlh_placement_newick3: pamlh_placement_newick with the three lengths written in (its phi form cannot express parts that do not
+ *   add up to t_v).
+ * Refused by name: what the grid calls refuse, fix_blength = 2 or 3 (the branch lengths are not parameters), and rate-matrix (UNREST)
+ *   models (the engine's message: the derivative of their P(t) needs a matrix product of its own). */
+int pamlh_attach_scores(pamlh *p, const double *x, int n_rows, const int *q, const int *edge, const int *role, const double *t3, double *lnL0, double *lnL, double *d1,
+                        double *d2);
+int pamlh_place_optimize(pamlh *p, const double *x, int n_rows, const int *q, const int *edge, double *t3, double *lnL, int *stats);
+int pamlh_place_ml(pamlh *p, const double *x, int keep, int n_pend, const double *pendant, double phi, int *rows_q, int *rows_edge, double *t3, double *lnL,
+                   double *lwr, int *n_rows);
+int pamlh_placement_newick3(pamlh *p, int q, int edge, double t_up, double t_dn, double t_pend, char *buf, int cap);
+
 /* method = 1 of the control file: minB / minbranches (treesub.c:7826, 8039) — the branch lengths are optimised one at a time
  * by Newton steps on the branch-local lnL, dlnL/dt, d2lnL/dt2 (paml_amd_eval_branch; the engine keeps the partials of both
  * sides of every edge resident, so a step along the tree costs the nodes on the path, not the tree), alternating with BFGS

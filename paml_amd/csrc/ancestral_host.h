@@ -1,5 +1,5 @@
 // ancestral_host.h — the host side that the calls walking a down pass and an outer pass over the whole tree share (defined in
-// engine_ancestral.hip; used there, by engine_gradient.hip, engine_curvature.hip, engine_nni.hip, engine_place.hip and engine_spr.hip): the packed tree, P(t)
+// engine_ancestral.hip; used there, by engine_gradient.hip, engine_curvature.hip, engine_nni.hip, engine_place.hip, engine_attach.hip and engine_spr.hip): the packed tree, P(t)
 // from the evaluation's own builders, the batch size and its workspace, the batch loop of the score calls, the rows' totals.
 #pragma once
 #include <initializer_list>

@@ -18,6 +18,8 @@
 //   engine_modelgrad.hip the derivative of lnL with respect to every input of the engine (rate matrices, effective lengths, freqK, root
 //                       frequencies) in one call: the outer pass that stores H_v, the weighted outer products, the pull-back
 //   engine_place.hip    the lnL of the tree with a query tip hung on every branch (the same shared host helpers as engine_nni.hip)
+//   engine_attach.hip   the lnL of the tree with a query tip hung on a branch at the row's own three lengths, with two derivatives (the
+//                       same shared host helpers; the rows' matrices by edge_pmat_fill, the classes by edge_combine)
 //   engine_nni.hip      the lnL of every nearest-neighbour-interchange neighbour of the tree (P(t), the down pass and the host helpers as
 //                       engine_gradient.hip; the outer pass without the derivative and the swap pass are its own kernels)
 // Ownership: every device buffer is a DevBuf and every event a DevEvent (dev_buf.h), freed by its destructor — the engine's as members

@@ -47,6 +47,7 @@ EXPORTS = [
     "paml_amd_edge_scores", "paml_amd_edge_info", "paml_amd_edge_list",
     "paml_amd_relabel_scores", "paml_amd_relabel_info",
     "paml_amd_placement_scores", "paml_amd_placement_info",
+    "paml_amd_attach_scores", "paml_amd_attach_info",
     "paml_amd_spr_scores", "paml_amd_spr_info", "paml_amd_spr_list",
 ]
 
@@ -62,7 +63,7 @@ UNIT_FLAGS = {}
 # kernel experiments: a variant library beside the default one — PAML_AMD_LIB=<dir>/libpaml_amd.so PAML_AMD_EXTRA_FLAGS="-DX=1" python -c
 # "from paml_amd import engine; engine.build()" compiles every unit with the extra flags into <dir> (objects in <dir>/obj)
 EXTRA_FLAGS = os.environ.get("PAML_AMD_EXTRA_FLAGS", "").split()
-UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_curvature", "engine_hessian", "engine_modelgrad", "engine_counts", "engine_nni", "engine_place", "engine_spr", "engine_edge", "engine_relabel")
+UNITS = ("engine_core", "engine_comm", "engine_eval", "engine_branch", "engine_beb", "engine_jitdbg", "engine_compress", "engine_pairwise", "engine_rell", "engine_simulate", "engine_ancestral", "engine_gradient", "engine_curvature", "engine_hessian", "engine_modelgrad", "engine_counts", "engine_nni", "engine_place", "engine_attach", "engine_spr", "engine_edge", "engine_relabel")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -672,6 +673,32 @@ class Engine:
                                                     int(pendant_label), C.byref(lnL0), _p(lnL), _p(lnf)))
         return dict(lnL0=lnL0.value, edges=ed, lnL=lnL, lnf=lnf)
 
+    def attach_scores(self, branch, gene_rate=None, queries=None, rows=None, t3=None, pendant_label=0, want_lnf=False):
+        """The lnL of the tree at `branch` with a query tip hung on a branch at the row's own three lengths, and its first and second
+        derivative along one of them, for many rows in one call (paml_amd_attach_scores): dict(lnL0 (the present tree's), rows, lnL, d1,
+        d2 = [n_rows], lnf=[n_rows][n_patt] or None).  queries: uint8 [n_q][n_patt] character codes; rows: [n_rows][3] = q, v (the branch
+        above v), role (-1: no derivative, 0: the branch above the new node, 1: the branch above v, 2: the query's); t3: [n_rows][3] =
+        t_up, t_dn, t_pend."""
+        b = np.ascontiguousarray(branch, dtype=np.float64)
+        g = None if gene_rate is None else np.ascontiguousarray(gene_rate, dtype=np.float64)
+        if queries is None or rows is None or t3 is None:
+            raise EngineError("attach_scores: queries, rows and t3 are all needed")
+        qz = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.uint8)
+        if qz.ndim != 2 or qz.shape[1] != self.n_patt:
+            raise EngineError("attach_scores: queries must be [n_q][n_patt]")
+        rw = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 3)
+        tt = np.ascontiguousarray(t3, dtype=np.float64).reshape(-1, 3)
+        if len(tt) != len(rw):
+            raise EngineError("attach_scores: t3 must be [n_rows][3]")
+        lnL0 = C.c_double()
+        lnL, d1, d2 = np.zeros(len(rw)), np.zeros(len(rw)), np.zeros(len(rw))
+        lnf = np.zeros((len(rw), self.n_patt)) if want_lnf else None
+        self._L.paml_amd_attach_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                   C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self._L.paml_amd_attach_scores(self._h, _p(b), _p(g), len(qz), _p(qz), len(rw), _p(rw), _p(tt), int(pendant_label), C.byref(lnL0),
+                                                 _p(lnL), _p(d1), _p(d2), _p(lnf)))
+        return dict(lnL0=lnL0.value, rows=rw, lnL=lnL, d1=d1, d2=d2, lnf=lnf)
+
     def spr_scores(self, branch, gene_rate=None, moves=None, radius=0, phi=0.5, want_lnf=False):
         """The lnL of subtree-prune-and-regraft neighbours of the tree at `branch` in one call (paml_amd_spr_scores): dict(lnL0 (the
         present tree's), moves=[n_moves][2] (s, x), lnL=[n_moves], lnf=[n_moves][n_patt] or None).  The subtree below s is hung on the
@@ -1258,6 +1285,17 @@ def placement_info():
     L.paml_amd_placement_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.paml_amd_placement_info.restype = None
     L.paml_amd_placement_info(C.byref(nb), C.byref(ms))
+    return dict(last_batches=nb.value, last_kernel_ms=ms.value)
+
+
+def attach_info():
+    """Batches walked by this thread's last Engine.attach_scores and the time of its kernels by HIP events
+    (paml_amd_attach_info): dict(last_batches, last_kernel_ms)."""
+    L = lib()
+    nb, ms = C.c_int(), C.c_double()
+    L.paml_amd_attach_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.paml_amd_attach_info.restype = None
+    L.paml_amd_attach_info(C.byref(nb), C.byref(ms))
     return dict(last_batches=nb.value, last_kernel_ms=ms.value)
 
 

@@ -168,6 +168,8 @@ void pamlh_set_eig_uvroot(pamlh *p, int i, const double *Q, const double *pi, do
 int pamlh_codon_pattern_flags(const pamlh *p, const int **row, const int **col, unsigned char *flags);      /* flags: room for 704 */
 int pamlh_load_impl(pamlh **out, const char *ctl_path, const char *program, int tree_index, const char *overrides, int placement, char *err, int errcap);
 int pamlh_split_queries(pamlh *p);      /* pamlh_place.c: after pamlh_read_seqs, before pamlh_read_tree */
+/* pamlh_support.c: one row's move of the safeguarded Newton iteration along one length (the edge and the placement optimiser) */
+int pamlh_newton_trial(int trial, int max_trials, double lo, double hi, double ln, double d1, double d2, double *l, double *ti, double *tn, double *step);
 pamlh *pamlh_state_clone(const pamlh *p);
 void pamlh_state_free(pamlh *q);
 #endif

@@ -28,6 +28,10 @@
  *    0.2, 0.4), the lnL of the tree with the query hung there at PHI (default 0.5) of the branch above the node, the difference to the
  *    tree's own lnL, the likelihood weight ratio — from one engine call, then the best placement's tree.  The parameter vector is the
  *    one the driver would evaluate, or the estimates after --optimize on the tree's sequences)
+ *    --place --place-ml [--keep N]: maximum-likelihood placement (pamlh_place_ml): per query its N best branches of the grid (default:
+ *    all) are maximised over the three lengths at the new node, one engine call per Newton step for all of them.  Per query one table
+ *    row per kept branch — father..node, t_up, t_dn and the pendant length at the maximum, the lnL, the difference to the tree's own
+ *    lnL, the likelihood weight ratio over the kept branches — then the best placement's tree with the three lengths written in
  *    --subst-counts [--per-site]: after the evaluation (or the estimates of --optimize), the posterior expected numbers of substitutions
  *    on every branch from one engine call (pamlh_subst_counts): one row per branch — father..node, t, then a column per label of the
  *    data type (codons: synonymous, nonsynonymous; nucleotides: transitions, transversions; amino acids: changes) and the total;
@@ -142,7 +146,7 @@ int main(int argc, char **argv)
    double x[4096], lnL, *lnf;
    int fg_scan = 0, fg_ngrid = 0;
    double fg_grid[64];
-   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0, spr_scores = 0, spr_search = 0, radius = 0, top = 0, place = 0, n_pend = 4, supports = 0, newton = 0, newton_full = 0, exact_hessian = 0, se_exact = 0, subst_counts = 0, per_site = 0;
+   int np, ntime, npatt, i, nx = 0, optimize = 0, ancestral = 0, ancestral_all = 0, gpus = 0, rank = 0, itree = 0, all_trees = 0, rell_gpu = 0, replicates = 0, analytic = 0, nni_scores = 0, nni_search = 0, max_moves = 0, spr_scores = 0, spr_search = 0, radius = 0, top = 0, place = 0, place_ml = 0, keep = 0, n_pend = 4, supports = 0, newton = 0, newton_full = 0, exact_hessian = 0, se_exact = 0, subst_counts = 0, per_site = 0;
    double pend[64] = {0.05, 0.1, 0.2, 0.4}, split = 0.5;
    char over[2048] = "";
    const char *sim_out = NULL, *bv_out = NULL;
@@ -176,6 +180,8 @@ int main(int argc, char **argv)
       else if (!strcmp(argv[i], "--radius") && i + 1 < argc) radius = atoi(argv[++i]);
       else if (!strcmp(argv[i], "--top") && i + 1 < argc) top = atoi(argv[++i]);
       else if (!strcmp(argv[i], "--place")) place = 1;
+      else if (!strcmp(argv[i], "--place-ml")) place_ml = 1;
+      else if (!strcmp(argv[i], "--keep") && i + 1 < argc) keep = atoi(argv[++i]);
       else if (!strcmp(argv[i], "--pendant") && i + 1 < argc) {      /* the grid of pendant lengths, e.g. "0.05,0.1,0.2" */
          char *tok = strtok(argv[++i], ",");
          for (n_pend = 0; tok && n_pend < 64; tok = strtok(NULL, ",")) pend[n_pend++] = atof(tok);
@@ -247,6 +253,7 @@ int main(int argc, char **argv)
    }
    if (gpus > 0 && spawn_ranks(gpus, device, &rank, comm_id)) { fprintf(stderr, "error: could not start %d ranks (GPUs visible: %d; librccl.so.1 present?)\n", gpus, paml_amd_device_count()); return 1; }
    if (place && (gpus > 0 || all_trees)) { fprintf(stderr, "error: --place runs on one GPU, on one tree\n"); return 1; }
+   if (place_ml && !place) { fprintf(stderr, "error: --place-ml goes with --place\n"); return 1; }
    if ((place ? pamlh_load_placement : pamlh_load_with)(&p, argv[2], argv[1], itree, over, err, sizeof(err))) { fprintf(stderr, "error: %s\n", err); return 1; }
    if (gpus > 0 && pamlh_set_shard(p, rank, gpus, comm_id)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
    if (pamlh_is_pairwise(p)) {      /* runmode = -2: all pairs' searches in lock step; 2ML.t, 2ML.dN, 2ML.dS and rst as the reference writes them */
@@ -453,6 +460,30 @@ int main(int argc, char **argv)
       sc = (double *)malloc((size_t)(nq > 0 ? nq : 1) * nb * n_pend * sizeof(double)); lwr = (double *)malloc((size_t)(nq > 0 ? nq : 1) * nb * sizeof(double));
       be = (int *)malloc((nq > 0 ? nq : 1) * sizeof(int)); bp = (double *)malloc((nq > 0 ? nq : 1) * sizeof(double)); bl = (double *)malloc((nq > 0 ? nq : 1) * sizeof(double));
       nw = (char *)malloc((size_t)160 * (nnode + 2) + 256);
+      if (place_ml) {      /* the kept branches of every query maximised over the three lengths at the new node */
+         int n_rows = 0, r, *rq = (int *)malloc((size_t)(nq > 0 ? nq : 1) * nb * sizeof(int)), *re = (int *)malloc((size_t)(nq > 0 ? nq : 1) * nb * sizeof(int));
+         double *t3 = (double *)malloc((size_t)3 * (nq > 0 ? nq : 1) * nb * sizeof(double)), *ml = (double *)malloc((size_t)(nq > 0 ? nq : 1) * nb * sizeof(double));
+         if (pamlh_placement_scores(p, x, n_pend, pend, split, &l0, sc) || pamlh_place_ml(p, x, keep, n_pend, pend, split, rq, re, t3, ml, lwr, &n_rows)) {
+            fprintf(stderr, "error: %s\n", pamlh_error(p));
+            return 1;
+         }
+         printf("maximum-likelihood placement of %d quer%s, %d of %d branches kept per query: lnL of the tree = %.6f\n", nq, nq == 1 ? "y" : "ies", n_rows / nq, nb, l0);
+         for (q = 0, r = 0; q < nq; q++) {
+            int best = r;
+            printf("\nquery %d (%s)\n%10s %10s %10s %10s %16s %14s %9s\n", q + 1, pamlh_query_name(p, q), "branch", "t_up", "t_dn", "pendant", "lnL", "difference", "LWR");
+            for (; r < n_rows && rq[r] == q; r++) if (ml[r] > ml[best]) best = r;
+            for (e = r - n_rows / nq; e < r; e++) {
+               char br[32];
+               snprintf(br, sizeof(br), "%d..%d", father[order[re[e]]] + 1, order[re[e]] + 1);
+               printf("%10s %10.6f %10.6f %10.6f %16.6f %14.6f %9.6f%s\n", br, t3[3 * e], t3[3 * e + 1], t3[3 * e + 2], ml[e], ml[e] - l0, lwr[e], e == best ? " *" : "");
+            }
+            if (pamlh_placement_newick3(p, q, re[best], t3[3 * best], t3[3 * best + 1], t3[3 * best + 2], nw, 160 * (nnode + 2) + 256)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
+            printf("%s\n", nw);
+         }
+         free(rq); free(re); free(t3); free(ml); free(father); free(sc); free(lwr); free(be); free(bp); free(bl); free(nw);
+         pamlh_free(p);
+         return 0;
+      }
       if (pamlh_placement_scores(p, x, n_pend, pend, split, &l0, sc) || pamlh_place(p, x, n_pend, pend, split, be, bp, bl, lwr)) { fprintf(stderr, "error: %s\n", pamlh_error(p)); return 1; }
       printf("placement of %d quer%s on %d branches (one engine call): lnL of the tree = %.6f, split %.4f\n", nq, nq == 1 ? "y" : "ies", nb, l0, split);
       for (q = 0; q < nq; q++) {

@@ -65,6 +65,28 @@ int pamlh_edge_list(pamlh *p, int *n_edges, int *edges, int *five)
    return 0;
 }
 
+/* One row's move in the safeguarded Newton iteration along one length (pamlh_edge_optimize, pamlh_place_optimize), after the call that
+ * showed ln, d1 and d2 at the trial length *tn (trial 0: at the accepted length itself).  A trial that did not fall is accepted (*ti,
+ * *l) and Newton's step is proposed from its derivatives where d2 < 0, otherwise the length doubled or halved along the gradient; one
+ * that fell halves the step from the accepted length; the target is clipped to [lo, hi].  Returns 1 with the next trial in *tn, or 0
+ * with *tn = *ti when the row waits: the trials are used up or the step is below 1e-10. */
+int pamlh_newton_trial(int trial, int max_trials, double lo, double hi, double ln, double d1, double d2, double *l, double *ti, double *tn, double *step)
+{
+   double s, target;
+   if (trial == 0 || ln >= *l) {      /* the trial did not fall: accepted, and the next step comes from its derivatives */
+      *ti = *tn;
+      if (trial) *l = ln;
+      if (d2 < 0) s = -d1 / d2;
+      else s = d1 > 0 ? *ti : d1 < 0 ? -0.5 * *ti : 0.0;
+   }
+   else s = 0.5 * *step;                 /* it fell: half the step from the accepted length */
+   target = fmin(fmax(*ti + s, lo), hi);
+   *step = s = target - *ti;
+   if (trial == max_trials || fabs(s) < 1e-10) { *tn = *ti; return 0; }
+   *tn = target;
+   return 1;
+}
+
 int pamlh_edge_optimize(pamlh *p, const double *x, int n_edges, const int *edges, const int *five, double *t5_out, double *l_out, int *stats)
 {
    int rc, i, j, sweep = 0, calls = 0, n_rows = 3 * n_edges, role, trial, at_bound = 0, active;
@@ -108,19 +130,12 @@ int pamlh_edge_optimize(pamlh *p, const double *x, int n_edges, const int *edges
             EDGE_CALL(tt);
             active = 0;
             for (i = 0; i < n_rows; i++) {
-               double *ti = t + 5 * i + role, *tn = tt + 5 * i + role, s, target;
                if (wait[i]) continue;
-               if (trial == 0 || ln[i] >= l[i]) {      /* the trial did not fall: accepted, and the next step comes from its derivatives */
-                  *ti = *tn;
-                  if (trial) l[i] = ln[i];
-                  if (d2[i] < 0) s = -d1[i] / d2[i];
-                  else s = d1[i] > 0 ? *ti : d1[i] < 0 ? -0.5 * *ti : 0.0;
+               if (!pamlh_newton_trial(trial, EDGE_TRIALS, EDGE_T_LO, EDGE_T_HI, ln[i], d1[i], d2[i], l + i, t + 5 * i + role, tt + 5 * i + role, step + i)) {
+                  wait[i] = 1;
+                  rows[4 * i + 3] = -1;
+                  continue;
                }
-               else s = 0.5 * step[i];                 /* it fell: half the step from the accepted length */
-               target = fmin(fmax(*ti + s, EDGE_T_LO), EDGE_T_HI);
-               step[i] = s = target - *ti;
-               if (trial == EDGE_TRIALS || fabs(s) < 1e-10) { wait[i] = 1; rows[4 * i + 3] = -1; *tn = *ti; continue; }
-               *tn = target;
                active++;
             }
             if (!active) break;

@@ -629,6 +629,63 @@ class Analysis:
             raise RuntimeError("pamlh_placement_newick: " + self._L.pamlh_error(self._h).decode())
         return buf.value.decode()
 
+    def attach_scores(self, x, q, edge, role, t3):
+        """lnL, d1 and d2 of query q[i] hung on branch edge[i] (index into branch_order()) at the lengths t3[i] = (t_up, t_dn, t_pend),
+        the derivatives along the branch role[i] names (-1: none, 0: up, 1: dn, 2: pendant), from one engine call (pamlh_attach_scores):
+        dict(lnL0, lnL, d1, d2)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        qi, ed, ro = (np.ascontiguousarray(np.atleast_1d(a), dtype=np.int32) for a in (q, edge, role))
+        tt = np.ascontiguousarray(t3, dtype=np.float64).reshape(-1, 3)
+        n = len(qi)
+        l0, lnl, d1, d2 = C.c_double(), np.zeros(max(1, n)), np.zeros(max(1, n)), np.zeros(max(1, n))
+        f = self._L.pamlh_attach_scores
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(C.c_double)] + [C.c_void_p] * 3
+        p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        if len(x) != self.np or not (len(ed) == len(ro) == len(tt) == n) or f(self._h, p(x), n, p(qi), p(ed), p(ro), p(tt), C.byref(l0), p(lnl), p(d1), p(d2)) != 0:
+            raise RuntimeError("pamlh_attach_scores: " + self._L.pamlh_error(self._h).decode())
+        return dict(lnL0=l0.value, lnL=lnl[:n], d1=d1[:n], d2=d2[:n])
+
+    def place_optimize(self, x, q, edge, t3):
+        """Every row (q[i], edge[i]) maximised over its three attachment lengths from the start t3[i], all rows in lock step with one
+        engine call per Newton step (pamlh_place_optimize): dict(t3=[n_rows][3] the maximising lengths, lnL=[n_rows], sweeps, calls,
+        at_bound)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        qi, ed = (np.ascontiguousarray(np.atleast_1d(a), dtype=np.int32) for a in (q, edge))
+        tt = np.ascontiguousarray(t3, dtype=np.float64).reshape(-1, 3).copy()
+        n = len(qi)
+        lnl, stats = np.zeros(max(1, n)), (C.c_int * 3)()
+        f = self._L.pamlh_place_optimize
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        if len(x) != self.np or not (len(ed) == len(tt) == n) or f(self._h, p(x), n, p(qi), p(ed), p(tt), p(lnl), stats) != 0:
+            raise RuntimeError("pamlh_place_optimize: " + self._L.pamlh_error(self._h).decode())
+        return dict(t3=tt, lnL=lnl[:n], sweeps=stats[0], calls=stats[1], at_bound=stats[2])
+
+    def place_ml(self, x, keep=0, pendant=(0.05, 0.1, 0.2, 0.4), phi=0.5):
+        """Maximum-likelihood placement (pamlh_place_ml): the grid call, then per query its `keep` best branches (keep <= 0: all) maximised
+        over the three lengths at the new node: dict(q, edge (index into branch_order()), t3=[n_rows][3], lnL, lwr = [n_rows] — the
+        likelihood weight ratios over each query's kept rows)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        pe = np.ascontiguousarray(np.atleast_1d(pendant), dtype=np.float64)
+        cap = max(1, self.n_queries) * (self.n_nodes - 1)
+        rq, re, tt, lnl, lwr, n = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros((cap, 3)), np.zeros(cap), np.zeros(cap), C.c_int()
+        f = self._L.pamlh_place_ml
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double] + [C.c_void_p] * 5 + [C.POINTER(C.c_int)]
+        p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        if len(x) != self.np or f(self._h, p(x), int(keep), len(pe), p(pe), float(phi), p(rq), p(re), p(tt), p(lnl), p(lwr), C.byref(n)) != 0:
+            raise RuntimeError("pamlh_place_ml: " + self._L.pamlh_error(self._h).decode())
+        k = n.value
+        return dict(q=rq[:k], edge=re[:k], t3=tt[:k], lnL=lnl[:k], lwr=lwr[:k])
+
+    def placement_newick3(self, q, edge, t_up, t_dn, t_pend):
+        """The tree with query q hung on branch `edge` (index into branch_order()) with the three attachment lengths written in, the
+        other lengths those of the last x (pamlh_placement_newick3)."""
+        buf = C.create_string_buffer(160 * (self.n_nodes + 2) + 256)
+        self._L.pamlh_placement_newick3.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_char_p, C.c_int]
+        if self._L.pamlh_placement_newick3(self._h, int(q), int(edge), float(t_up), float(t_dn), float(t_pend), buf, len(buf)) != 0:
+            raise RuntimeError("pamlh_placement_newick3: " + self._L.pamlh_error(self._h).decode())
+        return buf.value.decode()
+
     def write_bv(self, x, path):
         """The gradient and Hessian of the branch lengths at x in the layout of the reference's rst2 block (pamlh_write_bv)."""
         x = np.ascontiguousarray(x, dtype=np.float64)
