@@ -1,8 +1,10 @@
 // ancestral_host.h — the host side that the calls walking a down pass and an outer pass over the whole tree share (defined in
-// engine_ancestral.hip; used there, by engine_gradient.hip, engine_curvature.hip, engine_nni.hip, engine_place.hip, engine_attach.hip and engine_spr.hip): the packed tree, P(t)
-// from the evaluation's own builders, the batch size and its workspace, the batch loop of the score calls, the rows' totals.
+// engine_ancestral.hip; used there, by the derivative calls and, through score_host.h, by the six score calls): the packed tree, P(t)
+// from the evaluation's own builders, the batch size and its workspace, the batch loop, the rows' totals.  What only the score calls
+// share — their refusals, row checks, workspace plan, batch loop and totals — is in score_host.h.
 #pragma once
 #include <initializer_list>
+#include <vector>
 #include <type_traits>
 
 #include "engine_state.h"
@@ -68,12 +70,12 @@ int anc_pmat_waited(paml_amd_engine *e, const char *who, const double *branch, c
 int anc_keep_pmat(paml_amd_engine *e, DevBuf<double> *pint, DevBuf<double> *ptip, DevBuf<double> *PT, DevBuf<double> &P);
 double anc_arena_mb(const char *env);
 long anc_batch(double bytes_per_patt, long n_patt, const char *env = "PAML_AMD_ANC_ARENA_MB");
-int anc_alloc(paml_amd_engine *e, const char *who, std::initializer_list<AncBatchBuf> bufs, long *batch);
+int anc_alloc(paml_amd_engine *e, const char *who, const std::vector<AncBatchBuf> &bufs, long *batch);
 void anc_fill(const paml_amd_engine *e, const AncScratch &w, long batch, AncMargArgs &m);
 std::vector<long> anc_chunk_base(const paml_amd_engine *e);
 int anc_totals(paml_amd_engine *e, AncScratch &w, const double *partial, long n_chunks, double *d_out, std::vector<double> &out);
 int anc_common_checks(paml_amd_engine *e, const char *who);
-int anc_begin(paml_amd_engine *e, const char *who, const char *unrest_reason);
+int anc_begin(paml_amd_engine *e, const char *who, const char *unrest_reason);      // (score_begin, score_host.h, and a tree without a branch)
 int grad_dpmat(paml_amd_engine *e, DevBuf<double> &dP, DevBuf<double> *d2P, DevBuf<double> &PT);
 
 // 4 / 5 / 20 states, the engines that are not on the matrix cores (paml_amd_create: every other state count is KK_MFMA64): f(N) with the
@@ -125,43 +127,6 @@ int anc_batches(paml_amd_engine *e, AncScratch &w, A &m, long *chunk0, long batc
          w.info.batches++;
       }
    return 0;
-}
-
-// The batch loop of the score calls (NNI, placement, SPR), on anc_batches.  The outer pass of the present tree is nni_mfma_outer_kernel
-// (matrix cores) or the caller's kernel, lane_pass(lanes, pass); then the caller's kernel for the present tree's row if it has one
-// (present(lanes)); then, as the batch's copies out, per group of rows the caller's row kernel (rows(gi, tiles, lanes), which also names
-// the group in its arguments), its combining kernel (combine(gi, lanes)) and its copies to the caller's arrays (copy_out(gi, h0, nb), an
-// error code).  A batch's first group is timed with its down and outer passes, every other by itself.
-template <class LanePass, class Present, class Rows, class Combine, class CopyOut>
-int anc_score_batches(paml_amd_engine *e, AncScratch &w, NniArgs &o, long batch, int n_groups, LanePass lane_pass, Present present, Rows rows, Combine combine,
-                      CopyOut copy_out)
-{
-   hipStream_t st = e->stream;
-   o.swap0 = 0; o.n_group = 0;      // (the passes and the present tree's row run with no group named)
-   return anc_batches(
-      e, w, o.m, &o.chunk0, batch, [&](const AncBatch &b) { hipLaunchKernelGGL(nni_mfma_outer_kernel, b.tiles, dim3(256), 0, st, o); },
-      [&](const AncBatch &b, int pass) { lane_pass(b.lanes, pass); },
-      [&](const AncBatch &b) {
-         present(b.lanes);
-         HIPCHK(hipGetLastError());
-         return 0;
-      },
-      [&](const AncBatch &b) {
-         for (int gi = 0; gi < n_groups; gi++) {
-            if (gi) {
-               HIPCHK(w.lap(st));
-               HIPCHK(hipEventRecord(w.ev0, st));
-            }
-            rows(gi, b.tiles, b.lanes);
-            HIPCHK(hipGetLastError());
-            combine(gi, b.lanes);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(w.ev1, st));
-            if (int rc = copy_out(gi, b.h0, b.nb)) return rc;
-         }
-         o.swap0 = 0; o.n_group = 0;
-         return 0;
-      });
 }
 
 }  // namespace paml_amd

@@ -1,12 +1,12 @@
 // engine_ancestral.hip — ancestral reconstruction at every internal node in one call: marginal (AncestralMarginal / PostProbNode,
 // treesub.c:6288, 6142) and joint (AncestralJointPPSG2000 treesub.c:6964); the definitions in kernels_ancestral.h, the kernels here.
 // P(t) comes from the evaluation's own builders (launch_pmat, engine_eval.hip).  Also the host side every whole-tree call shares
-// (ancestral_host.h).
+// (ancestral_host.h) and the one the score calls share on top of it (score_host.h).
 // Built for gfx950 only (one of the translation units of libpaml_amd.so, see engine_state.h).
 #include "engine_state.h"
 #include "kernels_ancestral.h"
 #include "kernels_curvature.h"
-#include "ancestral_host.h"
+#include "score_host.h"
 
 static thread_local AncCallInfo anc_info;
 
@@ -290,7 +290,7 @@ long anc_batch(double bytes_per_patt, long n_patt, const char *env)
 }
 
 // the batch workspace, in the order listed: the batch is halved until all of it fits
-int anc_alloc(paml_amd_engine *e, const char *who, std::initializer_list<AncBatchBuf> bufs, long *batch)
+int anc_alloc(paml_amd_engine *e, const char *who, const std::vector<AncBatchBuf> &bufs, long *batch)
 {
    for (;;) {
       bool ok = true;
@@ -344,16 +344,35 @@ int anc_common_checks(paml_amd_engine *e, const char *who)
 }
 
 
-// What the derivative calls refuse before they allocate, in this order: anc_common_checks, more than one rank, a rate-matrix (UNREST)
-// set with the caller's sentence for it (`unrest_reason`; null: such sets are allowed), a tree without a branch.
-int anc_begin(paml_amd_engine *e, const char *who, const char *unrest_reason)
+// What the score calls refuse before they allocate, in this order: anc_common_checks, more than one rank, a rate-matrix (UNREST) set
+// with the caller's sentence for it (`unrest_reason`; null: such sets are allowed).
+int score_begin(paml_amd_engine *e, const char *who, const char *unrest_reason)
 {
    if (int rc = anc_common_checks(e, who)) return rc;
    if (e->world > 1) return fail(e, PAML_AMD_EUNSUPPORTED, std::string(who) + ": one rank only (this engine's communicator has " + std::to_string(e->world) + ")");
    for (size_t i = 0; unrest_reason && i < e->eigen.size(); i++)
       if (e->eigen[i].kind == PAML_AMD_EIGEN_QMAT) return fail(e, PAML_AMD_EUNSUPPORTED, std::string(who) + ": " + unrest_reason);
+   return 0;
+}
+
+// What the derivative calls refuse: the same, then a tree without a branch.
+int anc_begin(paml_amd_engine *e, const char *who, const char *unrest_reason)
+{
+   if (int rc = score_begin(e, who, unrest_reason)) return rc;
    if (e->tree.n_nodes < 2) return fail(e, PAML_AMD_EINVAL, std::string(who) + ": the tree has no branch");
    return 0;
+}
+
+// what the kernels that build P(t) and its derivatives read of the engine (a call adds its own outputs)
+GradPmatArgs grad_pmat_args(const paml_amd_engine *e)
+{
+   GradPmatArgs ga{};
+   ga.n = e->n; ga.K = e->K; ga.n_nodes = e->tree.n_nodes; ga.n_tips = e->n_tips; ga.root = e->tree.root; ga.n_labels = e->n_labels;
+   ga.rate_gs = e->rate_per_gene ? e->K : 0; ga.mfma = e->kk == KK_MFMA64 ? 1 : 0;
+   ga.label = e->d_label.p; ga.eigen_of = e->d_eigen_of.p; ga.eigen = e->d_eigen.p;
+   ga.branch = e->d_branch.p; ga.rate = e->d_rate.p; ga.gene_rate = e->d_gene_rate.p; ga.qfactor = e->d_qfactor.p;
+   ga.P = e->d_rowmajor.p;
+   return ga;
 }
 
 // dP (and d2P when asked for: curv_pmat_kernel instead of grad_pmat_kernel) of every (parameter set, node) behind anc_pmat's P(t), and on
@@ -366,14 +385,132 @@ int grad_dpmat(paml_amd_engine *e, DevBuf<double> &dP, DevBuf<double> *d2P, DevB
    HIPCHK(dP.ensure(pn * each));
    if (d2P) HIPCHK(d2P->ensure(pn * each));
    if (mfma) HIPCHK(PT.ensure(pn * 4096));
-   GradPmatArgs ga{};
-   ga.n = n; ga.K = K; ga.n_nodes = nn; ga.n_tips = e->n_tips; ga.root = e->tree.root; ga.n_labels = e->n_labels; ga.rate_gs = e->rate_per_gene ? K : 0; ga.mfma = mfma ? 1 : 0;
-   ga.label = e->d_label.p; ga.eigen_of = e->d_eigen_of.p; ga.eigen = e->d_eigen.p;
-   ga.branch = e->d_branch.p; ga.rate = e->d_rate.p; ga.gene_rate = e->d_gene_rate.p; ga.qfactor = e->d_qfactor.p;
-   ga.P = e->d_rowmajor.p; ga.dP = dP.p; ga.PT = PT.p; ga.d2P = d2P ? d2P->p : nullptr;
+   GradPmatArgs ga = grad_pmat_args(e);
+   ga.dP = dP.p; ga.PT = PT.p; ga.d2P = d2P ? d2P->p : nullptr;
    if (d2P) hipLaunchKernelGGL(curv_pmat_kernel, dim3(nn, G * K), dim3(256), 0, e->stream, ga);
    else hipLaunchKernelGGL(grad_pmat_kernel, dim3(nn, G * K), dim3(256), 0, e->stream, ga);
    HIPCHK(hipGetLastError());
+   return 0;
+}
+
+// ---- the score calls' host side (score_host.h) ----------------------------------------------------------------------------------
+
+// [v] = the father of v (-1: none)
+std::vector<int> score_fathers(const TreeDesc &T)
+{
+   std::vector<int> father(T.n_nodes, -1);
+   for (int v = 0; v < T.n_nodes; v++)
+      for (int j = T.sons_ptr[v]; j < T.sons_ptr[v + 1]; j++) father[T.sons[j]] = v;
+   return father;
+}
+
+bool score_son_of(const TreeDesc &T, int s, int v)
+{
+   for (int j = T.sons_ptr[v]; j < T.sons_ptr[v + 1]; j++)
+      if (T.sons[j] == s) return true;
+   return false;
+}
+
+// the node v of a row (`at`: the message's prefix, "call: row i: "): refused out of range, as a tip where the call has no use for one, and
+// as the root (`father`: a node without a father counts as one; null: the tree's root only)
+int score_check_node(paml_amd_engine *e, const std::string &at, int v, const std::vector<int> *father, bool tips_refused)
+{
+   const TreeDesc &T = e->tree;
+   if (v < 0 || v >= T.n_nodes) return fail(e, PAML_AMD_EINVAL, at + "node " + std::to_string(v) + " is out of range");
+   if (tips_refused && T.is_leaf(v)) return fail(e, PAML_AMD_EINVAL, at + "node " + std::to_string(v) + " is a tip");
+   if (v == T.root || (father && (*father)[v] < 0)) return fail(e, PAML_AMD_EINVAL, at + "node " + std::to_string(v) + " is the root");
+   return 0;
+}
+
+// query qi's row of character codes ([.][n_patt] in qz) in the engine's own numbering, into the same place of dst
+int score_query_codes(paml_amd_engine *e, const std::string &prefix, int qi, const unsigned char *qz, unsigned char *dst)
+{
+   const long n_patt = e->n_patt;
+   for (long h = 0; h < n_patt; h++) {
+      const int c = qz[(size_t)qi * n_patt + h];
+      if (c >= e->n_codes || e->code_nch[c] < 1)
+         return fail(e, PAML_AMD_EINVAL, prefix + "query " + std::to_string(qi) + ", pattern " + std::to_string(h) + ": character code " + std::to_string(c) +
+                                             (c >= e->n_codes ? " >= n_codes" : " has an empty state set"));
+      dst[(size_t)qi * n_patt + h] = e->code_new_of[c];
+   }
+   return 0;
+}
+
+// The present tree's matrices: anc_pmat, and on the matrix cores P^T of the internal nodes (all_nodes: of every node but the root) behind
+// it.  The caller queues its own uploads and kernels, then anc_pmat_wait (what it uploads is on its stack), then sets pmat_valid.
+int score_present_pmat(paml_amd_engine *e, const char *who, const double *branch, const double *gene_rate, ScoreScratch &w, const int *d_label, bool all_nodes)
+{
+   if (int rc = anc_pmat(e, who, branch, gene_rate, w, d_label)) return rc;
+   if (e->kk != KK_MFMA64) return 0;
+   const int nn = e->tree.n_nodes, psets = e->n_genes * e->K;
+   HIPCHK(w.PT.ensure((size_t)psets * nn * 4096));
+   if (all_nodes) hipLaunchKernelGGL(nni_pt_all_kernel, dim3(nn, psets), dim3(256), 0, e->stream, (const double *)e->d_rowmajor.p, w.PT.p, e->n, nn, e->tree.root);
+   else hipLaunchKernelGGL(nni_pt_kernel, dim3(nn, psets), dim3(256), 0, e->stream, (const double *)e->d_rowmajor.p, w.PT.p, e->n, nn, e->n_tips, e->tree.root);
+   HIPCHK(hipGetLastError());
+   return 0;
+}
+
+// bytes per pattern of the partials and the messages of the tree (L, G, SL, SG); a partial takes 64 doubles on the matrix cores, else n
+double score_fixed(const paml_amd_engine *e)
+{
+   return 2.0 * e->K * (e->tree.n_nodes - e->n_tips) * ((e->kk == KK_MFMA64 ? 64 : e->n) + 1) * 8;
+}
+
+// The workspace plan of a score call, and `partial` / `out` ([n_out + 1] rows) sized.  Per pattern the workspace (`env` MiB) holds `fixed`
+// bytes (0: score_fixed) and per_row bytes for every row of a group and for the extra rows (the present tree's).  One tile of patterns
+// with all n_rows does not fit: groups of as many rows as one tile has room for, at least one; a group has 65535 rows at most (the lanes'
+// row pass has a grid layer per row).  cap > 0: the rows of a group by the caller's own rule.
+int score_plan(paml_amd_engine *e, ScoreScratch &w, ScorePlan *plan, const char *env, double per_row, int n_rows, long n_out, int extra_rows, double fixed, int cap)
+{
+   const int K = e->K, n_int = e->tree.n_nodes - e->n_tips;
+   plan->n_chunks = anc_chunk_base(e)[e->n_genes];
+   HIPCHK(w.partial.ensure((size_t)(n_out + 1) * std::max<long>(plan->n_chunks, 1)));
+   HIPCHK(w.out.ensure((size_t)n_out + 1));
+   if (fixed == 0) fixed = score_fixed(e);
+   if (!cap) {
+      const double arena_mb = anc_arena_mb(env);
+      cap = n_rows;
+      if ((fixed + per_row * (n_rows + extra_rows)) * ANC_TILE > arena_mb * 1048576.0)
+         cap = (int)std::min<double>(n_rows, std::max(1.0, floor((arena_mb * 1048576.0 / ANC_TILE - fixed) / per_row) - extra_rows));
+      cap = std::min(cap, 65535);
+   }
+   plan->cap = cap;
+   plan->batch = anc_batch(fixed + per_row * (cap + extra_rows), e->n_patt, env);
+   plan->part = (size_t)K * n_int * (e->kk == KK_MFMA64 ? 64 : e->n);
+   plan->sc = (size_t)K * n_int;
+   return 0;
+}
+
+// the batch workspace: L, G, SL, SG of the plan, then the call's own buffers (anc_alloc: the plan's batch is halved until all of it fits)
+int score_alloc(paml_amd_engine *e, const char *who, ScoreScratch &w, ScorePlan &plan, std::initializer_list<AncBatchBuf> own)
+{
+   std::vector<AncBatchBuf> bufs{{&w.L, plan.part}, {&w.G, plan.part}, {&w.SL, plan.sc}, {&w.SG, plan.sc}};
+   bufs.insert(bufs.end(), own.begin(), own.end());
+   return anc_alloc(e, who, bufs, &plan.batch);
+}
+
+// what the passes of the present tree and the combining kernels read: anc_fill, and the rows' workspace ([K][cap + 1][batch], row `cap`
+// the present tree's), the chunks' sums, the root's first son (where the present tree's f_hk is taken)
+void score_fill(NniArgs &o, const ScoreScratch &w, const paml_amd_engine *e, const ScorePlan &plan, int n_rows)
+{
+   anc_fill(e, w, plan.batch, o.m);
+   o.PT = w.PT.p; o.cap = plan.cap; o.n_swaps = n_rows; o.f = w.f.p; o.sig = w.sig.p; o.weights = e->d_weights.p;
+   o.lnf = w.lnf.p; o.partial = w.partial.p; o.n_chunks = plan.n_chunks;
+   o.ref_node = e->tree.sons[e->tree.sons_ptr[e->tree.root]];
+}
+
+// anc_totals of `partial` ([vals.size() n_rows + 1][n_chunks]: value d of row i at d n_rows + i, the present tree last), scattered:
+// vals[d][index_of[i]] (null: [i]) and *lnL0
+int score_totals(paml_amd_engine *e, ScoreScratch &w, const ScorePlan &plan, long n_rows, const int *index_of, double *lnL0, std::initializer_list<double *> vals)
+{
+   std::vector<double> out(vals.size() * (size_t)n_rows + 1);
+   if (int rc = anc_totals(e, w, w.partial.p, plan.n_chunks, w.out.p, out)) return rc;
+   size_t d = 0;
+   for (double *dst : vals) {
+      for (long i = 0; i < n_rows; i++) dst[index_of ? index_of[i] : i] = out[d * (size_t)n_rows + i];
+      d++;
+   }
+   *lnL0 = out.back();
    return 0;
 }
 

@@ -2,10 +2,11 @@
 // second derivative along one of them, in one call (paml_amd_edge_scores), and the list of edges that have the three configurations
 // (paml_amd_edge_list, host only); the definition in kernels_edge.h, the kernels here.  The tree's own P(t) comes from the evaluation's
 // builders (anc_pmat, engine_ancestral.hip), the down pass is the ancestral module's, the outer pass is the NNI call's.
+// The host side that is not this call's own is the score calls' skeleton (score_host.h, defined in engine_ancestral.hip).
 // Built for gfx950 only (one of the translation units of libpaml_amd.so, see engine_state.h).
 #include "engine_state.h"
 #include "kernels_edge.h"
-#include "ancestral_host.h"
+#include "score_host.h"
 
 static thread_local AncCallInfo edge_info;
 
@@ -68,13 +69,10 @@ __global__ __launch_bounds__(256) void edge_mfma_kernel(EdgeArgs a)
    __shared__ __attribute__((aligned(16))) double sP[4096];
    const AncMargArgs &m = a.o.m;
    const AncTree &t = m.t;
-   const int tid = threadIdx.x, lane = tid & 63, n = m.n;
-   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-   const int q = lane >> 4, k = blockIdx.y;
-   const AncMfma w{sP, lane, wave, q};
-   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
-   const long pc = p < m.nb ? p : m.nb - 1;      // (lanes past the batch's end read the last pattern and write into the padding: p < stride)
-   const long pset = (long)m.gene * m.K + k;
+   const ScoreTile c = score_tile(m);
+   const int lane = c.lane, q = c.q, k = c.k, n = m.n;
+   const long g16 = c.g16, p = c.p, pc = c.pc, pset = c.pset;
+   const AncMfma w{sP, lane, c.wave, q};
    for (int i = 0; i < a.o.n_group; i++) {
       const int gi = a.o.swap0 + i;
       const int *rw = a.rows + 4L * gi, *on = a.ovr_node + (long)EDGE_SLOTS * gi;
@@ -158,29 +156,10 @@ __global__ __launch_bounds__(256) void edge_mfma_kernel(EdgeArgs a)
    }
 }
 
-// the classes of every (row, pattern) and the chunks' sums of w lnf, w g1, w g2: grid (stride / 256, rows); a wave = one chunk of
-// GRAD_CHUNK patterns.  partial: [3 n_rows + 1][n_chunks] = lnL, d1, d2 of the rows, then the present tree.
+// the rows' chunks go to their place in the list (edge_combine_rows, kernels_edge.h)
 __global__ __launch_bounds__(256) void edge_combine_kernel(EdgeArgs a)
 {
-   const long p = (long)blockIdx.x * 256 + threadIdx.x;
-   const bool present = (int)blockIdx.y == a.o.n_group;      // (a batch's first group is launched with a row more: the present tree)
-   double acc[3] = {0, 0, 0};
-   if (p < a.o.m.nb) {
-      if (present) acc[0] = nni_combine(a.o, a.o.cap, p);
-      else edge_combine(a, (int)blockIdx.y, p, acc);
-   }
-#pragma unroll
-   for (int off = 32; off >= 1; off >>= 1) {
-      acc[0] += __shfl_xor(acc[0], off);
-      acc[1] += __shfl_xor(acc[1], off);
-      acc[2] += __shfl_xor(acc[2], off);
-   }
-   const long chunk = a.o.chunk0 + (p >> 6);
-   if ((threadIdx.x & 63) != 0 || (p & ~63L) >= a.o.m.nb) return;
-   const long nr = a.o.n_swaps;
-   if (present) { a.o.partial[3 * nr * a.o.n_chunks + chunk] = acc[0]; return; }
-   const long out_row = a.o.swap0 + blockIdx.y;
-   for (int d = 0; d < 3; d++) a.o.partial[(d * nr + out_row) * a.o.n_chunks + chunk] = acc[d];
+   edge_combine_rows(a, [&](int row) { return a.o.swap0 + row; });
 }
 }  // namespace paml_amd
 
@@ -225,9 +204,9 @@ extern "C" int paml_amd_edge_list(int n_tips, int n_nodes, int root, const int *
 
 namespace {
 
-struct EdgeScratch : AncScratch {
-   using AncScratch::AncScratch;
-   DevBuf<double> PT, OM, ovr_t, f, f1, f2, sig, lnf, g1, g2, partial, out;
+struct EdgeScratch : ScoreScratch {
+   using ScoreScratch::ScoreScratch;
+   DevBuf<double> OM, ovr_t, f1, f2, g1, g2;
    DevBuf<int> rows, ovr_node;
 };
 
@@ -241,32 +220,19 @@ extern "C" int paml_amd_edge_scores(paml_amd_engine *e, const double *branch, co
    const char *who = "edge_scores";
    if (!e || !branch || !rows || !ovr_node || !ovr_t || !lnL0 || !lnL || !d1 || !d2) return fail(e, PAML_AMD_EINVAL, "edge_scores: null argument");
    if (n_rows < 1) return fail(e, PAML_AMD_EINVAL, "edge_scores: n_rows < 1");
-   if (int rc = anc_common_checks(e, who)) return rc;
-   if (e->world > 1) return fail(e, PAML_AMD_EUNSUPPORTED, "edge_scores: one rank only (this engine's communicator has " + std::to_string(e->world) + ")");
-   for (size_t i = 0; i < e->eigen.size(); i++)
-      if (e->eigen[i].kind == PAML_AMD_EIGEN_QMAT)
-         return fail(e, PAML_AMD_EUNSUPPORTED, "edge_scores: the derivative of a rate-matrix (UNREST) set's P(t) needs a matrix product of its own");
+   if (int rc = score_begin(e, who, "the derivative of a rate-matrix (UNREST) set's P(t) needs a matrix product of its own")) return rc;
    const TreeDesc &T = e->tree;
-   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, n_tips = e->n_tips, n_int = nn - n_tips;
+   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes;
    {
-      std::vector<int> father(nn, -1);
-      for (int v = 0; v < nn; v++)
-         for (int j = T.sons_ptr[v]; j < T.sons_ptr[v + 1]; j++) father[T.sons[j]] = v;
-      auto son_of = [&](int s, int v) {
-         for (int j = T.sons_ptr[v]; j < T.sons_ptr[v + 1]; j++)
-            if (T.sons[j] == s) return true;
-         return false;
-      };
+      const std::vector<int> father = score_fathers(T);
       for (int i = 0; i < n_rows; i++) {
          const int v = rows[4 * i], s = rows[4 * i + 1], x = rows[4 * i + 2], u = rows[4 * i + 3];
          const std::string at = "edge_scores: row " + std::to_string(i) + ": ";
-         if (v < 0 || v >= nn) return fail(e, PAML_AMD_EINVAL, at + "node " + std::to_string(v) + " is out of range");
-         if (T.is_leaf(v)) return fail(e, PAML_AMD_EINVAL, at + "node " + std::to_string(v) + " is a tip");
-         if (v == T.root || father[v] < 0) return fail(e, PAML_AMD_EINVAL, at + "node " + std::to_string(v) + " is the root");
+         if (int rc = score_check_node(e, at, v, &father, true)) return rc;
          const int f = father[v];
          if (s != -1 || x != -1) {
-            if (!son_of(s, v)) return fail(e, PAML_AMD_EINVAL, at + std::to_string(s) + " is not a son of " + std::to_string(v));
-            if (x == v || !son_of(x, f))
+            if (!score_son_of(T, s, v)) return fail(e, PAML_AMD_EINVAL, at + std::to_string(s) + " is not a son of " + std::to_string(v));
+            if (x == v || !score_son_of(T, x, f))
                return fail(e, PAML_AMD_EINVAL, at + std::to_string(x) + " is not a son of the father of " + std::to_string(v) + " other than it");
          }
          bool u_listed = u == -1;
@@ -274,7 +240,7 @@ extern "C" int paml_amd_edge_scores(paml_amd_engine *e, const double *branch, co
             const int c = ovr_node[EDGE_SLOTS * i + j];
             if (c == -1) continue;
             if (c == f && f == T.root) return fail(e, PAML_AMD_EINVAL, at + "override node " + std::to_string(c) + " is the root: no branch above it");
-            if (c < 0 || c >= nn || !(c == v || c == f || son_of(c, v) || son_of(c, f)))
+            if (c < 0 || c >= nn || !(c == v || c == f || score_son_of(T, c, v) || score_son_of(T, c, f)))
                return fail(e, PAML_AMD_EINVAL, at + "override node " + std::to_string(c) + " is not a branch around the edge");
             for (int j2 = 0; j2 < j; j2++)
                if (ovr_node[EDGE_SLOTS * i + j2] == c) return fail(e, PAML_AMD_EINVAL, at + "override node " + std::to_string(c) + " is listed twice");
@@ -287,14 +253,9 @@ extern "C" int paml_amd_edge_scores(paml_amd_engine *e, const double *branch, co
    hipStream_t st = e->stream;
    EdgeScratch w(edge_info);
    EdgeArgs a{};
-   AncMargArgs &m = a.o.m;
-   if (int rc = anc_tree_pack(e, who, w, &m.t)) return rc;
-   if (int rc = anc_pmat(e, who, branch, gene_rate, w)) return rc;
-   if (mfma) {
-      HIPCHK(w.PT.ensure((size_t)G * K * nn * 4096));
-      hipLaunchKernelGGL(nni_pt_kernel, dim3(nn, G * K), dim3(256), 0, st, (const double *)e->d_rowmajor.p, w.PT.p, n, nn, n_tips, T.root);
-      HIPCHK(hipGetLastError());
-   }
+   NniArgs &o = a.o;
+   if (int rc = anc_tree_pack(e, who, w, &o.m.t)) return rc;
+   if (int rc = score_present_pmat(e, who, branch, gene_rate, w)) return rc;
    const long msz = mfma ? 4096 : (long)n * n;
    HIPCHK(upload(w.rows, rows, (size_t)4 * n_rows, st));
    HIPCHK(upload(w.ovr_node, ovr_node, (size_t)EDGE_SLOTS * n_rows, st));
@@ -302,69 +263,34 @@ extern "C" int paml_amd_edge_scores(paml_amd_engine *e, const double *branch, co
    HIPCHK(w.OM.ensure((size_t)n_rows * G * K * EDGE_MATS * msz));
    {
       EdgePmatArgs pa{};
-      GradPmatArgs &ga = pa.g;
-      ga.n = n; ga.K = K; ga.n_nodes = nn; ga.n_tips = n_tips; ga.root = T.root; ga.n_labels = e->n_labels; ga.rate_gs = e->rate_per_gene ? K : 0; ga.mfma = mfma ? 1 : 0;
-      ga.label = e->d_label.p; ga.eigen_of = e->d_eigen_of.p; ga.eigen = e->d_eigen.p;
-      ga.rate = e->d_rate.p; ga.gene_rate = e->d_gene_rate.p; ga.qfactor = e->d_qfactor.p;
-      pa.father = m.t.father; pa.rows = w.rows.p; pa.ovr_node = w.ovr_node.p; pa.ovr_t = w.ovr_t.p; pa.OM = w.OM.p; pa.msz = msz; pa.psets = G * K;
+      pa.g = grad_pmat_args(e);
+      pa.father = o.m.t.father; pa.rows = w.rows.p; pa.ovr_node = w.ovr_node.p; pa.ovr_t = w.ovr_t.p; pa.OM = w.OM.p; pa.msz = msz; pa.psets = G * K;
       hipLaunchKernelGGL(edge_pmat_kernel, dim3((unsigned)n_rows * EDGE_SLOTS, G * K), dim3(256), 0, st, pa);
       HIPCHK(hipGetLastError());
    }
    if (int rc = anc_pmat_wait(e, w)) return rc;
    e->pmat_valid = true;      // (d_rowmajor holds every branch's P(t) of the tree at `branch`, in the tree's own orientation, as after nni_scores)
 
-   const std::vector<long> chunk_base = anc_chunk_base(e);
-   const long n_chunks = chunk_base[G];
-   HIPCHK(w.partial.ensure((size_t)(3 * n_rows + 1) * std::max<long>(n_chunks, 1)));
-   HIPCHK(w.out.ensure((size_t)3 * n_rows + 1));
-
    // the workspace per pattern: the partials and the messages, then (4 K + 3) doubles per row (the rows of a group and the present tree)
-   const int ns = mfma ? 64 : n;      // doubles a partial takes per pattern
-   const double fixed = 2.0 * K * n_int * (ns + 1) * 8, per_row = (4.0 * K + 3) * 8;
-   const double arena_mb = anc_arena_mb("PAML_AMD_EDGE_ARENA_MB");
-   int cap = n_rows;
-   if ((fixed + per_row * (n_rows + 1)) * ANC_TILE > arena_mb * 1048576.0)      // one tile with all rows does not fit: groups of rows
-      cap = (int)std::min<double>(n_rows, std::max(1.0, floor((arena_mb * 1048576.0 / ANC_TILE - fixed) / per_row) - 1));
-   cap = std::min(cap, 65535);      // (the lanes' row pass has a grid row per row)
-   long batch = anc_batch(fixed + per_row * (cap + 1), e->n_patt, "PAML_AMD_EDGE_ARENA_MB");
-   {
-      const size_t part = (size_t)K * n_int * ns, sc = (size_t)K * n_int, kr = (size_t)K * (cap + 1), r1 = (size_t)cap + 1;
-      if (int rc = anc_alloc(e, who, {{&w.L, part}, {&w.G, part}, {&w.SL, sc}, {&w.SG, sc}, {&w.f, kr}, {&w.f1, kr}, {&w.f2, kr}, {&w.sig, kr}, {&w.lnf, r1}, {&w.g1, r1}, {&w.g2, r1}}, &batch))
-         return rc;
-   }
-   anc_fill(e, w, batch, m);
-   NniArgs &o = a.o;
-   o.PT = w.PT.p; o.cap = cap; o.n_swaps = n_rows; o.f = w.f.p; o.sig = w.sig.p; o.weights = e->d_weights.p;
-   o.lnf = w.lnf.p; o.partial = w.partial.p; o.n_chunks = n_chunks;
-   o.ref_node = T.sons[T.sons_ptr[T.root]];
+   ScorePlan plan;
+   if (int rc = score_plan(e, w, &plan, "PAML_AMD_EDGE_ARENA_MB", (4.0 * K + 3) * 8, n_rows, 3L * n_rows)) return rc;
+   const int cap = plan.cap;
+   const size_t kr = (size_t)K * (cap + 1), r1 = (size_t)cap + 1;
+   if (int rc = score_alloc(e, who, w, plan, {{&w.f, kr}, {&w.f1, kr}, {&w.f2, kr}, {&w.sig, kr}, {&w.lnf, r1}, {&w.g1, r1}, {&w.g2, r1}})) return rc;
+   score_fill(o, w, e, plan, n_rows);
    a.rows = w.rows.p; a.ovr_node = w.ovr_node.p; a.OM = w.OM.p; a.psets = G * K;
    a.f1 = w.f1.p; a.f2 = w.f2.p; a.g1 = w.g1.p; a.g2 = w.g2.p;
-   const long n_patt = e->n_patt;
-   auto group = [&](int gi) { o.swap0 = gi * cap; o.n_group = std::min(cap, n_rows - o.swap0); };      // groups of `cap` rows in list order
    if (int rc = anc_score_batches(
-          e, w, o, batch, (n_rows + cap - 1) / cap,
-          [&](dim3 lanes, int pass) { anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(nni_lane_kernel<N()>, lanes, dim3(256), 0, st, o, pass); }); },
-          [](dim3) {},      // (the present tree's row is combined with the batch's first group)
+          e, w, o, plan.batch, score_n_groups(n_rows, cap),
           [&](int gi, dim3 tiles, dim3 lanes) {
-             group(gi);
+             score_group(o, cap, n_rows, gi);
              if (mfma) hipLaunchKernelGGL(edge_mfma_kernel, tiles, dim3(256), 0, st, a);
              else anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(edge_lane_row_kernel<N()>, dim3(lanes.x, K, o.n_group), dim3(256), 0, st, a); });
           },
           [&](int gi, dim3 lanes) { hipLaunchKernelGGL(edge_combine_kernel, dim3(lanes.x, o.n_group + (gi == 0 ? 1 : 0)), dim3(256), 0, st, a); },
-          [&](int, long h0, long nb) {      // the group's rows to the caller's [n_rows][n_patt]: one plain copy per row
-             if (lnf)
-                for (int i = 0; i < o.n_group; i++)
-                   HIPCHK(hipMemcpyAsync(lnf + (size_t)(o.swap0 + i) * n_patt + h0, w.lnf.p + (size_t)i * batch, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-             return 0;
+          [&](int, long h0, long nb) {      // the group's rows to the caller's [n_rows][n_patt]
+             return score_copy_rows(e, w.lnf.p, plan.batch, o.swap0, o.n_group, lnf, h0, nb, [](long i) { return i; });
           }))
       return rc;
-   std::vector<double> out((size_t)3 * n_rows + 1);
-   if (int rc = anc_totals(e, w, w.partial.p, n_chunks, w.out.p, out)) return rc;
-   for (int i = 0; i < n_rows; i++) {
-      lnL[i] = out[i];
-      d1[i] = out[(size_t)n_rows + i];
-      d2[i] = out[(size_t)2 * n_rows + i];
-   }
-   *lnL0 = out[(size_t)3 * n_rows];
-   return 0;
+   return score_totals(e, w, plan, n_rows, nullptr, lnL0, {lnL, d1, d2});
 }

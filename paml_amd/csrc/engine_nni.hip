@@ -2,10 +2,11 @@
 // (paml_amd_nni_scores) and the canonical list of swaps (paml_amd_nni_list, host only); the definition in kernels_nni.h, the kernels here.
 // P(t) comes from the evaluation's own builders (anc_pmat, engine_ancestral.hip), the down pass is the ancestral module's, the outer
 // pass is the gradient's without the derivative.
+// The host side that is not this call's own is the score calls' skeleton (score_host.h, defined in engine_ancestral.hip).
 // Built for gfx950 only (one of the translation units of libpaml_amd.so, see engine_state.h).
 #include "engine_state.h"
 #include "kernels_nni.h"
-#include "ancestral_host.h"
+#include "score_host.h"
 
 static thread_local AncCallInfo nni_info;
 
@@ -124,13 +125,10 @@ __global__ __launch_bounds__(256) void nni_mfma_kernel(NniArgs a)
    __shared__ __attribute__((aligned(16))) double sP[4096];
    const AncMargArgs &m = a.m;
    const AncTree &t = m.t;
-   const int tid = threadIdx.x, lane = tid & 63, n = m.n;
-   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-   const int q = lane >> 4, k = blockIdx.y;
-   const AncMfma w{sP, lane, wave, q};
-   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
-   const long pc = p < m.nb ? p : m.nb - 1;      // (lanes past the batch's end read the last pattern and write into the padding: p < stride)
-   const long pset = (long)m.gene * m.K + k;
+   const ScoreTile c = score_tile(m);
+   const int lane = c.lane, q = c.q, k = c.k, n = m.n;
+   const long g16 = c.g16, p = c.p, pc = c.pc, pset = c.pset;
+   const AncMfma w{sP, lane, c.wave, q};
    for (int i = 0; i < a.n_group; i++) {
       const int *sw = a.swaps + 3L * (a.swap0 + i);
       const int v = sw[0], s = sw[1], x = sw[2], f = t.father[v];
@@ -161,12 +159,10 @@ __global__ __launch_bounds__(256) void nni_combine_kernel(NniArgs a)
    const long p = (long)blockIdx.x * 256 + threadIdx.x;
    const bool present = (int)blockIdx.y == a.n_group;      // (a batch's first group is launched with a row more: the present tree)
    const int row = present ? a.cap : (int)blockIdx.y;
-   double acc = p < a.m.nb ? nni_combine(a, row, p) : 0.0;
-#pragma unroll
-   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-   const long chunk = a.chunk0 + (p >> 6);
+   const double acc = score_wave_sum(p < a.m.nb ? nni_combine(a, row, p) : 0.0);
    const long out_row = present ? a.n_swaps : a.swap0 + row;
-   if ((threadIdx.x & 63) == 0 && (p & ~63L) < a.m.nb) a.partial[out_row * a.n_chunks + chunk] = acc;
+   long chunk;
+   if (score_chunk_lane(a, p, &chunk)) a.partial[out_row * a.n_chunks + chunk] = acc;
 }
 }  // namespace paml_amd
 
@@ -202,9 +198,8 @@ extern "C" int paml_amd_nni_list(int n_tips, int n_nodes, int root, const int *s
 
 namespace {
 
-struct NniScratch : AncScratch {
-   using AncScratch::AncScratch;
-   DevBuf<double> PT, f, sig, lnf, partial, out;
+struct NniScratch : ScoreScratch {
+   using ScoreScratch::ScoreScratch;
    DevBuf<int> swaps;
 };
 
@@ -218,27 +213,17 @@ extern "C" int paml_amd_nni_scores(paml_amd_engine *e, const double *branch, con
    const char *who = "nni_scores";
    if (!e || !branch || !swaps || !lnL0 || !lnL) return fail(e, PAML_AMD_EINVAL, "nni_scores: null argument");
    if (n_swaps < 1) return fail(e, PAML_AMD_EINVAL, "nni_scores: n_swaps < 1");
-   if (int rc = anc_common_checks(e, who)) return rc;
-   if (e->world > 1) return fail(e, PAML_AMD_EUNSUPPORTED, "nni_scores: one rank only (this engine's communicator has " + std::to_string(e->world) + ")");
+   if (int rc = score_begin(e, who, nullptr)) return rc;
    const TreeDesc &T = e->tree;
-   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, n_tips = e->n_tips, n_int = nn - n_tips;
+   const int K = e->K;
    {
-      std::vector<int> father(nn, -1);
-      for (int v = 0; v < nn; v++)
-         for (int j = T.sons_ptr[v]; j < T.sons_ptr[v + 1]; j++) father[T.sons[j]] = v;
-      auto son_of = [&](int s, int v) {
-         for (int j = T.sons_ptr[v]; j < T.sons_ptr[v + 1]; j++)
-            if (T.sons[j] == s) return true;
-         return false;
-      };
+      const std::vector<int> father = score_fathers(T);
       for (int i = 0; i < n_swaps; i++) {
          const int v = swaps[3 * i], s = swaps[3 * i + 1], x = swaps[3 * i + 2];
          const std::string at = "nni_scores: swap " + std::to_string(i) + ": ";
-         if (v < 0 || v >= nn) return fail(e, PAML_AMD_EINVAL, at + "node " + std::to_string(v) + " is out of range");
-         if (T.is_leaf(v)) return fail(e, PAML_AMD_EINVAL, at + "node " + std::to_string(v) + " is a tip");
-         if (v == T.root || father[v] < 0) return fail(e, PAML_AMD_EINVAL, at + "node " + std::to_string(v) + " is the root");
-         if (!son_of(s, v)) return fail(e, PAML_AMD_EINVAL, at + std::to_string(s) + " is not a son of " + std::to_string(v));
-         if (x == v || !son_of(x, father[v]))
+         if (int rc = score_check_node(e, at, v, &father, true)) return rc;
+         if (!score_son_of(T, s, v)) return fail(e, PAML_AMD_EINVAL, at + std::to_string(s) + " is not a son of " + std::to_string(v));
+         if (x == v || !score_son_of(T, x, father[v]))
             return fail(e, PAML_AMD_EINVAL, at + std::to_string(x) + " is not a son of the father of " + std::to_string(v) + " other than it");
       }
    }
@@ -246,62 +231,31 @@ extern "C" int paml_amd_nni_scores(paml_amd_engine *e, const double *branch, con
    hipStream_t st = e->stream;
    NniScratch w(nni_info);
    NniArgs a{};
-   AncMargArgs &m = a.m;
-   if (int rc = anc_tree_pack(e, who, w, &m.t)) return rc;
-   if (int rc = anc_pmat(e, who, branch, gene_rate, w)) return rc;
-   if (mfma) {
-      HIPCHK(w.PT.ensure((size_t)G * K * nn * 4096));
-      hipLaunchKernelGGL(nni_pt_kernel, dim3(nn, G * K), dim3(256), 0, st, (const double *)e->d_rowmajor.p, w.PT.p, n, nn, n_tips, T.root);
-      HIPCHK(hipGetLastError());
-   }
+   if (int rc = anc_tree_pack(e, who, w, &a.m.t)) return rc;
+   if (int rc = score_present_pmat(e, who, branch, gene_rate, w)) return rc;
    HIPCHK(upload(w.swaps, swaps, (size_t)3 * n_swaps, st));
    if (int rc = anc_pmat_wait(e, w)) return rc;
    e->pmat_valid = true;      // (d_rowmajor holds every branch's P(t) in the tree's own orientation, as after the gradient)
 
-   const std::vector<long> chunk_base = anc_chunk_base(e);
-   const long n_chunks = chunk_base[G];
-   HIPCHK(w.partial.ensure((size_t)(n_swaps + 1) * std::max<long>(n_chunks, 1)));
-   HIPCHK(w.out.ensure((size_t)n_swaps + 1));
-
    // the workspace per pattern: the partials and the messages, then (2 K + 1) doubles per row (the swaps of a group and the present tree)
-   const int ns = mfma ? 64 : n;      // doubles a partial takes per pattern
-   const double fixed = 2.0 * K * n_int * (ns + 1) * 8, per_row = (2.0 * K + 1) * 8;
-   const double arena_mb = anc_arena_mb("PAML_AMD_NNI_ARENA_MB");
-   int cap = n_swaps;
-   if ((fixed + per_row * (n_swaps + 1)) * ANC_TILE > arena_mb * 1048576.0)      // one tile with all swaps does not fit: groups of swaps
-      cap = (int)std::min<double>(n_swaps, std::max(1.0, floor((arena_mb * 1048576.0 / ANC_TILE - fixed) / per_row) - 1));
-   cap = std::min(cap, 65535);      // (the lanes' swap pass has a grid row per swap)
-   long batch = anc_batch(fixed + per_row * (cap + 1), e->n_patt, "PAML_AMD_NNI_ARENA_MB");
-   {
-      const size_t part = (size_t)K * n_int * ns, sc = (size_t)K * n_int, rows = (size_t)K * (cap + 1);
-      if (int rc = anc_alloc(e, who, {{&w.L, part}, {&w.G, part}, {&w.SL, sc}, {&w.SG, sc}, {&w.f, rows}, {&w.sig, rows}, {&w.lnf, (size_t)cap + 1}}, &batch)) return rc;
-   }
-   anc_fill(e, w, batch, m);
-   a.PT = w.PT.p; a.swaps = w.swaps.p; a.cap = cap; a.n_swaps = n_swaps; a.f = w.f.p; a.sig = w.sig.p; a.weights = e->d_weights.p;
-   a.lnf = w.lnf.p; a.partial = w.partial.p; a.n_chunks = n_chunks;
-   a.ref_node = T.sons[T.sons_ptr[T.root]];
-   const long n_patt = e->n_patt;
-   auto group = [&](int gi) { a.swap0 = gi * cap; a.n_group = std::min(cap, n_swaps - a.swap0); };      // groups of `cap` swaps in list order
+   ScorePlan plan;
+   if (int rc = score_plan(e, w, &plan, "PAML_AMD_NNI_ARENA_MB", (2.0 * K + 1) * 8, n_swaps, n_swaps)) return rc;
+   const int cap = plan.cap;
+   const size_t rows = (size_t)K * (cap + 1);
+   if (int rc = score_alloc(e, who, w, plan, {{&w.f, rows}, {&w.sig, rows}, {&w.lnf, (size_t)cap + 1}})) return rc;
+   score_fill(a, w, e, plan, n_swaps);
+   a.swaps = w.swaps.p;
    if (int rc = anc_score_batches(
-          e, w, a, batch, (n_swaps + cap - 1) / cap,
-          [&](dim3 lanes, int pass) { anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(nni_lane_kernel<N()>, lanes, dim3(256), 0, st, a, pass); }); },
-          [](dim3) {},      // (the present tree's row is combined with the batch's first group)
+          e, w, a, plan.batch, score_n_groups(n_swaps, cap),
           [&](int gi, dim3 tiles, dim3 lanes) {
-             group(gi);
+             score_group(a, cap, n_swaps, gi);
              if (mfma) hipLaunchKernelGGL(nni_mfma_kernel, tiles, dim3(256), 0, st, a);
              else anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(nni_lane_swap_kernel<N()>, dim3(lanes.x, K, a.n_group), dim3(256), 0, st, a); });
           },
           [&](int gi, dim3 lanes) { hipLaunchKernelGGL(nni_combine_kernel, dim3(lanes.x, a.n_group + (gi == 0 ? 1 : 0)), dim3(256), 0, st, a); },
-          [&](int, long h0, long nb) {      // the group's rows to the caller's [n_swaps][n_patt]: one plain copy per swap
-             if (lnf)
-                for (int i = 0; i < a.n_group; i++)
-                   HIPCHK(hipMemcpyAsync(lnf + (size_t)(a.swap0 + i) * n_patt + h0, w.lnf.p + (size_t)i * batch, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-             return 0;
+          [&](int, long h0, long nb) {      // the group's rows to the caller's [n_swaps][n_patt]
+             return score_copy_rows(e, w.lnf.p, plan.batch, a.swap0, a.n_group, lnf, h0, nb, [](long i) { return i; });
           }))
       return rc;
-   std::vector<double> out((size_t)n_swaps + 1);
-   if (int rc = anc_totals(e, w, w.partial.p, n_chunks, w.out.p, out)) return rc;
-   for (int i = 0; i < n_swaps; i++) lnL[i] = out[i];
-   *lnL0 = out[n_swaps];
-   return 0;
+   return score_totals(e, w, plan, n_swaps, nullptr, lnL0, {lnL});
 }

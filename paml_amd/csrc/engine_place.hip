@@ -4,10 +4,11 @@
 // parts (1 - phi) t_v, the lower parts phi t_v, the pendant lengths (in the slots of the tips, every node labelled pendant_label), and last
 // the tree's own lengths, so that d_rowmajor and pmat_valid are left as after paml_amd_nni_scores.  The down pass is the ancestral
 // module's, the outer pass is the NNI module's.
+// The host side that is not this call's own is the score calls' skeleton (score_host.h, defined in engine_ancestral.hip).
 // Built for gfx950 only (one of the translation units of libpaml_amd.so, see engine_state.h).
 #include "engine_state.h"
 #include "kernels_place.h"
-#include "ancestral_host.h"
+#include "score_host.h"
 
 static thread_local AncCallInfo place_info;
 
@@ -31,20 +32,15 @@ __global__ __launch_bounds__(256) void place_mfma_kernel(PlaceArgs a)
    __shared__ __attribute__((aligned(16))) double sP[4096];
    const AncMargArgs &m = a.o.m;
    const AncTree &t = m.t;
-   const int tid = threadIdx.x, lane = tid & 63;
-   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-   const int q = lane >> 4, k = blockIdx.y;
-   const AncMfma w{sP, lane, wave, q};
-   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
-   const long pc = p < m.nb ? p : m.nb - 1;      // (lanes past the batch's end read the last pattern and write into the padding: p < stride)
-   const long pset = (long)m.gene * m.K + k;
+   const ScoreTile c = score_tile(m);
+   const int lane = c.lane, q = c.q, k = c.k;
+   const long g16 = c.g16, p = c.p, pc = c.pc, pset = c.pset;
+   const AncMfma w{sP, lane, c.wave, q};
    const double *tabs = a.ptip_pend + pset * a.n_pend * m.tip_words;
    for (int i = 0; i < a.n_group; i++) {
-      const int v = a.edges[a.edge0 + i], f = t.father[v];
+      const int v = a.edges[a.edge0 + i];
       double h[16], u[16], ls;
-      nni_mfma_father(m, k, g16, pc, lane, q, f, h, &ls);
-      for (int j = t.sons_ptr[f]; j < t.sons_ptr[f + 1]; j++)
-         if (t.sons[j] != v) anc_mfma_mul_son(m, w, k, g16, pc, t.sons[j], h, &ls);
+      score_mfma_hv(m, w, c, v, h, &ls);
       const long slot = pset * t.n_nodes + v;
       v4d acc[4];
       w.product(a.PTup + slot * 4096, h, acc);      // U_v = P_v((1 - phi) t)^T H_v
@@ -87,30 +83,26 @@ __global__ __launch_bounds__(256) void place_combine_kernel(PlaceArgs a, long ro
 {
    const long p = (long)blockIdx.x * 256 + threadIdx.x;
    const long row = row0 + blockIdx.y;
-   double acc = p < a.o.m.nb ? place_combine(a, row, p) : 0.0;
-#pragma unroll
-   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-   const long chunk = a.o.chunk0 + (p >> 6);
-   if ((threadIdx.x & 63) == 0 && (p & ~63L) < a.o.m.nb) a.partial[place_out_row(a, row) * a.o.n_chunks + chunk] = acc;
+   const double acc = score_wave_sum(p < a.o.m.nb ? place_combine(a, row, p) : 0.0);
+   long chunk;
+   if (score_chunk_lane(a.o, p, &chunk)) a.partial[place_out_row(a, row) * a.o.n_chunks + chunk] = acc;
 }
 
 // the present tree's row (the outer pass left f_hk and sigma in o.f / o.sig): grid (stride / 256)
 __global__ __launch_bounds__(256) void place_present_kernel(PlaceArgs a)
 {
    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-   double acc = p < a.o.m.nb ? nni_combine(a.o, 0, p) : 0.0;
-#pragma unroll
-   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-   const long chunk = a.o.chunk0 + (p >> 6);
-   if ((threadIdx.x & 63) == 0 && (p & ~63L) < a.o.m.nb) a.partial[(long)a.n_q * a.n_edges * a.n_pend * a.o.n_chunks + chunk] = acc;
+   const double acc = score_wave_sum(p < a.o.m.nb ? nni_combine(a.o, 0, p) : 0.0);
+   long chunk;
+   if (score_chunk_lane(a.o, p, &chunk)) a.partial[(long)a.n_q * a.n_edges * a.n_pend * a.o.n_chunks + chunk] = acc;
 }
 }  // namespace paml_amd
 
 namespace {
 
-struct PlaceScratch : AncScratch {
-   using AncScratch::AncScratch;
-   DevBuf<double> PT, Pup, Pdn, PTup, pint_dn, ptip_dn, Ppend, ptip_pend, f0, sig0, lnf0, f, sig, lnf, partial, out;
+struct PlaceScratch : ScoreScratch {      // (f, sig, lnf: the present tree's row; rf, rsig, rlnf: the rows of a group)
+   using ScoreScratch::ScoreScratch;
+   DevBuf<double> Pup, Pdn, PTup, pint_dn, ptip_dn, Ppend, ptip_pend, rf, rsig, rlnf;
    DevBuf<int> edges, lab;
    DevBuf<unsigned char> qz;
 };
@@ -128,18 +120,15 @@ extern "C" int paml_amd_placement_scores(paml_amd_engine *e, const double *branc
    if (n_q < 1) return fail(e, PAML_AMD_EINVAL, "placement_scores: n_q < 1");
    if (n_edges < 1) return fail(e, PAML_AMD_EINVAL, "placement_scores: n_edges < 1");
    if (n_pend < 1) return fail(e, PAML_AMD_EINVAL, "placement_scores: n_pend < 1");
-   if (int rc = anc_common_checks(e, who)) return rc;
-   if (e->world > 1) return fail(e, PAML_AMD_EUNSUPPORTED, "placement_scores: one rank only (this engine's communicator has " + std::to_string(e->world) + ")");
+   if (int rc = score_begin(e, who, nullptr)) return rc;
    const TreeDesc &T = e->tree;
-   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, n_tips = e->n_tips, n_int = nn - n_tips;
+   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, n_tips = e->n_tips;
    const long n_patt = e->n_patt;
    std::vector<int> edge_list;
    if (edges) {
       for (int i = 0; i < n_edges; i++) {
          const int v = edges[i];
-         const std::string at = "placement_scores: edge " + std::to_string(i) + ": ";
-         if (v < 0 || v >= nn) return fail(e, PAML_AMD_EINVAL, at + "node " + std::to_string(v) + " is out of range");
-         if (v == T.root) return fail(e, PAML_AMD_EINVAL, at + "node " + std::to_string(v) + " is the root");
+         if (int rc = score_check_node(e, "placement_scores: edge " + std::to_string(i) + ": ", v, nullptr, false)) return rc;
       }
       edge_list.assign(edges, edges + n_edges);
    }
@@ -158,13 +147,7 @@ extern "C" int paml_amd_placement_scores(paml_amd_engine *e, const double *branc
    // the queries' codes in the engine's own numbering
    std::vector<unsigned char> qcodes((size_t)n_q * n_patt);
    for (int qi = 0; qi < n_q; qi++)
-      for (long h = 0; h < n_patt; h++) {
-         const int c = qz[(size_t)qi * n_patt + h];
-         if (c >= e->n_codes || e->code_nch[c] < 1)
-            return fail(e, PAML_AMD_EINVAL, "placement_scores: query " + std::to_string(qi) + ", pattern " + std::to_string(h) + ": character code " + std::to_string(c) +
-                                                (c >= e->n_codes ? " >= n_codes" : " has an empty state set"));
-         qcodes[(size_t)qi * n_patt + h] = e->code_new_of[c];
-      }
+      if (int rc = score_query_codes(e, "placement_scores: ", qi, qz, qcodes.data())) return rc;
    std::vector<int> slots;      // where a pendant length's P(t) is built: the tips (their column tables are made for leaves only)
    for (int v = 0; v < n_tips; v++)
       if (v != T.root && T.is_leaf(v)) slots.push_back(v);
@@ -177,7 +160,7 @@ extern "C" int paml_amd_placement_scores(paml_amd_engine *e, const double *branc
    NniArgs &o = a.o;
    AncMargArgs &m = o.m;
    if (int rc = anc_tree_pack(e, who, w, &m.t)) return rc;
-   const size_t psets = (size_t)G * K, pn = psets * nn, nn2 = (size_t)n * n, tw = tip_words(e);
+   const size_t psets = (size_t)G * K, nn2 = (size_t)n * n, tw = tip_words(e);
    {
       // the upper and the lower part of every branch
       std::vector<double> b(nn);
@@ -208,52 +191,29 @@ extern "C" int paml_amd_placement_scores(paml_amd_engine *e, const double *branc
       }
    }
    // the tree's own lengths last: what the passes read, and what the engine keeps
-   if (int rc = anc_pmat(e, who, branch, gene_rate, w)) return rc;
-   if (mfma) {
-      HIPCHK(w.PT.ensure(pn * 4096));
-      hipLaunchKernelGGL(nni_pt_kernel, dim3(nn, (unsigned)psets), dim3(256), 0, st, (const double *)e->d_rowmajor.p, w.PT.p, n, nn, n_tips, T.root);
-      HIPCHK(hipGetLastError());
-   }
+   if (int rc = score_present_pmat(e, who, branch, gene_rate, w)) return rc;
    HIPCHK(upload(w.edges, edge_list.data(), edge_list.size(), st));
    HIPCHK(upload(w.qz, qcodes.data(), qcodes.size(), st));
    if (int rc = anc_pmat_wait(e, w)) return rc;
    e->pmat_valid = true;      // (d_rowmajor holds every branch's P(t) in the tree's own orientation, as after the gradient)
 
-   const std::vector<long> chunk_base = anc_chunk_base(e);
-   const long n_chunks = chunk_base[G];
-   const long rows_edge = (long)n_q * n_pend, n_rows = rows_edge * n_edges;
-   HIPCHK(w.partial.ensure((size_t)(n_rows + 1) * std::max<long>(n_chunks, 1)));
-   HIPCHK(w.out.ensure((size_t)n_rows + 1));
-
    // the workspace per pattern: the partials and the messages, then (2 K + 1) doubles per row (the present tree's, and n_q n_pend per edge of a group)
-   const int ns = mfma ? 64 : n;      // doubles a partial takes per pattern
-   const double fixed = 2.0 * K * n_int * (ns + 1) * 8 + (2.0 * K + 1) * 8, per_edge = (2.0 * K + 1) * 8 * rows_edge;
-   const double arena_mb = anc_arena_mb("PAML_AMD_PLACE_ARENA_MB");
-   int cap = n_edges;
-   if ((fixed + per_edge * n_edges) * ANC_TILE > arena_mb * 1048576.0)      // one tile with all rows does not fit: groups of edges
-      cap = (int)std::min<double>(n_edges, std::max(1.0, floor((arena_mb * 1048576.0 / ANC_TILE - fixed) / per_edge)));
-   cap = std::min(cap, 65535);      // (the lanes' edge pass has a grid layer per edge)
-   long batch = anc_batch(fixed + per_edge * cap, n_patt, "PAML_AMD_PLACE_ARENA_MB");
-   {
-      const size_t part = (size_t)K * n_int * ns, sc = (size_t)K * n_int, rows = (size_t)K * cap * rows_edge;
-      if (int rc = anc_alloc(e, who, {{&w.L, part}, {&w.G, part}, {&w.SL, sc}, {&w.SG, sc}, {&w.f0, (size_t)K}, {&w.sig0, (size_t)K}, {&w.lnf0, 1},
-                                      {&w.f, rows}, {&w.sig, rows}, {&w.lnf, (size_t)cap * rows_edge}}, &batch))
-         return rc;
-   }
-   anc_fill(e, w, batch, m);
-   o.PT = w.PT.p; o.cap = 0; o.f = w.f0.p; o.sig = w.sig0.p; o.weights = e->d_weights.p; o.lnf = w.lnf0.p; o.n_chunks = n_chunks;
-   o.ref_node = T.sons[T.sons_ptr[T.root]];
+   const long rows_edge = (long)n_q * n_pend, n_rows = rows_edge * n_edges;
+   const double per_row = (2.0 * K + 1) * 8;
+   ScorePlan plan;
+   // (the edges are what is grouped; no extra row: the present tree's is counted in the fixed part)
+   if (int rc = score_plan(e, w, &plan, "PAML_AMD_PLACE_ARENA_MB", per_row * rows_edge, n_edges, n_rows, 0, score_fixed(e) + per_row)) return rc;
+   const int cap = plan.cap;      // edges of a group (the lanes' edge pass has a grid layer per edge)
+   const size_t rows = (size_t)K * cap * rows_edge;
+   if (int rc = score_alloc(e, who, w, plan, {{&w.f, (size_t)K}, {&w.sig, (size_t)K}, {&w.lnf, 1}, {&w.rf, rows}, {&w.rsig, rows}, {&w.rlnf, (size_t)cap * rows_edge}})) return rc;
+   score_fill(o, w, e, plan, 0);
+   o.cap = 0;      // (the passes' workspace is the present tree's row alone; the groups' rows are PlaceArgs's own)
    a.Pup = w.Pup.p; a.Pdn = w.Pdn.p; a.PTup = w.PTup.p; a.pint_dn = w.pint_dn.p; a.ptip_dn = w.ptip_dn.p; a.Ppend = w.Ppend.p; a.ptip_pend = w.ptip_pend.p;
    a.qz = w.qz.p; a.edges = w.edges.p; a.n_q = n_q; a.n_pend = n_pend; a.n_edges = n_edges; a.cap = cap;
-   a.f = w.f.p; a.sig = w.sig.p; a.lnf = w.lnf.p; a.partial = w.partial.p;
+   a.f = w.rf.p; a.sig = w.rsig.p; a.lnf = w.rlnf.p; a.partial = w.partial.p;
    auto group = [&](int gi) { a.edge0 = gi * cap; a.n_group = std::min(cap, n_edges - a.edge0); };      // groups of `cap` edges in list order
    if (int rc = anc_score_batches(
-          e, w, o, batch, (n_edges + cap - 1) / cap,
-          [&](dim3 lanes, int pass) { anc_lanes(e->kk, [&](auto N) { hipLaunchKernelGGL(nni_lane_kernel<N()>, lanes, dim3(256), 0, st, o, pass); }); },
-          [&](dim3 lanes) {
-             a.edge0 = 0; a.n_group = 0;
-             hipLaunchKernelGGL(place_present_kernel, dim3(lanes.x), dim3(256), 0, st, a);
-          },
+          e, w, o, plan.batch, score_n_groups(n_edges, cap),
           [&](int gi, dim3 tiles, dim3 lanes) {
              group(gi);
              if (mfma) hipLaunchKernelGGL(place_mfma_kernel, tiles, dim3(256), 0, st, a);
@@ -264,16 +224,13 @@ extern "C" int paml_amd_placement_scores(paml_amd_engine *e, const double *branc
              for (long r0 = 0; r0 < rows; r0 += 65535)
                 hipLaunchKernelGGL(place_combine_kernel, dim3(lanes.x, (unsigned)std::min<long>(65535, rows - r0)), dim3(256), 0, st, a, r0);
           },
-          [&](int, long h0, long nb) {      // the group's rows to the caller's [n_q][n_edges][n_pend][n_patt]: one plain copy per row
-             if (lnf)
-                for (long r = 0; r < rows_edge * a.n_group; r++)
-                   HIPCHK(hipMemcpyAsync(lnf + (size_t)place_out_row(a, r) * n_patt + h0, w.lnf.p + (size_t)r * batch, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-             return 0;
+          [&](int, long h0, long nb) {      // the group's rows to the caller's [n_q][n_edges][n_pend][n_patt]
+             return score_copy_rows(e, w.rlnf.p, plan.batch, 0, rows_edge * a.n_group, lnf, h0, nb, [&](long r) { return place_out_row(a, r); });
+          },
+          [&](dim3 lanes) {      // the present tree's row, by a kernel of its own
+             a.edge0 = 0; a.n_group = 0;
+             hipLaunchKernelGGL(place_present_kernel, dim3(lanes.x), dim3(256), 0, st, a);
           }))
       return rc;
-   std::vector<double> out((size_t)n_rows + 1);
-   if (int rc = anc_totals(e, w, w.partial.p, n_chunks, w.out.p, out)) return rc;
-   for (long i = 0; i < n_rows; i++) lnL[i] = out[i];
-   *lnL0 = out[n_rows];
-   return 0;
+   return score_totals(e, w, plan, n_rows, nullptr, lnL0, {lnL});
 }

@@ -5,10 +5,11 @@
 // vector of the tree's size with the tree's own labels: the upper parts (1 - phi) t_v, the lower parts phi t_v, the merged lengths
 // t_v + t_father(v) stored at v, and last the tree's own lengths, so that d_rowmajor and pmat_valid are left as after
 // paml_amd_nni_scores.  The down pass is the ancestral module's, the outer pass is the NNI module's.
+// The host side that is not this call's own is the score calls' skeleton (score_host.h, defined in engine_ancestral.hip).
 // Built for gfx950 only (one of the translation units of libpaml_amd.so, see engine_state.h).
 #include "engine_state.h"
 #include "kernels_spr.h"
-#include "ancestral_host.h"
+#include "score_host.h"
 
 static thread_local AncCallInfo spr_info;
 
@@ -35,13 +36,10 @@ __global__ __launch_bounds__(256) void spr_mfma_kernel(SprArgs a)
    __shared__ __attribute__((aligned(16))) double sP[4096];
    const AncMargArgs &m = a.o.m;
    const AncTree &t = m.t;
-   const int tid = threadIdx.x, lane = tid & 63, n = m.n;
-   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-   const int q = lane >> 4, k = blockIdx.y;
-   const AncMfma w{sP, lane, wave, q};
-   const long g16 = (long)blockIdx.x * 4 + wave, p = g16 * 16 + (lane & 15);
-   const long pc = p < m.nb ? p : m.nb - 1;      // (lanes past the batch's end read the last pattern and write into the padding: p < stride)
-   const long pset = (long)m.gene * m.K + k;
+   const ScoreTile c = score_tile(m);
+   const int lane = c.lane, q = c.q, k = c.k, n = m.n;
+   const long g16 = c.g16, p = c.p, pc = c.pc, pset = c.pset;
+   const AncMfma w{sP, lane, c.wave, q};
    const long part = (long)k * t.n_int * (m.stride >> 4) + g16, sc = (long)k * t.n_int * m.stride;      // (+ node * (stride >> 4), * 1024; + node * stride)
    for (int ip = a.prune0; ip < a.prune0 + a.n_prunes; ip++) {
       const int *pr = a.prunes + (long)SPR_PRUNE_INTS * ip;
@@ -108,9 +106,9 @@ extern "C" int paml_amd_spr_list(int n_tips, int n_nodes, int root, const int *s
 
 namespace {
 
-struct SprScratch : AncScratch {
-   using AncScratch::AncScratch;
-   DevBuf<double> PT, Pup, Pdn, Pm, PTup, pint_dn, ptip_dn, pint_m, ptip_m, PTm, Lp, Ap, SLp, SAp, f, sig, lnf, partial, out;
+struct SprScratch : ScoreScratch {
+   using ScoreScratch::ScoreScratch;
+   DevBuf<double> Pup, Pdn, Pm, PTup, pint_dn, ptip_dn, pint_m, ptip_m, PTm, Lp, Ap, SLp, SAp;
    DevBuf<int> plan;
 };
 
@@ -125,10 +123,9 @@ extern "C" int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, con
    if (!e || !branch || !moves || !lnL0 || !lnL) return fail(e, PAML_AMD_EINVAL, "spr_scores: null argument");
    if (n_moves < 1) return fail(e, PAML_AMD_EINVAL, "spr_scores: n_moves < 1");
    if (!(phi >= 0 && phi <= 1)) return fail(e, PAML_AMD_EINVAL, "spr_scores: phi = " + std::to_string(phi) + " is outside [0, 1]");
-   if (int rc = anc_common_checks(e, who)) return rc;
-   if (e->world > 1) return fail(e, PAML_AMD_EUNSUPPORTED, "spr_scores: one rank only (this engine's communicator has " + std::to_string(e->world) + ")");
+   if (int rc = score_begin(e, who, nullptr)) return rc;
    const TreeDesc &T = e->tree;
-   const int nn = T.n_nodes, n = e->n, K = e->K, G = e->n_genes, n_tips = e->n_tips, n_int = nn - n_tips;
+   const int nn = T.n_nodes, K = e->K, n_tips = e->n_tips;
    const long n_patt = e->n_patt;
    const SprTreeView view{n_tips, nn, T.root, T.sons_ptr.data(), T.sons.data()};
    std::vector<int> father;
@@ -162,12 +159,7 @@ extern "C" int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, con
       if (int rc = anc_keep_pmat(e, &w.pint_m, &w.ptip_m, &w.PTm, w.Pm)) return rc;
    }
    // the tree's own lengths last: what the passes read, and what the engine keeps
-   if (int rc = anc_pmat(e, who, branch, gene_rate, w)) return rc;
-   if (mfma) {
-      HIPCHK(w.PT.ensure((size_t)G * K * nn * 4096));
-      hipLaunchKernelGGL(nni_pt_all_kernel, dim3(nn, (unsigned)(G * K)), dim3(256), 0, st, (const double *)e->d_rowmajor.p, w.PT.p, n, nn, T.root);
-      HIPCHK(hipGetLastError());
-   }
+   if (int rc = score_present_pmat(e, who, branch, gene_rate, w, nullptr, true)) return rc;
    const size_t o_steps = plan.prunes.size(), o_factors = o_steps + plan.steps.size();
    {
       std::vector<int> pack(plan.prunes);
@@ -179,15 +171,9 @@ extern "C" int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, con
    }
    e->pmat_valid = true;      // (d_rowmajor holds every branch's P(t) in the tree's own orientation, as after the gradient)
 
-   const std::vector<long> chunk_base = anc_chunk_base(e);
-   const long n_chunks = chunk_base[G];
-   HIPCHK(w.partial.ensure((size_t)(n_moves + 1) * std::max<long>(n_chunks, 1)));
-   HIPCHK(w.out.ensure((size_t)n_moves + 1));
-
    // the workspace per pattern: the partials and the messages of the tree and of one prune, then (2 K + 1) doubles per row (the moves of a
-   // group and the present tree)
-   const int ns = mfma ? 64 : n;      // doubles a partial takes per pattern
-   const double fixed = 4.0 * K * n_int * (ns + 1) * 8, per_row = (2.0 * K + 1) * 8;
+   // group and the present tree).  The rows of a group by a rule of this call's own:
+   const double fixed = 2 * score_fixed(e), per_row = (2.0 * K + 1) * 8;
    const double arena_mb = anc_arena_mb("PAML_AMD_SPR_ARENA_MB");
    int cap = n_moves;
    const double all_patt = (double)((n_patt + ANC_TILE - 1) / ANC_TILE * ANC_TILE);
@@ -196,6 +182,8 @@ extern "C" int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, con
    if ((fixed + per_row * (cap + 1)) * ANC_TILE > arena_mb * 1048576.0)      // one tile with these rows does not fit: fewer
       cap = (int)std::min<double>(n_moves, std::max(1.0, floor((arena_mb * 1048576.0 / ANC_TILE - fixed) / per_row) - 1));
    cap = std::min(std::max(cap, plan.max_rows), 65534);      // (a prune is not split; the combining kernel has a grid row per row and one for the present tree)
+   ScorePlan sp;
+   if (int rc = score_plan(e, w, &sp, "PAML_AMD_SPR_ARENA_MB", per_row, n_moves, n_moves, 1, fixed, cap)) return rc;
    // the groups: as many whole prunes as the rows hold
    std::vector<int> group_first(1, 0);
    {
@@ -207,17 +195,11 @@ extern "C" int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, con
       }
       group_first.push_back(plan.n_prunes());
    }
-   long batch = anc_batch(fixed + per_row * (cap + 1), n_patt, "PAML_AMD_SPR_ARENA_MB");
    {
-      const size_t part = (size_t)K * n_int * ns, sc = (size_t)K * n_int, rows = (size_t)K * (cap + 1);
-      if (int rc = anc_alloc(e, who, {{&w.L, part}, {&w.G, part}, {&w.SL, sc}, {&w.SG, sc}, {&w.Lp, part}, {&w.Ap, part}, {&w.SLp, sc}, {&w.SAp, sc},
-                                      {&w.f, rows}, {&w.sig, rows}, {&w.lnf, (size_t)cap + 1}}, &batch))
-         return rc;
+      const size_t rows = (size_t)K * (cap + 1);
+      if (int rc = score_alloc(e, who, w, sp, {{&w.Lp, sp.part}, {&w.Ap, sp.part}, {&w.SLp, sp.sc}, {&w.SAp, sp.sc}, {&w.f, rows}, {&w.sig, rows}, {&w.lnf, (size_t)cap + 1}})) return rc;
    }
-   anc_fill(e, w, batch, m);
-   o.PT = w.PT.p; o.cap = cap; o.n_swaps = n_moves; o.f = w.f.p; o.sig = w.sig.p; o.weights = e->d_weights.p;
-   o.lnf = w.lnf.p; o.partial = w.partial.p; o.n_chunks = n_chunks;
-   o.ref_node = T.sons[T.sons_ptr[T.root]];
+   score_fill(o, w, e, sp, n_moves);
    a.Pup = w.Pup.p; a.Pdn = w.Pdn.p; a.Pm = w.Pm.p; a.PTup = w.PTup.p; a.pint_dn = w.pint_dn.p; a.ptip_dn = w.ptip_dn.p;
    a.pint_m = w.pint_m.p; a.ptip_m = w.ptip_m.p; a.PTm = w.PTm.p;
    a.prunes = w.plan.p; a.steps = w.plan.p + o_steps; a.factors = w.plan.p + o_factors;
@@ -230,24 +212,17 @@ extern "C" int paml_amd_spr_scores(paml_amd_engine *e, const double *branch, con
       o.n_group = (ip1 < plan.n_prunes() ? plan.prunes[SPR_PRUNE_INTS * ip1 + 3] : n_moves) - o.swap0;
    };
    if (int rc = anc_score_batches(
-          e, w, o, batch, (int)group_first.size() - 1, lane_pass,
-          [](dim3) {},      // (the present tree's row is combined with the batch's first group)
+          e, w, o, sp.batch, (int)group_first.size() - 1,
           [&](int gi, dim3 tiles, dim3 lanes) {
              group(gi);
              if (mfma) hipLaunchKernelGGL(spr_mfma_kernel, tiles, dim3(256), 0, st, a);
              else lane_pass(lanes, 2);
           },
           [&](int gi, dim3 lanes) { hipLaunchKernelGGL(nni_combine_kernel, dim3(lanes.x, o.n_group + (gi == 0 ? 1 : 0)), dim3(256), 0, st, o); },
-          [&](int, long h0, long nb) {      // the group's rows to the caller's [n_moves][n_patt]: one plain copy per move
-             if (lnf)
-                for (int i = 0; i < o.n_group; i++)
-                   HIPCHK(hipMemcpyAsync(lnf + (size_t)plan.order[o.swap0 + i] * n_patt + h0, w.lnf.p + (size_t)i * batch, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-             return 0;
-          }))
+          [&](int, long h0, long nb) {      // the group's rows to the caller's [n_moves][n_patt], at the move's place in the caller's list
+             return score_copy_rows(e, w.lnf.p, sp.batch, o.swap0, o.n_group, lnf, h0, nb, [&](long i) { return plan.order[i]; });
+          },
+          nullptr, lane_pass))
       return rc;
-   std::vector<double> out((size_t)n_moves + 1);
-   if (int rc = anc_totals(e, w, w.partial.p, n_chunks, w.out.p, out)) return rc;
-   for (int i = 0; i < n_moves; i++) lnL[plan.order[i]] = out[i];
-   *lnL0 = out[n_moves];
-   return 0;
+   return score_totals(e, w, sp, n_moves, plan.order.data(), lnL0, {lnL});
 }

@@ -17,16 +17,18 @@
 //                       engine_ancestral.hip, whose host helpers it shares through ancestral_host.h; then its own kernels)
 //   engine_modelgrad.hip the derivative of lnL with respect to every input of the engine (rate matrices, effective lengths, freqK, root
 //                       frequencies) in one call: the outer pass that stores H_v, the weighted outer products, the pull-back
-//   engine_place.hip    the lnL of the tree with a query tip hung on every branch (the same shared host helpers as engine_nni.hip)
+//   engine_place.hip    the lnL of the tree with a query tip hung on every branch (the score calls' host side, score_host.h, as engine_nni.hip)
 //   engine_attach.hip   the lnL of the tree with a query tip hung on a branch at the row's own three lengths, with two derivatives (the
 //                       same shared host helpers; the rows' matrices by edge_pmat_fill, the classes by edge_combine)
-//   engine_nni.hip      the lnL of every nearest-neighbour-interchange neighbour of the tree (P(t), the down pass and the host helpers as
-//                       engine_gradient.hip; the outer pass without the derivative and the swap pass are its own kernels)
+//   engine_nni.hip      the lnL of every nearest-neighbour-interchange neighbour of the tree (P(t) and the down pass as engine_gradient.hip;
+//                       the host side is the score calls', score_host.h; the outer pass without the derivative and the swap pass are its own kernels)
 // Ownership: every device buffer is a DevBuf and every event a DevEvent (dev_buf.h), freed by its destructor — the engine's as members
 // of paml_amd_engine, a call's own as members of its scratch struct (AncScratch and its kin) — so nothing here lists buffers to free.
 // Teardown is ~paml_amd_engine alone: streams, communicator, pinned blocks, the profiling dump, modules; the members go after its body.
 // The host side the whole-tree calls share (refusals, P(t) and its derivatives, the batch workspace, the one batch loop anc_batches) is
-// ancestral_host.h, defined in engine_ancestral.hip.
+// ancestral_host.h, defined in engine_ancestral.hip.  What the six score calls (engine_{nni,edge,place,spr,relabel,attach}.hip) share on
+// top of it — score_begin, the rows' node and query checks, grad_pmat_args, score_present_pmat, the workspace plan (ScorePlan), score_fill,
+// anc_score_batches, score_totals — is score_host.h, defined there too; their kernels' shared prelude and epilogue are in kernels_nni.h.
 // Built for gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -127,7 +127,7 @@ template <int N> NNI_HD void attach_lane_node(const AttachArgs &a, int k, long p
 // ---- kernels: defined in engine_attach.hip ----------------------------------------------------------------------------------------
 
 struct AttachPmatArgs {
-   GradPmatArgs g;                        // the model (P, dP, PT unused); branch unused: the lengths are the rows'
+   GradPmatArgs g;                        // the model (grad_pmat_args; branch and P unread: the lengths are the rows')
    const int *rows;                       // AttachArgs::rows
    const double *t3;                      // [n_rows][3] = t_up, t_dn, t_pend, in the sorted order
    const unsigned long long *code_mask;   // [n_codes]

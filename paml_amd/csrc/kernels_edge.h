@@ -195,7 +195,7 @@ NNI_HD void edge_combine(const EdgeArgs &a, int row, long p, double (&out)[3])
 // ---- kernels: defined in engine_edge.hip ------------------------------------------------------------------------------------------
 
 struct EdgePmatArgs {
-   GradPmatArgs g;            // the model (P, dP, PT unused); branch unused: the lengths are the rows'
+   GradPmatArgs g;            // the model (grad_pmat_args; branch and P unread: the lengths are the rows')
    const int *father;         // [n_nodes]
    const int *rows, *ovr_node;
    const double *ovr_t;       // [n_rows][5]
@@ -279,6 +279,28 @@ __device__ __forceinline__ void edge_pmat_fill(const GradPmatArgs &g, int pset, 
 __global__ void edge_pmat_kernel(EdgePmatArgs a);
 __global__ void edge_mfma_kernel(EdgeArgs a);
 __global__ void edge_combine_kernel(EdgeArgs a);
+
+// The body of a combining kernel over rows of three values (edge_combine_kernel, attach_combine_kernel): the classes of every (row,
+// pattern) and the chunks' sums of w lnf, w g1, w g2: grid (stride / 256, rows); a wave = one chunk of GRAD_CHUNK patterns.  partial:
+// [3 n_rows + 1][n_chunks] = lnL, d1, d2 of the rows, row `row` of the group at out_row(row), then the present tree.
+template <class OutRow> __device__ __forceinline__ void edge_combine_rows(const EdgeArgs &a, OutRow out_row)
+{
+   const NniArgs &o = a.o;
+   const long p = (long)blockIdx.x * 256 + threadIdx.x;
+   const bool present = (int)blockIdx.y == o.n_group;      // (a batch's first group is launched with a row more: the present tree)
+   double acc[3] = {0, 0, 0};
+   if (p < o.m.nb) {
+      if (present) acc[0] = nni_combine(o, o.cap, p);
+      else edge_combine(a, (int)blockIdx.y, p, acc);
+   }
+   for (int d = 0; d < 3; d++) acc[d] = score_wave_sum(acc[d]);
+   long chunk;
+   if (!score_chunk_lane(o, p, &chunk)) return;
+   const long nr = o.n_swaps;
+   if (present) { o.partial[3 * nr * o.n_chunks + chunk] = acc[0]; return; }
+   const long row = out_row((int)blockIdx.y);
+   for (int d = 0; d < 3; d++) o.partial[(d * nr + row) * o.n_chunks + chunk] = acc[d];
+}
 
 #endif
 

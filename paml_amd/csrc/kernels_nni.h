@@ -212,6 +212,59 @@ __device__ __forceinline__ void nni_mfma_father(const AncMargArgs &m, int k, lon
    *ls = 0;
 }
 
+// where a lane of the matrix-core row kernels stands (grid (stride / ANC_TILE, K), four waves): lane = q * 16 + pattern; k: the class;
+// g16: the wave's group of sixteen patterns; p: the pattern in the batch; pc: the pattern read (lanes past the batch's end read the last
+// pattern and write into the padding: p < stride); pset: the class's parameter set
+struct ScoreTile {
+   int lane, wave, q, k;
+   long g16, p, pc, pset;
+};
+__device__ __forceinline__ ScoreTile score_tile(const AncMargArgs &m)
+{
+   ScoreTile c;
+   c.lane = threadIdx.x & 63;
+   c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+   c.q = c.lane >> 4;
+   c.k = blockIdx.y;
+   c.g16 = (long)blockIdx.x * 4 + c.wave;
+   c.p = c.g16 * 16 + (c.lane & 15);
+   c.pc = c.p < m.nb ? c.p : m.nb - 1;
+   c.pset = (long)m.gene * m.K + c.k;
+   return c;
+}
+
+// H_v = A_f prod_{sons of f other than v} M, f the father of v, and its log factor
+__device__ __forceinline__ void score_mfma_hv(const AncMargArgs &m, const AncMfma &w, const ScoreTile &c, int v, double (&h)[16], double *ls)
+{
+   const AncTree &t = m.t;
+   const int f = t.father[v];
+   nni_mfma_father(m, c.k, c.g16, c.pc, c.lane, c.q, f, h, ls);
+   for (int j = t.sons_ptr[f]; j < t.sons_ptr[f + 1]; j++)
+      if (t.sons[j] != v) anc_mfma_mul_son(m, w, c.k, c.g16, c.pc, t.sons[j], h, ls);
+}
+
+// L_v of an internal node v, its log factor added to *ls
+__device__ __forceinline__ void score_mfma_lv(const AncMargArgs &m, const ScoreTile &c, int v, double (&l)[16], double *ls)
+{
+   const long vi = (long)c.k * m.t.n_int + v - m.t.n_tips;
+   part_load(m.L + (vi * (m.stride >> 4) + c.g16) * 1024, c.lane, l);
+   *ls += m.SL[vi * m.stride + c.pc];
+}
+
+// The end of a combining kernel (grid (stride / 256, rows); a wave = one chunk of GRAD_CHUNK patterns): the wave's 64 terms added in a
+// fixed butterfly, and whether this lane stores the sum (lane 0 of a wave that starts inside the batch) with the chunk's index
+__device__ __forceinline__ double score_wave_sum(double acc)
+{
+#pragma unroll
+   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+   return acc;
+}
+__device__ __forceinline__ bool score_chunk_lane(const NniArgs &o, long p, long *chunk)
+{
+   *chunk = o.chunk0 + (p >> 6);
+   return (threadIdx.x & 63) == 0 && (p & ~63L) < o.m.nb;
+}
+
 #endif
 
 }  // namespace paml_amd

@@ -103,7 +103,7 @@ NNI_HD double relabel_combine(const RelabelArgs &a, int row, long p)
 // ---- kernels: defined in engine_relabel.hip ---------------------------------------------------------------------------------------
 
 struct RelabelPmatArgs {
-   GradPmatArgs g;            // the model (label, P, dP, PT unused); branch: the tree's lengths
+   GradPmatArgs g;            // the model (grad_pmat_args with no label: a slot names its own; P unread); branch: the tree's lengths
    const int *slots;          // [n_slots][2] = v, label
    const unsigned char *changed;
    double *OM;                // RelabelArgs::OM

@@ -3,12 +3,16 @@ compute the same bytes exactly when their outputs are the same file:
     python tools/whole_tree_bytes.py > profiles/whole_tree_bytes.txt
     PAML_AMD_LIB=<dir>/libpaml_amd.so python tools/whole_tree_bytes.py > profiles/whole_tree_bytes_parent.txt      (a library built from
                                                                            another commit's sources, as engine.build() documents)
-Calls: gradient (grad, lnf, scores), nni_scores / placement_scores / spr_scores (lnL0, lnL, lnf), ancestral_marginal (best, prob, post),
-ancestral_joint on the problems of one class (states, ln_best).  The three score calls run twice: with the default workspace, and with
-PAML_AMD_{NNI,PLACE,SPR}_ARENA_MB so small that the patterns are walked in several batches and the rows in several groups (the values of
-tests/test_{nni,placement,spr}_gpu.py: test_groups_of_*).  The problems are tests/helpers.random_problem's, 150 patterns or fewer:
-4 / 5 / 20 / 21 / 61 / 64 states, one and three classes, two genes, scaling every 3 nodes, a tree rooted at a tip, the 14-tip polytomy.
-Reads nothing outside the repository."""
+Calls: gradient (grad, lnf, scores), nni_scores / placement_scores / spr_scores (lnL0, lnL, lnf), edge_scores / attach_scores (lnL0, lnL,
+d1, d2, lnf) on the rows of tests/{edge,attach}_ref.all_rows, relabel_scores (lnL0, lnL, lnf, lnfk0, lnfk) on every (node, label) of the
+problem with three labels added (tests/relabel_ref.add_labels; an engine of its own), ancestral_marginal (best, prob, post),
+ancestral_joint on the problems of one class (states, ln_best).  The six score calls run twice: with the default workspace, and with
+PAML_AMD_{NNI,PLACE,SPR,EDGE,ATTACH,RELABEL}_ARENA_MB so small that the patterns are walked in several batches and the rows in several
+groups (the values of tests/test_{nni,placement,spr,edge,attach}_gpu.py: test_groups_of_*; relabel: the value of
+test_groups_of_rows_on_the_lane_kernels_have_the_same_bytes, since the 1 MiB of test_batches_groups_orders_and_calls_have_the_same_bytes
+holds all of a 150-pattern problem of few states); a "small" line is refused if the call was not split.  The problems are
+tests/helpers.random_problem's, 150 patterns or fewer: 4 / 5 / 20 / 21 / 61 / 64 states, one and three classes, two genes, scaling every
+3 nodes, a tree rooted at a tip, the 14-tip polytomy.  Reads nothing outside the repository."""
 import copy
 import hashlib
 import os
@@ -19,8 +23,11 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import attach_ref      # noqa: E402
+import edge_ref      # noqa: E402
 import helpers      # noqa: E402
 import placement_ref      # noqa: E402
+import relabel_ref      # noqa: E402
 from paml_amd import engine      # noqa: E402
 from paml_amd.problem import Tree      # noqa: E402
 
@@ -75,18 +82,21 @@ def report(name, call, sha, note=""):
     print("%-26s %-22s %s%s" % (name, call, sha, note), flush=True)
 
 
-def scores(name, call, env, small_mb, rows, rows_per_group, info, run):
-    """The call with the default workspace, then with `small_mb` MiB: several batches, and `rows` in groups of `rows_per_group` or fewer."""
+def scores(name, call, env, small_mb, rows, rows_per_group, info, run, keys=("lnL", "lnf")):
+    """The call with the default workspace, then with `small_mb` MiB: several batches, and `rows` in groups of `rows_per_group` or fewer.
+    Hashed: lnL0, then the arrays `keys`."""
+    def sha(got):
+        return digest(np.float64(got["lnL0"]), *[got[k] for k in keys])
     os.environ.pop(env, None)
     got = run()
-    report(name, call, digest(np.float64(got["lnL0"]), got["lnL"], got["lnf"]), "  batches %d" % info()["last_batches"])
+    report(name, call, sha(got), "  batches %d" % info()["last_batches"])
     os.environ[env] = "%.9f" % small_mb
     got = run()
     os.environ.pop(env)
     batches = info()["last_batches"]
     if batches < 2 or rows <= rows_per_group:
         raise SystemExit("%s %s: %d batches, %d rows in groups of %d: the small workspace does not split the call" % (name, call, batches, rows, rows_per_group))
-    report(name, call + "/small", digest(np.float64(got["lnL0"]), got["lnL"], got["lnf"]), "  batches %d" % batches)
+    report(name, call + "/small", sha(got), "  batches %d" % batches)
 
 
 def main():
@@ -112,11 +122,24 @@ def main():
         most = int(np.bincount(moves[:, 0]).max())
         scores(name, "spr_scores", "PAML_AMD_SPR_ARENA_MB", (2 * fixed + (2 * most + 1.5) * per_row) * 64 / 1048576.0, len(moves), 2 * most,
                engine.spr_info, lambda: eng.spr_scores(b, gr, phi=PHI, want_lnf=True))
+        per_row3 = (4 * K + 3) * 8      # (lnL, d1 and d2 of a row)
+        rows, on, ot = edge_ref.all_rows(t, seed=5)
+        scores(name, "edge_scores", "PAML_AMD_EDGE_ARENA_MB", (fixed + 5.5 * per_row3) * 64 / 1048576.0, len(rows), 4, engine.edge_info,
+               lambda: eng.edge_scores(b, gr, rows, on, ot, want_lnf=True), keys=("lnL", "d1", "d2", "lnf"))
+        arows, t3 = attach_ref.all_rows(pb, len(queries), seed=5)
+        scores(name, "attach_scores", "PAML_AMD_ATTACH_ARENA_MB", (fixed + 4.5 * per_row3) * 64 / 1048576.0, len(arows), 3, engine.attach_info,
+               lambda: eng.attach_scores(b, gr, queries, arows, t3, want_lnf=True), keys=("lnL", "d1", "d2", "lnf"))
         m = eng.ancestral_marginal(b, gr)
         report(name, "ancestral_marginal", digest(m["best"], m["prob"], m["post"]))
         if K == 1:
             j = eng.ancestral_joint(b, gr)
             report(name, "ancestral_joint", digest(j["states"], j["ln_best"]))
+        eng.close()
+        lpb = relabel_ref.add_labels(copy.deepcopy(pb), seed=7)      # relabel_scores wants labels that select something
+        eng = engine.engine_for(lpb, flags=flags)
+        scores(name, "relabel_scores", "PAML_AMD_RELABEL_ARENA_MB", (fixed + 6.5 * (3 * K + 1) * 8) * 64 / 1048576.0, 3 * (t.n_nodes - 1), 5,
+               engine.relabel_info, lambda: eng.relabel_scores(lpb.tree.branch, lpb.gene_rate, want_lnf=True, want_classes=True),
+               keys=("lnL", "lnf", "lnfk0", "lnfk"))
         eng.close()
 
 
